@@ -1,8 +1,9 @@
 """Headline benchmark: forward tokens/s of Backpack-Small (d=768, 12 heads, 12 layers, k=16 senses)
-at seq 1024, bf16, on N MI355X (BASELINE.json `metric`), plus the roofline fraction of the
-dominant HIP kernel and the CPU-eager baseline timed in the same run.
+at seq 1024, bf16, on N MI355X (BASELINE.json `metric`).  With --full, also the roofline fraction of
+the dominant HIP kernel and the CPU-eager baseline timed in the same run.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B|auto] [--workload NAME]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -11,8 +12,12 @@ in HBM; weights are random with the reference's init scheme (no network for chec
 The forward shards by batch with no data-path collective: N ranks = N independent replicas
 (weak scaling), value = all ranks' tokens / max-over-ranks time.
 
-Per-kernel durations are measured live with HIP events (torch.cuda.Event on the stream the kernels
-are launched on = torch's current stream) around every launch inside the timed region.
+A plain run sets up, warms up, times the K steps at the workload's largest --batch auto candidate (the batch the
+sweep picks on an MI355X for every workload), writes the last step's logits if --dump-outputs is given and prints
+the result line.  --full adds what takes runs of its own: the batch sweep (--batch auto is its default there), the
+other content orders, per-kernel HIP-event durations (torch.cuda.Event on the stream the kernels are launched on =
+torch's current stream, around every launch inside the timed region), clock / power sampling, the roofline and the
+CPU-eager baseline.
 """
 import argparse
 import json
@@ -55,6 +60,27 @@ MODELS = {
     'mini-k1': dict(n_embd=640, n_head=8, n_layer=8, num_content_vectors=1, shrink_final_inner=True),
     'small': dict(n_embd=768, n_head=12, n_layer=12, num_content_vectors=16),
 }
+DUMP_BYTES = 60_000_000     # --dump-outputs: what the written arrays may hold in all (a seeded row sample beyond it)
+
+
+def batch_candidates(default_batch):
+    """--batch auto's sweep; its largest entry is the plain run's batch (every recorded MI355X sweep picked it: the rate
+    is flat across the top of the sweep and the pick is the largest batch within 1 % of the best)."""
+    return [default_batch * m for m in (1, 2, 4, 8, 16, 24, 26, 28, 30, 32)]
+
+
+def dump_outputs(directory, logits):
+    """--dump-outputs: the logits of the last timed step as float32 rows of the (batch * seq, vocab) matrix in
+    DIR/logits.npy -- all rows when they fit in DUMP_BYTES, else a fixed seeded sample of rows in ascending order, so
+    two builds run with the same arguments compare output for output."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    rows = logits.reshape(-1, logits.shape[-1])
+    keep = max(1, DUMP_BYTES // (rows.shape[1] * 4))
+    if rows.shape[0] > keep:
+        pick = np.sort(np.random.default_rng(0).choice(rows.shape[0], keep, replace=False))
+        rows = rows[torch.from_numpy(pick).to(rows.device)]
+    np.save(os.path.join(directory, 'logits.npy'), rows.float().cpu().numpy())
 
 
 class KernelClock:
@@ -425,9 +451,10 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
-    ap.add_argument('--batch', default='auto',
-                    help="samples per GPU per step, or 'auto' (default): time a few steps at each of "
-                         "--batch-candidates and keep the fastest (north_star: batch sized for 288 GB of HBM)")
+    ap.add_argument('--batch', default=None,
+                    help="samples per GPU per step, or 'auto' (the default with --full): time a few steps at each of "
+                         "--batch-candidates and keep the fastest (north_star: batch sized for 288 GB of HBM); "
+                         "default without --full: the largest candidate, what the sweep picks on an MI355X")
     ap.add_argument('--batch-candidates', default=None,
                     help='comma-separated batch sizes tried by --batch auto (default: per workload)')
     ap.add_argument('--workload', default='small-1024', choices=sorted(WORKLOADS))
@@ -444,8 +471,8 @@ def main():
                          "'batch' (default for eager launches) = content network once per distinct token id of the batch, the "
                          "table rebuilt EVERY step; 'cached' (default with --graph: the only per-token form a graph can hold) = "
                          "the whole-vocabulary table built once per weight version, outside the timed region; 'position' = "
-                         "the reference's order, every position through the content network.  The other two orders are timed "
-                         "for a few steps in the same process and reported next to `value`.")
+                         "the reference's order, every position through the content network.  With --full the other two "
+                         "orders are timed for a few steps in the same process and reported next to `value`.")
     ap.add_argument('--no-content-dedup', action='store_true', help="same as --content position")
     ap.add_argument('--dist-backend', default='nccl', choices=['nccl', 'gloo'],
                     help="'nccl' (= RCCL, one rank per GPU) for every real run; 'gloo' moves the same collectives "
@@ -454,7 +481,15 @@ def main():
     ap.add_argument('--graph', action='store_true',
                     help='capture one forward in a HIP graph and replay it per step (launch-bound small '
                          'configs; per-kernel events are not taken in this mode)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the logits of the last one to DIR/logits.npy (float32 rows of '
+                         'the (batch * seq, vocab) matrix; a fixed seeded sample of rows beyond 60 MB)')
+    ap.add_argument('--full', action='store_true',
+                    help='also the batch sweep (--batch auto by default), the other content orders, per-kernel events, '
+                         'roofline, clock / power and the CPU baseline; without it only the headline steps run')
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit('--steps must be at least 1')
 
     rank = int(os.environ.get('RANK', '0'))
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -496,9 +531,13 @@ def main():
     sweep = None
     logits = LogitsBuffer(cfg.vocab_size, seq, dtype, device)
     cands = []
-    if args.batch == 'auto':
+    batch_arg = args.batch or ('auto' if args.full else None)
+    if batch_arg in ('auto', None):
         cands = ([int(c) for c in args.batch_candidates.split(',')] if args.batch_candidates
-                 else [default_batch * m for m in (1, 2, 4, 8, 16, 24, 26, 28, 30, 32)])
+                 else batch_candidates(default_batch))
+    if batch_arg is None:
+        batch = max(cands)      # (the candidates stay the fall-back below should this batch not fit)
+    elif batch_arg == 'auto':
         batch, sweep = pick_batch(model, make_ids, cands, seq, device, logits)
         torch.cuda.synchronize()
         if dist is not None:    # every rank runs the SMALLEST batch any rank picked (identical GPUs pick alike)
@@ -506,12 +545,12 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MIN)
             batch = int(t.item())
     else:
-        batch = int(args.batch)
+        batch = int(batch_arg)
     ids = make_ids(batch)
     logits_out = logits.get(batch)[:batch]
 
     clock = KernelClock()
-    if not args.no_kernel_events and not args.graph:
+    if args.full and not args.no_kernel_events and not args.graph:
         instrument(clock)
 
     def eager_step():
@@ -570,7 +609,7 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     clock.enabled = True
-    smi = ClockPowerSampler(local_rank).start() if rank == 0 else None   # side thread; reads the SMU's metrics table only
+    smi = ClockPowerSampler(local_rank).start() if rank == 0 and args.full else None   # side thread; reads the SMU's metrics table only
     t0 = time.perf_counter()
     for _ in range(args.steps):
         out = step()
@@ -582,6 +621,8 @@ def main():
     clock.enabled = False
     step_clocks = smi.stop() if smi is not None else None
     assert out.shape == (batch, seq, cfg.vocab_size) and bool(torch.isfinite(out[0, -1].float()).all())
+    if args.dump_outputs and rank == 0:     # before anything below writes the logits block again
+        dump_outputs(args.dump_outputs, out)
 
     # The same step in the OTHER content orders (the reference's per-position order among them), timed next to the headline
     # so that all numbers come from one process on one box: a few steps, same batch, same barriers.
@@ -639,7 +680,7 @@ def main():
     others = {}
     out = None
     for mode in ('position', 'cached', 'batch'):
-        if mode != content and not args.graph:   # (a replayed graph against eager launches would compare launch overheads)
+        if args.full and mode != content and not args.graph:   # (a replayed graph against eager launches would compare launch overheads)
             others[mode] = time_other(mode)
     model.transformer.sense_table_mode = MODES[content]
 
@@ -685,7 +726,9 @@ def main():
                                    f'{cfg.n_head} heads, {cfg.n_layer} layers, k={cfg.num_content_vectors} '
                                    f'senses, vocab {cfg.vocab_size}, seq {seq}',
                        'batch_per_gpu': batch, 'global_batch': batch * world, 'seq_len': seq,
-                       'batch_choice': 'auto: largest batch within 1 % of the best rate in batch_sweep (candidates up to 90 % of HBM; logits in one persistent block)' if sweep else 'given',
+                       'batch_choice': 'auto: largest batch within 1 % of the best rate in batch_sweep (candidates up to 90 % of HBM; logits in one persistent block)' if sweep
+                                       else 'given' if batch_arg is not None
+                                       else 'default: the largest --batch auto candidate (the sweep\'s pick on an MI355X; logits in one persistent block)',
                        'hbm_frac_peak': round(hbm_peak / torch.cuda.get_device_properties(device).total_memory, 3),
                        'content_network': {
                            'batch': 'once per distinct token id of the batch, EVERY step (torch.unique; the mix kernel gathers the '
@@ -775,7 +818,7 @@ def main():
             line['kernels'] = kernel_rows
         if sweep:
             line['batch_sweep'] = sweep
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline(model_name, seq, threads=args.cpu_threads)
         print(json.dumps(line), flush=True)
     if dist is not None:

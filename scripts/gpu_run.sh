@@ -27,6 +27,7 @@ case "$cmd" in
     timeout 600 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -n 5 ;;
   bench)
     tag=${1:-run}; shift || true
+    set -- --full "$@"    # the summary below reads the content orders and the roofline, which only --full reports
     timeout ${BP_TIMEOUT:-1200} python bench.py "$@" > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err
     echo "bench rc=$?"; tail -c 300 gpurun_out/${tag}_bench.err
     python - "$tag" <<'PY'

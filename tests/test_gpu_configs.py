@@ -547,7 +547,7 @@ def test_bench_launch_path_under_torchrun():
     """The driver's N-GPU launch line with N = 1: `python -m torch.distributed.run ... bench.py --gpus 1` goes through
     init_process_group('nccl'), the batch broadcast, the barriers and the MAX all-reduce of the elapsed time -- the code
     the 8-GPU run depends on -- and prints ONE JSON line with the contract's fields."""
-    line = _torchrun(['bench.py', '--gpus', '1', '--steps', '2', '--warmup', '1', '--batch', '8', '--no-cpu-baseline'])
+    line = _torchrun(['bench.py', '--gpus', '1', '--steps', '2', '--warmup', '1', '--batch', '8', '--no-cpu-baseline', '--full'])
     assert line['n_gpus'] == 1 and line['steps'] == 2 and line['unit'] == 'tokens/s' and line['value'] > 0
     assert line['config']['batch_per_gpu'] == 8 and line['scaling'] == 'weak' and 'roofline' in line
     line = _torchrun(['bench.py', '--gpus', '1', '--steps', '1', '--warmup', '1', '--batch', 'auto', '--batch-candidates',

@@ -303,16 +303,30 @@ def test_intervened_models_hip_vs_oracle():
         assert err <= 3 * ref + 2e-3
 
 
-def test_bench_script_contract():
-    """bench.py runs end to end (small workload) and prints ONE JSON line carrying the driver's contract keys,
-    the roofline object of the dominant attention-path kernel and per-kernel HIP-event timings."""
+def test_bench_script_contract(tmp_path):
+    """bench.py runs end to end (small workload) and prints ONE JSON line carrying the driver's contract keys; with
+    --full also the roofline object of the dominant attention-path kernel and per-kernel HIP-event timings.  A plain run
+    times the largest --batch auto candidate and, with --dump-outputs, writes the last step's logits rows."""
     import json
     import os
     import subprocess
     import sys
+    import numpy as np
     from conftest import ROOT
+    contract = ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
+                'vs_baseline', 'dtype', 'data', 'config')
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', 'micro-128', '--steps', '2',
+                          '--warmup', '1', '--dump-outputs', str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert all(key in d for key in contract) and d['steps'] == 2 and d['value'] > 0 and d['dtype'] == 'bf16'
+    assert d['config']['batch_per_gpu'] == 128 and 'batch_sweep' not in d and 'roofline' not in d
+    rows = np.load(tmp_path / 'logits.npy')
+    assert rows.dtype == np.float32 and rows.shape[1] == 50264 and rows.nbytes <= 64e6 and np.isfinite(rows).all()
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', 'micro-128', '--steps', '3',
-                          '--warmup', '1', '--no-cpu-baseline'], capture_output=True, text=True, timeout=600)
+                          '--warmup', '1', '--no-cpu-baseline', '--full'], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1
@@ -322,7 +336,7 @@ def test_bench_script_contract():
         assert key in d, key
     assert d['n_gpus'] == 1 and d['steps'] == 3 and d['value'] > 0 and d['vs_baseline'] is None
     assert set(d['roofline']) >= {'bound', 'achieved', 'peak', 'unit', 'frac', 'traffic', 'traffic_source'}
-    assert d['config']['batch_per_gpu'] in [r['batch'] for r in d['batch_sweep']]   # --batch auto is the default
+    assert d['config']['batch_per_gpu'] in [r['batch'] for r in d['batch_sweep']]   # --batch auto is the default with --full
     assert {k['kernel'] for k in d['kernels']} >= {'flash_fwd_kernel', 'sense_mix_kernel', 'add_layer_norm_kernel'}
 
 
@@ -336,7 +350,7 @@ def test_bench_reports_all_three_content_orders():
     import sys
     from conftest import ROOT
     base = [sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', 'micro-128', '--batch', '1024', '--steps', '3',
-            '--warmup', '1', '--no-cpu-baseline']
+            '--warmup', '1', '--no-cpu-baseline', '--full']
     out = subprocess.run(base, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][0])

@@ -39,7 +39,7 @@ def test_bench_two_ranks():
     """bench.py --gpus 2: weak scaling, value = the tokens of BOTH ranks over the slower rank's time, one JSON line,
     no cpu_baseline leg at N > 1; the auto batch is rank 0's pick, broadcast."""
     line = _torchrun2(['bench.py', '--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '4', '--dist-backend',
-                       'gloo'], 29542)
+                       'gloo', '--full'], 29542)
     assert line['n_gpus'] == 2 and line['scaling'] == 'weak'
     assert line['config']['batch_per_gpu'] == 4 and line['config']['global_batch'] == 8
     tokens = 2 * 4 * 1024 * 2

@@ -555,3 +555,28 @@ def test_bench_clock_power_sampler_without_a_gpu():
     assert set(out) >= {'sclk_mhz_mean', 'power_w_mean', 'power_cap_w', 'samples', 'source'}
     if out['source'] is None:
         assert out['sclk_mhz_mean'] is None and out['power_w_mean'] is None and out['samples'] == 0
+
+
+def test_bench_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """bench.py --dump-outputs: float32 rows of the (batch * seq, vocab) logits; all of them when they fit, else the same
+    seeded rows on every call, in ascending order, inside the byte budget."""
+    import importlib.util
+    import os
+    import numpy as np
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(os.path.dirname(os.path.dirname(
+        os.path.abspath(__file__))), 'bench.py'))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    small = torch.randn(2, 3, 5).bfloat16()
+    mod.dump_outputs(str(tmp_path / 'a'), small)
+    got = np.load(tmp_path / 'a' / 'logits.npy')
+    assert got.dtype == np.float32 and np.array_equal(got, small.float().reshape(6, 5).numpy())
+    vocab = 50264
+    big = torch.arange(2 * 1024, dtype=torch.float32)[:, None].expand(-1, vocab).view(2, 1024, vocab)   # row r holds r
+    for d in ('b', 'c'):
+        mod.dump_outputs(str(tmp_path / d), big)
+    b, c = np.load(tmp_path / 'b' / 'logits.npy'), np.load(tmp_path / 'c' / 'logits.npy')
+    assert np.array_equal(b, c) and b.shape == (mod.DUMP_BYTES // (vocab * 4), vocab)
+    assert os.path.getsize(tmp_path / 'b' / 'logits.npy') <= 64e6
+    rows = b[:, 0]
+    assert (np.diff(rows) > 0).all() and (b == rows[:, None]).all()
