@@ -55,9 +55,8 @@ template <class ET, bool F32> BP_DEV void store4(void *base, int64_t idx, const 
     }
 }
 
-// Streaming (non-temporal) forms for the forward's row data: every byte is touched once per launch.  BP_LN_NT selects
-// which accesses carry the hint (development A/B: 0 none, 1 stores, 2 loads and stores, 3 loads, 4 loads + residual store); the launcher picks per
-// call (see launch_flags).
+// Streaming (non-temporal) forms for the forward's row data: every byte is touched once per launch.  The launcher picks
+// which accesses carry the hint (see launch_flags).
 template <class ET, bool F32, bool NT> BP_DEV void load4s(const void *base, int64_t idx, float (&v)[4]) {
     if constexpr (!NT) {
         load4<ET, F32>(base, idx, v);
@@ -179,14 +178,10 @@ template <class ET, bool RES_F32, bool W_F32>
 static hipError_t launch_flags(const LnParams &p, hipStream_t stream) {
     const int ch = (p.cols + 255) / 256;
     dim3 g((unsigned)((p.rows + 3) / 4)), t(256);
-    // shipped: 4 -- x0 and the incoming residual are read once and never again, the outgoing residual is next read a GEMM
-    // and an attention launch later (long evicted at any batch that matters); z stays cacheable for the GEMM that follows.
-    // r04_d / r04_e on one box each: kernel alone -6.7 % (B = 64) ... -4 % (B = 1536) with nt loads, in the model
-    // 2.397 -> 2.336 ms per launch at B = 1536 (0.756 -> 0.776 of 8 TB/s), step +0.3 %
-#ifndef BP_LN_NT
-#define BP_LN_NT 4
-#endif
-    constexpr bool NTL = BP_LN_NT >= 2, NTS = BP_LN_NT == 1 || BP_LN_NT == 2 || BP_LN_NT == 4, NTZ = BP_LN_NT == 1 || BP_LN_NT == 2;
+    // non-temporal loads and residual store: x0 and the incoming residual are read once and never again, the outgoing
+    // residual is next read a GEMM and an attention launch later; z stays cacheable for the GEMM that follows
+    // (profiles/r04_d_ab_layernorm_nontemporal.jsonl)
+    constexpr bool NTL = true, NTS = true, NTZ = false;
     const bool scaled = p.rowscale != nullptr || p.colscale != nullptr;
 #define BP_LN_CASE(N) \
     if (ch <= N) { \

@@ -58,28 +58,15 @@ __device__ unsigned long long g_bwd_prof[2][8192][2][8];   // [kernel: 0 dq, 1 d
 
 namespace {
 
-// Development builds only (-DBP_BWD_WHATIF=<bits>, scripts/probes/flash_bwd_whatif): timing builds that DELETE one kind
-// of work (results are garbage on purpose).  1 no v_exp_f32, 2 no S / dP products, 4 no dV / dK / dQ products, 8 no
-// s_barrier (racy), 16 no epilogue stores, 32 no softmax VALU at all.  0 in the shipped library: every test below folds away.
-#ifndef BP_BWD_WHATIF
-#define BP_BWD_WHATIF 0
-#elif BP_BWD_WHATIF != 0
-#warning "BP_BWD_WHATIF: timing build of flash_bwd.hip -- gradients are garbage (bp_build_flags() reports it, bp_hip refuses it as the default library)"
-#endif
-constexpr int kWhatIf = BP_BWD_WHATIF;
-
-// ring depth of the streamed tiles: tile t + NSTAGE - 1 is requested at the start of step t (three slots measured
-// against two on one box, r03_j: 0.631 vs 0.616 ms at B = 64 -- the tile latency is not what the waves wait for)
-#ifndef BP_BWD_NSTAGE
-#define BP_BWD_NSTAGE 2
-#endif
+// ring depth of the streamed tiles: tile t + NSTAGE - 1 is requested at the start of step t (three slots were slower,
+// 0.631 vs 0.616 ms at B = 64, profiles/r03_j_bwd_ring3_ab.txt -- the tile latency is not what the waves wait for)
 // (the two passes of a paired causal workgroup chained into one tile stream, so that the ring never drains between
 // them: correct and 7 % slower, scripts/probes/flash_bwd_chain)
 
 template <int KD>
 struct BwdCfg {
     static constexpr int NT = 256, NWAVE = 4, BT = 64;               // BT: rows of a streamed tile
-    static constexpr int NSTAGE = KD <= 4 ? BP_BWD_NSTAGE : 2;       // (wide heads: 32 KB stages, two of them)
+    static constexpr int NSTAGE = 2;
     static constexpr int NV = (KD + 1) / 2;                          // 32-wide blocks of the head dimension
     static constexpr int ROW = KD <= 4 ? 128 : 256;                  // bytes per tile row in LDS (power of two)
     static constexpr int SLOTS = ROW / 16;
@@ -371,7 +358,6 @@ BP_DEV void flash_bwd_dkdv_tile(const FlashBwdParams p, char *smem, const uint32
         }
 #pragma unroll
         for (int s = 0; s < KD; ++s) {
-            if (kWhatIf & 2) break;
             const u32x4 a = lds_read_16B(st, G::Q_OFF + r_off[s] + qb * 32 * C::ROW);
             s_ = E::mfma(a, kf[s], s_);
             const u32x4 b = lds_read_16B(st, G::DO_OFF + r_off[s] + qb * 32 * C::ROW);
@@ -395,7 +381,7 @@ BP_DEV void flash_bwd_dkdv_tile(const FlashBwdParams p, char *smem, const uint32
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int r = 4 * g + i;
-                const float pv = (kWhatIf & 1) ? s_[r] * c2 : fast_exp2(s_[r] * c2);
+                const float pv = fast_exp2(s_[r] * c2);
                 if (DROP) {
                     const float z = ((keep >> r) & 1u) ? p.drop_scale : 0.f;
                     pe[i] = pv * z;
@@ -418,17 +404,9 @@ BP_DEV void flash_bwd_dkdv_tile(const FlashBwdParams p, char *smem, const uint32
             dsf[g >> 1][(g & 1) * 2 + 0] = E::pack2(de[0], de[1]);
             dsf[g >> 1][(g & 1) * 2 + 1] = E::pack2(de[2], de[3]);
         }
-        if (kWhatIf & 32) {   // no softmax VALU: the raw accumulator bits stand in for the packed operands
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) { pf[ks][i] = as_u32(s_[ks * 8 + i]); dsf[ks][i] = as_u32(dp[ks * 8 + i]); }
-        }
-        if (kWhatIf & 4) asm volatile("" ::"v"(pf[0]), "v"(pf[1]), "v"(dsf[0]), "v"(dsf[1]));
         // ---- dV^T += dO^T P ; dK^T += Q^T dS   (contraction over the 32 queries) -------------------
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            if (kWhatIf & 4) break;
             const int rows = (qb * 32 + ks * 16) * C::ROW;
 #pragma unroll
             for (int n = 0; n < NV; ++n) {
@@ -449,7 +427,7 @@ BP_DEV void flash_bwd_dkdv_tile(const FlashBwdParams p, char *smem, const uint32
         const int ahead = min(nqt - 1 - qt, C::NSTAGE - 2);   // tiles requested after tile qt
         if (stats_wave) ring_wait<2 * C::DMA + 1>(ahead);
         else ring_wait<2 * C::DMA>(ahead);
-        if (!(kWhatIf & 8)) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();
         if (qt + C::NSTAGE - 1 < nqt) issue(qt + C::NSTAGE - 1);
         return smem + ((qt - qt_begin) % C::NSTAGE) * G::STAGE;
     };
@@ -510,7 +488,6 @@ BP_DEV void flash_bwd_dkdv_tile(const FlashBwdParams p, char *smem, const uint32
     const int d_lim = my_key < seq_k ? p.d : 0;   // lanes past the sequence exchange, but store nothing
 #pragma unroll
     for (int n = 0; n < NV; ++n) {
-        if (kWhatIf & 16) { asm volatile("" ::"v"(dk[n]), "v"(dv[n])); continue; }
         store_block16<E, (KD <= 4)>(dkg, dk[n], p.scale, n, hh, d_lim);
         store_block16<E, (KD <= 4)>(dvg, dv[n], 1.f, n, hh, d_lim);
     }
@@ -663,7 +640,6 @@ BP_DEV void flash_bwd_dq_tile(const FlashBwdParams p, char *smem, const uint32_t
         for (int r = 0; r < 16; ++r) st_[r] = 0.f;
 #pragma unroll
         for (int s = 0; s < KD; ++s) {
-            if (kWhatIf & 2) break;
             const u32x4 a = lds_read_16B(st, K_OFF + r_off[s] + kk * 32 * C::ROW);
             st_ = E::mfma(a, qf[s], st_);
             const u32x4 b = lds_read_16B(st, V_OFF + r_off[s] + kk * 32 * C::ROW);
@@ -685,7 +661,7 @@ BP_DEV void flash_bwd_dq_tile(const FlashBwdParams p, char *smem, const uint32_t
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int r = 4 * g + i;
-                const float pv = (kWhatIf & 1) ? fmaf(st_[r], c2, lneg2) : fast_exp2(fmaf(st_[r], c2, lneg2));
+                const float pv = fast_exp2(fmaf(st_[r], c2, lneg2));
                 if (DROP) {
                     const float z = ((keep >> r) & 1u) ? p.drop_scale : 0.f;
                     de[i] = pv * fmaf(dpt[r], z, dneg);
@@ -697,17 +673,9 @@ BP_DEV void flash_bwd_dq_tile(const FlashBwdParams p, char *smem, const uint32_t
             dsf[g >> 1][(g & 1) * 2 + 0] = E::pack2(de[0], de[1]);
             dsf[g >> 1][(g & 1) * 2 + 1] = E::pack2(de[2], de[3]);
         }
-        if (kWhatIf & 32) {
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) dsf[ks][i] = as_u32(st_[ks * 8 + i]) ^ as_u32(dpt[ks * 8 + i]);
-        }
-        if (kWhatIf & 4) asm volatile("" ::"v"(dsf[0]), "v"(dsf[1]));
         // dQ^T += K^T dS^T  (contraction over the 32 keys)
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            if (kWhatIf & 4) break;
             const int rows = (kk * 32 + ks * 16) * C::ROW;
 #pragma unroll
             for (int n = 0; n < NV; ++n) {
@@ -720,7 +688,7 @@ BP_DEV void flash_bwd_dq_tile(const FlashBwdParams p, char *smem, const uint32_t
 
     auto step_begin = [&](int kb) -> const char * {
         ring_wait<2 * C::DMA>(min(nkb - 1 - kb, C::NSTAGE - 2));
-        if (!(kWhatIf & 8)) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();
         if (kb + C::NSTAGE - 1 < nkb) issue(kb + C::NSTAGE - 1);
         return smem + (kb % C::NSTAGE) * STAGE;
     };
@@ -788,10 +756,7 @@ BP_DEV void flash_bwd_dq_tile(const FlashBwdParams p, char *smem, const uint32_t
     uint16_t *dqg = reinterpret_cast<uint16_t *>(p.dq) + (si.q_row0 + q_row) * p.dq_rs + (int64_t)head * p.dq_hs;
     const int d_lim = my_q < seq_q ? p.d : 0;
 #pragma unroll
-    for (int n = 0; n < NV; ++n) {
-        if (kWhatIf & 16) { asm volatile("" ::"v"(dq[n])); continue; }
-        store_block16<E, (KD <= 4)>(dqg, dq[n], p.scale, n, hh, d_lim);
-    }
+    for (int n = 0; n < NV; ++n) store_block16<E, (KD <= 4)>(dqg, dq[n], p.scale, n, hh, d_lim);
     BWD_STAMP(0, pass, 7);
 }
 
@@ -799,12 +764,10 @@ BP_DEV void flash_bwd_dq_tile(const FlashBwdParams p, char *smem, const uint32_t
 // Kernels: a causal workgroup takes the heaviest remaining tile and the lightest of its (sample, head) -- tiles t
 // and n-1-t -- so that every workgroup carries the same work (in-order round-robin dispatch, see flash_fwd_dma.hip).
 // (the dropout variants spill 500+ registers at three waves per SIMD: they keep two)
-#ifndef BP_BWD_DKDV_MINWAVES
-#define BP_BWD_DKDV_MINWAVES(KD, DROP) ((KD) <= 4 && !(DROP) ? 3 : (KD) <= 4 ? 2 : 1)
-#endif
+constexpr int bwd_dkdv_min_waves(int kd, bool drop) { return kd <= 4 && !drop ? 3 : kd <= 4 ? 2 : 1; }
 
 template <class ET, int KD, bool FULLD, bool DROP>
-__global__ __launch_bounds__(256, BP_BWD_DKDV_MINWAVES(KD, DROP)) void flash_bwd_dkdv_kernel(const FlashBwdParams p) {
+__global__ __launch_bounds__(256, bwd_dkdv_min_waves(KD, DROP)) void flash_bwd_dkdv_kernel(const FlashBwdParams p) {
     __shared__ __attribute__((aligned(16))) char smem[DkdvCfg<KD>::SMEM];
     const uint32_t lds0 = lds_base_addr(smem);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -821,12 +784,10 @@ __global__ __launch_bounds__(256, BP_BWD_DKDV_MINWAVES(KD, DROP)) void flash_bwd
 }
 
 // waves per SIMD the register allocator must leave room for in the dQ kernel (512 VGPRs per SIMD lane)
-#ifndef BP_BWD_DQ_MINWAVES
-#define BP_BWD_DQ_MINWAVES(KD) ((KD) <= 4 ? 3 : 2)
-#endif
+constexpr int bwd_dq_min_waves(int kd) { return kd <= 4 ? 3 : 2; }
 
 template <class ET, int KD, bool FULLD, bool DROP>
-__global__ __launch_bounds__(256, BP_BWD_DQ_MINWAVES(KD)) void flash_bwd_dq_kernel(const FlashBwdParams p) {
+__global__ __launch_bounds__(256, bwd_dq_min_waves(KD)) void flash_bwd_dq_kernel(const FlashBwdParams p) {
     using C = BwdCfg<KD>;
     __shared__ __attribute__((aligned(16))) char smem[C::NSTAGE * 2 * C::TILE];
     const uint32_t lds0 = lds_base_addr(smem);

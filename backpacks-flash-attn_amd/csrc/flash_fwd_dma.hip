@@ -24,31 +24,16 @@
 //   * in-kernel dropout (training; reference fmha_fprop_kernel_1xN.h:494-506): counter-based bits per
 //     (batch*head, query, key), see bp_philox.h; dropped probabilities are zeroed AFTER the row sum, the
 //     output is scaled by 1 / (1 - p) once in the epilogue.
-// S^T of both key halves as one operand stream (mfma_stream, bp_common.h) instead of two dependent per-half chains:
-// +0.5 ... 1.7 % (r03_ao), 125 registers = still four waves per SIMD once the partial-tile DMA offsets left the
-// register file (see issue())
-#ifndef BP_FWD_STREAM
-#define BP_FWD_STREAM 1
-#endif
-// epilogue: O as 16-byte column groups (one v_permlane32_swap per dword pairs the half-waves' 8-byte pieces) instead of
-// 8-byte stores -- half the store instructions for the same bytes (the backward kernels' store_block16 has had this form
-// since round 3).  Same-box A/B, bit-identical on 137 cases (profiles/r06_c_ab_flash_wide_store.jsonl, r06_c_t21_bits.txt):
-// trunk shape B = 256 0.729 -> 0.707 ms, B = 2048 4.821 -> 4.688 ms (-2.8 %), S = 4096 +-0.5 %.  0 restores the 8-byte form.
-#ifndef BP_FWD_WIDE_STORE
-#define BP_FWD_WIDE_STORE 1
-#endif
 #include "bp_common.h"
 #include "bp_dma.h"
 #include "bp_kernels.h"
 #include "bp_philox.h"
 
+namespace bp {
+
 // waves per SIMD the register allocator must leave room for (512 VGPRs per SIMD lane): the trunk shapes
 // (head_dim <= 64; <= 96 without dropout since the odd K pitch of round 4) run at least three workgroups per CU
-#ifndef BP_FLASH_MINWAVES
-#define BP_FLASH_MINWAVES(NV, DROP) ((NV) <= 2 || ((NV) == 3 && !(DROP)) ? 3 : 1)
-#endif
-
-namespace bp {
+constexpr int flash_min_waves(int nv, bool drop) { return nv <= 2 || (nv == 3 && !drop) ? 3 : 1; }
 
 // Development builds only (-DBP_FWD_PROFILE, scripts/probes/flash_fwd_phases): every wave adds up s_memtime deltas per
 // phase of a pass; never in the shipped library.
@@ -63,26 +48,18 @@ __device__ unsigned long long g_fwd_prof[8192][4][12];
 #define FWD_ADD(k, expr) do { } while (0)
 #endif
 
-// BP_FWD_NWAVE = 8 (round-4 experiment, asked for by the round-3 review): a 512-thread workgroup covers 256 queries,
-// i.e. every K / V tile is fetched once per 256 queries instead of once per 128 (half the DMA instructions and barriers per
-// query); shapes whose tiles have fewer than eight 1-KiB pieces keep four waves.
-#ifndef BP_FWD_NWAVE
-#define BP_FWD_NWAVE 4
-#endif
+// four waves: 256-query workgroups of eight waves were 2-4 % slower at S = 1024 (profiles/r04_d_ab_flash_8wave_workgroups.jsonl)
 template <int KD, int NV, bool HAS_V>
 struct FlashDmaCfg {
-    static constexpr int NWAVE = (BP_FWD_NWAVE == 8 && KD <= 4 && KD >= 3 && (!HAS_V || NV >= 2)) ? 8 : 4;
+    static constexpr int NWAVE = 4;
     static constexpr int BM = 32 * NWAVE, BN = 64, NT = 64 * NWAVE, NSTAGE = 2;
     // K row pitch in LDS.  Head dims 64 and 128 fill a power-of-two pitch (128 / 256 bytes) and XOR-swizzle the
     // 16-byte slots (k_swz); every other width (d_h = 80: Mini; the senses' d_k = 48 / 24 / 16) takes an ODD number of slots,
     // 2 KD + 1 (a narrow K tile is also fewer DMA pieces: d_k = 16 moves 3 KB per tile instead of 8): the
     // quad-bank of (row, slot) is (row * KSLOTS + slot) mod 16, distinct for the 16 rows of every ds_read_b128 lane group
     // without any swizzle, and the tile shrinks from 16 KB to 11 / 13 / 15 KB -- at d_h = 80 that is 47 KB per workgroup
-    // instead of 57 KB, i.e. three workgroups per CU instead of two (round 4, BP_FWD_ODD_PITCH).
-#ifndef BP_FWD_ODD_PITCH
-#define BP_FWD_ODD_PITCH 1
-#endif
-    static constexpr bool ODD = BP_FWD_ODD_PITCH && KD != 4 && KD != 8;
+    // instead of 57 KB, i.e. three workgroups per CU instead of two (profiles/r04_j_ab_flash_odd_k_pitch_d80_d96_d112.jsonl).
+    static constexpr bool ODD = KD != 4 && KD != 8;
     static constexpr int KSLOTS = ODD ? 2 * KD + 1 : KD <= 4 ? 8 : 16;
     static constexpr int KROW = KSLOTS * 16;
     static constexpr int VROW = NV * 64;
@@ -270,18 +247,6 @@ BP_DEV void flash_fwd_tile(const FlashParams p, char *smem, const uint32_t lds0,
         for (int n = 0; n < NV; ++n) v_read_off[n] = v_lds_off<NV>(v_row_lane, n * 4 + v_ch_lane) + (lane & 1) * 8;
     }
 
-    // S^T of one 32-key half of the tile
-    auto scores = [&](const char *kbuf, int kk) {
-        f32x16 s_;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s_[r] = 0.f;
-#pragma unroll
-        for (int s = 0; s < KD; ++s) {
-            const u32x4 a = lds_read_16B(kbuf, k_read_off[s] + kk * 32 * C::KROW);
-            s_ = E::mfma(a, qf[s], s_);
-        }
-        return s_;
-    };
     // p (in place) = exp2(s*c2 - mc), returns my share of the row sum
     auto exponentiate = [&](f32x16 (&st)[2]) {
         float rs0 = 0.f, rs1 = 0.f;
@@ -430,8 +395,8 @@ BP_DEV void flash_fwd_tile(const FlashParams p, char *smem, const uint32_t lds0,
         unsigned long long t_s = t0, t_e = t0;
 #endif
         for (;;) {
-#if BP_FWD_STREAM
-            {   // both halves as one operand stream, alternating accumulators; operand i + 2 requested before MFMA i
+            {   // S^T of both 32-key halves as one operand stream, alternating accumulators; operand i + 2 requested
+                // before MFMA i (profiles/r03_ao_flash_fwd_diet_stream_ab.jsonl)
                 f32x16 zero;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) zero[r] = 0.f;
@@ -439,10 +404,6 @@ BP_DEV void flash_fwd_tile(const FlashParams p, char *smem, const uint32_t lds0,
                     [&](int i) { return lds_read_16B(kbuf, k_read_off[i >> 1] + (i & 1) * 32 * C::KROW); },
                     [&](int i, const u32x4 &a) { st[i & 1] = E::mfma(a, qf[i >> 1], i < 2 ? zero : st[i & 1]); });
             }
-#else
-            st[0] = scores(kbuf, 0);
-            st[1] = scores(kbuf, 1);
-#endif
 #ifdef BP_FWD_PROFILE
             asm volatile("" : "+v"(st[0]), "+v"(st[1]));
             t_s = __builtin_readcyclecounter();
@@ -525,11 +486,11 @@ BP_DEV void flash_fwd_tile(const FlashParams p, char *smem, const uint32_t lds0,
         }
         if (HAS_V) {
             uint16_t *og = reinterpret_cast<uint16_t *>(p.o) + o_off + (int64_t)my_q * p.o_rs + (int64_t)head * p.o_hs;
-#if BP_FWD_WIDE_STORE
             // 16-byte column groups: a lane holds columns 8g + 4hh .. +3 of its row for every g; one v_permlane32_swap per
             // dword pairs groups (g, g + 1) across the half-waves -- the lower half-wave then owns columns 8g .. 8g+7, the
             // upper one 8(g+1) .. 8(g+1)+7 -- and the epilogue issues half the store instructions for the same bytes
-            // (the store tail of a row-per-lane epilogue is bound by store ISSUE, not bandwidth: cdna_hip_programming T21)
+            // (the store tail of a row-per-lane epilogue is bound by store ISSUE, not bandwidth: cdna_hip_programming T21;
+            // profiles/r06_c_ab_flash_wide_store.jsonl)
 #pragma unroll
             for (int n = 0; n < NV; ++n)
 #pragma unroll
@@ -547,19 +508,6 @@ BP_DEV void flash_fwd_tile(const FlashParams p, char *smem, const uint32_t lds0,
                         *reinterpret_cast<u32x4 *>(og + d0) = w;
                     }
                 }
-#else
-#pragma unroll
-            for (int n = 0; n < NV; ++n)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int d0 = n * 32 + 8 * g + 4 * hh;
-                    if (d0 < p.d) {
-                        u32x2 w = {E::pack2(acc[n][4 * g + 0] * inv, acc[n][4 * g + 1] * inv),
-                                   E::pack2(acc[n][4 * g + 2] * inv, acc[n][4 * g + 3] * inv)};
-                        *reinterpret_cast<u32x2 *>(og + d0) = w;
-                    }
-                }
-#endif
         }
     }
 #ifdef BP_FWD_PROFILE
@@ -575,8 +523,7 @@ BP_DEV void flash_fwd_tile(const FlashParams p, char *smem, const uint32_t lds0,
 // (sample, head), the heaviest remaining and the lightest (t and n-1-t): every workgroup then carries the same
 // n+1 key blocks, nothing waits, and both tiles still belong to one group, i.e. one XCD's L2 holds their K/V.
 template <class ET, int KD, int NV, bool HAS_V, bool FULLD, bool DROP>
-__global__ __launch_bounds__((FlashDmaCfg<KD, NV, HAS_V>::NT),
-                             (FlashDmaCfg<KD, NV, HAS_V>::NWAVE == 8 ? 4 : BP_FLASH_MINWAVES(NV, DROP)))
+__global__ __launch_bounds__((FlashDmaCfg<KD, NV, HAS_V>::NT), flash_min_waves(NV, DROP))
 void flash_fwd_dma_kernel(const FlashParams p) {
     using C = FlashDmaCfg<KD, NV, HAS_V>;
     __shared__ __attribute__((aligned(16))) char smem[C::NSTAGE * C::STAGE];

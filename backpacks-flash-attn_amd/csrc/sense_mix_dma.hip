@@ -35,14 +35,6 @@
 #include "bp_dma.h"
 #include "bp_kernels.h"
 
-// the dense content stream: read once per job under the shipped ticket order -> non-temporal; the paired-ticket probe
-// (BP_MIX_ORDER == 2) WANTS the group's other workgroups to hit these lines in the L2
-#if defined(BP_MIX_ORDER) && BP_MIX_ORDER == 2
-#define BP_MIX_CONTENT_DMA dma16_s
-#else
-#define BP_MIX_CONTENT_DMA dma16_s_nt
-#endif
-
 namespace bp {
 
 // Development builds only (-DBP_MIX_PROFILE, scripts/probes/mix_timeline): every wave adds up the s_memtime ticks its
@@ -54,10 +46,6 @@ __device__ unsigned long long g_mix_prof[256][8][12];   // [workgroup][wave][pha
 #else
 #define MIX_TICK(var) do { } while (0)
 #define MIX_ADD(k, expr) do { } while (0)
-#endif
-
-#ifndef BP_MIX_X_PRIO
-#define BP_MIX_X_PRIO 3
 #endif
 
 template <int KD, bool WEIGHTED = false>
@@ -128,34 +116,7 @@ __global__ __launch_bounds__(512) void sense_mix_dma_kernel(const MixParams p) {
     MixQueues *queues = p.queues;
     uint32_t exhausted = 0;   // bit q: queue q has no jobs left (wave-uniform, only thread 0 uses it)
     const int my_xcd = blockIdx.x & 7;
-#if defined(BP_MIX_ORDER) && BP_MIX_ORDER == 2
-    // Paired tickets (probe): a ticket is the PAIR of query tiles (n-1-t, t) of one (sample, column chunk) group -- the long one
-    // first, the short one right behind it on the same workgroup -- and a group's pairs are consecutive tickets.  Every
-    // ticket of a group then costs the same (n + 1 tile sweeps), the group's workgroups start together at key 0 and stream
-    // the same content rows in step: one fetch from HBM, the rest L2 hits, where heaviest-first re-streams every tile.
-    int pending = -1;         // the short tile of my current ticket (thread 0 only)
-    const int n_pairs = (p.n_qtiles + 1) / 2;
-#endif
     auto next_job = [&]() -> int {   // thread 0 only; returns grp * 256 + qt, or -1
-#if defined(BP_MIX_ORDER) && BP_MIX_ORDER == 2
-        if (pending >= 0) { const int j = pending; pending = -1; return j; }
-        for (int t = 0; t < 8; ++t) {
-            const int q = (my_xcd + t) & 7;
-            if (exhausted & (1u << q)) continue;
-            const int groups = mix_queue_groups(p.b, p.n_chunks, q);
-            const int njobs = groups * n_pairs;
-            const int idx = njobs > 0 ? (int)atomicAdd(&queues->ticket[q], 1u) : njobs;
-            if (idx < njobs) {
-                const int gl = idx / n_pairs, pr = idx - gl * n_pairs;
-                const int grp = mix_queue_group(p.n_chunks, q, gl);
-                const int lng = p.n_qtiles - 1 - pr;
-                if (pr != lng) pending = grp * 256 + pr;
-                return grp * 256 + lng;
-            }
-            exhausted |= 1u << q;
-        }
-        return -1;
-#endif
         for (int t = 0; t < 8; ++t) {
             const int q = (my_xcd + t) & 7;
             if (exhausted & (1u << q)) continue;
@@ -168,13 +129,8 @@ __global__ __launch_bounds__(512) void sense_mix_dma_kernel(const MixParams p) {
                 // (sample-major order -- one sample's twelve jobs together -- fetches 4 % less and runs 2-3 % slower, r02_w)
                 // (table form, r04_ab: walking the queue column chunk by column chunk, so that the rows in flight chip-wide are
                 // one chunk's third of the table, is 1-2 % slower at B = 64 ... 2048 -- the memory-side cache does not pay it back)
-                // (round 6, S = 4096, review item "lockstep": -DBP_MIX_ORDER=1 hands out a group's query tiles as CONSECUTIVE
-                // tickets, heaviest first, so that the CUs of one XCD stream one (sample, column chunk) slab at a time --
-                // measured in profiles/r06_c_*; a development switch, the shipped order is the one below)
-#if defined(BP_MIX_ORDER) && BP_MIX_ORDER == 1
-                const int gl = idx / p.n_qtiles;
-                return mix_queue_group(p.n_chunks, q, gl) * 256 + (p.n_qtiles - 1 - (idx - gl * p.n_qtiles));
-#endif
+                // (a group's query tiles as consecutive tickets, profiles/r06_c_ab_mix_order_4096.jsonl, and paired tickets,
+                // profiles/r06_t_ab_mix_paired_tickets_*.txt, were measured and not adopted)
                 const int slot = idx / groups;
                 const int grp = mix_queue_group(p.n_chunks, q, idx - slot * groups);
                 return grp * 256 + (p.n_qtiles - 1 - slot);
@@ -289,8 +245,8 @@ __global__ __launch_bounds__(512) void sense_mix_dma_kernel(const MixParams p) {
                             continue;
                         }
                         const uint32_t back = (uint32_t)(max(c_piece_row(j) - last_row, 0) * p.c_rs) * 2u;
-                        BP_MIX_CONTENT_DMA(ct2, c_voff[j] - back,
-                                           __builtin_amdgcn_readfirstlane(stage_off + C::KTILE + (wave * C::C_DMA + j) * 1024));
+                        dma16_s_nt(ct2, c_voff[j] - back,
+                                   __builtin_amdgcn_readfirstlane(stage_off + C::KTILE + (wave * C::C_DMA + j) * 1024));
                     }
             } else {
 #pragma unroll
@@ -301,7 +257,7 @@ __global__ __launch_bounds__(512) void sense_mix_dma_kernel(const MixParams p) {
                     if ((pieces >> (C::K_DMA + j)) & 1u) {
                         if (GATHER) gather_piece(j, stage_off + C::KTILE + (wave * C::C_DMA + j) * 1024);
                         // the content stream is read once per job: non-temporal (-1.6 % at B=64, r02_p)
-                        else BP_MIX_CONTENT_DMA(ct2, c_voff[j], stage_off + C::KTILE + (wave * C::C_DMA + j) * 1024);
+                        else dma16_s_nt(ct2, c_voff[j], stage_off + C::KTILE + (wave * C::C_DMA + j) * 1024);
                     }
             }
             if (WEIGHTED && ((pieces >> (C::K_DMA + C::C_DMA)) & 1u)) {
@@ -444,7 +400,7 @@ __global__ __launch_bounds__(512) void sense_mix_dma_kernel(const MixParams p) {
             // X is one dependent chain (S^T -> softmax -> first MFMAs), Y a stream of independent MFMAs: without a
             // priority the older waves 0-3 win every arbitration, and X of waves 4-7 starves behind their Y (2230
             // clocks against 1360 the other way round, r03_ab timeline)
-            __builtin_amdgcn_s_setprio(BP_MIX_X_PRIO);
+            __builtin_amdgcn_s_setprio(3);
             f32x16 st0, st1;
             {
                 // S^T of both key halves as one operand stream, alternating accumulators (the per-half form waits for

@@ -10,9 +10,8 @@
 // (registers -> LDS, one __syncthreads per key block, 128 output columns per workgroup: S^T recomputed five times for
 // d = 640, every MFMA behind its own LDS round trip):
 //   * the K rows and the content rows of a 32-key block reach LDS by DMA (`global_load_lds_dwordx4`, bp_dma.h) into a
-//     ring: block i + 1 is in flight while block i is multiplied; one s_barrier per block.  RING is a template parameter (2 to
-//     4 slots with a counted vmcnt); three and four slots measured nothing over two (d_k = 160, B = 1024: 6.07 / 6.19 / 6.19
-//     ms, profiles/r06_i_*), so two are shipped and every wait drains the ring;
+//     2-slot ring: block i + 1 is in flight while block i is multiplied; one s_barrier per block, every wait drains the ring
+//     (three and four slots measured nothing over two, profiles/r06_i_*; two blocks per step were slower, profiles/r06_w_*);
 //   * a workgroup covers NB * 32 = 320 output columns, so S^T and the exponentials are recomputed twice per query block
 //     instead of five times; d_k = 160 runs eight waves per workgroup (256 queries share a block's rows; 4 waves x 320
 //     columns: 7.96 ms, 8 waves x 160 columns: 9.3 ms, 8 x 320: 6.15 ms, profiles/r06_h_*), d_k = 640 four (its 160 fragment
@@ -27,9 +26,10 @@
 
 namespace bp {
 
-template <int KD, int NW, int NB, int RING = 2, int SUB = 1>
+template <int KD, int NW, int NB>
 struct WideDmaCfg {
-    static constexpr int BK = 32 * SUB;                // keys per ring step: SUB 32-key blocks (one S^T / P V run each)
+    static constexpr int RING = 2;                     // ring slots
+    static constexpr int BK = 32;                      // keys per ring step
     static constexpr int NT = NW * 64;
     static constexpr int BM = NW * 32;                 // queries per workgroup (a wave owns 32)
     static constexpr int KSLOTS = 2 * KD + 1;          // 16-byte slots per K row, one of them padding (odd pitch)
@@ -40,13 +40,9 @@ struct WideDmaCfg {
     static constexpr int CROW = CSLOTS * 16;
     static constexpr int C_PIECES = BK * CSLOTS / 64;  // 2 NB (0 for the LSE kernel: K only)
     static constexpr int PIECES = K_PIECES + C_PIECES;
-    static constexpr int NPW = (PIECES + NW - 1) / NW; // DMA instructions per wave and step: the SAME number for every wave, so
-    static constexpr int STAGE = NPW * NW * 1024;      // that `s_waitcnt vmcnt((RING - 2) NPW)` means "my share of the oldest
-                                                       // block in flight has landed" (pieces past PIECES re-fetch a K chunk
-                                                       // into the stage's unused tail)
-    static constexpr int WAIT = (RING - 2) * NPW;      // my pieces of the younger blocks that may still be in flight
-    static_assert(RING >= 2 && RING * STAGE <= 160 * 1024, "LDS budget");
-    static_assert(WAIT <= 63, "vmcnt is a 6-bit field");
+    static constexpr int NPW = (PIECES + NW - 1) / NW; // DMA instructions per wave and step, the same for every wave (pieces
+    static constexpr int STAGE = NPW * NW * 1024;      // past PIECES re-fetch a K chunk into the stage's unused tail)
+    static_assert(RING * STAGE <= 160 * 1024, "LDS budget");
 };
 
 // byte offset of (row, logical 16-byte chunk ch) in a content image of NB 64-byte chunks per row; ds_read_b64_tr_b16 serves
@@ -61,9 +57,9 @@ template <int NB> BP_DEV int wide_c_off(int row, int ch) {
 }
 
 // The ring: per-lane source offsets of my DMA pieces (constant over the sweep), and the issue of one step's pieces.
-template <int KD, int NW, int NB, int RING = 2, int SUB = 1>
+template <int KD, int NW, int NB>
 struct WideRing {
-    using C = WideDmaCfg<KD, NW, NB, RING, SUB>;
+    using C = WideDmaCfg<KD, NW, NB>;
     uint32_t voff[C::NPW];
     // GATHER: the content rows are rows of a table picked by an index per key (bp_sense_mix_gather).  A content piece's
     // descriptor is then (row of the block) << 16 | byte offset of its column inside the chunk; the table row's byte offset
@@ -148,11 +144,11 @@ template <int KD> BP_DEV void wide_dma_load_q(u32x4 (&qf)[KD], const uint16_t *q
 }
 
 // ---- fused mix ---------------------------------------------------------------------------------------------------------
-template <class ET, int KD, int NW, int NB, int RING, bool GATHER, int SUB>
+template <class ET, int KD, int NW, int NB, bool GATHER>
 __global__ __launch_bounds__(NW * 64) void sense_mix_wide_dma_kernel(const MixParams p) {
-    using C = WideDmaCfg<KD, NW, NB, RING, SUB>;
+    using C = WideDmaCfg<KD, NW, NB>;
     using E = Elem<ET>;
-    constexpr int kIdsOff = RING * C::STAGE;           // GATHER: the job's row indices behind the ring, 4 bytes per key
+    constexpr int kIdsOff = C::RING * C::STAGE;        // GATHER: the job's row indices behind the ring, 4 bytes per key
     static_assert(!GATHER || kIdsOff + kMixGatherMaxKeys * 4 <= 160 * 1024, "LDS budget");
     __shared__ __attribute__((aligned(16))) char smem[kIdsOff + (GATHER ? kMixGatherMaxKeys * 4 : 0)];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -184,7 +180,7 @@ __global__ __launch_bounds__(NW * 64) void sense_mix_wide_dma_kernel(const MixPa
     const float c2 = p.scale_log2e;
     const int nb_live = min(NB, (p.dout - col_base + 31) / 32);
 
-    WideRing<KD, NW, NB, RING, SUB> ring;
+    WideRing<KD, NW, NB> ring;
     ring.setup(wave, lane, p.qk_rs, p.c_rs, col_base, p.dout, GATHER);
     int l_i = 0, kb_i = 0, slot_i = 0;                // (sense, key block) and ring slot of the next issue
     auto issue = [&]() {
@@ -197,7 +193,7 @@ __global__ __launch_bounds__(NW * 64) void sense_mix_wide_dma_kernel(const MixPa
             ring.issue(wave, lds0 + slot_i * C::STAGE, kt, ct);
         }
         if (++kb_i == nkb) { kb_i = 0; ++l_i; }
-        if (++slot_i == RING) slot_i = 0;
+        if (++slot_i == C::RING) slot_i = 0;
     };
 
     f32x16 acc[NB];
@@ -219,14 +215,11 @@ __global__ __launch_bounds__(NW * 64) void sense_mix_wide_dma_kernel(const MixPa
     float lse2 = 0.f;
     const uint16_t *qrow = qg + (int64_t)min(my_q, S - 1) * p.qk_rs;
 
-    for (int t = 0; t < RING - 1 && t < nsteps; ++t) issue();
+    for (int t = 0; t < C::RING - 1 && t < nsteps; ++t) issue();
     int slot_r = 0;                        // ring slot of this step's block
     for (int step = 0; step < nsteps; ++step) {
         const int l = step / nkb, kb = step - l * nkb;
-        // my pieces of this step's block have landed (RING - 2 younger blocks may stay in flight; in the sweep's last steps
-        // there are fewer of them: wait for all) ...
-        if (RING > 2 && step + RING - 2 < nsteps) wait_vmcnt<C::WAIT>();
-        else wait_vmcnt<0>();
+        wait_vmcnt<0>();                   // my pieces of this step's block have landed ...
         __builtin_amdgcn_s_barrier();      // ... so have everybody's; nobody reads the slot of the previous step any more
         if (kb == 0 && wave_has_rows) {    // a new sense: my row's fragments and log-sum-exp (the compiler's wait for these
                                            // loads also waits for the DMA in flight: once per sense)
@@ -234,17 +227,14 @@ __global__ __launch_bounds__(NW * 64) void sense_mix_wide_dma_kernel(const MixPa
             lse2 = p.lse[((int64_t)batch * p.nsenses + l) * p.lse_stride + my_q] * kLog2e;
             settle(lse2);
         }
-        if (step + RING - 1 < nsteps) issue();
+        if (step + C::RING - 1 < nsteps) issue();
         const char *stage = smem + slot_r * C::STAGE;
-        if (++slot_r == RING) slot_r = 0;
-#pragma unroll
-        for (int sub = 0; sub < SUB; ++sub)
-        if (wave_has_rows && kb * SUB + sub <= my_last_kb) {
-            const char *kbuf = stage + sub * 32 * C::KROW;
-            const char *cbuf = stage + C::KREGION + sub * 32 * C::CROW;
-            f32x16 st = wide_dma_scores<ET, KD, C::KROW, (NW <= 4)>(kbuf, qf, l31, hh);
+        if (++slot_r == C::RING) slot_r = 0;
+        const char *cbuf = stage + C::KREGION;
+        if (wave_has_rows && kb <= my_last_kb) {
+            f32x16 st = wide_dma_scores<ET, KD, C::KROW, (NW <= 4)>(stage, qf, l31, hh);
             u32x4 pf[2];
-            if (kb * SUB + sub == my_last_kb) {   // the diagonal block: exact zeros above the diagonal
+            if (kb == my_last_kb) {   // the diagonal block: exact zeros above the diagonal
                 const int lim = l31 - 4 * hh;   // my_q - kb * 32 - 4 hh
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks)
@@ -298,10 +288,10 @@ __global__ __launch_bounds__(NW * 64) void sense_mix_wide_dma_kernel(const MixPa
 }
 
 // ---- LSE ---------------------------------------------------------------------------------------------------------------
-template <class ET, int KD, int NW, int RING, int SUB>
+template <class ET, int KD, int NW>
 __global__ __launch_bounds__(NW * 64) void sense_lse_wide_dma_kernel(const MixParams p, float *lse_out) {
-    using C = WideDmaCfg<KD, NW, 0, RING, SUB>;
-    __shared__ __attribute__((aligned(16))) char smem[RING * C::STAGE];
+    using C = WideDmaCfg<KD, NW, 0>;
+    __shared__ __attribute__((aligned(16))) char smem[C::RING * C::STAGE];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hh = lane >> 5;
     const int S = p.s;
@@ -320,7 +310,7 @@ __global__ __launch_bounds__(NW * 64) void sense_lse_wide_dma_kernel(const MixPa
     const int my_last_kb = q0 / 32;                   // in 32-key blocks
     const float c2 = p.scale_log2e;
 
-    WideRing<KD, NW, 0, RING, SUB> ring;
+    WideRing<KD, NW, 0> ring;
     ring.setup(wave, lane, p.qk_rs, 0, 0, 0);
     u32x4 qf[KD];
     if (wave_has_rows) wide_dma_load_q<KD>(qf, qg + (int64_t)min(my_q, S - 1) * p.qk_rs, hh);
@@ -330,25 +320,18 @@ __global__ __launch_bounds__(NW * 64) void sense_lse_wide_dma_kernel(const MixPa
         const uint16_t *kt = kg + (int64_t)kb_i * C::BK * p.qk_rs;
         ring.issue(wave, lds0 + slot_i * C::STAGE, kt, kt);
         ++kb_i;
-        if (++slot_i == RING) slot_i = 0;
+        if (++slot_i == C::RING) slot_i = 0;
     };
-    for (int t = 0; t < RING - 1 && t < nkb; ++t) issue();
+    for (int t = 0; t < C::RING - 1 && t < nkb; ++t) issue();
     for (int kb = 0; kb < nkb; ++kb) {
-#ifdef BP_WIDE_WAIT_ALL   // probe build: deeper ring, but every wait drains it
         wait_vmcnt<0>();
-#else
-        if (RING > 2 && kb + RING - 2 < nkb) wait_vmcnt<C::WAIT>();
-        else wait_vmcnt<0>();
-#endif
         __builtin_amdgcn_s_barrier();
-        if (kb + RING - 1 < nkb) issue();
+        if (kb + C::RING - 1 < nkb) issue();
         const char *stage = smem + slot_r * C::STAGE;
-        if (++slot_r == RING) slot_r = 0;
-#pragma unroll
-        for (int sub = 0; sub < SUB; ++sub)
-        if (wave_has_rows && kb * SUB + sub <= my_last_kb) {
-            f32x16 st = wide_dma_scores<ET, KD, C::KROW, (NW <= 4)>(stage + sub * 32 * C::KROW, qf, l31, hh);
-            if (kb * SUB + sub == my_last_kb) {
+        if (++slot_r == C::RING) slot_r = 0;
+        if (wave_has_rows && kb <= my_last_kb) {
+            f32x16 st = wide_dma_scores<ET, KD, C::KROW, (NW <= 4)>(stage, qf, l31, hh);
+            if (kb == my_last_kb) {
                 const int lim = l31 - 4 * hh;
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
@@ -379,68 +362,38 @@ __global__ __launch_bounds__(NW * 64) void sense_lse_wide_dma_kernel(const MixPa
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------
-// d_k = 160: eight waves x 160 columns (256 queries share a block's K and content rows; two waves per SIMD);
+// d_k = 160: eight waves x 320 columns (256 queries share a block's K and content rows; two waves per SIMD);
 // d_k = 640: four waves x 320 columns (160 fragment + 160 accumulator registers: one wave per SIMD owns the file).
-#ifndef BP_WIDE160_NW
-#define BP_WIDE160_NW 8
-#endif
-#ifndef BP_WIDE160_NB
-#define BP_WIDE160_NB 10
-#endif
-#ifndef BP_WIDE160_RING
-#define BP_WIDE160_RING 2
-#endif
-#ifndef BP_WIDE160_LSE_RING
-#define BP_WIDE160_LSE_RING 2
-#endif
-#ifndef BP_WIDE640_LSE_RING
-#define BP_WIDE640_LSE_RING 2
-#endif
-
-// 32-key blocks per ring step at d_k = 160 when the length allows (s % (32 SUB) == 0).  Two blocks per step -- half the
-// barriers and waits, 61 KB stages -- measured SLOWER for the mix (6.13 -> 6.43 ms at B = 1024, table form 6.59 -> 6.68; LSE
-// 1.17 -> 1.15; profiles/r06_w_*): the barrier count is not what the step waits for.  One block per step is shipped.
-#ifndef BP_WIDE160_SUB
-#define BP_WIDE160_SUB 1
-#endif
-
 bool sense_wide_dma_takes(int s, int dk, int dout, bool vec_qk, bool vec_c, bool weighted) {
-#ifdef BP_WIDE_NO_DMA   // variant build for A/B runs: everything wide on the staged kernels of sense_wide.hip
-    return false;
-#endif
     return vec_qk && vec_c && !weighted && (dk == 160 || dk == 640) && s % 32 == 0 && s > 0 && dout % 8 == 0;
 }
 
-template <class ET, int KD, int NW, int NB, int RING, int SUB>
+template <class ET, int KD, int NW, int NB>
 static hipError_t launch_mix_wide_dma_cfg(const MixParams &p, hipStream_t stream) {
-    using C = WideDmaCfg<KD, NW, NB, RING, SUB>;
+    using C = WideDmaCfg<KD, NW, NB>;
     const int n_qtiles = (p.s + C::BM - 1) / C::BM;
     const int n_chunks = (p.dout + NB * 32 - 1) / (NB * 32);
     const dim3 grid(xcd_grid(p.b * n_chunks, n_qtiles)), block(C::NT);
     if (p.row_index != nullptr)
-        hipLaunchKernelGGL((sense_mix_wide_dma_kernel<ET, KD, NW, NB, RING, true, SUB>), grid, block, 0, stream, p);
+        hipLaunchKernelGGL((sense_mix_wide_dma_kernel<ET, KD, NW, NB, true>), grid, block, 0, stream, p);
     else
-        hipLaunchKernelGGL((sense_mix_wide_dma_kernel<ET, KD, NW, NB, RING, false, SUB>), grid, block, 0, stream, p);
+        hipLaunchKernelGGL((sense_mix_wide_dma_kernel<ET, KD, NW, NB, false>), grid, block, 0, stream, p);
     return hipGetLastError();
 }
 
 hipError_t launch_sense_mix_wide_dma(const MixParams &p, int dtype, hipStream_t stream) {
-    if (p.dk == 160 && BP_WIDE160_SUB > 1 && p.s % (32 * BP_WIDE160_SUB) == 0)
-        return dtype == 1
-                   ? launch_mix_wide_dma_cfg<BF16, 10, BP_WIDE160_NW, BP_WIDE160_NB, BP_WIDE160_RING, BP_WIDE160_SUB>(p, stream)
-                   : launch_mix_wide_dma_cfg<F16, 10, BP_WIDE160_NW, BP_WIDE160_NB, BP_WIDE160_RING, BP_WIDE160_SUB>(p, stream);
     if (p.dk == 160)
-        return dtype == 1 ? launch_mix_wide_dma_cfg<BF16, 10, BP_WIDE160_NW, BP_WIDE160_NB, BP_WIDE160_RING, 1>(p, stream)
-                          : launch_mix_wide_dma_cfg<F16, 10, BP_WIDE160_NW, BP_WIDE160_NB, BP_WIDE160_RING, 1>(p, stream);
-    return dtype == 1 ? launch_mix_wide_dma_cfg<BF16, 40, 4, 10, 2, 1>(p, stream)
-                      : launch_mix_wide_dma_cfg<F16, 40, 4, 10, 2, 1>(p, stream);
+        return dtype == 1 ? launch_mix_wide_dma_cfg<BF16, 10, 8, 10>(p, stream)
+                          : launch_mix_wide_dma_cfg<F16, 10, 8, 10>(p, stream);
+    return dtype == 1 ? launch_mix_wide_dma_cfg<BF16, 40, 4, 10>(p, stream)
+                      : launch_mix_wide_dma_cfg<F16, 40, 4, 10>(p, stream);
 }
 
-template <class ET, int KD, int NW, int RING, int SUB>
+template <class ET, int KD, int NW>
 static hipError_t launch_lse_wide_dma_cfg(const MixParams &p, float *lse, hipStream_t stream) {
-    using C = WideDmaCfg<KD, NW, 0, RING, SUB>;
+    using C = WideDmaCfg<KD, NW, 0>;
     const dim3 grid(xcd_grid(p.b * p.nsenses, (p.s + C::BM - 1) / C::BM)), block(C::NT);
-    hipLaunchKernelGGL((sense_lse_wide_dma_kernel<ET, KD, NW, RING, SUB>), grid, block, 0, stream, p, lse);
+    hipLaunchKernelGGL((sense_lse_wide_dma_kernel<ET, KD, NW>), grid, block, 0, stream, p, lse);
     return hipGetLastError();
 }
 
@@ -450,14 +403,11 @@ hipError_t launch_sense_lse_wide_dma(const void *q, const void *k, float *lse, i
     MixParams p{};
     p.q = q; p.k = k; p.qk_bs = qk_bs; p.qk_rs = qk_rs; p.qk_ss = qk_ss;
     p.lse_stride = lse_stride; p.b = b; p.s = s; p.nsenses = nsenses; p.dk = dk; p.scale_log2e = scale_log2e;
-    if (dk == 160 && BP_WIDE160_SUB > 1 && s % (32 * BP_WIDE160_SUB) == 0)
-        return dtype == 1 ? launch_lse_wide_dma_cfg<BF16, 10, 8, BP_WIDE160_LSE_RING, BP_WIDE160_SUB>(p, lse, stream)
-                          : launch_lse_wide_dma_cfg<F16, 10, 8, BP_WIDE160_LSE_RING, BP_WIDE160_SUB>(p, lse, stream);
     if (dk == 160)
-        return dtype == 1 ? launch_lse_wide_dma_cfg<BF16, 10, 8, BP_WIDE160_LSE_RING, 1>(p, lse, stream)
-                          : launch_lse_wide_dma_cfg<F16, 10, 8, BP_WIDE160_LSE_RING, 1>(p, lse, stream);
-    return dtype == 1 ? launch_lse_wide_dma_cfg<BF16, 40, 4, BP_WIDE640_LSE_RING, 1>(p, lse, stream)
-                      : launch_lse_wide_dma_cfg<F16, 40, 4, BP_WIDE640_LSE_RING, 1>(p, lse, stream);
+        return dtype == 1 ? launch_lse_wide_dma_cfg<BF16, 10, 8>(p, lse, stream)
+                          : launch_lse_wide_dma_cfg<F16, 10, 8>(p, lse, stream);
+    return dtype == 1 ? launch_lse_wide_dma_cfg<BF16, 40, 4>(p, lse, stream)
+                      : launch_lse_wide_dma_cfg<F16, 40, 4>(p, lse, stream);
 }
 
 }  // namespace bp

@@ -481,7 +481,7 @@ def _combine_senses(contextualization, content):
     accumulated in fp32 inside one GEMM instead of being a 16-bit sum of 16-bit products).  On ROCm 7.2 the BLAS
     backward of the batched `contextualization @ content` in bf16 takes a memory fault at Backpack-Small dimensions
     (k 16, S 1024, d 768 -- with or without a contiguous content, with or without a materialised gradient of the
-    sum; fp32 and the einsum form do not: scripts/debug/r03_blas_fault.py, profiles/r03_h_blas_fault.txt).  The HIP
+    sum; fp32 and the einsum form do not: profiles/r03_h_blas_fault.txt, the script at f493116).  The HIP
     path (use_flash_attn) never touches any of this."""
     if contextualization.is_cuda and contextualization.dtype != torch.float32 and torch.is_grad_enabled() \
             and (contextualization.requires_grad or content.requires_grad):

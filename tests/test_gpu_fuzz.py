@@ -9,7 +9,7 @@ dense and table (gather) form.  Every case is a fixed function of its seed, so a
 the oracle (oracle/ref_cpu.py) in fp32 on the CPU under the reference's rule: error <= 2 x the error of the same-dtype eager
 op sequence (+ two 16-bit rounding units of the result's range).  (On the CPU on purpose: run on the GPU, the oracle's own
 autograd -- library GEMMs on odd, transposed shapes -- ended a 3000-case hunt with an illegal memory access inside a
-torch kernel, scripts/debug/r05_fuzz_trace.py.)
+torch kernel; localised by scripts/debug/r05_fuzz_trace.py at commit f493116.)
 """
 import os
 import random
