@@ -14,7 +14,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('BP_HIP_LIB') or os.path.join(_HERE, 'libbackpack_hip.so')  # env: A/B builds only
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 _lib = None
 
@@ -82,6 +82,10 @@ SIGNATURES = {
     'bp_bias_gelu_fwd': (_i32, [_ptr] * 4 + [_i64, _i32, _i32, _ptr]),
     'bp_bias_gelu_bwd': (_i32, [_ptr] * 5 + [_i64, _i32, _i32, _i32, _ptr]),
     'bp_column_sum': (_i32, [_ptr] * 3 + [_i64, _i32, _i32, _i32, _ptr]),
+    'bp_flash_decode_ws_floats': (_i64, [_i32] * 4),
+    'bp_flash_decode': (_i32, [_ptr] * 8 + [_i64] + [_i32] * 4 + [_i64] * 13 + [_f32, _i32, _ptr]),
+    'bp_sense_decode_ws_floats': (_i64, [_i32] * 4),
+    'bp_sense_decode': (_i32, [_ptr] * 9 + [_i64] + [_i32] * 5 + [_i64] + [_i64] * 11 + [_f32, _i32, _ptr]),
 }
 
 
@@ -999,3 +1003,119 @@ class GraphedForward:
                                    'refreshed in place; capture a new GraphedForward')
         self.graph.replay()
         return self.static_out
+
+
+# ---- KV-cached decoding (C ABI bp_flash_decode / bp_sense_decode) ---------------------------------------------------
+
+def _decode_ws(floats, device):
+    # fresh per call, like the other workspaces: the caching allocator hands it back once the stream has used it, and a
+    # captured graph keeps its own block
+    return torch.empty((max(int(floats), 4),), dtype=torch.float32, device=device)
+
+
+def _vec16(*tensors):
+    return all(t.data_ptr() % 16 == 0 and t.stride(-1) == 1 and all(s % 8 == 0 for s in t.stride()[:-1])
+               for t in tensors)
+
+
+def flash_decode_supported(q, kv_cache):
+    """Whether bp_flash_decode takes these operands: 16-bit CUDA tensors, head_dim % 8 == 0 and <= 128, 16-byte
+    friendly layouts (include/bp_hip.h)."""
+    if not (q.is_cuda and kv_cache.is_cuda) or q.dtype not in (torch.float16, torch.bfloat16) or kv_cache.dtype != q.dtype:
+        return False
+    d = q.shape[-1]
+    return d % 8 == 0 and d <= 128 and kv_cache.dim() == 5 and _vec16(q, kv_cache)
+
+
+def flash_decode(q, k_new, v_new, kv_cache, cache_seqlens, softmax_scale=None, out=None, return_lse=False):
+    """One decode step of trunk attention against the reference's KV cache.
+
+    q, k_new, v_new (B, H, D) 16-bit; kv_cache (B, max_seqlen, 2, H, D) (already offset to the batch rows of this call);
+    cache_seqlens (B,) int32 on the device: cached positions of every sample BEFORE this token.  Writes k_new / v_new into
+    cache row cache_seqlens[b] and returns out (B, H, D) = softmax(scale q K[0..L]^T) V[0..L] (and the fp32 (B, H) LSE with
+    return_lse).  The lengths are not advanced; the host never reads them."""
+    _require_cuda(q, k_new, v_new, kv_cache, cache_seqlens)
+    if q.dim() != 3 or k_new.shape != q.shape or v_new.shape != q.shape:
+        raise RuntimeError('bp_hip.flash_decode: q, k_new, v_new must be (B, H, D) of one shape')
+    b, h, d = q.shape
+    if kv_cache.dim() != 5 or kv_cache.shape[0] != b or kv_cache.shape[2] != 2 or tuple(kv_cache.shape[3:]) != (h, d):
+        raise RuntimeError(f'bp_hip.flash_decode: kv_cache must be (B, max_seqlen, 2, H, D) = ({b}, *, 2, {h}, {d}), '
+                           f'got {tuple(kv_cache.shape)}')
+    if k_new.dtype != q.dtype or v_new.dtype != q.dtype or kv_cache.dtype != q.dtype:
+        raise RuntimeError('bp_hip.flash_decode: q, k_new, v_new and kv_cache dtypes differ')
+    if cache_seqlens.shape != (b,) or cache_seqlens.dtype != torch.int32 or not cache_seqlens.is_contiguous():
+        raise RuntimeError('bp_hip.flash_decode: cache_seqlens must be a contiguous (B,) int32 tensor')
+    scale = softmax_scale or d ** -0.5
+    max_s = kv_cache.shape[1]
+    if out is None:
+        out = torch.empty((b, h, d), dtype=q.dtype, device=q.device)
+    lse = torch.empty((b, h), dtype=torch.float32, device=q.device) if return_lse else None
+    with torch.cuda.device(q.device):
+        floats = lib().bp_flash_decode_ws_floats(b, h, d, max_s)
+        ws = _decode_ws(floats, q.device)
+        code = lib().bp_flash_decode(
+            q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(), kv_cache.data_ptr(), cache_seqlens.data_ptr(),
+            out.data_ptr(), lse.data_ptr() if lse is not None else None, ws.data_ptr(), ws.numel(),
+            b, h, d, max_s, q.stride(0), q.stride(1), k_new.stride(0), k_new.stride(1), v_new.stride(0), v_new.stride(1),
+            kv_cache.stride(0), kv_cache.stride(1), kv_cache.stride(2), kv_cache.stride(3),
+            out.stride(0), out.stride(1), h, float(scale), _dtype_code(q), _stream())
+    _check(code, 'bp_flash_decode')
+    return (out, lse) if return_lse else out
+
+
+SENSE_DECODE_MAX_SENSES = 64
+SENSE_DECODE_MAX_DOUT = 2048
+
+
+def sense_decode_supported(q, k_cache, table):
+    """Whether bp_sense_decode takes these operands: 16-bit CUDA tensors, d_k % 8 == 0 and <= SENSE_MAX_DK, at most 64
+    senses, d_out % 8 == 0 and <= 2048, 16-byte friendly layouts."""
+    if not (q.is_cuda and k_cache.is_cuda and table.is_cuda) or q.dtype not in (torch.float16, torch.bfloat16):
+        return False
+    if k_cache.dtype != q.dtype or table.dtype != q.dtype or q.dim() != 3 or table.dim() != 3:
+        return False
+    k, dk, dout = q.shape[1], q.shape[2], table.shape[2]
+    return (dk % 8 == 0 and dk <= SENSE_MAX_DK and 1 <= k <= SENSE_DECODE_MAX_SENSES and dout % 8 == 0
+            and dout <= SENSE_DECODE_MAX_DOUT and _vec16(q, k_cache, table))
+
+
+def sense_decode(q, k_new, k_cache, table, row_index, new_row, cache_seqlens, softmax_scale=None, out=None):
+    """One decode step of the Backpack sense contraction.
+
+    q, k_new (B, k, d_k) 16-bit (the two halves of ContextSelfAttn.project for the new token); k_cache (B, max_seqlen, k,
+    d_k); table (rows, k, d_out) sense vectors, read through row_index (B, max_seqlen) int32 (table form: token ids into the
+    whole-vocabulary table; cache form: b * max_seqlen + j into a per-position content cache); new_row (B,) int32 the new
+    position's row; cache_seqlens (B,) int32 cached positions before this one.  Appends k_new and new_row at position
+    cache_seqlens[b] and returns (B, d_out) = sum_l sum_{j<=t} softmax_j(scale q_l . k_l(j)) table[row(j), l]."""
+    _require_cuda(q, k_new, k_cache, table, row_index, new_row, cache_seqlens)
+    if q.dim() != 3 or k_new.shape != q.shape:
+        raise RuntimeError('bp_hip.sense_decode: q and k_new must be (B, k, d_k) of one shape')
+    b, k, dk = q.shape
+    if k_cache.dim() != 4 or k_cache.shape[0] != b or tuple(k_cache.shape[2:]) != (k, dk):
+        raise RuntimeError(f'bp_hip.sense_decode: k_cache must be (B, max_seqlen, k, d_k) = ({b}, *, {k}, {dk}), '
+                           f'got {tuple(k_cache.shape)}')
+    max_s = k_cache.shape[1]
+    if table.dim() != 3 or table.shape[1] != k:
+        raise RuntimeError('bp_hip.sense_decode: table must be (rows, k, d_out)')
+    if k_new.dtype != q.dtype or k_cache.dtype != q.dtype or table.dtype != q.dtype:
+        raise RuntimeError('bp_hip.sense_decode: q, k_new, k_cache and table dtypes differ')
+    if row_index.shape != (b, max_s) or row_index.dtype != torch.int32 or row_index.stride(-1) != 1:
+        raise RuntimeError('bp_hip.sense_decode: row_index must be (B, max_seqlen) int32, unit stride along the sequence')
+    for name, t in (('new_row', new_row), ('cache_seqlens', cache_seqlens)):
+        if t.shape != (b,) or t.dtype != torch.int32 or not t.is_contiguous():
+            raise RuntimeError(f'bp_hip.sense_decode: {name} must be a contiguous (B,) int32 tensor')
+    dout = table.shape[2]
+    scale = softmax_scale or dk ** -0.5
+    if out is None:
+        out = torch.empty((b, dout), dtype=q.dtype, device=q.device)
+    with torch.cuda.device(q.device):
+        floats = lib().bp_sense_decode_ws_floats(b, k, dout, max_s)
+        ws = _decode_ws(floats, q.device)
+        code = lib().bp_sense_decode(
+            q.data_ptr(), k_new.data_ptr(), k_cache.data_ptr(), table.data_ptr(), row_index.data_ptr(),
+            new_row.data_ptr(), cache_seqlens.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(),
+            b, k, dk, dout, max_s, table.shape[0], q.stride(0), q.stride(1), k_new.stride(0), k_new.stride(1),
+            k_cache.stride(0), k_cache.stride(1), k_cache.stride(2), table.stride(0), table.stride(1),
+            row_index.stride(0), out.stride(0), float(scale), _dtype_code(q), _stream())
+    _check(code, 'bp_sense_decode')
+    return out

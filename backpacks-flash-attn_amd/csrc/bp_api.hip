@@ -7,6 +7,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <initializer_list>
+
 #include "../../include/bp_hip.h"
 #include "bp_common.h"
 #include "bp_kernels.h"
@@ -748,6 +750,117 @@ int bp_xentropy_bwd(const float *grad_losses, const void *logits, const float *l
     p.total_classes = total_classes > 0 ? total_classes : cols;
     p.smoothing = smoothing;
     hipError_t e = bp::launch_xentropy_bwd(p, dtype, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? BP_OK : BP_ERR_LAUNCH;
+}
+
+}  // extern "C"
+
+// ---- KV-cached decoding (bp_flash_decode / bp_sense_decode) ----
+namespace {
+inline bool strides8(std::initializer_list<int64_t> strides) {
+    for (int64_t s : strides)
+        if (!mult8(s)) return false;
+    return true;
+}
+}  // namespace
+
+extern "C" {
+
+int64_t bp_flash_decode_ws_floats(int batch, int nheads, int head_dim, int max_seqlen) {
+    if (batch <= 0 || nheads <= 0 || head_dim <= 0 || max_seqlen <= 0) return 0;
+    return (int64_t)batch * nheads * bp::decode_nsplit(batch, nheads, max_seqlen) * (head_dim + 2);
+}
+
+int bp_flash_decode(const void *q, const void *k_new, const void *v_new, void *kv_cache, const int32_t *cache_seqlens,
+                    void *out, float *softmax_lse, float *ws, int64_t ws_floats,
+                    int batch, int nheads, int head_dim, int max_seqlen,
+                    int64_t q_batch_stride, int64_t q_head_stride,
+                    int64_t knew_batch_stride, int64_t knew_head_stride,
+                    int64_t vnew_batch_stride, int64_t vnew_head_stride,
+                    int64_t kv_batch_stride, int64_t kv_row_stride, int64_t kv_two_stride, int64_t kv_head_stride,
+                    int64_t o_batch_stride, int64_t o_head_stride, int64_t lse_batch_stride,
+                    float softmax_scale, int dtype, bp_stream_t stream) {
+    if (dtype != BP_DTYPE_F16 && dtype != BP_DTYPE_BF16) return BP_ERR_DTYPE;
+    if (head_dim < 1 || head_dim > 128 || head_dim % 8 != 0) return BP_ERR_HEAD_DIM;
+    if (batch <= 0 || batch > 65535 || nheads <= 0 || nheads > 65535 || max_seqlen <= 0) return BP_ERR_SHAPE;
+    if (q == nullptr || k_new == nullptr || v_new == nullptr || kv_cache == nullptr || cache_seqlens == nullptr
+        || out == nullptr || ws == nullptr)
+        return BP_ERR_SHAPE;
+    if (!aligned16(q) || !aligned16(k_new) || !aligned16(v_new) || !aligned16(kv_cache) || !aligned16(out)
+        || !aligned16(ws))
+        return BP_ERR_SHAPE;
+    if (!strides8({q_batch_stride, q_head_stride, knew_batch_stride, knew_head_stride, vnew_batch_stride,
+                   vnew_head_stride, kv_batch_stride, kv_row_stride, kv_two_stride, kv_head_stride, o_batch_stride,
+                   o_head_stride}))
+        return BP_ERR_SHAPE;
+    if (softmax_lse != nullptr && lse_batch_stride < nheads) return BP_ERR_SHAPE;
+    if (!scale_ok(softmax_scale)) return BP_ERR_SCALE;
+    if (ws_floats < bp_flash_decode_ws_floats(batch, nheads, head_dim, max_seqlen)) return BP_ERR_WORKSPACE;
+    bp::DecodeParams p{};
+    p.q = q; p.k_new = k_new; p.v_new = v_new;
+    p.k_cache = kv_cache; p.v = static_cast<uint16_t *>(kv_cache) + kv_two_stride;
+    p.q_bs = q_batch_stride; p.q_gs = q_head_stride;
+    p.kn_bs = knew_batch_stride; p.kn_gs = knew_head_stride;
+    p.vn_bs = vnew_batch_stride; p.vn_gs = vnew_head_stride;
+    p.kc_bs = p.vc_bs = kv_batch_stride; p.kc_rs = p.vc_rs = kv_row_stride; p.kc_gs = p.vc_gs = kv_head_stride;
+    p.seqlens = cache_seqlens;
+    p.b = batch; p.groups = nheads; p.dk = p.dv = head_dim; p.max_seqlen = max_seqlen;
+    p.nsplit = bp::decode_nsplit(batch, nheads, max_seqlen);
+    p.ws_acc = ws;
+    p.ws_ml = ws + (int64_t)batch * nheads * p.nsplit * head_dim;
+    p.o = out; p.o_bs = o_batch_stride; p.o_gs = o_head_stride;
+    p.lse = softmax_lse; p.lse_bs = lse_batch_stride;
+    p.scale_log2e = softmax_scale * 1.4426950408889634f;
+    hipError_t e = bp::launch_flash_decode(p, dtype, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? BP_OK : BP_ERR_LAUNCH;
+}
+
+int64_t bp_sense_decode_ws_floats(int batch, int nsenses, int d_out, int max_seqlen) {
+    if (batch <= 0 || nsenses <= 0 || d_out <= 0 || max_seqlen <= 0) return 0;
+    return (int64_t)batch * nsenses * bp::decode_nsplit(batch, nsenses, max_seqlen) * (d_out + 2);
+}
+
+int bp_sense_decode(const void *q, const void *k_new, void *k_cache, const void *table, int32_t *row_index,
+                    const int32_t *new_row, const int32_t *cache_seqlens, void *out, float *ws, int64_t ws_floats,
+                    int batch, int nsenses, int d_k, int d_out, int max_seqlen, int64_t table_rows,
+                    int64_t q_batch_stride, int64_t q_sense_stride,
+                    int64_t knew_batch_stride, int64_t knew_sense_stride,
+                    int64_t kc_batch_stride, int64_t kc_row_stride, int64_t kc_sense_stride,
+                    int64_t t_row_stride, int64_t t_sense_stride, int64_t idx_batch_stride,
+                    int64_t o_batch_stride, float softmax_scale, int dtype, bp_stream_t stream) {
+    if (dtype != BP_DTYPE_F16 && dtype != BP_DTYPE_BF16) return BP_ERR_DTYPE;
+    if (d_k < 1 || d_k > bp::kWideMaxDk || d_k % 8 != 0) return BP_ERR_HEAD_DIM;
+    if (d_out < 1) return BP_ERR_DOUT;
+    if (d_out % 8 != 0 || d_out > 2048) return BP_ERR_SHAPE;
+    if (batch <= 0 || batch > 65535 || nsenses <= 0 || nsenses > 64 || max_seqlen <= 0 || table_rows <= 0
+        || table_rows > 0x7fffffffLL)
+        return BP_ERR_SHAPE;
+    if (q == nullptr || k_new == nullptr || k_cache == nullptr || table == nullptr || row_index == nullptr
+        || new_row == nullptr || cache_seqlens == nullptr || out == nullptr || ws == nullptr)
+        return BP_ERR_SHAPE;
+    if (!aligned16(q) || !aligned16(k_new) || !aligned16(k_cache) || !aligned16(table) || !aligned16(out)
+        || !aligned16(ws))
+        return BP_ERR_SHAPE;
+    if (!strides8({q_batch_stride, q_sense_stride, knew_batch_stride, knew_sense_stride, kc_batch_stride, kc_row_stride,
+                   kc_sense_stride, t_row_stride, t_sense_stride, o_batch_stride}))
+        return BP_ERR_SHAPE;
+    if (!scale_ok(softmax_scale)) return BP_ERR_SCALE;
+    if (ws_floats < bp_sense_decode_ws_floats(batch, nsenses, d_out, max_seqlen)) return BP_ERR_WORKSPACE;
+    bp::DecodeParams p{};
+    p.q = q; p.k_new = k_new; p.k_cache = k_cache; p.v = const_cast<void *>(table);
+    p.q_bs = q_batch_stride; p.q_gs = q_sense_stride;
+    p.kn_bs = knew_batch_stride; p.kn_gs = knew_sense_stride;
+    p.kc_bs = kc_batch_stride; p.kc_rs = kc_row_stride; p.kc_gs = kc_sense_stride;
+    p.vc_rs = t_row_stride; p.vc_gs = t_sense_stride;
+    p.row_index = row_index; p.ri_bs = idx_batch_stride; p.new_row = new_row; p.table_rows = table_rows;
+    p.seqlens = cache_seqlens;
+    p.b = batch; p.groups = nsenses; p.dk = d_k; p.dv = d_out; p.max_seqlen = max_seqlen;
+    p.nsplit = bp::decode_nsplit(batch, nsenses, max_seqlen);
+    p.ws_acc = ws;
+    p.ws_ml = ws + (int64_t)batch * nsenses * p.nsplit * d_out;
+    p.o = out; p.o_bs = o_batch_stride;
+    p.scale_log2e = softmax_scale * 1.4426950408889634f;
+    hipError_t e = bp::launch_sense_decode(p, dtype, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? BP_OK : BP_ERR_LAUNCH;
 }
 

@@ -237,4 +237,29 @@ hipError_t launch_sense_lse_wide_dma(const void *q, const void *k, float *lse, i
                                      int64_t qk_rs, int64_t qk_ss, int b, int s, int nsenses, int dk, float scale_log2e,
                                      int dtype, hipStream_t stream);
 
+// Single-query decode against a cache (decode_core.h): bp_flash_decode (groups = heads; value rows from the V half of the
+// cache) and bp_sense_decode (groups = senses; value rows from a table through a row index).  Element strides.
+struct DecodeParams {
+    const void *q, *k_new, *v_new;
+    void *k_cache, *v;                // v: V half of the KV cache (trunk) / the content table (senses)
+    int64_t q_bs, q_gs, kn_bs, kn_gs, vn_bs, vn_gs;
+    int64_t kc_bs, kc_rs, kc_gs;      // key of (b, j, g): k_cache + b*kc_bs + j*kc_rs + g*kc_gs
+    int64_t vc_bs, vc_rs, vc_gs;      // trunk: value of (b, j, g); senses: table row r, sense g at r*vc_rs + g*vc_gs
+    int32_t *row_index;               // senses: (b, max_seqlen) table row of every cached position, stride ri_bs
+    int64_t ri_bs;
+    const int32_t *new_row;           // senses: (b) table row of the new position
+    int64_t table_rows;
+    const int32_t *seqlens;           // (b) cached positions before the new one
+    float *ws_acc, *ws_ml;            // (b, groups, nsplit, dv) and (b, groups, nsplit, 2) fp32 partials
+    void *o;
+    int64_t o_bs, o_gs;
+    float *lse;                       // trunk only, optional: (b, lse_bs) natural-log LSE of every head's row
+    int64_t lse_bs;
+    int b, groups, dk, dv, max_seqlen, nsplit;
+    float scale_log2e;
+};
+int decode_nsplit(int batch, int groups, int max_seqlen);
+hipError_t launch_flash_decode(const DecodeParams &p, int dtype, hipStream_t stream);
+hipError_t launch_sense_decode(const DecodeParams &p, int dtype, hipStream_t stream);
+
 }  // namespace bp

@@ -14,7 +14,7 @@ from transformers import GPT2Config
 
 from flash_attn.modules.block import Block
 from flash_attn.modules.embedding import GPT2Embeddings
-from flash_attn.modules.mha import MHA
+from flash_attn.modules.mha import MHA, cache_lengths
 from flash_attn.modules.mlp import FusedDenseGeluDense, Mlp
 from flash_attn.ops.layer_norm import dropout_add_layer_norm
 from flash_attn.utils.pretrained import state_dict_from_pretrained
@@ -132,7 +132,13 @@ class GPTModel(GPTPreTrainedModel):
                            initializer_range=config.initializer_range))
 
     def forward(self, input_ids, position_ids=None, inference_params=None):
-        assert inference_params is None, 'KV-cache decoding is out of scope'
+        """`inference_params` (src/utils/generation.py InferenceParams): KV-cached generation, forwarded to every mixer
+        (reference gpt.py:243).  In a decode step without `position_ids` the position of sample b is its cached length,
+        read on the device."""
+        if inference_params is not None and position_ids is None and inference_params.sequence_len_offset > 0:
+            lengths = cache_lengths(inference_params, input_ids.shape[0], input_ids.device)
+            position_ids = lengths.long().unsqueeze(1) + torch.arange(input_ids.shape[1], device=input_ids.device)
+        mixer_kwargs = None if inference_params is None else {'inference_params': inference_params}
         hidden = self.embeddings(input_ids, position_ids=position_ids)
         if self.fused_dropout_add_ln:
             # one HIP launch: residual (fp32) = hidden, hidden = LN(residual)   (reference gpt.py:236-240)
@@ -144,7 +150,7 @@ class GPTModel(GPTPreTrainedModel):
             residual = self.emb_drop(hidden).float()   # residual stream stays fp32 (gpt.py:231-234)
             hidden = self.ln_0(residual.to(dtype=self.ln_0.weight.dtype))
         for layer in self.layers:
-            hidden, residual = layer(hidden, residual)
+            hidden, residual = layer(hidden, residual, mixer_kwargs=mixer_kwargs)
         return hidden
 
 
@@ -164,6 +170,6 @@ class GPTLMHeadModel(GPTPreTrainedModel):
         self.lm_head.weight = self.transformer.embeddings.word_embeddings.weight
 
     def forward(self, input_ids, position_ids=None, inference_params=None):
-        hidden = self.transformer(input_ids, position_ids=position_ids)
+        hidden = self.transformer(input_ids, position_ids=position_ids, inference_params=inference_params)
         CausalLMOutput = namedtuple('CausalLMOutput', ['logits'])
         return CausalLMOutput(logits=self.lm_head(hidden))

@@ -9,6 +9,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+import bp_hip
 from flash_attn.flash_attn_interface import (flash_attn_unpadded_kvpacked_func,
                                              flash_attn_unpadded_qkvpacked_func)
 from flash_attn.ops.fused_dense import FusedDense
@@ -183,8 +184,8 @@ class MHA(nn.Module):
                 inference_params=None, **kwargs):
         """x (batch, seqlen, hidden) or, with cu_seqlens/max_seqlen, (total, hidden)."""
         if inference_params is not None:
-            raise NotImplementedError('gfx950 build: KV-cache decoding is out of scope; the '
-                                      "reference's own generation re-runs the full forward")
+            assert key_padding_mask is None and cu_seqlens is None and max_seqlen is None
+            return self._forward_cached(x, inference_params)
         if cu_seqlens is not None:
             assert max_seqlen is not None and key_padding_mask is None and self.use_flash_attn
         if key_padding_mask is not None:
@@ -204,3 +205,79 @@ class MHA(nn.Module):
             context = self.inner_attn(qkv, **kwargs)
         out = self.out_proj(context.flatten(-2))
         return out if not self.return_residual else (out, x)
+
+    # ---- KV-cached generation: the reference's contract (mha.py:356-440, flash_attn/utils/generation.py:23-55) --------
+    # key_value_memory_dict[layer_idx] is a (max_batch, max_seqlen, 2, nheads, head_dim) cache, created on first use.
+    #   prefill (sequence_len_offset == 0, any length): causal attention over the prompt, its K/V written at [0, S)
+    #   decode  (one new token per sample): the new K/V is written at position L_b and the token attends to [0, L_b];
+    #           L_b = inference_params.lengths_per_sample[b] (device int32) when set, else sequence_len_offset for all.
+    # The HIP path decodes with bp_flash_decode (append + attention in one call, no host read of the lengths); the eager
+    # twin does the same bookkeeping in torch.  More than one new token at a non-zero offset is refused: the reference
+    # runs that case without a causal mask among the new tokens.
+
+    def _kv_cache(self, inference_params, like):
+        assert self.layer_idx is not None, 'generation requires layer_idx in the constructor'
+        cache = inference_params.key_value_memory_dict.get(self.layer_idx)
+        if cache is None:
+            # zeros, not empty: the eager twin reads the whole (masked) cache, never garbage
+            cache = torch.zeros(inference_params.max_batch_size, inference_params.max_sequence_len, 2, self.num_heads,
+                                self.head_dim, dtype=like.dtype, device=like.device)
+            inference_params.key_value_memory_dict[self.layer_idx] = cache
+        return cache
+
+    def _forward_cached(self, x, inference_params):
+        if torch.is_grad_enabled() and (x.requires_grad or self.Wqkv.weight.requires_grad):
+            raise RuntimeError('KV-cached decoding is inference-only: run it under torch.no_grad() or '
+                               'torch.inference_mode()')
+        if self.return_residual:
+            qkv, x = self.Wqkv(x)
+        else:
+            qkv = self.Wqkv(x)
+        qkv = qkv.unflatten(-1, (3, self.num_heads, self.head_dim))      # (B, S, 3, H, D)
+        batch, seqlen = qkv.shape[:2]
+        cache = self._kv_cache(inference_params, qkv)
+        b0 = inference_params.batch_size_offset
+        b1 = b0 + batch
+        assert b1 <= cache.shape[0], 'batch_size_offset + batch exceeds max_batch_size'
+        if inference_params.sequence_len_offset == 0:
+            assert seqlen <= cache.shape[1], 'prompt longer than max_sequence_len'
+            cache[b0:b1, :seqlen] = qkv[:, :, 1:]
+            context = self.inner_attn(qkv)                                  # causal flash kernel / eager twin
+        elif seqlen != 1:
+            raise NotImplementedError(
+                f'KV-cached decoding takes one new token per sample after the prompt (got {seqlen} at offset '
+                f'{inference_params.sequence_len_offset}); feed multi-token continuations one token at a time')
+        else:
+            lengths = cache_lengths(inference_params, batch, qkv.device)
+            scale = self.inner_attn.softmax_scale or self.head_dim ** -0.5
+            q, k_new, v_new = qkv[:, 0].unbind(dim=1)                       # (B, H, D) each
+            if self.use_flash_attn:
+                context = bp_hip.flash_decode(q, k_new, v_new, cache[b0:b1], lengths, scale).unsqueeze(1)
+            else:
+                context = _eager_decode(q, qkv[:, 0, 1:], cache, b0, lengths, scale).unsqueeze(1)
+        out = self.out_proj(context.flatten(-2))
+        return out if not self.return_residual else (out, x)
+
+
+def cache_lengths(inference_params, batch, device):
+    """(batch,) int32 cached positions of the samples of this call: `lengths_per_sample` (device) when the caller keeps
+    per-sample lengths, else `sequence_len_offset` for every sample (the reference's contract)."""
+    lengths = getattr(inference_params, 'lengths_per_sample', None)
+    if lengths is not None:
+        b0 = inference_params.batch_size_offset
+        return lengths[b0:b0 + batch]
+    return torch.full((batch,), inference_params.sequence_len_offset, dtype=torch.int32, device=device)
+
+
+def _eager_decode(q, kv_new, cache, b0, lengths, scale):
+    """Eager twin of bp_flash_decode: append kv_new (B, 2, H, D) at row lengths[b], attend to rows [0, lengths[b]]
+    (reference op order: scale K, softmax in v.dtype)."""
+    batch = q.shape[0]
+    rows = torch.arange(b0, b0 + batch, device=q.device)
+    cache[rows, lengths.long()] = kv_new
+    k, v = cache[b0:b0 + batch].unbind(dim=2)                              # (B, M, H, D)
+    scores = torch.einsum('bhd,bshd->bhs', q, k * scale)
+    visible = torch.arange(cache.shape[1], device=q.device)[None, :] <= lengths[:, None].long()
+    scores = scores.masked_fill(~visible[:, None, :], float('-inf'))
+    attn = torch.softmax(scores, dim=-1, dtype=v.dtype)
+    return torch.einsum('bhs,bshd->bhd', attn, v)

@@ -28,6 +28,7 @@ from transformers import GPT2Config
 import bp_hip
 from flash_attn.models.gpt import GPTModel, GPTPreTrainedModel, _activation, _init_weights, _pad_vocab
 from flash_attn.modules.block import Block
+from flash_attn.modules.mha import cache_lengths
 from flash_attn.modules.mlp import FusedDenseGeluDense, Mlp
 from flash_attn.ops.fused_dense import FusedDense, fused_dense_func
 from flash_attn.ops.layer_norm import dropout_add_layer_norm
@@ -404,8 +405,8 @@ class BackpackModel(GPTPreTrainedModel):
         content = torch.nn.functional.embedding(inverse, rows.reshape(u, k * d))   # (B,S,k*d): every position's row
         return content.view(*input_ids.shape, k, d).transpose(1, 2)    # (B,k,S,d) view, as content_model returns it
 
-    def _mix_from_table(self, hidden, rows, index):
-        qk = self.contextualization_attn.project(hidden)
+    def _mix_from_table(self, hidden, rows, index, qk=None):
+        qk = self.contextualization_attn.project(hidden) if qk is None else qk
         if bp_hip.sense_mix_gather_supported(qk, rows, index.shape[1]):
             # the mix kernel reads the table rows itself: no (B,S,k,d) content tensor at all
             return bp_hip.sense_mix_gather(qk, rows, index.to(torch.int32), self.contextualization_attn.scale())
@@ -451,7 +452,89 @@ class BackpackModel(GPTPreTrainedModel):
             del content
         return out
 
+    # ---- KV-cached decoding ---------------------------------------------------------------------------------------------
+    # Besides the trunk's K/V caches (flash_attn/modules/mha.py), a decode step of a Backpack needs, for every earlier
+    # position j, the sense keys k_l(j) and the sense vectors C_l(x_j).  Both live in `key_value_memory_dict`:
+    #   'backpack_sense_k'  (max_batch, max_seqlen, k, d_k) sense keys (d_k as `project` returns it, padded on the HIP path)
+    #   'backpack_rows'     (max_batch, max_seqlen) int32: the row of every position in the table the step reads
+    #   'backpack_content'  (max_batch * max_seqlen, k, d), cache form only: the content network's rows per position
+    # Table form (the cached whole-vocabulary sense table is available: sense_table_mode 'cached'): rows = token ids.
+    # Cache form (modes 'batch' / 'off', or no table): the content network runs on the new tokens only -- exact, it is
+    # per token -- and its rows are appended; rows = b * max_seqlen + j.  The form is fixed by the prefill.
+    # Fused senses decode with bp_sense_decode; non-fused ones (d_k > 640, use_flash_attn=False) with an eager restatement.
+
+    def _decode_sense_table(self, input_ids):
+        if self.sense_table_mode == 'cached' and self.dedup_content and self.fused_senses and not self.training \
+                and input_ids.is_cuda:
+            return self.sense_table()
+        return None
+
+    def _decode_caches(self, ip, qk, content_form, like):
+        caches = ip.key_value_memory_dict
+        k, dk = qk.shape[3], qk.shape[4]
+        mb, ms = ip.max_batch_size, ip.max_sequence_len
+        if 'backpack_sense_k' not in caches:
+            caches['backpack_sense_k'] = torch.zeros(mb, ms, k, dk, dtype=qk.dtype, device=qk.device)
+            caches['backpack_rows'] = torch.zeros(mb, ms, dtype=torch.int32, device=qk.device)
+            if content_form:
+                caches['backpack_content'] = torch.zeros(mb * ms, k, self.config.n_embd, dtype=like.dtype,
+                                                         device=like.device)
+        return caches['backpack_sense_k'], caches['backpack_rows'], caches.get('backpack_content')
+
+    def _forward_cached(self, input_ids, position_ids, ip):
+        if torch.is_grad_enabled():
+            raise RuntimeError('KV-cached decoding is inference-only: run it under torch.no_grad() or '
+                               'torch.inference_mode()')
+        batch, seqlen = input_ids.shape
+        prefill = ip.sequence_len_offset == 0
+        if not prefill and seqlen != 1:
+            raise NotImplementedError(
+                f'KV-cached decoding takes one new token per sample after the prompt (got {seqlen} at offset '
+                f'{ip.sequence_len_offset}); feed multi-token continuations one token at a time')
+        hidden = self.gpt2_model(input_ids, position_ids=position_ids, inference_params=ip)
+        attn = self.contextualization_attn
+        qk = attn.project(hidden)                                        # (B, S, 2, k, d_k)
+        if prefill:
+            table = self._decode_sense_table(input_ids)
+        else:
+            table = None if 'backpack_content' in ip.key_value_memory_dict else self.sense_table()
+            if table is None and 'backpack_content' not in ip.key_value_memory_dict:
+                raise RuntimeError('Backpack decode: the cache was filled in table form but the sense table is gone '
+                                   '(weights changed, or .train() was called, since the prefill)')
+        key_cache, rows, content_cache = self._decode_caches(ip, qk, table is None, hidden)
+        b0, ms = ip.batch_size_offset, ip.max_sequence_len
+        b1 = b0 + batch
+        sample = torch.arange(b0, b1, device=input_ids.device)
+        if prefill:
+            key_cache[b0:b1, :seqlen] = qk[:, :, 1]
+            if table is not None:
+                rows[b0:b1, :seqlen] = input_ids
+                return self._mix_from_table(hidden, table, input_ids, qk=qk)
+            content = self.content_model(input_ids)                      # (B, k, S, d) view of (B, S, k*d)
+            rows[b0:b1, :seqlen] = sample[:, None] * ms + torch.arange(seqlen, device=input_ids.device)
+            content_cache.view(-1, ms, *content_cache.shape[1:])[b0:b1, :seqlen] = content.transpose(1, 2)
+            if self.fused_senses:
+                return bp_hip.sense_mix(qk, content.transpose(1, 2), attn.scale())
+            return _combine_senses(attn(hidden), content)
+        lengths = cache_lengths(ip, batch, input_ids.device)
+        if table is not None:
+            new_row = input_ids[:, 0].to(torch.int32)
+        else:
+            new_row = (sample * ms + lengths).to(torch.int32)
+            content_cache.index_copy_(0, new_row.long(), self.content_model(input_ids)[:, :, 0])
+            table = content_cache
+        q, k_new = qk[:, 0, 0], qk[:, 0, 1]                             # (B, k, d_k)
+        if self.fused_senses:
+            if not bp_hip.sense_decode_supported(q, key_cache, table):
+                raise RuntimeError(f'Backpack decode: bp_sense_decode does not take k = {q.shape[1]} senses of width '
+                                   f'{q.shape[2]} with {table.shape[2]} output columns (include/bp_hip.h)')
+            return bp_hip.sense_decode(q, k_new, key_cache[b0:b1], table, rows[b0:b1], new_row, lengths,
+                                       attn.scale()).unsqueeze(1)
+        return _eager_sense_decode(q, k_new, key_cache, table, rows, new_row, b0, lengths, attn.scale()).unsqueeze(1)
+
     def forward(self, input_ids, position_ids=None, inference_params=None):
+        if inference_params is not None:
+            return self._forward_cached(input_ids, position_ids, inference_params)
         contextl_hidden_states = self.gpt2_model(input_ids, position_ids=position_ids,
                                                  inference_params=inference_params)
         if self._token_table_allowed(input_ids):
@@ -472,6 +555,22 @@ class BackpackModel(GPTPreTrainedModel):
                                              self.contextualization_attn.scale())
         contextualization = self.contextualization_attn(contextl_hidden_states)   # (B,k,S,S)
         return _combine_senses(contextualization, content)                         # (B,S,d)
+
+
+def _eager_sense_decode(q, k_new, key_cache, table, rows, new_row, b0, lengths, scale):
+    """Eager restatement of bp_sense_decode (the non-fused Backpacks): append the new key and row at position lengths[b],
+    then o = sum_l sum_{j <= L} softmax_j(q_l . k_l(j) * scale) table[rows[b, j], l] (ContextSelfAttn's op order)."""
+    batch = q.shape[0]
+    sample = torch.arange(b0, b0 + batch, device=q.device)
+    key_cache[sample, lengths.long()] = k_new
+    rows[sample, lengths.long()] = new_row
+    keys = key_cache[b0:b0 + batch]                                        # (B, M, k, d_k)
+    scores = torch.einsum('bld,bsld->bls', q, keys * scale)
+    visible = torch.arange(keys.shape[1], device=q.device)[None, :] <= lengths[:, None].long()
+    scores = scores.masked_fill(~visible[:, None, :], float('-inf'))
+    weights = torch.softmax(scores, dim=-1, dtype=q.dtype)                 # (B, k, M)
+    content = table[rows[b0:b0 + batch].long()]                            # (B, M, k, d)
+    return torch.einsum('bls,bsld->bd', weights, content)
 
 
 def _combine_senses(contextualization, content):

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define BP_ABI_VERSION 9   /* 2: *_dropout entry points added; 3: bias/GELU + column-sum entry points added, the
+#define BP_ABI_VERSION 10  /* 2: *_dropout entry points added; 3: bias/GELU + column-sum entry points added, the
                               persistent sense-mix launches take a caller-owned `queue_ws`; 4: bp_flash_bwd* take the
                               size of `dsum_ws` (bp_flash_bwd_ws_floats) and check it, queue_ws == NULL is refused
                               while the stream is capturing (BP_ERR_QUEUE_WS); 5: bp_dropout_add_layer_norm_scaled{,_bwd}
@@ -37,7 +37,9 @@ extern "C" {
                               8: bp_sense_lse / _alpha / _mix / _mix_weighted take sense widths d_k up to 640 (wide senses:
                               the reference's vecs-4 / vecs-1 ablations), bp_build_flags() added;
                               9: bp_sense_mix_gather takes the two few-sense widths d_k = 160 / 640 (seqlen % 32 == 0; any
-                              number of table rows) */
+                              number of table rows);
+                              10: bp_flash_decode / bp_sense_decode (KV-cached single-token decoding) and their
+                              *_ws_floats queries added */
 
 /* element type of q/k/v/out/content tensors */
 #define BP_DTYPE_F16 0
@@ -499,6 +501,67 @@ int bp_bias_gelu_bwd(const void *grad, const void *pre, void *dpre, void *dbias,
                      int dtype, int dbias_is_f32, bp_stream_t stream);
 int bp_column_sum(const void *grad, void *dbias, float *ws, int64_t rows, int cols, int dtype, int dbias_is_f32,
                   bp_stream_t stream);
+
+/*
+ * bp_flash_decode -- trunk attention of ONE new query row per (sample, head) against a KV cache, appending the new
+ * token's key and value.  Serves the decode step of the reference's generation contract (flash_attn/modules/mha.py
+ * _update_kv_cache + inner_cross_attn with causal=False, flash_attn/utils/generation.py greedy_decode), whose cache is
+ *   kv_cache     (batch, max_seqlen, 2, nheads, head_dim) 16-bit, element strides kv_batch / kv_row / kv_two / kv_head,
+ *                last stride 1 (the caller offsets the base by batch_size_offset rows)
+ *   cache_seqlens  (batch) int32 DEVICE array: cached positions of sample b BEFORE this token, L_b.  The kernel writes
+ *                k_new / v_new into cache row L_b and the query attends to rows [0, L_b], the new one included; lengths
+ *                may differ between samples.  The host never reads them (one captured graph serves every step); a
+ *                length outside [0, max_seqlen - 1] is clamped into it.  The lengths are not advanced here.
+ *   q, k_new, v_new  (batch, nheads, head_dim) 16-bit, strides *_batch / *_head, last stride 1
+ *   out          (batch, nheads, head_dim) 16-bit, strides o_batch / o_head, last stride 1
+ *   softmax_lse  (batch, lse_batch_stride) fp32 or NULL: natural-log LSE of every head's row
+ *   ws           fp32 workspace of ws_floats >= bp_flash_decode_ws_floats(batch, nheads, head_dim, max_seqlen)
+ *                elements (BP_ERR_WORKSPACE otherwise), contents undefined on entry; it belongs to the call until the
+ *                stream has run it
+ * Softmax and accumulation in fp32; split over the keys with a fixed-order combine in a second launch: the result is
+ * bit-identical across calls (no atomics).  head_dim % 8 == 0 and <= 128 (BP_ERR_HEAD_DIM otherwise); 16-byte aligned
+ * bases, strides multiples of 8 (BP_ERR_SHAPE otherwise).
+ */
+int64_t bp_flash_decode_ws_floats(int batch, int nheads, int head_dim, int max_seqlen);
+int bp_flash_decode(const void *q, const void *k_new, const void *v_new, void *kv_cache, const int32_t *cache_seqlens,
+                    void *out, float *softmax_lse, float *ws, int64_t ws_floats,
+                    int batch, int nheads, int head_dim, int max_seqlen,
+                    int64_t q_batch_stride, int64_t q_head_stride,
+                    int64_t knew_batch_stride, int64_t knew_head_stride,
+                    int64_t vnew_batch_stride, int64_t vnew_head_stride,
+                    int64_t kv_batch_stride, int64_t kv_row_stride, int64_t kv_two_stride, int64_t kv_head_stride,
+                    int64_t o_batch_stride, int64_t o_head_stride, int64_t lse_batch_stride,
+                    float softmax_scale, int dtype, bp_stream_t stream);
+
+/*
+ * bp_sense_decode -- the Backpack sense contraction for ONE new position t per sample (training/src/models/backpack.py
+ * :297-314 restricted to the last row), appending the new position's sense key and row index:
+ *   out[b,:] = sum_l sum_{j<=t} softmax_j(scale q[b,l,:].k_l(j)) table[row(b,j), l, :],   t = L_b = cache_seqlens[b]
+ *   q, k_new     (batch, nsenses, d_k) 16-bit: the q / k halves of ContextSelfAttn.project for the new token, strides
+ *                *_batch / *_sense, last stride 1
+ *   k_cache      (batch, max_seqlen, nsenses, d_k) 16-bit sense keys of the cached positions, strides kc_batch / kc_row /
+ *                kc_sense, last stride 1; row L_b is written with k_new
+ *   table        (table_rows, nsenses, d_out) 16-bit sense vectors, strides t_row / t_sense, last stride 1: the whole-
+ *                vocabulary sense table (row = token id) or a per-position content cache (row = b * max_seqlen + j)
+ *   row_index    (batch, max_seqlen) int32, stride idx_batch: table row of every cached position; entry L_b is written
+ *                with new_row[b].  Rows are clamped as unsigned values to table_rows - 1 (as bp_sense_mix_gather)
+ *   new_row      (batch) int32 table row of the new position
+ *   cache_seqlens  as in bp_flash_decode
+ *   out          (batch, d_out) 16-bit, batch stride o_batch, last stride 1
+ *   ws           fp32 workspace of ws_floats >= bp_sense_decode_ws_floats(batch, nsenses, d_out, max_seqlen) elements
+ * A separate softmax per sense, fp32 accumulation, split over the keys with a fixed-order combine (no (batch, nsenses, t)
+ * weight tensor in memory, bit-identical across calls).  1 <= nsenses <= 64, d_k % 8 == 0 and <= 640 (BP_ERR_HEAD_DIM),
+ * d_out >= 1 (BP_ERR_DOUT), d_out % 8 == 0 and <= 2048, 16-byte aligned bases, strides multiples of 8 (BP_ERR_SHAPE).
+ */
+int64_t bp_sense_decode_ws_floats(int batch, int nsenses, int d_out, int max_seqlen);
+int bp_sense_decode(const void *q, const void *k_new, void *k_cache, const void *table, int32_t *row_index,
+                    const int32_t *new_row, const int32_t *cache_seqlens, void *out, float *ws, int64_t ws_floats,
+                    int batch, int nsenses, int d_k, int d_out, int max_seqlen, int64_t table_rows,
+                    int64_t q_batch_stride, int64_t q_sense_stride,
+                    int64_t knew_batch_stride, int64_t knew_sense_stride,
+                    int64_t kc_batch_stride, int64_t kc_row_stride, int64_t kc_sense_stride,
+                    int64_t t_row_stride, int64_t t_sense_stride, int64_t idx_batch_stride,
+                    int64_t o_batch_stride, float softmax_scale, int dtype, bp_stream_t stream);
 
 #ifdef __cplusplus
 }
