@@ -137,6 +137,14 @@ def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _call(name, device, *args):
+    """Entry point `name` of the library on `device`: the current stream is read inside the device context (that
+    device's stream) and appended to `args`; a failure code raises."""
+    with torch.cuda.device(device):
+        code = getattr(lib(), name)(*args, _stream())
+    _check(code, name)
+
+
 def _require_cuda(*tensors):
     for t in tensors:
         if t is not None and not t.is_cuda:
@@ -212,18 +220,16 @@ def flash_fwd(q, k, v, out, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen
     # legal, as in the reference's mha_fwd, which only reads the offsets.)
     lse_len = round_up(max_seqlen_q, 16)
     lse = torch.empty((batch, nheads, lse_len), dtype=torch.float32, device=q.device)
-    with torch.cuda.device(q.device):
-        code = lib().bp_flash_fwd_dropout(
-            q.data_ptr(), k.data_ptr(), v.data_ptr() if v is not None else None,
-            out.data_ptr() if out is not None else None, lse.data_ptr(),
-            cu_seqlens_q.data_ptr() if cu_seqlens_q is not None else None,
-            cu_seqlens_k.data_ptr() if cu_seqlens_k is not None else None,
-            batch, nheads, d, int(max_seqlen_q), int(max_seqlen_k),
-            q.stride(0), q.stride(1), k.stride(0), k.stride(1),
-            v.stride(0) if v is not None else 0, v.stride(1) if v is not None else 0,
-            out.stride(0) if out is not None else 0, out.stride(1) if out is not None else 0,
-            lse_len, float(softmax_scale), int(bool(causal)), _dtype_code(q), dropout_p, rng_ptr, _stream())
-    _check(code, 'bp_flash_fwd_dropout')
+    _call('bp_flash_fwd_dropout', q.device,
+          q.data_ptr(), k.data_ptr(), v.data_ptr() if v is not None else None,
+          out.data_ptr() if out is not None else None, lse.data_ptr(),
+          cu_seqlens_q.data_ptr() if cu_seqlens_q is not None else None,
+          cu_seqlens_k.data_ptr() if cu_seqlens_k is not None else None,
+          batch, nheads, d, int(max_seqlen_q), int(max_seqlen_k),
+          q.stride(0), q.stride(1), k.stride(0), k.stride(1),
+          v.stride(0) if v is not None else 0, v.stride(1) if v is not None else 0,
+          out.stride(0) if out is not None else 0, out.stride(1) if out is not None else 0,
+          lse_len, float(softmax_scale), int(bool(causal)), _dtype_code(q), dropout_p, rng_ptr)
     return lse
 
 
@@ -288,18 +294,16 @@ def flash_bwd(dout, q, k, v, out, softmax_lse, dq, dk, dv, cu_seqlens_q, cu_seql
     # workspace for the row statistics -D_i = -sum_d dO_i[d] * O_i[d] and -L_i / scale (filled by the dQ kernel, read
     # by the dK/dV kernel)
     dsum = torch.empty(int(lib().bp_flash_bwd_ws_floats(batch, nheads, lse_len)), dtype=torch.float32, device=q.device)
-    with torch.cuda.device(q.device):
-        code = lib().bp_flash_bwd_dropout(
-            dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
-            softmax_lse.data_ptr(), dsum.data_ptr(), dsum.numel(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
-            cu_seqlens_q.data_ptr() if cu_seqlens_q is not None else None,
-            cu_seqlens_k.data_ptr() if cu_seqlens_k is not None else None,
-            batch, nheads, d, int(max_seqlen_q), int(max_seqlen_k),
-            dout.stride(0), dout.stride(1), q.stride(0), q.stride(1), k.stride(0), k.stride(1),
-            v.stride(0), v.stride(1), out.stride(0), out.stride(1), dq.stride(0), dq.stride(1),
-            dk.stride(0), dk.stride(1), dv.stride(0), dv.stride(1), lse_len, float(softmax_scale),
-            int(bool(causal)), _dtype_code(q), dropout_p, rng_ptr, _stream())
-    _check(code, 'bp_flash_bwd_dropout')
+    _call('bp_flash_bwd_dropout', q.device,
+          dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
+          softmax_lse.data_ptr(), dsum.data_ptr(), dsum.numel(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
+          cu_seqlens_q.data_ptr() if cu_seqlens_q is not None else None,
+          cu_seqlens_k.data_ptr() if cu_seqlens_k is not None else None,
+          batch, nheads, d, int(max_seqlen_q), int(max_seqlen_k),
+          dout.stride(0), dout.stride(1), q.stride(0), q.stride(1), k.stride(0), k.stride(1),
+          v.stride(0), v.stride(1), out.stride(0), out.stride(1), dq.stride(0), dq.stride(1),
+          dk.stride(0), dk.stride(1), dv.stride(0), dv.stride(1), lse_len, float(softmax_scale),
+          int(bool(causal)), _dtype_code(q), dropout_p, rng_ptr)
     return dq, dk, dv
 
 
@@ -316,13 +320,11 @@ def attn_probs(q, k, lse, softmax_scale, causal, dropout_p=0.0, rng_state=None):
     if q.stride(-1) != 1 or k.stride(-1) != 1 or not lse.is_contiguous():
         raise RuntimeError('bp_hip.attn_probs: bad strides')
     probs = torch.empty((b, h, sq, sk), dtype=q.dtype, device=q.device)
-    with torch.cuda.device(q.device):
-        code = lib().bp_attn_probs_dropout(
-            q.data_ptr(), k.data_ptr(), lse.data_ptr(), probs.data_ptr(), b, h, d, sq, sk,
-            q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1), k.stride(2),
-            lse.shape[-1], probs.stride(0), probs.stride(1), probs.stride(2),
-            float(softmax_scale), int(bool(causal)), _dtype_code(q), dropout_p, rng_ptr, _stream())
-    _check(code, 'bp_attn_probs_dropout')
+    _call('bp_attn_probs_dropout', q.device,
+          q.data_ptr(), k.data_ptr(), lse.data_ptr(), probs.data_ptr(), b, h, d, sq, sk,
+          q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1), k.stride(2),
+          lse.shape[-1], probs.stride(0), probs.stride(1), probs.stride(2),
+          float(softmax_scale), int(bool(causal)), _dtype_code(q), dropout_p, rng_ptr)
     return probs
 
 
@@ -342,30 +344,30 @@ def _check_qk(qk):
     return qk.shape[0], qk.shape[1], qk.shape[3], qk.shape[4]
 
 
-def _vector_friendly_qk(qk):
-    """The LDS-DMA kernels move 16-byte chunks, i.e. need d_k % 8 == 0.  The Mini k=64 ablation has
-    d_k = 10 (training/configs/experiment/owt/backpack-mini-flash-vecs-64.yaml): zero-pad the head
-    dimension to the next multiple of 8 (zeros add nothing to q.k) instead of falling to the
-    element-wise loader.  Returns (qk', true d_k) -- callers keep scaling by the TRUE d_k."""
-    dk = qk.shape[-1]
-    if dk % 8 == 0:
-        return qk, dk
-    pad = (-dk) % 8
-    return torch.nn.functional.pad(qk, (0, pad)), dk
+def _vec16(*tensors):
+    """16-byte friendly layouts: 16-byte aligned bases, a unit last stride and every other stride a multiple of 8."""
+    return all(t.data_ptr() % 16 == 0 and t.stride(-1) == 1 and all(s % 8 == 0 for s in t.stride()[:-1])
+               for t in tensors)
+
+
+def _sense_qk(qk, softmax_scale):
+    """The preamble of the sense wrappers: (qk', b, s, k, d_k', scale), the scale defaulting to the TRUE d_k's.  The
+    LDS-DMA kernels move 16-byte chunks, i.e. need d_k % 8 == 0.  The Mini k=64 ablation has d_k = 10
+    (training/configs/experiment/owt/backpack-mini-flash-vecs-64.yaml): qk' zero-pads the head dimension to the next
+    multiple of 8, d_k' (zeros add nothing to q.k), instead of falling to the element-wise loader."""
+    b, s, k, dk = _check_qk(qk)
+    scale = softmax_scale or dk ** -0.5
+    if dk % 8:
+        qk = torch.nn.functional.pad(qk, (0, (-dk) % 8))
+    return qk, b, s, k, qk.shape[-1], scale
 
 
 def sense_lse(qk, softmax_scale=None):
     """qk (B,S,2,k,d_k) -> lse (B,k,roundup(S,16)) fp32: log-sum-exp of every causal row."""
-    b, s, k, dk = _check_qk(qk)
-    scale = softmax_scale or dk ** -0.5
-    qk, _ = _vector_friendly_qk(qk)
-    dk = qk.shape[-1]
+    qk, b, s, k, dk, scale = _sense_qk(qk, softmax_scale)
     lse = torch.empty((b, k, round_up(s, 16)), dtype=torch.float32, device=qk.device)
-    with torch.cuda.device(qk.device):
-        code = lib().bp_sense_lse(qk.data_ptr(), lse.data_ptr(), b, s, k, dk,
-                                  qk.stride(0), qk.stride(1), qk.stride(2), qk.stride(3),
-                                  float(scale), _dtype_code(qk), _stream())
-    _check(code, 'bp_sense_lse')
+    _call('bp_sense_lse', qk.device, qk.data_ptr(), lse.data_ptr(), b, s, k, dk,
+          qk.stride(0), qk.stride(1), qk.stride(2), qk.stride(3), float(scale), _dtype_code(qk))
     return lse
 
 
@@ -380,17 +382,11 @@ def _lse_ws(qk, lse, b, s, k):
 def sense_alpha(qk, softmax_scale=None, lse=None):
     """qk (B,S,2,k,d_k) -> alpha (B,k,S,S), causal softmax over keys, exact zeros above the
     diagonal (replaces backpack.py:116-122).  `lse`: optional result of sense_lse(qk)."""
-    b, s, k, dk = _check_qk(qk)
-    scale = softmax_scale or dk ** -0.5
-    qk, _ = _vector_friendly_qk(qk)
-    dk = qk.shape[-1]
+    qk, b, s, k, dk, scale = _sense_qk(qk, softmax_scale)
     alpha = torch.empty((b, k, s, s), dtype=qk.dtype, device=qk.device)
     ws, ready = _lse_ws(qk, lse, b, s, k)
-    with torch.cuda.device(qk.device):
-        code = lib().bp_sense_alpha(qk.data_ptr(), alpha.data_ptr(), ws.data_ptr(), ready, b, s, k, dk,
-                                    qk.stride(0), qk.stride(1), qk.stride(2), qk.stride(3),
-                                    float(scale), _dtype_code(qk), _stream())
-    _check(code, 'bp_sense_alpha')
+    _call('bp_sense_alpha', qk.device, qk.data_ptr(), alpha.data_ptr(), ws.data_ptr(), ready, b, s, k, dk,
+          qk.stride(0), qk.stride(1), qk.stride(2), qk.stride(3), float(scale), _dtype_code(qk))
     return alpha
 
 
@@ -403,16 +399,13 @@ def sense_mix(qk, content, softmax_scale=None, out=None, lse=None, key_weight=No
     key_weight (B,k,S), optional: alpha[b,l,:,s] (= content row s of sense l) is scaled by
     key_weight[b,l,s] inside the kernel -- the intervention hook of intervened_models.py:97-101 and
     test_genderbias.py:71-78 (C ABI bp_sense_mix_weighted)."""
-    b, s, k, dk = _check_qk(qk)
+    qk, b, s, k, dk, scale = _sense_qk(qk, softmax_scale)
     _require_cuda(content)
     if content.dim() != 4 or content.shape[:3] != (b, s, k) or content.stride(-1) != 1:
         raise RuntimeError('bp_hip.sense_mix: content must be (B, S, k, d_out), last dim contiguous')
     if content.dtype != qk.dtype:
         raise RuntimeError('bp_hip.sense_mix: qk and content dtypes differ')
     dout = content.shape[3]
-    scale = softmax_scale or dk ** -0.5
-    qk, _ = _vector_friendly_qk(qk)
-    dk = qk.shape[-1]
     if out is None:
         out = torch.empty((b, s, dout), dtype=qk.dtype, device=qk.device)
     ws, ready = _lse_ws(qk, lse, b, s, k)
@@ -425,16 +418,13 @@ def sense_mix(qk, content, softmax_scale=None, out=None, lse=None, key_weight=No
         if kw.stride(-1) != 1:
             kw = kw.contiguous()
     queue_ws = _queue_ws(qk.device)   # alive until the launch call has returned (stream-ordered reuse afterwards)
-    with torch.cuda.device(qk.device):
-        code = lib().bp_sense_mix_weighted(
-            qk.data_ptr(), content.data_ptr(), kw.data_ptr() if kw is not None else None, out.data_ptr(),
-            ws.data_ptr(), ready, b, s, k, dk, dout,
-            qk.stride(0), qk.stride(1), qk.stride(2), qk.stride(3),
-            content.stride(0), content.stride(1), content.stride(2),
-            kw.stride(0) if kw is not None else 0, kw.stride(1) if kw is not None else 0,
-            out.stride(0), out.stride(1), float(scale), _dtype_code(qk), queue_ws.data_ptr(), _stream())
-    del queue_ws
-    _check(code, 'bp_sense_mix_weighted')
+    _call('bp_sense_mix_weighted', qk.device,
+          qk.data_ptr(), content.data_ptr(), kw.data_ptr() if kw is not None else None, out.data_ptr(),
+          ws.data_ptr(), ready, b, s, k, dk, dout,
+          qk.stride(0), qk.stride(1), qk.stride(2), qk.stride(3),
+          content.stride(0), content.stride(1), content.stride(2),
+          kw.stride(0) if kw is not None else 0, kw.stride(1) if kw is not None else 0,
+          out.stride(0), out.stride(1), float(scale), _dtype_code(qk), queue_ws.data_ptr())
     return out
 
 
@@ -444,44 +434,36 @@ SENSE_MAX_DK = 640     # widest sense bp_sense_lse / _alpha / _mix take (include
 WIDE_RING_DK = (160, 640)   # sense widths beyond 128 the LDS-DMA ring kernels take (csrc/sense_wide_dma.hip), with S % 32 == 0
 
 
-def _wide_ring_takes(dk, seqlen):
-    return dk in WIDE_RING_DK and seqlen % 32 == 0
+def _gather_limits(qk, table, seqlen):
+    """(exceeded, reason) of every limit of bp_sense_mix_gather (include/bp_hip.h): the 16-byte vector path, seqlen <= 4096,
+    32-bit byte offsets into the table; senses up to 128 wide with at most 65 536 table rows (any GPT-2 vocabulary), or the
+    reference's two few-sense widths (WIDE_RING_DK, seqlen a multiple of 32: the ring kernels of csrc/sense_wide_dma.hip,
+    any row count)."""
+    dk = round_up(qk.shape[-1], 8)
+    wide = dk > 128
+    rows = table.shape[0]
+    return (
+        (wide and not (dk in WIDE_RING_DK and seqlen % 32 == 0),
+         f'sense width {qk.shape[-1]} > 128 and not {WIDE_RING_DK} at a sequence length that is a multiple of 32 '
+         '(those senses take the dense kernel)'),
+        (seqlen > 4096, f'sequence length {seqlen} > 4096 (a job keeps its keys\' row indices in LDS)'),
+        (not wide and rows > 65536, f'{rows} table rows > 65536 (u16 row indices)'),
+        (rows * table.stride(0) * table.element_size() >= 2 ** 32, 'table of 4 GiB or more (32-bit byte offsets)'),
+        (not (qk.is_cuda and table.is_cuda), 'qk or table not on the GPU'),
+        (table.dim() != 3 or table.shape[2] % 8 != 0 or not _vec16(table),
+         'table layout (last dim contiguous, 16-byte aligned rows, d % 8 == 0 required)'),
+        (wide and not _vec16(qk), 'qk layout (senses wider than 128 need 16-byte aligned rows)'),
+    )
 
 
 def sense_mix_gather_supported(qk, table, seqlen):
-    """Shapes bp_sense_mix_gather takes (include/bp_hip.h): the 16-byte vector path, seqlen <= 4096, 32-bit byte offsets into
-    the table; senses up to 128 wide with at most 65 536 table rows (any GPT-2 vocabulary), or the reference's two few-sense
-    widths (160 / 640, seqlen a multiple of 32: the ring kernels of csrc/sense_wide_dma.hip, any row count)."""
-    dk = round_up(qk.shape[-1], 8)
-    wide = dk > 128
-    return ((dk <= 128 or _wide_ring_takes(dk, seqlen)) and qk.is_cuda and table.is_cuda and table.dim() == 3
-            and table.stride(-1) == 1 and table.shape[2] % 8 == 0
-            and table.stride(0) % 8 == 0 and table.stride(1) % 8 == 0 and table.data_ptr() % 16 == 0
-            and seqlen <= 4096 and (wide or table.shape[0] <= 65536)
-            and (not wide or _vector_friendly_strides(qk))
-            and table.shape[0] * table.stride(0) * table.element_size() < 2 ** 32)
-
-
-def _vector_friendly_strides(qk):
-    return qk.data_ptr() % 16 == 0 and all(st % 8 == 0 for st in qk.stride()[:4])
+    """Shapes bp_sense_mix_gather takes: those that exceed none of its limits (_gather_limits)."""
+    return not any(exceeded for exceeded, _ in _gather_limits(qk, table, seqlen))
 
 
 def sense_mix_gather_limits(qk, table, seqlen):
-    """Which limit of bp_sense_mix_gather a call exceeds, as text (callers log it when they fall back to a torch gather)."""
-    why = []
-    dk = round_up(qk.shape[-1], 8)
-    if dk > 128 and not _wide_ring_takes(dk, seqlen):
-        why.append(f'sense width {qk.shape[-1]} > 128 and not {WIDE_RING_DK} at a sequence length that is a multiple of 32 '
-                   '(those senses take the dense kernel)')
-    if seqlen > 4096:
-        why.append(f'sequence length {seqlen} > 4096 (a job keeps its keys\' row indices in LDS)')
-    if table.shape[0] > 65536 and dk <= 128:
-        why.append(f'{table.shape[0]} table rows > 65536 (u16 row indices)')
-    if table.shape[0] * table.stride(0) * table.element_size() >= 2 ** 32:
-        why.append('table of 4 GiB or more (32-bit byte offsets)')
-    if not why:
-        why.append('table layout (last dim contiguous, 16-byte aligned rows, d % 8 == 0 required)')
-    return '; '.join(why)
+    """Which limits of bp_sense_mix_gather a call exceeds, as text (callers log it when they fall back to a torch gather)."""
+    return '; '.join(reason for exceeded, reason in _gather_limits(qk, table, seqlen) if exceeded)
 
 
 def sense_mix_gather(qk, table, row_index, softmax_scale=None, out=None, lse=None):
@@ -490,7 +472,7 @@ def sense_mix_gather(qk, table, row_index, softmax_scale=None, out=None, lse=Non
     qk (B,S,2,k,d_k); table (rows, k, d_out), e.g. the content network's output for the distinct tokens of the batch;
     row_index (B,S) int32 (torch.unique's inverse); returns (B,S,d_out).  The (B,S,k,d_out) content tensor of
     backpack.py:276 is never materialised (C ABI bp_sense_mix_gather)."""
-    b, s, k, dk = _check_qk(qk)
+    qk, b, s, k, dk, scale = _sense_qk(qk, softmax_scale)
     _require_cuda(table, row_index)
     if table.dim() != 3 or table.shape[1] != k or table.stride(-1) != 1:
         raise RuntimeError('bp_hip.sense_mix_gather: table must be (rows, k, d_out), last dim contiguous')
@@ -499,22 +481,16 @@ def sense_mix_gather(qk, table, row_index, softmax_scale=None, out=None, lse=Non
     if row_index.shape != (b, s) or row_index.dtype != torch.int32 or row_index.stride(-1) != 1:
         raise RuntimeError('bp_hip.sense_mix_gather: row_index must be (B, S) int32, unit stride along S')
     dout = table.shape[2]
-    scale = softmax_scale or dk ** -0.5
-    qk, _ = _vector_friendly_qk(qk)
-    dk = qk.shape[-1]
     if out is None:
         out = torch.empty((b, s, dout), dtype=qk.dtype, device=qk.device)
     ws, ready = _lse_ws(qk, lse, b, s, k)
     queue_ws = _queue_ws(qk.device)   # alive until the launch call has returned
-    with torch.cuda.device(qk.device):
-        code = lib().bp_sense_mix_gather(
-            qk.data_ptr(), table.data_ptr(), row_index.data_ptr(), out.data_ptr(), ws.data_ptr(), ready,
-            b, s, k, dk, dout, table.shape[0],
-            qk.stride(0), qk.stride(1), qk.stride(2), qk.stride(3),
-            table.stride(0), table.stride(1), row_index.stride(0),
-            out.stride(0), out.stride(1), float(scale), _dtype_code(qk), queue_ws.data_ptr(), _stream())
-    del queue_ws
-    _check(code, 'bp_sense_mix_gather')
+    _call('bp_sense_mix_gather', qk.device,
+          qk.data_ptr(), table.data_ptr(), row_index.data_ptr(), out.data_ptr(), ws.data_ptr(), ready,
+          b, s, k, dk, dout, table.shape[0],
+          qk.stride(0), qk.stride(1), qk.stride(2), qk.stride(3),
+          table.stride(0), table.stride(1), row_index.stride(0),
+          out.stride(0), out.stride(1), float(scale), _dtype_code(qk), queue_ws.data_ptr())
     return out
 
 
@@ -586,16 +562,14 @@ def add_layer_norm(x0, x1, weight, bias, eps, residual_dtype=None, return_residu
     rows = x0c.numel() // cols
     wc, bc = weight.contiguous(), bias.contiguous()
     rowscale, colscale = _ln_scales(x0c, weight, rowscale, colscale)
-    with torch.cuda.device(x0.device):
-        code = lib().bp_dropout_add_layer_norm_scaled(
-            x0c.data_ptr(), x1c.data_ptr() if x1c is not None else None, wc.data_ptr(), bc.data_ptr(),
-            rowscale.data_ptr() if rowscale is not None else None,
-            colscale.data_ptr() if colscale is not None else None,
-            z.data_ptr(), xo.data_ptr() if xo is not None else None,
-            dmask.data_ptr() if (dmask is not None and dropout_p > 0.0) else None, rows, cols, float(eps), code_dt,
-            int(x0_f32), int(x1c is not None and x1c.dtype == torch.float32), int(residual_dtype == torch.float32),
-            int(weight.dtype == torch.float32), dropout_p, rng_ptr, _stream())
-    _check(code, 'bp_dropout_add_layer_norm_scaled')
+    _call('bp_dropout_add_layer_norm_scaled', x0.device,
+          x0c.data_ptr(), x1c.data_ptr() if x1c is not None else None, wc.data_ptr(), bc.data_ptr(),
+          rowscale.data_ptr() if rowscale is not None else None,
+          colscale.data_ptr() if colscale is not None else None,
+          z.data_ptr(), xo.data_ptr() if xo is not None else None,
+          dmask.data_ptr() if (dmask is not None and dropout_p > 0.0) else None, rows, cols, float(eps), code_dt,
+          int(x0_f32), int(x1c is not None and x1c.dtype == torch.float32), int(residual_dtype == torch.float32),
+          int(weight.dtype == torch.float32), dropout_p, rng_ptr)
     outs = (z, xo) if return_residual else (z,)
     if return_dropout_mask:
         outs = outs + (dmask,)
@@ -615,10 +589,8 @@ def softmax_bwd_causal_(alpha, dalpha, softmax_scale):
             or not dalpha.is_contiguous() or alpha.shape[-1] != alpha.shape[-2]:
         raise RuntimeError('bp_hip.softmax_bwd_causal_: alpha and dalpha must be equal-shaped contiguous (..., S, S)')
     s = alpha.shape[-1]
-    with torch.cuda.device(alpha.device):
-        code = lib().bp_softmax_bwd_causal(alpha.data_ptr(), dalpha.data_ptr(), alpha.numel() // (s * s), s,
-                                           float(softmax_scale), _dtype_code(alpha), _stream())
-    _check(code, 'bp_softmax_bwd_causal')
+    _call('bp_softmax_bwd_causal', alpha.device, alpha.data_ptr(), dalpha.data_ptr(), alpha.numel() // (s * s), s,
+          float(softmax_scale), _dtype_code(alpha))
     return dalpha
 
 
@@ -631,14 +603,11 @@ def sense_mix_dc(qk, dout, lse, softmax_scale, like):
     b, s, k, dk = _check_qk(qk)
     dcontent = torch.empty((b, s, k, like.shape[-1]), dtype=like.dtype, device=like.device)
     queue_ws = _queue_ws(qk.device)
-    with torch.cuda.device(qk.device):
-        code = lib().bp_sense_mix_dc(
-            qk.data_ptr(), dout.data_ptr(), lse.data_ptr(), dcontent.data_ptr(), b, s, k, dk, like.shape[-1],
-            qk.stride(0), qk.stride(1), qk.stride(2), qk.stride(3), dout.stride(0), dout.stride(1),
-            dcontent.stride(0), dcontent.stride(1), dcontent.stride(2), float(softmax_scale), _dtype_code(qk),
-            queue_ws.data_ptr(), _stream())
-    del queue_ws
-    _check(code, 'bp_sense_mix_dc')
+    _call('bp_sense_mix_dc', qk.device,
+          qk.data_ptr(), dout.data_ptr(), lse.data_ptr(), dcontent.data_ptr(), b, s, k, dk, like.shape[-1],
+          qk.stride(0), qk.stride(1), qk.stride(2), qk.stride(3), dout.stride(0), dout.stride(1),
+          dcontent.stride(0), dcontent.stride(1), dcontent.stride(2), float(softmax_scale), _dtype_code(qk),
+          queue_ws.data_ptr())
     return dcontent
 
 
@@ -654,7 +623,7 @@ def sense_dqk(qk, content, dout, lse, softmax_scale):
     dk_acc = torch.zeros((b, s, k, dk), dtype=torch.float32, device=qk.device)
     dsum = torch.empty((b, k, round_up(s, 16)), dtype=torch.float32, device=qk.device)
     buf = torch.empty(b * s * k * SLAB, dtype=qk.dtype, device=qk.device)
-    code_dt, stream = _dtype_code(qk), _stream()
+    code_dt = _dtype_code(qk)
     for t0 in range(0, s, SLAB):
         n = min(s, t0 + SLAB) * k
         rows = dout[:, t0:t0 + SLAB]
@@ -662,13 +631,11 @@ def sense_dqk(qk, content, dout, lse, softmax_scale):
             rows = torch.nn.functional.pad(rows, (0, 0, 0, SLAB - rows.shape[1]))
         dpt = buf[:b * n * SLAB].view(b, n, SLAB)
         torch.bmm(c_flat[:, :n], rows.transpose(1, 2), out=dpt)
-        with torch.cuda.device(qk.device):
-            code = lib().bp_sense_dq_dk(
-                qk.data_ptr(), dpt.data_ptr(), lse.data_ptr(), dsum.data_ptr(), dqk.data_ptr(), dk_acc.data_ptr(),
-                b, s, k, dk, t0, qk.stride(0), qk.stride(1), qk.stride(2), qk.stride(3), dpt.stride(0),
-                dqk.stride(0), dqk.stride(1), dqk.stride(3), dk_acc.stride(0), dk_acc.stride(1), dk_acc.stride(2),
-                float(softmax_scale), code_dt, stream)
-        _check(code, 'bp_sense_dq_dk')
+        _call('bp_sense_dq_dk', qk.device,
+              qk.data_ptr(), dpt.data_ptr(), lse.data_ptr(), dsum.data_ptr(), dqk.data_ptr(), dk_acc.data_ptr(),
+              b, s, k, dk, t0, qk.stride(0), qk.stride(1), qk.stride(2), qk.stride(3), dpt.stride(0),
+              dqk.stride(0), dqk.stride(1), dqk.stride(3), dk_acc.stride(0), dk_acc.stride(1), dk_acc.stride(2),
+              float(softmax_scale), code_dt)
     dqk[:, :, 1] = dk_acc
     return dqk
 
@@ -735,17 +702,23 @@ def _sense_mix_backward_rebuild(ctx, qk, content, lse, key_weight, dout):
         dalpha = torch.matmul(g, content.permute(0, 2, 3, 1))                  # (B,k,S_t,S_s)
         if key_weight is not None:
             dalpha = dalpha * key_weight.unsqueeze(2).to(dalpha.dtype)
-        dalpha = dalpha.contiguous()
-        if softmax_bwd_causal_supported(alpha):
-            ds = softmax_bwd_causal_(alpha, dalpha, ctx.scale)
-        else:
-            a32, d32 = alpha.float(), dalpha.float()
-            ds = (ctx.scale * a32 * (d32 - (a32 * d32).sum(-1, keepdim=True))).to(alpha.dtype)
-        q, kk = qk[:, :, 0].transpose(1, 2), qk[:, :, 1].transpose(1, 2)       # (B,k,S,dk)
-        dq = torch.matmul(ds, kk)
-        dkk = torch.matmul(ds.transpose(2, 3), q)
-        dqk = torch.stack([dq.transpose(1, 2), dkk.transpose(1, 2)], dim=2)   # (B,S,2,k,dk)
+        dqk = _scores_backward(qk, alpha, dalpha.contiguous(), ctx.scale)
     return dqk, dcontent, None, None
+
+
+def _scores_backward(qk, alpha, dalpha, scale):
+    """dqk (B,S,2,k,dk) from alpha (B,k,S,S) and its gradient dalpha (contiguous, overwritten): the causal softmax
+    backward (bp_softmax_bwd_causal in place, an fp32 torch expression for shapes it does not take), then dq = dS k and
+    dk = dS^T q."""
+    if softmax_bwd_causal_supported(alpha):
+        ds = softmax_bwd_causal_(alpha, dalpha, scale)
+    else:
+        a32, d32 = alpha.float(), dalpha.float()
+        ds = (scale * a32 * (d32 - (a32 * d32).sum(-1, keepdim=True))).to(alpha.dtype)
+    q, kk = qk[:, :, 0].transpose(1, 2), qk[:, :, 1].transpose(1, 2)       # (B,k,S,dk)
+    dq = torch.matmul(ds, kk)
+    dkk = torch.matmul(ds.transpose(2, 3), q)
+    return torch.stack([dq.transpose(1, 2), dkk.transpose(1, 2)], dim=2)
 
 
 def sense_mix_autograd(qk, content, softmax_scale=None, key_weight=None):
@@ -769,16 +742,7 @@ class SenseAlphaFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dalpha):
         qk, alpha = ctx.saved_tensors
-        dalpha = dalpha.contiguous().clone()
-        if softmax_bwd_causal_supported(alpha):
-            ds = softmax_bwd_causal_(alpha, dalpha, ctx.scale)
-        else:
-            a32, d32 = alpha.float(), dalpha.float()
-            ds = (ctx.scale * a32 * (d32 - (a32 * d32).sum(-1, keepdim=True))).to(alpha.dtype)
-        q, kk = qk[:, :, 0].transpose(1, 2), qk[:, :, 1].transpose(1, 2)
-        dq = torch.matmul(ds, kk)
-        dkk = torch.matmul(ds.transpose(2, 3), q)
-        return torch.stack([dq.transpose(1, 2), dkk.transpose(1, 2)], dim=2), None
+        return _scores_backward(qk, alpha, dalpha.contiguous().clone(), ctx.scale), None
 
 
 def sense_alpha_autograd(qk, softmax_scale=None):
@@ -824,16 +788,14 @@ def add_layer_norm_bwd(dz, dx_in, x, weight, eps, want_dx1, dropout_p=0.0, rng_s
     dw, db = torch.empty_like(weight), torch.empty_like(weight)
     dcs = torch.empty_like(weight) if colscale is not None else None
     ws = torch.empty(int(lib().bp_ln_bwd_ws_floats(cols, int(colscale is not None))), dtype=torch.float32, device=dz.device)
-    with torch.cuda.device(dz.device):
-        code = lib().bp_dropout_add_layer_norm_scaled_bwd(
-            dzc.data_ptr(), dxc.data_ptr() if dxc is not None else None, xc.data_ptr(),
-            x0c.data_ptr() if x0c is not None else None, weight.data_ptr(),
-            rowscale.data_ptr() if rowscale is not None else None, colscale.data_ptr() if colscale is not None else None,
-            dx0.data_ptr(), dx1.data_ptr() if dx1 is not None else None, dw.data_ptr(), db.data_ptr(),
-            dcs.data_ptr() if dcs is not None else None, ws.data_ptr(), ws.numel(), rows, cols, float(eps), code_dt,
-            int(dzc.dtype == torch.float32), int(xc.dtype == torch.float32), int(weight.dtype == torch.float32),
-            dropout_p, rng_ptr, _stream())
-    _check(code, 'bp_dropout_add_layer_norm_scaled_bwd')
+    _call('bp_dropout_add_layer_norm_scaled_bwd', dz.device,
+          dzc.data_ptr(), dxc.data_ptr() if dxc is not None else None, xc.data_ptr(),
+          x0c.data_ptr() if x0c is not None else None, weight.data_ptr(),
+          rowscale.data_ptr() if rowscale is not None else None, colscale.data_ptr() if colscale is not None else None,
+          dx0.data_ptr(), dx1.data_ptr() if dx1 is not None else None, dw.data_ptr(), db.data_ptr(),
+          dcs.data_ptr() if dcs is not None else None, ws.data_ptr(), ws.numel(), rows, cols, float(eps), code_dt,
+          int(dzc.dtype == torch.float32), int(xc.dtype == torch.float32), int(weight.dtype == torch.float32),
+          dropout_p, rng_ptr)
     return (dx0, dx1, dw, db) if colscale is None else (dx0, dx1, dw, db, dcs)
 
 
@@ -854,11 +816,8 @@ def xentropy_fwd(logits, labels, smoothing=0.0, total_classes=-1):
     rows, cols = logits.shape
     losses = torch.empty(rows, dtype=torch.float32, device=logits.device)
     lse = torch.empty(rows, dtype=torch.float32, device=logits.device)
-    with torch.cuda.device(logits.device):
-        code = lib().bp_xentropy_fwd(logits.data_ptr(), labels.data_ptr(), losses.data_ptr(), lse.data_ptr(),
-                                     rows, cols, logits.stride(0), float(smoothing), int(total_classes),
-                                     _xent_dtype(logits), _stream())
-    _check(code, 'bp_xentropy_fwd')
+    _call('bp_xentropy_fwd', logits.device, logits.data_ptr(), labels.data_ptr(), losses.data_ptr(), lse.data_ptr(),
+          rows, cols, logits.stride(0), float(smoothing), int(total_classes), _xent_dtype(logits))
     return losses, lse
 
 
@@ -870,11 +829,9 @@ def xentropy_bwd(grad_losses, logits, lse, labels, smoothing=0.0, inplace=False,
     grad = logits if inplace else torch.empty_like(logits)
     g = grad_losses.to(torch.float32).contiguous()
     labels = labels.to(torch.int64).contiguous()
-    with torch.cuda.device(logits.device):
-        code = lib().bp_xentropy_bwd(g.data_ptr(), logits.data_ptr(), lse.data_ptr(), labels.data_ptr(),
-                                     grad.data_ptr(), rows, cols, logits.stride(0), grad.stride(0),
-                                     float(smoothing), int(total_classes), _xent_dtype(logits), _stream())
-    _check(code, 'bp_xentropy_bwd')
+    _call('bp_xentropy_bwd', logits.device, g.data_ptr(), logits.data_ptr(), lse.data_ptr(), labels.data_ptr(),
+          grad.data_ptr(), rows, cols, logits.stride(0), grad.stride(0), float(smoothing), int(total_classes),
+          _xent_dtype(logits))
     return grad
 
 
@@ -899,11 +856,8 @@ def bias_gelu_fwd(x, bias=None, save_pre=False, out=None):
         raise RuntimeError('bp_hip.bias_gelu_fwd: bias must be a contiguous (cols,) tensor of x\'s dtype')
     y = torch.empty_like(x) if out is None else out
     pre = torch.empty_like(x) if (save_pre and bias is not None) else None
-    with torch.cuda.device(x.device):
-        code = lib().bp_bias_gelu_fwd(x.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                      pre.data_ptr() if pre is not None else None, y.data_ptr(), rows, cols,
-                                      _dtype_code(x), _stream())
-    _check(code, 'bp_bias_gelu_fwd')
+    _call('bp_bias_gelu_fwd', x.device, x.data_ptr(), bias.data_ptr() if bias is not None else None,
+          pre.data_ptr() if pre is not None else None, y.data_ptr(), rows, cols, _dtype_code(x))
     return y, (pre if pre is not None else (x if save_pre else None))
 
 
@@ -926,12 +880,9 @@ def bias_gelu_bwd(grad, pre, bias_grad_dtype=None, inplace=False):
             raise RuntimeError('bp_hip.bias_gelu_bwd: bias gradient dtype must be fp32 or grad\'s dtype')
         dbias = torch.empty(cols, dtype=bias_grad_dtype, device=grad.device)
         ws = _bias_grad_ws(rows, cols, grad.device)
-    with torch.cuda.device(grad.device):
-        code = lib().bp_bias_gelu_bwd(grad.data_ptr(), pre.data_ptr(), dpre.data_ptr(),
-                                      dbias.data_ptr() if dbias is not None else None,
-                                      ws.data_ptr() if ws is not None else None, rows, cols, _dtype_code(grad),
-                                      int(bias_grad_dtype == torch.float32), _stream())
-    _check(code, 'bp_bias_gelu_bwd')
+    _call('bp_bias_gelu_bwd', grad.device, grad.data_ptr(), pre.data_ptr(), dpre.data_ptr(),
+          dbias.data_ptr() if dbias is not None else None, ws.data_ptr() if ws is not None else None, rows, cols,
+          _dtype_code(grad), int(bias_grad_dtype == torch.float32))
     return dpre, dbias
 
 
@@ -945,10 +896,8 @@ def column_sum(grad, out_dtype=None):
         raise RuntimeError('bp_hip.column_sum: output dtype must be fp32 or grad\'s dtype')
     dbias = torch.empty(cols, dtype=out_dtype, device=grad.device)
     ws = _bias_grad_ws(rows, cols, grad.device)
-    with torch.cuda.device(grad.device):
-        code = lib().bp_column_sum(grad.data_ptr(), dbias.data_ptr(), ws.data_ptr(), rows, cols, _dtype_code(grad),
-                                   int(out_dtype == torch.float32), _stream())
-    _check(code, 'bp_column_sum')
+    _call('bp_column_sum', grad.device, grad.data_ptr(), dbias.data_ptr(), ws.data_ptr(), rows, cols, _dtype_code(grad),
+          int(out_dtype == torch.float32))
     return dbias
 
 
@@ -1013,11 +962,6 @@ def _decode_ws(floats, device):
     return torch.empty((max(int(floats), 4),), dtype=torch.float32, device=device)
 
 
-def _vec16(*tensors):
-    return all(t.data_ptr() % 16 == 0 and t.stride(-1) == 1 and all(s % 8 == 0 for s in t.stride()[:-1])
-               for t in tensors)
-
-
 def flash_decode_supported(q, kv_cache):
     """Whether bp_flash_decode takes these operands: 16-bit CUDA tensors, head_dim % 8 == 0 and <= 128, 16-byte
     friendly layouts (include/bp_hip.h)."""
@@ -1050,16 +994,13 @@ def flash_decode(q, k_new, v_new, kv_cache, cache_seqlens, softmax_scale=None, o
     if out is None:
         out = torch.empty((b, h, d), dtype=q.dtype, device=q.device)
     lse = torch.empty((b, h), dtype=torch.float32, device=q.device) if return_lse else None
-    with torch.cuda.device(q.device):
-        floats = lib().bp_flash_decode_ws_floats(b, h, d, max_s)
-        ws = _decode_ws(floats, q.device)
-        code = lib().bp_flash_decode(
-            q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(), kv_cache.data_ptr(), cache_seqlens.data_ptr(),
-            out.data_ptr(), lse.data_ptr() if lse is not None else None, ws.data_ptr(), ws.numel(),
-            b, h, d, max_s, q.stride(0), q.stride(1), k_new.stride(0), k_new.stride(1), v_new.stride(0), v_new.stride(1),
-            kv_cache.stride(0), kv_cache.stride(1), kv_cache.stride(2), kv_cache.stride(3),
-            out.stride(0), out.stride(1), h, float(scale), _dtype_code(q), _stream())
-    _check(code, 'bp_flash_decode')
+    ws = _decode_ws(lib().bp_flash_decode_ws_floats(b, h, d, max_s), q.device)
+    _call('bp_flash_decode', q.device,
+          q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(), kv_cache.data_ptr(), cache_seqlens.data_ptr(),
+          out.data_ptr(), lse.data_ptr() if lse is not None else None, ws.data_ptr(), ws.numel(),
+          b, h, d, max_s, q.stride(0), q.stride(1), k_new.stride(0), k_new.stride(1), v_new.stride(0), v_new.stride(1),
+          kv_cache.stride(0), kv_cache.stride(1), kv_cache.stride(2), kv_cache.stride(3),
+          out.stride(0), out.stride(1), h, float(scale), _dtype_code(q))
     return (out, lse) if return_lse else out
 
 
@@ -1108,14 +1049,11 @@ def sense_decode(q, k_new, k_cache, table, row_index, new_row, cache_seqlens, so
     scale = softmax_scale or dk ** -0.5
     if out is None:
         out = torch.empty((b, dout), dtype=q.dtype, device=q.device)
-    with torch.cuda.device(q.device):
-        floats = lib().bp_sense_decode_ws_floats(b, k, dout, max_s)
-        ws = _decode_ws(floats, q.device)
-        code = lib().bp_sense_decode(
-            q.data_ptr(), k_new.data_ptr(), k_cache.data_ptr(), table.data_ptr(), row_index.data_ptr(),
-            new_row.data_ptr(), cache_seqlens.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(),
-            b, k, dk, dout, max_s, table.shape[0], q.stride(0), q.stride(1), k_new.stride(0), k_new.stride(1),
-            k_cache.stride(0), k_cache.stride(1), k_cache.stride(2), table.stride(0), table.stride(1),
-            row_index.stride(0), out.stride(0), float(scale), _dtype_code(q), _stream())
-    _check(code, 'bp_sense_decode')
+    ws = _decode_ws(lib().bp_sense_decode_ws_floats(b, k, dout, max_s), q.device)
+    _call('bp_sense_decode', q.device,
+          q.data_ptr(), k_new.data_ptr(), k_cache.data_ptr(), table.data_ptr(), row_index.data_ptr(),
+          new_row.data_ptr(), cache_seqlens.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(),
+          b, k, dk, dout, max_s, table.shape[0], q.stride(0), q.stride(1), k_new.stride(0), k_new.stride(1),
+          k_cache.stride(0), k_cache.stride(1), k_cache.stride(2), table.stride(0), table.stride(1),
+          row_index.stride(0), out.stride(0), float(scale), _dtype_code(q))
     return out

@@ -4,8 +4,6 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include <initializer_list>
 
@@ -16,10 +14,27 @@
 namespace {
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+inline bool aligned16(std::initializer_list<const void *> ptrs) {
+    for (const void *p : ptrs)
+        if (!aligned16(p)) return false;
+    return true;
+}
+// optional operands: only the ones given (non-NULL) must be aligned
+inline bool aligned16_or_null(std::initializer_list<const void *> ptrs) {
+    for (const void *p : ptrs)
+        if (p != nullptr && !aligned16(p)) return false;
+    return true;
+}
 inline bool mult8(int64_t x) { return (x & 7) == 0; }
+inline bool strides8(std::initializer_list<int64_t> strides) {
+    for (int64_t s : strides)
+        if (!mult8(s)) return false;
+    return true;
+}
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 inline bool scale_ok(float s) { return isfinite(s) && s > 0.f; }
+inline int launch_status(hipError_t e) { return e == hipSuccess ? BP_OK : BP_ERR_LAUNCH; }
 
 // queue_ws == NULL means "a record of the library's own ring" (include/bp_hip.h).  A graph captured that way would
 // replay on a record every other NULL launch also cycles through, so it is refused instead of documented as unsafe.
@@ -47,28 +62,55 @@ inline bool dropout_args(float p, const uint64_t *rng_state, uint32_t &thr, floa
     return true;
 }
 
-// Measurement switches exist only in development builds (build_hip.py --variant NAME -- -DBP_DEV_BUILD):
-// the shipped library reads no environment variable.  BP_FLASH_IMPL=staged / BP_MIX_IMPL=staged force the
-// register-staged kernels for shapes the LDS-DMA ring kernels accept; BP_FLASH_PAIR=0 unpairs causal tiles.
-#ifdef BP_DEV_BUILD
-inline bool env_is(const char *name, const char *value) {
-    const char *e = getenv(name);
-    return e != nullptr && strcmp(e, value) == 0;
-}
-inline bool dev_force_staged_flash() { static const bool v = env_is("BP_FLASH_IMPL", "staged"); return v; }
-inline bool dev_force_staged_mix() { static const bool v = env_is("BP_MIX_IMPL", "staged"); return v; }
-inline bool dev_flash_pair() { static const bool v = !env_is("BP_FLASH_PAIR", "0"); return v; }
-#else
-inline bool dev_force_staged_flash() { return false; }
-inline bool dev_force_staged_mix() { return false; }
-inline bool dev_flash_pair() { return true; }
-#endif
-
 // 16-byte friendly shapes take the LDS-DMA ring kernel; anything else (odd head dims, unaligned
 // views) the register-staged kernel with its element-wise loader.
 inline hipError_t dispatch_flash(const bp::FlashParams &p, int dtype, bool vec, hipStream_t st) {
-    if (vec && !dev_force_staged_flash()) return bp::launch_flash_fwd_dma(p, dtype, st);
-    return bp::launch_flash_fwd(p, dtype, vec, st);
+    return vec ? bp::launch_flash_fwd_dma(p, dtype, st) : bp::launch_flash_fwd(p, dtype, false, st);
+}
+
+// The q and k halves of a (B, S, 2, k, d_k) qk operand are 16-byte friendly.
+inline bool qk_vec16(int d_k, const uint16_t *q, int64_t two_stride, int64_t bs, int64_t rs, int64_t ss) {
+    return d_k % 8 == 0 && aligned16({q, q + two_stride}) && strides8({bs, rs, ss});
+}
+
+// The kernel family of every sense entry point (LSE pre-pass, alpha, mix, gathering mix).  Senses up to 128 wide take
+// the narrow kernels (flash_fwd*.hip, attn_probs.hip, sense_mix*.hip), wider ones the wide kernels (sense_wide*.hip).
+// Within each, 16-byte friendly operands (vec_qk, vec_c) take the LDS-DMA ring kernel, anything else the
+// register-staged kernel with its element-wise loader; the wide ring kernels take the reference's two few-sense
+// configurations only (sense_wide_dma_takes).  d_out == 0: no content operand (the LSE pre-pass, alpha).  gather: the
+// gathering mix, which has no staged kernels (its caller refuses those shapes) and a tighter sequence limit of its own.
+enum class SenseKernel { NarrowRing, NarrowStaged, WideRing, WideStaged };
+
+inline SenseKernel sense_route(int d_k, int seqlen, int d_out, bool vec_qk, bool vec_c, bool weighted, bool gather) {
+    if (d_k > 128)
+        return bp::sense_wide_dma_takes(seqlen, d_k, d_out, vec_qk, vec_c, weighted) ? SenseKernel::WideRing
+                                                                                       : SenseKernel::WideStaged;
+    // the mix ring kernel numbers its jobs group * 256 + query tile: at most 256 tiles of 256 queries
+    const bool ring_fits = d_out == 0 || gather || seqlen <= 256 * 256;
+    return vec_qk && vec_c && ring_fits ? SenseKernel::NarrowRing : SenseKernel::NarrowStaged;
+}
+
+inline bool is_wide(SenseKernel k) { return k == SenseKernel::WideRing || k == SenseKernel::WideStaged; }
+
+// Parameters of the forward mix kernels; the weighted form adds key weights, the gathering form a row index.
+inline bp::MixParams mix_params(const void *qk, const void *content, void *out, float *lse_ws,
+                                int batch, int seqlen, int nsenses, int d_k, int d_out,
+                                int64_t qk_bs, int64_t qk_rs, int64_t qk_two, int64_t qk_ss,
+                                int64_t c_bs, int64_t c_rs, int64_t c_ss, int64_t o_bs, int64_t o_rs,
+                                float softmax_scale, void *queue_ws) {
+    const uint16_t *qp = static_cast<const uint16_t *>(qk);
+    bp::MixParams p{};
+    p.q = qp; p.k = qp + qk_two; p.c = content; p.o = out; p.lse = lse_ws;
+    p.qk_bs = qk_bs; p.qk_rs = qk_rs; p.qk_ss = qk_ss;
+    p.c_bs = c_bs; p.c_rs = c_rs; p.c_ss = c_ss;
+    p.o_bs = o_bs; p.o_rs = o_rs;
+    p.lse_stride = round_up(seqlen, 16);
+    p.b = batch; p.s = seqlen; p.nsenses = nsenses; p.dk = d_k; p.dout = d_out;
+    p.n_qtiles = (seqlen + 255) / 256;
+    p.n_chunks = (d_out + 255) / 256;
+    p.scale_log2e = softmax_scale * bp::kLog2e;
+    p.queues = static_cast<bp::MixQueues *>(queue_ws);
+    return p;
 }
 
 }  // namespace
@@ -100,9 +142,6 @@ int bp_build_flags(void) {
 #endif
 #if defined(BP_BWD_WHATIF) && BP_BWD_WHATIF != 0
     flags |= 2;
-#endif
-#ifdef BP_DEV_BUILD
-    flags |= 4;
 #endif
     return flags;
 }
@@ -153,20 +192,18 @@ int bp_flash_fwd_dropout(const void *q, const void *k, const void *v, void *out,
     p.max_sq = max_seqlen_q; p.max_sk = max_seqlen_k;
     p.n_qtiles = (max_seqlen_q + 127) / 128;
     p.causal = is_causal ? 1 : 0;
-    p.pair = (p.causal && p.n_qtiles > 1 && dev_flash_pair()) ? 1 : 0;
+    p.pair = (p.causal && p.n_qtiles > 1) ? 1 : 0;
     p.scale_log2e = softmax_scale * bp::kLog2e;
     p.rng_state = rng_state;
     if (!dropout_args(p_dropout, rng_state, p.drop_thr, p.drop_scale)) return BP_ERR_DROPOUT;
     if (p.drop_thr != 0u && v == nullptr) return BP_ERR_DROPOUT;   // dropout acts on P V: nothing to drop in an LSE pass
 
-    bool vec = (head_dim % 8 == 0) && aligned16(q) && aligned16(k) && mult8(q_row_stride) &&
-               mult8(q_head_stride) && mult8(k_row_stride) && mult8(k_head_stride);
+    bool vec = head_dim % 8 == 0 && aligned16({q, k}) &&
+               strides8({q_row_stride, q_head_stride, k_row_stride, k_head_stride});
     if (v != nullptr)
-        vec = vec && aligned16(v) && aligned16(out) && mult8(v_row_stride) && mult8(v_head_stride) &&
-              mult8(o_row_stride) && mult8(o_head_stride);
+        vec = vec && aligned16({v, out}) && strides8({v_row_stride, v_head_stride, o_row_stride, o_head_stride});
     if (p.drop_thr != 0u && !vec) return BP_ERR_DROPOUT;   // the element-wise loader path has no dropout
-    hipError_t e = dispatch_flash(p, dtype, vec, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? BP_OK : BP_ERR_LAUNCH;
+    return launch_status(dispatch_flash(p, dtype, vec, static_cast<hipStream_t>(stream)));
 }
 
 int bp_attn_probs(const void *q, const void *k, const float *softmax_lse, void *probs,
@@ -206,16 +243,14 @@ int bp_attn_probs_dropout(const void *q, const void *k, const float *softmax_lse
     p.causal = is_causal ? 1 : 0;
     p.p_vec = ((reinterpret_cast<uintptr_t>(probs) & 7u) == 0 && (p_batch_stride & 3) == 0 &&
                (p_head_stride & 3) == 0 && (p_row_stride & 3) == 0) ? 1 : 0;
-    p.p_vec16 = (aligned16(probs) && mult8(p_batch_stride) && mult8(p_head_stride) && mult8(p_row_stride)) ? 1 : 0;
+    p.p_vec16 = (aligned16(probs) && strides8({p_batch_stride, p_head_stride, p_row_stride})) ? 1 : 0;
     p.scale_log2e = softmax_scale * bp::kLog2e;
     p.rng_state = rng_state;
     float unused_scale;
     if (!dropout_args(p_dropout, rng_state, p.drop_thr, unused_scale)) return BP_ERR_DROPOUT;
-    const bool vec = (head_dim % 8 == 0) && aligned16(q) && aligned16(k) && mult8(q_batch_stride) &&
-                     mult8(q_row_stride) && mult8(q_head_stride) && mult8(k_batch_stride) &&
-                     mult8(k_row_stride) && mult8(k_head_stride);
-    hipError_t e = bp::launch_attn_probs(p, dtype, vec, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? BP_OK : BP_ERR_LAUNCH;
+    const bool vec = head_dim % 8 == 0 && aligned16({q, k}) &&
+                     strides8({q_batch_stride, q_row_stride, q_head_stride, k_batch_stride, k_row_stride, k_head_stride});
+    return launch_status(bp::launch_attn_probs(p, dtype, vec, static_cast<hipStream_t>(stream)));
 }
 
 // LSE of every (sense, query): the flash kernel in LSE-only mode with the k senses as heads.
@@ -234,19 +269,20 @@ static int sense_lse(const void *qk, float *lse_ws, int batch, int seqlen, int n
     p.max_sq = seqlen; p.max_sk = seqlen;
     p.n_qtiles = (seqlen + 127) / 128;
     p.causal = 1;
-    p.pair = (p.n_qtiles > 1 && dev_flash_pair()) ? 1 : 0;
+    p.pair = p.n_qtiles > 1 ? 1 : 0;
     p.scale_log2e = softmax_scale * bp::kLog2e;
-    const bool vec = (d_k % 8 == 0) && aligned16(qp) && aligned16(kp) && mult8(qk_bs) && mult8(qk_rs) &&
-                     mult8(qk_ss);
-    hipError_t e;
-    if (d_k > 128 && bp::sense_wide_dma_takes(seqlen, d_k, 8, vec, true, false))   // d_k = 160 / 640: sense_wide_dma.hip
-        e = bp::launch_sense_lse_wide_dma(qp, kp, lse_ws, p.lse_stride, qk_bs, qk_rs, qk_ss, batch, seqlen, nsenses, d_k,
-                                          p.scale_log2e, dtype, stream);
-    else if (d_k > 128)   // wide senses (sense_wide.hip): the reference's vecs-4 / vecs-1 ablations
-        e = bp::launch_sense_lse_wide(qp, kp, lse_ws, p.lse_stride, qk_bs, qk_rs, qk_ss, batch, seqlen, nsenses, d_k,
-                                      p.scale_log2e, dtype, vec, stream);
-    else e = dispatch_flash(p, dtype, vec, stream);
-    return e == hipSuccess ? BP_OK : BP_ERR_LAUNCH;
+    const bool vec = qk_vec16(d_k, qp, qk_two, qk_bs, qk_rs, qk_ss);
+    switch (sense_route(d_k, seqlen, 0, vec, true, false, false)) {
+        case SenseKernel::WideRing:     // d_k = 160 / 640: sense_wide_dma.hip
+            return launch_status(bp::launch_sense_lse_wide_dma(qp, kp, lse_ws, p.lse_stride, qk_bs, qk_rs, qk_ss, batch,
+                                                               seqlen, nsenses, d_k, p.scale_log2e, dtype, stream));
+        case SenseKernel::WideStaged:   // wide senses (sense_wide.hip): the reference's vecs-4 / vecs-1 ablations
+            return launch_status(bp::launch_sense_lse_wide(qp, kp, lse_ws, p.lse_stride, qk_bs, qk_rs, qk_ss, batch,
+                                                           seqlen, nsenses, d_k, p.scale_log2e, dtype, vec, stream));
+        case SenseKernel::NarrowRing:
+        case SenseKernel::NarrowStaged: break;
+    }
+    return launch_status(dispatch_flash(p, dtype, vec, stream));   // narrow: the flash kernel, the ring one exactly when vec
 }
 
 int bp_sense_lse(const void *qk, float *lse, int batch, int seqlen, int nsenses, int d_k,
@@ -279,15 +315,11 @@ int bp_sense_alpha(const void *qk, void *alpha, float *lse_ws, int lse_ready,
     }
     const uint16_t *qp = static_cast<const uint16_t *>(qk);
     const int64_t S = seqlen;
-    if (d_k > 128) {
-        const uint16_t *kp = qp + qk_two_stride;
-        const bool vec = (d_k % 8 == 0) && aligned16(qp) && aligned16(kp) && mult8(qk_batch_stride) &&
-                         mult8(qk_row_stride) && mult8(qk_sense_stride);
-        const hipError_t e = bp::launch_sense_alpha_wide(qp, kp, lse_ws, round_up(seqlen, 16), alpha, qk_batch_stride,
-                                                         qk_row_stride, qk_sense_stride, batch, seqlen, nsenses, d_k,
-                                                         softmax_scale * bp::kLog2e, dtype, vec, st);
-        return e == hipSuccess ? BP_OK : BP_ERR_LAUNCH;
-    }
+    const bool vec = qk_vec16(d_k, qp, qk_two_stride, qk_batch_stride, qk_row_stride, qk_sense_stride);
+    if (is_wide(sense_route(d_k, seqlen, 0, vec, true, false, false)))   // one alpha kernel for wide senses: sense_wide.hip
+        return launch_status(bp::launch_sense_alpha_wide(qp, qp + qk_two_stride, lse_ws, round_up(seqlen, 16), alpha,
+                                                         qk_batch_stride, qk_row_stride, qk_sense_stride, batch, seqlen,
+                                                         nsenses, d_k, softmax_scale * bp::kLog2e, dtype, vec, st));
     return bp_attn_probs(qp, qp + qk_two_stride, lse_ws, alpha, batch, nsenses, d_k, seqlen, seqlen,
                          qk_batch_stride, qk_row_stride, qk_sense_stride,
                          qk_batch_stride, qk_row_stride, qk_sense_stride,
@@ -333,31 +365,21 @@ int bp_sense_mix_weighted(const void *qk, const void *content, const float *key_
         if (rc != BP_OK) return rc;
     }
 
-    const uint16_t *qp = static_cast<const uint16_t *>(qk);
-    bp::MixParams p{};
-    p.q = qp; p.k = qp + qk_two_stride; p.c = content; p.o = out; p.lse = lse_ws;
+    bp::MixParams p = mix_params(qk, content, out, lse_ws, batch, seqlen, nsenses, d_k, d_out, qk_batch_stride,
+                                 qk_row_stride, qk_two_stride, qk_sense_stride, c_batch_stride, c_row_stride,
+                                 c_sense_stride, o_batch_stride, o_row_stride, softmax_scale, queue_ws);
     p.kw = key_weight; p.kw_bs = kw_batch_stride; p.kw_ss = kw_sense_stride;
-    p.qk_bs = qk_batch_stride; p.qk_rs = qk_row_stride; p.qk_ss = qk_sense_stride;
-    p.c_bs = c_batch_stride; p.c_rs = c_row_stride; p.c_ss = c_sense_stride;
-    p.o_bs = o_batch_stride; p.o_rs = o_row_stride;
-    p.lse_stride = round_up(seqlen, 16);
-    p.b = batch; p.s = seqlen; p.nsenses = nsenses; p.dk = d_k; p.dout = d_out;
-    p.n_qtiles = (seqlen + 255) / 256;
-    p.n_chunks = (d_out + 255) / 256;
-    p.scale_log2e = softmax_scale * bp::kLog2e;
-    p.queues = static_cast<bp::MixQueues *>(queue_ws);
-    const bool vec_qk = (d_k % 8 == 0) && aligned16(p.q) && aligned16(p.k) && mult8(qk_batch_stride) &&
-                        mult8(qk_row_stride) && mult8(qk_sense_stride);
-    const bool vec_c = (d_out % 8 == 0) && aligned16(content) && aligned16(out) && mult8(c_batch_stride) &&
-                       mult8(c_row_stride) && mult8(c_sense_stride) && mult8(o_batch_stride) &&
-                       mult8(o_row_stride);
-    hipError_t e;
-    if (d_k > 128 && bp::sense_wide_dma_takes(seqlen, d_k, d_out, vec_qk, vec_c, key_weight != nullptr))
-        e = bp::launch_sense_mix_wide_dma(p, dtype, st);                         // d_k = 160 / 640: sense_wide_dma.hip
-    else if (d_k > 128) e = bp::launch_sense_mix_wide(p, dtype, vec_qk, vec_c, st);   // few wide senses: sense_wide.hip
-    else if (vec_qk && vec_c && p.n_qtiles <= 256 && !dev_force_staged_mix()) e = bp::launch_sense_mix_dma(p, dtype, st);
-    else e = bp::launch_sense_mix(p, dtype, vec_qk, vec_c, st);
-    return e == hipSuccess ? BP_OK : BP_ERR_LAUNCH;
+    const bool vec_qk = qk_vec16(d_k, static_cast<const uint16_t *>(qk), qk_two_stride, qk_batch_stride, qk_row_stride,
+                                 qk_sense_stride);
+    const bool vec_c = d_out % 8 == 0 && aligned16({content, out}) &&
+                       strides8({c_batch_stride, c_row_stride, c_sense_stride, o_batch_stride, o_row_stride});
+    switch (sense_route(d_k, seqlen, d_out, vec_qk, vec_c, key_weight != nullptr, false)) {
+        case SenseKernel::WideRing:   return launch_status(bp::launch_sense_mix_wide_dma(p, dtype, st));   // d_k = 160 / 640
+        case SenseKernel::WideStaged: return launch_status(bp::launch_sense_mix_wide(p, dtype, vec_qk, vec_c, st));
+        case SenseKernel::NarrowRing: return launch_status(bp::launch_sense_mix_dma(p, dtype, st));
+        case SenseKernel::NarrowStaged: break;
+    }
+    return launch_status(bp::launch_sense_mix(p, dtype, vec_qk, vec_c, st));
 }
 
 int bp_sense_mix_gather(const void *qk, const void *table, const int32_t *row_index, void *out,
@@ -369,21 +391,20 @@ int bp_sense_mix_gather(const void *qk, const void *table, const int32_t *row_in
                         int64_t o_batch_stride, int64_t o_row_stride,
                         float softmax_scale, int dtype, void *queue_ws, bp_stream_t stream) {
     if (dtype != BP_DTYPE_F16 && dtype != BP_DTYPE_BF16) return BP_ERR_DTYPE;
-    // wide senses: the reference's two few-sense widths on the ring kernels of sense_wide_dma.hip (row indices as u32 in LDS:
-    // no limit on the row count); everything else wider than 128 is gathered by the caller
-    const bool wide = d_k > 128 && bp::sense_wide_dma_takes(seqlen, d_k, d_out, true, true, false);
-    if (d_k < 8 || (d_k > 128 && !wide) || d_k % 8 != 0) return BP_ERR_HEAD_DIM;
+    // the ring kernels only: wide senses at the reference's two few-sense widths (sense_wide_dma.hip, row indices as u32 in
+    // LDS: no limit on the row count); every other shape is gathered by the caller.  16-byte friendliness is checked below.
+    const SenseKernel route = sense_route(d_k, seqlen, d_out, d_k % 8 == 0, true, false, true);
+    const bool wide = route == SenseKernel::WideRing;
+    if (d_k < 8 || (route != SenseKernel::NarrowRing && !wide)) return BP_ERR_HEAD_DIM;
     if (queue_ws != nullptr && !aligned16(queue_ws)) return BP_ERR_SHAPE;
     if (d_out < 8 || d_out % 8 != 0) return BP_ERR_DOUT;
     if (batch <= 0 || nsenses <= 0 || seqlen <= 0 || seqlen > bp::kMixGatherMaxKeys || table_rows <= 0 ||
         (!wide && table_rows > bp::kMixGatherMaxRows)) return BP_ERR_SHAPE;
     if (qk == nullptr || table == nullptr || row_index == nullptr || out == nullptr || lse_ws == nullptr) return BP_ERR_SHAPE;
     if (!scale_ok(softmax_scale)) return BP_ERR_SCALE;
-    const uint16_t *qp = static_cast<const uint16_t *>(qk);
-    if (!aligned16(qp) || !aligned16(qp + qk_two_stride) || !aligned16(table) || !aligned16(out)) return BP_ERR_SHAPE;
-    const int64_t strides[] = {qk_batch_stride, qk_row_stride, qk_sense_stride, t_row_stride, t_sense_stride,
-                               o_batch_stride, o_row_stride};
-    for (int64_t v : strides) if (!mult8(v)) return BP_ERR_SHAPE;
+    if (!qk_vec16(d_k, static_cast<const uint16_t *>(qk), qk_two_stride, qk_batch_stride, qk_row_stride, qk_sense_stride) ||
+        !aligned16({table, out}) || !strides8({t_row_stride, t_sense_stride, o_batch_stride, o_row_stride}))
+        return BP_ERR_SHAPE;
     if (t_row_stride <= 0 || table_rows * t_row_stride * 2 >= (int64_t(1) << 32)) return BP_ERR_SHAPE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (null_queue_ws_on_capturing_stream(queue_ws, st)) return BP_ERR_QUEUE_WS;
@@ -392,20 +413,11 @@ int bp_sense_mix_gather(const void *qk, const void *table, const int32_t *row_in
                            qk_two_stride, qk_sense_stride, softmax_scale, dtype, st);
         if (rc != BP_OK) return rc;
     }
-    bp::MixParams p{};
-    p.q = qp; p.k = qp + qk_two_stride; p.c = table; p.o = out; p.lse = lse_ws;
+    bp::MixParams p = mix_params(qk, table, out, lse_ws, batch, seqlen, nsenses, d_k, d_out, qk_batch_stride,
+                                 qk_row_stride, qk_two_stride, qk_sense_stride, 0, t_row_stride, t_sense_stride,
+                                 o_batch_stride, o_row_stride, softmax_scale, queue_ws);
     p.row_index = row_index; p.idx_bs = idx_batch_stride; p.last_table_row = (uint32_t)(table_rows - 1);
-    p.qk_bs = qk_batch_stride; p.qk_rs = qk_row_stride; p.qk_ss = qk_sense_stride;
-    p.c_bs = 0; p.c_rs = t_row_stride; p.c_ss = t_sense_stride;
-    p.o_bs = o_batch_stride; p.o_rs = o_row_stride;
-    p.lse_stride = round_up(seqlen, 16);
-    p.b = batch; p.s = seqlen; p.nsenses = nsenses; p.dk = d_k; p.dout = d_out;
-    p.n_qtiles = (seqlen + 255) / 256;
-    p.n_chunks = (d_out + 255) / 256;
-    p.scale_log2e = softmax_scale * bp::kLog2e;
-    p.queues = static_cast<bp::MixQueues *>(queue_ws);
-    const hipError_t e = wide ? bp::launch_sense_mix_wide_dma(p, dtype, st) : bp::launch_sense_mix_dma(p, dtype, st);
-    return e == hipSuccess ? BP_OK : BP_ERR_LAUNCH;
+    return launch_status(wide ? bp::launch_sense_mix_wide_dma(p, dtype, st) : bp::launch_sense_mix_dma(p, dtype, st));
 }
 
 int bp_sense_mix_dc(const void *qk, const void *dout, const float *lse, void *dcontent,
@@ -422,10 +434,9 @@ int bp_sense_mix_dc(const void *qk, const void *dout, const float *lse, void *dc
     if (qk == nullptr || dout == nullptr || lse == nullptr || dcontent == nullptr) return BP_ERR_SHAPE;
     if (!scale_ok(softmax_scale)) return BP_ERR_SCALE;
     const uint16_t *qp = static_cast<const uint16_t *>(qk);
-    if (!aligned16(qp) || !aligned16(qp + qk_two_stride) || !aligned16(dout) || !aligned16(dcontent)) return BP_ERR_SHAPE;
-    const int64_t strides[] = {qk_batch_stride, qk_row_stride, qk_sense_stride, do_batch_stride, do_row_stride,
-                               c_batch_stride, c_row_stride, c_sense_stride};
-    for (int64_t st : strides) if (!mult8(st)) return BP_ERR_SHAPE;
+    if (!qk_vec16(d_k, qp, qk_two_stride, qk_batch_stride, qk_row_stride, qk_sense_stride) || !aligned16({dout, dcontent}) ||
+        !strides8({do_batch_stride, do_row_stride, c_batch_stride, c_row_stride, c_sense_stride}))
+        return BP_ERR_SHAPE;
     if (null_queue_ws_on_capturing_stream(queue_ws, static_cast<hipStream_t>(stream))) return BP_ERR_QUEUE_WS;
     bp::MixBwdParams p{};
     p.q = qp; p.k = qp + qk_two_stride; p.dout = dout; p.dc = dcontent; p.lse = lse;
@@ -438,8 +449,7 @@ int bp_sense_mix_dc(const void *qk, const void *dout, const float *lse, void *dc
     p.n_chunks = (d_out + 255) / 256;
     p.scale_log2e = softmax_scale * bp::kLog2e;
     p.queues = static_cast<bp::MixQueues *>(queue_ws);
-    hipError_t e = bp::launch_sense_mix_dc(p, dtype, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? BP_OK : BP_ERR_LAUNCH;
+    return launch_status(bp::launch_sense_mix_dc(p, dtype, static_cast<hipStream_t>(stream)));
 }
 
 int bp_sense_dq_dk(const void *qk, const void *dpt, const float *lse, float *dsum_ws, void *dqk, float *dk_acc,
@@ -455,11 +465,9 @@ int bp_sense_dq_dk(const void *qk, const void *dpt, const float *lse, float *dsu
     if (!qk || !dpt || !lse || !dsum_ws || !dqk || !dk_acc) return BP_ERR_SHAPE;
     if (!scale_ok(softmax_scale)) return BP_ERR_SCALE;
     const uint16_t *qp = static_cast<const uint16_t *>(qk);
-    if (!aligned16(qp) || !aligned16(qp + qk_two_stride) || !aligned16(dpt) || !aligned16(dqk) || !aligned16(dk_acc))
+    if (!qk_vec16(d_k, qp, qk_two_stride, qk_batch_stride, qk_row_stride, qk_sense_stride) ||
+        !aligned16({dpt, dqk, dk_acc}) || !strides8({dpt_batch_stride, dqk_batch_stride, dqk_row_stride, dqk_sense_stride}))
         return BP_ERR_SHAPE;
-    const int64_t strides[] = {qk_batch_stride, qk_row_stride, qk_sense_stride, dpt_batch_stride, dqk_batch_stride,
-                               dqk_row_stride, dqk_sense_stride};
-    for (int64_t st : strides) if (!mult8(st)) return BP_ERR_SHAPE;
     if ((dka_batch_stride | dka_row_stride | dka_sense_stride) & 3) return BP_ERR_SHAPE;
     bp::SenseGradParams p{};
     p.q = qp; p.k = qp + qk_two_stride; p.dpt = dpt; p.lse = lse; p.dsum = dsum_ws; p.dq = dqk; p.dk_acc = dk_acc;
@@ -470,8 +478,7 @@ int bp_sense_dq_dk(const void *qk, const void *dpt, const float *lse, float *dsu
     p.lse_stride = round_up(seqlen, 16);
     p.b = batch; p.s = seqlen; p.nsenses = nsenses; p.dk = d_k; p.t0 = t0;
     p.scale = softmax_scale;
-    hipError_t e = bp::launch_sense_dq_dk(p, dtype, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? BP_OK : BP_ERR_LAUNCH;
+    return launch_status(bp::launch_sense_dq_dk(p, dtype, static_cast<hipStream_t>(stream)));
 }
 
 int64_t bp_flash_bwd_ws_floats(int batch, int nheads, int64_t lse_stride) {
@@ -521,12 +528,11 @@ int bp_flash_bwd_dropout(const void *dout, const void *q, const void *k, const v
     if (!dout || !q || !k || !v || !out || !softmax_lse || !dsum_ws || !dq || !dk || !dv) return BP_ERR_SHAPE;
     if ((cu_seqlens_q == nullptr) != (cu_seqlens_k == nullptr)) return BP_ERR_SHAPE;
     if (!scale_ok(softmax_scale)) return BP_ERR_SCALE;
-    const void *ptrs[] = {dout, q, k, v, out, dq, dk, dv, softmax_lse, dsum_ws};
-    for (const void *ptr : ptrs) if (!aligned16(ptr)) return BP_ERR_SHAPE;
-    const int64_t strides[] = {do_row_stride, do_head_stride, q_row_stride, q_head_stride, k_row_stride,
-                               k_head_stride, v_row_stride, v_head_stride, o_row_stride, o_head_stride, dq_row_stride, dq_head_stride,
-                               dk_row_stride, dk_head_stride, dv_row_stride, dv_head_stride};
-    for (int64_t st : strides) if (!mult8(st)) return BP_ERR_SHAPE;
+    if (!aligned16({dout, q, k, v, out, dq, dk, dv, softmax_lse, dsum_ws}) ||
+        !strides8({do_row_stride, do_head_stride, q_row_stride, q_head_stride, k_row_stride, k_head_stride, v_row_stride,
+                   v_head_stride, o_row_stride, o_head_stride, dq_row_stride, dq_head_stride, dk_row_stride,
+                   dk_head_stride, dv_row_stride, dv_head_stride}))
+        return BP_ERR_SHAPE;
     if (lse_stride % 16 != 0) return BP_ERR_SHAPE;
     // the dQ kernel writes both statistics rows of every (batch, head): an ABI-2-sized buffer would be overrun
     if (dsum_ws_floats < bp_flash_bwd_ws_floats(batch, nheads, lse_stride)) return BP_ERR_WORKSPACE;
@@ -547,7 +553,7 @@ int bp_flash_bwd_dropout(const void *dout, const void *q, const void *k, const v
     if (!dropout_args(p_dropout, rng_state, p.drop_thr, p.drop_scale)) return BP_ERR_DROPOUT;
     hipError_t e = bp::launch_flash_bwd(p, dtype, static_cast<hipStream_t>(stream));
     if (e == hipErrorNotSupported) return BP_ERR_HEAD_DIM;
-    return e == hipSuccess ? BP_OK : BP_ERR_LAUNCH;
+    return launch_status(e);
 }
 
 int bp_add_layer_norm(const void *x0, const void *x1, const void *gamma, const void *beta, void *z,
@@ -573,9 +579,7 @@ int bp_dropout_add_layer_norm_scaled(const void *x0, const void *x1, const void 
     if (dtype != BP_DTYPE_F16 && dtype != BP_DTYPE_BF16) return BP_ERR_DTYPE;
     if (rows <= 0 || rows > 0xffffffffLL || cols <= 0 || cols % 4 != 0 || cols > 8192) return BP_ERR_SHAPE;
     if (x0 == nullptr || gamma == nullptr || beta == nullptr || z == nullptr) return BP_ERR_SHAPE;
-    if (!aligned16(x0) || !aligned16(gamma) || !aligned16(beta) || !aligned16(z) ||
-        (x1 != nullptr && !aligned16(x1)) || (x_out != nullptr && !aligned16(x_out)) ||
-        (colscale != nullptr && !aligned16(colscale)) ||
+    if (!aligned16({x0, gamma, beta, z}) || !aligned16_or_null({x1, x_out, colscale}) ||
         (rowscale != nullptr && (reinterpret_cast<uintptr_t>(rowscale) & (x0_is_f32 ? 3u : 1u)) != 0) ||
         (dmask != nullptr && (reinterpret_cast<uintptr_t>(dmask) & 3u) != 0))
         return BP_ERR_SHAPE;
@@ -592,21 +596,20 @@ int bp_dropout_add_layer_norm_scaled(const void *x0, const void *x1, const void 
     p.dmask = dmask; p.rng_state = rng_state;
     p.rowscale = rowscale; p.colscale = colscale;
     if (!dropout_args(p_dropout, rng_state, p.drop_thr, p.drop_scale)) return BP_ERR_DROPOUT;
-    hipError_t e = bp::launch_add_layer_norm(p, dtype, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? BP_OK : BP_ERR_LAUNCH;
+    return launch_status(bp::launch_add_layer_norm(p, dtype, static_cast<hipStream_t>(stream)));
 }
 
 int bp_softmax_bwd_causal(const void *alpha, void *dalpha_inout, int64_t n_matrices, int seqlen,
                           float softmax_scale, int dtype, bp_stream_t stream) {
     if (dtype != BP_DTYPE_F16 && dtype != BP_DTYPE_BF16) return BP_ERR_DTYPE;
     if (n_matrices <= 0 || seqlen <= 0 || seqlen % 8 != 0 || seqlen > 4096) return BP_ERR_SHAPE;
-    if (alpha == nullptr || dalpha_inout == nullptr || !aligned16(alpha) || !aligned16(dalpha_inout)) return BP_ERR_SHAPE;
+    if (alpha == nullptr || dalpha_inout == nullptr || !aligned16({alpha, dalpha_inout})) return BP_ERR_SHAPE;
     if (!scale_ok(softmax_scale)) return BP_ERR_SCALE;
     bp::SoftmaxBwdParams p{};
     p.alpha = alpha; p.dp = dalpha_inout; p.rows = n_matrices * seqlen; p.s = seqlen; p.scale = softmax_scale;
     hipError_t e = bp::launch_softmax_bwd_causal(p, dtype, static_cast<hipStream_t>(stream));
     if (e == hipErrorNotSupported) return BP_ERR_SHAPE;
-    return e == hipSuccess ? BP_OK : BP_ERR_LAUNCH;
+    return launch_status(e);
 }
 
 int bp_add_layer_norm_bwd(const void *dz, const void *dx_in, const void *x, const void *gamma,
@@ -643,8 +646,7 @@ int bp_dropout_add_layer_norm_scaled_bwd(const void *dz, const void *dx_in, cons
     if (rows <= 0 || rows > 0xffffffffLL || cols <= 0 || cols % 4 != 0 || cols > 2048) return BP_ERR_SHAPE;
     if (!dz || !x || !gamma || !dx0 || !dgamma || !dbeta || !ws) return BP_ERR_SHAPE;
     if (colscale != nullptr && (x0 == nullptr || dcolscale == nullptr)) return BP_ERR_SHAPE;   // (layer_norm.py:36-37)
-    const void *ptrs[] = {dz, dx_in, x, x0, gamma, colscale, dx0, dx1, dgamma, dbeta, dcolscale, ws};
-    for (const void *ptr : ptrs) if (ptr != nullptr && !aligned16(ptr)) return BP_ERR_SHAPE;
+    if (!aligned16_or_null({dz, dx_in, x, x0, gamma, colscale, dx0, dx1, dgamma, dbeta, dcolscale, ws})) return BP_ERR_SHAPE;
     if (rowscale != nullptr && (reinterpret_cast<uintptr_t>(rowscale) & (x0_is_f32 ? 3u : 1u)) != 0) return BP_ERR_SHAPE;
     if (!(isfinite(epsilon) && epsilon >= 0.f)) return BP_ERR_SCALE;
     if (x0_is_f32 && !res_is_f32) return BP_ERR_DTYPE;
@@ -660,7 +662,7 @@ int bp_dropout_add_layer_norm_scaled_bwd(const void *dz, const void *dx_in, cons
     if (!dropout_args(p_dropout, rng_state, p.drop_thr, p.drop_scale)) return BP_ERR_DROPOUT;
     hipError_t e = bp::launch_add_layer_norm_bwd(p, dtype, static_cast<hipStream_t>(stream));
     if (e == hipErrorNotSupported) return BP_ERR_SHAPE;
-    return e == hipSuccess ? BP_OK : BP_ERR_LAUNCH;
+    return launch_status(e);
 }
 
 int64_t bp_bias_grad_ws_floats(int64_t rows, int cols) {
@@ -672,13 +674,12 @@ int bp_bias_gelu_fwd(const void *x, const void *bias, void *pre_out, void *y, in
                      bp_stream_t stream) {
     if (dtype != BP_DTYPE_F16 && dtype != BP_DTYPE_BF16) return BP_ERR_DTYPE;
     if (rows <= 0 || cols <= 0 || cols % 8 != 0) return BP_ERR_SHAPE;
-    if (x == nullptr || y == nullptr || !aligned16(x) || !aligned16(y)) return BP_ERR_SHAPE;
-    if ((bias != nullptr && !aligned16(bias)) || (pre_out != nullptr && !aligned16(pre_out))) return BP_ERR_SHAPE;
+    if (x == nullptr || y == nullptr || !aligned16({x, y})) return BP_ERR_SHAPE;
+    if (!aligned16_or_null({bias, pre_out})) return BP_ERR_SHAPE;
     if (pre_out != nullptr && bias == nullptr) return BP_ERR_SHAPE;   // without a bias the pre-activation IS x
     bp::BiasGeluParams p{};
     p.x = x; p.bias = bias; p.pre = pre_out; p.y = y; p.rows = rows; p.cols = cols;
-    hipError_t e = bp::launch_bias_gelu_fwd(p, dtype, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? BP_OK : BP_ERR_LAUNCH;
+    return launch_status(bp::launch_bias_gelu_fwd(p, dtype, static_cast<hipStream_t>(stream)));
 }
 
 static int bias_grad_common(const void *grad, void *dbias, float *ws, int64_t rows, int cols, int dtype) {
@@ -693,12 +694,11 @@ int bp_bias_gelu_bwd(const void *grad, const void *pre, void *dpre, void *dbias,
                      int dtype, int dbias_is_f32, bp_stream_t stream) {
     const int rc = bias_grad_common(grad, dbias, ws, rows, cols, dtype);
     if (rc != BP_OK) return rc;
-    if (pre == nullptr || dpre == nullptr || !aligned16(pre) || !aligned16(dpre)) return BP_ERR_SHAPE;
+    if (pre == nullptr || dpre == nullptr || !aligned16({pre, dpre})) return BP_ERR_SHAPE;
     bp::BiasGeluParams p{};
     p.x = grad; p.pre = const_cast<void *>(pre); p.y = dpre; p.dbias = dbias; p.ws = dbias != nullptr ? ws : nullptr;
     p.rows = rows; p.cols = cols; p.dbias_f32 = dbias_is_f32 ? 1 : 0;
-    hipError_t e = bp::launch_bias_gelu_bwd(p, dtype, true, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? BP_OK : BP_ERR_LAUNCH;
+    return launch_status(bp::launch_bias_gelu_bwd(p, dtype, true, static_cast<hipStream_t>(stream)));
 }
 
 int bp_column_sum(const void *grad, void *dbias, float *ws, int64_t rows, int cols, int dtype, int dbias_is_f32,
@@ -708,8 +708,7 @@ int bp_column_sum(const void *grad, void *dbias, float *ws, int64_t rows, int co
     if (dbias == nullptr) return BP_ERR_SHAPE;
     bp::BiasGeluParams p{};
     p.x = grad; p.dbias = dbias; p.ws = ws; p.rows = rows; p.cols = cols; p.dbias_f32 = dbias_is_f32 ? 1 : 0;
-    hipError_t e = bp::launch_bias_gelu_bwd(p, dtype, false, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? BP_OK : BP_ERR_LAUNCH;
+    return launch_status(bp::launch_bias_gelu_bwd(p, dtype, false, static_cast<hipStream_t>(stream)));
 }
 
 static int xent_common(int64_t rows, int cols, int64_t row_stride, float smoothing, int dtype) {
@@ -730,8 +729,7 @@ int bp_xentropy_fwd(const void *logits, const int64_t *labels, float *losses, fl
     p.rows = rows; p.cols = cols; p.row_stride = row_stride;
     p.total_classes = total_classes > 0 ? total_classes : cols;
     p.smoothing = smoothing;
-    hipError_t e = bp::launch_xentropy_fwd(p, dtype, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? BP_OK : BP_ERR_LAUNCH;
+    return launch_status(bp::launch_xentropy_fwd(p, dtype, static_cast<hipStream_t>(stream)));
 }
 
 int bp_xentropy_bwd(const float *grad_losses, const void *logits, const float *lse, const int64_t *labels,
@@ -749,22 +747,10 @@ int bp_xentropy_bwd(const float *grad_losses, const void *logits, const float *l
     p.rows = rows; p.cols = cols; p.row_stride = row_stride; p.grad_row_stride = grad_row_stride;
     p.total_classes = total_classes > 0 ? total_classes : cols;
     p.smoothing = smoothing;
-    hipError_t e = bp::launch_xentropy_bwd(p, dtype, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? BP_OK : BP_ERR_LAUNCH;
+    return launch_status(bp::launch_xentropy_bwd(p, dtype, static_cast<hipStream_t>(stream)));
 }
-
-}  // extern "C"
 
 // ---- KV-cached decoding (bp_flash_decode / bp_sense_decode) ----
-namespace {
-inline bool strides8(std::initializer_list<int64_t> strides) {
-    for (int64_t s : strides)
-        if (!mult8(s)) return false;
-    return true;
-}
-}  // namespace
-
-extern "C" {
 
 int64_t bp_flash_decode_ws_floats(int batch, int nheads, int head_dim, int max_seqlen) {
     if (batch <= 0 || nheads <= 0 || head_dim <= 0 || max_seqlen <= 0) return 0;
@@ -786,9 +772,7 @@ int bp_flash_decode(const void *q, const void *k_new, const void *v_new, void *k
     if (q == nullptr || k_new == nullptr || v_new == nullptr || kv_cache == nullptr || cache_seqlens == nullptr
         || out == nullptr || ws == nullptr)
         return BP_ERR_SHAPE;
-    if (!aligned16(q) || !aligned16(k_new) || !aligned16(v_new) || !aligned16(kv_cache) || !aligned16(out)
-        || !aligned16(ws))
-        return BP_ERR_SHAPE;
+    if (!aligned16({q, k_new, v_new, kv_cache, out, ws})) return BP_ERR_SHAPE;
     if (!strides8({q_batch_stride, q_head_stride, knew_batch_stride, knew_head_stride, vnew_batch_stride,
                    vnew_head_stride, kv_batch_stride, kv_row_stride, kv_two_stride, kv_head_stride, o_batch_stride,
                    o_head_stride}))
@@ -810,9 +794,8 @@ int bp_flash_decode(const void *q, const void *k_new, const void *v_new, void *k
     p.ws_ml = ws + (int64_t)batch * nheads * p.nsplit * head_dim;
     p.o = out; p.o_bs = o_batch_stride; p.o_gs = o_head_stride;
     p.lse = softmax_lse; p.lse_bs = lse_batch_stride;
-    p.scale_log2e = softmax_scale * 1.4426950408889634f;
-    hipError_t e = bp::launch_flash_decode(p, dtype, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? BP_OK : BP_ERR_LAUNCH;
+    p.scale_log2e = softmax_scale * bp::kLog2e;
+    return launch_status(bp::launch_flash_decode(p, dtype, static_cast<hipStream_t>(stream)));
 }
 
 int64_t bp_sense_decode_ws_floats(int batch, int nsenses, int d_out, int max_seqlen) {
@@ -838,9 +821,7 @@ int bp_sense_decode(const void *q, const void *k_new, void *k_cache, const void 
     if (q == nullptr || k_new == nullptr || k_cache == nullptr || table == nullptr || row_index == nullptr
         || new_row == nullptr || cache_seqlens == nullptr || out == nullptr || ws == nullptr)
         return BP_ERR_SHAPE;
-    if (!aligned16(q) || !aligned16(k_new) || !aligned16(k_cache) || !aligned16(table) || !aligned16(out)
-        || !aligned16(ws))
-        return BP_ERR_SHAPE;
+    if (!aligned16({q, k_new, k_cache, table, out, ws})) return BP_ERR_SHAPE;
     if (!strides8({q_batch_stride, q_sense_stride, knew_batch_stride, knew_sense_stride, kc_batch_stride, kc_row_stride,
                    kc_sense_stride, t_row_stride, t_sense_stride, o_batch_stride}))
         return BP_ERR_SHAPE;
@@ -859,9 +840,8 @@ int bp_sense_decode(const void *q, const void *k_new, void *k_cache, const void 
     p.ws_acc = ws;
     p.ws_ml = ws + (int64_t)batch * nsenses * p.nsplit * d_out;
     p.o = out; p.o_bs = o_batch_stride;
-    p.scale_log2e = softmax_scale * 1.4426950408889634f;
-    hipError_t e = bp::launch_sense_decode(p, dtype, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? BP_OK : BP_ERR_LAUNCH;
+    p.scale_log2e = softmax_scale * bp::kLog2e;
+    return launch_status(bp::launch_sense_decode(p, dtype, static_cast<hipStream_t>(stream)));
 }
 
 }  // extern "C"

@@ -65,8 +65,8 @@ typedef void *bp_stream_t; /* a hipStream_t */
 const char *bp_strerror(int code);
 int bp_abi_version(void);
 /* 0 for a product build.  Bit 0: -DBP_FWD_WHATIF, bit 1: -DBP_BWD_WHATIF (timing builds that delete work on purpose:
- * results are garbage), bit 2: -DBP_DEV_BUILD (run-time experiment switches compiled in).  A binding should refuse to
- * load a library with bit 0 or 1 set as its default one. */
+ * results are garbage); no other bit is defined.  A binding should refuse to load a library with bit 0 or 1 set as its
+ * default one. */
 int bp_build_flags(void);
 
 /*

@@ -11,20 +11,42 @@ from conftest import ROOT
 import bp_hip
 
 
-def declared_symbols():
+def declared_prototypes():
+    """name -> (return type, [parameter types]) of every prototype include/bp_hip.h declares."""
     text = open(os.path.join(ROOT, 'include', 'bp_hip.h')).read()
     text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    return sorted(set(re.findall(r'\b(bp_[a-z_0-9]+)\s*\(', text)))
+    text = re.sub(r'^\s*#.*$', '', text, flags=re.M)
+    protos = {}
+    for ret, name, params in re.findall(r'([\w\s*]+?)\b(bp_[a-z_0-9]+)\s*\(([^)]*)\)\s*;', text):
+        params = [] if params.strip() == 'void' else [' '.join(re.sub(r'\w+$', '', p).split()) for p in params.split(',')]
+        protos[name] = (' '.join(ret.split()), params)
+    return protos
+
+
+def ctypes_of(c_type):
+    if c_type == 'const char *':
+        return ctypes.c_char_p
+    if c_type.endswith('*') or c_type == 'bp_stream_t':
+        return ctypes.c_void_p
+    return {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float}[c_type]
 
 
 def test_library_exports_every_declared_symbol():
     handle = bp_hip.lib()
-    names = declared_symbols()
+    protos = declared_prototypes()
+    names = sorted(protos)
     assert {'bp_flash_fwd', 'bp_attn_probs', 'bp_sense_lse', 'bp_sense_alpha', 'bp_sense_mix',
             'bp_strerror', 'bp_abi_version', 'bp_build_flags'} <= set(names)
     for name in names:
         assert hasattr(handle, name), name
     assert set(bp_hip.SIGNATURES) == set(names)
+    # the ctypes table states every prototype of the header, argument by argument
+    for name, (ret, params) in protos.items():
+        restype, argtypes = bp_hip.SIGNATURES[name]
+        assert restype is ctypes_of(ret), (name, ret)
+        assert len(argtypes) == len(params), (name, len(argtypes), len(params))
+        for i, (have, c_type) in enumerate(zip(argtypes, params)):
+            assert have is ctypes_of(c_type), (name, i, c_type)
     assert handle.bp_abi_version() == bp_hip.ABI_VERSION
     assert handle.bp_build_flags() == 0       # a product build: no what-if timing switches, no dev switches
 
