@@ -174,37 +174,29 @@ __global__ __launch_bounds__(256) void add_layer_norm_kernel(const LnParams p) {
     }
 }
 
-template <class ET, bool RES_F32, bool W_F32>
-static hipError_t launch_flags(const LnParams &p, hipStream_t stream) {
-    const int ch = (p.cols + 255) / 256;
-    dim3 g((unsigned)((p.rows + 3) / 4)), t(256);
+hipError_t launch_add_layer_norm(const LnParams &p, int dtype, hipStream_t stream) {
+    const dim3 g((unsigned)((p.rows + 3) / 4)), t(256);
+    const int chunks = (p.cols + 255) / 256;
     // non-temporal loads and residual store: x0 and the incoming residual are read once and never again, the outgoing
     // residual is next read a GEMM and an attention launch later; z stays cacheable for the GEMM that follows
     // (profiles/r04_d_ab_layernorm_nontemporal.jsonl)
     constexpr bool NTL = true, NTS = true, NTZ = false;
-    const bool scaled = p.rowscale != nullptr || p.colscale != nullptr;
-#define BP_LN_CASE(N) \
-    if (ch <= N) { \
-        if (scaled) hipLaunchKernelGGL((add_layer_norm_kernel<ET, N, RES_F32, W_F32, NTL, NTS, NTZ, true>), g, t, 0, stream, p); \
-        else hipLaunchKernelGGL((add_layer_norm_kernel<ET, N, RES_F32, W_F32, NTL, NTS, NTZ, false>), g, t, 0, stream, p); \
-        return hipGetLastError(); }
-    BP_LN_CASE(1) BP_LN_CASE(2) BP_LN_CASE(3) BP_LN_CASE(4) BP_LN_CASE(6) BP_LN_CASE(8)
-    BP_LN_CASE(12) BP_LN_CASE(16) BP_LN_CASE(24) BP_LN_CASE(32)
-#undef BP_LN_CASE
-    return hipErrorInvalidValue;
-}
-
-template <class ET>
-static hipError_t launch_et(const LnParams &p, hipStream_t stream) {
     // residual dtype: x1's when given, else x_out's (the API guarantees they agree when both exist)
     const bool res_f32 = (p.x1 != nullptr) ? p.x1_f32 != 0 : p.xo_f32 != 0;
-    const bool w_f32 = p.w_f32 != 0;
-    if (res_f32) return w_f32 ? launch_flags<ET, true, true>(p, stream) : launch_flags<ET, true, false>(p, stream);
-    return w_f32 ? launch_flags<ET, false, true>(p, stream) : launch_flags<ET, false, false>(p, stream);
-}
-
-hipError_t launch_add_layer_norm(const LnParams &p, int dtype, hipStream_t stream) {
-    return dtype == 1 ? launch_et<BF16>(p, stream) : launch_et<F16>(p, stream);
+    const bool scaled = p.rowscale != nullptr || p.colscale != nullptr;
+    return with_dtype(dtype, [&](auto et) {
+        return with_flag(res_f32, [&](auto res) {
+            return with_flag(p.w_f32 != 0, [&](auto w) {
+                return with_flag(scaled, [&](auto sc) {
+                    return with_bound<1, 2, 3, 4, 6, 8, 12, 16, 24, 32>(chunks, hipErrorInvalidValue, [&](auto ch) {
+                        hipLaunchKernelGGL((add_layer_norm_kernel<decltype(et), ch, res, w, NTL, NTS, NTZ, sc>), g, t, 0,
+                                           stream, p);
+                        return hipGetLastError();
+                    });
+                });
+            });
+        });
+    });
 }
 
 // =====================================================================================================
@@ -412,34 +404,27 @@ __global__ __launch_bounds__(1024) void ln_bwd_reduce_kernel(const LnBwdParams p
     }
 }
 
-template <class ET, bool RES_F32, bool W_F32>
-static hipError_t launch_bwd_flags(const LnBwdParams &p, hipStream_t stream) {
-    const int ch = (p.cols + 255) / 256;
-    dim3 g((unsigned)p.n_wg), t(256);
-    const bool scaled = p.rowscale != nullptr || p.colscale != nullptr;
-#define BP_LNB_CASE(N) \
-    if (ch <= N) { \
-        if (scaled) hipLaunchKernelGGL((add_layer_norm_bwd_kernel<ET, N, RES_F32, W_F32, true>), g, t, 0, stream, p); \
-        else hipLaunchKernelGGL((add_layer_norm_bwd_kernel<ET, N, RES_F32, W_F32, false>), g, t, 0, stream, p); \
-    } else
-    BP_LNB_CASE(1) BP_LNB_CASE(2) BP_LNB_CASE(3) BP_LNB_CASE(4) BP_LNB_CASE(6) BP_LNB_CASE(8)
-    { return hipErrorNotSupported; }
-#undef BP_LNB_CASE
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((ln_bwd_reduce_kernel<ET, W_F32>), dim3((p.cols + 63) / 64), dim3(1024), 0, stream, p);
-    return hipGetLastError();
-}
-
-template <class ET>
-static hipError_t launch_bwd_et(const LnBwdParams &p, hipStream_t stream) {
-    if (p.res_f32) return p.w_f32 ? launch_bwd_flags<ET, true, true>(p, stream) : launch_bwd_flags<ET, true, false>(p, stream);
-    return p.w_f32 ? launch_bwd_flags<ET, false, true>(p, stream) : launch_bwd_flags<ET, false, false>(p, stream);
-}
-
 // cols % 4 == 0 and <= 2048 (the model widths 384 / 640 / 768 and up); larger rows: hipErrorNotSupported
 hipError_t launch_add_layer_norm_bwd(const LnBwdParams &p, int dtype, hipStream_t stream) {
-    return dtype == 1 ? launch_bwd_et<BF16>(p, stream) : launch_bwd_et<F16>(p, stream);
+    const dim3 g((unsigned)p.n_wg), t(256);
+    const int chunks = (p.cols + 255) / 256;
+    const bool scaled = p.rowscale != nullptr || p.colscale != nullptr;
+    return with_dtype(dtype, [&](auto et) {
+        return with_flag(p.res_f32 != 0, [&](auto res) {
+            return with_flag(p.w_f32 != 0, [&](auto w) {
+                using ET = decltype(et);
+                const hipError_t e = with_flag(scaled, [&](auto sc) {
+                    return with_bound<1, 2, 3, 4, 6, 8>(chunks, hipErrorNotSupported, [&](auto ch) {
+                        hipLaunchKernelGGL((add_layer_norm_bwd_kernel<ET, ch, res, w, sc>), g, t, 0, stream, p);
+                        return hipGetLastError();
+                    });
+                });
+                if (e != hipSuccess) return e;
+                hipLaunchKernelGGL((ln_bwd_reduce_kernel<ET, w>), dim3((p.cols + 63) / 64), dim3(1024), 0, stream, p);
+                return hipGetLastError();
+            });
+        });
+    });
 }
 
 }  // namespace bp

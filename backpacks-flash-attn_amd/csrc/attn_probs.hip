@@ -245,31 +245,16 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(const ProbsParams p) {
     }
 }
 
-template <class ET, int KD>
-static hipError_t launch_kd(const ProbsParams &p, bool vec, hipStream_t stream) {
-    const int n_qtiles = (p.sq + 127) / 128;
-    dim3 g(xcd_grid(p.b * p.h, n_qtiles)), t(256);
-    if (vec) hipLaunchKernelGGL((attn_probs_kernel<ET, KD, true>), g, t, 0, stream, p);
-    else hipLaunchKernelGGL((attn_probs_kernel<ET, KD, false>), g, t, 0, stream, p);
-    return hipGetLastError();
-}
-
-template <class ET>
-static hipError_t launch_et(const ProbsParams &p, bool vec, hipStream_t stream) {
-    switch ((p.d + 15) / 16) {
-        case 1: return launch_kd<ET, 1>(p, vec, stream);
-        case 2: return launch_kd<ET, 2>(p, vec, stream);
-        case 3: return launch_kd<ET, 3>(p, vec, stream);
-        case 4: return launch_kd<ET, 4>(p, vec, stream);
-        case 5: return launch_kd<ET, 5>(p, vec, stream);
-        case 6: return launch_kd<ET, 6>(p, vec, stream);
-        case 7: return launch_kd<ET, 7>(p, vec, stream);
-        default: return launch_kd<ET, 8>(p, vec, stream);
-    }
-}
-
 hipError_t launch_attn_probs(const ProbsParams &p, int dtype, bool vec, hipStream_t stream) {
-    return dtype == 1 ? launch_et<BF16>(p, vec, stream) : launch_et<F16>(p, vec, stream);
+    const dim3 grid(xcd_grid(p.b * p.h, (p.sq + 127) / 128)), block(256);
+    return with_dtype(dtype, [&](auto et) {
+        return with_kd(p.d, [&](auto kd) {
+            return with_flag(vec, [&](auto v) {
+                hipLaunchKernelGGL((attn_probs_kernel<decltype(et), kd, v>), grid, block, 0, stream, p);
+                return hipGetLastError();
+            });
+        });
+    });
 }
 
 }  // namespace bp

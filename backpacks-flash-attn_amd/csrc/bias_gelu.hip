@@ -193,20 +193,18 @@ __global__ __launch_bounds__(256) void colsum_finish_kernel(const BiasGeluParams
     }
 }
 
-template <class ET>
-static hipError_t fwd_et(const BiasGeluParams &p, hipStream_t stream) {
+hipError_t launch_bias_gelu_fwd(const BiasGeluParams &p, int dtype, hipStream_t stream) {
     const int64_t nchunks = p.rows * (p.cols / 8);
     int64_t wgs = (nchunks + 255) / 256;
     if (wgs > 8192) wgs = 8192;   // 32 resident waves per CU x 256 CUs, then grid-stride
-    dim3 g((unsigned)wgs), t(256);
-    if (p.bias == nullptr) hipLaunchKernelGGL((bias_gelu_fwd_kernel<ET, false, false>), g, t, 0, stream, p);
-    else if (p.pre != nullptr) hipLaunchKernelGGL((bias_gelu_fwd_kernel<ET, true, true>), g, t, 0, stream, p);
-    else hipLaunchKernelGGL((bias_gelu_fwd_kernel<ET, true, false>), g, t, 0, stream, p);
-    return hipGetLastError();
-}
-
-hipError_t launch_bias_gelu_fwd(const BiasGeluParams &p, int dtype, hipStream_t stream) {
-    return dtype == 1 ? fwd_et<BF16>(p, stream) : fwd_et<F16>(p, stream);
+    const dim3 g((unsigned)wgs), t(256);
+    return with_dtype(dtype, [&](auto et) {
+        using ET = decltype(et);
+        if (p.bias == nullptr) hipLaunchKernelGGL((bias_gelu_fwd_kernel<ET, false, false>), g, t, 0, stream, p);
+        else if (p.pre != nullptr) hipLaunchKernelGGL((bias_gelu_fwd_kernel<ET, true, true>), g, t, 0, stream, p);
+        else hipLaunchKernelGGL((bias_gelu_fwd_kernel<ET, true, false>), g, t, 0, stream, p);
+        return hipGetLastError();
+    });
 }
 
 int bias_gelu_bwd_slices(int64_t rows, int cols) {
@@ -220,21 +218,19 @@ int bias_gelu_bwd_slices(int64_t rows, int cols) {
 // rows per trip of the dGELU kernel (two 16-byte loads each)
 constexpr int kGeluBwdRows = 4;
 
-template <class ET>
-static hipError_t bwd_et(const BiasGeluParams &p, bool gelu, hipStream_t stream) {
+hipError_t launch_bias_gelu_bwd(const BiasGeluParams &p, int dtype, bool gelu, hipStream_t stream) {
     const int chunks = (p.cols + 511) / 512;
     const int nsl = bias_gelu_bwd_slices(p.rows, p.cols);
-    dim3 g(chunks, nsl), t(256);
-    if (gelu) hipLaunchKernelGGL((bias_gelu_bwd_kernel<ET, true, kGeluBwdRows>), g, t, 0, stream, p);
-    else hipLaunchKernelGGL((bias_gelu_bwd_kernel<ET, false, 8>), g, t, 0, stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess || p.dbias == nullptr) return e;
-    hipLaunchKernelGGL((colsum_finish_kernel<ET>), dim3((p.cols + 63) / 64), dim3(256), 0, stream, p, nsl);
-    return hipGetLastError();
-}
-
-hipError_t launch_bias_gelu_bwd(const BiasGeluParams &p, int dtype, bool gelu, hipStream_t stream) {
-    return dtype == 1 ? bwd_et<BF16>(p, gelu, stream) : bwd_et<F16>(p, gelu, stream);
+    const dim3 g(chunks, nsl), t(256);
+    return with_dtype(dtype, [&](auto et) {
+        using ET = decltype(et);
+        if (gelu) hipLaunchKernelGGL((bias_gelu_bwd_kernel<ET, true, kGeluBwdRows>), g, t, 0, stream, p);
+        else hipLaunchKernelGGL((bias_gelu_bwd_kernel<ET, false, 8>), g, t, 0, stream, p);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess || p.dbias == nullptr) return e;
+        hipLaunchKernelGGL((colsum_finish_kernel<ET>), dim3((p.cols + 63) / 64), dim3(256), 0, stream, p, nsl);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace bp

@@ -65,7 +65,7 @@ inline bool dropout_args(float p, const uint64_t *rng_state, uint32_t &thr, floa
 // 16-byte friendly shapes take the LDS-DMA ring kernel; anything else (odd head dims, unaligned
 // views) the register-staged kernel with its element-wise loader.
 inline hipError_t dispatch_flash(const bp::FlashParams &p, int dtype, bool vec, hipStream_t st) {
-    return vec ? bp::launch_flash_fwd_dma(p, dtype, st) : bp::launch_flash_fwd(p, dtype, false, st);
+    return vec ? bp::launch_flash_fwd_dma(p, dtype, st) : bp::launch_flash_fwd(p, dtype, st);
 }
 
 // The q and k halves of a (B, S, 2, k, d_k) qk operand are 16-byte friendly.
@@ -272,13 +272,13 @@ static int sense_lse(const void *qk, float *lse_ws, int batch, int seqlen, int n
     p.pair = p.n_qtiles > 1 ? 1 : 0;
     p.scale_log2e = softmax_scale * bp::kLog2e;
     const bool vec = qk_vec16(d_k, qp, qk_two, qk_bs, qk_rs, qk_ss);
+    const bp::MixParams m = mix_params(qk, nullptr, nullptr, lse_ws, batch, seqlen, nsenses, d_k, 0, qk_bs, qk_rs, qk_two,
+                                       qk_ss, 0, 0, 0, 0, 0, softmax_scale, nullptr);
     switch (sense_route(d_k, seqlen, 0, vec, true, false, false)) {
         case SenseKernel::WideRing:     // d_k = 160 / 640: sense_wide_dma.hip
-            return launch_status(bp::launch_sense_lse_wide_dma(qp, kp, lse_ws, p.lse_stride, qk_bs, qk_rs, qk_ss, batch,
-                                                               seqlen, nsenses, d_k, p.scale_log2e, dtype, stream));
+            return launch_status(bp::launch_sense_lse_wide_dma(m, lse_ws, dtype, stream));
         case SenseKernel::WideStaged:   // wide senses (sense_wide.hip): the reference's vecs-4 / vecs-1 ablations
-            return launch_status(bp::launch_sense_lse_wide(qp, kp, lse_ws, p.lse_stride, qk_bs, qk_rs, qk_ss, batch,
-                                                           seqlen, nsenses, d_k, p.scale_log2e, dtype, vec, stream));
+            return launch_status(bp::launch_sense_lse_wide(m, lse_ws, dtype, vec, stream));
         case SenseKernel::NarrowRing:
         case SenseKernel::NarrowStaged: break;
     }
@@ -316,10 +316,12 @@ int bp_sense_alpha(const void *qk, void *alpha, float *lse_ws, int lse_ready,
     const uint16_t *qp = static_cast<const uint16_t *>(qk);
     const int64_t S = seqlen;
     const bool vec = qk_vec16(d_k, qp, qk_two_stride, qk_batch_stride, qk_row_stride, qk_sense_stride);
-    if (is_wide(sense_route(d_k, seqlen, 0, vec, true, false, false)))   // one alpha kernel for wide senses: sense_wide.hip
-        return launch_status(bp::launch_sense_alpha_wide(qp, qp + qk_two_stride, lse_ws, round_up(seqlen, 16), alpha,
-                                                         qk_batch_stride, qk_row_stride, qk_sense_stride, batch, seqlen,
-                                                         nsenses, d_k, softmax_scale * bp::kLog2e, dtype, vec, st));
+    if (is_wide(sense_route(d_k, seqlen, 0, vec, true, false, false))) {   // one alpha kernel for wide senses: sense_wide.hip
+        const bp::MixParams m = mix_params(qk, nullptr, nullptr, lse_ws, batch, seqlen, nsenses, d_k, 0, qk_batch_stride,
+                                           qk_row_stride, qk_two_stride, qk_sense_stride, 0, 0, 0, 0, 0, softmax_scale,
+                                           nullptr);
+        return launch_status(bp::launch_sense_alpha_wide(m, alpha, dtype, vec, st));
+    }
     return bp_attn_probs(qp, qp + qk_two_stride, lse_ws, alpha, batch, nsenses, d_k, seqlen, seqlen,
                          qk_batch_stride, qk_row_stride, qk_sense_stride,
                          qk_batch_stride, qk_row_stride, qk_sense_stride,

@@ -4,7 +4,47 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "../../include/bp_hip.h"
+#include "bp_common.h"
+
 namespace bp {
+
+// ---- launcher dispatch: a run-time value becomes a compile-time constant for a generic lambda --------------------------
+// f receives BF16{} / F16{}, a std::integral_constant or a std::bool_constant; the constants convert to template
+// arguments as they are (`kernel<decltype(et), kd, vec>`).  Only what a lambda body names is instantiated: a restriction
+// of the instantiation set is an `if constexpr` in the body.
+template <class F> hipError_t with_dtype(int dtype, F &&f) { return dtype == BP_DTYPE_BF16 ? f(BF16{}) : f(F16{}); }
+
+template <class F> hipError_t with_flag(bool b, F &&f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
+// 16-column steps of a head / sense width d <= 128: KD = ceil(d / 16), 8 for anything outside 1..7
+template <int KD = 1, class F> hipError_t with_kd(int d, F &&f) {
+    if constexpr (KD < 8)
+        if ((d + 15) / 16 != KD) return with_kd<KD + 1>(d, f);
+    return f(std::integral_constant<int, KD>{});
+}
+// 64-column V chunks of the trunk kernels (flash_fwd*.hip) for KD steps: 1, 1, 2, 2, 3, 3, 4, 4
+constexpr int trunk_nv(int kd) { return (kd + 1) / 2; }
+
+// the smallest N of the list with x <= N; `none` when x exceeds them all
+template <int N, int... Ns, class F> hipError_t with_bound(int x, hipError_t none, F &&f) {
+    if (x <= N) return f(std::integral_constant<int, N>{});
+    if constexpr (sizeof...(Ns) > 0) return with_bound<Ns...>(x, none, f);
+    else return none;
+}
+
+// workgroups of a persistent launch: one per CU of the current device (cached per thread; 256 when the query fails),
+// fewer when there are fewer jobs
+inline int persistent_grid(int njobs) {
+    thread_local int cached_dev = -1, cus = 0;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return njobs < 256 ? njobs : 256;
+    if (dev != cached_dev) {
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+        cached_dev = dev;
+    }
+    return njobs < cus ? njobs : cus;
+}
 
 // All strides are in ELEMENTS (16-bit elements for q/k/v/o/c, fp32 for lse).
 struct FlashParams {
@@ -213,7 +253,7 @@ struct BiasGeluParams {
 hipError_t launch_bias_gelu_fwd(const BiasGeluParams &p, int dtype, hipStream_t stream);
 hipError_t launch_bias_gelu_bwd(const BiasGeluParams &p, int dtype, bool gelu, hipStream_t stream);
 int bias_gelu_bwd_slices(int64_t rows, int cols);
-hipError_t launch_flash_fwd(const FlashParams &p, int dtype, bool vec, hipStream_t stream);
+hipError_t launch_flash_fwd(const FlashParams &p, int dtype, hipStream_t stream);
 // LDS-DMA ring version; needs 16-byte friendly shapes (vec)
 hipError_t launch_flash_fwd_dma(const FlashParams &p, int dtype, hipStream_t stream);
 hipError_t launch_attn_probs(const ProbsParams &p, int dtype, bool vec, hipStream_t stream);
@@ -222,20 +262,15 @@ hipError_t launch_sense_mix(const MixParams &p, int dtype, bool vec_qk, bool vec
 hipError_t launch_sense_mix_dma(const MixParams &p, int dtype, hipStream_t stream);
 // wide senses, 128 < d_k <= kWideMaxDk (sense_wide.hip): the reference's few-sense ablations (vecs-4: 160, vecs-1: 640)
 constexpr int kWideMaxDk = 640;
-hipError_t launch_sense_lse_wide(const void *q, const void *k, float *lse, int64_t lse_stride, int64_t qk_bs,
-                                 int64_t qk_rs, int64_t qk_ss, int b, int s, int nsenses, int dk, float scale_log2e,
-                                 int dtype, bool vec, hipStream_t stream);
-hipError_t launch_sense_alpha_wide(const void *q, const void *k, float *lse, int64_t lse_stride, void *alpha,
-                                   int64_t qk_bs, int64_t qk_rs, int64_t qk_ss, int b, int s, int nsenses, int dk,
-                                   float scale_log2e, int dtype, bool vec, hipStream_t stream);
+// the LSE pre-pass and alpha take the mix operands without content (d_out = 0): `lse` is written, alpha reads p.lse
+hipError_t launch_sense_lse_wide(const MixParams &p, float *lse, int dtype, bool vec, hipStream_t stream);
+hipError_t launch_sense_alpha_wide(const MixParams &p, void *alpha, int dtype, bool vec, hipStream_t stream);
 hipError_t launch_sense_mix_wide(const MixParams &p, int dtype, bool vec_qk, bool vec_c, hipStream_t stream);
 // LDS-DMA ring versions for the reference's two few-sense configurations exactly (d_k = 160 / 640, 16-byte friendly
 // operands, s % 32 == 0): sense_wide_dma.hip
 bool sense_wide_dma_takes(int s, int dk, int dout, bool vec_qk, bool vec_c, bool weighted);
 hipError_t launch_sense_mix_wide_dma(const MixParams &p, int dtype, hipStream_t stream);
-hipError_t launch_sense_lse_wide_dma(const void *q, const void *k, float *lse, int64_t lse_stride, int64_t qk_bs,
-                                     int64_t qk_rs, int64_t qk_ss, int b, int s, int nsenses, int dk, float scale_log2e,
-                                     int dtype, hipStream_t stream);
+hipError_t launch_sense_lse_wide_dma(const MixParams &p, float *lse, int dtype, hipStream_t stream);
 
 // Single-query decode against a cache (decode_core.h): bp_flash_decode (groups = heads; value rows from the V half of the
 // cache) and bp_sense_decode (groups = senses; value rows from a table through a row index).  Element strides.

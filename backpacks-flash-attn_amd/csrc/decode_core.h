@@ -306,20 +306,17 @@ hipError_t launch_decode_pair(const DecodeParams &p, int nout, hipStream_t st) {
     return hipGetLastError();
 }
 
-template <class ET, bool SENSE>
-hipError_t launch_decode_dtype(const DecodeParams &p, int nout, hipStream_t st) {
-    const int qc = p.dk >> 3;
-    if (qc <= 1) return launch_decode_pair<ET, 1, 1, SENSE>(p, nout, st);
-    if (qc <= 2) return launch_decode_pair<ET, 2, 1, SENSE>(p, nout, st);
-    if (qc <= 4) return launch_decode_pair<ET, 4, 1, SENSE>(p, nout, st);
-    if (qc <= 8) return launch_decode_pair<ET, 8, 1, SENSE>(p, nout, st);
-    if (qc <= 16) return launch_decode_pair<ET, 16, 1, SENSE>(p, nout, st);
-    if constexpr (SENSE) {
-        if (qc <= 32) return launch_decode_pair<ET, 32, 1, SENSE>(p, nout, st);
-        if (qc <= 64) return launch_decode_pair<ET, 64, 1, SENSE>(p, nout, st);
-        if (qc <= 128) return launch_decode_pair<ET, 64, 2, SENSE>(p, nout, st);
-    }
-    return hipErrorNotSupported;
+// G: 8-column chunks of the query row per key group (a power of two); the trunk (d_h <= 128) needs up to 16, the senses
+// (d_k <= 640) go on to 64 and past that take the row in NQ = 2 passes
+template <bool SENSE>
+hipError_t launch_decode(const DecodeParams &p, int dtype, int nout, hipStream_t st) {
+    return with_dtype(dtype, [&](auto et) {
+        return with_bound<1, 2, 4, 8, 16, 32, 64, 128>(p.dk >> 3, hipErrorNotSupported, [&](auto qc) {
+            constexpr int G = qc < 64 ? int(qc) : 64;
+            if constexpr (!SENSE && qc > 16) return hipErrorNotSupported;
+            else return launch_decode_pair<decltype(et), G, qc / G, SENSE>(p, nout, st);
+        });
+    });
 }
 
 }  // namespace bp

@@ -817,34 +817,20 @@ static hipError_t launch_drop(const FlashBwdParams &p, hipStream_t stream) {
     return hipGetLastError();
 }
 
-template <class ET, int KD>
-static hipError_t launch_one(const FlashBwdParams &p, hipStream_t stream) {
-    const bool drop = p.drop_thr != 0u;
-    if constexpr (KD == 4 || KD == 8) {
-        if (p.d == KD * 16)
-            return drop ? launch_drop<ET, KD, true, true>(p, stream) : launch_drop<ET, KD, true, false>(p, stream);
-    }
-    return drop ? launch_drop<ET, KD, false, true>(p, stream) : launch_drop<ET, KD, false, false>(p, stream);
-}
-
-template <class ET>
-static hipError_t launch_et(const FlashBwdParams &p, hipStream_t stream) {
-    switch ((p.d + 15) / 16) {
-        case 1: return launch_one<ET, 1>(p, stream);
-        case 2: return launch_one<ET, 2>(p, stream);
-        case 3: return launch_one<ET, 3>(p, stream);
-        case 4: return launch_one<ET, 4>(p, stream);
-        case 5: return launch_one<ET, 5>(p, stream);   // d_h = 80 (Mini)
-        case 6: return launch_one<ET, 6>(p, stream);
-        case 7: return launch_one<ET, 7>(p, stream);
-        default: return launch_one<ET, 8>(p, stream);
-    }
-}
-
 // head_dim % 8 == 0 and <= 128 (the trunk's 64 / 80 and the senses' 48/40/24), 16-byte friendly strides.
 hipError_t launch_flash_bwd(const FlashBwdParams &p, int dtype, hipStream_t stream) {
     if (p.d > 128) return hipErrorNotSupported;
-    return dtype == 1 ? launch_et<BF16>(p, stream) : launch_et<F16>(p, stream);
+    return with_dtype(dtype, [&](auto et) {
+        return with_kd(p.d, [&](auto kd) {
+            return with_flag(p.drop_thr != 0u, [&](auto drop) {
+                using ET = decltype(et);
+                if constexpr (kd == 4 || kd == 8) {
+                    if (p.d == kd * 16) return launch_drop<ET, kd, true, drop>(p, stream);
+                }
+                return launch_drop<ET, kd, false, drop>(p, stream);
+            });
+        });
+    });
 }
 
 #ifdef BP_BWD_PROFILE

@@ -8,8 +8,7 @@ namespace bp {
 int decode_nsplit(int batch, int groups, int max_seqlen) { return decode_nsplit_impl(batch, groups, max_seqlen); }
 
 hipError_t launch_flash_decode(const DecodeParams &p, int dtype, hipStream_t stream) {
-    const int nout = p.b * p.groups;
-    return dtype == 1 ? launch_decode_dtype<BF16, false>(p, nout, stream) : launch_decode_dtype<F16, false>(p, nout, stream);
+    return launch_decode<false>(p, dtype, p.b * p.groups, stream);
 }
 
 }  // namespace bp

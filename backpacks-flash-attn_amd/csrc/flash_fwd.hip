@@ -34,7 +34,7 @@ struct FlashCfg {
     static constexpr int V_ITERS = HAS_V ? (BN * VCH + NT - 1) / NT : 0;
 };
 
-template <class ET, int KD, int NV, bool HAS_V, bool VEC>
+template <class ET, int KD, int NV, bool HAS_V>
 __global__ __launch_bounds__(256) void flash_fwd_kernel(const FlashParams p) {
     using C = FlashCfg<KD, NV, HAS_V>;
     using E = Elem<ET>;
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256) void flash_fwd_kernel(const FlashParams p) {
         u32x4 v = {0u, 0u, 0u, 0u};
         if (my_q < seq_q && col < p.d) {
             const uint16_t *row = qg + (int64_t)my_q * p.q_rs;
-            v = VEC ? ld_global_16B(row + col) : ld_global_8x2B(row, col, p.d);
+            v = ld_global_8x2B(row, col, p.d);
         }
         qf[s] = v;
     }
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(256) void flash_fwd_kernel(const FlashParams p) {
             u32x4 v = {0u, 0u, 0u, 0u};
             if (c < C::BN * C::KCH && key < seq_k && ch * 8 < p.d) {
                 const uint16_t *r = kg + (int64_t)key * p.k_rs;
-                v = VEC ? ld_global_16B(r + ch * 8) : ld_global_8x2B(r, ch * 8, p.d);
+                v = ld_global_8x2B(r, ch * 8, p.d);
             }
             kreg[i] = v;
         }
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(256) void flash_fwd_kernel(const FlashParams p) {
                 u32x4 v = {0u, 0u, 0u, 0u};   // rows past the sequence MUST be zero: 0 * NaN = NaN in PV
                 if (c < C::BN * C::VCH && key < seq_k && ch * 8 < p.d) {
                     const uint16_t *r = vg + (int64_t)key * p.v_rs;
-                    v = VEC ? ld_global_16B(r + ch * 8) : ld_global_8x2B(r, ch * 8, p.d);
+                    v = ld_global_8x2B(r, ch * 8, p.d);
                 }
                 vreg[i] = v;
             }
@@ -267,51 +267,25 @@ __global__ __launch_bounds__(256) void flash_fwd_kernel(const FlashParams p) {
                     const int d0 = n * 32 + 8 * g + 4 * hh;
                     const float x0 = acc[n][4 * g + 0] * inv, x1 = acc[n][4 * g + 1] * inv;
                     const float x2 = acc[n][4 * g + 2] * inv, x3 = acc[n][4 * g + 3] * inv;
-                    if (VEC) {
-                        if (d0 < p.d) {
-                            u32x2 w = {E::pack2(x0, x1), E::pack2(x2, x3)};
-                            *reinterpret_cast<u32x2 *>(og + d0) = w;
-                        }
-                    } else {
-                        if (d0 + 0 < p.d) og[d0 + 0] = E::from_float(x0);
-                        if (d0 + 1 < p.d) og[d0 + 1] = E::from_float(x1);
-                        if (d0 + 2 < p.d) og[d0 + 2] = E::from_float(x2);
-                        if (d0 + 3 < p.d) og[d0 + 3] = E::from_float(x3);
-                    }
+                    if (d0 + 0 < p.d) og[d0 + 0] = E::from_float(x0);
+                    if (d0 + 1 < p.d) og[d0 + 1] = E::from_float(x1);
+                    if (d0 + 2 < p.d) og[d0 + 2] = E::from_float(x2);
+                    if (d0 + 3 < p.d) og[d0 + 3] = E::from_float(x3);
                 }
         }
     }
 }
 
-template <class ET, int KD, int NV, bool HAS_V>
-static hipError_t launch_one(const FlashParams &p, bool vec, hipStream_t stream) {
-    const int grid = xcd_grid(p.b * p.h, p.n_qtiles);
-    if (vec)
-        hipLaunchKernelGGL((flash_fwd_kernel<ET, KD, NV, HAS_V, true>), dim3(grid), dim3(256), 0, stream, p);
-    else
-        hipLaunchKernelGGL((flash_fwd_kernel<ET, KD, NV, HAS_V, false>), dim3(grid), dim3(256), 0, stream, p);
-    return hipGetLastError();
-}
-
-template <class ET, bool HAS_V>
-static hipError_t launch_dim(const FlashParams &p, bool vec, hipStream_t stream) {
-    const int kd = (p.d + 15) / 16;
-    switch (kd) {
-        case 1: return launch_one<ET, 1, 1, HAS_V>(p, vec, stream);
-        case 2: return launch_one<ET, 2, 1, HAS_V>(p, vec, stream);
-        case 3: return launch_one<ET, 3, 2, HAS_V>(p, vec, stream);
-        case 4: return launch_one<ET, 4, 2, HAS_V>(p, vec, stream);
-        case 5: return launch_one<ET, 5, 3, HAS_V>(p, vec, stream);
-        case 6: return launch_one<ET, 6, 3, HAS_V>(p, vec, stream);
-        case 7: return launch_one<ET, 7, 4, HAS_V>(p, vec, stream);
-        default: return launch_one<ET, 8, 4, HAS_V>(p, vec, stream);
-    }
-}
-
-hipError_t launch_flash_fwd(const FlashParams &p, int dtype, bool vec, hipStream_t stream) {
-    const bool has_v = p.v != nullptr;
-    if (dtype == 1) return has_v ? launch_dim<BF16, true>(p, vec, stream) : launch_dim<BF16, false>(p, vec, stream);
-    return has_v ? launch_dim<F16, true>(p, vec, stream) : launch_dim<F16, false>(p, vec, stream);
+hipError_t launch_flash_fwd(const FlashParams &p, int dtype, hipStream_t stream) {
+    const dim3 grid(xcd_grid(p.b * p.h, p.n_qtiles)), block(256);
+    return with_dtype(dtype, [&](auto et) {
+        return with_flag(p.v != nullptr, [&](auto has_v) {
+            return with_kd(p.d, [&](auto kd) {
+                hipLaunchKernelGGL((flash_fwd_kernel<decltype(et), kd, trunk_nv(kd), has_v>), grid, block, 0, stream, p);
+                return hipGetLastError();
+            });
+        });
+    });
 }
 
 }  // namespace bp

@@ -553,8 +553,9 @@ static hipError_t launch_one(const FlashParams &p, hipStream_t stream) {
     return hipGetLastError();
 }
 
-template <class ET, int KD, int NV, bool HAS_V, bool DROP>
+template <class ET, int KD, bool HAS_V, bool DROP>
 static hipError_t launch_kd(const FlashParams &p, hipStream_t stream) {
+    constexpr int NV = trunk_nv(KD);
     using C = FlashDmaCfg<KD, NV, HAS_V>;
     if constexpr (KD == 4 || KD == 8) {
         if (p.d * 2 == C::KROW) return launch_one<ET, KD, NV, HAS_V, true, DROP>(p, stream);
@@ -562,31 +563,16 @@ static hipError_t launch_kd(const FlashParams &p, hipStream_t stream) {
     return launch_one<ET, KD, NV, HAS_V, false, DROP>(p, stream);
 }
 
-template <class ET, bool HAS_V, bool DROP>
-static hipError_t launch_dim(const FlashParams &p, hipStream_t stream) {
-    switch ((p.d + 15) / 16) {
-        case 1: return launch_kd<ET, 1, 1, HAS_V, DROP>(p, stream);
-        case 2: return launch_kd<ET, 2, 1, HAS_V, DROP>(p, stream);
-        case 3: return launch_kd<ET, 3, 2, HAS_V, DROP>(p, stream);
-        case 4: return launch_kd<ET, 4, 2, HAS_V, DROP>(p, stream);
-        case 5: return launch_kd<ET, 5, 3, HAS_V, DROP>(p, stream);
-        case 6: return launch_kd<ET, 6, 3, HAS_V, DROP>(p, stream);
-        case 7: return launch_kd<ET, 7, 4, HAS_V, DROP>(p, stream);
-        default: return launch_kd<ET, 8, 4, HAS_V, DROP>(p, stream);
-    }
-}
-
-template <class ET>
-static hipError_t launch_et(const FlashParams &p, hipStream_t stream) {
-    if (p.v == nullptr) return launch_dim<ET, false, false>(p, stream);
-    if (p.drop_thr != 0u) return launch_dim<ET, true, true>(p, stream);
-    return launch_dim<ET, true, false>(p, stream);
-}
-
 // Requires head_dim % 8 == 0, 16-byte aligned bases, strides multiples of 8, seq_k >= 1 per sequence
-// handled inside (nkb == 0 issues nothing).
+// handled inside (nkb == 0 issues nothing).  Dropout only with a V operand.
 hipError_t launch_flash_fwd_dma(const FlashParams &p, int dtype, hipStream_t stream) {
-    return dtype == 1 ? launch_et<BF16>(p, stream) : launch_et<F16>(p, stream);
+    return with_dtype(dtype, [&](auto et) {
+        return with_kd(p.d, [&](auto kd) {
+            using ET = decltype(et);
+            if (p.v == nullptr) return launch_kd<ET, kd, false, false>(p, stream);
+            return with_flag(p.drop_thr != 0u, [&](auto drop) { return launch_kd<ET, kd, true, drop>(p, stream); });
+        });
+    });
 }
 
 #ifdef BP_FWD_PROFILE

@@ -8,7 +8,7 @@
 namespace bp {
 
 hipError_t launch_sense_decode(const DecodeParams &p, int dtype, hipStream_t stream) {
-    return dtype == 1 ? launch_decode_dtype<BF16, true>(p, p.b, stream) : launch_decode_dtype<F16, true>(p, p.b, stream);
+    return launch_decode<true>(p, dtype, p.b, stream);
 }
 
 }  // namespace bp

@@ -228,34 +228,18 @@ __global__ __launch_bounds__(512) void sense_mix_kernel(const MixParams p) {
         }
 }
 
-template <class ET, int KD>
-static hipError_t launch_kd(const MixParams &p, bool vq, bool vc, hipStream_t stream) {
-    const int grid = xcd_grid(p.b * p.n_chunks, p.n_qtiles);
-    dim3 g(grid), t(512);
-    if (vq && vc) hipLaunchKernelGGL((sense_mix_kernel<ET, KD, true, true>), g, t, 0, stream, p);
-    else if (vq) hipLaunchKernelGGL((sense_mix_kernel<ET, KD, true, false>), g, t, 0, stream, p);
-    else if (vc) hipLaunchKernelGGL((sense_mix_kernel<ET, KD, false, true>), g, t, 0, stream, p);
-    else hipLaunchKernelGGL((sense_mix_kernel<ET, KD, false, false>), g, t, 0, stream, p);
-    return hipGetLastError();
-}
-
-template <class ET>
-static hipError_t launch_et(const MixParams &p, bool vq, bool vc, hipStream_t stream) {
-    const int kd = (p.dk + 15) / 16;
-    switch (kd) {
-        case 1: return launch_kd<ET, 1>(p, vq, vc, stream);
-        case 2: return launch_kd<ET, 2>(p, vq, vc, stream);
-        case 3: return launch_kd<ET, 3>(p, vq, vc, stream);
-        case 4: return launch_kd<ET, 4>(p, vq, vc, stream);
-        case 5: return launch_kd<ET, 5>(p, vq, vc, stream);
-        case 6: return launch_kd<ET, 6>(p, vq, vc, stream);
-        case 7: return launch_kd<ET, 7>(p, vq, vc, stream);
-        default: return launch_kd<ET, 8>(p, vq, vc, stream);
-    }
-}
-
 hipError_t launch_sense_mix(const MixParams &p, int dtype, bool vec_qk, bool vec_c, hipStream_t stream) {
-    return dtype == 1 ? launch_et<BF16>(p, vec_qk, vec_c, stream) : launch_et<F16>(p, vec_qk, vec_c, stream);
+    const dim3 grid(xcd_grid(p.b * p.n_chunks, p.n_qtiles)), block(512);
+    return with_dtype(dtype, [&](auto et) {
+        return with_kd(p.dk, [&](auto kd) {
+            return with_flag(vec_qk, [&](auto vq) {
+                return with_flag(vec_c, [&](auto vc) {
+                    hipLaunchKernelGGL((sense_mix_kernel<decltype(et), kd, vq, vc>), grid, block, 0, stream, p);
+                    return hipGetLastError();
+                });
+            });
+        });
+    });
 }
 
 }  // namespace bp

@@ -849,73 +849,33 @@ __global__ __launch_bounds__(256) void sense_dk_kernel(const SenseGradParams p) 
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------
-static int persistent_grid() {
-    thread_local int cached_dev = -1, cus = 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    if (dev != cached_dev) {
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        cached_dev = dev;
-    }
-    return cus;
-}
-
-template <class ET, int KD>
-static hipError_t launch_dc_kd(MixBwdParams p, hipStream_t stream) {
+hipError_t launch_sense_mix_dc(const MixBwdParams &params, int dtype, hipStream_t stream) {
+    MixBwdParams p = params;
     const hipError_t armed = arm_mix_queues(p.queues, stream);   // sense_mix_dma.hip
     if (armed != hipSuccess) return armed;
-    const int njobs = p.b * p.n_chunks * p.n_ktiles;
-    const int cus = persistent_grid();
-    dim3 g(njobs < cus ? njobs : cus), t(512);
-    if (p.dout_cols % 256 == 0) hipLaunchKernelGGL((sense_mix_dc_kernel<ET, KD, true>), g, t, 0, stream, p);
-    else hipLaunchKernelGGL((sense_mix_dc_kernel<ET, KD, false>), g, t, 0, stream, p);
-    return hipGetLastError();
-}
-
-template <class ET>
-static hipError_t launch_dc_et(const MixBwdParams &p, hipStream_t stream) {
-    switch ((p.dk + 15) / 16) {
-        case 1: return launch_dc_kd<ET, 1>(p, stream);
-        case 2: return launch_dc_kd<ET, 2>(p, stream);
-        case 3: return launch_dc_kd<ET, 3>(p, stream);
-        case 4: return launch_dc_kd<ET, 4>(p, stream);
-        case 5: return launch_dc_kd<ET, 5>(p, stream);
-        case 6: return launch_dc_kd<ET, 6>(p, stream);
-        case 7: return launch_dc_kd<ET, 7>(p, stream);
-        default: return launch_dc_kd<ET, 8>(p, stream);
-    }
-}
-
-hipError_t launch_sense_mix_dc(const MixBwdParams &p, int dtype, hipStream_t stream) {
-    return dtype == 1 ? launch_dc_et<BF16>(p, stream) : launch_dc_et<F16>(p, stream);
-}
-
-template <class ET, int KD>
-static hipError_t launch_grad_kd(const SenseGradParams &p, hipStream_t stream) {
-    hipLaunchKernelGGL((sense_dq_kernel<ET, KD>), dim3(p.b * p.nsenses), dim3(256), 0, stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    const int per_bl = ((p.s < p.t0 + 128 ? p.s : p.t0 + 128) + 127) / 128;
-    hipLaunchKernelGGL((sense_dk_kernel<ET, KD>), dim3(p.b * p.nsenses * per_bl), dim3(256), 0, stream, p);
-    return hipGetLastError();
-}
-
-template <class ET>
-static hipError_t launch_grad_et(const SenseGradParams &p, hipStream_t stream) {
-    switch ((p.dk + 15) / 16) {
-        case 1: return launch_grad_kd<ET, 1>(p, stream);
-        case 2: return launch_grad_kd<ET, 2>(p, stream);
-        case 3: return launch_grad_kd<ET, 3>(p, stream);
-        case 4: return launch_grad_kd<ET, 4>(p, stream);
-        case 5: return launch_grad_kd<ET, 5>(p, stream);
-        case 6: return launch_grad_kd<ET, 6>(p, stream);
-        case 7: return launch_grad_kd<ET, 7>(p, stream);
-        default: return launch_grad_kd<ET, 8>(p, stream);
-    }
+    const dim3 g(persistent_grid(p.b * p.n_chunks * p.n_ktiles)), t(512);
+    return with_dtype(dtype, [&](auto et) {
+        return with_kd(p.dk, [&](auto kd) {
+            return with_flag(p.dout_cols % 256 == 0, [&](auto full) {
+                hipLaunchKernelGGL((sense_mix_dc_kernel<decltype(et), kd, full>), g, t, 0, stream, p);
+                return hipGetLastError();
+            });
+        });
+    });
 }
 
 hipError_t launch_sense_dq_dk(const SenseGradParams &p, int dtype, hipStream_t stream) {
-    return dtype == 1 ? launch_grad_et<BF16>(p, stream) : launch_grad_et<F16>(p, stream);
+    const int per_bl = ((p.s < p.t0 + 128 ? p.s : p.t0 + 128) + 127) / 128;
+    return with_dtype(dtype, [&](auto et) {
+        return with_kd(p.dk, [&](auto kd) {
+            using ET = decltype(et);
+            hipLaunchKernelGGL((sense_dq_kernel<ET, kd>), dim3(p.b * p.nsenses), dim3(256), 0, stream, p);
+            hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL((sense_dk_kernel<ET, kd>), dim3(p.b * p.nsenses * per_bl), dim3(256), 0, stream, p);
+            return hipGetLastError();
+        });
+    });
 }
 
 }  // namespace bp

@@ -677,49 +677,6 @@ hipError_t arm_mix_queues(MixQueues *&queues, hipStream_t stream) {
     return hipGetLastError();
 }
 
-static int mix_persistent_grid() {
-    thread_local int cached_dev = -1, cus = 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    if (dev != cached_dev) {
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        cached_dev = dev;
-    }
-    return cus;
-}
-
-template <class ET, int KD>
-static hipError_t launch_kd(MixParams p, hipStream_t stream) {
-    const hipError_t armed = arm_mix_queues(p.queues, stream);
-    if (armed != hipSuccess) return armed;
-    const int njobs = p.b * p.n_chunks * p.n_qtiles;
-    const int cus = mix_persistent_grid();
-    dim3 g(njobs < cus ? njobs : cus), t(512);   // 120 KB of LDS: one workgroup per CU
-    if (p.row_index != nullptr) {   // (bp_api.hip: never together with key weights)
-        if (p.dout % 256 == 0) hipLaunchKernelGGL((sense_mix_dma_kernel<ET, KD, true, false, true>), g, t, 0, stream, p);
-        else hipLaunchKernelGGL((sense_mix_dma_kernel<ET, KD, false, false, true>), g, t, 0, stream, p);
-    } else if (p.kw != nullptr) {
-        if (p.dout % 256 == 0) hipLaunchKernelGGL((sense_mix_dma_kernel<ET, KD, true, true>), g, t, 0, stream, p);
-        else hipLaunchKernelGGL((sense_mix_dma_kernel<ET, KD, false, true>), g, t, 0, stream, p);
-    } else if (p.dout % 256 == 0) hipLaunchKernelGGL((sense_mix_dma_kernel<ET, KD, true, false>), g, t, 0, stream, p);
-    else hipLaunchKernelGGL((sense_mix_dma_kernel<ET, KD, false, false>), g, t, 0, stream, p);
-    return hipGetLastError();
-}
-
-template <class ET>
-static hipError_t launch_et(const MixParams &p, hipStream_t stream) {
-    switch ((p.dk + 15) / 16) {
-        case 1: return launch_kd<ET, 1>(p, stream);
-        case 2: return launch_kd<ET, 2>(p, stream);
-        case 3: return launch_kd<ET, 3>(p, stream);
-        case 4: return launch_kd<ET, 4>(p, stream);
-        case 5: return launch_kd<ET, 5>(p, stream);
-        case 6: return launch_kd<ET, 6>(p, stream);
-        case 7: return launch_kd<ET, 7>(p, stream);
-        default: return launch_kd<ET, 8>(p, stream);
-    }
-}
-
 #ifdef BP_MIX_PROFILE
 extern "C" int bp_dev_mix_prof(unsigned long long *host) {
     return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_mix_prof), sizeof(g_mix_prof)) == hipSuccess ? 0 : -1;
@@ -727,8 +684,23 @@ extern "C" int bp_dev_mix_prof(unsigned long long *host) {
 #endif
 
 // Requires: d_k % 8 == 0, d_out % 8 == 0, all bases 16-byte aligned, all strides multiples of 8, n_qtiles <= 256.
-hipError_t launch_sense_mix_dma(const MixParams &p, int dtype, hipStream_t stream) {
-    return dtype == 1 ? launch_et<BF16>(p, stream) : launch_et<F16>(p, stream);
+hipError_t launch_sense_mix_dma(const MixParams &params, int dtype, hipStream_t stream) {
+    MixParams p = params;
+    const hipError_t armed = arm_mix_queues(p.queues, stream);
+    if (armed != hipSuccess) return armed;
+    const dim3 g(persistent_grid(p.b * p.n_chunks * p.n_qtiles)), t(512);   // 120 KB of LDS: one workgroup per CU
+    return with_dtype(dtype, [&](auto et) {
+        return with_kd(p.dk, [&](auto kd) {
+            return with_flag(p.dout % 256 == 0, [&](auto full) {
+                using ET = decltype(et);
+                if (p.row_index != nullptr)   // (bp_api.hip: never together with key weights)
+                    hipLaunchKernelGGL((sense_mix_dma_kernel<ET, kd, full, false, true>), g, t, 0, stream, p);
+                else if (p.kw != nullptr) hipLaunchKernelGGL((sense_mix_dma_kernel<ET, kd, full, true>), g, t, 0, stream, p);
+                else hipLaunchKernelGGL((sense_mix_dma_kernel<ET, kd, full, false>), g, t, 0, stream, p);
+                return hipGetLastError();
+            });
+        });
+    });
 }
 
 }  // namespace bp

@@ -411,74 +411,54 @@ __global__ __launch_bounds__(256) void sense_mix_wide_kernel(const MixParams p) 
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------
-static WideParams wide_params(const void *q, const void *k, float *lse, int64_t lse_stride, int64_t qk_bs, int64_t qk_rs,
-                              int64_t qk_ss, int b, int s, int nsenses, int dk, float scale_log2e) {
-    WideParams w;
-    w.q = static_cast<const uint16_t *>(q); w.k = static_cast<const uint16_t *>(k);
-    w.qk_bs = qk_bs; w.qk_rs = qk_rs; w.qk_ss = qk_ss;
-    w.lse = lse; w.lse_stride = lse_stride;
-    w.b = b; w.s = s; w.nsenses = nsenses; w.dk = dk; w.scale_log2e = scale_log2e;
-    return w;
+// the LSE / alpha kernels' operands out of the mix operands; `lse` is written (LSE) or read (alpha)
+static WideParams wide_params(const MixParams &p, float *lse) {
+    return WideParams{static_cast<const uint16_t *>(p.q), static_cast<const uint16_t *>(p.k), p.qk_bs, p.qk_rs, p.qk_ss,
+                      lse, p.lse_stride, p.b, p.s, p.nsenses, p.dk, p.scale_log2e};
 }
 
-// one instantiation per (dtype, alignment class, width class)
-#define BP_WIDE_DISPATCH(KERNEL, DTYPE, VEC, DK, ...)                                                          \
-    do {                                                                                                       \
-        const bool small_ = (DK) <= 16 * kWideSmallKd;                                                         \
-        if ((DTYPE) == 1) {                                                                                    \
-            if (VEC) { if (small_) hipLaunchKernelGGL((KERNEL<BF16, true, kWideSmallKd>), __VA_ARGS__);        \
-                       else hipLaunchKernelGGL((KERNEL<BF16, true, kWideLargeKd>), __VA_ARGS__); }             \
-            else { if (small_) hipLaunchKernelGGL((KERNEL<BF16, false, kWideSmallKd>), __VA_ARGS__);           \
-                   else hipLaunchKernelGGL((KERNEL<BF16, false, kWideLargeKd>), __VA_ARGS__); }                \
-        } else {                                                                                               \
-            if (VEC) { if (small_) hipLaunchKernelGGL((KERNEL<F16, true, kWideSmallKd>), __VA_ARGS__);         \
-                       else hipLaunchKernelGGL((KERNEL<F16, true, kWideLargeKd>), __VA_ARGS__); }              \
-            else { if (small_) hipLaunchKernelGGL((KERNEL<F16, false, kWideSmallKd>), __VA_ARGS__);            \
-                   else hipLaunchKernelGGL((KERNEL<F16, false, kWideLargeKd>), __VA_ARGS__); }                 \
-        }                                                                                                      \
-    } while (0)
-
-hipError_t launch_sense_lse_wide(const void *q, const void *k, float *lse, int64_t lse_stride, int64_t qk_bs,
-                                 int64_t qk_rs, int64_t qk_ss, int b, int s, int nsenses, int dk, float scale_log2e,
-                                 int dtype, bool vec, hipStream_t stream) {
-    const WideParams w = wide_params(q, k, lse, lse_stride, qk_bs, qk_rs, qk_ss, b, s, nsenses, dk, scale_log2e);
-    const dim3 grid(xcd_grid(b * nsenses, (s + 127) / 128)), block(256);
-    BP_WIDE_DISPATCH(sense_lse_wide_kernel, dtype, vec, dk, grid, block, 0, stream, w);
-    return hipGetLastError();
+// one instantiation per (dtype, alignment class, width class): f(element type, VEC, KDT)
+template <class F> static hipError_t with_wide(int dtype, bool vec, int dk, F &&f) {
+    return with_dtype(dtype, [&](auto et) {
+        return with_flag(vec, [&](auto v) {
+            if (dk <= 16 * kWideSmallKd) return f(et, v, std::integral_constant<int, kWideSmallKd>{});
+            return f(et, v, std::integral_constant<int, kWideLargeKd>{});
+        });
+    });
 }
 
-hipError_t launch_sense_alpha_wide(const void *q, const void *k, float *lse, int64_t lse_stride, void *alpha,
-                                   int64_t qk_bs, int64_t qk_rs, int64_t qk_ss, int b, int s, int nsenses, int dk,
-                                   float scale_log2e, int dtype, bool vec, hipStream_t stream) {
+hipError_t launch_sense_lse_wide(const MixParams &p, float *lse, int dtype, bool vec, hipStream_t stream) {
+    const WideParams w = wide_params(p, lse);
+    const dim3 grid(xcd_grid(p.b * p.nsenses, (p.s + 127) / 128)), block(256);
+    return with_wide(dtype, vec, p.dk, [&](auto et, auto v, auto kdt) {
+        hipLaunchKernelGGL((sense_lse_wide_kernel<decltype(et), v, kdt>), grid, block, 0, stream, w);
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_sense_alpha_wide(const MixParams &p, void *alpha, int dtype, bool vec, hipStream_t stream) {
     WideAlphaParams pa;
-    pa.w = wide_params(q, k, lse, lse_stride, qk_bs, qk_rs, qk_ss, b, s, nsenses, dk, scale_log2e);
+    pa.w = wide_params(p, const_cast<float *>(p.lse));
     pa.alpha = static_cast<uint16_t *>(alpha);
-    pa.vec_store = (s % 4 == 0) && ((reinterpret_cast<uintptr_t>(alpha) & 7) == 0);
-    const dim3 grid(xcd_grid(b * nsenses, (s + 127) / 128)), block(256);
-    BP_WIDE_DISPATCH(sense_alpha_wide_kernel, dtype, vec, dk, grid, block, 0, stream, pa);
-    return hipGetLastError();
-}
-
-template <class ET, int KDT>
-static hipError_t launch_mix_wide_et(const MixParams &p, bool vq, bool vc, hipStream_t stream) {
-    using W = WideCfgT<KDT>;
-    const int n_qtiles = (p.s + W::BM - 1) / W::BM;
-    const int n_chunks = (p.dout + W::NB * 32 - 1) / (W::NB * 32);
-    const dim3 grid(xcd_grid(p.b * n_chunks, n_qtiles)), block(W::NT);
-    if (vq && vc) hipLaunchKernelGGL((sense_mix_wide_kernel<ET, true, true, KDT>), grid, block, 0, stream, p);
-    else if (vq) hipLaunchKernelGGL((sense_mix_wide_kernel<ET, true, false, KDT>), grid, block, 0, stream, p);
-    else if (vc) hipLaunchKernelGGL((sense_mix_wide_kernel<ET, false, true, KDT>), grid, block, 0, stream, p);
-    else hipLaunchKernelGGL((sense_mix_wide_kernel<ET, false, false, KDT>), grid, block, 0, stream, p);
-    return hipGetLastError();
+    pa.vec_store = (p.s % 4 == 0) && ((reinterpret_cast<uintptr_t>(alpha) & 7) == 0);
+    const dim3 grid(xcd_grid(p.b * p.nsenses, (p.s + 127) / 128)), block(256);
+    return with_wide(dtype, vec, p.dk, [&](auto et, auto v, auto kdt) {
+        hipLaunchKernelGGL((sense_alpha_wide_kernel<decltype(et), v, kdt>), grid, block, 0, stream, pa);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_sense_mix_wide(const MixParams &p, int dtype, bool vec_qk, bool vec_c, hipStream_t stream) {
-    const bool small_ = p.dk <= 16 * kWideSmallKd;
-    if (dtype == 1)
-        return small_ ? launch_mix_wide_et<BF16, kWideSmallKd>(p, vec_qk, vec_c, stream)
-                      : launch_mix_wide_et<BF16, kWideLargeKd>(p, vec_qk, vec_c, stream);
-    return small_ ? launch_mix_wide_et<F16, kWideSmallKd>(p, vec_qk, vec_c, stream)
-                  : launch_mix_wide_et<F16, kWideLargeKd>(p, vec_qk, vec_c, stream);
+    return with_wide(dtype, vec_qk, p.dk, [&](auto et, auto vq, auto kdt) {
+        using W = WideCfgT<kdt>;
+        const int n_qtiles = (p.s + W::BM - 1) / W::BM;
+        const int n_chunks = (p.dout + W::NB * 32 - 1) / (W::NB * 32);
+        const dim3 grid(xcd_grid(p.b * n_chunks, n_qtiles)), block(W::NT);
+        return with_flag(vec_c, [&](auto vc) {
+            hipLaunchKernelGGL((sense_mix_wide_kernel<decltype(et), vq, vc, kdt>), grid, block, 0, stream, p);
+            return hipGetLastError();
+        });
+    });
 }
 
 }  // namespace bp

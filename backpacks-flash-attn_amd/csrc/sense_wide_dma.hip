@@ -382,11 +382,10 @@ static hipError_t launch_mix_wide_dma_cfg(const MixParams &p, hipStream_t stream
 }
 
 hipError_t launch_sense_mix_wide_dma(const MixParams &p, int dtype, hipStream_t stream) {
-    if (p.dk == 160)
-        return dtype == 1 ? launch_mix_wide_dma_cfg<BF16, 10, 8, 10>(p, stream)
-                          : launch_mix_wide_dma_cfg<F16, 10, 8, 10>(p, stream);
-    return dtype == 1 ? launch_mix_wide_dma_cfg<BF16, 40, 4, 10>(p, stream)
-                      : launch_mix_wide_dma_cfg<F16, 40, 4, 10>(p, stream);
+    return with_dtype(dtype, [&](auto et) {
+        if (p.dk == 160) return launch_mix_wide_dma_cfg<decltype(et), 10, 8, 10>(p, stream);
+        return launch_mix_wide_dma_cfg<decltype(et), 40, 4, 10>(p, stream);
+    });
 }
 
 template <class ET, int KD, int NW>
@@ -397,17 +396,11 @@ static hipError_t launch_lse_wide_dma_cfg(const MixParams &p, float *lse, hipStr
     return hipGetLastError();
 }
 
-hipError_t launch_sense_lse_wide_dma(const void *q, const void *k, float *lse, int64_t lse_stride, int64_t qk_bs,
-                                     int64_t qk_rs, int64_t qk_ss, int b, int s, int nsenses, int dk, float scale_log2e,
-                                     int dtype, hipStream_t stream) {
-    MixParams p{};
-    p.q = q; p.k = k; p.qk_bs = qk_bs; p.qk_rs = qk_rs; p.qk_ss = qk_ss;
-    p.lse_stride = lse_stride; p.b = b; p.s = s; p.nsenses = nsenses; p.dk = dk; p.scale_log2e = scale_log2e;
-    if (dk == 160)
-        return dtype == 1 ? launch_lse_wide_dma_cfg<BF16, 10, 8>(p, lse, stream)
-                          : launch_lse_wide_dma_cfg<F16, 10, 8>(p, lse, stream);
-    return dtype == 1 ? launch_lse_wide_dma_cfg<BF16, 40, 4>(p, lse, stream)
-                      : launch_lse_wide_dma_cfg<F16, 40, 4>(p, lse, stream);
+hipError_t launch_sense_lse_wide_dma(const MixParams &p, float *lse, int dtype, hipStream_t stream) {
+    return with_dtype(dtype, [&](auto et) {
+        if (p.dk == 160) return launch_lse_wide_dma_cfg<decltype(et), 10, 8>(p, lse, stream);
+        return launch_lse_wide_dma_cfg<decltype(et), 40, 4>(p, lse, stream);
+    });
 }
 
 }  // namespace bp

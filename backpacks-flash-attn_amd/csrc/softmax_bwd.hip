@@ -64,20 +64,15 @@ __global__ __launch_bounds__(256) void softmax_bwd_causal_kernel(const SoftmaxBw
     }
 }
 
-template <class ET>
-static hipError_t launch_sb(const SoftmaxBwdParams &p, hipStream_t stream) {
-    const int ch = (p.s + 511) / 512;
-    dim3 g((unsigned)((p.rows + 3) / 4)), t(256);
-#define BP_SB_CASE(N) \
-    if (ch <= N) { hipLaunchKernelGGL((softmax_bwd_causal_kernel<ET, N>), g, t, 0, stream, p); return hipGetLastError(); }
-    BP_SB_CASE(1) BP_SB_CASE(2) BP_SB_CASE(4) BP_SB_CASE(8)
-#undef BP_SB_CASE
-    return hipErrorNotSupported;
-}
-
 // rows = n_matrices * s; s % 8 == 0 and <= 4096; both buffers contiguous (n, s, s), 16-byte aligned
 hipError_t launch_softmax_bwd_causal(const SoftmaxBwdParams &p, int dtype, hipStream_t stream) {
-    return dtype == 1 ? launch_sb<BF16>(p, stream) : launch_sb<F16>(p, stream);
+    const dim3 g((unsigned)((p.rows + 3) / 4)), t(256);
+    return with_dtype(dtype, [&](auto et) {
+        return with_bound<1, 2, 4, 8>((p.s + 511) / 512, hipErrorNotSupported, [&](auto ch) {
+            hipLaunchKernelGGL((softmax_bwd_causal_kernel<decltype(et), ch>), g, t, 0, stream, p);
+            return hipGetLastError();
+        });
+    });
 }
 
 }  // namespace bp

@@ -171,21 +171,24 @@ __global__ __launch_bounds__(256) void xentropy_bwd_kernel(const XentParams p) {
     }
 }
 
-// dtype: 0 fp16, 1 bf16, 2 fp32
+// fp16 / bf16 logits, or fp32 (BP_DTYPE_F32: the only other code the entry points admit)
+template <class F> static hipError_t with_xent_dtype(int dtype, F &&f) {
+    if (dtype == BP_DTYPE_F16 || dtype == BP_DTYPE_BF16) return with_dtype(dtype, f);
+    return f(float{});
+}
+
 hipError_t launch_xentropy_fwd(const XentParams &p, int dtype, hipStream_t stream) {
-    dim3 g((unsigned)p.rows), t(256);
-    if (dtype == 1) hipLaunchKernelGGL((xentropy_fwd_kernel<BF16>), g, t, 0, stream, p);
-    else if (dtype == 0) hipLaunchKernelGGL((xentropy_fwd_kernel<F16>), g, t, 0, stream, p);
-    else hipLaunchKernelGGL((xentropy_fwd_kernel<float>), g, t, 0, stream, p);
-    return hipGetLastError();
+    return with_xent_dtype(dtype, [&](auto et) {
+        hipLaunchKernelGGL((xentropy_fwd_kernel<decltype(et)>), dim3((unsigned)p.rows), dim3(256), 0, stream, p);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_xentropy_bwd(const XentParams &p, int dtype, hipStream_t stream) {
-    dim3 g((unsigned)p.rows), t(256);
-    if (dtype == 1) hipLaunchKernelGGL((xentropy_bwd_kernel<BF16>), g, t, 0, stream, p);
-    else if (dtype == 0) hipLaunchKernelGGL((xentropy_bwd_kernel<F16>), g, t, 0, stream, p);
-    else hipLaunchKernelGGL((xentropy_bwd_kernel<float>), g, t, 0, stream, p);
-    return hipGetLastError();
+    return with_xent_dtype(dtype, [&](auto et) {
+        hipLaunchKernelGGL((xentropy_bwd_kernel<decltype(et)>), dim3((unsigned)p.rows), dim3(256), 0, stream, p);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace bp
