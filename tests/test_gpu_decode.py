@@ -86,9 +86,18 @@ def _sense_ref(q, keys, content, scale, dtype):
 @pytest.mark.parametrize('form', ['table', 'cache'])
 @pytest.mark.parametrize('shape', SENSE_SHAPES, ids=[f'dk{s[1]}_k{s[2]}' for s in SENSE_SHAPES])
 def test_sense_decode_matches_fp32(shape, form):
+    _sense_decode_matches_fp32(shape, form, torch.bfloat16)
+
+
+@pytest.mark.parametrize('form', ['table', 'cache'])
+@pytest.mark.parametrize('shape', SENSE_SHAPES, ids=[f'dk{s[1]}_k{s[2]}' for s in SENSE_SHAPES])
+def test_sense_decode_matches_fp32_in_fp16(shape, form):
+    _sense_decode_matches_fp32(shape, form, torch.float16)
+
+
+def _sense_decode_matches_fp32(shape, form, dtype):
     bp = _bp()
     dkp, dk, k, dout = shape
-    dtype = torch.bfloat16
     g = torch.Generator(device=DEV).manual_seed(dkp * 7 + k)
     lengths = SENSE_LENGTHS if dkp <= 48 else SENSE_LENGTHS[:4] + [4096]
     b, max_s, vocab = len(lengths), 4100, 997
@@ -123,7 +132,7 @@ def test_sense_decode_matches_fp32(shape, form):
         content = table[idx]
         ref = _sense_ref(q[i], keys, content, scale, torch.float32)
         eager = _sense_ref(q[i], keys, content, scale, dtype)
-        _within_2x(out[i], ref, eager, f'sense_decode {shape} {form} L={L}')
+        _within_2x(out[i], ref, eager, f'sense_decode {shape} {form} {dtype} L={L}')
     again = bp.sense_decode(q, k_new, k_cache, table, rows, new_row, seqlens, scale)
     assert torch.equal(again, out), 'repeated calls must be bit-identical'
 

@@ -10,6 +10,7 @@ import torch
 from conftest import ROOT
 
 import bp_hip
+import decode_needles as N
 from flash_attn.models.gpt import GPTLMHeadModel
 from src.models.backpack import BackpackConfig, BackpackLMHeadModel
 from src.utils.generation import InferenceParams
@@ -222,6 +223,71 @@ def test_python_wrappers_refuse_host_tensors():
     assert not bp_hip.flash_decode_supported(q, torch.zeros(1, 8, 2, 2, 64, dtype=torch.bfloat16))
     with pytest.raises(RuntimeError, match='GPU'):
         bp_hip.flash_decode(q, q, q, torch.zeros(1, 8, 2, 2, 64, dtype=torch.bfloat16), torch.zeros(1, dtype=torch.int32))
+
+
+def _needle_rows(positions, cap=24):
+    """Every distinct needle of a case once (at most `cap`, spread evenly, ends kept)."""
+    if len(positions) <= cap:
+        return positions
+    step = (len(positions) - 1) / (cap - 1)
+    return sorted({positions[round(i * step)] for i in range(cap)})
+
+
+def _assert_needles_exact(q, keys, vals, scale, want, dtypes, what, senses=0):
+    for ref in (N.attend_fp32, N.attend_splitwise):
+        got = ref(q, keys, vals, scale)
+        assert torch.equal(got, want), (what, ref.__name__, (got - want).abs().max().item())
+    if senses:   # an output row is the sum over its senses AND their keys, the ~1e-20 of the other keys included
+        p = torch.softmax(scale * (q @ keys.T), dim=-1)
+        for pg, vg, wg in zip(p.split(senses), vals.split(senses), want.split(senses)):
+            assert torch.equal(torch.einsum('ln,lnw->w', pg, vg), wg.sum(dim=0)), what
+    for dtype in dtypes:   # every operand is exact in both 16-bit types
+        for t in (q, keys, vals):
+            assert torch.equal(t.to(dtype).float(), t), (what, dtype)
+
+
+def test_needle_construction_is_exact_in_fp32():
+    """The inputs of tests/test_gpu_decode_edges.py section A (tests/decode_needles.py): for every collected case and every
+    cache length, on a spread sample of at most 24 of the GPU test's needle positions (ends kept), the plain fp32 softmax
+    reference and a split-wise online-softmax restatement both return the needle's value row bit for bit (trunk), and the
+    senses' rows sum exactly.  Exactness rests on the score gap and on integer values, not on the position, the column or
+    which output row carries a needle: so a sample of positions, the first 32 value columns, and rows dealt round-robin
+    (the GPU test deals them with decode_needles.assign) keep this check to a few seconds."""
+    h = bp_hip.lib()
+    dtypes = (torch.bfloat16, torch.float16)
+    checked = 0
+    for case in N.TRUNK_CASES:
+        d, b, nh, ms = case['d'], case['batch'], case['heads'], case['max_seqlen']
+        nsplit = h.bp_flash_decode_ws_floats(b, nh, d, ms) // (b * nh * (d + 2))
+        assert nsplit == {'split64': 64, 'split8': 8, 'split1': 1}[case['regime']]
+        for L in N.lengths(nsplit, d, ms):
+            needles = _needle_rows(N.needle_positions(L, nsplit))
+            pos = torch.arange(L + 1)
+            keys = N.code(pos, d)
+            jstar = torch.tensor(needles)
+            rows = torch.arange(len(needles)) % (b * nh)             # (sample, head) of the row carrying each needle
+            vals = N.values(N.trunk_value_ids(case, rows[:, None] // nh, rows[:, None] % nh, pos[None]), min(d, 32))
+            want = vals[torch.arange(len(needles)), jstar]
+            _assert_needles_exact(N.code(jstar, d), keys, vals, N.scale(d), want, dtypes, (case, L))
+            checked += len(needles)
+    for case in N.SENSE_CASES:
+        dkp, dk, k, dout, b, ms = (case[x] for x in ('dkp', 'dk', 'k', 'dout', 'batch', 'max_seqlen'))
+        nsplit = h.bp_sense_decode_ws_floats(b, k, dout, ms) // (b * k * (dout + 2))
+        w = min(dout, 32)
+        for form in ('table', 'cache'):
+            for L in N.lengths(nsplit, dk, ms):
+                needles = _needle_rows(N.needle_positions(L, nsplit))
+                pos = torch.arange(L + 1)
+                keys = N.code(pos, dk, dkp)
+                jstar = torch.tensor(needles)
+                rows = torch.arange(len(needles)) % (b * k)          # (sample, sense) of the row carrying each needle
+                table_rows = N.sense_row(case, form, rows[:, None] // k, pos[None])
+                vals = N.sense_value(table_rows, rows[:, None] % k, w)
+                want = vals[torch.arange(len(needles)), jstar]
+                _assert_needles_exact(N.code(jstar, dk, dkp), keys, vals, N.scale(dk), want, dtypes, (case, form, L), senses=k)
+                checked += len(needles)
+    # the sum over 64 senses of integers up to 8 is an exact fp32 integer (|sum| <= 512 < 2^24) in any order
+    assert checked > 3000
 
 
 @pytest.fixture(scope='module')
