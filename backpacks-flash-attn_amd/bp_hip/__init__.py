@@ -14,7 +14,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('BP_HIP_LIB') or os.path.join(_HERE, 'libbackpack_hip.so')  # env: A/B builds only
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 _lib = None
 
@@ -86,6 +86,8 @@ SIGNATURES = {
     'bp_flash_decode': (_i32, [_ptr] * 8 + [_i64] + [_i32] * 4 + [_i64] * 13 + [_f32, _i32, _ptr]),
     'bp_sense_decode_ws_floats': (_i64, [_i32] * 4),
     'bp_sense_decode': (_i32, [_ptr] * 9 + [_i64] + [_i32] * 5 + [_i64] + [_i64] * 11 + [_f32, _i32, _ptr]),
+    'bp_sense_decode_weighted': (_i32, [_ptr] * 10 + [_i64] + [_i32] * 5 + [_i64] + [_i64] * 13 + [_f32, _i32, _ptr]),
+    'bp_sense_rows_dot': (_i32, [_ptr] * 6 + [_i32] * 4 + [_i64] + [_i64] * 6 + [_i32, _ptr]),
 }
 
 
@@ -954,7 +956,7 @@ class GraphedForward:
         return self.static_out
 
 
-# ---- KV-cached decoding (C ABI bp_flash_decode / bp_sense_decode) ---------------------------------------------------
+# ---- KV-cached decoding (C ABI bp_flash_decode / bp_sense_decode{,_weighted} / bp_sense_rows_dot) ---------------------------------------------------
 
 def _decode_ws(floats, device):
     # fresh per call, like the other workspaces: the caching allocator hands it back once the stream has used it, and a
@@ -1020,14 +1022,29 @@ def sense_decode_supported(q, k_cache, table):
             and dout <= SENSE_DECODE_MAX_DOUT and _vec16(q, k_cache, table))
 
 
-def sense_decode(q, k_new, k_cache, table, row_index, new_row, cache_seqlens, softmax_scale=None, out=None):
+def _decode_key_weight_ok(key_weight, b, k, max_s):
+    return (key_weight.is_cuda and key_weight.dtype == torch.float32 and tuple(key_weight.shape) == (b, k, max_s)
+            and key_weight.stride(-1) == 1 and key_weight.stride(0) >= max_s and key_weight.stride(1) >= max_s)
+
+
+def sense_decode_weighted_supported(q, k_cache, table, key_weight):
+    """sense_decode_supported plus the weights' contract: fp32 (B, k, max_seqlen), unit stride along the positions."""
+    return sense_decode_supported(q, k_cache, table) and k_cache.dim() == 4 \
+        and _decode_key_weight_ok(key_weight, q.shape[0], q.shape[1], k_cache.shape[1])
+
+
+def sense_decode(q, k_new, k_cache, table, row_index, new_row, cache_seqlens, softmax_scale=None, out=None,
+                 key_weight=None):
     """One decode step of the Backpack sense contraction.
 
     q, k_new (B, k, d_k) 16-bit (the two halves of ContextSelfAttn.project for the new token); k_cache (B, max_seqlen, k,
     d_k); table (rows, k, d_out) sense vectors, read through row_index (B, max_seqlen) int32 (table form: token ids into the
     whole-vocabulary table; cache form: b * max_seqlen + j into a per-position content cache); new_row (B,) int32 the new
     position's row; cache_seqlens (B,) int32 cached positions before this one.  Appends k_new and new_row at position
-    cache_seqlens[b] and returns (B, d_out) = sum_l sum_{j<=t} softmax_j(scale q_l . k_l(j)) table[row(j), l]."""
+    cache_seqlens[b] and returns (B, d_out) = sum_l sum_{j<=t} softmax_j(scale q_l . k_l(j)) table[row(j), l].
+
+    key_weight (B, k, max_seqlen) fp32 or None: per-(sense, position) weights on the probabilities (they do not enter the
+    softmax), entries [0, cache_seqlens[b]] read, the new position's included; C ABI bp_sense_decode_weighted."""
     _require_cuda(q, k_new, k_cache, table, row_index, new_row, cache_seqlens)
     if q.dim() != 3 or k_new.shape != q.shape:
         raise RuntimeError('bp_hip.sense_decode: q and k_new must be (B, k, d_k) of one shape')
@@ -1050,10 +1067,59 @@ def sense_decode(q, k_new, k_cache, table, row_index, new_row, cache_seqlens, so
     if out is None:
         out = torch.empty((b, dout), dtype=q.dtype, device=q.device)
     ws = _decode_ws(lib().bp_sense_decode_ws_floats(b, k, dout, max_s), q.device)
+    if key_weight is not None:
+        if not _decode_key_weight_ok(key_weight, b, k, max_s):
+            raise RuntimeError(f'bp_hip.sense_decode: key_weight must be a float32 CUDA tensor of shape ({b}, {k}, {max_s}) '
+                               'with unit stride along the positions')
+        _call('bp_sense_decode_weighted', q.device,
+              q.data_ptr(), k_new.data_ptr(), k_cache.data_ptr(), table.data_ptr(), row_index.data_ptr(),
+              new_row.data_ptr(), cache_seqlens.data_ptr(), key_weight.data_ptr(), out.data_ptr(), ws.data_ptr(),
+              ws.numel(), b, k, dk, dout, max_s, table.shape[0], q.stride(0), q.stride(1), k_new.stride(0),
+              k_new.stride(1), k_cache.stride(0), k_cache.stride(1), k_cache.stride(2), table.stride(0), table.stride(1),
+              row_index.stride(0), out.stride(0), key_weight.stride(0), key_weight.stride(1), float(scale),
+              _dtype_code(q))
+        return out
     _call('bp_sense_decode', q.device,
           q.data_ptr(), k_new.data_ptr(), k_cache.data_ptr(), table.data_ptr(), row_index.data_ptr(),
           new_row.data_ptr(), cache_seqlens.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(),
           b, k, dk, dout, max_s, table.shape[0], q.stride(0), q.stride(1), k_new.stride(0), k_new.stride(1),
           k_cache.stride(0), k_cache.stride(1), k_cache.stride(2), table.stride(0), table.stride(1),
           row_index.stride(0), out.stride(0), float(scale), _dtype_code(q))
+    return out
+
+
+def sense_rows_dot_supported(table, vec):
+    """Whether bp_sense_rows_dot takes these operands: 16-bit CUDA tensors of one dtype, at most 64 senses, d_out % 8 == 0
+    and <= 2048, 16-byte friendly layouts."""
+    if not (table.is_cuda and vec.is_cuda) or table.dtype not in (torch.float16, torch.bfloat16) or vec.dtype != table.dtype:
+        return False
+    if table.dim() != 3 or vec.dim() != 2 or vec.shape[1] != table.shape[2]:
+        return False
+    k, dout = table.shape[1], table.shape[2]
+    return 1 <= k <= SENSE_DECODE_MAX_SENSES and dout % 8 == 0 and dout <= SENSE_DECODE_MAX_DOUT and _vec16(table, vec)
+
+
+def sense_rows_dot(table, row_index, new_row, cache_seqlens, vec, out):
+    """out[b, l, j] = table[row(b, j), l, :] . vec[b, :] for j = 0 .. cache_seqlens[b], where row(b, j) = row_index[b, j] for
+    the cached positions and new_row[b] for j = cache_seqlens[b] (C ABI bp_sense_rows_dot; the annealed intervention's
+    running similarity sums).  table (rows, k, d_out) and vec (B, d_out) 16-bit; row_index (B, max_seqlen) int32 (only
+    read); out (B, k, max_seqlen) fp32, unit stride along the positions, written in place at [0, cache_seqlens[b]] and
+    returned.  The lengths stay on the device."""
+    _require_cuda(table, row_index, new_row, cache_seqlens, vec, out)
+    if table.dim() != 3 or vec.dim() != 2 or vec.shape[1] != table.shape[2] or vec.dtype != table.dtype:
+        raise RuntimeError('bp_hip.sense_rows_dot: table must be (rows, k, d_out) and vec (B, d_out) of the same dtype')
+    b, (k, dout) = vec.shape[0], table.shape[1:]
+    if row_index.dim() != 2 or row_index.shape[0] != b or row_index.dtype != torch.int32 or row_index.stride(-1) != 1:
+        raise RuntimeError('bp_hip.sense_rows_dot: row_index must be (B, max_seqlen) int32, unit stride along the sequence')
+    max_s = row_index.shape[1]
+    for name, t in (('new_row', new_row), ('cache_seqlens', cache_seqlens)):
+        if t.shape != (b,) or t.dtype != torch.int32 or not t.is_contiguous():
+            raise RuntimeError(f'bp_hip.sense_rows_dot: {name} must be a contiguous (B,) int32 tensor')
+    if not _decode_key_weight_ok(out, b, k, max_s):
+        raise RuntimeError(f'bp_hip.sense_rows_dot: out must be a float32 CUDA tensor of shape ({b}, {k}, {max_s}) with unit '
+                           'stride along the positions')
+    _call('bp_sense_rows_dot', table.device,
+          table.data_ptr(), row_index.data_ptr(), new_row.data_ptr(), cache_seqlens.data_ptr(), vec.data_ptr(),
+          out.data_ptr(), b, k, dout, max_s, table.shape[0], table.stride(0), table.stride(1), row_index.stride(0),
+          vec.stride(0), out.stride(0), out.stride(1), _dtype_code(table))
     return out

@@ -752,7 +752,7 @@ int bp_xentropy_bwd(const float *grad_losses, const void *logits, const float *l
     return launch_status(bp::launch_xentropy_bwd(p, dtype, static_cast<hipStream_t>(stream)));
 }
 
-// ---- KV-cached decoding (bp_flash_decode / bp_sense_decode) ----
+// ---- KV-cached decoding (bp_flash_decode / bp_sense_decode{,_weighted} / bp_sense_rows_dot) ----
 
 int64_t bp_flash_decode_ws_floats(int batch, int nheads, int head_dim, int max_seqlen) {
     if (batch <= 0 || nheads <= 0 || head_dim <= 0 || max_seqlen <= 0) return 0;
@@ -813,6 +813,23 @@ int bp_sense_decode(const void *q, const void *k_new, void *k_cache, const void 
                     int64_t kc_batch_stride, int64_t kc_row_stride, int64_t kc_sense_stride,
                     int64_t t_row_stride, int64_t t_sense_stride, int64_t idx_batch_stride,
                     int64_t o_batch_stride, float softmax_scale, int dtype, bp_stream_t stream) {
+    return bp_sense_decode_weighted(q, k_new, k_cache, table, row_index, new_row, cache_seqlens, nullptr, out, ws,
+                                    ws_floats, batch, nsenses, d_k, d_out, max_seqlen, table_rows, q_batch_stride,
+                                    q_sense_stride, knew_batch_stride, knew_sense_stride, kc_batch_stride, kc_row_stride,
+                                    kc_sense_stride, t_row_stride, t_sense_stride, idx_batch_stride, o_batch_stride, 0, 0,
+                                    softmax_scale, dtype, stream);
+}
+
+int bp_sense_decode_weighted(const void *q, const void *k_new, void *k_cache, const void *table, int32_t *row_index,
+                             const int32_t *new_row, const int32_t *cache_seqlens, const float *key_weight, void *out,
+                             float *ws, int64_t ws_floats,
+                             int batch, int nsenses, int d_k, int d_out, int max_seqlen, int64_t table_rows,
+                             int64_t q_batch_stride, int64_t q_sense_stride,
+                             int64_t knew_batch_stride, int64_t knew_sense_stride,
+                             int64_t kc_batch_stride, int64_t kc_row_stride, int64_t kc_sense_stride,
+                             int64_t t_row_stride, int64_t t_sense_stride, int64_t idx_batch_stride,
+                             int64_t o_batch_stride, int64_t kw_batch_stride, int64_t kw_sense_stride,
+                             float softmax_scale, int dtype, bp_stream_t stream) {
     if (dtype != BP_DTYPE_F16 && dtype != BP_DTYPE_BF16) return BP_ERR_DTYPE;
     if (d_k < 1 || d_k > bp::kWideMaxDk || d_k % 8 != 0) return BP_ERR_HEAD_DIM;
     if (d_out < 1) return BP_ERR_DOUT;
@@ -827,6 +844,8 @@ int bp_sense_decode(const void *q, const void *k_new, void *k_cache, const void 
     if (!strides8({q_batch_stride, q_sense_stride, knew_batch_stride, knew_sense_stride, kc_batch_stride, kc_row_stride,
                    kc_sense_stride, t_row_stride, t_sense_stride, o_batch_stride}))
         return BP_ERR_SHAPE;
+    // a weight row holds max_seqlen entries; rows of different (sample, sense) pairs do not overlap
+    if (key_weight != nullptr && (kw_sense_stride < max_seqlen || kw_batch_stride < max_seqlen)) return BP_ERR_SHAPE;
     if (!scale_ok(softmax_scale)) return BP_ERR_SCALE;
     if (ws_floats < bp_sense_decode_ws_floats(batch, nsenses, d_out, max_seqlen)) return BP_ERR_WORKSPACE;
     bp::DecodeParams p{};
@@ -843,7 +862,34 @@ int bp_sense_decode(const void *q, const void *k_new, void *k_cache, const void 
     p.ws_ml = ws + (int64_t)batch * nsenses * p.nsplit * d_out;
     p.o = out; p.o_bs = o_batch_stride;
     p.scale_log2e = softmax_scale * bp::kLog2e;
-    return launch_status(bp::launch_sense_decode(p, dtype, static_cast<hipStream_t>(stream)));
+    if (key_weight == nullptr) return launch_status(bp::launch_sense_decode(p, dtype, static_cast<hipStream_t>(stream)));
+    p.key_weight = key_weight; p.kw_bs = kw_batch_stride; p.kw_gs = kw_sense_stride;
+    return launch_status(bp::launch_sense_decode_weighted(p, dtype, static_cast<hipStream_t>(stream)));
+}
+
+int bp_sense_rows_dot(const void *table, const int32_t *row_index, const int32_t *new_row, const int32_t *cache_seqlens,
+                      const void *vec, float *out,
+                      int batch, int nsenses, int d_out, int max_seqlen, int64_t table_rows,
+                      int64_t t_row_stride, int64_t t_sense_stride, int64_t idx_batch_stride, int64_t vec_batch_stride,
+                      int64_t o_batch_stride, int64_t o_sense_stride, int dtype, bp_stream_t stream) {
+    if (dtype != BP_DTYPE_F16 && dtype != BP_DTYPE_BF16) return BP_ERR_DTYPE;
+    if (d_out < 1) return BP_ERR_DOUT;
+    if (d_out % 8 != 0 || d_out > 2048) return BP_ERR_SHAPE;
+    if (batch <= 0 || batch > 65535 || nsenses <= 0 || nsenses > 64 || max_seqlen <= 0 || table_rows <= 0
+        || table_rows > 0x7fffffffLL)
+        return BP_ERR_SHAPE;
+    if (table == nullptr || row_index == nullptr || new_row == nullptr || cache_seqlens == nullptr || vec == nullptr
+        || out == nullptr)
+        return BP_ERR_SHAPE;
+    if (!aligned16({table, vec})) return BP_ERR_SHAPE;
+    if (!strides8({t_row_stride, t_sense_stride, vec_batch_stride})) return BP_ERR_SHAPE;
+    if (o_sense_stride < max_seqlen || o_batch_stride < max_seqlen) return BP_ERR_SHAPE;
+    bp::RowsDotParams p{};
+    p.table = table; p.vec = vec; p.row_index = row_index; p.new_row = new_row; p.seqlens = cache_seqlens; p.out = out;
+    p.t_rs = t_row_stride; p.t_gs = t_sense_stride; p.ri_bs = idx_batch_stride; p.v_bs = vec_batch_stride;
+    p.o_bs = o_batch_stride; p.o_gs = o_sense_stride; p.table_rows = table_rows;
+    p.b = batch; p.groups = nsenses; p.dout = d_out; p.max_seqlen = max_seqlen;
+    return launch_status(bp::launch_sense_rows_dot(p, dtype, static_cast<hipStream_t>(stream)));
 }
 
 }  // extern "C"

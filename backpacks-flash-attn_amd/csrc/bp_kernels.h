@@ -292,9 +292,26 @@ struct DecodeParams {
     int64_t lse_bs;
     int b, groups, dk, dv, max_seqlen, nsplit;
     float scale_log2e;
+    // bp_sense_decode_weighted only (last, so the kernels without them keep their argument offsets): fp32 weight of
+    // (b, g, j) at key_weight + b*kw_bs + g*kw_gs + j
+    const float *key_weight;
+    int64_t kw_bs, kw_gs;
 };
 int decode_nsplit(int batch, int groups, int max_seqlen);
 hipError_t launch_flash_decode(const DecodeParams &p, int dtype, hipStream_t stream);
 hipError_t launch_sense_decode(const DecodeParams &p, int dtype, hipStream_t stream);
+// the senses' combine alone: second launch of the weighted decode, whose split kernels are a code object of their own
+hipError_t launch_sense_decode_combine(const DecodeParams &p, int dtype, hipStream_t stream);
+hipError_t launch_sense_decode_weighted(const DecodeParams &p, int dtype, hipStream_t stream);
+
+// bp_sense_rows_dot (sense_rows_dot.hip): out[b, l, j] = table[row(b, j), l, :] . vec[b, :] for j = 0 .. seqlens[b]
+struct RowsDotParams {
+    const void *table, *vec;
+    const int32_t *row_index, *new_row, *seqlens;
+    float *out;
+    int64_t t_rs, t_gs, ri_bs, v_bs, o_bs, o_gs, table_rows;
+    int b, groups, dout, max_seqlen;
+};
+hipError_t launch_sense_rows_dot(const RowsDotParams &p, int dtype, hipStream_t stream);
 
 }  // namespace bp

@@ -40,17 +40,28 @@ BP_DEV int dec_length(const DecodeParams &p, int b) {
     return L < 0 ? 0 : (L >= p.max_seqlen ? p.max_seqlen - 1 : L);   // never index outside the cache
 }
 
+// Weighted form (senses only, bp_sense_decode_weighted): decode_split_kernel<Weighted<ET>, G, NQ, true> multiplies the
+// probability of key j by key_weight[b, g, j] in phase B; the weight never enters the softmax (m and l are the plain
+// kernel's).  The flag rides on the element tag, so the plain instantiations keep their names and their code.
+template <class ET> struct Weighted {};
+template <class T> struct DecodeTag { using elem = T; static constexpr bool weighted = false; };
+template <class T> struct DecodeTag<Weighted<T>> { using elem = T; static constexpr bool weighted = true; };
+
 template <class ET, int G, int NQ, bool SENSE>
 __global__ __launch_bounds__(DEC_THREADS) void decode_split_kernel(DecodeParams p) {
-    using E = Elem<ET>;
+    constexpr bool WEIGHTED = DecodeTag<ET>::weighted;
+    static_assert(SENSE || !WEIGHTED, "key weights belong to the sense contraction");
+    using E = Elem<typename DecodeTag<ET>::elem>;
     constexpr int KPW = 64 / G;                   // keys per wave per pass
     constexpr int KPB = 4 * KPW;                  // keys per workgroup per pass
     constexpr int NP = (DEC_TILE + KPB - 1) / KPB;
-    __shared__ __attribute__((aligned(16))) float smem[3 * 2 * DEC_TILE + DEC_THREADS * 8];
+    constexpr int NARR = WEIGHTED ? 4 : 3;        // [2][64] arrays in front of the reduction block
+    __shared__ __attribute__((aligned(16))) float smem[NARR * 2 * DEC_TILE + DEC_THREADS * 8];
     float *sc = smem;                             // [2][64] scores
     float *pb = smem + 2 * DEC_TILE;              // [2][64] probabilities
     int *rows = reinterpret_cast<int *>(smem + 4 * DEC_TILE);   // [2][64] table rows (senses)
-    float *red = smem + 6 * DEC_TILE;             // [R][NC][8] final reduction
+    float *kw = smem + 6 * DEC_TILE;              // [2][64] key weights (weighted form)
+    float *red = smem + NARR * 2 * DEC_TILE;      // [R][NC][8] final reduction
 
     const int split = blockIdx.x, g = blockIdx.y, b = blockIdx.z;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -136,6 +147,7 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_split_kernel(DecodeParams 
                     }
                     const uint32_t ur = (uint32_t)row;   // clamp as unsigned: a bad index reads the last row
                     rows[buf * DEC_TILE + jj] = (int)(ur < (uint32_t)p.table_rows ? ur : (uint32_t)(p.table_rows - 1));
+                    if constexpr (WEIGHTED) kw[buf * DEC_TILE + jj] = p.key_weight[b * p.kw_bs + g * p.kw_gs + j];
                 }
             }
         }
@@ -170,6 +182,7 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_split_kernel(DecodeParams 
                     if (jj < tl) {
                         const int j = jt + jj;
                         pj[u] = pb[buf * DEC_TILE + jj];
+                        if constexpr (WEIGHTED) pj[u] *= kw[buf * DEC_TILE + jj];
                         const uint16_t *vrow;
                         if constexpr (SENSE) {
                             vrow = static_cast<const uint16_t *>(p.v) + (int64_t)rows[buf * DEC_TILE + jj] * p.vc_rs
@@ -296,14 +309,19 @@ inline int decode_nsplit_impl(int batch, int groups, int max_seqlen) {
     return want < 1 ? 1 : want;
 }
 
+template <class ET, bool SENSE>
+hipError_t launch_decode_combine(const DecodeParams &p, int nout, hipStream_t st) {
+    const int nc = p.dv >> 3;
+    hipLaunchKernelGGL((decode_combine_kernel<ET, SENSE>), dim3(nout, (nc + 7) / 8), dim3(DEC_THREADS), 0, st, p);
+    return hipGetLastError();
+}
+
 template <class ET, int G, int NQ, bool SENSE>
 hipError_t launch_decode_pair(const DecodeParams &p, int nout, hipStream_t st) {
     hipLaunchKernelGGL((decode_split_kernel<ET, G, NQ, SENSE>), dim3(p.nsplit, p.groups, p.b), dim3(DEC_THREADS), 0, st, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    const int nc = p.dv >> 3;
-    hipLaunchKernelGGL((decode_combine_kernel<ET, SENSE>), dim3(nout, (nc + 7) / 8), dim3(DEC_THREADS), 0, st, p);
-    return hipGetLastError();
+    return launch_decode_combine<ET, SENSE>(p, nout, st);
 }
 
 // G: 8-column chunks of the query row per key group (a power of two); the trunk (d_h <= 128) needs up to 16, the senses

@@ -11,4 +11,8 @@ hipError_t launch_sense_decode(const DecodeParams &p, int dtype, hipStream_t str
     return launch_decode<true>(p, dtype, p.b, stream);
 }
 
+hipError_t launch_sense_decode_combine(const DecodeParams &p, int dtype, hipStream_t stream) {
+    return with_dtype(dtype, [&](auto et) { return launch_decode_combine<decltype(et), true>(p, p.b, stream); });
+}
+
 }  // namespace bp

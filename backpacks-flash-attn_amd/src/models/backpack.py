@@ -462,6 +462,14 @@ class BackpackModel(GPTPreTrainedModel):
     # Cache form (modes 'batch' / 'off', or no table): the content network runs on the new tokens only -- exact, it is
     # per token -- and its rows are appended; rows = b * max_seqlen + j.  The form is fixed by the prefill.
     # Fused senses decode with bp_sense_decode; non-fused ones (d_k > 640, use_flash_attn=False) with an eager restatement.
+    #
+    # `intervention` (src/models/intervened_models.py, nothing else): the one hook of the cached path.  An object with
+    #   cache_form_only                       True: never the table form (its rows are edited per position)
+    #   edit_rows(input_ids, content)         cache form: the (B,k,S,d) rows of the new positions, before they are appended
+    #   prefill_key_weight(model, input_ids, content, ip)                         -> (B,k,S) fp32 or None
+    #   step_key_weight(model, input_ids, table, rows, new_row, lengths, ip)      -> (B,k,max_seqlen) fp32 or None
+    # The weights go to bp_sense_mix / bp_sense_decode as `key_weight`.  Without a hook nothing here differs from the plain
+    # model, call for call.
 
     def _decode_sense_table(self, input_ids):
         if self.sense_table_mode == 'cached' and self.dedup_content and self.fused_senses and not self.training \
@@ -481,7 +489,7 @@ class BackpackModel(GPTPreTrainedModel):
                                                          device=like.device)
         return caches['backpack_sense_k'], caches['backpack_rows'], caches.get('backpack_content')
 
-    def _forward_cached(self, input_ids, position_ids, ip):
+    def _forward_cached(self, input_ids, position_ids, ip, intervention=None):
         if torch.is_grad_enabled():
             raise RuntimeError('KV-cached decoding is inference-only: run it under torch.no_grad() or '
                                'torch.inference_mode()')
@@ -495,7 +503,8 @@ class BackpackModel(GPTPreTrainedModel):
         attn = self.contextualization_attn
         qk = attn.project(hidden)                                        # (B, S, 2, k, d_k)
         if prefill:
-            table = self._decode_sense_table(input_ids)
+            cache_form_only = intervention is not None and intervention.cache_form_only
+            table = None if cache_form_only else self._decode_sense_table(input_ids)
         else:
             table = None if 'backpack_content' in ip.key_value_memory_dict else self.sense_table()
             if table is None and 'backpack_content' not in ip.key_value_memory_dict:
@@ -509,28 +518,53 @@ class BackpackModel(GPTPreTrainedModel):
             key_cache[b0:b1, :seqlen] = qk[:, :, 1]
             if table is not None:
                 rows[b0:b1, :seqlen] = input_ids
-                return self._mix_from_table(hidden, table, input_ids, qk=qk)
-            content = self.content_model(input_ids)                      # (B, k, S, d) view of (B, S, k*d)
-            rows[b0:b1, :seqlen] = sample[:, None] * ms + torch.arange(seqlen, device=input_ids.device)
-            content_cache.view(-1, ms, *content_cache.shape[1:])[b0:b1, :seqlen] = content.transpose(1, 2)
+                if intervention is None:
+                    return self._mix_from_table(hidden, table, input_ids, qk=qk)
+                # bp_sense_mix_gather has no weighted form: torch gathers the prompt's rows (prompts are short), as the
+                # fallback of _mix_from_table does
+                content = F.embedding(input_ids, table.reshape(table.shape[0], -1)) \
+                    .view(batch, seqlen, *table.shape[1:]).transpose(1, 2)
+            else:
+                content = self.content_model(input_ids)                  # (B, k, S, d) view of (B, S, k*d)
+                if intervention is not None:
+                    content = intervention.edit_rows(input_ids, content)
+                rows[b0:b1, :seqlen] = sample[:, None] * ms + torch.arange(seqlen, device=input_ids.device)
+                content_cache.view(-1, ms, *content_cache.shape[1:])[b0:b1, :seqlen] = content.transpose(1, 2)
+            key_weight = None if intervention is None else intervention.prefill_key_weight(self, input_ids, content, ip)
             if self.fused_senses:
-                return bp_hip.sense_mix(qk, content.transpose(1, 2), attn.scale())
+                if key_weight is None:
+                    return bp_hip.sense_mix(qk, content.transpose(1, 2), attn.scale())
+                return bp_hip.sense_mix(qk, content.transpose(1, 2), attn.scale(), key_weight=key_weight)
+            if key_weight is not None:
+                content = content * key_weight.unsqueeze(3).to(content.dtype)
             return _combine_senses(attn(hidden), content)
         lengths = cache_lengths(ip, batch, input_ids.device)
         if table is not None:
             new_row = input_ids[:, 0].to(torch.int32)
         else:
             new_row = (sample * ms + lengths).to(torch.int32)
-            content_cache.index_copy_(0, new_row.long(), self.content_model(input_ids)[:, :, 0])
+            if intervention is None:
+                content_cache.index_copy_(0, new_row.long(), self.content_model(input_ids)[:, :, 0])
+            else:
+                content_cache.index_copy_(0, new_row.long(),
+                                          intervention.edit_rows(input_ids, self.content_model(input_ids))[:, :, 0])
             table = content_cache
         q, k_new = qk[:, 0, 0], qk[:, 0, 1]                             # (B, k, d_k)
+        key_weight = None if intervention is None else \
+            intervention.step_key_weight(self, input_ids, table, rows[b0:b1], new_row, lengths, ip)
         if self.fused_senses:
             if not bp_hip.sense_decode_supported(q, key_cache, table):
                 raise RuntimeError(f'Backpack decode: bp_sense_decode does not take k = {q.shape[1]} senses of width '
                                    f'{q.shape[2]} with {table.shape[2]} output columns (include/bp_hip.h)')
-            return bp_hip.sense_decode(q, k_new, key_cache[b0:b1], table, rows[b0:b1], new_row, lengths,
-                                       attn.scale()).unsqueeze(1)
-        return _eager_sense_decode(q, k_new, key_cache, table, rows, new_row, b0, lengths, attn.scale()).unsqueeze(1)
+            if key_weight is None:
+                return bp_hip.sense_decode(q, k_new, key_cache[b0:b1], table, rows[b0:b1], new_row, lengths,
+                                           attn.scale()).unsqueeze(1)
+            return bp_hip.sense_decode(q, k_new, key_cache[b0:b1], table, rows[b0:b1], new_row, lengths, attn.scale(),
+                                       key_weight=key_weight).unsqueeze(1)
+        if key_weight is None:
+            return _eager_sense_decode(q, k_new, key_cache, table, rows, new_row, b0, lengths, attn.scale()).unsqueeze(1)
+        return _eager_sense_decode(q, k_new, key_cache, table, rows, new_row, b0, lengths, attn.scale(),
+                                   key_weight=key_weight).unsqueeze(1)
 
     def forward(self, input_ids, position_ids=None, inference_params=None):
         if inference_params is not None:
@@ -557,9 +591,10 @@ class BackpackModel(GPTPreTrainedModel):
         return _combine_senses(contextualization, content)                         # (B,S,d)
 
 
-def _eager_sense_decode(q, k_new, key_cache, table, rows, new_row, b0, lengths, scale):
+def _eager_sense_decode(q, k_new, key_cache, table, rows, new_row, b0, lengths, scale, key_weight=None):
     """Eager restatement of bp_sense_decode (the non-fused Backpacks): append the new key and row at position lengths[b],
-    then o = sum_l sum_{j <= L} softmax_j(q_l . k_l(j) * scale) table[rows[b, j], l] (ContextSelfAttn's op order)."""
+    then o = sum_l sum_{j <= L} softmax_j(q_l . k_l(j) * scale) table[rows[b, j], l] (ContextSelfAttn's op order).
+    `key_weight` (B, k, max_seqlen) fp32: bp_sense_decode_weighted, the probabilities times the weights of keys 0 .. L."""
     batch = q.shape[0]
     sample = torch.arange(b0, b0 + batch, device=q.device)
     key_cache[sample, lengths.long()] = k_new
@@ -569,6 +604,8 @@ def _eager_sense_decode(q, k_new, key_cache, table, rows, new_row, b0, lengths, 
     visible = torch.arange(keys.shape[1], device=q.device)[None, :] <= lengths[:, None].long()
     scores = scores.masked_fill(~visible[:, None, :], float('-inf'))
     weights = torch.softmax(scores, dim=-1, dtype=q.dtype)                 # (B, k, M)
+    if key_weight is not None:
+        weights = weights * torch.where(visible[:, None, :], key_weight, 0.0).to(weights.dtype)
     content = table[rows[b0:b0 + batch].long()]                            # (B, M, k, d)
     return torch.einsum('bls,bsld->bd', weights, content)
 

@@ -14,6 +14,18 @@ when the wrapped network runs its HIP path (`config.use_flash_attn`), it stays O
     so it is a (S x S) product per sense against the gathered embeddings instead of a gather out of a
     (B,k,S,vocab) tensor (identical numbers, 50264/S times less work and memory).
 With `use_flash_attn=False` the reference's eager op sequence runs (any device / dtype).
+
+KV-cached decoding (`forward(..., inference_params=ip)`, `generate` / `sample` with `kv_cache=True`): the wrappers are the
+`intervention` hook of `BackpackModel._forward_cached`.  Weighted: the per-(sense, position) weights of the cached
+positions live in `ip.key_value_memory_dict` and enter the step as `key_weight` of bp_sense_decode_weighted; the annealed
+weights change at every step, but the similarity sums behind them are running sums, advanced by one gathered GEMV over
+the cached rows (bp_sense_rows_dot).  ReplacedWord: cache form, the listed tokens' rows are replaced as they are appended.
+State, all (max_batch_size, ..., max_sequence_len), indexed on the device through the cached lengths:
+  'intervened_ids'     int64 token ids of the cached positions
+  'intervened_weight'  fp32 (., k, .) the key weights the contraction reads
+  'intervened_sims'    fp32 (., k, .) annealed: sum_j relu(C_l(x_i) . E[x_j]) over the tokens so far
+  'intervened_dots'    fp32 (., k, .) annealed: the step's dot products (bp_sense_rows_dot's output)
+  'intervened_content_weights' / 'intervened_replace'   device copies of content_weights / sense_dict, made by the prefill
 """
 from collections import namedtuple
 
@@ -53,8 +65,41 @@ def mask_annealing(model, input_ids, target_vector, content, annealing_scale=0.1
     return scores
 
 
+def _anneal_weights(sims, picked, annealing_scale, upweight_nearby, first_position=0):
+    """sims (B,k,n) fp32 similarity sums, picked (B,k,n) content_weights of the tokens -> (B,k,n) fp32 weights
+    (mask_annealing's score + create_content_soft_mask; position i of the last axis is first_position + i)."""
+    scores = torch.sigmoid(-annealing_scale * sims + 6)
+    if upweight_nearby:
+        scores = scores * (1 + torch.arange(first_position, first_position + sims.shape[2], device=sims.device) / 100)
+    return picked * scores + (1 - scores)
+
+
 class _Intervened(nn.Module, GenerationMixin):
     """Shared plumbing: the three stages of the wrapped network, and the contraction."""
+
+    # ---- the `intervention` hook of BackpackModel._forward_cached: by default nothing is edited, nothing weighted ----
+    cache_form_only = False
+
+    def edit_rows(self, input_ids, content):
+        return content
+
+    def prefill_key_weight(self, model, input_ids, content, ip):
+        return None
+
+    def step_key_weight(self, model, input_ids, table, rows, new_row, lengths, ip):
+        return None
+
+    def _forward_cached(self, input_ids, position_ids, inference_params):
+        mixed = self.backpack_network.transformer._forward_cached(input_ids, position_ids, inference_params,
+                                                                  intervention=self)
+        return CausalLMOutput(logits=self.backpack_network.lm_head(mixed))
+
+    @staticmethod
+    def _state(ip, name, shape, dtype, device):
+        caches = ip.key_value_memory_dict
+        if name not in caches:
+            caches[name] = torch.zeros(shape, dtype=dtype, device=device)
+        return caches[name]
 
     def _stages(self, input_ids, position_ids, inference_params):
         t = self.backpack_network.transformer
@@ -99,9 +144,81 @@ class WeightedBackpackLMHeadModel(_Intervened):
         self.upweight_nearby = upweight_nearby
 
     def forward(self, input_ids, position_ids=None, inference_params=None):
+        if inference_params is not None:
+            return self._forward_cached(input_ids, position_ids, inference_params)
         t, hidden, content = self._stages(input_ids, position_ids, inference_params)
         mixed = self._mix(t, hidden, content, self._weights(input_ids, content))
         return CausalLMOutput(logits=self.backpack_network.lm_head(mixed))
+
+    # ---- KV-cached decoding ----
+    def _cached_state(self, ip, k, device):
+        mb, ms = ip.max_batch_size, ip.max_sequence_len
+        ids = self._state(ip, 'intervened_ids', (mb, ms), torch.long, device)
+        weight = self._state(ip, 'intervened_weight', (mb, k, ms), torch.float32, device)
+        return ids, weight
+
+    def prefill_key_weight(self, model, input_ids, content, ip):
+        batch, seqlen = input_ids.shape
+        k = content.shape[1]
+        b0 = ip.batch_size_offset
+        ids, weight = self._cached_state(ip, k, input_ids.device)
+        # one device copy of the (vocab, k) weights per prefill: the steps index it without touching the host
+        cw = ip.key_value_memory_dict['intervened_content_weights'] = \
+            self.content_weights.to(device=input_ids.device, dtype=torch.float32)
+        ids[b0:b0 + batch, :seqlen] = input_ids
+        picked = cw[input_ids].transpose(1, 2)                                     # (B,k,S)
+        if self.anneal:
+            emb = self.backpack_network.lm_head.weight[input_ids]                  # (B,S,d)
+            sims = torch.relu(content @ emb.transpose(1, 2).unsqueeze(1)).sum(dim=3, dtype=torch.float32)
+            mb, ms = ip.max_batch_size, ip.max_sequence_len
+            self._state(ip, 'intervened_sims', (mb, k, ms), torch.float32, input_ids.device)[b0:b0 + batch, :, :seqlen] = sims
+            self._state(ip, 'intervened_dots', (mb, k, ms), torch.float32, input_ids.device)
+            picked = _anneal_weights(sims, picked, self.annealing_scale, self.upweight_nearby)
+        weight[b0:b0 + batch, :, :seqlen] = picked
+        return picked.contiguous()
+
+    def step_key_weight(self, model, input_ids, table, rows, new_row, lengths, ip):
+        batch = input_ids.shape[0]
+        b0, ms = ip.batch_size_offset, ip.max_sequence_len
+        caches = ip.key_value_memory_dict
+        ids, weight, cw = caches['intervened_ids'], caches['intervened_weight'], caches['intervened_content_weights']
+        sample = torch.arange(b0, b0 + batch, device=input_ids.device)
+        at = lengths.long()
+        ids[sample, at] = input_ids[:, 0]
+        if not self.anneal:
+            weight[sample, :, at] = cw[input_ids[:, 0]]                            # fixed once appended
+            return weight[b0:b0 + batch]
+        # sims[b,l,i] += relu(C_l(x_i) . E[x_L]) for the cached i < L, and the new position's own sum over all tokens; the
+        # pair (L, L) comes once, out of the rows-dot (its row is new_row).  Fixed shapes over max_sequence_len masked by
+        # the device lengths: a captured step is valid for every later step.
+        emb_w = self.backpack_network.lm_head.weight
+        sims, dots = caches['intervened_sims'][b0:b0 + batch], caches['intervened_dots'][b0:b0 + batch]
+        vec = emb_w[input_ids[:, 0]]                                               # (B,d) = E[x_L]
+        pos = torch.arange(ms, device=input_ids.device)
+        cached, new = pos[None, :] < at[:, None], pos[None, :] == at[:, None]      # (B,ms)
+        if model.fused_senses:
+            if not bp_hip.sense_rows_dot_supported(table, vec):
+                raise RuntimeError(f'Backpack decode: bp_sense_rows_dot does not take {table.shape[1]} senses with '
+                                   f'{table.shape[2]} output columns (include/bp_hip.h)')
+            bp_hip.sense_rows_dot(table, rows, new_row, lengths, vec, dots)
+        else:
+            dots.copy_(_eager_rows_dot(table, rows, new_row, lengths, vec))
+        own = torch.einsum('bld,bjd->blj', table[new_row.long()], emb_w[ids[b0:b0 + batch]])   # (B,k,ms)
+        own = torch.where(cached[:, None, :], torch.relu(own).float(), 0.0).sum(dim=2, keepdim=True)
+        hit = torch.relu(dots)
+        sims.copy_(torch.where(cached[:, None, :], sims + hit, torch.where(new[:, None, :], own + hit, sims)))
+        picked = cw[ids[b0:b0 + batch]].transpose(1, 2)                            # (B,k,ms)
+        weight[b0:b0 + batch] = _anneal_weights(sims, picked, self.annealing_scale, self.upweight_nearby)
+        return weight[b0:b0 + batch]
+
+
+def _eager_rows_dot(table, rows, new_row, lengths, vec):
+    """Eager restatement of bp_sense_rows_dot over the whole row index: (B,k,max_seqlen) fp32 = table[row(b,j), l] . vec[b]
+    in the tensors' dtype, position lengths[b] taking new_row[b]; entries past it carry no meaning."""
+    pos = torch.arange(rows.shape[1], device=rows.device)
+    index = torch.where(pos[None, :] == lengths[:, None].long(), new_row[:, None].long(), rows.long())
+    index = index.clamp(0, table.shape[0] - 1)
+    return torch.einsum('bjld,bd->blj', table[index], vec).float()
 
 
 class NegativeWeightedBackpackLMHeadModel(WeightedBackpackLMHeadModel):
@@ -109,6 +226,10 @@ class NegativeWeightedBackpackLMHeadModel(WeightedBackpackLMHeadModel):
     then the contraction runs on vocabulary-sized content (reference :108-165)."""
 
     def forward(self, input_ids, position_ids=None, inference_params=None):
+        if inference_params is not None:
+            raise NotImplementedError(
+                'NegativeWeightedBackpackLMHeadModel has no KV-cached decoding: its content is vocabulary-sized per '
+                '(position, sense) and does not fit a cache; generate without kv_cache')
         t, hidden, content = self._stages(input_ids, position_ids, inference_params)
         weights = self._weights(input_ids, content)                              # (B,k,S)
         # everything in the content's storage order (B,S,k,.) -- the order the kernel reads -- so the
@@ -140,7 +261,35 @@ class ReplacedWordLMHeadModel(_Intervened):
                 content[b_idx, :, s_idx, :] = senses.to(content.device, content.dtype)
         return content
 
+    # ---- KV-cached decoding: cache form only (the rows are edited as they are appended; the whole-vocabulary table is
+    # neither cloned nor edited), sense_dict as a device lookup so that a captured step asks the host nothing ----
+    cache_form_only = True
+
+    def edit_rows(self, input_ids, content):
+        slot, rows = self._lookup
+        s = slot[input_ids]                                                       # (B,S), -1 = keep the token's own rows
+        picked = rows[s.clamp(min=0)]                                             # (B,S,k,d)
+        return torch.where((s >= 0)[:, :, None, None], picked, content.transpose(1, 2)).transpose(1, 2)
+
+    def _read_sense_dict(self, ip, device, dtype):
+        """token id -> slot (vocab,) and the stacked replacement rows (n,k,d): once per prefill."""
+        vocab = self.backpack_network.lm_head.weight.shape[0]
+        t = self.backpack_network.transformer
+        slot = torch.full((vocab,), -1, dtype=torch.long)
+        rows = [torch.zeros(t.num_content_vectors, t.config.n_embd)]              # slot 0 when the dict is empty
+        for n, (word, senses) in enumerate(self.sense_dict.items()):
+            slot[int(word)] = n
+            rows.append(senses.detach().cpu().float())
+        rows = rows[1:] or rows
+        ip.key_value_memory_dict['intervened_replace'] = (slot.to(device), torch.stack(rows).to(device, dtype))
+
     def forward(self, input_ids, position_ids=None, inference_params=None):
+        if inference_params is not None:
+            ip = inference_params
+            if ip.sequence_len_offset == 0:
+                self._read_sense_dict(ip, input_ids.device, self.backpack_network.lm_head.weight.dtype)
+            self._lookup = ip.key_value_memory_dict['intervened_replace']
+            return self._forward_cached(input_ids, position_ids, ip)
         t, hidden, content = self._stages(input_ids, position_ids, inference_params)
         content = self.replace_content(input_ids, content)
         if t.fused_senses and content.transpose(1, 2).stride(-1) != 1:

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define BP_ABI_VERSION 10  /* 2: *_dropout entry points added; 3: bias/GELU + column-sum entry points added, the
+#define BP_ABI_VERSION 11  /* 2: *_dropout entry points added; 3: bias/GELU + column-sum entry points added, the
                               persistent sense-mix launches take a caller-owned `queue_ws`; 4: bp_flash_bwd* take the
                               size of `dsum_ws` (bp_flash_bwd_ws_floats) and check it, queue_ws == NULL is refused
                               while the stream is capturing (BP_ERR_QUEUE_WS); 5: bp_dropout_add_layer_norm_scaled{,_bwd}
@@ -39,7 +39,10 @@ extern "C" {
                               9: bp_sense_mix_gather takes the two few-sense widths d_k = 160 / 640 (seqlen % 32 == 0; any
                               number of table rows);
                               10: bp_flash_decode / bp_sense_decode (KV-cached single-token decoding) and their
-                              *_ws_floats queries added */
+                              *_ws_floats queries added;
+                              11: bp_sense_decode_weighted (per-key weights on the decode step's probabilities) and
+                              bp_sense_rows_dot (dot products of the cached positions' sense vectors with one vector)
+                              added: KV-cached decoding of the intervened Backpacks */
 
 /* element type of q/k/v/out/content tensors */
 #define BP_DTYPE_F16 0
@@ -562,6 +565,47 @@ int bp_sense_decode(const void *q, const void *k_new, void *k_cache, const void 
                     int64_t kc_batch_stride, int64_t kc_row_stride, int64_t kc_sense_stride,
                     int64_t t_row_stride, int64_t t_sense_stride, int64_t idx_batch_stride,
                     int64_t o_batch_stride, float softmax_scale, int dtype, bp_stream_t stream);
+
+/*
+ * bp_sense_decode_weighted -- bp_sense_decode with the intervention hook of bp_sense_mix_weighted, restricted to the
+ * last row (training/src/models/intervened_models.py:78-101, test_genderbias.py:71-78 on a KV cache):
+ *   out[b,:] = sum_l sum_{j<=t} softmax_j(scale q[b,l,:].k_l(j)) key_weight[b,l,j] table[row(b,j), l, :]
+ *   key_weight   (batch, nsenses, max_seqlen) fp32, element strides kw_batch / kw_sense (each >= max_seqlen), unit stride
+ *                along the positions.  Entries [0, L_b] are read, entry L_b (the new position's) included: the caller
+ *                fills it before the call.  Never written.  The weight multiplies the normalised probability and does
+ *                not enter the softmax.  NULL: bp_sense_decode exactly (the strides are then ignored)
+ * Every other operand, the append of key and row index, the clamps, the split and its fixed-order combine, the limits and
+ * the error codes are bp_sense_decode's; the workspace is sized by bp_sense_decode_ws_floats.
+ */
+int bp_sense_decode_weighted(const void *q, const void *k_new, void *k_cache, const void *table, int32_t *row_index,
+                             const int32_t *new_row, const int32_t *cache_seqlens, const float *key_weight, void *out,
+                             float *ws, int64_t ws_floats,
+                             int batch, int nsenses, int d_k, int d_out, int max_seqlen, int64_t table_rows,
+                             int64_t q_batch_stride, int64_t q_sense_stride,
+                             int64_t knew_batch_stride, int64_t knew_sense_stride,
+                             int64_t kc_batch_stride, int64_t kc_row_stride, int64_t kc_sense_stride,
+                             int64_t t_row_stride, int64_t t_sense_stride, int64_t idx_batch_stride,
+                             int64_t o_batch_stride, int64_t kw_batch_stride, int64_t kw_sense_stride,
+                             float softmax_scale, int dtype, bp_stream_t stream);
+
+/*
+ * bp_sense_rows_dot -- dot products of the sense vectors of every cached position, and of the new one, with one vector
+ * per sample: the update of the running similarity sums of mask_annealing (intervened_models.py:29-53) in a decode step,
+ *   out[b,l,j] = sum_c table[row(b,j), l, c] * vec[b,c],   j = 0 .. L_b,   row(b, L_b) = new_row[b]
+ *   table, row_index, new_row, cache_seqlens, table_rows   as in bp_sense_decode, clamps included; nothing but `out` is
+ *                written (row_index in particular is only read, entry L_b not at all)
+ *   vec          (batch, d_out) 16-bit, batch stride vec_batch, last stride 1
+ *   out          (batch, nsenses, max_seqlen) fp32, element strides o_batch / o_sense (each >= max_seqlen), unit stride
+ *                along the positions; entries j > L_b are left untouched
+ * fp32 accumulation in a fixed order (bit-identical across calls); the lengths are read on the device only.
+ * 1 <= nsenses <= 64, d_out >= 1 (BP_ERR_DOUT), d_out % 8 == 0 and <= 2048, table and vec 16-byte aligned, their strides
+ * multiples of 8 (BP_ERR_SHAPE).
+ */
+int bp_sense_rows_dot(const void *table, const int32_t *row_index, const int32_t *new_row, const int32_t *cache_seqlens,
+                      const void *vec, float *out,
+                      int batch, int nsenses, int d_out, int max_seqlen, int64_t table_rows,
+                      int64_t t_row_stride, int64_t t_sense_stride, int64_t idx_batch_stride, int64_t vec_batch_stride,
+                      int64_t o_batch_stride, int64_t o_sense_stride, int dtype, bp_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -3,7 +3,12 @@ against generate(..., cg=True), one captured full-width forward replayed per tok
 generate(..., kv_cache=True) eagerly and with cg=True (one captured decode step replayed per token; src/utils/generation.py).
 
     python scripts/bench_generate.py [--batch 1] [--prompt 16] [--max-length 128] [--model small] [--modes off,cached]
-                                     [--legs full,kv]"""
+                                     [--legs full,kv] [--intervention none|weighted|weighted-anneal|replaced]
+
+--intervention wraps the model in the control-experiment classes of src/models/intervened_models.py (seeded
+content_weights in [0, 3); for the annealed form a scale of 6 / median of the similarity sums at half the final length, so
+that the scores are not saturated; eight replaced tokens, four of them in the prompt) and times the same legs on the
+wrapper."""
 import argparse
 import json
 import os
@@ -24,6 +29,7 @@ def main():
     ap.add_argument('--model', default='small')
     ap.add_argument('--modes', default='off,cached', help='sense_table modes to run')
     ap.add_argument('--legs', default='full,kv', help='full: growing-prefix loop and its graph; kv: the KV-cached legs')
+    ap.add_argument('--intervention', default='none', choices=['none', 'weighted', 'weighted-anneal', 'replaced'])
     a = ap.parse_args()
     from bench import MODELS
     from src.models.backpack import BackpackConfig, BackpackLMHeadModel
@@ -34,15 +40,18 @@ def main():
     torch.manual_seed(0)
     model = BackpackLMHeadModel(cfg, device=dev, dtype=torch.bfloat16).eval()
     ids = torch.randint(0, 50257, (a.batch, a.prompt), device=dev)
+    extra = {}
+    if a.intervention != 'none':
+        model, extra = intervene(model, a.intervention, ids, (a.prompt + a.max_length) // 2)
     legs = []
     if 'full' in a.legs.split(','):
         legs += [('eager_loop', False, False), ('graph_replay', True, False)]
     if 'kv' in a.legs.split(','):
         legs += [('kv_cache_eager', False, True), ('kv_cache_graph', True, True)]
     for mode in a.modes.split(','):   # content network per position (the reference's order) / cached whole-vocabulary table
-        model.transformer.sense_table_mode = mode
+        getattr(model, 'backpack_network', model).transformer.sense_table_mode = mode
         res = dict(model=a.model, batch=a.batch, prompt=a.prompt, max_length=a.max_length,
-                   new_tokens=a.max_length - 1 - a.prompt, sense_table=mode)
+                   new_tokens=a.max_length - 1 - a.prompt, sense_table=mode, **extra)
         outs = {}
         for key, cg, kv in legs:
             model.generate(ids, max_length=a.max_length, cg=cg, kv_cache=kv)      # warm-up (allocator, library handles)
@@ -62,6 +71,29 @@ def main():
                 res['kv_tokens_equal_fraction'] = round(
                     (outs['kv_cache_eager'] == outs['eager_loop']).float().mean().item(), 4)
         print(json.dumps(res), flush=True)
+
+def intervene(model, kind, ids, middle):
+    """The wrapper of `kind` around `model`, and what to report about it."""
+    from src.models.intervened_models import ReplacedWordLMHeadModel, WeightedBackpackLMHeadModel
+    g = torch.Generator().manual_seed(11)
+    k, d, vocab = model.config.num_content_vectors, model.config.n_embd, model.lm_head.weight.shape[0]
+    if kind == 'replaced':
+        words = ids[0, :4].tolist() + torch.randint(0, 50257, (4,), generator=g).tolist()
+        senses = {w: (torch.randn(k, d, generator=g) * 0.02).to(ids.device, torch.bfloat16) for w in words}
+        return ReplacedWordLMHeadModel(model, senses).eval(), dict(intervention=kind)
+    cw = (torch.rand(vocab, k, generator=g) * 3).to(ids.device)
+    if kind == 'weighted':
+        return WeightedBackpackLMHeadModel(model, cw, None, 0.1, anneal=False).eval(), dict(intervention=kind)
+    with torch.no_grad():   # random tokens stand in for the continuation of a randomly initialised model
+        probe = torch.randint(0, 50257, (ids.shape[0], middle), device=ids.device)
+        content = model.transformer.content_model(probe).float()
+        sims = torch.relu(content @ model.lm_head.weight[probe].float().transpose(1, 2).unsqueeze(1)).sum(dim=3)
+    scale = 6.0 / sims.median().item()
+    scores = torch.sigmoid(-scale * sims + 6)
+    band = ((scores >= 0.1) & (scores <= 0.9)).float().mean().item()
+    return (WeightedBackpackLMHeadModel(model, cw, None, scale, anneal=True).eval(),
+            dict(intervention=kind, annealing_scale=round(scale, 3), scores_in_band=round(band, 3)))
+
 
 if __name__ == '__main__':
     main()
