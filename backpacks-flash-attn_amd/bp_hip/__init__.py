@@ -934,9 +934,9 @@ class GraphedForward:
         # whose refresh did not land in this storage is refused instead of reading a freed block.
         self._pinned = []
         for m in module.modules():
-            if hasattr(m, 'pin_sense_table') and getattr(m, '_sense_table', None) is not None:
+            if hasattr(m, 'pin_sense_table') and m.sense_table_rows(stale_too=True) is not None:
                 m.pin_sense_table()
-                self._pinned.append((m, m._sense_table[1]))
+                self._pinned.append((m, m.sense_table_rows(stale_too=True)))
         self.module = module
 
     def __call__(self, x):
@@ -948,8 +948,8 @@ class GraphedForward:
             with torch.no_grad():
                 self.refresh()
         for m, table in self._pinned:
-            now = m._sense_table[1] if m._sense_table is not None else None
-            if now is None or now.data_ptr() != table.data_ptr() or m._sense_table[0] is None:
+            now = m.sense_table_rows()             # None: dropped, or stale and not refreshed
+            if now is None or now.data_ptr() != table.data_ptr():
                 raise RuntimeError('bp_hip.GraphedForward: the sense table the graph reads was replaced or could not be '
                                    'refreshed in place; capture a new GraphedForward')
         self.graph.replay()

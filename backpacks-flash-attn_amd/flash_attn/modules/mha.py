@@ -243,11 +243,8 @@ class MHA(nn.Module):
             assert seqlen <= cache.shape[1], 'prompt longer than max_sequence_len'
             cache[b0:b1, :seqlen] = qkv[:, :, 1:]
             context = self.inner_attn(qkv)                                  # causal flash kernel / eager twin
-        elif seqlen != 1:
-            raise NotImplementedError(
-                f'KV-cached decoding takes one new token per sample after the prompt (got {seqlen} at offset '
-                f'{inference_params.sequence_len_offset}); feed multi-token continuations one token at a time')
         else:
+            refuse_multi_token_step(seqlen, inference_params)
             lengths = cache_lengths(inference_params, batch, qkv.device)
             scale = self.inner_attn.softmax_scale or self.head_dim ** -0.5
             q, k_new, v_new = qkv[:, 0].unbind(dim=1)                       # (B, H, D) each
@@ -267,6 +264,14 @@ def cache_lengths(inference_params, batch, device):
         b0 = inference_params.batch_size_offset
         return lengths[b0:b0 + batch]
     return torch.full((batch,), inference_params.sequence_len_offset, dtype=torch.int32, device=device)
+
+
+def refuse_multi_token_step(seqlen, inference_params):
+    """After the prompt (`sequence_len_offset` > 0) a cached call takes ONE new token per sample: MHA's contract above."""
+    if inference_params.sequence_len_offset != 0 and seqlen != 1:
+        raise NotImplementedError(
+            f'KV-cached decoding takes one new token per sample after the prompt (got {seqlen} at offset '
+            f'{inference_params.sequence_len_offset}); feed multi-token continuations one token at a time')
 
 
 def _eager_decode(q, kv_new, cache, b0, lengths, scale):

@@ -28,7 +28,7 @@ from transformers import GPT2Config
 import bp_hip
 from flash_attn.models.gpt import GPTModel, GPTPreTrainedModel, _activation, _init_weights, _pad_vocab
 from flash_attn.modules.block import Block
-from flash_attn.modules.mha import cache_lengths
+from flash_attn.modules.mha import cache_lengths, refuse_multi_token_step
 from flash_attn.modules.mlp import FusedDenseGeluDense, Mlp
 from flash_attn.ops.fused_dense import FusedDense, fused_dense_func
 from flash_attn.ops.layer_norm import dropout_add_layer_norm
@@ -79,6 +79,14 @@ def create_nomix_block(config, expand_out=False, layer_idx=None, process_group=N
     return block
 
 
+def _version_key(params):
+    """What tells that one of `params` was updated (`_version` moves on every in-place update, `data_ptr` on a reload /
+    `.to()`; writes through `.data` move neither).  None when one is an inference tensor: no version counter to key on."""
+    if any(p.is_inference() for p in params):
+        return None
+    return tuple((p.data_ptr(), p._version, p.dtype, p.device) for p in params)
+
+
 class ContextSelfAttn(nn.Module):
     """num_content_vectors causal attention maps per pair of positions (reference :94-122).
 
@@ -104,6 +112,7 @@ class ContextSelfAttn(nn.Module):
                           f'{embed_dim // num_content_vectors} > {bp_hip.SENSE_MAX_DK}: the sense weights and their combination '
                           'run as the eager op sequence on the GPU (the HIP sense kernels cover d_k <= '
                           f'{bp_hip.SENSE_MAX_DK}); the trunk keeps its HIP kernels')
+        self._padded_cache = None      # (version key, padded weight, padded bias) of `_padded_projection`
 
     def project(self, encoded):
         """encoded (B,S,d) -> qk (B,S,2,k,d_k).  On the HIP path a d_k that is not a multiple of 8 (the Mini
@@ -135,17 +144,13 @@ class ContextSelfAttn(nn.Module):
         # While a HIP graph is being captured the pad kernels must be PART of the graph: a cached copy made outside
         # (e.g. by GraphedForward's warm-up forwards) would be what every replay reads, also after the weights were
         # updated in place.  Inference tensors carry no version counter: nothing to key a cache on, pad per call.
-        if (weight.is_cuda and torch.cuda.is_current_stream_capturing()) or weight.is_inference() \
-                or bias.is_inference():
-            with torch.no_grad():
+        key = None if weight.is_cuda and torch.cuda.is_current_stream_capturing() else _version_key((weight, bias))
+        with torch.no_grad():
+            if key is None:
                 return pad_now()
-        key = (weight.data_ptr(), weight._version, bias.data_ptr(), bias._version, weight.dtype, weight.device)
-        cached = getattr(self, '_padded_cache', None)
-        if cached is None or cached[0] != key:
-            with torch.no_grad():
-                cached = (key,) + pad_now()
-            self._padded_cache = cached
-        return cached[1], cached[2]
+            if self._padded_cache is None or self._padded_cache[0] != key:
+                self._padded_cache = (key,) + pad_now()
+        return self._padded_cache[1:]
 
     def scale(self):
         """softmax scale of the TRUE sense width d/k (reference :117), whatever `project` padded to."""
@@ -234,6 +239,75 @@ class BackpackContentModule(nn.Module):
         return hidden.reshape(bs, s, self.num_content_vectors, self.n_embd).transpose(1, 2)
 
 
+class _SenseTable:
+    """The whole-vocabulary sense table of one content model and everything that decides whether it may be served.
+    A plain object: it registers nothing with the model and is no part of its state dict."""
+
+    def __init__(self, content_model):
+        self.content_model = content_model
+        self.rows = None            # (V, k, d) storage; kept when the table goes stale: a rebuild lands in the SAME storage
+        self.key = None             # `_version_key` of the parameters the rows were built from; None = stale (or no rows)
+        self.fingerprint = None     # `key` + the sums of the parameter values, when the build was asked to `verify`
+        self.pinned = False         # a captured graph holds the storage's address: training leaves a stale table, not none
+        self.oom_warned = False
+
+    def version_key(self, fingerprint=False):
+        params = list(self.content_model.parameters())
+        key = _version_key(params)
+        if key is not None and fingerprint:
+            # `p.data.copy_()` / `p.data.mul_()` (the reference's own EMA swap, training/src/utils/ema.py:121,165) write the
+            # storage WITHOUT moving `p._version`: only the values themselves tell.  One fp32 sum per parameter, one
+            # device-to-host copy (a synchronisation: callers decide when that is affordable, `_verify_applies`).
+            with torch.no_grad():
+                sums = torch.stack([torch.sum(p.detach(), dtype=torch.float32) for p in params])
+            key = key + (tuple(sums.tolist()),)
+        return key
+
+    def invalidate(self):
+        self.key = self.fingerprint = None
+
+    def training_starts(self):
+        # training runs per position; do not hold 1-4 GB of stale rows -- unless a captured graph reads this storage
+        self.invalidate()
+        if not self.pinned:
+            self.rows = None
+
+    def lookup(self, verify=False):
+        """The rows, rebuilt in place first when the parameters moved on, or None: see BackpackModel.sense_table."""
+        key = self.version_key()
+        if key is None:
+            return None
+        if self.key == key:
+            if not verify:
+                return self.rows
+            if self.fingerprint is not None and self.fingerprint == self.version_key(fingerprint=True):
+                return self.rows
+            # (a table built without a fingerprint cannot vouch for the values: rebuild once, then it can)
+        weight = self.content_model.embeddings.word_embeddings.weight
+        if weight.is_cuda and torch.cuda.is_current_stream_capturing():
+            return None
+        fingerprint = self.version_key(fingerprint=True) if verify else None
+        with torch.inference_mode(False), torch.no_grad():
+            was_training = self.content_model.training
+            self.content_model.eval()                 # (also the embedding module it shares with the trunk)
+            try:
+                ids = torch.arange(weight.shape[0], device=weight.device).unsqueeze(0)
+                rows = self.content_model(ids)[0].transpose(0, 1)      # (V,k,d): the (1,V,k*d) block as it lies
+                if self.rows is not None and (self.rows.shape, self.rows.dtype, self.rows.device) == \
+                        (rows.shape, rows.dtype, rows.device):
+                    rows = self.rows.copy_(rows)
+            except torch.OutOfMemoryError:
+                if not self.oom_warned:
+                    warnings.warn('Backpack: not enough memory for the whole-vocabulary sense table; the forward runs '
+                                  'the content network per position')
+                    self.oom_warned = True
+                return None
+            finally:
+                self.content_model.train(was_training)
+        self.rows, self.key, self.fingerprint = rows, key, fingerprint
+        return rows
+
+
 class BackpackModel(GPTPreTrainedModel):
 
     def __init__(self, config: BackpackConfig, process_group=None, device=None, dtype=None):
@@ -251,10 +325,11 @@ class BackpackModel(GPTPreTrainedModel):
         # 'batch' mode pays from about 0.65 x vocab positions up with uniformly random ids (Small, S = 1024: equal at 32 k
         # positions, -6 % at 49 k, -12 % at 100 k; profiles/r05_a_content_modes_small.jsonl); text repeats tokens and pays earlier
         self.dedup_min_positions = int(getattr(config, 'dedup_min_positions', config.vocab_size))
-        self._sense_table = None
+        self._gather_fallback_said = False
         self.gpt2_model = GPTModel(config, **factory_kwargs)
         self.content_model = BackpackContentModule(config, self.num_content_vectors,
                                                    self.gpt2_model.embeddings, **factory_kwargs)
+        self._sense_table = _SenseTable(self.content_model)
         self.embeddings = self.gpt2_model.embeddings   # shared with the contextualisation model
         self.contextualization_attn = ContextSelfAttn(self.num_content_vectors, config.n_embd,
                                                       use_hip=self.use_hip, **factory_kwargs)
@@ -279,9 +354,12 @@ class BackpackModel(GPTPreTrainedModel):
     # Mathematically identical to the per-position order; bits can differ where the BLAS GEMMs round a row differently
     # when the row count changes.  Training always runs per position (dropout inside the content network, autograd).
 
+    def _table_mode(self):
+        """`sense_table_mode` as it applies now: 'off' while no token table may be used; callers add autograd, device, capture."""
+        return self.sense_table_mode if self.dedup_content and self.fused_senses and not self.training else 'off'
+
     def _token_table_allowed(self, input_ids):
-        return (self.dedup_content and self.sense_table_mode != 'off' and self.fused_senses and not self.training
-                and not torch.is_grad_enabled() and input_ids.is_cuda)
+        return self._table_mode() != 'off' and not torch.is_grad_enabled() and input_ids.is_cuda
 
     def _dedup_applies(self, input_ids):
         """True when this forward builds the table of the batch's distinct tokens ('batch' mode, or 'cached' mode whose
@@ -292,20 +370,6 @@ class BackpackModel(GPTPreTrainedModel):
         if self.sense_table_mode == 'cached' and self.sense_table() is not None:
             return False
         return input_ids.numel() >= self.dedup_min_positions
-
-    def _sense_table_key(self, fingerprint=False):
-        params = list(self.content_model.parameters())
-        if any(p.is_inference() for p in params):
-            return None                       # no version counter to key a cache on
-        key = tuple((p.data_ptr(), p._version, p.dtype, p.device) for p in params)
-        if fingerprint:
-            # `p.data.copy_()` / `p.data.mul_()` (the reference's own EMA swap, training/src/utils/ema.py:121,165) write the
-            # storage WITHOUT moving `p._version`: only the values themselves tell.  One fp32 sum per parameter, one
-            # device-to-host copy (a synchronisation: callers decide when that is affordable, `_verify_applies`).
-            with torch.no_grad():
-                sums = torch.stack([torch.sum(p.detach(), dtype=torch.float32) for p in params])
-            key = key + (tuple(sums.tolist()),)
-        return key
 
     def _verify_applies(self, input_ids):
         """Whether this forward also checks the cached table against the parameter VALUES (`config.sense_table_verify`:
@@ -326,13 +390,12 @@ class BackpackModel(GPTPreTrainedModel):
         `p.data.mul_()`, writes through `untyped_storage()` -- when the forward is too small for the automatic value check
         (see `_verify_applies`).  In-place updates through the parameter itself, `load_state_dict`, `.to()` are seen
         without it."""
-        if self._sense_table is not None:
-            self._sense_table = (None, self._sense_table[1], None)
+        self._sense_table.invalidate()
 
     def pin_sense_table(self, pinned=True):
         """Keep the table's storage across `.train()` (a captured HIP graph holds its address: bp_hip.GraphedForward pins
         it); an unpinned table is dropped when training starts."""
-        self._sense_table_pinned = bool(pinned)
+        self._sense_table.pinned = bool(pinned)
 
     def sense_table(self, verify=False):
         """(vocab rows, k, d): the content network's output for EVERY row of the word embedding, kept until a parameter of
@@ -344,53 +407,22 @@ class BackpackModel(GPTPreTrainedModel):
         (inference-mode parameters), when the table would have to be built while a stream is capturing, or when the
         build runs out of memory (one warning; the forward then takes the per-position order).  1.2 GB at
         Backpack-Small, 4.1 GB at Mini k = 64; ~5 ms to build."""
-        key = self._sense_table_key()
-        if key is None:
-            return None
-        cached = self._sense_table
-        if cached is not None and cached[0] == key:
-            if not verify:
-                return cached[1]
-            full = self._sense_table_key(fingerprint=True)
-            if cached[2] is not None and cached[2] == full:
-                return cached[1]
-            # (a table built without a fingerprint cannot vouch for the values: rebuild once, then it can)
-        weight = self.embeddings.word_embeddings.weight
-        if weight.is_cuda and torch.cuda.is_current_stream_capturing():
-            return None
-        full = self._sense_table_key(fingerprint=True) if verify else None
-        with torch.inference_mode(False), torch.no_grad():
-            was_training = self.content_model.training
-            self.content_model.eval()                 # (also the embedding module it shares with the trunk)
-            try:
-                ids = torch.arange(weight.shape[0], device=weight.device).unsqueeze(0)
-                rows = self.content_model(ids)[0].transpose(0, 1)      # (V,k,d): the (1,V,k*d) block as it lies
-                if cached is not None and cached[1].shape == rows.shape and cached[1].dtype == rows.dtype \
-                        and cached[1].device == rows.device:
-                    cached[1].copy_(rows)
-                    rows = cached[1]
-            except torch.OutOfMemoryError:
-                if not getattr(self, '_sense_table_oom_warned', False):
-                    warnings.warn('Backpack: not enough memory for the whole-vocabulary sense table; the forward runs '
-                                  'the content network per position')
-                    self._sense_table_oom_warned = True
-                return None
-            finally:
-                self.content_model.train(was_training)
-        self._sense_table = (key, rows, full)
-        return rows
+        return self._sense_table.lookup(verify)
+
+    def sense_table_rows(self, stale_too=False):
+        """The rows the table vouches for as it stands (no lookup, no rebuild), or None; `stale_too`: its storage, stale or not."""
+        return self._sense_table.rows if stale_too or self._sense_table.key is not None else None
 
     def refresh_inference_caches(self):
         """Bring the cached sense table up to date with the weights (a no-op when it is); call in front of replaying a
         captured graph of this model after an in-place weight update (after a `.data` update: `invalidate_sense_table()`
         first)."""
-        if self.sense_table_mode == 'cached' and self.dedup_content and self.fused_senses and not self.training:
+        if self._table_mode() == 'cached':
             self.sense_table()
 
     def train(self, mode=True):
-        if mode and self._sense_table is not None:
-            # training runs per position; do not hold 1-4 GB of stale rows -- unless a captured graph reads this storage
-            self._sense_table = (None, self._sense_table[1], None) if getattr(self, '_sense_table_pinned', False) else None
+        if mode:
+            self._sense_table.training_starts()
         return super().train(mode)
 
     def _table_of_unique_tokens(self, input_ids):
@@ -412,7 +444,7 @@ class BackpackModel(GPTPreTrainedModel):
             return bp_hip.sense_mix_gather(qk, rows, index.to(torch.int32), self.contextualization_attn.scale())
         # shapes the gathering kernel does not take: torch gathers the rows into the (B,S,k,d) tensor the dense kernel
         # reads -- said once per model, with the limit that was hit (bp_hip.sense_mix_gather_limits)
-        if not getattr(self, '_gather_fallback_said', False):
+        if not self._gather_fallback_said:
             self._gather_fallback_said = True
             warnings.warn('Backpack: the sense table is gathered by torch into a (B, S, k*d) tensor instead of inside the '
                           'mix kernel: ' + bp_hip.sense_mix_gather_limits(qk, rows, index.shape[1]))
@@ -463,23 +495,13 @@ class BackpackModel(GPTPreTrainedModel):
     # per token -- and its rows are appended; rows = b * max_seqlen + j.  The form is fixed by the prefill.
     # Fused senses decode with bp_sense_decode; non-fused ones (d_k > 640, use_flash_attn=False) with an eager restatement.
     #
-    # `intervention` (src/models/intervened_models.py, nothing else): the one hook of the cached path.  An object with
-    #   cache_form_only                       True: never the table form (its rows are edited per position)
-    #   edit_rows(input_ids, content)         cache form: the (B,k,S,d) rows of the new positions, before they are appended
-    #   prefill_key_weight(model, input_ids, content, ip)                         -> (B,k,S) fp32 or None
-    #   step_key_weight(model, input_ids, table, rows, new_row, lengths, ip)      -> (B,k,max_seqlen) fp32 or None
-    # The weights go to bp_sense_mix / bp_sense_decode as `key_weight`.  Without a hook nothing here differs from the plain
-    # model, call for call.
-
-    def _decode_sense_table(self, input_ids):
-        if self.sense_table_mode == 'cached' and self.dedup_content and self.fused_senses and not self.training \
-                and input_ids.is_cuda:
-            return self.sense_table()
-        return None
+    # A wrapper that changes what enters the contraction passes itself as `intervention` (a SenseIntervention, below).
+    # Without one nothing here differs from the plain model, call for call.
 
     def _decode_caches(self, ip, qk, content_form, like):
+        """The Backpack's caches (created by the first prefill) and the batch rows b0:b1 of this call."""
         caches = ip.key_value_memory_dict
-        k, dk = qk.shape[3], qk.shape[4]
+        batch, k, dk = qk.shape[0], qk.shape[3], qk.shape[4]
         mb, ms = ip.max_batch_size, ip.max_sequence_len
         if 'backpack_sense_k' not in caches:
             caches['backpack_sense_k'] = torch.zeros(mb, ms, k, dk, dtype=qk.dtype, device=qk.device)
@@ -487,90 +509,83 @@ class BackpackModel(GPTPreTrainedModel):
             if content_form:
                 caches['backpack_content'] = torch.zeros(mb * ms, k, self.config.n_embd, dtype=like.dtype,
                                                          device=like.device)
-        return caches['backpack_sense_k'], caches['backpack_rows'], caches.get('backpack_content')
+        b0 = ip.batch_size_offset
+        return _DecodeCaches(caches['backpack_sense_k'], caches['backpack_rows'], caches.get('backpack_content'), b0,
+                             b0 + batch, torch.arange(b0, b0 + batch, device=qk.device))
 
     def _forward_cached(self, input_ids, position_ids, ip, intervention=None):
         if torch.is_grad_enabled():
             raise RuntimeError('KV-cached decoding is inference-only: run it under torch.no_grad() or '
                                'torch.inference_mode()')
-        batch, seqlen = input_ids.shape
-        prefill = ip.sequence_len_offset == 0
-        if not prefill and seqlen != 1:
-            raise NotImplementedError(
-                f'KV-cached decoding takes one new token per sample after the prompt (got {seqlen} at offset '
-                f'{ip.sequence_len_offset}); feed multi-token continuations one token at a time')
+        refuse_multi_token_step(input_ids.shape[1], ip)
         hidden = self.gpt2_model(input_ids, position_ids=position_ids, inference_params=ip)
-        attn = self.contextualization_attn
-        qk = attn.project(hidden)                                        # (B, S, 2, k, d_k)
-        if prefill:
-            cache_form_only = intervention is not None and intervention.cache_form_only
-            table = None if cache_form_only else self._decode_sense_table(input_ids)
+        qk = self.contextualization_attn.project(hidden)                 # (B, S, 2, k, d_k)
+        phase = self._cached_prefill if ip.sequence_len_offset == 0 else self._cached_step
+        return phase(input_ids, hidden, qk, ip, intervention)
+
+    def _cached_prefill(self, input_ids, hidden, qk, ip, intervention):
+        """The prompt: fills the caches (and fixes their form), returns the mix of every prompt position (B, S, d)."""
+        batch, seqlen = input_ids.shape
+        cache_form_only = intervention is not None and intervention.cache_form_only
+        table = self.sense_table() if self._table_mode() == 'cached' and input_ids.is_cuda and not cache_form_only else None
+        c = self._decode_caches(ip, qk, table is None, hidden)
+        c.keys[c.b0:c.b1, :seqlen] = qk[:, :, 1]
+        if table is not None:
+            c.rows[c.b0:c.b1, :seqlen] = input_ids
+            if intervention is None:
+                return self._mix_from_table(hidden, table, input_ids, qk=qk)
+            # bp_sense_mix_gather has no weighted form: torch gathers the prompt's rows (prompts are short), as the
+            # fallback of _mix_from_table does
+            content = F.embedding(input_ids, table.reshape(table.shape[0], -1)) \
+                .view(batch, seqlen, *table.shape[1:]).transpose(1, 2)
         else:
-            table = None if 'backpack_content' in ip.key_value_memory_dict else self.sense_table()
-            if table is None and 'backpack_content' not in ip.key_value_memory_dict:
-                raise RuntimeError('Backpack decode: the cache was filled in table form but the sense table is gone '
-                                   '(weights changed, or .train() was called, since the prefill)')
-        key_cache, rows, content_cache = self._decode_caches(ip, qk, table is None, hidden)
-        b0, ms = ip.batch_size_offset, ip.max_sequence_len
-        b1 = b0 + batch
-        sample = torch.arange(b0, b1, device=input_ids.device)
-        if prefill:
-            key_cache[b0:b1, :seqlen] = qk[:, :, 1]
-            if table is not None:
-                rows[b0:b1, :seqlen] = input_ids
-                if intervention is None:
-                    return self._mix_from_table(hidden, table, input_ids, qk=qk)
-                # bp_sense_mix_gather has no weighted form: torch gathers the prompt's rows (prompts are short), as the
-                # fallback of _mix_from_table does
-                content = F.embedding(input_ids, table.reshape(table.shape[0], -1)) \
-                    .view(batch, seqlen, *table.shape[1:]).transpose(1, 2)
-            else:
-                content = self.content_model(input_ids)                  # (B, k, S, d) view of (B, S, k*d)
-                if intervention is not None:
-                    content = intervention.edit_rows(input_ids, content)
-                rows[b0:b1, :seqlen] = sample[:, None] * ms + torch.arange(seqlen, device=input_ids.device)
-                content_cache.view(-1, ms, *content_cache.shape[1:])[b0:b1, :seqlen] = content.transpose(1, 2)
-            key_weight = None if intervention is None else intervention.prefill_key_weight(self, input_ids, content, ip)
-            if self.fused_senses:
-                if key_weight is None:
-                    return bp_hip.sense_mix(qk, content.transpose(1, 2), attn.scale())
-                return bp_hip.sense_mix(qk, content.transpose(1, 2), attn.scale(), key_weight=key_weight)
-            if key_weight is not None:
-                content = content * key_weight.unsqueeze(3).to(content.dtype)
-            return _combine_senses(attn(hidden), content)
-        lengths = cache_lengths(ip, batch, input_ids.device)
+            content = self.content_model(input_ids)                      # (B, k, S, d) view of (B, S, k*d)
+            if intervention is not None:
+                content = intervention.edit_rows(input_ids, content, ip)
+            c.rows[c.b0:c.b1, :seqlen] = c.sample[:, None] * ip.max_sequence_len + torch.arange(seqlen, device=qk.device)
+            c.content.view(-1, ip.max_sequence_len, *c.content.shape[1:])[c.b0:c.b1, :seqlen] = content.transpose(1, 2)
+        key_weight = None if intervention is None else intervention.prefill_key_weight(self, input_ids, content, ip)
+        attn = self.contextualization_attn
+        if self.fused_senses:
+            return bp_hip.sense_mix(qk, content.transpose(1, 2), attn.scale(), key_weight=key_weight)
+        if key_weight is not None:
+            content = content * key_weight.unsqueeze(3).to(content.dtype)
+        return _combine_senses(attn(hidden), content)
+
+    def _cached_step(self, input_ids, hidden, qk, ip, intervention):
+        """One new token per sample: appends its key and row to the caches, returns its mix (B, 1, d)."""
+        table = None if 'backpack_content' in ip.key_value_memory_dict else self.sense_table()
+        if table is None and 'backpack_content' not in ip.key_value_memory_dict:
+            raise RuntimeError('Backpack decode: the cache was filled in table form but the sense table is gone '
+                               '(weights changed, or .train() was called, since the prefill)')
+        c = self._decode_caches(ip, qk, table is None, hidden)
+        lengths = cache_lengths(ip, input_ids.shape[0], input_ids.device)
         if table is not None:
             new_row = input_ids[:, 0].to(torch.int32)
         else:
-            new_row = (sample * ms + lengths).to(torch.int32)
-            if intervention is None:
-                content_cache.index_copy_(0, new_row.long(), self.content_model(input_ids)[:, :, 0])
-            else:
-                content_cache.index_copy_(0, new_row.long(),
-                                          intervention.edit_rows(input_ids, self.content_model(input_ids))[:, :, 0])
-            table = content_cache
+            new_row = (c.sample * ip.max_sequence_len + lengths).to(torch.int32)
+            at, content = new_row.long(), self.content_model(input_ids)
+            if intervention is not None:
+                content = intervention.edit_rows(input_ids, content, ip)
+            c.content.index_copy_(0, at, content[:, :, 0])
+            table = c.content
         q, k_new = qk[:, 0, 0], qk[:, 0, 1]                             # (B, k, d_k)
         key_weight = None if intervention is None else \
-            intervention.step_key_weight(self, input_ids, table, rows[b0:b1], new_row, lengths, ip)
-        if self.fused_senses:
-            if not bp_hip.sense_decode_supported(q, key_cache, table):
-                raise RuntimeError(f'Backpack decode: bp_sense_decode does not take k = {q.shape[1]} senses of width '
-                                   f'{q.shape[2]} with {table.shape[2]} output columns (include/bp_hip.h)')
-            if key_weight is None:
-                return bp_hip.sense_decode(q, k_new, key_cache[b0:b1], table, rows[b0:b1], new_row, lengths,
-                                           attn.scale()).unsqueeze(1)
-            return bp_hip.sense_decode(q, k_new, key_cache[b0:b1], table, rows[b0:b1], new_row, lengths, attn.scale(),
+            intervention.step_key_weight(self, input_ids, table, c.rows[c.b0:c.b1], new_row, lengths, ip)
+        scale = self.contextualization_attn.scale()
+        if not self.fused_senses:
+            return _eager_sense_decode(q, k_new, c.keys, table, c.rows, new_row, c.b0, lengths, scale,
                                        key_weight=key_weight).unsqueeze(1)
-        if key_weight is None:
-            return _eager_sense_decode(q, k_new, key_cache, table, rows, new_row, b0, lengths, attn.scale()).unsqueeze(1)
-        return _eager_sense_decode(q, k_new, key_cache, table, rows, new_row, b0, lengths, attn.scale(),
+        if not bp_hip.sense_decode_supported(q, c.keys, table):
+            raise RuntimeError(f'Backpack decode: bp_sense_decode does not take k = {q.shape[1]} senses of width '
+                               f'{q.shape[2]} with {table.shape[2]} output columns (include/bp_hip.h)')
+        return bp_hip.sense_decode(q, k_new, c.keys[c.b0:c.b1], table, c.rows[c.b0:c.b1], new_row, lengths, scale,
                                    key_weight=key_weight).unsqueeze(1)
 
     def forward(self, input_ids, position_ids=None, inference_params=None):
         if inference_params is not None:
             return self._forward_cached(input_ids, position_ids, inference_params)
-        contextl_hidden_states = self.gpt2_model(input_ids, position_ids=position_ids,
-                                                 inference_params=inference_params)
+        contextl_hidden_states = self.gpt2_model(input_ids, position_ids=position_ids, inference_params=None)
         if self._token_table_allowed(input_ids):
             if self.sense_table_mode == 'cached':
                 rows = self.sense_table(verify=self._verify_applies(input_ids))
@@ -589,6 +604,26 @@ class BackpackModel(GPTPreTrainedModel):
                                              self.contextualization_attn.scale())
         contextualization = self.contextualization_attn(contextl_hidden_states)   # (B,k,S,S)
         return _combine_senses(contextualization, content)                         # (B,S,d)
+
+
+# What one cached call works on: the three caches (`content` None = table form), its batch rows b0:b1 and their indices
+_DecodeCaches = namedtuple('_DecodeCaches', ['keys', 'rows', 'content', 'b0', 'b1', 'sample'])
+
+
+class SenseIntervention:
+    """The one hook of the cached path (src/models/intervened_models.py): what a wrapper may change in what enters the
+    contraction.  State kept between calls lives in `key_value_memory_dict`; the defaults edit and weight nothing."""
+
+    cache_form_only = False     # True: never the table form (the rows are edited per position)
+
+    def edit_rows(self, input_ids, content, inference_params):
+        return content          # cache form: the (B,k,S,d) rows of the new positions, before they are appended
+
+    def prefill_key_weight(self, model, input_ids, content, inference_params):
+        return None             # or the (B,k,S) fp32 weights of the prompt's positions: `key_weight` of bp_sense_mix
+
+    def step_key_weight(self, model, input_ids, table, rows, new_row, lengths, inference_params):
+        return None             # or the (B,k,max_seqlen) fp32 weights of positions 0 .. L: `key_weight` of bp_sense_decode
 
 
 def _eager_sense_decode(q, k_new, key_cache, table, rows, new_row, b0, lengths, scale, key_weight=None):

@@ -16,10 +16,10 @@ when the wrapped network runs its HIP path (`config.use_flash_attn`), it stays O
 With `use_flash_attn=False` the reference's eager op sequence runs (any device / dtype).
 
 KV-cached decoding (`forward(..., inference_params=ip)`, `generate` / `sample` with `kv_cache=True`): the wrappers are the
-`intervention` hook of `BackpackModel._forward_cached`.  Weighted: the per-(sense, position) weights of the cached
-positions live in `ip.key_value_memory_dict` and enter the step as `key_weight` of bp_sense_decode_weighted; the annealed
-weights change at every step, but the similarity sums behind them are running sums, advanced by one gathered GEMV over
-the cached rows (bp_sense_rows_dot).  ReplacedWord: cache form, the listed tokens' rows are replaced as they are appended.
+`SenseIntervention` of `BackpackModel`'s cached path.  Weighted: the per-(sense, position) weights of the cached positions
+live in `ip.key_value_memory_dict` and enter the step as `key_weight` of bp_sense_decode_weighted; the annealed weights
+change at every step, but the similarity sums behind them are running sums, advanced by one gathered GEMV over the cached
+rows (bp_sense_rows_dot).  ReplacedWord: cache form, the listed tokens' rows are replaced as they are appended.
 State, all (max_batch_size, ..., max_sequence_len), indexed on the device through the cached lengths:
   'intervened_ids'     int64 token ids of the cached positions
   'intervened_weight'  fp32 (., k, .) the key weights the contraction reads
@@ -33,6 +33,7 @@ import torch
 from torch import nn
 
 import bp_hip
+from src.models.backpack import SenseIntervention
 from src.utils.generation import GenerationMixin
 
 CausalLMOutput = namedtuple('CausalLMOutput', ['logits'])
@@ -74,37 +75,20 @@ def _anneal_weights(sims, picked, annealing_scale, upweight_nearby, first_positi
     return picked * scores + (1 - scores)
 
 
-class _Intervened(nn.Module, GenerationMixin):
-    """Shared plumbing: the three stages of the wrapped network, and the contraction."""
+class _Intervened(nn.Module, GenerationMixin, SenseIntervention):
+    """Shared plumbing: the three stages of the wrapped network, the contraction, and where a call goes -- with
+    `inference_params` to the cached path of the wrapped BackpackModel (its hook: this wrapper), else to `_mixed`."""
 
-    # ---- the `intervention` hook of BackpackModel._forward_cached: by default nothing is edited, nothing weighted ----
-    cache_form_only = False
-
-    def edit_rows(self, input_ids, content):
-        return content
-
-    def prefill_key_weight(self, model, input_ids, content, ip):
-        return None
-
-    def step_key_weight(self, model, input_ids, table, rows, new_row, lengths, ip):
-        return None
-
-    def _forward_cached(self, input_ids, position_ids, inference_params):
-        mixed = self.backpack_network.transformer._forward_cached(input_ids, position_ids, inference_params,
-                                                                  intervention=self)
+    def forward(self, input_ids, position_ids=None, inference_params=None):
+        cached = self.backpack_network.transformer._forward_cached
+        mixed = self._mixed(input_ids, position_ids) if inference_params is None else \
+            cached(input_ids, position_ids, inference_params, intervention=self)
         return CausalLMOutput(logits=self.backpack_network.lm_head(mixed))
 
-    @staticmethod
-    def _state(ip, name, shape, dtype, device):
-        caches = ip.key_value_memory_dict
-        if name not in caches:
-            caches[name] = torch.zeros(shape, dtype=dtype, device=device)
-        return caches[name]
-
-    def _stages(self, input_ids, position_ids, inference_params):
+    def _stages(self, input_ids, position_ids):
         t = self.backpack_network.transformer
-        hidden = t.gpt2_model(input_ids, position_ids=position_ids, inference_params=inference_params)
-        content = t.content_model(input_ids, position_ids, inference_params)      # (B,k,S,d) view
+        hidden = t.gpt2_model(input_ids, position_ids=position_ids, inference_params=None)
+        content = t.content_model(input_ids, position_ids, None)                  # (B,k,S,d) view
         return t, hidden, content
 
     @staticmethod
@@ -143,36 +127,36 @@ class WeightedBackpackLMHeadModel(_Intervened):
         self.anneal = anneal
         self.upweight_nearby = upweight_nearby
 
-    def forward(self, input_ids, position_ids=None, inference_params=None):
-        if inference_params is not None:
-            return self._forward_cached(input_ids, position_ids, inference_params)
-        t, hidden, content = self._stages(input_ids, position_ids, inference_params)
-        mixed = self._mix(t, hidden, content, self._weights(input_ids, content))
-        return CausalLMOutput(logits=self.backpack_network.lm_head(mixed))
+    def _mixed(self, input_ids, position_ids):
+        t, hidden, content = self._stages(input_ids, position_ids)
+        return self._mix(t, hidden, content, self._weights(input_ids, content))
 
     # ---- KV-cached decoding ----
-    def _cached_state(self, ip, k, device):
-        mb, ms = ip.max_batch_size, ip.max_sequence_len
-        ids = self._state(ip, 'intervened_ids', (mb, ms), torch.long, device)
-        weight = self._state(ip, 'intervened_weight', (mb, k, ms), torch.float32, device)
-        return ids, weight
+    def _cached_state(self, ip, k=None, device=None):
+        """The wrapper's (ids, weight, sims, dots, content_weights) of `key_value_memory_dict`; given `k`: made by the prefill."""
+        caches = ip.key_value_memory_dict
+        if k is not None:
+            mb, ms = ip.max_batch_size, ip.max_sequence_len
+            state = {'intervened_ids': ((mb, ms), torch.long), 'intervened_weight': ((mb, k, ms), torch.float32)}
+            if self.anneal:
+                state.update(intervened_sims=((mb, k, ms), torch.float32), intervened_dots=((mb, k, ms), torch.float32))
+            for name, (shape, dtype) in state.items():
+                if name not in caches:
+                    caches[name] = torch.zeros(shape, dtype=dtype, device=device)
+            # one device copy of the (vocab, k) weights per prefill: the steps index it without touching the host
+            caches['intervened_content_weights'] = self.content_weights.to(device=device, dtype=torch.float32)
+        return tuple(caches.get('intervened_' + name) for name in ('ids', 'weight', 'sims', 'dots', 'content_weights'))
 
     def prefill_key_weight(self, model, input_ids, content, ip):
         batch, seqlen = input_ids.shape
-        k = content.shape[1]
         b0 = ip.batch_size_offset
-        ids, weight = self._cached_state(ip, k, input_ids.device)
-        # one device copy of the (vocab, k) weights per prefill: the steps index it without touching the host
-        cw = ip.key_value_memory_dict['intervened_content_weights'] = \
-            self.content_weights.to(device=input_ids.device, dtype=torch.float32)
+        ids, weight, sims_state, _, cw = self._cached_state(ip, content.shape[1], input_ids.device)
         ids[b0:b0 + batch, :seqlen] = input_ids
         picked = cw[input_ids].transpose(1, 2)                                     # (B,k,S)
         if self.anneal:
             emb = self.backpack_network.lm_head.weight[input_ids]                  # (B,S,d)
             sims = torch.relu(content @ emb.transpose(1, 2).unsqueeze(1)).sum(dim=3, dtype=torch.float32)
-            mb, ms = ip.max_batch_size, ip.max_sequence_len
-            self._state(ip, 'intervened_sims', (mb, k, ms), torch.float32, input_ids.device)[b0:b0 + batch, :, :seqlen] = sims
-            self._state(ip, 'intervened_dots', (mb, k, ms), torch.float32, input_ids.device)
+            sims_state[b0:b0 + batch, :, :seqlen] = sims
             picked = _anneal_weights(sims, picked, self.annealing_scale, self.upweight_nearby)
         weight[b0:b0 + batch, :, :seqlen] = picked
         return picked.contiguous()
@@ -180,8 +164,7 @@ class WeightedBackpackLMHeadModel(_Intervened):
     def step_key_weight(self, model, input_ids, table, rows, new_row, lengths, ip):
         batch = input_ids.shape[0]
         b0, ms = ip.batch_size_offset, ip.max_sequence_len
-        caches = ip.key_value_memory_dict
-        ids, weight, cw = caches['intervened_ids'], caches['intervened_weight'], caches['intervened_content_weights']
+        ids, weight, sims, dots, cw = self._cached_state(ip)
         sample = torch.arange(b0, b0 + batch, device=input_ids.device)
         at = lengths.long()
         ids[sample, at] = input_ids[:, 0]
@@ -192,7 +175,7 @@ class WeightedBackpackLMHeadModel(_Intervened):
         # pair (L, L) comes once, out of the rows-dot (its row is new_row).  Fixed shapes over max_sequence_len masked by
         # the device lengths: a captured step is valid for every later step.
         emb_w = self.backpack_network.lm_head.weight
-        sims, dots = caches['intervened_sims'][b0:b0 + batch], caches['intervened_dots'][b0:b0 + batch]
+        sims, dots = sims[b0:b0 + batch], dots[b0:b0 + batch]
         vec = emb_w[input_ids[:, 0]]                                               # (B,d) = E[x_L]
         pos = torch.arange(ms, device=input_ids.device)
         cached, new = pos[None, :] < at[:, None], pos[None, :] == at[:, None]      # (B,ms)
@@ -230,7 +213,7 @@ class NegativeWeightedBackpackLMHeadModel(WeightedBackpackLMHeadModel):
             raise NotImplementedError(
                 'NegativeWeightedBackpackLMHeadModel has no KV-cached decoding: its content is vocabulary-sized per '
                 '(position, sense) and does not fit a cache; generate without kv_cache')
-        t, hidden, content = self._stages(input_ids, position_ids, inference_params)
+        t, hidden, content = self._stages(input_ids, position_ids)
         weights = self._weights(input_ids, content)                              # (B,k,S)
         # everything in the content's storage order (B,S,k,.) -- the order the kernel reads -- so the
         # vocabulary-sized tensors are produced once and never transposed in memory
@@ -265,8 +248,10 @@ class ReplacedWordLMHeadModel(_Intervened):
     # neither cloned nor edited), sense_dict as a device lookup so that a captured step asks the host nothing ----
     cache_form_only = True
 
-    def edit_rows(self, input_ids, content):
-        slot, rows = self._lookup
+    def edit_rows(self, input_ids, content, ip):
+        if ip.sequence_len_offset == 0:
+            self._read_sense_dict(ip, input_ids.device, self.backpack_network.lm_head.weight.dtype)
+        slot, rows = ip.key_value_memory_dict['intervened_replace']
         s = slot[input_ids]                                                       # (B,S), -1 = keep the token's own rows
         picked = rows[s.clamp(min=0)]                                             # (B,S,k,d)
         return torch.where((s >= 0)[:, :, None, None], picked, content.transpose(1, 2)).transpose(1, 2)
@@ -283,16 +268,9 @@ class ReplacedWordLMHeadModel(_Intervened):
         rows = rows[1:] or rows
         ip.key_value_memory_dict['intervened_replace'] = (slot.to(device), torch.stack(rows).to(device, dtype))
 
-    def forward(self, input_ids, position_ids=None, inference_params=None):
-        if inference_params is not None:
-            ip = inference_params
-            if ip.sequence_len_offset == 0:
-                self._read_sense_dict(ip, input_ids.device, self.backpack_network.lm_head.weight.dtype)
-            self._lookup = ip.key_value_memory_dict['intervened_replace']
-            return self._forward_cached(input_ids, position_ids, ip)
-        t, hidden, content = self._stages(input_ids, position_ids, inference_params)
+    def _mixed(self, input_ids, position_ids):
+        t, hidden, content = self._stages(input_ids, position_ids)
         content = self.replace_content(input_ids, content)
         if t.fused_senses and content.transpose(1, 2).stride(-1) != 1:
             content = content.contiguous()
-        mixed = self._mix(t, hidden, content)
-        return CausalLMOutput(logits=self.backpack_network.lm_head(mixed))
+        return self._mix(t, hidden, content)

@@ -128,41 +128,40 @@ def _decode_cached(input_ids, model, max_length, pick, cg=False):
     return DecoderOnlyOutput(sequences=torch.cat(tokens, dim=1), scores=tuple(scores))
 
 
+def _run_loop(input_ids, model, max_length, pick, cg, kv_cache):
+    if kv_cache:
+        return _decode_cached(input_ids, model, max_length, pick, cg=cg)
+    if cg and input_ids.is_cuda:
+        return _decode_graphed(input_ids, model, max_length, pick)
+    return _decode(input_ids, model, max_length, pick)
+
+
 def greedy_decode(input_ids, model, max_length, cg=False, kv_cache=False):
     """input_ids (batch, seq_len) -> sequences (batch, max_length - 1): argmax continuation.
     cg=True: one captured full-width forward replayed per token (CUDA tensors only), see _decode_graphed.
     kv_cache=True: prefill once, then one cached step per token (with cg=True: one captured step), see _decode_cached."""
-    pick = lambda logits: torch.argmax(logits, dim=-1)   # noqa: E731
-    if kv_cache:
-        return _decode_cached(input_ids, model, max_length, pick, cg=cg)
-    if cg and input_ids.is_cuda:
-        return _decode_graphed(input_ids, model, max_length, pick)
-    return _decode(input_ids, model, max_length, pick)
+    return _run_loop(input_ids, model, max_length, lambda logits: torch.argmax(logits, dim=-1), cg, kv_cache)
 
 
 def sample(input_ids, model, max_length, cg=False, kv_cache=False):
-    """Ancestral sampling from softmax(logits) (reference :23-48)."""
+    """Ancestral sampling from softmax(logits) (reference :23-48); cg / kv_cache as in greedy_decode."""
     def pick(logits):
         return torch.distributions.Categorical(logits=torch.log_softmax(logits.float(), dim=-1)).sample()
-    if kv_cache:
-        return _decode_cached(input_ids, model, max_length, pick, cg=cg)
-    if cg and input_ids.is_cuda:
-        return _decode_graphed(input_ids, model, max_length, pick)
-    return _decode(input_ids, model, max_length, pick)
+    return _run_loop(input_ids, model, max_length, pick, cg, kv_cache)
 
 
 class GenerationMixin:
 
-    def generate(self, input_ids, max_length, return_dict_in_generate=False, output_scores=False, cg=False,
-                 kv_cache=False):
-        output = greedy_decode(input_ids, self, max_length, cg=cg, kv_cache=kv_cache)
+    def _generate(self, decode, input_ids, max_length, return_dict_in_generate, output_scores, cg, kv_cache):
+        output = decode(input_ids, self, max_length, cg=cg, kv_cache=kv_cache)
         if not output_scores:
             output.scores = None
         return output if return_dict_in_generate else output.sequences
 
+    def generate(self, input_ids, max_length, return_dict_in_generate=False, output_scores=False, cg=False,
+                 kv_cache=False):
+        return self._generate(greedy_decode, input_ids, max_length, return_dict_in_generate, output_scores, cg, kv_cache)
+
     def sample(self, input_ids, max_length, return_dict_in_generate=False, output_scores=False, cg=False,
                kv_cache=False):
-        output = sample(input_ids, self, max_length, cg=cg, kv_cache=kv_cache)
-        if not output_scores:
-            output.scores = None
-        return output if return_dict_in_generate else output.sequences
+        return self._generate(sample, input_ids, max_length, return_dict_in_generate, output_scores, cg, kv_cache)

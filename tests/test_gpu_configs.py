@@ -160,7 +160,7 @@ def test_mini_few_sense_ablations_whole_model_seq1024(name):
         warnings.simplefilter('always')
         for mode in ('off', 'cached'):
             _assert_model_parity(run, _hidden(run, run['ids'], mode), f'{name} S=1024 [{mode}]')
-    assert t._sense_table is not None and not any('gathered by torch' in str(w.message) for w in caught)
+    assert t.sense_table_rows() is not None and not any('gathered by torch' in str(w.message) for w in caught)
 
 
 def test_few_sense_model_trains_on_the_hip_trunk():
@@ -253,7 +253,7 @@ def test_sense_table_follows_the_weights_and_survives_graph_capture():
     # periodic evaluation during training: the graph pinned the table's storage, so train() / eval() keep the address the
     # captured kernels read; the replay refreshes it in place (advisor, round 5: the table used to be freed here)
     model.train()
-    assert t._sense_table is not None and t._sense_table[0] is None and t._sense_table[1].data_ptr() == ptr
+    assert t._sense_table.key is None and t._sense_table.rows is not None and t._sense_table.rows.data_ptr() == ptr
     with pytest.raises(RuntimeError):
         fwd(ids)                                                                   # captured in eval mode
     with torch.no_grad():
@@ -284,11 +284,11 @@ def test_sense_table_follows_the_weights_and_survives_graph_capture():
     del fwd
     t.pin_sense_table(False)
     model.train()
-    assert t._sense_table is None
+    assert t._sense_table.rows is None and t._sense_table.key is None
     model.eval()
     with torch.inference_mode():                                                   # generation runs like this
         out = model(ids).logits
-    assert torch.isfinite(out.float()).all() and t._sense_table is not None
+    assert torch.isfinite(out.float()).all() and t.sense_table_rows() is not None
 
 
 def test_small_config5_whole_model_seq4096_fp16():

@@ -4,84 +4,22 @@ forward."""
 import pytest
 import torch
 
+from decode_support import (DEV, FLASH_LENGTHS, MODELS, SENSE_SHAPES, VOCAB, _cached_logits, _flash_decode_matches_fp32, _fp32_twin,
+                            _model, _sense_decode_matches_fp32)
+
 pytestmark = pytest.mark.gpu
-DEV = torch.device('cuda', 0)
-
-
-def _bp():
-    import bp_hip
-    bp_hip.lib()
-    return bp_hip
-
-
-def _within_2x(got, ref, eager, what):
-    """max|kernel - fp32 oracle| <= 2 max|same-dtype eager - fp32 oracle| + 1e-5 (tests/test_gpu_kernels.py)."""
-    ref = ref.float().cpu()
-    err = (got.float().cpu() - ref).abs().max().item()
-    base = (eager.float().cpu() - ref).abs().max().item()
-    print(f'{what}: kernel {err:.3e} eager-same-dtype {base:.3e}')
-    assert err <= 2 * base + 1e-5, (what, err, base)
-
-
-def _attend(q, keys, values, scale, dtype):
-    """softmax(scale q . k_j) v summed over j, in `dtype` (the eager twin's op order: scale K, softmax in v's dtype)."""
-    q, keys, values = q.to(dtype), keys.to(dtype), values.to(dtype)
-    scores = torch.einsum('hd,shd->hs', q, keys * scale)
-    p = torch.softmax(scores, dim=-1, dtype=dtype)
-    return torch.einsum('hs,shd->hd', p, values)
 
 
 # ---- bp_flash_decode --------------------------------------------------------------------------------------------------
-
-FLASH_LENGTHS = [[0, 1, 2, 63, 64, 65, 1000, 4096], [1024, 5], [1]]
-
 
 @pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize('d', [64, 80, 128])
 @pytest.mark.parametrize('lengths', FLASH_LENGTHS, ids=['mixed8', 'two', 'one'])
 def test_flash_decode_matches_fp32(d, dtype, lengths):
-    bp = _bp()
-    g = torch.Generator(device=DEV).manual_seed(d + len(lengths))
-    b, h, max_s, off = len(lengths), 4, 4104, 2
-    full = torch.randn(b + off + 1, max_s, 2, h, d, device=DEV, generator=g).to(dtype)
-    cache = full[off:off + b]                    # a cache at a non-zero batch_size_offset
-    q, k_new, v_new = (torch.randn(b, h, d, device=DEV, generator=g).to(dtype) * s for s in (2.0, 1.0, 1.0))
-    seqlens = torch.tensor(lengths, dtype=torch.int32, device=DEV)
-    before = full.clone()
-    scale = d ** -0.5
-    out, lse = bp.flash_decode(q, k_new, v_new, cache, seqlens, scale, return_lse=True)
-    torch.cuda.synchronize()
-    want_cache = before.clone()
-    for i, L in enumerate(lengths):
-        want_cache[off + i, L, 0] = k_new[i]
-        want_cache[off + i, L, 1] = v_new[i]
-    assert torch.equal(full, want_cache), 'only row L of each sample may change, and it must hold k_new / v_new'
-    for i, L in enumerate(lengths):
-        keys = torch.cat([before[off + i, :L, 0], k_new[i:i + 1]])
-        values = torch.cat([before[off + i, :L, 1], v_new[i:i + 1]])
-        ref = _attend(q[i], keys, values, scale, torch.float32)
-        eager = _attend(q[i], keys, values, scale, dtype)
-        _within_2x(out[i], ref, eager, f'flash_decode d={d} {dtype} L={L}')
-        ref_lse = torch.logsumexp(torch.einsum('hd,shd->hs', q[i].float(), keys.float()) * scale, dim=-1)
-        torch.testing.assert_close(lse[i], ref_lse, rtol=1e-5, atol=1e-4)
-    again = bp.flash_decode(q, k_new, v_new, cache, seqlens, scale)
-    assert torch.equal(again, out), 'repeated calls must be bit-identical'
+    _flash_decode_matches_fp32(d, dtype, lengths)
 
 
 # ---- bp_sense_decode --------------------------------------------------------------------------------------------------
-
-# (d_k as project() returns it, true d_k, senses, d_out): Micro, Small, Mini k = 64 (10 padded to 16), k = 4, k = 1
-SENSE_SHAPES = [(24, 24, 16, 384), (48, 48, 16, 768), (16, 10, 64, 640), (160, 160, 4, 640), (640, 640, 1, 640)]
-SENSE_LENGTHS = [0, 1, 63, 64, 65, 1000, 4096, 7]
-
-
-def _sense_ref(q, keys, content, scale, dtype):
-    """o = sum_l sum_j softmax_j(scale q_l . k_l(j)) content[j, l] (ContextSelfAttn + _combine_senses on the last row)."""
-    q, keys, content = q.to(dtype), keys.to(dtype), content.to(dtype)
-    scores = torch.einsum('ld,sld->ls', q, keys * scale)
-    p = torch.softmax(scores, dim=-1, dtype=dtype)
-    return torch.einsum('ls,sld->d', p, content)
-
 
 @pytest.mark.parametrize('form', ['table', 'cache'])
 @pytest.mark.parametrize('shape', SENSE_SHAPES, ids=[f'dk{s[1]}_k{s[2]}' for s in SENSE_SHAPES])
@@ -95,88 +33,7 @@ def test_sense_decode_matches_fp32_in_fp16(shape, form):
     _sense_decode_matches_fp32(shape, form, torch.float16)
 
 
-def _sense_decode_matches_fp32(shape, form, dtype):
-    bp = _bp()
-    dkp, dk, k, dout = shape
-    g = torch.Generator(device=DEV).manual_seed(dkp * 7 + k)
-    lengths = SENSE_LENGTHS if dkp <= 48 else SENSE_LENGTHS[:4] + [4096]
-    b, max_s, vocab = len(lengths), 4100, 997
-    pad = torch.zeros(dkp, device=DEV)
-    pad[:dk] = 1.0                                # the padded columns of project() are exactly zero
-
-    def senses(*lead):
-        return (torch.randn(*lead, k, dkp, device=DEV, generator=g) * pad).to(dtype)
-    q, k_new = senses(b) * 2, senses(b)
-    k_cache = senses(b, max_s)
-    if form == 'table':
-        table = torch.randn(vocab, k, dout, device=DEV, generator=g).to(dtype)
-        rows = torch.randint(0, vocab, (b, max_s), device=DEV, generator=g, dtype=torch.int32)
-        new_row = torch.randint(0, vocab, (b,), device=DEV, generator=g, dtype=torch.int32)
-    else:
-        table = torch.randn(b * max_s, k, dout, device=DEV, generator=g).to(dtype)
-        rows = (torch.arange(b, device=DEV)[:, None] * max_s + torch.arange(max_s, device=DEV)).int()
-        new_row = (torch.arange(b, device=DEV) * max_s + torch.tensor(lengths, device=DEV)).int()
-    seqlens = torch.tensor(lengths, dtype=torch.int32, device=DEV)
-    kc_before, rows_before = k_cache.clone(), rows.clone()
-    scale = dk ** -0.5
-    out = bp.sense_decode(q, k_new, k_cache, table, rows, new_row, seqlens, scale)
-    torch.cuda.synchronize()
-    want_kc, want_rows = kc_before.clone(), rows_before.clone()
-    for i, L in enumerate(lengths):
-        want_kc[i, L] = k_new[i]
-        want_rows[i, L] = new_row[i]
-    assert torch.equal(k_cache, want_kc) and torch.equal(rows, want_rows)
-    for i, L in enumerate(lengths):
-        keys = torch.cat([kc_before[i, :L], k_new[i:i + 1]])
-        idx = torch.cat([rows_before[i, :L], new_row[i:i + 1]]).long()
-        content = table[idx]
-        ref = _sense_ref(q[i], keys, content, scale, torch.float32)
-        eager = _sense_ref(q[i], keys, content, scale, dtype)
-        _within_2x(out[i], ref, eager, f'sense_decode {shape} {form} {dtype} L={L}')
-    again = bp.sense_decode(q, k_new, k_cache, table, rows, new_row, seqlens, scale)
-    assert torch.equal(again, out), 'repeated calls must be bit-identical'
-
-
 # ---- model level ------------------------------------------------------------------------------------------------------
-
-MODELS = {   # two layers of each trunk, the sense shapes of the named configurations
-    'micro': dict(n_embd=384, n_head=6, num_content_vectors=16),
-    'small': dict(n_embd=768, n_head=12, num_content_vectors=16),
-    'mini_k64': dict(n_embd=640, n_head=8, num_content_vectors=64),
-    'mini_k4': dict(n_embd=640, n_head=8, num_content_vectors=4),
-    'mini_k1': dict(n_embd=640, n_head=8, num_content_vectors=1),
-}
-VOCAB = 4096
-
-
-def _model(name, seed=0):
-    from src.models.backpack import BackpackConfig, BackpackLMHeadModel
-    import warnings
-    torch.manual_seed(seed)
-    cfg = BackpackConfig(n_layer=2, vocab_size=VOCAB, n_positions=256, scale_attn_by_inverse_layer_idx=True,
-                         use_flash_attn=True, fused_bias_fc=True, fused_dense_gelu_dense=True, fused_dropout_add_ln=True,
-                         pad_vocab_size_multiple=8, **MODELS[name])
-    with warnings.catch_warnings():
-        warnings.simplefilter('ignore')
-        model = BackpackLMHeadModel(cfg, device=DEV, dtype=torch.bfloat16).eval()
-    # sharpen the sense softmax as Small's x 8 does at d_k = 48 (score spread ~ mult^2 sqrt(d_k)): a fixed x 8 would make the
-    # one-sense d_k = 640 model 3.6 x sharper, where near-ties turn one-ulp trunk differences into large weight swings
-    dk = cfg.n_embd // cfg.num_content_vectors
-    with torch.no_grad():
-        model.transformer.contextualization_attn.Wqkv.weight.mul_(8.0 * (48 / dk) ** 0.25)
-    assert model.transformer.fused_senses
-    return model
-
-
-def _fp32_twin(model):
-    """The eager op sequence (use_flash_attn=False) in fp32 with the same weights: the oracle of the model-level checks."""
-    from src.models.backpack import BackpackConfig, BackpackLMHeadModel
-    kw = {k: v for k, v in model.config.to_dict().items() if k in ('n_embd', 'n_head', 'n_layer', 'num_content_vectors',
-                                                                   'vocab_size', 'n_positions')}
-    twin = BackpackLMHeadModel(BackpackConfig(scale_attn_by_inverse_layer_idx=True, use_flash_attn=False, **kw))
-    twin.load_state_dict({k: v.float() for k, v in model.state_dict().items()})
-    return twin.to(DEV).eval()
-
 
 @pytest.mark.parametrize('mode', ['cached', 'off'])
 @pytest.mark.parametrize('name', list(MODELS))
@@ -212,18 +69,6 @@ def test_cached_decode_matches_the_full_forward(name, mode):
             worst = max(worst, err / bound)
             assert err <= bound, (name, mode, t, err, base, ref.abs().max().item())
     print(f'{name} [{mode}]: worst step error {worst:.2f} of the bound')
-
-
-def _cached_logits(model, seq, prompt):
-    """Logits of the last position of `seq` (1, S) by prefill on `prompt` tokens + cached steps."""
-    from src.utils.generation import InferenceParams
-    ip = InferenceParams(max_sequence_len=seq.shape[1], max_batch_size=1)
-    with torch.inference_mode():
-        logits = model(seq[:, :prompt], inference_params=ip).logits[:, -1]
-        for t in range(prompt, seq.shape[1]):
-            ip.sequence_len_offset = t
-            logits = model(seq[:, t:t + 1], inference_params=ip).logits[:, -1]
-    return logits[0].float()
 
 
 def test_graph_replay_is_bit_identical_to_eager_steps():

@@ -48,9 +48,9 @@ import pytest
 import torch
 
 import decode_needles as N
-from test_gpu_decode import (FLASH_LENGTHS, _attend, _bp, _sense_decode_matches_fp32, _sense_ref, _within_2x,
-                             test_flash_decode_matches_fp32 as _flash_decode_matches_fp32)
-from test_gpu_fuzz import _close
+from decode_support import (FLASH_LENGTHS, _ar, _attend, _bp, _flash_decode_matches_fp32, _same_bits,
+                            _sense_decode_matches_fp32, _sense_ref, _within_2x)
+from decode_support import _close_drawn as _close
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device('cuda', 0)
@@ -59,15 +59,6 @@ DTYPE_IDS = ['bf16', 'fp16']
 SEEDS = range(int(os.environ.get('BP_FUZZ_SEEDS', '24')))
 NAN = float('nan')
 INT32_MAX, INT32_MIN = 2 ** 31 - 1, -(2 ** 31)
-
-
-def _bits(t):
-    """A 16-bit or int32 tensor as integers: torch.equal on these compares NaN payloads too."""
-    return t.view(torch.int16) if t.element_size() == 2 else t.view(torch.int32)
-
-
-def _same_bits(a, b):
-    return a.shape == b.shape and torch.equal(_bits(a), _bits(b))
 
 
 def _flash_nsplit(bp, b, h, d, max_s):
@@ -103,10 +94,6 @@ def _sense_abi(bp, q, k_new, k_cache, table, rows, new_row, seqlens, scale, out,
              k_cache.stride(0), k_cache.stride(1), k_cache.stride(2), table.stride(0), table.stride(1), rows.stride(0),
              out.stride(0), float(scale), bp._dtype_code(q))
     return out
-
-
-def _ar(n):
-    return torch.arange(n, device=DEV)
 
 
 # ---- A. needles ---------------------------------------------------------------------------------------------------------

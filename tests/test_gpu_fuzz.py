@@ -17,6 +17,7 @@ import random
 import pytest
 import torch
 
+from decode_support import _close_drawn as _close
 from oracle import ref_cpu as R
 
 pytestmark = pytest.mark.gpu
@@ -27,19 +28,6 @@ SEEDS = range(int(os.environ.get('BP_FUZZ_SEEDS', '24')))      # (a longer hunt:
 def _bp():
     import bp_hip
     return bp_hip
-
-
-def _close(got, ref32, eager, name, factor=2.0, floor=2.0, floor_range=0.0):
-    dtype = got.dtype
-    got, ref32, eager = got.float().cpu(), ref32.float().cpu(), eager.float().cpu()
-    assert torch.isfinite(got).all(), name
-    err = (got - ref32).abs().max().item() if got.numel() else 0.0
-    base = (eager - ref32).abs().max().item() if got.numel() else 0.0
-    # floor: two units of 16-bit rounding at the result's range (tiny drawn cases -- two keys, one head -- leave the eager
-    # yardstick at zero or one ulp, where "twice the eager error" says nothing)
-    eps = 2.0 ** -8 if dtype == torch.bfloat16 else 2.0 ** -11
-    ulp = floor * eps * max(ref32.abs().max().item() if got.numel() else 0.0, floor_range)
-    assert err <= factor * base + ulp + 1e-5, f'{name}: {err:.3e} > {factor} x {base:.3e} + {ulp:.1e}'
 
 
 def _grads(q, k, v, dout, causal, scale, upcast):

@@ -6,14 +6,15 @@ Annealed cases: the scale is 6 / (a middle quantile of the fp32 twin's similarit
 each annealed test asserts on the fp32 twin that at least half of the scores it compares (before `upweight_nearby`) lie
 in [0.1, 0.9]: with the default scale every score of a fresh model is sigmoid(6) and a wrong running sum would not show.
 content_weights are drawn from [0, 3) so that a dropped weight moves the logits."""
+import inspect
 from unittest import mock
 
 import pytest
 import torch
 
 import decode_needles as N
-from test_gpu_decode import (MODELS, SENSE_LENGTHS, SENSE_SHAPES, VOCAB, _bp, _cached_logits, _fp32_twin, _model,
-                             _sense_ref, _within_2x)
+from decode_support import (SENSE_LENGTHS, SENSE_SHAPES, VOCAB, _anneal_scale, _ar, _assert_scores_in_band, _bp,
+                            _cached_logits, _fp32_twin, _model, _same_bits, _within_2x)
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device('cuda', 0)
@@ -21,18 +22,6 @@ DTYPES = [torch.bfloat16, torch.float16]
 DTYPE_IDS = ['bf16', 'fp16']
 NAN = float('nan')
 SHAPE_IDS = [f'dk{s[1]}_k{s[2]}' for s in SENSE_SHAPES]
-
-
-def _bits(t):
-    return t.view(torch.int16) if t.element_size() == 2 else t.view(torch.int32)
-
-
-def _same_bits(a, b):
-    return a.shape == b.shape and torch.equal(_bits(a), _bits(b))
-
-
-def _ar(n):
-    return torch.arange(n, device=DEV)
 
 
 def _operands(shape, form, dtype, g):
@@ -220,30 +209,6 @@ def test_sense_rows_dot_matches_fp64(shape, form, dtype):
 WRAPPERS = ['weighted', 'weighted-anneal', 'replaced']
 
 
-def _sims(twin, ids):
-    with torch.no_grad():
-        content = twin.transformer.content_model(ids)
-        emb = twin.lm_head.weight[ids]
-        return torch.relu(content @ emb.transpose(1, 2).unsqueeze(1)).sum(dim=3)
-
-
-def _in_band(scale, sims):
-    scores = torch.sigmoid(-scale * sims + 6)
-    return ((scores >= 0.1) & (scores <= 0.9)).float().mean().item()
-
-
-def _anneal_scale(twin, ids, lengths):
-    sims = torch.cat([_sims(twin, ids[:, :n]).flatten() for n in lengths])
-    return max((6.0 / sims.quantile(q).item() for q in (0.3, 0.4, 0.5, 0.6, 0.7)), key=lambda sc: _in_band(sc, sims))
-
-
-def _assert_scores_in_band(twin, ids, scale, lengths):
-    sims = torch.cat([_sims(twin, ids[:, :n]).flatten() for n in lengths])
-    inside = _in_band(scale, sims)
-    print(f'annealing scale {scale:.2f}: {100 * inside:.0f} % of {sims.numel()} scores in [0.1, 0.9]')
-    assert inside >= 0.5, inside
-
-
 def _wrappers(kind, model, twin, ids, lengths, words=()):
     """The HIP wrapper and its fp32 twin, same intervention."""
     from src.models.intervened_models import ReplacedWordLMHeadModel, WeightedBackpackLMHeadModel
@@ -316,7 +281,7 @@ def test_plain_model_step_launches_what_it_launched():
         model(ids[:, 16:], inference_params=ip)
     assert spy.call_count == 1 and not boom.called
     args, kwargs = spy.call_args
-    assert len(args) == 8 and kwargs == {}
+    assert inspect.signature(bp.sense_decode).bind(*args, **kwargs).arguments.get('key_weight') is None
 
 
 def test_annealed_graph_replay_is_bit_identical_to_eager_steps():

@@ -450,7 +450,7 @@ def test_whole_vocabulary_sense_table_is_the_content_network_row_by_row_and_foll
     with torch.no_grad():
         want = t.content_model(ids)                                    # (B,k,S,d)
         logits = model(ids).logits
-    assert t._sense_table is None                                      # the CPU forward never built one
+    assert t._sense_table.rows is None                                 # the CPU forward never built one
     table = t.sense_table()
     vocab = t.embeddings.word_embeddings.weight.shape[0]
     assert table.shape == (vocab, 4, 64) and not table.requires_grad and t.sense_table() is table
@@ -465,9 +465,9 @@ def test_whole_vocabulary_sense_table_is_the_content_network_row_by_row_and_foll
     again = t.sense_table()
     assert not torch.allclose(again[5], before[5] + 1.0, atol=1e-3) and torch.allclose(again[6], before[6] + 1.0, atol=1e-5)
     model.load_state_dict({k: v.clone() for k, v in model.state_dict().items()})   # copy_ in place: versions move again
-    assert t._sense_table[0] != t._sense_table_key()
+    assert t._sense_table.key != t._sense_table.version_key()
     model.train()
-    assert t._sense_table is None
+    assert t._sense_table.rows is None and t._sense_table.key is None
     model.eval()
     with torch.inference_mode():
         inside = t.sense_table()                                       # built as a normal tensor even in inference mode
@@ -492,12 +492,13 @@ def test_whole_vocabulary_sense_table_is_the_content_network_row_by_row_and_foll
     # a pinned table (a captured graph holds its address) survives .train() as storage and is refilled in place
     t.pin_sense_table()
     model.train()
-    assert t._sense_table is not None and t._sense_table[0] is None
+    assert t._sense_table.rows is not None and t._sense_table.rows.data_ptr() == ptr and t._sense_table.key is None
+    assert t.sense_table_rows(stale_too=True) is t._sense_table.rows and t.sense_table_rows() is None
     model.eval()
     assert t.sense_table().data_ptr() == ptr
     t.pin_sense_table(False)
     model.train()
-    assert t._sense_table is None
+    assert t._sense_table.rows is None and t._sense_table.key is None
     model.eval()
     # 'auto' verification: never for CPU tensors, on the GPU from `sense_table_verify_min_positions` positions up
     assert not t._verify_applies(ids)

@@ -7,6 +7,7 @@ is sigmoid(6) and a wrong running sum would go unnoticed.  The scale is therefor
 model's sims over every prefix a test compares), and every annealed test asserts that at least half of the scores it compares (before
 `upweight_nearby`) lie in [0.1, 0.9].  content_weights are drawn from [0, 3) so that a dropped weight moves the logits."""
 import ctypes
+import inspect
 import os
 import sys
 from unittest import mock
@@ -17,45 +18,20 @@ import torch
 from conftest import ROOT
 
 import bp_hip
+from decode_support import PROMPT, STEPS, _anneal_scale, _assert_scores_in_band
+from decode_support import _close_fp32 as _close
+from decode_support import _nano_backpack as _backpack
 import src.models.backpack as backpack_module
 import src.models.intervened_models as IM
 from oracle import ref_cpu as R
 from src.models.intervened_models import (NegativeWeightedBackpackLMHeadModel, ReplacedWordLMHeadModel,
                                           WeightedBackpackLMHeadModel)
 from src.utils.generation import InferenceParams, greedy_decode
-from test_kv_cache_host import PROMPT, STEPS, _backpack, _close
 
 VOCAB, K, D = 200, 16, 384
 OCFG = dict(n_embd=D, n_head=6, n_layer=2, num_content_vectors=K, layer_norm_epsilon=1e-5,
             scale_attn_by_inverse_layer_idx=True)
 VARIANTS = ['weighted', 'weighted-anneal', 'weighted-anneal-flat', 'replaced']
-
-
-def _sims(model, ids):
-    """fp32 oracle of the similarity sums: (B,k,S) sum_j relu(C_l(x_i) . E[x_j]) over the whole of `ids`."""
-    with torch.no_grad():
-        content = model.transformer.content_model(ids)
-        emb = model.lm_head.weight[ids]
-        return torch.relu(content @ emb.transpose(1, 2).unsqueeze(1)).sum(dim=3)
-
-
-def _in_band(scale, sims):
-    scores = torch.sigmoid(-scale * sims + 6)
-    return ((scores >= 0.1) & (scores <= 0.9)).float().mean().item()
-
-
-def _anneal_scale(model, ids, lengths):
-    """6 / q-quantile of the similarity sums pooled over the prefixes of the given lengths (score 1/2 at that quantile);
-    of q = 0.3 .. 0.7 the one that leaves most scores unsaturated."""
-    sims = torch.cat([_sims(model, ids[:, :n]).flatten() for n in lengths])
-    return max((6.0 / sims.quantile(q).item() for q in (0.3, 0.4, 0.5, 0.6, 0.7)), key=lambda sc: _in_band(sc, sims))
-
-
-def _assert_scores_in_band(model, ids, scale, lengths):
-    sims = torch.cat([_sims(model, ids[:, :n]).flatten() for n in lengths])
-    inside = _in_band(scale, sims)
-    print(f'annealing scale {scale:.2f}: {100 * inside:.0f} % of {sims.numel()} scores in [0.1, 0.9]')
-    assert inside >= 0.5, inside
 
 
 def _wrapper(variant, model, ids, lengths=range(PROMPT, PROMPT + STEPS + 1), replaced=None):
@@ -178,7 +154,7 @@ def test_plain_model_steps_touch_nothing_of_the_intervention_code():
         got = model(ids[:, PROMPT:], inference_params=ip).logits[:, -1]
         assert spy.call_count == 1
         args, kwargs = spy.call_args
-        assert len(args) == 9 and kwargs == {}
+        assert inspect.signature(real).bind(*args, **kwargs).arguments.get('key_weight') is None
         _close(got, model(ids).logits[:, -1], 'plain step')
     assert not boom.called
     assert set(ip.key_value_memory_dict) == {0, 1, 'backpack_sense_k', 'backpack_rows', 'backpack_content'}

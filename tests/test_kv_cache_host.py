@@ -11,13 +11,12 @@ from conftest import ROOT
 
 import bp_hip
 import decode_needles as N
+from decode_support import PROMPT, STEPS
+from decode_support import _close_fp32 as _close
+from decode_support import _nano_backpack as _backpack
 from flash_attn.models.gpt import GPTLMHeadModel
-from src.models.backpack import BackpackConfig, BackpackLMHeadModel
 from src.utils.generation import InferenceParams
 from transformers import GPT2Config
-
-PROMPT, STEPS = 7, 20
-
 
 def _gpt(seed=0):
     torch.manual_seed(seed)
@@ -30,26 +29,8 @@ def _gpt(seed=0):
     return model
 
 
-def _backpack(seed=0, **kw):
-    torch.manual_seed(seed)
-    cfg = BackpackConfig(n_embd=384, n_head=6, n_layer=2, num_content_vectors=16, vocab_size=200, n_positions=64,
-                         resid_pdrop=0.0, embd_pdrop=0.0, attn_pdrop=0.0, scale_attn_by_inverse_layer_idx=True,
-                         use_flash_attn=False, **kw)
-    model = BackpackLMHeadModel(cfg).eval()
-    with torch.no_grad():
-        model.transformer.contextualization_attn.Wqkv.weight.mul_(8.0)
-        for layer in model.transformer.gpt2_model.layers:
-            layer.mixer.Wqkv.weight.mul_(6.0)
-    return model
-
-
 def _model(kind):
     return _gpt() if kind == 'gpt' else _backpack()
-
-
-def _close(got, want, what):
-    err = (got - want).abs().max().item()
-    assert err <= 1e-4 * want.abs().max().item(), (what, err, want.abs().max().item())
 
 
 @pytest.mark.parametrize('kind', ['gpt', 'backpack'])
