@@ -88,6 +88,7 @@ SIGNATURES = {
     'bp_sense_decode': (_i32, [_ptr] * 9 + [_i64] + [_i32] * 5 + [_i64] + [_i64] * 11 + [_f32, _i32, _ptr]),
     'bp_sense_decode_weighted': (_i32, [_ptr] * 10 + [_i64] + [_i32] * 5 + [_i64] + [_i64] * 13 + [_f32, _i32, _ptr]),
     'bp_sense_rows_dot': (_i32, [_ptr] * 6 + [_i32] * 4 + [_i64] + [_i64] * 6 + [_i32, _ptr]),
+    'bp_pick_token': (_i32, [_ptr] * 6 + [_i32] * 2 + [_i64] * 3 + [_i32] * 2 + [_f32, _i32, _f32, _i32, _ptr]),
 }
 
 
@@ -1123,3 +1124,47 @@ def sense_rows_dot(table, row_index, new_row, cache_seqlens, vec, out):
           out.data_ptr(), b, k, dout, max_s, table.shape[0], table.stride(0), table.stride(1), row_index.stride(0),
           vec.stride(0), out.stride(0), out.stride(1), _dtype_code(table))
     return out
+
+
+# ---- token selection on the device (C ABI bp_pick_token) ---------------------------------------------------------------------------------------------
+
+_PICK_DTYPES = {torch.float16: 0, torch.bfloat16: 1, torch.float32: 2}
+
+
+def pick_token(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rng_state=None, counters=None, tokens=None,
+               sequences=None, return_stats=False):
+    """The next token of every row of `logits` (B, vocab) fp16 / bf16 / fp32 (any row stride), chosen on the device by one
+    launch that reads no host value (legal inside a HIP-graph capture): argmax (lowest index of the maximum, NaN largest),
+    or with do_sample a draw after temperature, top-k (ties kept) and top-p -- the contract is in include/bp_hip.h.
+
+    rng_state: int64 {seed, offset} on the device (new_rng_state; drawn from torch's generator when None and do_sample);
+    counters (B,) int32 on the device: the Philox counter of every row and the column of `sequences` (B, cols) int64 that
+    also receives the pick (skipped outside [0, cols)); None: counter 0.  tokens: optional int64 output with B elements
+    (any stride along its first dimension), allocated when None.  Returns tokens, or (tokens, stats) with return_stats:
+    stats (B, 4) fp32 = lowest kept scaled logit, log-sum-exp of the kept ones, kept count, the uniform u."""
+    _require_cuda(logits, rng_state, counters, tokens, sequences)
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.dtype not in _PICK_DTYPES:
+        raise RuntimeError('bp_hip.pick_token: logits must be (B, vocab) fp16 / bf16 / fp32 with a contiguous last dimension')
+    batch, vocab = logits.shape
+    if do_sample and rng_state is None:
+        rng_state = new_rng_state(logits.device)
+    if rng_state is not None and (rng_state.dtype != torch.int64 or rng_state.numel() != 2 or not rng_state.is_contiguous()):
+        raise RuntimeError('bp_hip.pick_token: rng_state must be a contiguous int64 tensor of 2 elements')
+    if counters is not None and (counters.shape != (batch,) or counters.dtype != torch.int32 or not counters.is_contiguous()):
+        raise RuntimeError('bp_hip.pick_token: counters must be a contiguous (B,) int32 tensor')
+    if tokens is None:
+        tokens = torch.empty((batch,), dtype=torch.int64, device=logits.device)
+    if tokens.dtype != torch.int64 or tokens.numel() != batch or tokens.shape[0] != batch:
+        raise RuntimeError('bp_hip.pick_token: tokens must be int64 with B elements along its first dimension')
+    if sequences is not None and (sequences.dim() != 2 or sequences.shape[0] != batch or sequences.dtype != torch.int64
+                                  or sequences.stride(1) != 1):
+        raise RuntimeError('bp_hip.pick_token: sequences must be (B, cols) int64 with a contiguous last dimension')
+    stats = torch.empty((batch, 4), dtype=torch.float32, device=logits.device) if return_stats else None
+    _call('bp_pick_token', logits.device,
+          logits.data_ptr(), tokens.data_ptr(), sequences.data_ptr() if sequences is not None else None,
+          stats.data_ptr() if stats is not None else None, rng_state.data_ptr() if rng_state is not None else None,
+          counters.data_ptr() if counters is not None else None, batch, vocab, logits.stride(0),
+          tokens.stride(0) if batch > 1 else 1, sequences.stride(0) if sequences is not None else 0,
+          sequences.shape[1] if sequences is not None else 0, int(bool(do_sample)), float(temperature), int(top_k),
+          float(top_p), _PICK_DTYPES[logits.dtype])
+    return (tokens, stats) if return_stats else tokens

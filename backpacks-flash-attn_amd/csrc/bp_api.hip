@@ -129,6 +129,7 @@ const char *bp_strerror(int code) {
         case BP_ERR_DROPOUT: return "dropout: p must be in [0, 1), rng_state non-NULL when p > 0, 16-byte friendly shapes only";
         case BP_ERR_QUEUE_WS: return "queue_ws must be caller-owned (non-NULL) while the stream is being captured";
         case BP_ERR_WORKSPACE: return "workspace smaller than the *_ws_floats() query of this entry point";
+        case BP_ERR_SAMPLING: return "token sampling: top_p must be in (0, 1], rng_state non-NULL when do_sample";
         default: return "unknown error";
     }
 }
@@ -890,6 +891,34 @@ int bp_sense_rows_dot(const void *table, const int32_t *row_index, const int32_t
     p.o_bs = o_batch_stride; p.o_gs = o_sense_stride; p.table_rows = table_rows;
     p.b = batch; p.groups = nsenses; p.dout = d_out; p.max_seqlen = max_seqlen;
     return launch_status(bp::launch_sense_rows_dot(p, dtype, static_cast<hipStream_t>(stream)));
+}
+
+// ---- token selection (bp_pick_token) ----
+
+int bp_pick_token(const void *logits, int64_t *tokens, int64_t *sequences, float *stats, const uint64_t *rng_state,
+                  const int32_t *counters, int batch, int vocab, int64_t row_stride, int64_t tokens_stride,
+                  int64_t seq_stride, int seq_cols, int do_sample, float temperature, int top_k, float top_p, int dtype,
+                  bp_stream_t stream) {
+    if (dtype != BP_DTYPE_F16 && dtype != BP_DTYPE_BF16 && dtype != BP_DTYPE_F32) return BP_ERR_DTYPE;
+    if (batch <= 0 || vocab <= 0 || vocab > (1 << 23) || row_stride < vocab || tokens_stride < 1) return BP_ERR_SHAPE;
+    if (logits == nullptr || tokens == nullptr) return BP_ERR_SHAPE;
+    if (sequences != nullptr && (seq_cols < 1 || seq_stride < seq_cols)) return BP_ERR_SHAPE;
+    const uintptr_t elem = dtype == BP_DTYPE_F32 ? 4 : 2;
+    if (reinterpret_cast<uintptr_t>(logits) % elem || reinterpret_cast<uintptr_t>(tokens) % 8
+        || reinterpret_cast<uintptr_t>(sequences) % 8 || reinterpret_cast<uintptr_t>(stats) % 4
+        || reinterpret_cast<uintptr_t>(rng_state) % 8 || reinterpret_cast<uintptr_t>(counters) % 4)
+        return BP_ERR_SHAPE;
+    if (!scale_ok(temperature) || !scale_ok(1.f / temperature)) return BP_ERR_SCALE;
+    if (!(top_p > 0.f && top_p <= 1.f)) return BP_ERR_SAMPLING;
+    if (do_sample && rng_state == nullptr) return BP_ERR_SAMPLING;
+    bp::PickParams p{};
+    p.logits = logits; p.tokens = tokens; p.sequences = sequences; p.stats = stats; p.rng_state = rng_state;
+    p.counters = counters;
+    p.row_stride = row_stride; p.tokens_stride = tokens_stride; p.seq_stride = seq_stride;
+    p.batch = batch; p.vocab = vocab; p.seq_cols = seq_cols;
+    p.do_sample = do_sample ? 1 : 0; p.top_k = top_k;
+    p.inv_t = 1.f / temperature; p.top_p = top_p;
+    return launch_status(bp::launch_pick_token(p, dtype, static_cast<hipStream_t>(stream)));
 }
 
 }  // extern "C"

@@ -314,4 +314,19 @@ struct RowsDotParams {
 };
 hipError_t launch_sense_rows_dot(const RowsDotParams &p, int dtype, hipStream_t stream);
 
+// bp_pick_token (pick_token.hip): one token per row of logits -- argmax, or a draw after temperature / top-k / top-p
+struct PickParams {
+    const void *logits;          // (batch, vocab) 16-bit or fp32, element stride row_stride, last stride 1; only read
+    int64_t *tokens;             // token of row b at tokens[b * tokens_stride]
+    int64_t *sequences;          // optional: row b, column counters[b] receives the token when 0 <= column < seq_cols
+    float *stats;                // optional (batch, 4): lowest kept z, log-sum-exp of the kept z, kept count, u
+    const uint64_t *rng_state;   // device {seed, offset} (bp_philox.h); read when do_sample
+    const int32_t *counters;     // optional (batch): Philox counter of every row = column of `sequences`; NULL: 0
+    int64_t row_stride, tokens_stride, seq_stride;
+    int batch, vocab, seq_cols;
+    int do_sample, top_k;
+    float inv_t, top_p;          // 1 / temperature
+};
+hipError_t launch_pick_token(const PickParams &p, int dtype, hipStream_t stream);
+
 }  // namespace bp

@@ -1,6 +1,8 @@
 """Greedy decoding / sampling -- mirror of the reference's training/src/utils/generation.py:23-92.  By default, as
 upstream, there is no KV cache: every step re-runs the whole forward on the grown prefix (so every step exercises the
 HIP attention and sense-mix kernels); `kv_cache=True` decodes on the caches of InferenceParams instead (_decode_cached).
+`temperature`, `top_k`, `top_p`, `rng_state` or `device_pick=True` move the pick to the device (bp_pick_token; _eager_pick on CPU tensors), on the cache with
+cg=True inside the captured step (_decode_cached_picked); without them the loops below run as they always did.
 Differences kept deliberately small: the result is a plain dataclass instead of the
 transformers `*DecoderOnlyOutput` classes (removed in transformers 5), and the appended token is
 `unsqueeze(1)` so batch sizes > 1 work (the reference's `unsqueeze(0)` in greedy_decode, :68, only
@@ -128,7 +130,165 @@ def _decode_cached(input_ids, model, max_length, pick, cg=False):
     return DecoderOnlyOutput(sequences=torch.cat(tokens, dim=1), scores=tuple(scores))
 
 
-def _run_loop(input_ids, model, max_length, pick, cg, kv_cache):
+# ---- the device pick: temperature / top-k / top-p, one definition for the HIP kernel and its torch restatement -----------------
+
+_M32 = 0xFFFFFFFF
+
+
+def _philox2x32(c0, c1, key):
+    """Philox2x32-10 (csrc/bp_philox.h) on int64 tensors holding 32-bit values: the 32 x 32 -> 64 bit product is built from
+    16-bit halves, so nothing leaves the signed 64-bit range."""
+    for _ in range(10):
+        hi16, lo16 = c0 >> 16, c0 & 0xFFFF
+        ph, pl = hi16 * 0xD256D193, lo16 * 0xD256D193                 # < 2^48 each; product = (ph << 16) + pl
+        low = ((ph & 0xFFFF) << 16) + (pl & _M32)
+        prod_hi = ((ph >> 16) + (pl >> 32) + (low >> 32)) & _M32
+        c0, c1 = prod_hi ^ key ^ c1, low & _M32
+        key = (key + 0x9E3779B9) & _M32
+    return c0, c1
+
+
+def _pick_uniforms(rng_state, counters):
+    """float64 u = ((r0 >> 8) + 0.5) 2^-24 of every row b: (r0, _) = philox2x32(counters[b], salt, key), (key, salt) =
+    dropout_stream(rng_state, b) (csrc/bp_philox.h; tests/philox_ref.py restates both with numpy)."""
+    seed, offset = rng_state[0], rng_state[1]
+    rows = torch.arange(counters.shape[0], dtype=torch.int64, device=counters.device)
+    a, b = _philox2x32(offset & _M32, (offset >> 32) & _M32, seed & _M32)
+    key, salt = _philox2x32(a ^ rows, b.expand_as(rows), (seed >> 32) & _M32)
+    r0, _ = _philox2x32(counters.to(torch.int64) & _M32, salt, key)
+    return ((r0 >> 8).double() + 0.5) * 2.0 ** -24
+
+
+def _eager_pick(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rng_state=None, counters=None):
+    """The contract of bp_pick_token (include/bp_hip.h) in torch ops, for tensors the kernel does not take (CPU): tokens
+    (batch,) int64 of logits (batch, vocab).  Greedy: torch.argmax (lowest index of the maximum, a NaN largest).  Sampling:
+    z = float(x) / T in fp32; top-k keeps z >= the k-th largest (ties kept); top-p keeps a token iff the kept mass strictly
+    above its logit is < p; the token is the lowest index whose cumulative kept probability exceeds u; rows with a NaN or
+    +inf, or without a finite logit, take the greedy answer.  Masses are float64 here and 40-bit fixed point in the kernel:
+    the two agree wherever u is not within rounding of a boundary of the cumulative distribution."""
+    x = logits.float()
+    greedy = torch.argmax(x, dim=-1)
+    if not do_sample:
+        return greedy
+    batch, vocab = x.shape
+    if counters is None:
+        counters = torch.zeros((batch,), dtype=torch.int32, device=x.device)
+    z = x * (torch.ones((), dtype=torch.float32, device=x.device) / temperature)
+    zmax = z.max(dim=-1, keepdim=True).values
+    degenerate = (torch.isnan(z).any(dim=-1) | (z == float('inf')).any(dim=-1) | (zmax[:, 0] == float('-inf')))
+    z = torch.where(degenerate[:, None], torch.zeros_like(z), z)          # any finite row: its result is discarded
+    zmax = torch.where(degenerate[:, None], torch.zeros_like(zmax), zmax)
+    keep = torch.ones_like(z, dtype=torch.bool)
+    if 0 < top_k < vocab:
+        keep = z >= torch.topk(z, top_k, dim=-1).values[:, -1:]
+    w = torch.exp((z - zmax).double()) * keep
+    if top_p < 1.0:
+        zs, order = torch.sort(torch.where(keep, z, torch.full_like(z, float('-inf'))), dim=-1, descending=True, stable=True)
+        ws = torch.gather(w, 1, order)
+        before = torch.cumsum(ws, dim=-1) - ws                            # mass in front of every sorted position
+        idx = torch.arange(vocab, device=x.device).expand_as(zs)
+        new_run = torch.ones_like(zs, dtype=torch.bool)
+        new_run[:, 1:] = zs[:, 1:] != zs[:, :-1]
+        run_start = torch.cummax(torch.where(new_run, idx, torch.zeros_like(idx)), dim=-1).values
+        above = torch.gather(before, 1, run_start)                        # mass of strictly larger logits: ties share it
+        keep_sorted = above < top_p * ws.sum(dim=-1, keepdim=True)
+        keep = keep & torch.zeros_like(keep).scatter_(1, order, keep_sorted)
+        w = w * keep
+    cdf = torch.cumsum(w, dim=-1)
+    u = _pick_uniforms(rng_state, counters)
+    hit = cdf > (u * cdf[:, -1])[:, None]
+    last_kept = vocab - 1 - torch.flip(keep, dims=(-1,)).int().argmax(dim=-1)
+    drawn = torch.where(hit.any(dim=-1), hit.int().argmax(dim=-1), last_kept)
+    return torch.where(degenerate, greedy, drawn)
+
+
+class _Picker:
+    """The pick of the decode loops through bp_pick_token (CUDA tensors) or _eager_pick: argmax when not do_sample, else a
+    draw after temperature / top-k / top-p.  `counters` (batch,) int32 on the logits' device hold the 0-based sequence
+    position of the token being picked: the Philox counter, and the column of `sequences` that receives the token."""
+
+    def __init__(self, do_sample, temperature, top_k, top_p, rng_state, device):
+        if not (temperature > 0.0 and temperature < float('inf')) or not 0.0 < top_p <= 1.0:
+            raise ValueError('generation: temperature must be finite and > 0, top_p in (0, 1]')
+        self.do_sample, self.temperature, self.top_k, self.top_p = do_sample, float(temperature), int(top_k), float(top_p)
+        if do_sample and rng_state is None:       # from torch's generator: torch.manual_seed reproduces a run
+            rng_state = torch.randint(-2 ** 63, 2 ** 63 - 1, (2,), dtype=torch.int64, device=device)
+        self.rng_state = rng_state.to(device) if rng_state is not None else None
+
+    def __call__(self, logits, counters, tokens=None, sequences=None):
+        """tokens (batch,) int64; also stored into `tokens` (batch elements) and column counters[b] of `sequences`."""
+        if logits.is_cuda:
+            import bp_hip
+            out = bp_hip.pick_token(logits, self.do_sample, self.temperature, self.top_k, self.top_p, self.rng_state,
+                                    counters, tokens=tokens, sequences=sequences)
+            return out.view(-1)
+        picked = _eager_pick(logits, self.do_sample, self.temperature, self.top_k, self.top_p, self.rng_state, counters)
+        if tokens is not None:
+            tokens.view(-1).copy_(picked)
+        if sequences is not None:
+            cols = counters.long()
+            ok = (cols >= 0) & (cols < sequences.shape[1])
+            rows = torch.arange(sequences.shape[0], device=sequences.device)
+            sequences[rows[ok], cols[ok]] = picked[ok]
+        return picked
+
+    def loop_pick(self, input_ids):
+        """pick(logits) for the loops without a cache, which keep a device position of their own."""
+        position = torch.full((input_ids.shape[0],), input_ids.shape[1], dtype=torch.int32, device=input_ids.device)
+
+        def pick(logits):
+            picked = self(logits, position)
+            position.add_(1)
+            return picked.to(input_ids.dtype)
+        return pick
+
+
+def _decode_cached_picked(input_ids, model, max_length, picker, cg=False):
+    """_decode_cached with the pick on the device: the counter of a pick is `lengths_per_sample` after the step's
+    increment, the pick writes the next step's input (`static_ids`) and column `position` of the preallocated `sequences`.
+    With cg=True the captured graph is model step, length increment, pick: a generated token is one replay, with no launch
+    and no host read outside it.  Same index contract as _decode (the final pick lands outside `sequences` and is dropped)."""
+    batch, seqlen_og = input_ids.shape
+    width = max(seqlen_og, max_length - 1)
+    ip = InferenceParams(max_sequence_len=width, max_batch_size=batch)
+    ip.lengths_per_sample = torch.zeros((batch,), dtype=torch.int32, device=input_ids.device)
+    sequences = torch.zeros((batch, width), dtype=torch.int64, device=input_ids.device)
+    sequences[:, :seqlen_og] = input_ids
+    static_ids = torch.zeros((batch, 1), dtype=torch.int64, device=input_ids.device)
+    with torch.inference_mode():
+        logits = model(input_ids, inference_params=ip).logits[:, -1]
+        scores = [logits]
+        ip.sequence_len_offset = seqlen_og
+        ip.lengths_per_sample.fill_(seqlen_og)
+        picker(logits, ip.lengths_per_sample, tokens=static_ids, sequences=sequences)
+
+        def step():
+            step_logits = model(static_ids, inference_params=ip).logits[:, -1]
+            ip.lengths_per_sample += 1
+            picker(step_logits, ip.lengths_per_sample, tokens=static_ids, sequences=sequences)
+
+        seqlen = seqlen_og + 1
+        graph = None
+        while seqlen < max_length:
+            if graph is not None:
+                graph.replay()
+            else:
+                step()
+                if cg and input_ids.is_cuda and seqlen + 1 < max_length:
+                    graph = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(graph):
+                        step()
+                    # the capture ran nothing: lengths, caches, static_ids and sequences are as the eager step left them
+            ip.sequence_len_offset += 1
+            seqlen += 1
+    return DecoderOnlyOutput(sequences=sequences.to(input_ids.dtype), scores=tuple(scores))
+
+
+def _run_loop(input_ids, model, max_length, pick, cg, kv_cache, picker=None):
+    if picker is not None:
+        if kv_cache:
+            return _decode_cached_picked(input_ids, model, max_length, picker, cg=cg)
+        pick = picker.loop_pick(input_ids)
     if kv_cache:
         return _decode_cached(input_ids, model, max_length, pick, cg=cg)
     if cg and input_ids.is_cuda:
@@ -136,32 +296,55 @@ def _run_loop(input_ids, model, max_length, pick, cg, kv_cache):
     return _decode(input_ids, model, max_length, pick)
 
 
-def greedy_decode(input_ids, model, max_length, cg=False, kv_cache=False):
+def _picker(input_ids, do_sample, temperature, top_k, top_p, rng_state, device_pick):
+    """None when no option of the device pick is given: the loops then run exactly as before."""
+    if not (device_pick or temperature != 1.0 or top_k != 0 or top_p != 1.0 or rng_state is not None):
+        return None
+    return _Picker(do_sample, temperature, top_k, top_p, rng_state, input_ids.device)
+
+
+def greedy_decode(input_ids, model, max_length, cg=False, kv_cache=False, temperature=1.0, top_k=0, top_p=1.0,
+                  rng_state=None, device_pick=False):
     """input_ids (batch, seq_len) -> sequences (batch, max_length - 1): argmax continuation.
     cg=True: one captured full-width forward replayed per token (CUDA tensors only), see _decode_graphed.
-    kv_cache=True: prefill once, then one cached step per token (with cg=True: one captured step), see _decode_cached."""
-    return _run_loop(input_ids, model, max_length, lambda logits: torch.argmax(logits, dim=-1), cg, kv_cache)
+    kv_cache=True: prefill once, then one cached step per token (with cg=True: one captured step), see _decode_cached.
+    device_pick=True: the argmax runs in bp_pick_token (on CPU tensors: _eager_pick), with kv_cache and cg inside the
+    captured step (_decode_cached_picked); the sampling options are accepted for symmetry and do not change an argmax."""
+    picker = _picker(input_ids, False, temperature, top_k, top_p, rng_state, device_pick)
+    return _run_loop(input_ids, model, max_length, lambda logits: torch.argmax(logits, dim=-1), cg, kv_cache, picker)
 
 
-def sample(input_ids, model, max_length, cg=False, kv_cache=False):
-    """Ancestral sampling from softmax(logits) (reference :23-48); cg / kv_cache as in greedy_decode."""
+def sample(input_ids, model, max_length, cg=False, kv_cache=False, temperature=1.0, top_k=0, top_p=1.0, rng_state=None,
+           device_pick=False):
+    """Ancestral sampling from softmax(logits) (reference :23-48); cg / kv_cache as in greedy_decode.
+    temperature, top_k (ties at the threshold kept, as the reference's top_k_filter, training/run_pplm.py:569-581), top_p:
+    the usual filters; any of them, an `rng_state` or device_pick=True selects the device pick (bp_pick_token, contract in
+    include/bp_hip.h; _eager_pick on CPU tensors).  rng_state: int64 {seed, offset} (bp_hip.new_rng_state), drawn from
+    torch's generator when None; the token at sequence position t of row b is a pure function of (logits, rng_state, b, t),
+    so cached, graphed and growing-prefix runs under one rng_state draw the same numbers."""
+    picker = _picker(input_ids, True, temperature, top_k, top_p, rng_state, device_pick)
+
     def pick(logits):
         return torch.distributions.Categorical(logits=torch.log_softmax(logits.float(), dim=-1)).sample()
-    return _run_loop(input_ids, model, max_length, pick, cg, kv_cache)
+    return _run_loop(input_ids, model, max_length, pick, cg, kv_cache, picker)
 
 
 class GenerationMixin:
 
-    def _generate(self, decode, input_ids, max_length, return_dict_in_generate, output_scores, cg, kv_cache):
-        output = decode(input_ids, self, max_length, cg=cg, kv_cache=kv_cache)
+    def _generate(self, decode, input_ids, max_length, return_dict_in_generate, output_scores, cg, kv_cache, **pick_options):
+        output = decode(input_ids, self, max_length, cg=cg, kv_cache=kv_cache, **pick_options)
         if not output_scores:
             output.scores = None
         return output if return_dict_in_generate else output.sequences
 
     def generate(self, input_ids, max_length, return_dict_in_generate=False, output_scores=False, cg=False,
-                 kv_cache=False):
-        return self._generate(greedy_decode, input_ids, max_length, return_dict_in_generate, output_scores, cg, kv_cache)
+                 kv_cache=False, temperature=1.0, top_k=0, top_p=1.0, rng_state=None, device_pick=False):
+        return self._generate(greedy_decode, input_ids, max_length, return_dict_in_generate, output_scores, cg, kv_cache,
+                              temperature=temperature, top_k=top_k, top_p=top_p, rng_state=rng_state,
+                              device_pick=device_pick)
 
     def sample(self, input_ids, max_length, return_dict_in_generate=False, output_scores=False, cg=False,
-               kv_cache=False):
-        return self._generate(sample, input_ids, max_length, return_dict_in_generate, output_scores, cg, kv_cache)
+               kv_cache=False, temperature=1.0, top_k=0, top_p=1.0, rng_state=None, device_pick=False):
+        return self._generate(sample, input_ids, max_length, return_dict_in_generate, output_scores, cg, kv_cache,
+                              temperature=temperature, top_k=top_k, top_p=top_p, rng_state=rng_state,
+                              device_pick=device_pick)

@@ -42,12 +42,14 @@ extern "C" {
                               *_ws_floats queries added;
                               11: bp_sense_decode_weighted (per-key weights on the decode step's probabilities) and
                               bp_sense_rows_dot (dot products of the cached positions' sense vectors with one vector)
-                              added: KV-cached decoding of the intervened Backpacks */
+                              added: KV-cached decoding of the intervened Backpacks;
+                              (still 11, a purely additive entry point: bp_pick_token, token selection on the device --
+                              argmax, temperature, top-k, top-p -- and BP_ERR_SAMPLING) */
 
 /* element type of q/k/v/out/content tensors */
 #define BP_DTYPE_F16 0
 #define BP_DTYPE_BF16 1
-#define BP_DTYPE_F32 2   /* accepted by the cross-entropy entry points only */
+#define BP_DTYPE_F32 2   /* accepted by the cross-entropy entry points and bp_pick_token only */
 
 #define BP_OK 0
 #define BP_ERR_DTYPE -1       /* dtype is not BP_DTYPE_F16 / BP_DTYPE_BF16         (fmha_api.cpp:215-219) */
@@ -59,6 +61,7 @@ extern "C" {
 #define BP_ERR_DROPOUT -7     /* p_dropout outside [0,1), rng_state NULL with p > 0, or a shape the dropout path lacks */
 #define BP_ERR_QUEUE_WS -8    /* persistent launch with queue_ws == NULL on a stream that is being captured            */
 #define BP_ERR_WORKSPACE -9   /* a caller-provided workspace is smaller than the entry point's *_ws_floats() query     */
+#define BP_ERR_SAMPLING -10   /* bp_pick_token: top_p outside (0, 1], or do_sample without an rng_state                */
 
 #define BP_QUEUE_WS_BYTES 64   /* `queue_ws` of the persistent sense-mix launches */
 
@@ -606,6 +609,43 @@ int bp_sense_rows_dot(const void *table, const int32_t *row_index, const int32_t
                       int batch, int nsenses, int d_out, int max_seqlen, int64_t table_rows,
                       int64_t t_row_stride, int64_t t_sense_stride, int64_t idx_batch_stride, int64_t vec_batch_stride,
                       int64_t o_batch_stride, int64_t o_sense_stride, int dtype, bp_stream_t stream);
+
+/*
+ * bp_pick_token -- the next token of every row of logits, chosen on the device: the pick of a decode step (the
+ * reference's greedy_decode / sample, flash_attn/utils/generation.py, pick on the host with torch.argmax /
+ * torch.multinomial; its control baseline samples with temperature and top_k, training/run_pplm.py:80,347-348,569-581).
+ * No host value enters the pick, so one captured launch serves every step of a replayed decode graph.
+ *   logits     (batch, vocab) fp16 / bf16 / fp32 (dtype 0 / 1 / 2), element stride row_stride >= vocab, last stride 1, any
+ *              element-aligned base (16-byte loads start at the first 16-byte boundary).  Only read.
+ *   tokens     int64, the pick of row b at tokens[b * tokens_stride]
+ *   sequences  optional int64 (batch, seq_stride): row b, column counters[b] also receives the pick; the write is skipped
+ *              when that column is outside [0, seq_cols)
+ *   stats      optional fp32 (batch, 4) contiguous: {lowest kept z, natural-log sum-exp of the kept z, kept count, u}; greedy and
+ *              degenerate rows report the maximum twice and a count of 1
+ *   rng_state  DEVICE {seed, offset} as in bp_flash_fwd_dropout; read when do_sample, never written
+ *   counters   optional int32 (batch) on the device; NULL means 0 for every row
+ * do_sample == 0: the lowest index of the maximal logit; a NaN counts as larger than every number (torch.argmax).
+ * do_sample != 0, with z_i = float(x_i) * (1 / temperature) (the reciprocal rounded to fp32 first):
+ *   top_k   0 < top_k < vocab: tau = the top_k-th largest z counted with multiplicity, keep z_i >= tau (ties at the threshold
+ *           are all kept); top_k <= 0 or >= vocab: off
+ *   top_p   < 1: on the probabilities renormalised over what top_k kept, keep i iff the total probability of kept tokens
+ *           with z_j > z_i is < top_p (equal logits share a fate; without ties the smallest prefix whose mass reaches top_p)
+ *   u       ((r0 >> 8) + 0.5) * 2^-24 as a real number in (0, 1) (stats holds its fp32 rounding), (r0, _) =
+ *           philox2x32(counters[b], salt, key) with (key, salt) the stream of index b of rng_state (csrc/bp_philox.h;
+ *           tests/philox_ref.py: stream, philox2x32)
+ *   token   the lowest index t, in vocabulary order, whose cumulative kept probability through t exceeds u
+ *   a row whose kept mass is not positive and finite (a NaN or +inf among the z, or no finite z) takes the do_sample == 0 answer
+ * Probabilities are exp(z_i - max z) in 40-bit fixed point, so every sum is an integer sum: the result is a pure function of
+ * the arguments, bit for bit, whatever the order of the additions.
+ * Errors, before any launch: BP_ERR_DTYPE; BP_ERR_SHAPE (batch or vocab < 1, vocab > 2^23, row_stride < vocab, tokens_stride
+ * < 1, sequences with seq_cols < 1 or seq_stride < seq_cols, a NULL logits / tokens, a misaligned pointer); BP_ERR_SCALE
+ * (temperature not finite or not > 0, checked for greedy calls too); BP_ERR_SAMPLING (top_p outside (0, 1]; do_sample with a
+ * NULL rng_state).
+ */
+int bp_pick_token(const void *logits, int64_t *tokens, int64_t *sequences, float *stats, const uint64_t *rng_state,
+                  const int32_t *counters, int batch, int vocab, int64_t row_stride, int64_t tokens_stride,
+                  int64_t seq_stride, int seq_cols, int do_sample, float temperature, int top_k, float top_p, int dtype,
+                  bp_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -4,6 +4,14 @@ generate(..., kv_cache=True) eagerly and with cg=True (one captured decode step 
 
     python scripts/bench_generate.py [--batch 1] [--prompt 16] [--max-length 128] [--model small] [--modes off,cached]
                                      [--legs full,kv] [--intervention none|weighted|weighted-anneal|replaced]
+                                     [--pick torch|device|torch,device] [--sample] [--temperature T] [--top-k K] [--top-p P]
+                                     [--repeats N]
+
+--pick chooses how the next token is picked: `torch` is torch.argmax / torch.distributions.Categorical on the host side
+of the loop, `device` the bp_pick_token kernel (device_pick=True; with kv_cache and cg inside the captured step).  With
+both, the two picks alternate inside every leg, --repeats times each, in one process: the line then carries the median
+and every run of each (`<leg>_<pick>_ms`, `<leg>_<pick>_ms_runs`).  --sample times sample() instead of generate();
+--temperature / --top-k / --top-p go to the device pick only (the torch pick has no such options).
 
 --intervention wraps the model in the control-experiment classes of src/models/intervened_models.py (seeded
 content_weights in [0, 3); for the annealed form a scale of 6 / median of the similarity sums at half the final length, so
@@ -30,6 +38,12 @@ def main():
     ap.add_argument('--modes', default='off,cached', help='sense_table modes to run')
     ap.add_argument('--legs', default='full,kv', help='full: growing-prefix loop and its graph; kv: the KV-cached legs')
     ap.add_argument('--intervention', default='none', choices=['none', 'weighted', 'weighted-anneal', 'replaced'])
+    ap.add_argument('--pick', default='torch', help='torch, device, or torch,device (alternating)')
+    ap.add_argument('--sample', action='store_true', help='time sample() instead of generate()')
+    ap.add_argument('--temperature', type=float, default=1.0)
+    ap.add_argument('--top-k', type=int, default=0)
+    ap.add_argument('--top-p', type=float, default=1.0)
+    ap.add_argument('--repeats', type=int, default=1)
     a = ap.parse_args()
     from bench import MODELS
     from src.models.backpack import BackpackConfig, BackpackLMHeadModel
@@ -53,19 +67,35 @@ def main():
         res = dict(model=a.model, batch=a.batch, prompt=a.prompt, max_length=a.max_length,
                    new_tokens=a.max_length - 1 - a.prompt, sense_table=mode, **extra)
         outs = {}
+        picks = a.pick.split(',')
+        plain = picks == ['torch'] and not a.sample and a.repeats == 1      # the line of earlier revisions, key for key
+        if not plain:
+            res.update(sample=a.sample, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p)
+        options = dict(torch={}, device=dict(device_pick=True, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p))
+        decode = model.sample if a.sample else model.generate
         for key, cg, kv in legs:
-            model.generate(ids, max_length=a.max_length, cg=cg, kv_cache=kv)      # warm-up (allocator, library handles)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            outs[key] = model.generate(ids, max_length=a.max_length, cg=cg, kv_cache=kv)
-            torch.cuda.synchronize()
-            dt = time.perf_counter() - t0
-            res[key + '_ms'] = round(dt * 1e3, 1)
-            res[key + '_ms_per_token'] = round(dt * 1e3 / res['new_tokens'], 3)
+            runs = {pick: [] for pick in picks}
+            for pick in picks:                                               # warm-up (allocator, library handles)
+                decode(ids, max_length=a.max_length, cg=cg, kv_cache=kv, **options[pick])
+            for _ in range(a.repeats):
+                for pick in picks:
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    out = decode(ids, max_length=a.max_length, cg=cg, kv_cache=kv, **options[pick])
+                    torch.cuda.synchronize()
+                    runs[pick].append((time.perf_counter() - t0) * 1e3)
+                    outs[key if pick == picks[0] else key + '_' + pick] = out
+            for pick in picks:
+                name = key if plain else key + '_' + pick
+                dt = sorted(runs[pick])[len(runs[pick]) // 2]
+                res[name + '_ms'] = round(dt, 1)
+                res[name + '_ms_per_token'] = round(dt / res['new_tokens'], 3)
+                if not plain:
+                    res[name + '_ms_runs'] = [round(r, 1) for r in runs[pick]]
         # random weights: near-uniform logits, ties flip easily
         if 'eager_loop' in outs:
             res['tokens_equal_fraction'] = round((outs['eager_loop'] == outs['graph_replay']).float().mean().item(), 4)
-        if 'kv_cache_eager' in outs:
+        if 'kv_cache_eager' in outs and not (a.sample and picks[0] == 'torch'):   # the torch sampler draws anew per call
             res['kv_tokens_equal_graph'] = bool(torch.equal(outs['kv_cache_eager'], outs['kv_cache_graph']))
             if 'eager_loop' in outs:
                 res['kv_tokens_equal_fraction'] = round(
