@@ -85,8 +85,8 @@ inline SenseKernel sense_route(int d_k, int seqlen, int d_out, bool vec_qk, bool
     if (d_k > 128)
         return bp::sense_wide_dma_takes(seqlen, d_k, d_out, vec_qk, vec_c, weighted) ? SenseKernel::WideRing
                                                                                        : SenseKernel::WideStaged;
-    // the mix ring kernel numbers its jobs group * 256 + query tile: at most 256 tiles of 256 queries
-    const bool ring_fits = d_out == 0 || gather || seqlen <= 256 * 256;
+    // the mix ring kernels number their jobs group * kMixMaxTiles + tile (mix_ring.h): tiles of 256 queries
+    const bool ring_fits = d_out == 0 || gather || seqlen <= bp::kMixMaxTiles * 256;
     return vec_qk && vec_c && ring_fits ? SenseKernel::NarrowRing : SenseKernel::NarrowStaged;
 }
 

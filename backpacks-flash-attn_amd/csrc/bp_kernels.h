@@ -101,13 +101,15 @@ struct ProbsParams {
     uint32_t drop_thr;
 };
 
-// job queues of the persistent sense-mix launches (sense_mix_dma.hip, sense_mix_bwd.hip): one ticket per XCD.
+// job queues of the persistent sense-mix launches (mix_ring.h; sense_mix_dma.hip, sense_mix_bwd.hip): one ticket per XCD.
 // 64 bytes, zeroed in front of every launch (arm_mix_queues)
 struct MixQueues {
     unsigned int ticket[8];
     unsigned int pad[8];
 };
 hipError_t arm_mix_queues(MixQueues *&queues, hipStream_t stream);   // NULL -> a record of the library's ring
+// a job is numbered group * kMixMaxTiles + tile: at most this many 256-row tiles per sequence (bp_api.hip, sense_route)
+constexpr int kMixMaxTiles = 256;
 
 struct MixParams {
     const void *q, *k;        // q_l[t] = q + b*qk_bs + t*qk_rs + l*qk_ss ; k likewise

@@ -24,26 +24,12 @@
 #include "bp_common.h"
 #include "bp_dma.h"
 #include "bp_kernels.h"
+#include "mix_ring.h"
 
 namespace bp {
 
-template <int KD>
-struct MixDcCfg {
-    static constexpr int BM = 256, BQ = 64, NB = 8, BNC = 256, NT = 512, NWAVE = 8, NSTAGE = 3;
-    static constexpr int QROW = KD <= 4 ? 128 : 256;   // bytes per Q row (power of two, XOR-swizzled)
-    static constexpr int QSLOTS = QROW / 16;
-    static constexpr int DROW = 512;                    // bytes per dout row (256 columns)
-    static constexpr int QTILE = BQ * QROW;
-    static constexpr int DTILE = BQ * DROW;
-    static constexpr int STATS = NWAVE * 256;           // per wave: lse of the tile's 64 queries (fp32)
-    static constexpr int STAGE = QTILE + DTILE + STATS;
-    static constexpr int Q_DMA = QTILE / 1024 / NWAVE;  // 1 or 2
-    static constexpr int D_DMA = DTILE / 1024 / NWAVE;  // 4
-    static constexpr int DMA_PER_STAGE = Q_DMA + D_DMA + 1;
-    static constexpr int Q_ROWS_PER_DMA = 1024 / QROW;
-    static constexpr int JOB_OFF = NSTAGE * STAGE;
-    static constexpr int SMEM = JOB_OFF + 16;
-};
+// the ring of mix_ring.h: A = Q rows, B = dout rows, aux = lse of the tile's 64 queries
+template <int KD> using MixDcCfg = MixRingCfg<KD, true>;
 
 template <class ET, int KD, bool FULL>
 __global__ __launch_bounds__(512) void sense_mix_dc_kernel(const MixBwdParams p) {
@@ -60,47 +46,13 @@ __global__ __launch_bounds__(512) void sense_mix_dc_kernel(const MixBwdParams p)
     const float c2 = p.scale_log2e;
     const uint32_t lds0 = lds_base_addr(smem);
 
-    int q_read_off[KD];   // Q fragment (A operand of S = Q K^T): row l31 (+32*kk), logical slot 2*s + hh
-#pragma unroll
-    for (int s = 0; s < KD; ++s) q_read_off[s] = l31 * C::QROW + (((2 * s + hh) ^ k_swz<C::QROW>(l31)) * 16);
-    const int d_row_lane = 4 * hh + ((lane & 15) >> 2);
-    const int d_ch_lane = ((lane >> 4) & 1) * 2 + ((lane & 3) >> 1);
-    static_assert(C::NB == 8, "d_read_off assumes 8 column blocks");
-    int d_read_off[4];   // dout^T fragment; block n + 4 sits 256 bytes after block n (see sense_mix_dma.hip)
-#pragma unroll
-    for (int n = 0; n < 4; ++n) d_read_off[n] = v_lds_off<C::NB>(d_row_lane, n * 4 + d_ch_lane) + (lane & 1) * 8;
+    const MixTileReader<C> rd(lane);
+    uint32_t exhausted = 0;   // job queues with no jobs left (mix_take_job)
 
-    // ---- job queues (as in sense_mix_dma.hip; slot 0 = key tile 0 = the most query tiles) ----------------------
-    MixQueues *queues = p.queues;
-    uint32_t exhausted = 0;
-    const int my_xcd = blockIdx.x & 7;
-    auto next_job = [&]() -> int {   // thread 0 only; returns grp * 256 + key tile, or -1
-        for (int t = 0; t < 8; ++t) {
-            const int q = (my_xcd + t) & 7;
-            if (exhausted & (1u << q)) continue;
-            const int groups = mix_queue_groups(p.b, p.n_chunks, q);
-            const int njobs = groups * p.n_ktiles;
-            const int idx = njobs > 0 ? (int)atomicAdd(&queues->ticket[q], 1u) : njobs;
-            if (idx < njobs) {
-                const int slot = idx / groups;
-                const int grp = mix_queue_group(p.n_chunks, q, idx - slot * groups);
-                return grp * 256 + slot;
-            }
-            exhausted |= 1u << q;
-        }
-        return -1;
-    };
-
-    for (;;) {
-        __syncthreads();
-        if (tid == 0) *reinterpret_cast<int *>(smem + C::JOB_OFF) = next_job();
-        __syncthreads();
-        const int job = __builtin_amdgcn_readfirstlane(*reinterpret_cast<const int *>(smem + C::JOB_OFF));
-        if (job < 0) break;
-        const int grp = job >> 8, kt = job & 255;
-        const int batch = grp / p.n_chunks;
-        const int chunk = grp - batch * p.n_chunks;
-        const int col_base = chunk * C::BNC;
+    for (int word; (word = mix_take_job<C>(smem, p.queues, exhausted, p.b, p.n_chunks, p.n_ktiles)) >= 0;) {
+        const MixJob job = mix_decode_job<C>(word, p.n_chunks);
+        const int batch = job.batch, col_base = job.col_base;
+        const int kt = job.rank;   // key tile 0 = the most query tiles = the heaviest first
 
         const uint16_t *qg = reinterpret_cast<const uint16_t *>(p.q) + batch * p.qk_bs;
         const uint16_t *kg = reinterpret_cast<const uint16_t *>(p.k) + batch * p.qk_bs;
@@ -114,77 +66,23 @@ __global__ __launch_bounds__(512) void sense_mix_dc_kernel(const MixBwdParams p)
         const int nb_live = FULL ? C::NB : min(C::NB, (p.dout_cols - col_base + 31) / 32);
 
         // query tiles (64 queries) of this job: [qb_begin, nqb); masks needed before qb_clean and in a partial last tile
-        const int nqb = (S + C::BQ - 1) / C::BQ;
-        const int qb_begin = (kt * C::BM) / C::BQ;
-        const int qb_full_end = S / C::BQ;
-        const int qb_clean = min(qb_begin + C::BM / C::BQ, nqb);
-        const int nq = nqb - qb_begin;
+        const int nqb = (S + C::BK - 1) / C::BK;
+        const int qb_begin = (kt * C::BM) / C::BK;
+        const int qb_full_end = S / C::BK;
+        const int qb_clean = min(qb_begin + C::BM / C::BK, nqb);
 
-        // Per-lane byte offsets of my DMA pieces inside a tile, rebuilt per job from an opaque copy of the lane index so
-        // that the row / column tables are not hoisted to kernel entry and kept alive (and spilled) across the job loop;
-        // the partial last tile clamps its rows inside issue(), in a cold branch (see sense_mix_dma.hip).
-        int lane_o = lane;
-        asm volatile("" : "+v"(lane_o));
-        const int qb_partial = (S % C::BQ) != 0 ? nqb - 1 : -1;
-        const int last_row = S - 1 - (nqb - 1) * C::BQ;
-        auto q_piece_row = [&](int j) { return (wave * C::Q_DMA + j) * C::Q_ROWS_PER_DMA + lane_o / C::QSLOTS; };
-        auto d_piece_row = [&](int j) { return (wave * C::D_DMA + j) * 2 + (lane_o >> 5); };
-        uint32_t q_voff[C::Q_DMA], d_voff[C::D_DMA];
-#pragma unroll
-        for (int j = 0; j < C::Q_DMA; ++j) {
-            const int row = q_piece_row(j);
-            const int logical = (lane_o % C::QSLOTS) ^ k_swz<C::QROW>(row);
-            const int col = logical * 8 < p.dk ? logical * 8 : 0;   // pad slot: a duplicate of column 0 (meets zero K columns)
-            q_voff[j] = (uint32_t)(row * p.qk_rs + col) * 2u;
-        }
-#pragma unroll
-        for (int j = 0; j < C::D_DMA; ++j) {
-            const int row = d_piece_row(j);
-            const int stored = lane_o & 31;
-            const int logical = (((stored >> 2) ^ (row & 3)) << 2) | (stored & 3);
-            const int col = (FULL || col_base + logical * 8 < p.dout_cols) ? col_base + logical * 8 : col_base;
-            d_voff[j] = (uint32_t)(row * p.do_rs + col) * 2u;
-        }
-
-        // DMA pieces of the tile two steps ahead, (l2, qb2); its base pointers are carried and advanced on the scalar unit
-        // once per step (advance2), as in sense_mix_dma.hip
-        int l2 = 0, qb2 = qb_begin;
-        const int64_t q_tile_step = (int64_t)C::BQ * p.qk_rs, d_tile_step = (int64_t)C::BQ * p.do_rs;
-        const uint16_t *qs2 = qg + (int64_t)qb_begin * q_tile_step;   // first tile of sense l2
-        const uint16_t *qt2 = qs2;
-        const uint16_t *dt2 = dg + (int64_t)qb_begin * d_tile_step;
-        auto issue = [&](int, int, int slot, uint32_t pieces) {
-            const uint32_t stage_off = lds0 + slot * C::STAGE;
-            if (__builtin_expect(qb2 == qb_partial, 0)) {
-#pragma unroll
-                for (int j = 0; j < C::Q_DMA; ++j)
-                    if ((pieces >> j) & 1u) {
-                        const uint32_t back = (uint32_t)(max(q_piece_row(j) - last_row, 0) * p.qk_rs) * 2u;
-                        dma16_s(qt2, q_voff[j] - back, __builtin_amdgcn_readfirstlane(stage_off + (wave * C::Q_DMA + j) * 1024));
-                    }
-#pragma unroll
-                for (int j = 0; j < C::D_DMA; ++j)
-                    if ((pieces >> (C::Q_DMA + j)) & 1u) {
-                        const uint32_t back = (uint32_t)(max(d_piece_row(j) - last_row, 0) * p.do_rs) * 2u;
-                        dma16_s(dt2, d_voff[j] - back,
-                                __builtin_amdgcn_readfirstlane(stage_off + C::QTILE + (wave * C::D_DMA + j) * 1024));
-                    }
-            } else {
-#pragma unroll
-                for (int j = 0; j < C::Q_DMA; ++j)
-                    if ((pieces >> j) & 1u) dma16_s(qt2, q_voff[j], stage_off + (wave * C::Q_DMA + j) * 1024);
-#pragma unroll
-                for (int j = 0; j < C::D_DMA; ++j)
-                    if ((pieces >> (C::Q_DMA + j)) & 1u)
-                        dma16_s(dt2, d_voff[j], stage_off + C::QTILE + (wave * C::D_DMA + j) * 1024);
-            }
-            if ((pieces >> (C::Q_DMA + C::D_DMA)) & 1u) {
-                // lse of the tile's 64 queries for sense l2: lane i fetches lse[q0 + i] into the wave's own 256-B slot
-                const float *src = p.lse + ((int64_t)batch * p.nsenses + l2) * p.lse_stride + min(qb2 * C::BQ + lane, S - 1);
-                dma4(src, stage_off + C::QTILE + C::DTILE + wave * 256);
-            }
+        // the DMA side of the job (mix_ring.h): query tiles [qb_begin, nqb) of every sense; dout does not depend on the sense
+        MixStream<C> ring;
+        ring.begin_job(lds0, wave, lane, S, p.nsenses, qb_begin, S, qg, p.qk_rs, p.qk_ss, p.dk, dg, p.do_rs, 0);
+        uint32_t d_voff[C::B_DMA];
+        ring.template b_offsets<FULL>(d_voff, p.do_rs, col_base, p.dout_cols);
+        auto issue = [&](int slot, uint32_t pieces) {
+            ring.issue(
+                slot, pieces,
+                [&](int j, int back, uint32_t lds_dst) { dma16_s(ring.bt2, d_voff[j] - (uint32_t)(back * p.do_rs) * 2u, lds_dst); },
+                [&](int l) { return p.lse + ((int64_t)batch * p.nsenses + l) * p.lse_stride; });   // lse[b, l, :]
         };
-        constexpr uint32_t kAllPieces = (1u << C::DMA_PER_STAGE) - 1u;
+        constexpr uint32_t kAllPieces = C::ALL_PIECES;
 
         f32x16 acc[C::NB];
         u32x4 kf[KD];
@@ -201,21 +99,9 @@ __global__ __launch_bounds__(512) void sense_mix_dc_kernel(const MixBwdParams p)
             }
         };
 
-        // S of the 32-query half kk of the tile: rows = queries (registers), column = my key
-        auto scores = [&](int stage, int kk) {
-            f32x16 st;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) st[r] = 0.f;
-#pragma unroll
-            for (int s = 0; s < KD; ++s) {
-                const u32x4 a = lds_read_16B(smem, q_read_off[s] + stage + kk * 32 * C::QROW);
-                st = E::mfma(a, kf[s], st);
-            }
-            return st;
-        };
         // lse (in log2 units) of the queries my registers hold: four runs of four consecutive queries
         auto row_lse = [&](int stage, int kk, float (&l2)[16]) {
-            const int base = stage + C::QTILE + C::DTILE + wave * 256 + (kk * 32 + 4 * hh) * 4;
+            const int base = stage + C::AUX_OFF + wave * 256 + (kk * 32 + 4 * hh) * 4;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const u32x4 w4 = lds_read_16B(smem, base + g * 32);
@@ -226,28 +112,9 @@ __global__ __launch_bounds__(512) void sense_mix_dc_kernel(const MixBwdParams p)
                 }
             }
         };
-        auto pack = [&](const f32x16 &st, u32x4 (&pf)[2]) {
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) pf[ks][i] = E::pack2(st[ks * 8 + 2 * i], st[ks * 8 + 2 * i + 1]);
-        };
-        auto d_operand = [&](int rows, int n) {
-            const u32x2 lo = lds_read_tr16_8B(smem, d_read_off[n & 3] + (n >> 2) * 256 + rows);
-            const u32x2 hi = lds_read_tr16_8B(smem, d_read_off[n & 3] + (n >> 2) * 256 + rows + 8 * C::DROW);
-            return u32x4{lo[0], lo[1], hi[0], hi[1]};
-        };
-        // dC^T += dout^T P over N consecutive 16-query steps (pk[0..N-1]) from query row `row0` of the tile at `stage`, as
-        // one operand stream (mfma_stream, bp_common.h: the dout^T operand of MFMA i + 2 requested before MFMA i)
+        // dC^T += dout^T P over the 16-query steps pk[] from query row `row0` of the tile at `stage` (one operand stream)
         auto pv_stream = [&](int stage, int row0, const auto &pk, auto &&mid) {
-            constexpr int N = sizeof(pk) / sizeof(pk[0]) * C::NB;
-            const int base = stage + C::QTILE + row0 * C::DROW;
-            mfma_stream<N>([&](int i) { return d_operand(base + (i >> 3) * 16 * C::DROW, i & 7); },
-                           [&](int i, const u32x4 &a) {
-                               if (FULL || (i & 7) < nb_live) acc[i & 7] = E::mfma(a, pk[i >> 3], acc[i & 7]);
-                               asm volatile("" : "+v"(acc[i & 7]));
-                               mid(i);
-                           });
+            mix_pv_stream<E, C, FULL>(smem, rd, acc, nb_live, stage, row0, pk, mid);
         };
 
         // ---- steady-state step (every query of the tile exists and sees every key of the workgroup), cut as in
@@ -261,74 +128,50 @@ __global__ __launch_bounds__(512) void sense_mix_dc_kernel(const MixBwdParams p)
             f32x16 st1;
             {
                 f32x16 st0;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) st0[r] = st1[r] = 0.f;
-                mfma_stream<2 * KD>(
-                    [&](int i) { return lds_read_16B(smem, q_read_off[i >> 1] + stage + (i & 1) * 32 * C::QROW); },
-                    [&](int i, const u32x4 &a) {
-                        if (i & 1) { st1 = E::mfma(a, kf[i >> 1], st1); asm volatile("" : "+v"(st1)); }
-                        else { st0 = E::mfma(a, kf[i >> 1], st0); asm volatile("" : "+v"(st0)); }
-                    });
+                mix_scores_both<E, C>(smem, rd, stage, kf, st0, st1);   // S of both query halves as one operand stream
                 float lq[16];
                 row_lse(stage, 0, lq);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) st0[r] = fast_exp2(fmaf(st0[r], c2, -lq[r]));
-                pack(st0, pf0);
+                mix_pack<E>(st0, pf0);
             }
             float lq1[16];
             row_lse(stage, 1, lq1);
-            if (dma) issue(0, 0, slot2, 0x03u);
-            {
-                const int rows = stage + C::QTILE;
-                u32x4 a = d_operand(rows, 0);
-#pragma unroll
-                for (int n = 0; n < C::NB; ++n) {
-                    u32x4 a_next = a;
-                    if (n + 1 < C::NB) a_next = d_operand(rows, n + 1);
-                    asm volatile("" : "+v"(a));
-                    acc[n] = E::mfma(a, pf0[0], acc[n]);
-                    asm volatile("" : "+v"(acc[n]));
-                    float x0 = st1[2 * n], x1 = st1[2 * n + 1];
-                    asm volatile("" : "+v"(x0), "+v"(x1));
-                    x0 = fast_exp2(fmaf(x0, c2, -lq1[2 * n]));
-                    x1 = fast_exp2(fmaf(x1, c2, -lq1[2 * n + 1]));
-                    asm volatile("" : "+v"(x0), "+v"(x1));
-                    st1[2 * n] = x0;
-                    st1[2 * n + 1] = x1;
-                    a = a_next;
-                }
-            }
-            if (dma) issue(0, 0, slot2, kAllPieces & ~0x03u);
+            if (dma) issue(slot2, 0x03u);
+            // 8 MFMAs of half 0, queries 0..15, with the exponentials of half 1 between them (one lse per register: its query's;
+            // every column block, the ones past dout_cols are never stored)
+            mix_x_block<E, C, true>(smem, rd, acc, C::NB, stage, pf0[0], st1, c2, [&](int r) { return lq1[r]; });
+            if (dma) issue(slot2, kAllPieces & ~0x03u);
             pfc[0] = pf0[1];
             u32x4 pf1[2];
-            pack(st1, pf1);
+            mix_pack<E>(st1, pf1);
             pfc[1] = pf1[0];
             pfc[2] = pf1[1];
             asm volatile("" : "+v"(pfc[0]), "+v"(pfc[1]), "+v"(pfc[2]));   // the packs belong to X, not behind the barrier
             __builtin_amdgcn_s_setprio(0);
         };
         auto clean_y = [&](int stage, int slot2, bool dma) {
-            if (dma) issue(0, 0, slot2, 0x03u);
+            if (dma) issue(slot2, 0x03u);
             pv_stream(stage, 16, pfc, [&](int i) {
-                if (i == 11 && dma) issue(0, 0, slot2, kAllPieces & ~0x03u);
+                if (i == 11 && dma) issue(slot2, kAllPieces & ~0x03u);
             });
         };
 
         // ---- a step in the diagonal region or on the partial last tile: per-half liveness, masking
-        auto edge_step = [&](int stage, int qb, int l2, int qb2, int slot2) {
-            issue(l2, qb2, slot2, 0x01u);
+        auto edge_step = [&](int stage, int qb, int slot2) {
+            issue(slot2, 0x01u);
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) {
                 const int qsub = qb * 2 + kk;
                 const bool live = wave_has_keys && qsub >= my_key_sub && qsub * 32 < S;
                 u32x4 pf[2];
                 if (live) {
-                    f32x16 st = scores(stage, kk);
+                    f32x16 st = mix_scores<E, C>(smem, rd, stage, kk, kf);
                     float lq[16];
                     row_lse(stage, kk, lq);
 #pragma unroll
                     for (int r = 0; r < 16; ++r) st[r] = fast_exp2(fmaf(st[r], c2, -lq[r]));
-                    pack(st, pf);
+                    mix_pack<E>(st, pf);
                     // query of register r: qsub*32 + (r&3) + 8*(r>>2) + 4*hh.  It must exist (< S) and must not lie
                     // before my key: AND masks on the packed words (AND also kills an inf from an invisible pair).
                     const int q_lim = S - 1 - qsub * 32 - 4 * hh;                   // largest valid rel index (w/o 4hh)
@@ -347,38 +190,12 @@ __global__ __launch_bounds__(512) void sense_mix_dc_kernel(const MixBwdParams p)
                     }
                     pv_stream(stage, kk * 32, pf, [](int) {});
                 }
-                issue(l2, qb2, slot2, kk == 0 ? 0x0eu : (kAllPieces & ~0x0fu));
+                issue(slot2, kk == 0 ? 0x0eu : (kAllPieces & ~0x0fu));
             }
         };
 
-        // ---- pipeline: two tiles in flight (steps past the end re-fetch the last tile, see sense_mix_dma.hip) -----
-        auto advance2 = [&]() {
-            if (qb2 + 1 < nqb) {
-                ++qb2;
-                qt2 += q_tile_step;
-                dt2 += d_tile_step;
-            } else if (l2 + 1 < p.nsenses) {
-                ++l2;
-                qb2 = qb_begin;
-                qs2 += p.qk_ss;
-                qt2 = qs2;
-                dt2 = dg + (int64_t)qb_begin * d_tile_step;   // dout does not depend on the sense
-            }
-        };
-        issue(0, qb_begin, 0, kAllPieces);
-        advance2();
-        issue(l2, qb2, 1, kAllPieces);
-        advance2();
-
-        int slot = 0;
-        auto step_begin = [&]() {
-            wait_vmcnt<C::DMA_PER_STAGE>();
-            __builtin_amdgcn_s_barrier();
-        };
-        auto step_end = [&]() {
-            slot = slot == 2 ? 0 : slot + 1;
-            advance2();
-        };
+        // ---- pipeline: two tiles in flight (mix_ring.h) ------------------------------------------------------------
+        ring.prime([&](int slot) { issue(slot, kAllPieces); });
         uint16_t *dcg = reinterpret_cast<uint16_t *>(p.dc) + batch * p.c_bs + (int64_t)my_key * p.c_rs;
         for (int l = 0; l < p.nsenses; ++l) {
             if (wave_has_keys) take_k(l);
@@ -387,46 +204,31 @@ __global__ __launch_bounds__(512) void sense_mix_dc_kernel(const MixBwdParams p)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[n][r] = 0.f;
             for (int qb = qb_begin; qb < qb_clean; ++qb) {
-                step_begin();
-                edge_step(slot * C::STAGE, qb, l2, qb2, slot >= 1 ? slot - 1 : 2);
-                step_end();
+                ring.step_begin();
+                edge_step(ring.stage(), qb, ring.refill_slot());
+                ring.step_end();
             }
             // clean steps, two barriers each; waves 4-7 one barrier late (see sense_mix_dma.hip for the ring argument)
             if (qb_clean < qb_full_end) {
                 const bool late = wave >= C::NWAVE / 2;
-                if (late) step_begin();
+                if (late) ring.step_begin();
                 for (int qb = qb_clean; qb < qb_full_end; ++qb) {
-                    step_begin();
-                    clean_x(slot * C::STAGE, slot >= 1 ? slot - 1 : 2, late);
-                    step_begin();
-                    clean_y(slot * C::STAGE, slot >= 1 ? slot - 1 : 2, !late);
-                    step_end();
+                    ring.step_begin();
+                    clean_x(ring.stage(), ring.refill_slot(), late);
+                    ring.step_begin();
+                    clean_y(ring.stage(), ring.refill_slot(), !late);
+                    ring.step_end();
                 }
                 if (!late) __builtin_amdgcn_s_barrier();
             }
             for (int qb = max(qb_clean, qb_full_end); qb < nqb; ++qb) {
-                step_begin();
-                edge_step(slot * C::STAGE, qb, l2, qb2, slot >= 1 ? slot - 1 : 2);
-                step_end();
+                ring.step_begin();
+                edge_step(ring.stage(), qb, ring.refill_slot());
+                ring.step_end();
             }
             // dC[my key, sense l, chunk columns]
-            if (wave_has_keys && my_key < S) {
-                uint16_t *og = dcg + (int64_t)l * p.c_ss;
-#pragma unroll
-                for (int n = 0; n < C::NB; ++n)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const int col = col_base + n * 32 + 8 * g + 4 * hh;
-                        if (col < p.dout_cols) {
-                            u32x2 w = {E::pack2(acc[n][4 * g + 0], acc[n][4 * g + 1]),
-                                       E::pack2(acc[n][4 * g + 2], acc[n][4 * g + 3])};
-                            // (plain stores: 8-byte per-lane pieces marked non-temporal cost 1.6 -> 4.6 ms, r02_p)
-                            *reinterpret_cast<u32x2 *>(og + col) = w;
-                        }
-                    }
-            }
+            if (wave_has_keys && my_key < S) mix_store_row<E, C>(dcg + (int64_t)l * p.c_ss, acc, col_base, p.dout_cols, hh);
         }
-        (void)nq;
         wait_vmcnt<0>();
     }
 
@@ -850,17 +652,9 @@ __global__ __launch_bounds__(256) void sense_dk_kernel(const SenseGradParams p) 
 
 // ---- launchers -------------------------------------------------------------------------------------------------
 hipError_t launch_sense_mix_dc(const MixBwdParams &params, int dtype, hipStream_t stream) {
-    MixBwdParams p = params;
-    const hipError_t armed = arm_mix_queues(p.queues, stream);   // sense_mix_dma.hip
-    if (armed != hipSuccess) return armed;
-    const dim3 g(persistent_grid(p.b * p.n_chunks * p.n_ktiles)), t(512);
-    return with_dtype(dtype, [&](auto et) {
-        return with_kd(p.dk, [&](auto kd) {
-            return with_flag(p.dout_cols % 256 == 0, [&](auto full) {
-                hipLaunchKernelGGL((sense_mix_dc_kernel<decltype(et), kd, full>), g, t, 0, stream, p);
-                return hipGetLastError();
-            });
-        });
+    return launch_mix_persistent(params, params.n_ktiles, params.dout_cols, dtype, stream,
+                                 [&](auto et, auto kd, auto full, dim3 g, dim3 t, const MixBwdParams &p) {
+        hipLaunchKernelGGL((sense_mix_dc_kernel<decltype(et), kd, full>), g, t, 0, stream, p);
     });
 }
 

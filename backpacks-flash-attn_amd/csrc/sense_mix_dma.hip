@@ -34,6 +34,7 @@
 #include "bp_common.h"
 #include "bp_dma.h"
 #include "bp_kernels.h"
+#include "mix_ring.h"
 
 namespace bp {
 
@@ -48,36 +49,24 @@ __device__ unsigned long long g_mix_prof[256][8][12];   // [workgroup][wave][pha
 #define MIX_ADD(k, expr) do { } while (0)
 #endif
 
+// The ring (mix_ring.h: A = K rows, B = content rows, aux = key weights when WEIGHTED) and, behind it, the forward's own areas
 template <int KD, bool WEIGHTED = false>
-struct MixDmaCfg {
-    static constexpr int BM = 256, BK = 64, NB = 8, BNC = 256, NT = 512, NWAVE = 8, NSTAGE = 3;
-    static constexpr int KROW = KD <= 4 ? 128 : 256;   // bytes per K row (power of two, XOR-swizzled)
-    static constexpr int KSLOTS = KROW / 16;
-    static constexpr int CROW = 512;
-    static constexpr int KTILE = BK * KROW;
-    static constexpr int CTILE = BK * CROW;
-    static constexpr int WTILE = WEIGHTED ? NWAVE * 256 : 0;   // per wave: the tile's 64 key weights (fp32)
-    static constexpr int STAGE = KTILE + CTILE + WTILE;
-    static constexpr int K_DMA = KTILE / 1024 / NWAVE;   // DMA instructions per wave per tile (1 or 2)
-    static constexpr int C_DMA = CTILE / 1024 / NWAVE;   // 4
-    static constexpr int DMA_PER_STAGE = K_DMA + C_DMA + (WEIGHTED ? 1 : 0);
-    static constexpr int K_ROWS_PER_DMA = 1024 / KROW;   // 8 or 4
-    static constexpr int JOB_OFF = NSTAGE * STAGE;       // 16 bytes: job broadcast
-    static constexpr int SMEM = JOB_OFF + 16;
+struct MixDmaCfg : MixRingCfg<KD, WEIGHTED> {
+    using R = MixRingCfg<KD, WEIGHTED>;
     // Next sense's query operands, staged through LDS by DMA (see request_q): per wave KD fragments of 64 lanes x 16 B and
     // 64 x 4 B of log-sum-exp.  Only where the ring leaves room (128-byte K rows) and the flat two-phase loop runs.
     static constexpr bool ASYNC_Q = !WEIGHTED && KD <= 3;   // (d_k = 64 spills with the staging reads; wider ones have no LDS left)
-    static constexpr int QSTAGE_OFF = SMEM;
+    static constexpr int QSTAGE_OFF = R::SMEM;
     static constexpr int QSTAGE_WAVE = KD * 1024 + 256;
-    static constexpr int QSTAGE_BYTES = ASYNC_Q ? NWAVE * QSTAGE_WAVE : 0;
+    static constexpr int QSTAGE_BYTES = ASYNC_Q ? R::NWAVE * QSTAGE_WAVE : 0;
     // GATHER (bp_sense_mix_gather): the content rows are rows of a TABLE (one per token id), picked by an index per key.
     // The job's row indices live behind the staging area as u16: 8 KB = 4096 keys (= kMixGatherMaxKeys, bp_kernels.h), tables
     // of up to 65 536 rows (= kMixGatherMaxRows: any GPT-2 vocabulary); the byte offset row * row bytes is formed per piece.
     // (A u16 / u32 switch per launch costs the d_k = 48 instantiation five spilled registers: larger tables are gathered by
     // the caller, bp_hip.sense_mix_gather_supported.)
-    static constexpr int GATHER_OFF = SMEM + QSTAGE_BYTES;
+    static constexpr int GATHER_OFF = R::SMEM + QSTAGE_BYTES;
     static constexpr int GATHER_BYTES = 8192;
-    static constexpr int LDS_BYTES = SMEM + QSTAGE_BYTES;
+    static constexpr int LDS_BYTES = R::SMEM + QSTAGE_BYTES;
     static_assert(LDS_BYTES + GATHER_BYTES <= 160 * 1024, "LDS budget");
 };
 
@@ -96,64 +85,17 @@ __global__ __launch_bounds__(512) void sense_mix_dma_kernel(const MixParams p) {
     const float c2 = p.scale_log2e;
     const uint32_t lds0 = lds_base_addr(smem);
 
-    // lane-constant LDS read offsets
-    int k_read_off[KD];   // K fragment (A operand of S^T): row l31 (+32*kk), logical slot 2*s + hh
-#pragma unroll
-    for (int s = 0; s < KD; ++s)
-        k_read_off[s] = l31 * C::KROW + (((2 * s + hh) ^ k_swz<C::KROW>(l31)) * 16);
-    // (k_swz only looks at row bits 0..3, so +32 rows keeps the same swizzle)
-    const int c_row_lane = 4 * hh + ((lane & 15) >> 2);
-    const int c_ch_lane = ((lane >> 4) & 1) * 2 + ((lane & 3) >> 1);
-    // C^T fragment: (row c_row_lane, 16-col group of block n), +8 rows keeps swizzle.  The swizzle XORs the 64-B chunk
-    // index n with row & 3, i.e. only its low two bits: block n + 4 sits exactly 256 bytes after block n, so four
-    // lane offsets + an immediate serve the eight blocks.
-    static_assert(C::NB == 8, "c_read_off assumes 8 column blocks");
-    int c_read_off[4];
-#pragma unroll
-    for (int n = 0; n < 4; ++n) c_read_off[n] = v_lds_off<C::NB>(c_row_lane, n * 4 + c_ch_lane) + (lane & 1) * 8;
-
-    // ---- job queues -------------------------------------------------------------------------------------
-    MixQueues *queues = p.queues;
-    uint32_t exhausted = 0;   // bit q: queue q has no jobs left (wave-uniform, only thread 0 uses it)
-    const int my_xcd = blockIdx.x & 7;
-    auto next_job = [&]() -> int {   // thread 0 only; returns grp * 256 + qt, or -1
-        for (int t = 0; t < 8; ++t) {
-            const int q = (my_xcd + t) & 7;
-            if (exhausted & (1u << q)) continue;
-            const int groups = mix_queue_groups(p.b, p.n_chunks, q);
-            const int njobs = groups * p.n_qtiles;
-            const int idx = njobs > 0 ? (int)atomicAdd(&queues->ticket[q], 1u) : njobs;
-            if (idx < njobs) {
-                // all groups' heaviest tiles first (a group's tiles together, so that its C slab is re-read while it might
-                // still be cached, gained nothing: 1.32 / 1.34 ms against 1.29 / 1.28 ms at B = 64, same fetch traffic, r02_e)
-                // (sample-major order -- one sample's twelve jobs together -- fetches 4 % less and runs 2-3 % slower, r02_w)
-                // (table form, r04_ab: walking the queue column chunk by column chunk, so that the rows in flight chip-wide are
-                // one chunk's third of the table, is 1-2 % slower at B = 64 ... 2048 -- the memory-side cache does not pay it back)
-                // (a group's query tiles as consecutive tickets, profiles/r06_c_ab_mix_order_4096.jsonl, and paired tickets,
-                // profiles/r06_t_ab_mix_paired_tickets_*.txt, were measured and not adopted)
-                const int slot = idx / groups;
-                const int grp = mix_queue_group(p.n_chunks, q, idx - slot * groups);
-                return grp * 256 + (p.n_qtiles - 1 - slot);
-            }
-            exhausted |= 1u << q;
-        }
-        return -1;
-    };
+    const MixTileReader<C> rd(lane);
+    uint32_t exhausted = 0;   // job queues with no jobs left (mix_take_job)
 
 #ifdef BP_MIX_PROFILE
     unsigned long long prof[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
-    for (;;) {
-        __syncthreads();   // every wave is done with the previous job's ring (and has read its job word)
-        if (tid == 0) *reinterpret_cast<int *>(smem + C::JOB_OFF) = next_job();
-        __syncthreads();
-        const int job = __builtin_amdgcn_readfirstlane(*reinterpret_cast<const int *>(smem + C::JOB_OFF));
-        if (job < 0) break;
-        const int grp = job >> 8, qt = job & 255;
+    for (int word; (word = mix_take_job<C>(smem, p.queues, exhausted, p.b, p.n_chunks, p.n_qtiles)) >= 0;) {
+        const MixJob job = mix_decode_job<C>(word, p.n_chunks);
+        const int batch = job.batch, col_base = job.col_base;
+        const int qt = p.n_qtiles - 1 - job.rank;   // heaviest query tiles (the last ones) first
         MIX_TICK(job_t0);
-        const int batch = grp / p.n_chunks;
-        const int chunk = grp - batch * p.n_chunks;
-        const int col_base = chunk * C::BNC;
 
         const uint16_t *qg = reinterpret_cast<const uint16_t *>(p.q) + batch * p.qk_bs;
         const uint16_t *kg = reinterpret_cast<const uint16_t *>(p.k) + batch * p.qk_bs;
@@ -161,7 +103,6 @@ __global__ __launch_bounds__(512) void sense_mix_dma_kernel(const MixParams p) {
 
         const int k_end = min(S, qt * C::BM + C::BM);
         const int nkb = (k_end + C::BK - 1) / C::BK;
-        const int nsteps = p.nsenses * nkb;
         // key tiles below this index are full and entirely visible to every row of the workgroup
         const int nkb_clean = WEIGHTED ? 0 : min((qt * C::BM) / C::BK, S / C::BK);
 
@@ -172,35 +113,11 @@ __global__ __launch_bounds__(512) void sense_mix_dma_kernel(const MixParams p) {
         const int my_diag_sub = q0 >> 5;   // index of the 32-key sub-block that holds my diagonal
         const int nb_live = FULL ? C::NB : min(C::NB, (p.dout - col_base + 31) / 32);
 
-        // Per-lane byte offsets of my DMA pieces inside a tile (the scalar tile base is added by the DMA instruction).
-        // K piece j of this wave: rows (wave*K_DMA + j)*RPD + lane/KSLOTS, stored slot lane%KSLOTS; C piece j: rows
-        // (wave*C_DMA + j)*2 + lane/32, stored chunk lane%32.  They are rebuilt PER JOB from an opaque copy of the lane
-        // index: as loop invariants hipcc hoists the row / column tables to kernel entry and keeps them alive across
-        // the whole job loop -- ten registers that the d_k = 48 instantiation then spilled to scratch (round-3 review).
-        // The job's only possible partial tile (the last one, when the sequence ends inside it) clamps its rows to the
-        // final valid key inside issue(), in a cold branch, instead of carrying a second offset set.
-        int lane_o = lane;
-        asm volatile("" : "+v"(lane_o));
-        const int kb_partial = (k_end == S && (S % C::BK) != 0) ? nkb - 1 : -1;
-        const int last_row = S - 1 - (nkb - 1) * C::BK;
-        auto k_piece_row = [&](int j) { return (wave * C::K_DMA + j) * C::K_ROWS_PER_DMA + lane_o / C::KSLOTS; };
-        auto c_piece_row = [&](int j) { return (wave * C::C_DMA + j) * 2 + (lane_o >> 5); };
-        uint32_t k_voff[C::K_DMA], c_voff[C::C_DMA];
-#pragma unroll
-        for (int j = 0; j < C::K_DMA; ++j) {
-            const int row = k_piece_row(j);
-            const int logical = (lane_o % C::KSLOTS) ^ k_swz<C::KROW>(row);
-            const int col = logical * 8 < p.dk ? logical * 8 : 0;   // pad slot: a duplicate of column 0 (finite)
-            k_voff[j] = (uint32_t)(row * p.qk_rs + col) * 2u;
-        }
-#pragma unroll
-        for (int j = 0; j < C::C_DMA; ++j) {
-            const int row = c_piece_row(j);
-            const int stored = lane_o & 31;
-            const int logical = (((stored >> 2) ^ (row & 3)) << 2) | (stored & 3);
-            const int col = (FULL || col_base + logical * 8 < p.dout) ? col_base + logical * 8 : col_base;
-            c_voff[j] = (uint32_t)((GATHER ? 0 : row * p.c_rs) + col) * 2u;   // (GATHER: the row part comes from the table)
-        }
+        // the DMA side of the job (mix_ring.h): key tiles [0, nkb) of every sense
+        MixStream<C> ring;
+        ring.begin_job(lds0, wave, lane, S, p.nsenses, 0, k_end, kg, p.qk_rs, p.qk_ss, p.dk, cg, p.c_rs, p.c_ss);
+        uint32_t c_voff[C::B_DMA];
+        ring.template b_offsets<FULL>(c_voff, GATHER ? 0 : p.c_rs, col_base, p.dout);   // (GATHER: the row part comes from the table)
         if (GATHER) {
             // table row of every key of the job, clamped past the sequence end (those keys are masked) and to the table
             // (an index outside it reads its last row, never memory outside it); every wave is done with the previous
@@ -213,60 +130,25 @@ __global__ __launch_bounds__(512) void sense_mix_dma_kernel(const MixParams p) {
             __syncthreads();
         }
 
-        // DMA pieces of the tile two steps ahead, (l2, kb2), into ring slot `slot`; `pieces` selects a subset (bit j).
-        // The tile's base pointers kt2 / ct2 are carried and advanced on the scalar unit once per step (advance2 below):
-        // recomputing them from (l, kb) in each of a step's calls cost ~120 SALU instructions per step.
-        int l2 = 0, kb2 = 0;                     // (sense, tile) of step + 2
-        const uint16_t *ks2 = kg, *cs2 = cg;     // key / content base of sense l2
-        const uint16_t *kt2 = kg, *ct2 = cg;     // ... of tile kb2 in it
-        const int64_t k_tile_step = (int64_t)C::BK * p.qk_rs, c_tile_step = (int64_t)C::BK * p.c_rs;
-        // GATHER: piece j of tile kb2 = two table rows, their indices read from the job's LDS table; the base is the
+        // GATHER: B piece j of tile ring.t2 = two table rows, their indices read from the job's LDS table; the base is the
         // SENSE's (table + l2 * c_ss), and table rows are re-read by other jobs, so the loads stay cacheable
         const uint32_t gather_row_bytes = (uint32_t)p.c_rs * 2u;
         auto gather_piece = [&](int j, uint32_t lds_dst) {
-            const int key = kb2 * C::BK + c_piece_row(j);
+            const int key = ring.t2 * C::BK + ring.b_piece_row(j);
             const uint32_t row = *reinterpret_cast<const uint16_t *>(smem + C::GATHER_OFF + key * 2);
-            dma16_s(cs2, row * gather_row_bytes + c_voff[j], lds_dst);
+            dma16_s(ring.bs2, row * gather_row_bytes + c_voff[j], lds_dst);
         };
-        auto issue = [&](int, int, int slot, uint32_t pieces) {
-            const uint32_t stage_off = lds0 + slot * C::STAGE;
-            if (__builtin_expect(kb2 == kb_partial, 0)) {
-#pragma unroll
-                for (int j = 0; j < C::K_DMA; ++j)
-                    if ((pieces >> j) & 1u) {
-                        const uint32_t back = (uint32_t)(max(k_piece_row(j) - last_row, 0) * p.qk_rs) * 2u;
-                        dma16_s(kt2, k_voff[j] - back, __builtin_amdgcn_readfirstlane(stage_off + (wave * C::K_DMA + j) * 1024));
-                    }
-#pragma unroll
-                for (int j = 0; j < C::C_DMA; ++j)
-                    if ((pieces >> (C::K_DMA + j)) & 1u) {
-                        if (GATHER) {
-                            gather_piece(j, __builtin_amdgcn_readfirstlane(stage_off + C::KTILE + (wave * C::C_DMA + j) * 1024));
-                            continue;
-                        }
-                        const uint32_t back = (uint32_t)(max(c_piece_row(j) - last_row, 0) * p.c_rs) * 2u;
-                        dma16_s_nt(ct2, c_voff[j] - back,
-                                   __builtin_amdgcn_readfirstlane(stage_off + C::KTILE + (wave * C::C_DMA + j) * 1024));
-                    }
-            } else {
-#pragma unroll
-                for (int j = 0; j < C::K_DMA; ++j)
-                    if ((pieces >> j) & 1u) dma16_s(kt2, k_voff[j], stage_off + (wave * C::K_DMA + j) * 1024);
-#pragma unroll
-                for (int j = 0; j < C::C_DMA; ++j)
-                    if ((pieces >> (C::K_DMA + j)) & 1u) {
-                        if (GATHER) gather_piece(j, stage_off + C::KTILE + (wave * C::C_DMA + j) * 1024);
-                        // the content stream is read once per job: non-temporal (-1.6 % at B=64, r02_p)
-                        else dma16_s_nt(ct2, c_voff[j], stage_off + C::KTILE + (wave * C::C_DMA + j) * 1024);
-                    }
-            }
-            if (WEIGHTED && ((pieces >> (C::K_DMA + C::C_DMA)) & 1u)) {
-                // key weights of this (sense, tile): lane i fetches w[key0 + i] into the wave's own 256-B slot
-                const float *src = p.kw + batch * p.kw_bs + (int64_t)l2 * p.kw_ss + min(kb2 * C::BK + lane, S - 1);
-                dma4(src, stage_off + C::KTILE + C::CTILE + wave * 256);
-            }
+        auto issue = [&](int slot, uint32_t pieces) {
+            ring.issue(
+                slot, pieces,
+                [&](int j, int back, uint32_t lds_dst) {
+                    if (GATHER) gather_piece(j, lds_dst);
+                    // the content stream is read once per job: non-temporal (-1.6 % at B=64, r02_p)
+                    else dma16_s_nt(ring.bt2, c_voff[j] - (uint32_t)(back * p.c_rs) * 2u, lds_dst);
+                },
+                [&](int l) { return p.kw + batch * p.kw_bs + (int64_t)l * p.kw_ss; });   // key weights w[b, l, :]
         };
-        constexpr uint32_t kAllPieces = (1u << C::DMA_PER_STAGE) - 1u;
+        constexpr uint32_t kAllPieces = C::ALL_PIECES;
 
         f32x16 acc[C::NB];
 #pragma unroll
@@ -319,47 +201,13 @@ __global__ __launch_bounds__(512) void sense_mix_dma_kernel(const MixParams p) {
             lse2 = *reinterpret_cast<const float *>(smem + qstage + KD * 1024 + lane * 4) * kLog2e;
         };
 
-        // S^T of the 32-key half kk of the tile in ring slot byte offset `stage`
-        auto scores = [&](int stage, int kk) {
-            f32x16 st;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) st[r] = 0.f;
-#pragma unroll
-            for (int s = 0; s < KD; ++s) {
-                const u32x4 a = lds_read_16B(smem, k_read_off[s] + stage + kk * 32 * C::KROW);
-                st = E::mfma(a, qf[s], st);
-            }
-            return st;
-        };
         auto exponentiate = [&](f32x16 &st) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) st[r] = fast_exp2(fmaf(st[r], c2, -lse2));
         };
-        auto pack = [&](const f32x16 &st, u32x4 (&pf)[2]) {
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) pf[ks][i] = E::pack2(st[ks * 8 + 2 * i], st[ks * 8 + 2 * i + 1]);
-        };
-        // C^T operand of column block n at LDS byte offset `rows` (16 keys x 256 columns)
-        auto c_operand = [&](int rows, int n) {
-            const u32x2 lo = lds_read_tr16_8B(smem, c_read_off[n & 3] + (n >> 2) * 256 + rows);
-            const u32x2 hi = lds_read_tr16_8B(smem, c_read_off[n & 3] + (n >> 2) * 256 + rows + 8 * C::CROW);
-            return u32x4{lo[0], lo[1], hi[0], hi[1]};
-        };
-        // O^T += C^T P^T over N consecutive 16-key steps (pk[0..N-1]) from key row `row0` of the tile at `stage`: 8 N MFMAs
-        // as ONE operand stream with the C^T operand of MFMA i + 2 requested before MFMA i issues (mfma_stream,
-        // bp_common.h) -- hipcc on its own puts "2 ds_read, s_waitcnt lgkmcnt(0)" in front of every MFMA: 75-85 clocks
-        // per MFMA where the pipe needs 32 (r03_aa/ab timelines).  `mid(i)` runs behind MFMA i (DMA issue points).
+        // O^T += C^T P^T over the 16-key steps pk[] from key row `row0` of the tile at `stage` (one operand stream)
         auto pv_stream = [&](int stage, int row0, const auto &pk, auto &&mid) {
-            constexpr int N = sizeof(pk) / sizeof(pk[0]) * C::NB;
-            const int base = stage + C::KTILE + row0 * C::CROW;
-            mfma_stream<N>([&](int i) { return c_operand(base + (i >> 3) * 16 * C::CROW, i & 7); },
-                           [&](int i, const u32x4 &a) {
-                               if (FULL || (i & 7) < nb_live) acc[i & 7] = E::mfma(a, pk[i >> 3], acc[i & 7]);
-                               asm volatile("" : "+v"(acc[i & 7]));
-                               mid(i);
-                           });
+            mix_pv_stream<E, C, FULL>(smem, rd, acc, nb_live, stage, row0, pk, mid);
         };
 
         // Causal mask of one 32-key half on its packed P^T words.  `rel` = the half's sub-block index minus the index of
@@ -394,7 +242,7 @@ __global__ __launch_bounds__(512) void sense_mix_dma_kernel(const MixParams p) {
         u32x4 pfc[3];   // P^T of half 0 keys 16..31, of half 1 keys 0..15 and 16..31
         auto step_x = [&](int stage, int kb, int slot2, bool dma, bool live, bool edge) {
             if (!live) {
-                if (dma) issue(0, 0, slot2, kAllPieces);
+                if (dma) issue(slot2, kAllPieces);
                 return;
             }
             // X is one dependent chain (S^T -> softmax -> first MFMAs), Y a stream of independent MFMAs: without a
@@ -402,49 +250,18 @@ __global__ __launch_bounds__(512) void sense_mix_dma_kernel(const MixParams p) {
             // clocks against 1360 the other way round, r03_ab timeline)
             __builtin_amdgcn_s_setprio(3);
             f32x16 st0, st1;
-            {
-                // S^T of both key halves as one operand stream, alternating accumulators (the per-half form waits for
-                // an LDS round trip in front of each of its KD dependent MFMAs: ~600 clocks for the six of d_k = 48)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) st0[r] = st1[r] = 0.f;
-                mfma_stream<2 * KD>(
-                    [&](int i) { return lds_read_16B(smem, k_read_off[i >> 1] + stage + (i & 1) * 32 * C::KROW); },
-                    [&](int i, const u32x4 &a) {
-                        if (i & 1) { st1 = E::mfma(a, qf[i >> 1], st1); asm volatile("" : "+v"(st1)); }
-                        else { st0 = E::mfma(a, qf[i >> 1], st0); asm volatile("" : "+v"(st0)); }
-                    });
-            }
+            mix_scores_both<E, C>(smem, rd, stage, qf, st0, st1);   // S^T of both key halves as one operand stream
             u32x4 pf0[2];
             exponentiate(st0);
-            pack(st0, pf0);
+            mix_pack<E>(st0, pf0);
             if (edge) mask_half(pf0, 2 * kb - my_diag_sub);
-            if (dma) issue(0, 0, slot2, 0x03u);
-            // 8 MFMAs of half 0, keys 0..15, each followed by 2 fma + 2 exp of half 1; the C operand of MFMA n+1 is
-            // requested before MFMA n issues, so the LDS latency hides behind a full MFMA
-            {
-                const int rows = stage + C::KTILE;
-                u32x4 a = c_operand(rows, 0);
-#pragma unroll
-                for (int n = 0; n < C::NB; ++n) {
-                    u32x4 a_next = a;
-                    if (n + 1 < C::NB) a_next = c_operand(rows, n + 1);
-                    asm volatile("" : "+v"(a));
-                    if (FULL || n < nb_live) acc[n] = E::mfma(a, pf0[0], acc[n]);   // (partial last column chunk: d = 640, 384, ...)
-                    asm volatile("" : "+v"(acc[n]));
-                    float x0 = st1[2 * n], x1 = st1[2 * n + 1];
-                    asm volatile("" : "+v"(x0), "+v"(x1));
-                    x0 = fast_exp2(fmaf(x0, c2, -lse2));
-                    x1 = fast_exp2(fmaf(x1, c2, -lse2));
-                    asm volatile("" : "+v"(x0), "+v"(x1));
-                    st1[2 * n] = x0;
-                    st1[2 * n + 1] = x1;
-                    a = a_next;
-                }
-            }
-            if (dma) issue(0, 0, slot2, kAllPieces & ~0x03u);
+            if (dma) issue(slot2, 0x03u);
+            // 8 MFMAs of half 0, keys 0..15, with the exponentials of half 1 between them (one lse per lane: my query's)
+            mix_x_block<E, C, FULL>(smem, rd, acc, nb_live, stage, pf0[0], st1, c2, [&](int) { return lse2; });
+            if (dma) issue(slot2, kAllPieces & ~0x03u);
             pfc[0] = pf0[1];
             u32x4 pf1[2];
-            pack(st1, pf1);
+            mix_pack<E>(st1, pf1);
             if (edge) mask_half(pf1, 2 * kb + 1 - my_diag_sub);
             pfc[1] = pf1[0];
             pfc[2] = pf1[1];
@@ -453,30 +270,30 @@ __global__ __launch_bounds__(512) void sense_mix_dma_kernel(const MixParams p) {
         };
         auto step_y = [&](int stage, int slot2, bool dma, bool live) {
             if (!live) {
-                if (dma) issue(0, 0, slot2, kAllPieces);
+                if (dma) issue(slot2, kAllPieces);
                 return;
             }
-            if (dma) issue(0, 0, slot2, 0x03u);
+            if (dma) issue(slot2, 0x03u);
             pv_stream(stage, 16, pfc, [&](int i) {
-                if (i == 11 && dma) issue(0, 0, slot2, kAllPieces & ~0x03u);
+                if (i == 11 && dma) issue(slot2, kAllPieces & ~0x03u);
             });
         };
 
         // ---- key-weighted launches (the intervention hook): every step in the simple one-phase per-half form
         auto weighted_step = [&](int stage, int l, int kb, int slot2) {
-            issue(0, 0, slot2, 0x01u);
+            issue(slot2, 0x01u);
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) {
                 const int sub = kb * 2 + kk;
                 const bool live = wave_has_rows && sub <= my_diag_sub;
                 u32x4 pf[2];
                 if (live) {
-                    f32x16 st = scores(stage, kk);
+                    f32x16 st = mix_scores<E, C>(smem, rd, stage, kk, qf);
                     exponentiate(st);
                     if (WEIGHTED) {
                         // alpha[b, l, :, key] *= w[b, l, key]  (register r holds key (r & 3) + 8 (r >> 2) + 4 hh of the
                         // sub-block: four runs of four consecutive keys)
-                        const int wbase = stage + C::KTILE + C::CTILE + wave * 256 + (kk * 32 + 4 * hh) * 4;
+                        const int wbase = stage + C::AUX_OFF + wave * 256 + (kk * 32 + 4 * hh) * 4;
 #pragma unroll
                         for (int g = 0; g < 4; ++g) {
                             const u32x4 w4 = lds_read_16B(smem, wbase + g * 32);
@@ -487,55 +304,26 @@ __global__ __launch_bounds__(512) void sense_mix_dma_kernel(const MixParams p) {
                             }
                         }
                     }
-                    pack(st, pf);
+                    mix_pack<E>(st, pf);
                     mask_half(pf, sub - my_diag_sub);
                     pv_stream(stage, kk * 32, pf, [](int) {});
                 }
-                issue(0, 0, slot2, kk == 0 ? 0x0eu : (kAllPieces & ~0x0fu));
+                issue(slot2, kk == 0 ? 0x0eu : (kAllPieces & ~0x0fu));
             }
         };
 
         // ---- pipeline: two tiles in flight ---------------------------------------------------------------
-        // step -> (sense, key tile); a step past the end re-fetches the last tile (harmless, keeps every wave's
-        // DMA count per step constant so the counted wait below never changes).  The clean and the edge steps
-        // of a sense run in two consecutive loops, each with ONE body: the accumulators then never meet at an
-        // if/else join (hipcc answers such a join of 128 registers with copies and spills).
-        auto advance2 = [&]() {
-            if (kb2 + 1 < nkb) {
-                ++kb2;
-                kt2 += k_tile_step;
-                ct2 += c_tile_step;
-            } else if (l2 + 1 < p.nsenses) {
-                ++l2;
-                kb2 = 0;
-                ks2 += p.qk_ss;
-                cs2 += p.c_ss;
-                kt2 = ks2;
-                ct2 = cs2;
-            }
-        };
-        issue(0, 0, 0, kAllPieces);
-        advance2();
-        issue(l2, kb2, 1, kAllPieces);
-        advance2();
-
-        int slot = 0;                            // ring slot of the current step
-        auto step_begin = [&]() {
-            wait_vmcnt<C::DMA_PER_STAGE>();   // my share of the current tile has landed (the next may be in flight)
-            __builtin_amdgcn_s_barrier();     // ... and everybody's; all waves are done reading slot (slot + 2) % 3
-        };
-        auto step_end = [&]() {
-            slot = slot == 2 ? 0 : slot + 1;
-            advance2();
-        };
+        // The clean and the edge steps of a sense run in two consecutive loops, each with ONE body: the accumulators
+        // then never meet at an if/else join (hipcc answers such a join of 128 registers with copies and spills).
+        ring.prime([&](int slot) { issue(slot, kAllPieces); });
         if (wave_has_rows) take_q(0);
         if (WEIGHTED) {
             for (int l = 0; l < p.nsenses; ++l) {
                 if (l > 0 && wave_has_rows) take_q(l);
                 for (int kb = 0; kb < nkb; ++kb) {
-                    step_begin();
-                    weighted_step(slot * C::STAGE, l, kb, slot >= 1 ? slot - 1 : 2);
-                    step_end();
+                    ring.step_begin();
+                    weighted_step(ring.stage(), l, kb, ring.refill_slot());
+                    ring.step_end();
                 }
             }
         } else {
@@ -560,38 +348,38 @@ __global__ __launch_bounds__(512) void sense_mix_dma_kernel(const MixParams p) {
                 const int next_sense = (C::ASYNC_Q && wave_has_rows && l + 1 < p.nsenses) ? l + 1 : -1;
                 if (!C::ASYNC_Q && l > 0 && wave_has_rows) take_q(l);   // (no LDS left for the staging: plain loads)
                 if (nkb_clean > 0) {
-                    if (late) step_begin();
+                    if (late) ring.step_begin();
                     for (int kb = 0; kb < nkb_clean; ++kb) {
-                        const int slot2 = slot >= 1 ? slot - 1 : 2;
+                        const int slot2 = ring.refill_slot();
                         MIX_TICK(t0);
-                        step_begin();
+                        ring.step_begin();
                         MIX_TICK(t1);
-                        step_x(slot * C::STAGE, kb, slot2, late, true, false);   // (waves without rows run on clamped operands: nothing is stored)
+                        step_x(ring.stage(), kb, slot2, late, true, false);   // (waves without rows run on clamped operands: nothing is stored)
 #ifdef BP_MIX_PROFILE
                         asm volatile("" : "+v"(acc[7]), "+v"(pfc[0]), "+v"(pfc[1]), "+v"(pfc[2]));
 #endif
                         MIX_TICK(t2);
-                        step_begin();
+                        ring.step_begin();
                         MIX_TICK(t3);
-                        step_y(slot * C::STAGE, slot2, !late, true);
+                        step_y(ring.stage(), slot2, !late, true);
 #ifdef BP_MIX_PROFILE
                         asm volatile("" : "+v"(acc[7]));
 #endif
                         MIX_TICK(t4);
                         MIX_ADD(0, t1 - t0); MIX_ADD(1, t2 - t1); MIX_ADD(2, t3 - t2); MIX_ADD(3, t4 - t3); MIX_ADD(6, 1);
-                        step_end();
+                        ring.step_end();
                     }
                     if (!late) __builtin_amdgcn_s_barrier();
                 }
                 for (int kb = nkb_clean; kb < nkb; ++kb) {   // (never empty: the diagonal tile is one of these)
                     const bool live = wave_has_rows && 2 * kb <= my_diag_sub;
-                    const int slot2 = slot >= 1 ? slot - 1 : 2;
+                    const int slot2 = ring.refill_slot();
                     MIX_TICK(e0);
-                    step_begin();
+                    ring.step_begin();
                     MIX_TICK(e1);
-                    step_x(slot * C::STAGE, kb, slot2, false, live, true);
+                    step_x(ring.stage(), kb, slot2, false, live, true);
                     if (kb == nkb - 1 && next_sense >= 0) request_q(next_sense);   // in front of the step's DMA pieces (in Y)
-                    step_y(slot * C::STAGE, slot2, true, live);
+                    step_y(ring.stage(), slot2, true, live);
 #ifdef BP_MIX_PROFILE
                     asm volatile("" : "+v"(acc[7]));
 #endif
@@ -608,7 +396,7 @@ __global__ __launch_bounds__(512) void sense_mix_dma_kernel(const MixParams p) {
                         if (live) { prof[partner_live ? 10 : 8] += e2 - e1; prof[partner_live ? 11 : 9] += 1; }
                     }
 #endif
-                    step_end();
+                    ring.step_end();
                 }
                 if (next_sense >= 0) adopt_q();
             }
@@ -617,17 +405,7 @@ __global__ __launch_bounds__(512) void sense_mix_dma_kernel(const MixParams p) {
 
         if (wave_has_rows && my_q < S) {
             uint16_t *og = reinterpret_cast<uint16_t *>(p.o) + batch * p.o_bs + (int64_t)my_q * p.o_rs;
-#pragma unroll
-            for (int n = 0; n < C::NB; ++n)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int col = col_base + n * 32 + 8 * g + 4 * hh;
-                    if (col < p.dout) {
-                        u32x2 w = {E::pack2(acc[n][4 * g + 0], acc[n][4 * g + 1]),
-                                   E::pack2(acc[n][4 * g + 2], acc[n][4 * g + 3])};
-                        *reinterpret_cast<u32x2 *>(og + col) = w;
-                    }
-                }
+            mix_store_row<E, C>(og, acc, col_base, p.dout, hh);
         }
         MIX_TICK(job_t1);
         MIX_ADD(7, job_t1 - job_t0);
@@ -685,21 +463,13 @@ extern "C" int bp_dev_mix_prof(unsigned long long *host) {
 
 // Requires: d_k % 8 == 0, d_out % 8 == 0, all bases 16-byte aligned, all strides multiples of 8, n_qtiles <= 256.
 hipError_t launch_sense_mix_dma(const MixParams &params, int dtype, hipStream_t stream) {
-    MixParams p = params;
-    const hipError_t armed = arm_mix_queues(p.queues, stream);
-    if (armed != hipSuccess) return armed;
-    const dim3 g(persistent_grid(p.b * p.n_chunks * p.n_qtiles)), t(512);   // 120 KB of LDS: one workgroup per CU
-    return with_dtype(dtype, [&](auto et) {
-        return with_kd(p.dk, [&](auto kd) {
-            return with_flag(p.dout % 256 == 0, [&](auto full) {
-                using ET = decltype(et);
-                if (p.row_index != nullptr)   // (bp_api.hip: never together with key weights)
-                    hipLaunchKernelGGL((sense_mix_dma_kernel<ET, kd, full, false, true>), g, t, 0, stream, p);
-                else if (p.kw != nullptr) hipLaunchKernelGGL((sense_mix_dma_kernel<ET, kd, full, true>), g, t, 0, stream, p);
-                else hipLaunchKernelGGL((sense_mix_dma_kernel<ET, kd, full, false>), g, t, 0, stream, p);
-                return hipGetLastError();
-            });
-        });
+    return launch_mix_persistent(params, params.n_qtiles, params.dout, dtype, stream,
+                                 [&](auto et, auto kd, auto full, dim3 g, dim3 t, const MixParams &p) {
+        using ET = decltype(et);
+        if (p.row_index != nullptr)   // (bp_api.hip: never together with key weights)
+            hipLaunchKernelGGL((sense_mix_dma_kernel<ET, kd, full, false, true>), g, t, 0, stream, p);
+        else if (p.kw != nullptr) hipLaunchKernelGGL((sense_mix_dma_kernel<ET, kd, full, true>), g, t, 0, stream, p);
+        else hipLaunchKernelGGL((sense_mix_dma_kernel<ET, kd, full, false>), g, t, 0, stream, p);
     });
 }
 
