@@ -37,6 +37,11 @@
 //   * two tile bodies per kernel, in sequential loops with one body each: the clean body (every (query, key) pair
 //     of the wave's sub-block visible, no sequence end) carries no compare or select at all; the edge body (the
 //     diagonal sub-block, the sequence's last tile) masks with selects against per-lane limits.
+// What the two kernels share has one definition each, in front of them: the front matter of a pass (BwdPass), the
+// two-tensor tile stream (BwdStream) and the ring step (ring_step), the zero fill of the ring (zero_ring), the row
+// fragment loader (load_row), the read-offset tables with the row-wise and the transposed read (BwdTileReader), the
+// epilogue (store_row) and the pairing of the causal passes (bwd_paired_passes, bwd_slots).  What differs -- the
+// sub-block bodies with their masks, the dropout expressions, the D / L handling, the clean / edge loops -- is theirs.
 #include "bp_common.h"
 #include "bp_dma.h"
 #include "bp_kernels.h"
@@ -63,8 +68,9 @@ namespace {
 // (the two passes of a paired causal workgroup chained into one tile stream, so that the ring never drains between
 // them: correct and 7 % slower, scripts/probes/flash_bwd_chain)
 
-template <int KD>
+template <int KD_>
 struct BwdCfg {
+    static constexpr int KD = KD_;
     static constexpr int NT = 256, NWAVE = 4, BT = 64;               // BT: rows of a streamed tile
     static constexpr int NSTAGE = 2;
     static constexpr int NV = (KD + 1) / 2;                          // 32-wide blocks of the head dimension
@@ -98,22 +104,124 @@ template <class C> BP_DEV const uint16_t *piece_base(const uint16_t *tile, int j
 }
 template <class C> BP_DEV int piece_lds(int wave, int j) { return (j * C::NWAVE + wave) * 1024; }
 
-// lane offsets of the two read patterns
-template <class C> BP_DEV int row_read_off(int l31, int hh, int s) {
-    return l31 * C::ROW + (((2 * s + hh) ^ bwd_swz<C::ROW>(l31)) * 16);
-}
-// transposing read of head-dim block n, rows (4 hh + quad row) + 8 h: see lds_read_tr16_8B
-template <class C> BP_DEV int tr_read_off(int lane, int n, int h) {
-    const int row = 4 * (lane >> 5) + ((lane & 15) >> 2) + 8 * h;
-    const int slot = 4 * n + ((lane >> 4) & 1) * 2 + ((lane & 3) >> 1);
-    return row * C::ROW + ((slot ^ bwd_swz<C::ROW>(row)) * 16) + (lane & 1) * 8;
-}
+// The two read patterns of an image: the lane offsets, and the reads.  `img` is the byte offset, inside the stage `st`,
+// of the first image row wanted.
+template <class C> struct BwdTileReader {
+    int r_off[C::KD];      // row-wise: row l31, logical slot 2 s + hh
+    int t_off[C::NV][2];   // transposing: head-dim block n, rows (4 hh + quad row) + 0 / + 8 (see lds_read_tr16_8B)
+
+    // lane = 32 hh + l31.  (l31 and hh arrive from the pass record and the transposing row spells `lane >> 5` out: with
+    // either formed the other way the dq dropout kernel of d = 64 takes one more register, 158)
+    BP_DEV BwdTileReader(int lane, int l31, int hh) {
+#pragma unroll
+        for (int s = 0; s < C::KD; ++s) r_off[s] = l31 * C::ROW + (((2 * s + hh) ^ bwd_swz<C::ROW>(l31)) * 16);
+#pragma unroll
+        for (int n = 0; n < C::NV; ++n)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int row = 4 * (lane >> 5) + ((lane & 15) >> 2) + 8 * h;
+                const int slot = 4 * n + ((lane >> 4) & 1) * 2 + ((lane & 3) >> 1);
+                t_off[n][h] = row * C::ROW + ((slot ^ bwd_swz<C::ROW>(row)) * 16) + (lane & 1) * 8;
+            }
+    }
+    // A operand of a product that contracts over the head dimension: 32 rows (lane = row l31), column step s
+    BP_DEV u32x4 rows(const char *st, int img, int s) const { return lds_read_16B(st, img + r_off[s]); }
+    // A operand of a product that contracts over 16 rows of the image: head-dim block n, transposed
+    BP_DEV u32x4 transposed(const char *st, int img, int n) const {
+        const u32x2 lo = lds_read_tr16_8B(st, img + t_off[n][0]);
+        const u32x2 hi = lds_read_tr16_8B(st, img + t_off[n][1]);
+        return u32x4{lo[0], lo[1], hi[0], hi[1]};
+    }
+};
 
 // wait until at most `ahead` tiles of PER DMA instructions each are still in flight (ahead: wave-uniform, 0..2)
 template <int PER> BP_DEV void ring_wait(int ahead) {
     if (ahead <= 0) wait_vmcnt<0>();
     else if (ahead == 1) wait_vmcnt<PER>();
     else wait_vmcnt<2 * PER>();
+}
+// Ring step of tile t of a sweep [t0, t_end): my share of the tile has landed (the younger tiles may still be in flight:
+// every tile costs a wave the same number of DMA instructions, so the wait is a count), everybody's after the barrier;
+// refill the slot that was read during the previous step.  Returns the slot that holds tile t.
+// The count is PER, or PER + 1 for a wave with `one_more` (wave-uniform; the statistics waves of dkdv).  (With the one
+// more as a second instantiation, called from the other arm of a branch on the wave, the dkdv kernel of d = 64 spilled
+// 4 registers instead of 2.)
+template <class C, int PER, class Issue> BP_DEV int ring_step(int t, int t0, int t_end, int one_more, Issue &&issue) {
+    const int ahead = min(t_end - 1 - t, C::NSTAGE - 2);   // tiles requested after tile t
+    if (one_more) ring_wait<PER + 1>(ahead);
+    else ring_wait<PER>(ahead);
+    __builtin_amdgcn_s_barrier();
+    if (t + C::NSTAGE - 1 < t_end) issue(t + C::NSTAGE - 1);
+    return (t - t0) % C::NSTAGE;
+}
+
+// The DMA side of a sweep: 64-row tiles of TWO tensors a and b (Q and dO, or K and V) into the images at A_OFF and B_OFF
+// of a stage.  Constant per-lane byte offsets, scalar tile pointers.
+// (the clamped offsets of the one partial tile a sweep can meet are recomputed from the lane's row in that cold step
+// instead of living in registers all along: four registers the three-waves-per-SIMD bound does not have)
+template <class C, int A_OFF, int B_OFF, bool FULLD> struct BwdStream {
+    const uint16_t *a_tile, *b_tile;   // tile of the NEXT issue
+    int64_t a_rs, b_rs;                // row strides in elements
+    int64_t a_step, b_step;            // ... and tile strides
+    uint32_t a_voff, b_voff;           // (one offset per tensor, see piece())
+    bool piece_live;
+    int t_partial, last_row;           // the partial tile (-1: none) and its last row
+
+    // a, b: row 0 of the two tensors, `nrows` rows of d columns; the sweep starts at tile t0
+    BP_DEV BwdStream(const uint16_t *a, int64_t a_rs_, const uint16_t *b, int64_t b_rs_, int t0, int nrows, int d, int wave, int lane)
+        : a_tile(a + (int64_t)t0 * C::BT * a_rs_), b_tile(b + (int64_t)t0 * C::BT * b_rs_), a_rs(a_rs_), b_rs(b_rs_) {
+        a_step = (int64_t)C::BT * a_rs, b_step = (int64_t)C::BT * b_rs;
+        t_partial = (nrows % C::BT) != 0 ? nrows / C::BT : -1;
+        last_row = nrows - 1 - (nrows / C::BT) * C::BT;
+        int row, col;
+        piece<C>(wave, lane, row, col);
+        piece_live = FULLD || col < d;
+        a_voff = (uint32_t)(row * a_rs + col) * 2u;
+        b_voff = (uint32_t)(row * b_rs + col) * 2u;
+    }
+    // my pieces of tile `tile` (the next one) into the stage at LDS address `st`: a piece j, then b piece j
+    BP_DEV void issue(uint32_t st, int tile, int wave) {
+        if (piece_live) {
+            if (__builtin_expect(tile == t_partial, 0)) {
+#pragma unroll
+                for (int j = 0; j < C::DMA; ++j) {
+                    // rows past the sequence's last one re-read it; the offset is taken from the TILE base here (from
+                    // the piece base it could come out negative, and the instruction adds it unsigned)
+                    int row, col;
+                    piece<C>(wave, lane_id_now(), row, col);
+                    row = min(row + j * C::NWAVE * C::ROWS_PER_DMA, last_row);
+                    dma16_s(a_tile, (uint32_t)(row * a_rs + col) * 2u, __builtin_amdgcn_readfirstlane(st + A_OFF + piece_lds<C>(wave, j)));
+                    dma16_s(b_tile, (uint32_t)(row * b_rs + col) * 2u, __builtin_amdgcn_readfirstlane(st + B_OFF + piece_lds<C>(wave, j)));
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < C::DMA; ++j) {
+                    dma16_s(piece_base<C>(a_tile, j, a_rs), a_voff, __builtin_amdgcn_readfirstlane(st + A_OFF + piece_lds<C>(wave, j)));
+                    dma16_s(piece_base<C>(b_tile, j, b_rs), b_voff, __builtin_amdgcn_readfirstlane(st + B_OFF + piece_lds<C>(wave, j)));
+                }
+            }
+        }
+        a_tile += a_step;
+        b_tile += b_step;
+    }
+};
+
+// pad slots of the images must read as 0 when d is not the full row (they meet zero columns of the B operands in the MFMAs)
+template <class C> BP_DEV void zero_ring(char *smem, int bytes, int tid) {
+    const u32x4 z = {0u, 0u, 0u, 0u};
+    for (int off = tid * 16; off < bytes; off += C::NT * 16) lds_write_16B(smem, off, z);
+    __syncthreads();
+}
+
+// 16-byte fragments of one row as MFMA B operands (lane = row, 8 consecutive d: columns 16 s + 8 hh ...); columns >= d: 0
+template <int KD, bool FULLD> BP_DEV void load_row(u32x4 (&f)[KD], const uint16_t *row, int hh, int d) {
+#pragma unroll
+    for (int s = 0; s < KD; ++s) {
+        const int col = 16 * s + 8 * hh;
+        u32x4 a = {0u, 0u, 0u, 0u};
+        if (FULLD || col < d) a = ld_global_16B(row + col);
+        f[s] = a;
+    }
 }
 
 // Epilogue store of one accumulator block (rows d = 32 n + 8 g + 4 hh + i, column = lane l31) as 16-byte pieces: the
@@ -168,6 +276,46 @@ BP_DEV SeqInfo seq_info(const FlashBwdParams &p, int batch) {
     return s;
 }
 
+// What a pass of either kernel starts from.
+// (the lane index is recomputed per pass, not `threadIdx.x & 63`, and the wave index arrives as a scalar: everything
+// derived from threadIdx.x would otherwise be hoisted in front of the two passes of a paired workgroup and live --
+// spilled -- across the first pass's tile loops)
+struct BwdPass : SeqInfo {
+    int lane, tid, l31, hh;               // tid = wave * 64 + lane, lane = 32 hh + l31
+    int batch, head;
+    const uint16_t *qg, *dog, *kg, *vg;   // row 0 of this (sample, head)
+};
+BP_DEV BwdPass bwd_pass(const FlashBwdParams &p, int wave, int bh) {
+    BwdPass w;
+    w.lane = lane_id_now();
+    w.tid = wave * 64 + w.lane;
+    w.l31 = w.lane & 31;
+    w.hh = w.lane >> 5;
+    w.batch = bh / p.h;
+    w.head = bh - w.batch * p.h;
+    static_cast<SeqInfo &>(w) = seq_info(p, w.batch);
+    w.qg = reinterpret_cast<const uint16_t *>(p.q) + w.q_row0 * p.q_rs + (int64_t)w.head * p.q_hs;
+    w.dog = reinterpret_cast<const uint16_t *>(p.dout) + w.q_row0 * p.do_rs + (int64_t)w.head * p.do_hs;
+    w.kg = reinterpret_cast<const uint16_t *>(p.k) + w.k_row0 * p.k_rs + (int64_t)w.head * p.k_hs;
+    w.vg = reinterpret_cast<const uint16_t *>(p.v) + w.k_row0 * p.v_rs + (int64_t)w.head * p.v_hs;
+    return w;
+}
+
+// Epilogue: this lane's row `row` of a gradient (rows of the sample from `row0`, `nrows` of them; strides in elements)
+// from the NV accumulator blocks.  Lanes past the sequence exchange, but store nothing.
+template <class E, int KD>
+BP_DEV void store_row(void *out, int64_t row0, int64_t rs, int64_t head_off, int row, int nrows,
+                      const f32x16 (&acc)[BwdCfg<KD>::NV], float scale, int hh, int d) {
+    int r = min(row, nrows - 1);
+    // (opaque here: hipcc otherwise forms the 64-bit output row pointers in front of the tile loops and carries --
+    // spills -- them across the clean loop)
+    asm volatile("" : "+v"(r));
+    uint16_t *g = reinterpret_cast<uint16_t *>(out) + (row0 + r) * rs + head_off;
+    const int d_lim = row < nrows ? d : 0;
+#pragma unroll
+    for (int n = 0; n < BwdCfg<KD>::NV; ++n) store_block16<E, (KD <= 4)>(g, acc[n], scale, n, hh, d_lim);
+}
+
 }  // namespace
 
 // statistics workspace: per (batch, head) two rows of lse_stride floats: -D, then -L / scale
@@ -197,28 +345,13 @@ BP_DEV void flash_bwd_dkdv_tile(const FlashBwdParams p, char *smem, const uint32
     using E = Elem<ET>;
     constexpr int NV = C::NV;
 
-    // (the lane index is recomputed per pass, not `threadIdx.x & 63`, and the wave index arrives as a scalar: everything
-    // derived from threadIdx.x would otherwise be hoisted in front of the two passes of a paired workgroup and live --
-    // spilled -- across the first pass's tile loops)
-    const int lane = lane_id_now();
-    const int tid = wave * 64 + lane;
-    const int l31 = lane & 31;
-    const int hh = lane >> 5;
-
-    const int batch = bh / p.h;
-    const int head = bh - batch * p.h;
-    const SeqInfo si = seq_info(p, batch);
-    const int seq_q = si.seq_q, seq_k = si.seq_k;
+    const BwdPass w = bwd_pass(p, wave, bh);
+    const int hh = w.hh, seq_q = w.seq_q, seq_k = w.seq_k;
     if (kt * 128 >= seq_k) return;
-
-    const uint16_t *qg = reinterpret_cast<const uint16_t *>(p.q) + si.q_row0 * p.q_rs + (int64_t)head * p.q_hs;
-    const uint16_t *dog = reinterpret_cast<const uint16_t *>(p.dout) + si.q_row0 * p.do_rs + (int64_t)head * p.do_hs;
-    const uint16_t *kg = reinterpret_cast<const uint16_t *>(p.k) + si.k_row0 * p.k_rs + (int64_t)head * p.k_hs;
-    const uint16_t *vg = reinterpret_cast<const uint16_t *>(p.v) + si.k_row0 * p.v_rs + (int64_t)head * p.v_hs;
-    const float *stats_g = stats_row(p, batch, head);
+    const float *stats_g = stats_row(p, w.batch, w.head);
 
     const int key0 = kt * 128 + wave * 32;        // first key of this wave
-    const int my_key = key0 + l31;
+    const int my_key = key0 + w.l31;
     const bool wave_has_keys = key0 < seq_k;
     const float c2 = p.scale * kLog2e;
 
@@ -228,8 +361,8 @@ BP_DEV void flash_bwd_dkdv_tile(const FlashBwdParams p, char *smem, const uint32
     if (qt_begin >= nqt) {
         // no query sees these keys (causal, seq_k > seq_q): their gradients are zero
         if (wave_has_keys && my_key < seq_k) {
-            uint16_t *dkg = reinterpret_cast<uint16_t *>(p.dk) + (si.k_row0 + my_key) * p.dk_rs + (int64_t)head * p.dk_hs;
-            uint16_t *dvg = reinterpret_cast<uint16_t *>(p.dv) + (si.k_row0 + my_key) * p.dv_rs + (int64_t)head * p.dv_hs;
+            uint16_t *dkg = reinterpret_cast<uint16_t *>(p.dk) + (w.k_row0 + my_key) * p.dk_rs + (int64_t)w.head * p.dk_hs;
+            uint16_t *dvg = reinterpret_cast<uint16_t *>(p.dv) + (w.k_row0 + my_key) * p.dv_rs + (int64_t)w.head * p.dv_hs;
             for (int d0 = 4 * hh; d0 < p.d; d0 += 8) {
                 *reinterpret_cast<u32x2 *>(dkg + d0) = u32x2{0u, 0u};
                 *reinterpret_cast<u32x2 *>(dvg + d0) = u32x2{0u, 0u};
@@ -238,11 +371,7 @@ BP_DEV void flash_bwd_dkdv_tile(const FlashBwdParams p, char *smem, const uint32
         return;
     }
 
-    if (!FULLD) {   // pad slots of the images must read as 0 (they meet zero K / V columns in the MFMAs)
-        const u32x4 z = {0u, 0u, 0u, 0u};
-        for (int off = tid * 16; off < G::SMEM; off += C::NT * 16) lds_write_16B(smem, off, z);
-        __syncthreads();
-    }
+    if (!FULLD) zero_ring<C>(smem, G::SMEM, w.tid);
 
     DropoutStream rng = {0u, 0u};
     if (DROP) rng = dropout_stream(p.rng_state, (uint32_t)bh);
@@ -252,72 +381,23 @@ BP_DEV void flash_bwd_dkdv_tile(const FlashBwdParams p, char *smem, const uint32
     u32x4 kf[KD], vf[KD];
     {
         const int key = min(my_key, seq_k - 1);
-#pragma unroll
-        for (int s = 0; s < KD; ++s) {
-            const int col = 16 * s + 8 * hh;
-            u32x4 a = {0u, 0u, 0u, 0u}, b = {0u, 0u, 0u, 0u};
-            if (FULLD || col < p.d) {
-                a = ld_global_16B(kg + (int64_t)key * p.k_rs + col);
-                b = ld_global_16B(vg + (int64_t)key * p.v_rs + col);
-            }
-            kf[s] = a;
-            vf[s] = b;
-        }
+        load_row<KD, FULLD>(kf, w.kg + (int64_t)key * p.k_rs, hh, p.d);
+        load_row<KD, FULLD>(vf, w.vg + (int64_t)key * p.v_rs, hh, p.d);
     }
 
-    // ---- DMA: constant per-lane byte offsets, scalar tile pointers --------------------------------------
-    const int qt_partial = (seq_q % C::BT) != 0 ? seq_q / C::BT : -1;
-    const int last_row = seq_q - 1 - (seq_q / C::BT) * C::BT;
-    // (the clamped offsets of the one partial tile a sweep can meet are recomputed from the lane's row in that cold
-    // step instead of living in registers all along: four registers the three-waves-per-SIMD bound does not have)
-    uint32_t q_voff, do_voff;
-    bool piece_live;
-    {
-        int row, col;
-        piece<C>(wave, lane, row, col);
-        piece_live = FULLD || col < p.d;
-        q_voff = (uint32_t)(row * p.q_rs + col) * 2u;
-        do_voff = (uint32_t)(row * p.do_rs + col) * 2u;
-    }
+    // ---- DMA: the Q and dO tiles, and behind them the tile's row statistics ------------------------------
+    BwdStream<C, G::Q_OFF, G::DO_OFF, FULLD> stream(w.qg, p.q_rs, w.dog, p.do_rs, qt_begin, seq_q, p.d, wave, w.lane);
     // (a scalar int, not the bool `wave < 2`: hipcc kept a per-lane copy of the bool alive across the pass -- one more spill)
     int stats_wave = 1 - (wave >> 1);
     asm volatile("" : "+s"(stats_wave));
-    const int64_t q_tile_stride = (int64_t)C::BT * p.q_rs, do_tile_stride = (int64_t)C::BT * p.do_rs;
-    const uint16_t *qt_ptr = qg + (int64_t)qt_begin * q_tile_stride;     // tile of the NEXT issue
-    const uint16_t *dot_ptr = dog + (int64_t)qt_begin * do_tile_stride;
     auto issue = [&](int qt) {
         const uint32_t st = __builtin_amdgcn_readfirstlane(lds0 + ((qt - qt_begin) % C::NSTAGE) * G::STAGE);
-        if (piece_live) {
-            if (__builtin_expect(qt == qt_partial, 0)) {
-#pragma unroll
-                for (int j = 0; j < C::DMA; ++j) {
-                    // rows past the sequence's last one re-read it; the offset is taken from the TILE base here (from
-                    // the piece base it could come out negative, and the instruction adds it unsigned)
-                    int row, col;
-                    piece<C>(wave, lane_id_now(), row, col);
-                    row = min(row + j * C::NWAVE * C::ROWS_PER_DMA, last_row);
-                    dma16_s(qt_ptr, (uint32_t)(row * p.q_rs + col) * 2u,
-                            __builtin_amdgcn_readfirstlane(st + G::Q_OFF + piece_lds<C>(wave, j)));
-                    dma16_s(dot_ptr, (uint32_t)(row * p.do_rs + col) * 2u,
-                            __builtin_amdgcn_readfirstlane(st + G::DO_OFF + piece_lds<C>(wave, j)));
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < C::DMA; ++j) {
-                    dma16_s(piece_base<C>(qt_ptr, j, p.q_rs), q_voff,
-                            __builtin_amdgcn_readfirstlane(st + G::Q_OFF + piece_lds<C>(wave, j)));
-                    dma16_s(piece_base<C>(dot_ptr, j, p.do_rs), do_voff,
-                            __builtin_amdgcn_readfirstlane(st + G::DO_OFF + piece_lds<C>(wave, j)));
-                }
-            }
-        }
+        stream.issue(st, qt, wave);
         // the tile's 64 x -D (wave 0) and 64 x -L/scale (wave 1); rows past the sequence: anything, they are masked
         if (stats_wave) {
             const float *src = stats_g + wave * p.lse_stride + min(qt * C::BT + lane_id_now(), (int)p.lse_stride - 1);
             dma4(src, st + G::D_OFF + wave * 256);
         }
-        qt_ptr += q_tile_stride;
-        dot_ptr += do_tile_stride;
     };
 
     f32x16 dk[NV], dv[NV];
@@ -326,15 +406,7 @@ BP_DEV void flash_bwd_dkdv_tile(const FlashBwdParams p, char *smem, const uint32
 #pragma unroll
         for (int r = 0; r < 16; ++r) { dk[n][r] = 0.f; dv[n][r] = 0.f; }
 
-    int r_off[KD];   // A operand rows (lane = query l31)
-#pragma unroll
-    for (int s = 0; s < KD; ++s) r_off[s] = row_read_off<C>(l31, hh, s);
-    int t_off[NV][2];   // transposing reads: head-dim block n, rows +0 / +8
-#pragma unroll
-    for (int n = 0; n < NV; ++n) {
-        t_off[n][0] = tr_read_off<C>(lane, n, 0);
-        t_off[n][1] = tr_read_off<C>(lane, n, 1);
-    }
+    const BwdTileReader<C> rd(w.lane, w.l31, hh);   // row-wise: lane = query l31
 
     // One 32-query sub-block `qb` of the tile in `st`.  EDGE: mask what is not a (query, key) pair of the problem.
     auto sub_block = [&](const char *st, int qt, int qb, auto EDGE) {
@@ -358,10 +430,8 @@ BP_DEV void flash_bwd_dkdv_tile(const FlashBwdParams p, char *smem, const uint32
         }
 #pragma unroll
         for (int s = 0; s < KD; ++s) {
-            const u32x4 a = lds_read_16B(st, G::Q_OFF + r_off[s] + qb * 32 * C::ROW);
-            s_ = E::mfma(a, kf[s], s_);
-            const u32x4 b = lds_read_16B(st, G::DO_OFF + r_off[s] + qb * 32 * C::ROW);
-            dp = E::mfma(b, vf[s], dp);
+            s_ = E::mfma(rd.rows(st, G::Q_OFF + qb * 32 * C::ROW, s), kf[s], s_);
+            dp = E::mfma(rd.rows(st, G::DO_OFF + qb * 32 * C::ROW, s), vf[s], dp);
         }
         // ---- P = exp2((S - L/scale) c), dS = P (dP - D) ----------------------------------------------------
         uint32_t keep = 0xffffu;   // bit 4g+i: query qbase + 8g + 4hh + i keeps my key
@@ -410,26 +480,14 @@ BP_DEV void flash_bwd_dkdv_tile(const FlashBwdParams p, char *smem, const uint32
             const int rows = (qb * 32 + ks * 16) * C::ROW;
 #pragma unroll
             for (int n = 0; n < NV; ++n) {
-                const u32x2 lo = lds_read_tr16_8B(st, G::DO_OFF + t_off[n][0] + rows);
-                const u32x2 hi = lds_read_tr16_8B(st, G::DO_OFF + t_off[n][1] + rows);
-                dv[n] = E::mfma(u32x4{lo[0], lo[1], hi[0], hi[1]}, pf[ks], dv[n]);
-                const u32x2 lo2 = lds_read_tr16_8B(st, G::Q_OFF + t_off[n][0] + rows);
-                const u32x2 hi2 = lds_read_tr16_8B(st, G::Q_OFF + t_off[n][1] + rows);
-                dk[n] = E::mfma(u32x4{lo2[0], lo2[1], hi2[0], hi2[1]}, dsf[ks], dk[n]);
+                dv[n] = E::mfma(rd.transposed(st, G::DO_OFF + rows, n), pf[ks], dv[n]);
+                dk[n] = E::mfma(rd.transposed(st, G::Q_OFF + rows, n), dsf[ks], dk[n]);
             }
         }
     };
 
-    // ring step: my share of tile qt has landed (the younger tiles may still be in flight: every tile costs a wave
-    // the same number of DMA instructions, so the wait is a count), everybody's after the barrier; refill the slot
-    // that was read during the previous step
     auto step_begin = [&](int qt) -> const char * {
-        const int ahead = min(nqt - 1 - qt, C::NSTAGE - 2);   // tiles requested after tile qt
-        if (stats_wave) ring_wait<2 * C::DMA + 1>(ahead);
-        else ring_wait<2 * C::DMA>(ahead);
-        __builtin_amdgcn_s_barrier();
-        if (qt + C::NSTAGE - 1 < nqt) issue(qt + C::NSTAGE - 1);
-        return smem + ((qt - qt_begin) % C::NSTAGE) * G::STAGE;
+        return smem + ring_step<C, 2 * C::DMA>(qt, qt_begin, nqt, stats_wave, issue) * G::STAGE;
     };
     // a tile near the diagonal or the sequence end: per sub-block skip / masked body
     auto edge_tile = [&](int qt) {
@@ -479,18 +537,8 @@ BP_DEV void flash_bwd_dkdv_tile(const FlashBwdParams p, char *smem, const uint32
     BWD_STAMP(1, pass, 6);   // all tiles done
 
     if (!wave_has_keys) return;
-    int key_row = min(my_key, seq_k - 1);
-    // (opaque here: hipcc otherwise forms the two 64-bit output row pointers in front of the tile loops and carries --
-    // spills -- them across the clean loop)
-    asm volatile("" : "+v"(key_row));
-    uint16_t *dkg = reinterpret_cast<uint16_t *>(p.dk) + (si.k_row0 + key_row) * p.dk_rs + (int64_t)head * p.dk_hs;
-    uint16_t *dvg = reinterpret_cast<uint16_t *>(p.dv) + (si.k_row0 + key_row) * p.dv_rs + (int64_t)head * p.dv_hs;
-    const int d_lim = my_key < seq_k ? p.d : 0;   // lanes past the sequence exchange, but store nothing
-#pragma unroll
-    for (int n = 0; n < NV; ++n) {
-        store_block16<E, (KD <= 4)>(dkg, dk[n], p.scale, n, hh, d_lim);
-        store_block16<E, (KD <= 4)>(dvg, dv[n], 1.f, n, hh, d_lim);
-    }
+    store_row<E, KD>(p.dk, w.k_row0, p.dk_rs, (int64_t)w.head * p.dk_hs, my_key, seq_k, dk, p.scale, hh, p.d);
+    store_row<E, KD>(p.dv, w.k_row0, p.dv_rs, (int64_t)w.head * p.dv_hs, my_key, seq_k, dv, 1.f, hh, p.d);
     BWD_STAMP(1, pass, 7);   // stores issued
 }
 
@@ -508,39 +556,20 @@ BP_DEV void flash_bwd_dq_tile(const FlashBwdParams p, char *smem, const uint32_t
     // stage = K image | V image
     constexpr int K_OFF = 0, V_OFF = C::TILE, STAGE = 2 * C::TILE;
 
-    // (the lane index is recomputed per pass, not `threadIdx.x & 63`, and the wave index arrives as a scalar: everything
-    // derived from threadIdx.x would otherwise be hoisted in front of the two passes of a paired workgroup and live --
-    // spilled -- across the first pass's tile loops)
-    const int lane = lane_id_now();
-    const int tid = wave * 64 + lane;
-    const int l31 = lane & 31;
-    const int hh = lane >> 5;
-
-    const int batch = bh / p.h;
-    const int head = bh - batch * p.h;
-    const SeqInfo si = seq_info(p, batch);
-    const int seq_q = si.seq_q, seq_k = si.seq_k;
+    const BwdPass w = bwd_pass(p, wave, bh);
+    const int hh = w.hh, seq_q = w.seq_q, seq_k = w.seq_k;
     if (qt * 128 >= seq_q) return;
-
-    const uint16_t *qg = reinterpret_cast<const uint16_t *>(p.q) + si.q_row0 * p.q_rs + (int64_t)head * p.q_hs;
-    const uint16_t *dog = reinterpret_cast<const uint16_t *>(p.dout) + si.q_row0 * p.do_rs + (int64_t)head * p.do_hs;
-    const uint16_t *kg = reinterpret_cast<const uint16_t *>(p.k) + si.k_row0 * p.k_rs + (int64_t)head * p.k_hs;
-    const uint16_t *vg = reinterpret_cast<const uint16_t *>(p.v) + si.k_row0 * p.v_rs + (int64_t)head * p.v_hs;
 
     int k_end = seq_k;
     if (p.causal) k_end = min(seq_k, qt * 128 + 128);
     const int nkb = (k_end + C::BT - 1) / C::BT;
 
     const int q0 = qt * 128 + wave * 32;
-    const int my_q = q0 + l31;
+    const int my_q = q0 + w.l31;
     const bool wave_has_rows = q0 < seq_q;
     const float c2 = p.scale * kLog2e;
 
-    if (!FULLD) {
-        const u32x4 z = {0u, 0u, 0u, 0u};
-        for (int off = tid * 16; off < C::NSTAGE * STAGE; off += C::NT * 16) lds_write_16B(smem, off, z);
-        __syncthreads();
-    }
+    if (!FULLD) zero_ring<C>(smem, C::NSTAGE * STAGE, w.tid);
 
     DropoutStream rng = {0u, 0u};
     if (DROP) rng = dropout_stream(p.rng_state, (uint32_t)bh);
@@ -550,21 +579,10 @@ BP_DEV void flash_bwd_dq_tile(const FlashBwdParams p, char *smem, const uint32_t
     float lse_row;
     {
         const int q = min(my_q, seq_q - 1);
-        const uint16_t *og = reinterpret_cast<const uint16_t *>(p.out) + (si.q_row0 + q) * p.o_rs + (int64_t)head * p.o_hs;
-#pragma unroll
-        for (int s = 0; s < KD; ++s) {
-            const int col = 16 * s + 8 * hh;
-            u32x4 a = {0u, 0u, 0u, 0u}, b = {0u, 0u, 0u, 0u}, o = {0u, 0u, 0u, 0u};
-            if (FULLD || col < p.d) {
-                a = ld_global_16B(qg + (int64_t)q * p.q_rs + col);
-                b = ld_global_16B(dog + (int64_t)q * p.do_rs + col);
-                o = ld_global_16B(og + col);
-            }
-            qf[s] = a;
-            dof[s] = b;
-            of[s] = o;
-        }
-        lse_row = p.lse[((int64_t)batch * p.h + head) * p.lse_stride + q];
+        load_row<KD, FULLD>(qf, w.qg + (int64_t)q * p.q_rs, hh, p.d);
+        load_row<KD, FULLD>(dof, w.dog + (int64_t)q * p.do_rs, hh, p.d);
+        load_row<KD, FULLD>(of, reinterpret_cast<const uint16_t *>(p.out) + (w.q_row0 + q) * p.o_rs + (int64_t)w.head * p.o_hs, hh, p.d);
+        lse_row = p.lse[((int64_t)w.batch * p.h + w.head) * p.lse_stride + q];
     }
     // row constants, filled in behind the first DMA issue (below): -L / scale, -D of my row; -D as the MFMA C operand
     // of the first K-step of every dP chain (never written: the chains start from it); -L is a per-lane scalar here
@@ -572,47 +590,9 @@ BP_DEV void flash_bwd_dq_tile(const FlashBwdParams p, char *smem, const uint32_t
     float lneg = 0.f, dneg = 0.f, lneg2 = 0.f;
     f32x16 c_d;
 
-    // ---- DMA -----------------------------------------------------------------------------------------------
-    const int kb_partial = (seq_k % C::BT) != 0 ? seq_k / C::BT : -1;
-    const int last_row = seq_k - 1 - (seq_k / C::BT) * C::BT;
-    uint32_t k_voff, v_voff;   // (one offset per tensor, see piece(); partial tile: clamped in its own cold step)
-    bool piece_live;
-    {
-        int row, col;
-        piece<C>(wave, lane, row, col);
-        piece_live = FULLD || col < p.d;
-        k_voff = (uint32_t)(row * p.k_rs + col) * 2u;
-        v_voff = (uint32_t)(row * p.v_rs + col) * 2u;
-    }
-    const int64_t k_tile_stride = (int64_t)C::BT * p.k_rs, v_tile_stride = (int64_t)C::BT * p.v_rs;
-    const uint16_t *kt_ptr = kg, *vt_ptr = vg;
-    auto issue = [&](int kb) {
-        const uint32_t st = __builtin_amdgcn_readfirstlane(lds0 + (kb % C::NSTAGE) * STAGE);
-        if (piece_live) {
-            if (__builtin_expect(kb == kb_partial, 0)) {
-#pragma unroll
-                for (int j = 0; j < C::DMA; ++j) {
-                    int row, col;   // (offset from the TILE base, see the dK/dV kernel)
-                    piece<C>(wave, lane_id_now(), row, col);
-                    row = min(row + j * C::NWAVE * C::ROWS_PER_DMA, last_row);
-                    dma16_s(kt_ptr, (uint32_t)(row * p.k_rs + col) * 2u,
-                            __builtin_amdgcn_readfirstlane(st + K_OFF + piece_lds<C>(wave, j)));
-                    dma16_s(vt_ptr, (uint32_t)(row * p.v_rs + col) * 2u,
-                            __builtin_amdgcn_readfirstlane(st + V_OFF + piece_lds<C>(wave, j)));
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < C::DMA; ++j) {
-                    dma16_s(piece_base<C>(kt_ptr, j, p.k_rs), k_voff,
-                            __builtin_amdgcn_readfirstlane(st + K_OFF + piece_lds<C>(wave, j)));
-                    dma16_s(piece_base<C>(vt_ptr, j, p.v_rs), v_voff,
-                            __builtin_amdgcn_readfirstlane(st + V_OFF + piece_lds<C>(wave, j)));
-                }
-            }
-        }
-        kt_ptr += k_tile_stride;
-        vt_ptr += v_tile_stride;
-    };
+    // ---- DMA: the K and V tiles, from tile 0 ---------------------------------------------------------------
+    BwdStream<C, K_OFF, V_OFF, FULLD> stream(w.kg, p.k_rs, w.vg, p.v_rs, 0, seq_k, p.d, wave, w.lane);
+    auto issue = [&](int kb) { stream.issue(__builtin_amdgcn_readfirstlane(lds0 + (kb % C::NSTAGE) * STAGE), kb, wave); };
 
     f32x16 dq[NV];
 #pragma unroll
@@ -620,15 +600,7 @@ BP_DEV void flash_bwd_dq_tile(const FlashBwdParams p, char *smem, const uint32_t
 #pragma unroll
         for (int r = 0; r < 16; ++r) dq[n][r] = 0.f;
 
-    int r_off[KD];
-#pragma unroll
-    for (int s = 0; s < KD; ++s) r_off[s] = row_read_off<C>(l31, hh, s);
-    int t_off[NV][2];
-#pragma unroll
-    for (int n = 0; n < NV; ++n) {
-        t_off[n][0] = tr_read_off<C>(lane, n, 0);
-        t_off[n][1] = tr_read_off<C>(lane, n, 1);
-    }
+    const BwdTileReader<C> rd(w.lane, w.l31, hh);   // row-wise: lane = key l31
 
     // one 32-key sub-block kk of the tile in `st`
     auto sub_block = [&](const char *st, int kb, int kk, auto EDGE) {
@@ -640,10 +612,8 @@ BP_DEV void flash_bwd_dq_tile(const FlashBwdParams p, char *smem, const uint32_t
         for (int r = 0; r < 16; ++r) st_[r] = 0.f;
 #pragma unroll
         for (int s = 0; s < KD; ++s) {
-            const u32x4 a = lds_read_16B(st, K_OFF + r_off[s] + kk * 32 * C::ROW);
-            st_ = E::mfma(a, qf[s], st_);
-            const u32x4 b = lds_read_16B(st, V_OFF + r_off[s] + kk * 32 * C::ROW);
-            dpt = E::mfma(b, dof[s], dpt);
+            st_ = E::mfma(rd.rows(st, K_OFF + kk * 32 * C::ROW, s), qf[s], st_);
+            dpt = E::mfma(rd.rows(st, V_OFF + kk * 32 * C::ROW, s), dof[s], dpt);
         }
         uint32_t keep = 0xffffu;   // bit 4g+i: my query keeps key kbase + 8g + 4hh + i
         if (DROP) keep = dropout_keep_rowlane(rng, p.drop_thr, (uint32_t)my_q, (uint32_t)kbase, hh);
@@ -678,20 +648,11 @@ BP_DEV void flash_bwd_dq_tile(const FlashBwdParams p, char *smem, const uint32_t
         for (int ks = 0; ks < 2; ++ks) {
             const int rows = (kk * 32 + ks * 16) * C::ROW;
 #pragma unroll
-            for (int n = 0; n < NV; ++n) {
-                const u32x2 lo = lds_read_tr16_8B(st, K_OFF + t_off[n][0] + rows);
-                const u32x2 hi = lds_read_tr16_8B(st, K_OFF + t_off[n][1] + rows);
-                dq[n] = E::mfma(u32x4{lo[0], lo[1], hi[0], hi[1]}, dsf[ks], dq[n]);
-            }
+            for (int n = 0; n < NV; ++n) dq[n] = E::mfma(rd.transposed(st, K_OFF + rows, n), dsf[ks], dq[n]);
         }
     };
 
-    auto step_begin = [&](int kb) -> const char * {
-        ring_wait<2 * C::DMA>(min(nkb - 1 - kb, C::NSTAGE - 2));
-        __builtin_amdgcn_s_barrier();
-        if (kb + C::NSTAGE - 1 < nkb) issue(kb + C::NSTAGE - 1);
-        return smem + (kb % C::NSTAGE) * STAGE;
-    };
+    auto step_begin = [&](int kb) -> const char * { return smem + ring_step<C, 2 * C::DMA>(kb, 0, nkb, 0, issue) * STAGE; };
     // Which key tiles this wave computes, and which of them the clean body may take: every key exists and every
     // (query, key) pair of my 32 rows is visible (as in flash_fwd_dma.hip).
     const int my_nkb = !wave_has_rows ? 0 : p.causal ? min(nkb, (q0 + 31) / C::BT + 1) : nkb;
@@ -717,7 +678,7 @@ BP_DEV void flash_bwd_dq_tile(const FlashBwdParams p, char *smem, const uint32_t
         lneg = lse_row == -INFINITY ? 0.f : -lse_row / p.scale;
         dneg = -xhalf_sum(part);   // the two half-waves hold the two 8-column halves of every 16
         if (hh == 0 && wave_has_rows && my_q < seq_q) {
-            float *st = stats_row(p, batch, head);
+            float *st = stats_row(p, w.batch, w.head);
             st[min(my_q, seq_q - 1)] = dneg;
             st[p.lse_stride + min(my_q, seq_q - 1)] = lneg;
         }
@@ -751,18 +712,30 @@ BP_DEV void flash_bwd_dq_tile(const FlashBwdParams p, char *smem, const uint32_t
     BWD_STAMP(0, pass, 6);   // all tiles done
 
     if (!wave_has_rows) return;
-    int q_row = min(my_q, seq_q - 1);
-    asm volatile("" : "+v"(q_row));   // (as in the dK/dV epilogue: keep the output pointer out of the tile loops)
-    uint16_t *dqg = reinterpret_cast<uint16_t *>(p.dq) + (si.q_row0 + q_row) * p.dq_rs + (int64_t)head * p.dq_hs;
-    const int d_lim = my_q < seq_q ? p.d : 0;
-#pragma unroll
-    for (int n = 0; n < NV; ++n) store_block16<E, (KD <= 4)>(dqg, dq[n], p.scale, n, hh, d_lim);
+    store_row<E, KD>(p.dq, w.q_row0, p.dq_rs, (int64_t)w.head * p.dq_hs, my_q, seq_q, dq, p.scale, hh, p.d);
     BWD_STAMP(0, pass, 7);
 }
 
-
 // Kernels: a causal workgroup takes the heaviest remaining tile and the lightest of its (sample, head) -- tiles t
 // and n-1-t -- so that every workgroup carries the same work (in-order round-robin dispatch, see flash_fwd_dma.hip).
+
+// workgroups ("slots") per (sample, head) with n tiles: the kernels' decoding of blockIdx.x and the launch's grid
+__host__ __device__ constexpr int bwd_slots(bool causal, int n) { return causal && n > 1 ? (n + 1) / 2 : n; }
+
+// The one or two passes of this workgroup: tile(wave, bh, t, pass) for t = slot and t = n-1-slot, `slot_first` says in
+// which order (key tile 0 and query tile n-1 are the heaviest).
+template <class Tile> BP_DEV void bwd_paired_passes(const FlashBwdParams &p, int n, bool slot_first, Tile &&tile) {
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    int bh, slot;
+    if (!xcd_map(blockIdx.x, p.b * p.h, bwd_slots(p.causal, n), bh, slot)) return;
+    const int other = n - 1 - slot;
+    const int npass = (p.causal && n > 1 && other != slot) ? 2 : 1;
+    for (int pass = 0; pass < npass; ++pass) {
+        if (pass) __syncthreads();
+        tile(wave, bh, (pass == 0) == slot_first ? slot : other, pass);
+    }
+}
+
 // (the dropout variants spill 500+ registers at three waves per SIMD: they keep two)
 constexpr int bwd_dkdv_min_waves(int kd, bool drop) { return kd <= 4 && !drop ? 3 : kd <= 4 ? 2 : 1; }
 
@@ -770,17 +743,9 @@ template <class ET, int KD, bool FULLD, bool DROP>
 __global__ __launch_bounds__(256, bwd_dkdv_min_waves(KD, DROP)) void flash_bwd_dkdv_kernel(const FlashBwdParams p) {
     __shared__ __attribute__((aligned(16))) char smem[DkdvCfg<KD>::SMEM];
     const uint32_t lds0 = lds_base_addr(smem);
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int n = (p.max_sk + 127) / 128;
-    const bool pair = p.causal && n > 1;
-    int bh, slot;
-    if (!xcd_map(blockIdx.x, p.b * p.h, pair ? (n + 1) / 2 : n, bh, slot)) return;   // key tile 0 = most work
-    const int other = n - 1 - slot;
-    const int npass = (pair && other != slot) ? 2 : 1;
-    for (int pass = 0; pass < npass; ++pass) {
-        if (pass) __syncthreads();
-        flash_bwd_dkdv_tile<ET, KD, FULLD, DROP>(p, smem, lds0, wave, bh, pass ? other : slot, pass);
-    }
+    bwd_paired_passes(p, (p.max_sk + 127) / 128, true, [&](int wave, int bh, int kt, int pass) {
+        flash_bwd_dkdv_tile<ET, KD, FULLD, DROP>(p, smem, lds0, wave, bh, kt, pass);
+    });
 }
 
 // waves per SIMD the register allocator must leave room for in the dQ kernel (512 VGPRs per SIMD lane)
@@ -791,28 +756,19 @@ __global__ __launch_bounds__(256, bwd_dq_min_waves(KD)) void flash_bwd_dq_kernel
     using C = BwdCfg<KD>;
     __shared__ __attribute__((aligned(16))) char smem[C::NSTAGE * 2 * C::TILE];
     const uint32_t lds0 = lds_base_addr(smem);
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int n = (p.max_sq + 127) / 128;
-    const bool pair = p.causal && n > 1;
-    int bh, slot;
-    if (!xcd_map(blockIdx.x, p.b * p.h, pair ? (n + 1) / 2 : n, bh, slot)) return;
-    const int heavy = n - 1 - slot;
-    const int npass = (pair && heavy != slot) ? 2 : 1;
-    for (int pass = 0; pass < npass; ++pass) {
-        if (pass) __syncthreads();
-        flash_bwd_dq_tile<ET, KD, FULLD, DROP>(p, smem, lds0, wave, bh, pass ? slot : heavy, pass);
-    }
+    bwd_paired_passes(p, (p.max_sq + 127) / 128, false, [&](int wave, int bh, int qt, int pass) {
+        flash_bwd_dq_tile<ET, KD, FULLD, DROP>(p, smem, lds0, wave, bh, qt, pass);
+    });
 }
 
 template <class ET, int KD, bool FULLD, bool DROP>
 static hipError_t launch_drop(const FlashBwdParams &p, hipStream_t stream) {
     // dq first: it also produces the row statistics the dkdv kernel consumes
-    const int nq = (p.max_sq + 127) / 128, nk = (p.max_sk + 127) / 128;
-    const int gq = xcd_grid(p.b * p.h, (p.causal && nq > 1) ? (nq + 1) / 2 : nq);
+    const int gq = xcd_grid(p.b * p.h, bwd_slots(p.causal, (p.max_sq + 127) / 128));
     hipLaunchKernelGGL((flash_bwd_dq_kernel<ET, KD, FULLD, DROP>), dim3(gq), dim3(256), 0, stream, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    const int gk = xcd_grid(p.b * p.h, (p.causal && nk > 1) ? (nk + 1) / 2 : nk);
+    const int gk = xcd_grid(p.b * p.h, bwd_slots(p.causal, (p.max_sk + 127) / 128));
     hipLaunchKernelGGL((flash_bwd_dkdv_kernel<ET, KD, FULLD, DROP>), dim3(gk), dim3(256), 0, stream, p);
     return hipGetLastError();
 }
