@@ -89,6 +89,7 @@ SIGNATURES = {
     'bp_sense_decode_weighted': (_i32, [_ptr] * 10 + [_i64] + [_i32] * 5 + [_i64] + [_i64] * 13 + [_f32, _i32, _ptr]),
     'bp_sense_rows_dot': (_i32, [_ptr] * 6 + [_i32] * 4 + [_i64] + [_i64] * 6 + [_i32, _ptr]),
     'bp_pick_token': (_i32, [_ptr] * 6 + [_i32] * 2 + [_i64] * 3 + [_i32] * 2 + [_f32, _i32, _f32, _i32, _ptr]),
+    'bp_pick_token_ctl': (_i32, [_ptr] * 7 + [_i32] * 2 + [_i64] * 3 + [_i32] * 2 + [_f32, _i32, _f32, _f32] + [_i32] * 4 + [_ptr]),
 }
 
 
@@ -1126,13 +1127,14 @@ def sense_rows_dot(table, row_index, new_row, cache_seqlens, vec, out):
     return out
 
 
-# ---- token selection on the device (C ABI bp_pick_token) ---------------------------------------------------------------------------------------------
+# ---- token selection on the device (C ABI bp_pick_token, bp_pick_token_ctl) ---------------------------------------------------------------------------------------------
 
 _PICK_DTYPES = {torch.float16: 0, torch.bfloat16: 1, torch.float32: 2}
 
 
 def pick_token(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rng_state=None, counters=None, tokens=None,
-               sequences=None, return_stats=False):
+               sequences=None, return_stats=False, repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, min_length=0,
+               finished=None):
     """The next token of every row of `logits` (B, vocab) fp16 / bf16 / fp32 (any row stride), chosen on the device by one
     launch that reads no host value (legal inside a HIP-graph capture): argmax (lowest index of the maximum, NaN largest),
     or with do_sample a draw after temperature, top-k (ties kept) and top-p -- the contract is in include/bp_hip.h.
@@ -1141,8 +1143,14 @@ def pick_token(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rng
     counters (B,) int32 on the device: the Philox counter of every row and the column of `sequences` (B, cols) int64 that
     also receives the pick (skipped outside [0, cols)); None: counter 0.  tokens: optional int64 output with B elements
     (any stride along its first dimension), allocated when None.  Returns tokens, or (tokens, stats) with return_stats:
-    stats (B, 4) fp32 = lowest kept scaled logit, log-sum-exp of the kept ones, kept count, the uniform u."""
-    _require_cuda(logits, rng_state, counters, tokens, sequences)
+    stats (B, 4) fp32 = lowest kept scaled logit, log-sum-exp of the kept ones, kept count, the uniform u.
+
+    repetition_penalty, eos_token_id, pad_token_id (default: eos_token_id), min_length, finished ((B,) int32 on the device,
+    read and written) select bp_pick_token_ctl: tokens of the history sequences[b, :counters[b]] have their logit multiplied
+    by the penalty (negative) or its reciprocal, the EOS entry is -inf while counters[b] < min_length, a row whose flag is
+    set picks the pad, and a row that picks the EOS id has its flag set.  With all five at their defaults the call is
+    bp_pick_token's, argument for argument."""
+    _require_cuda(logits, rng_state, counters, tokens, sequences, finished)
     if logits.dim() != 2 or logits.stride(1) != 1 or logits.dtype not in _PICK_DTYPES:
         raise RuntimeError('bp_hip.pick_token: logits must be (B, vocab) fp16 / bf16 / fp32 with a contiguous last dimension')
     batch, vocab = logits.shape
@@ -1160,6 +1168,23 @@ def pick_token(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rng
                                   or sequences.stride(1) != 1):
         raise RuntimeError('bp_hip.pick_token: sequences must be (B, cols) int64 with a contiguous last dimension')
     stats = torch.empty((batch, 4), dtype=torch.float32, device=logits.device) if return_stats else None
+    if not (repetition_penalty == 1.0 and eos_token_id is None and pad_token_id is None and min_length == 0
+            and finished is None):
+        if finished is not None and (finished.shape != (batch,) or finished.dtype != torch.int32
+                                     or not finished.is_contiguous()):
+            raise RuntimeError('bp_hip.pick_token: finished must be a contiguous (B,) int32 tensor')
+        if pad_token_id is None:
+            pad_token_id = eos_token_id if eos_token_id is not None else 0
+        _call('bp_pick_token_ctl', logits.device,
+              logits.data_ptr(), tokens.data_ptr(), sequences.data_ptr() if sequences is not None else None,
+              stats.data_ptr() if stats is not None else None, rng_state.data_ptr() if rng_state is not None else None,
+              counters.data_ptr() if counters is not None else None, finished.data_ptr() if finished is not None else None,
+              batch, vocab, logits.stride(0), tokens.stride(0) if batch > 1 else 1,
+              sequences.stride(0) if sequences is not None else 0, sequences.shape[1] if sequences is not None else 0,
+              int(bool(do_sample)), float(temperature), int(top_k), float(top_p), float(repetition_penalty),
+              -1 if eos_token_id is None else int(eos_token_id), int(pad_token_id), int(min_length),
+              _PICK_DTYPES[logits.dtype])
+        return (tokens, stats) if return_stats else tokens
     _call('bp_pick_token', logits.device,
           logits.data_ptr(), tokens.data_ptr(), sequences.data_ptr() if sequences is not None else None,
           stats.data_ptr() if stats is not None else None, rng_state.data_ptr() if rng_state is not None else None,

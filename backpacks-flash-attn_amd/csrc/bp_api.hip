@@ -129,7 +129,8 @@ const char *bp_strerror(int code) {
         case BP_ERR_DROPOUT: return "dropout: p must be in [0, 1), rng_state non-NULL when p > 0, 16-byte friendly shapes only";
         case BP_ERR_QUEUE_WS: return "queue_ws must be caller-owned (non-NULL) while the stream is being captured";
         case BP_ERR_WORKSPACE: return "workspace smaller than the *_ws_floats() query of this entry point";
-        case BP_ERR_SAMPLING: return "token sampling: top_p must be in (0, 1], rng_state non-NULL when do_sample";
+        case BP_ERR_SAMPLING: return "token sampling: top_p must be in (0, 1], rng_state non-NULL when do_sample; repetition_penalty finite and > 0 and, "
+                                     "unless 1, with sequences; an eos_token_id with finished flags";
         default: return "unknown error";
     }
 }
@@ -893,12 +894,13 @@ int bp_sense_rows_dot(const void *table, const int32_t *row_index, const int32_t
     return launch_status(bp::launch_sense_rows_dot(p, dtype, static_cast<hipStream_t>(stream)));
 }
 
-// ---- token selection (bp_pick_token) ----
+// ---- token selection (bp_pick_token, bp_pick_token_ctl) ----
 
-int bp_pick_token(const void *logits, int64_t *tokens, int64_t *sequences, float *stats, const uint64_t *rng_state,
-                  const int32_t *counters, int batch, int vocab, int64_t row_stride, int64_t tokens_stride,
-                  int64_t seq_stride, int seq_cols, int do_sample, float temperature, int top_k, float top_p, int dtype,
-                  bp_stream_t stream) {
+// the argument checks of bp_pick_token and the parameters they admit; bp_pick_token_ctl adds its own behind them
+static int pick_params(bp::PickParams &p, const void *logits, int64_t *tokens, int64_t *sequences, float *stats,
+                       const uint64_t *rng_state, const int32_t *counters, int batch, int vocab, int64_t row_stride,
+                       int64_t tokens_stride, int64_t seq_stride, int seq_cols, int do_sample, float temperature, int top_k,
+                       float top_p, int dtype) {
     if (dtype != BP_DTYPE_F16 && dtype != BP_DTYPE_BF16 && dtype != BP_DTYPE_F32) return BP_ERR_DTYPE;
     if (batch <= 0 || vocab <= 0 || vocab > (1 << 23) || row_stride < vocab || tokens_stride < 1) return BP_ERR_SHAPE;
     if (logits == nullptr || tokens == nullptr) return BP_ERR_SHAPE;
@@ -911,14 +913,47 @@ int bp_pick_token(const void *logits, int64_t *tokens, int64_t *sequences, float
     if (!scale_ok(temperature) || !scale_ok(1.f / temperature)) return BP_ERR_SCALE;
     if (!(top_p > 0.f && top_p <= 1.f)) return BP_ERR_SAMPLING;
     if (do_sample && rng_state == nullptr) return BP_ERR_SAMPLING;
-    bp::PickParams p{};
     p.logits = logits; p.tokens = tokens; p.sequences = sequences; p.stats = stats; p.rng_state = rng_state;
     p.counters = counters;
     p.row_stride = row_stride; p.tokens_stride = tokens_stride; p.seq_stride = seq_stride;
     p.batch = batch; p.vocab = vocab; p.seq_cols = seq_cols;
     p.do_sample = do_sample ? 1 : 0; p.top_k = top_k;
     p.inv_t = 1.f / temperature; p.top_p = top_p;
+    p.finished = nullptr; p.theta = p.inv_theta = 1.f; p.eos = -1; p.pad = 0; p.min_length = 0;
+    return BP_OK;
+}
+
+int bp_pick_token(const void *logits, int64_t *tokens, int64_t *sequences, float *stats, const uint64_t *rng_state,
+                  const int32_t *counters, int batch, int vocab, int64_t row_stride, int64_t tokens_stride,
+                  int64_t seq_stride, int seq_cols, int do_sample, float temperature, int top_k, float top_p, int dtype,
+                  bp_stream_t stream) {
+    bp::PickParams p{};
+    const int e = pick_params(p, logits, tokens, sequences, stats, rng_state, counters, batch, vocab, row_stride,
+                              tokens_stride, seq_stride, seq_cols, do_sample, temperature, top_k, top_p, dtype);
+    if (e != BP_OK) return e;
     return launch_status(bp::launch_pick_token(p, dtype, static_cast<hipStream_t>(stream)));
+}
+
+int bp_pick_token_ctl(const void *logits, int64_t *tokens, int64_t *sequences, float *stats, const uint64_t *rng_state,
+                      const int32_t *counters, int32_t *finished,
+                      int batch, int vocab, int64_t row_stride, int64_t tokens_stride, int64_t seq_stride, int seq_cols,
+                      int do_sample, float temperature, int top_k, float top_p,
+                      float repetition_penalty, int eos_token_id, int pad_token_id, int min_length,
+                      int dtype, bp_stream_t stream) {
+    bp::PickParams p{};
+    const int e = pick_params(p, logits, tokens, sequences, stats, rng_state, counters, batch, vocab, row_stride,
+                              tokens_stride, seq_stride, seq_cols, do_sample, temperature, top_k, top_p, dtype);
+    if (e != BP_OK) return e;
+    if (!scale_ok(repetition_penalty) || !scale_ok(1.f / repetition_penalty)) return BP_ERR_SAMPLING;
+    if (repetition_penalty != 1.f && sequences == nullptr) return BP_ERR_SAMPLING;
+    if (eos_token_id >= 0 && finished == nullptr) return BP_ERR_SAMPLING;
+    if (eos_token_id >= vocab || min_length < 0 || reinterpret_cast<uintptr_t>(finished) % 4) return BP_ERR_SHAPE;
+    if (finished != nullptr && (pad_token_id < 0 || pad_token_id >= vocab)) return BP_ERR_SHAPE;
+    if (repetition_penalty != 1.f && vocab > (1 << 19)) return BP_ERR_SHAPE;   // the history bitmap: 64 KB of LDS at most
+    p.finished = finished;
+    p.theta = repetition_penalty; p.inv_theta = 1.f / repetition_penalty;
+    p.eos = eos_token_id < 0 ? -1 : eos_token_id; p.pad = pad_token_id; p.min_length = min_length;
+    return launch_status(bp::launch_pick_token_ctl(p, dtype, static_cast<hipStream_t>(stream)));
 }
 
 }  // extern "C"

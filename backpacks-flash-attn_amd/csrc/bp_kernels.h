@@ -328,7 +328,12 @@ struct PickParams {
     int batch, vocab, seq_cols;
     int do_sample, top_k;
     float inv_t, top_p;          // 1 / temperature
+    // bp_pick_token_ctl only (pick_token_ctl.hip); the plain kernels never read past top_p
+    int32_t *finished;           // optional (batch): a set flag turns the row's pick into `pad`; set when the pick is `eos`
+    float theta, inv_theta;      // repetition penalty and its reciprocal
+    int eos, pad, min_length;    // eos < 0: none; the EOS entry counts as -inf while counters[b] < min_length
 };
 hipError_t launch_pick_token(const PickParams &p, int dtype, hipStream_t stream);
+hipError_t launch_pick_token_ctl(const PickParams &p, int dtype, hipStream_t stream);
 
 }  // namespace bp

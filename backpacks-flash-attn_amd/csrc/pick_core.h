@@ -1,0 +1,529 @@
+// Token selection on the device for the decode loops: one row of logits in, one token out.  The shared body of
+// bp_pick_token (csrc/pick_token.hip) and bp_pick_token_ctl (csrc/pick_token_ctl.hip).
+//
+// Replaces the host-driven picks of the generation loops (src/utils/generation.py: torch.argmax, and
+// torch.distributions.Categorical, whose argument validation reads a device value on the host) and adds the sampling
+// options of the reference's control baseline (training/run_pplm.py:80,347-348,569-581: temperature, top_k with ties
+// kept).  The contract, restated by _eager_pick (src/utils/generation.py) and by the tests:
+//
+//   greedy    lowest index of the maximal logit; a NaN counts as larger than every number (torch.argmax)
+//   sampling  z_i = float(x_i) * (1 / T)
+//             top-k   tau = k-th largest z with multiplicity, keep z_i >= tau (ties kept); off for k <= 0 or k >= vocab
+//             top-p   on the probabilities renormalised over what top-k kept: keep i iff the mass of kept tokens with
+//                     z_j > z_i is < p (equal logits share a fate)
+//             u       ((r0 >> 8) + 0.5) 2^-24, (r0, _) = philox2x32(counters[b], salt, key), (key, salt) the stream of row b
+//             token   lowest index t, in vocabulary order, whose cumulative kept probability through t exceeds u
+//             degenerate rows (a NaN or +inf, or nothing finite) take the greedy answer
+//
+// One 1024-thread workgroup per row, 16-byte loads, every pass re-reads the row (it stays in L2).  All masses are FIXED POINT:
+// w_i = trunc(exp(z_i - max z) 2^40) as a 64-bit integer, so sums do not depend on their order -- histogram atomics on LDS,
+// wave reductions and the vocabulary-order scan all give the same bits on every call -- and the comparisons of the
+// contract (mass above < p S, cumulative mass > u S) are exact integer comparisons.  The quantisation (2^-40 per term against a
+// total >= 1) is far below the fp32 rounding of the exponentials themselves.
+//
+// Passes over the row:
+//   1  argmax on a 64-bit (ordered value, ~index) key: the greedy token, max z, and the degenerate cases
+//   2  top-k: radix select of the k-th largest element on the order-preserving integer key of x (x -> z is monotone), 8 bits
+//      a round: two rounds for 16-bit logits, four for fp32; rounds after the first only touch the selected bucket
+//   3  top-p: the same select with the fixed-point masses as weights; its first round also yields the mass top-k kept
+//   4  the scan: per-lane sums in a wave-contiguous layout (wave w owns a contiguous run of chunks, lane l of step s the chunk
+//      64 s + l of it), the total, then the ONE wave that holds the target walks its run again with a wave prefix sum
+// The histograms are 32 copies (lane & 31) of 256 bins, a copy stride of 257 words: a wave's lanes that hit one bin land in
+// different banks, and at most two lanes share an address.
+//
+// Controlled form (bp_pick_token_ctl, pick_token_ctl.hip): pick_token_kernel<Controlled<ET>> adds a repetition penalty over
+// the row's history, an EOS mask below min_length and the finished flags (contract in include/bp_hip.h).  The flag rides on
+// the element tag, in a code object of its own, so the plain instantiations keep their names and their code.  What it changes:
+//   0  before pass 1: a row finished on entry writes the pad and returns; otherwise the history sequences[b, 0 : min(c, cols)]
+//      becomes a bitmap in dynamic LDS, one bit per vocabulary entry (atomicOr on LDS words; ids outside [0, vocab) dropped)
+//   *  every pass takes its value from ONE helper (Logits::x / Logits::z): pen(float(x) [* 1/T]) with the EOS entry as -inf.
+//      pen multiplies a member of the history by theta (negative) or 1/theta (otherwise): one fp32 multiplication
+//   1  also the maximum of z: pen(x * 1/T) and pen(x) * 1/T round differently, so max z is not xmax * 1/T any more
+//   2, 3  select on the 32-bit key of the fp32 z itself (four rounds for every element type): pen is not monotone across the
+//      two classes, so the key of the raw element no longer orders the row; the threshold is the z the key stands for
+//   5  after the token is written: finished[b] = 1 by that one lane when the token is the EOS id
+#pragma once
+#include <type_traits>
+
+#include "bp_common.h"
+#include "bp_kernels.h"
+#include "bp_philox.h"
+
+namespace bp {
+
+// Controlled form: the flag rides on the element tag (as Weighted<ET> in decode_core.h)
+template <class ET> struct Controlled {};
+template <class T> struct PickTag { using elem = T; static constexpr bool ctl = false; };
+template <class T> struct PickTag<Controlled<T>> { using elem = T; static constexpr bool ctl = true; };
+
+namespace {
+
+constexpr int kPickThreads = 1024;
+constexpr int kPickWaves = kPickThreads / 64;
+constexpr int kHistCopies = 32;
+constexpr int kHistStride = 257;
+constexpr float kFixedOne = 1099511627776.f;   // 2^40
+
+typedef unsigned long long u64;
+
+template <class ET> struct PickElem;   // raw bits of an element <-> float, 16-byte loads, the order-preserving key
+template <> struct PickElem<float> {
+    static constexpr int N = 4, EB = 4, KEY_BITS = 32;
+    static BP_DEV float to_f32(uint32_t raw) { return as_f32(raw); }
+    static BP_DEV uint32_t one(const char *p) { return *reinterpret_cast<const uint32_t *>(p); }
+    static BP_DEV void load(const char *p, uint32_t (&raw)[8]) {
+        const u32x4 w = *reinterpret_cast<const u32x4 *>(p);
+        const uint32_t a = w[0], b = w[1], c = w[2], d = w[3];
+        raw[0] = a; raw[1] = b; raw[2] = c; raw[3] = d;
+    }
+    static BP_DEV uint32_t key(uint32_t raw) { return raw ^ ((raw & 0x80000000u) ? 0xffffffffu : 0x80000000u); }
+    static BP_DEV uint32_t unkey(uint32_t k) { return k ^ ((k & 0x80000000u) ? 0x80000000u : 0xffffffffu); }
+};
+template <class H> struct PickElem16 {
+    static constexpr int N = 8, EB = 2, KEY_BITS = 16;
+    static BP_DEV float to_f32(uint32_t raw) { return Elem<H>::lo_f32(raw); }
+    static BP_DEV uint32_t one(const char *p) { return *reinterpret_cast<const uint16_t *>(p); }
+    static BP_DEV void load(const char *p, uint32_t (&raw)[8]) {
+        const u32x4 w = *reinterpret_cast<const u32x4 *>(p);
+        const uint32_t a = w[0], b = w[1], c = w[2], d = w[3];
+        raw[0] = a & 0xffffu; raw[1] = a >> 16; raw[2] = b & 0xffffu; raw[3] = b >> 16;
+        raw[4] = c & 0xffffu; raw[5] = c >> 16; raw[6] = d & 0xffffu; raw[7] = d >> 16;
+    }
+    static BP_DEV uint32_t key(uint32_t raw) { return raw ^ ((raw & 0x8000u) ? 0xffffu : 0x8000u); }
+    static BP_DEV uint32_t unkey(uint32_t k) { return k ^ ((k & 0x8000u) ? 0x8000u : 0xffffu); }
+};
+template <> struct PickElem<BF16> : PickElem16<BF16> {};
+template <> struct PickElem<F16> : PickElem16<F16> {};
+
+BP_DEV u64 shfl_xor_u64(u64 v, int mask) {
+    const uint32_t lo = __shfl_xor((uint32_t)v, mask), hi = __shfl_xor((uint32_t)(v >> 32), mask);
+    return ((u64)hi << 32) | lo;
+}
+BP_DEV u64 shfl_up_u64(u64 v, int delta) {
+    const uint32_t lo = __shfl_up((uint32_t)v, delta), hi = __shfl_up((uint32_t)(v >> 32), delta);
+    return ((u64)hi << 32) | lo;
+}
+BP_DEV u64 shfl_u64(u64 v, int lane) {
+    const uint32_t lo = __shfl((uint32_t)v, lane), hi = __shfl((uint32_t)(v >> 32), lane);
+    return ((u64)hi << 32) | lo;
+}
+BP_DEV u64 wave_sum_u64(u64 v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += shfl_xor_u64(v, o);
+    return v;
+}
+BP_DEV u64 wave_max_u64(u64 v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const u64 w = shfl_xor_u64(v, o);
+        v = w > v ? w : v;
+    }
+    return v;
+}
+// inclusive prefix sum over the lanes of a wave
+BP_DEV u64 wave_scan_u64(u64 v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const u64 w = shfl_up_u64(v, o);
+        if (lane >= o) v += w;
+    }
+    return v;
+}
+
+// value part of the argmax key: NaN above everything, -0 == +0, otherwise the order of the floats
+BP_DEV uint32_t greedy_key(float x) {
+    if (x != x) return 0xffffffffu;
+    const uint32_t raw = as_u32(x + 0.f);   // -0 + 0 = +0
+    return raw ^ ((raw & 0x80000000u) ? 0xffffffffu : 0x80000000u);
+}
+BP_DEV float greedy_unkey(uint32_t k) { return as_f32(k ^ ((k & 0x80000000u) ? 0x80000000u : 0xffffffffu)); }
+
+// exp(z - m) in fixed point; z <= m, m finite
+BP_DEV u64 fixed_mass(float z, float m) { return (u64)(fast_exp2((z - m) * kLog2e) * kFixedOne); }
+
+struct PickShared {
+    u64 hist[kHistCopies * kHistStride];
+    u64 bins[256];
+    u64 wave64[kPickWaves];
+    float wavef[kPickWaves];
+    int wavei[kPickWaves];
+    u64 sel_above;
+    uint32_t sel_digit;
+};
+
+// The row as seen by one lane: chunks of N elements on 16-byte boundaries of the address space (chunk 0 starts at or
+// before the row), wave w owning the chunks [w cpw, (w + 1) cpw).  Chunks that reach outside the row are read element
+// by element; `mask` has a bit per valid element.
+template <class ET> struct RowView {
+    using E = PickElem<ET>;
+    const char *vbase;   // address of chunk 0
+    int head, vocab, nch, cpw;
+    BP_DEV RowView(const char *row, int vocab_) : vocab(vocab_) {
+        head = (int)((reinterpret_cast<uintptr_t>(row) & 15u) / E::EB);
+        vbase = row - head * E::EB;
+        nch = (vocab + head + E::N - 1) / E::N;
+        cpw = (nch + kPickWaves - 1) / kPickWaves;
+    }
+    BP_DEV int steps() const { return (cpw + 63) / 64; }
+    // chunk of (wave, step, lane), -1 past the wave's run
+    BP_DEV int chunk(int wave, int step, int lane) const {
+        const int local = step * 64 + lane;
+        const int c = wave * cpw + local;
+        return (local < cpw && c < nch) ? c : -1;
+    }
+    // returns the column of element 0 of the chunk (may be negative for chunk 0)
+    BP_DEV int load(int c, uint32_t (&raw)[8], uint32_t &mask) const {
+        const int col0 = c * E::N - head;
+        if (col0 >= 0 && col0 + E::N <= vocab) {
+            E::load(vbase + (int64_t)c * 16, raw);
+            mask = (1u << E::N) - 1u;
+        } else {
+            mask = 0;
+#pragma unroll
+            for (int i = 0; i < E::N; ++i) {
+                const int col = col0 + i;
+                const bool ok = col >= 0 && col < vocab;
+                raw[i] = ok ? E::one(vbase + ((int64_t)c * E::N + i) * E::EB) : 0u;
+                if (ok) mask |= 1u << i;
+            }
+        }
+        return col0;
+    }
+};
+
+// The value of an element as every pass sees it.  Plain rows: x = float(raw), z = x * (1 / T).
+template <class TAG> struct Logits {
+    using E = PickElem<typename PickTag<TAG>::elem>;
+    float inv_t;
+    BP_DEV Logits(const PickParams &p, int, const uint32_t *) : inv_t(p.inv_t) {}
+    struct Chunk {};
+    BP_DEV Chunk chunk(const RowView<typename PickTag<TAG>::elem> &, int) const { return Chunk{}; }
+    BP_DEV float x(uint32_t raw, Chunk, int) const { return E::to_f32(raw); }
+    BP_DEV float z(uint32_t raw, Chunk, int) const { return E::to_f32(raw) * inv_t; }
+};
+// Controlled rows: pen() on the members of the history, then the EOS entry as -inf.  A Chunk is the column of element 0
+// of chunk c and the membership bits of its elements, bit i for column col0 + i (the bitmap carries one spare word: two
+// words cover any chunk).
+template <class ET> struct Logits<Controlled<ET>> {
+    using E = PickElem<ET>;
+    const uint32_t *bitmap;   // NULL: no history (theta == 1, no sequences, or nothing in front of the position)
+    float inv_t, theta, inv_theta;
+    int eos;                  // the masked column, -1 for none
+    BP_DEV Logits(const PickParams &p, int counter, const uint32_t *bitmap_)
+        : bitmap(bitmap_), inv_t(p.inv_t), theta(p.theta), inv_theta(p.inv_theta),
+          eos(p.eos >= 0 && counter < p.min_length ? p.eos : -1) {}
+    struct Chunk { int col0; uint32_t members; };
+    BP_DEV Chunk chunk(const RowView<ET> &row, int c) const {
+        const int col0 = (c < 0 ? 0 : c) * E::N - row.head;
+        if (bitmap == nullptr) return Chunk{col0, 0u};
+        const int base = col0 < 0 ? 0 : col0;
+        const u64 two = (u64)bitmap[base >> 5] | ((u64)bitmap[(base >> 5) + 1] << 32);
+        return Chunk{col0, (uint32_t)(two >> (base & 31)) << (base - col0)};
+    }
+    BP_DEV float ctl(float v, Chunk ck, int i) const {
+        if ((ck.members >> i) & 1u) v = v < 0.f ? v * theta : v * inv_theta;
+        return ck.col0 + i == eos ? -INFINITY : v;
+    }
+    // element i of the chunk
+    BP_DEV float x(uint32_t raw, Chunk ck, int i) const { return ctl(E::to_f32(raw), ck, i); }
+    BP_DEV float z(uint32_t raw, Chunk ck, int i) const { return ctl(E::to_f32(raw) * inv_t, ck, i); }
+};
+
+// Key source of the radix select.  Plain rows: the order-preserving key of the RAW element (x -> z is monotone), 16 or 32
+// bits.  Controlled rows: the 32-bit key of the fp32 z, whose threshold is z itself.
+template <class TAG> struct SelectKey {
+    using E = PickElem<typename PickTag<TAG>::elem>;
+    static constexpr int BITS = E::KEY_BITS;
+    static BP_DEV uint32_t key(uint32_t raw, float) { return E::key(raw); }
+    static BP_DEV float threshold(uint32_t k, float inv_t) { return E::to_f32(E::unkey(k)) * inv_t; }
+};
+template <class ET> struct SelectKey<Controlled<ET>> {
+    static constexpr int BITS = 32;
+    static BP_DEV uint32_t key(uint32_t, float z) { return PickElem<float>::key(as_u32(z)); }
+    static BP_DEV float threshold(uint32_t k, float) { return as_f32(PickElem<float>::unkey(k)); }
+};
+
+// Radix select, 8 bits a round from the top of the key: among the elements with z >= lo, the key K with
+//   weight{key > K} < target <= weight{key >= K}
+// weight = 1 (top-k: target = k) or the fixed-point mass (top-p: target = ceil(p total), `total` from the first round).
+// Returns K to every thread.
+template <class TAG, bool WEIGHTED>
+BP_DEV uint32_t radix_select(const RowView<typename PickTag<TAG>::elem> &row, PickShared &sh, const Logits<TAG> &lg, float zmax,
+                             float lo, u64 target, float top_p) {
+    using E = PickElem<typename PickTag<TAG>::elem>;
+    using KEY = SelectKey<TAG>;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint32_t prefix = 0;
+    u64 above = 0;
+    constexpr int ROUNDS = KEY::BITS / 8;
+    for (int r = 0; r < ROUNDS; ++r) {
+        const int shift = KEY::BITS - 8 * (r + 1);
+        for (int i = tid; i < kHistCopies * kHistStride; i += kPickThreads) sh.hist[i] = 0;
+        __syncthreads();
+        u64 *mine = sh.hist + (lane & (kHistCopies - 1)) * kHistStride;
+        for (int s = 0; s < row.steps(); ++s) {
+            const int c = row.chunk(wave, s, lane);
+            if (c < 0) continue;
+            uint32_t raw[8], mask;
+            row.load(c, raw, mask);
+            const auto ck = lg.chunk(row, c);
+#pragma unroll
+            for (int i = 0; i < E::N; ++i) {
+                const float z = lg.z(raw[i], ck, i);
+                const uint32_t key = KEY::key(raw[i], z);
+                const bool in_bucket = r == 0 || (key >> (shift + 8)) == prefix;
+                if (((mask >> i) & 1u) && z >= lo && in_bucket) {
+                    const u64 w = WEIGHTED ? fixed_mass(z, zmax) : 1ull;
+                    if (w) atomicAdd(&mine[(key >> shift) & 255u], w);
+                }
+            }
+        }
+        __syncthreads();
+        if (tid < 256) {
+            u64 t = 0;
+            for (int cp = 0; cp < kHistCopies; ++cp) t += sh.hist[cp * kHistStride + tid];
+            sh.bins[tid] = t;
+        }
+        __syncthreads();
+        if (wave == 0) {
+            // lane l holds the digits 255 - 4 l ... 252 - 4 l: lanes and registers in DESCENDING digit order
+            u64 c4[4], tot = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                c4[j] = sh.bins[255 - 4 * lane - j];
+                tot += c4[j];
+            }
+            const u64 incl = wave_scan_u64(tot, lane);
+            if (WEIGHTED && r == 0) {
+                const u64 total = shfl_u64(incl, 63);
+                u64 t = (u64)ceil((double)top_p * (double)total);
+                t = t < 1 ? 1 : t;
+                target = t > total ? total : t;   // only wave 0 needs it, and keeps it for the later rounds
+            }
+            u64 run = above + incl - tot;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (run < target && run + c4[j] >= target) {
+                    sh.sel_digit = 255 - 4 * lane - j;
+                    sh.sel_above = run;
+                }
+                run += c4[j];
+            }
+        }
+        __syncthreads();
+        prefix = (prefix << 8) | sh.sel_digit;
+        above = sh.sel_above;
+        __syncthreads();   // sel_* are rewritten by the next round
+    }
+    return prefix;
+}
+
+}  // namespace
+
+template <class TAG>
+__global__ __launch_bounds__(kPickThreads) void pick_token_kernel(const PickParams p) {
+    using ET = typename PickTag<TAG>::elem;
+    using E = PickElem<ET>;
+    constexpr bool CTL = PickTag<TAG>::ctl;
+    __shared__ PickShared sh;
+    const int b = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const RowView<ET> row(static_cast<const char *>(p.logits) + (int64_t)b * p.row_stride * E::EB, p.vocab);
+    const int counter = p.counters ? p.counters[b] : 0;
+
+    const uint32_t *bitmap = nullptr;
+    if constexpr (CTL) {
+        extern __shared__ uint32_t pick_bitmap[];   // (vocab + 31) / 32 + 1 words when theta != 1, else none
+        if (p.finished && p.finished[b] != 0) {     // workgroup-uniform: the pad, no draw, the flag stays
+            if (tid == 0) {
+                p.tokens[(int64_t)b * p.tokens_stride] = p.pad;
+                if (p.sequences && counter >= 0 && counter < p.seq_cols) p.sequences[(int64_t)b * p.seq_stride + counter] = p.pad;
+                if (p.stats) {
+                    float u = 0.f;
+                    if (p.do_sample) {
+                        const DropoutStream rs = dropout_stream(p.rng_state, (uint32_t)b);
+                        uint32_t r0, r1;
+                        philox2x32((uint32_t)counter, rs.salt, rs.key, r0, r1);
+                        u = ((float)(r0 >> 8) + 0.5f) * 0x1p-24f;
+                    }
+                    float *st = p.stats + (int64_t)b * 4;
+                    st[0] = 0.f; st[1] = 0.f; st[2] = 0.f; st[3] = u;
+                }
+            }
+            return;
+        }
+        const int hist = counter < p.seq_cols ? counter : p.seq_cols;
+        if (p.theta != 1.f && p.sequences && hist > 0) {
+            const int words = (p.vocab + 31) / 32 + 1;
+            for (int i = tid; i < words; i += kPickThreads) pick_bitmap[i] = 0u;
+            __syncthreads();
+            const int64_t *seq = p.sequences + (int64_t)b * p.seq_stride;
+            for (int j = tid; j < hist; j += kPickThreads) {
+                const int64_t id = seq[j];
+                if (id >= 0 && id < (int64_t)p.vocab) atomicOr(&pick_bitmap[id >> 5], 1u << (id & 31));
+            }
+            __syncthreads();
+            bitmap = pick_bitmap;
+        }
+    }
+    const Logits<TAG> lg(p, counter, bitmap);
+
+    // ---- pass 1: argmax.  key = (ordered value << 32) | ~index: the maximum is the largest value at its lowest index
+    u64 best = 0;
+    uint32_t zbest = 0;   // controlled rows: the ordered maximum of z as well
+    for (int s = 0; s < row.steps(); ++s) {
+        const int c = row.chunk(wave, s, lane);
+        if (c < 0) continue;
+        uint32_t raw[8], mask;
+        const int col0 = row.load(c, raw, mask);
+        const auto ck = lg.chunk(row, c);
+#pragma unroll
+        for (int i = 0; i < E::N; ++i) {
+            const u64 k = ((u64)greedy_key(lg.x(raw[i], ck, i)) << 32) | (uint32_t)~(uint32_t)(col0 + i);
+            if (((mask >> i) & 1u) && k > best) best = k;
+            if constexpr (CTL) {
+                const uint32_t zk = greedy_key(lg.z(raw[i], ck, i));
+                if (((mask >> i) & 1u) && zk > zbest) zbest = zk;
+            }
+        }
+    }
+    best = wave_max_u64(best);
+    if (lane == 0) sh.wave64[wave] = best;
+    __syncthreads();
+    best = sh.wave64[0];
+#pragma unroll
+    for (int w = 1; w < kPickWaves; ++w) best = sh.wave64[w] > best ? sh.wave64[w] : best;
+    __syncthreads();   // wave64 is reused by the scan
+    if constexpr (CTL) {
+        zbest = (uint32_t)wave_max_u64((u64)zbest);
+        if (lane == 0) sh.wave64[wave] = zbest;
+        __syncthreads();
+        zbest = (uint32_t)sh.wave64[0];
+#pragma unroll
+        for (int w = 1; w < kPickWaves; ++w) zbest = (uint32_t)sh.wave64[w] > zbest ? (uint32_t)sh.wave64[w] : zbest;
+        __syncthreads();
+    }
+    const uint32_t gkey = (uint32_t)(best >> 32);
+    const int greedy = (int)~(uint32_t)best;
+    const float xmax = greedy_unkey(gkey);   // garbage for a NaN, which is caught first
+
+    int token = greedy;
+    bool sampled = false;   // workgroup-uniform: the row is drawn from, not degenerate
+    float st_lo = xmax, st_lse = xmax, st_count = 1.f, st_u = 0.f;
+    if (p.do_sample) {
+        const DropoutStream rs = dropout_stream(p.rng_state, (uint32_t)b);
+        uint32_t r0, r1;
+        philox2x32((uint32_t)counter, rs.salt, rs.key, r0, r1);
+        const uint32_t n24 = r0 >> 8;
+        st_u = ((float)n24 + 0.5f) * 0x1p-24f;
+        // (a NaN row keeps the plain form: its zmax only reaches `stats`)
+        const float zmax = CTL && gkey != 0xffffffffu ? greedy_unkey(zbest) : xmax * p.inv_t;
+        st_lo = st_lse = zmax;
+        const bool degenerate = gkey == 0xffffffffu || !(fabsf(zmax) < INFINITY);
+        sampled = !degenerate;
+        if (sampled) {
+            float lo = -INFINITY;
+            if (p.top_k > 0 && p.top_k < p.vocab) {
+                const uint32_t k = radix_select<TAG, false>(row, sh, lg, zmax, lo, (u64)p.top_k, 1.f);
+                lo = SelectKey<TAG>::threshold(k, p.inv_t);
+            }
+            if (p.top_p < 1.f) {
+                const uint32_t k = radix_select<TAG, true>(row, sh, lg, zmax, lo, 0, p.top_p);
+                lo = SelectKey<TAG>::threshold(k, p.inv_t);
+            }
+            // ---- the scan.  Lane sums, wave totals, the row's total (all integers: no order to fix)
+            u64 acc = 0;
+            int count = 0;
+            float zmin = INFINITY;
+            for (int s = 0; s < row.steps(); ++s) {
+                const int c = row.chunk(wave, s, lane);
+                if (c < 0) continue;
+                uint32_t raw[8], mask;
+                row.load(c, raw, mask);
+                const auto ck = lg.chunk(row, c);
+#pragma unroll
+                for (int i = 0; i < E::N; ++i) {
+                    const float z = lg.z(raw[i], ck, i);
+                    if (((mask >> i) & 1u) && z >= lo) {
+                        acc += fixed_mass(z, zmax);
+                        ++count;
+                        zmin = fminf(zmin, z);
+                    }
+                }
+            }
+            acc = wave_sum_u64(acc);
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) {
+                count += __shfl_xor(count, o);
+                zmin = fminf(zmin, __shfl_xor(zmin, o));
+            }
+            if (lane == 0) { sh.wave64[wave] = acc; sh.wavei[wave] = count; sh.wavef[wave] = zmin; }
+            __syncthreads();
+            u64 total = 0, before_wave = 0;
+            count = 0;
+            zmin = INFINITY;
+#pragma unroll
+            for (int w = 0; w < kPickWaves; ++w) {
+                if (w == wave) before_wave = total;
+                total += sh.wave64[w];
+                count += sh.wavei[w];
+                zmin = fminf(zmin, sh.wavef[w]);
+            }
+            // the draw: lowest t with C(t) > u S  <=>  C(t) > floor(u S) for the integers C; u S = (2 n + 1) S 2^-25
+            u64 target = (u64)((double)(2u * n24 + 1u) * (double)total * 0x1p-25);
+            if (target >= total) target = total - 1;   // total >= 2^40: the maximum itself is always kept
+            st_lo = zmin;
+            st_lse = zmax + fast_log2((float)total * (1.f / kFixedOne)) * kLn2;
+            st_count = (float)count;
+            const u64 mine = sh.wave64[wave];
+            token = -1;
+            if (before_wave <= target && target < before_wave + mine) {   // exactly one wave
+                u64 run = before_wave;
+                for (int s = 0; s < row.steps(); ++s) {
+                    const int c = row.chunk(wave, s, lane);
+                    uint32_t raw[8] = {0, 0, 0, 0, 0, 0, 0, 0}, mask = 0;
+                    int col0 = 0;
+                    if (c >= 0) col0 = row.load(c, raw, mask);
+                    const auto ck = lg.chunk(row, c);
+                    u64 wgt[8], v = 0;
+#pragma unroll
+                    for (int i = 0; i < E::N; ++i) {
+                        const float z = lg.z(raw[i], ck, i);
+                        wgt[i] = (((mask >> i) & 1u) && z >= lo) ? fixed_mass(z, zmax) : 0ull;
+                        v += wgt[i];
+                    }
+                    const u64 incl = wave_scan_u64(v, lane);
+                    const u64 step_total = shfl_u64(incl, 63);
+                    if (target < run + step_total) {   // wave-uniform
+                        const u64 hit = __ballot(run + incl > target);
+                        const int first = __ffsll((long long)hit) - 1;
+                        if (lane == first) {
+                            u64 cum = run + incl - v;
+#pragma unroll
+                            for (int i = 0; i < E::N; ++i) {
+                                cum += wgt[i];
+                                if (token < 0 && cum > target) token = col0 + i;
+                            }
+                        }
+                        break;
+                    }
+                    run += step_total;
+                }
+            }
+        }
+    }
+    // the greedy answer is known to every thread (thread 0 writes it), a drawn token to the lane that found it
+    if (sampled ? token >= 0 : tid == 0) {
+        p.tokens[(int64_t)b * p.tokens_stride] = token;
+        if (p.sequences && counter >= 0 && counter < p.seq_cols) p.sequences[(int64_t)b * p.seq_stride + counter] = token;
+        if constexpr (CTL) {
+            if (p.finished && p.eos >= 0 && token == p.eos) p.finished[b] = 1;
+        }
+    }
+    if (p.stats && tid == 0) {
+        float *st = p.stats + (int64_t)b * 4;
+        st[0] = st_lo; st[1] = st_lse; st[2] = st_count; st[3] = st_u;
+    }
+}
+
+}  // namespace bp

@@ -3,6 +3,8 @@ upstream, there is no KV cache: every step re-runs the whole forward on the grow
 HIP attention and sense-mix kernels); `kv_cache=True` decodes on the caches of InferenceParams instead (_decode_cached).
 `temperature`, `top_k`, `top_p`, `rng_state` or `device_pick=True` move the pick to the device (bp_pick_token; _eager_pick on CPU tensors), on the cache with
 cg=True inside the captured step (_decode_cached_picked); without them the loops below run as they always did.
+`repetition_penalty`, `eos_token_id`, `pad_token_id` and `min_length` (kv_cache=True only) select the controlled pick
+(bp_pick_token_ctl): rows stop at their EOS, the loop ends once every row has, and `lengths` reports where.
 Differences kept deliberately small: the result is a plain dataclass instead of the
 transformers `*DecoderOnlyOutput` classes (removed in transformers 5), and the appended token is
 `unsqueeze(1)` so batch sizes > 1 work (the reference's `unsqueeze(0)` in greedy_decode, :68, only
@@ -39,6 +41,7 @@ class InferenceParams:
 class DecoderOnlyOutput:
     sequences: torch.Tensor
     scores: Optional[Tuple[torch.Tensor, ...]] = None
+    lengths: Optional[torch.Tensor] = None      # (batch,) int64: 1 + the column of every row's first EOS, when an EOS id is given
 
 
 def _decode(input_ids, model, max_length, pick):
@@ -133,6 +136,7 @@ def _decode_cached(input_ids, model, max_length, pick, cg=False):
 # ---- the device pick: temperature / top-k / top-p, one definition for the HIP kernel and its torch restatement -----------------
 
 _M32 = 0xFFFFFFFF
+_DEFAULT_STOP_CHECK_EVERY = 16      # steps between two polls of the finished flags (_StopPoll); see DESIGN.md
 
 
 def _philox2x32(c0, c1, key):
@@ -159,21 +163,59 @@ def _pick_uniforms(rng_state, counters):
     return ((r0 >> 8).double() + 0.5) * 2.0 ** -24
 
 
-def _eager_pick(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rng_state=None, counters=None):
+def _history_mask(sequences, counters, vocab):
+    """(batch, vocab) bool: the ids of sequences[b, :min(counters[b], cols)] that lie inside [0, vocab)."""
+    batch, cols = sequences.shape
+    seen = (torch.arange(cols, device=sequences.device)[None, :] < counters.long()[:, None])
+    seen = seen & (sequences >= 0) & (sequences < vocab)
+    member = torch.zeros((batch, vocab + 1), dtype=torch.bool, device=sequences.device)
+    member.scatter_(1, torch.where(seen, sequences, torch.full_like(sequences, vocab)), True)   # the rest lands in a spare column
+    return member[:, :vocab]
+
+
+def _eager_pick(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rng_state=None, counters=None,
+                repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, min_length=0, finished=None, sequences=None):
     """The contract of bp_pick_token (include/bp_hip.h) in torch ops, for tensors the kernel does not take (CPU): tokens
     (batch,) int64 of logits (batch, vocab).  Greedy: torch.argmax (lowest index of the maximum, a NaN largest).  Sampling:
     z = float(x) / T in fp32; top-k keeps z >= the k-th largest (ties kept); top-p keeps a token iff the kept mass strictly
     above its logit is < p; the token is the lowest index whose cumulative kept probability exceeds u; rows with a NaN or
     +inf, or without a finite logit, take the greedy answer.  Masses are float64 here and 40-bit fixed point in the kernel:
-    the two agree wherever u is not within rounding of a boundary of the cumulative distribution."""
+    the two agree wherever u is not within rounding of a boundary of the cumulative distribution.
+
+    The controls of bp_pick_token_ctl: ids of the history sequences[b, :counters[b]] have their value multiplied by
+    repetition_penalty (negative values) or by its fp32 reciprocal (the others), in fp32, after the temperature; the EOS
+    entry is -inf while counters[b] < min_length; rows whose `finished` flag is set take pad_token_id (default: the EOS
+    id).  `finished` is only read here: _Picker sets the flag of a row that picked the EOS id."""
     x = logits.float()
-    greedy = torch.argmax(x, dim=-1)
-    if not do_sample:
-        return greedy
     batch, vocab = x.shape
     if counters is None:
         counters = torch.zeros((batch,), dtype=torch.int32, device=x.device)
-    z = x * (torch.ones((), dtype=torch.float32, device=x.device) / temperature)
+    one = torch.ones((), dtype=torch.float32, device=x.device)
+    member = None
+    if repetition_penalty != 1.0 and sequences is not None:
+        member = _history_mask(sequences, counters, vocab)
+    masked = None
+    if eos_token_id is not None and eos_token_id >= 0:
+        masked = torch.zeros((batch, vocab), dtype=torch.bool, device=x.device)
+        masked[:, eos_token_id] = counters < min_length
+
+    def controlled(v):
+        if member is not None:
+            v = torch.where(member, torch.where(v < 0, v * repetition_penalty, v * (one / repetition_penalty)), v)
+        if masked is not None:
+            v = torch.where(masked, torch.full_like(v, float('-inf')), v)
+        return v
+
+    def done(picked):
+        if finished is None:
+            return picked
+        pad = pad_token_id if pad_token_id is not None else (eos_token_id if eos_token_id is not None else 0)
+        return torch.where(finished != 0, torch.full_like(picked, pad), picked)
+
+    greedy = torch.argmax(controlled(x), dim=-1)
+    if not do_sample:
+        return done(greedy)
+    z = controlled(x * (one / temperature))
     zmax = z.max(dim=-1, keepdim=True).values
     degenerate = (torch.isnan(z).any(dim=-1) | (z == float('inf')).any(dim=-1) | (zmax[:, 0] == float('-inf')))
     z = torch.where(degenerate[:, None], torch.zeros_like(z), z)          # any finite row: its result is discarded
@@ -199,30 +241,54 @@ def _eager_pick(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rn
     hit = cdf > (u * cdf[:, -1])[:, None]
     last_kept = vocab - 1 - torch.flip(keep, dims=(-1,)).int().argmax(dim=-1)
     drawn = torch.where(hit.any(dim=-1), hit.int().argmax(dim=-1), last_kept)
-    return torch.where(degenerate, greedy, drawn)
+    return done(torch.where(degenerate, greedy, drawn))
 
 
 class _Picker:
     """The pick of the decode loops through bp_pick_token (CUDA tensors) or _eager_pick: argmax when not do_sample, else a
     draw after temperature / top-k / top-p.  `counters` (batch,) int32 on the logits' device hold the 0-based sequence
-    position of the token being picked: the Philox counter, and the column of `sequences` that receives the token."""
+    position of the token being picked: the Philox counter, and the column of `sequences` that receives the token.
+    With an EOS id it owns `finished` (batch,) int32 on the logits' device, allocated by the first pick: the flag of a row
+    is set by the pick that returns the EOS id, and every later pick of that row returns the pad."""
 
-    def __init__(self, do_sample, temperature, top_k, top_p, rng_state, device):
+    def __init__(self, do_sample, temperature, top_k, top_p, rng_state, device, repetition_penalty=1.0, eos_token_id=None,
+                 pad_token_id=None, min_length=0):
         if not (temperature > 0.0 and temperature < float('inf')) or not 0.0 < top_p <= 1.0:
             raise ValueError('generation: temperature must be finite and > 0, top_p in (0, 1]')
+        if not (repetition_penalty > 0.0 and repetition_penalty < float('inf')):
+            raise ValueError('generation: repetition_penalty must be finite and > 0')
+        if min_length < 0 or (eos_token_id is not None and eos_token_id < 0) or (pad_token_id is not None and pad_token_id < 0):
+            raise ValueError('generation: min_length, eos_token_id and pad_token_id must not be negative')
         self.do_sample, self.temperature, self.top_k, self.top_p = do_sample, float(temperature), int(top_k), float(top_p)
+        self.repetition_penalty, self.eos_token_id, self.min_length = float(repetition_penalty), eos_token_id, int(min_length)
+        self.pad_token_id = pad_token_id if pad_token_id is not None else eos_token_id
+        self.controlled = (repetition_penalty != 1.0 or eos_token_id is not None or pad_token_id is not None
+                           or min_length != 0)
+        self.finished = None
         if do_sample and rng_state is None:       # from torch's generator: torch.manual_seed reproduces a run
             rng_state = torch.randint(-2 ** 63, 2 ** 63 - 1, (2,), dtype=torch.int64, device=device)
         self.rng_state = rng_state.to(device) if rng_state is not None else None
 
     def __call__(self, logits, counters, tokens=None, sequences=None):
         """tokens (batch,) int64; also stored into `tokens` (batch elements) and column counters[b] of `sequences`."""
+        if self.eos_token_id is not None and self.finished is None:
+            self.finished = torch.zeros((logits.shape[0],), dtype=torch.int32, device=logits.device)
         if logits.is_cuda:
             import bp_hip
-            out = bp_hip.pick_token(logits, self.do_sample, self.temperature, self.top_k, self.top_p, self.rng_state,
-                                    counters, tokens=tokens, sequences=sequences)
+            if not self.controlled:
+                out = bp_hip.pick_token(logits, self.do_sample, self.temperature, self.top_k, self.top_p, self.rng_state,
+                                        counters, tokens=tokens, sequences=sequences)
+            else:
+                out = bp_hip.pick_token(logits, self.do_sample, self.temperature, self.top_k, self.top_p, self.rng_state,
+                                        counters, tokens=tokens, sequences=sequences,
+                                        repetition_penalty=self.repetition_penalty, eos_token_id=self.eos_token_id,
+                                        pad_token_id=self.pad_token_id, min_length=self.min_length, finished=self.finished)
             return out.view(-1)
-        picked = _eager_pick(logits, self.do_sample, self.temperature, self.top_k, self.top_p, self.rng_state, counters)
+        picked = _eager_pick(logits, self.do_sample, self.temperature, self.top_k, self.top_p, self.rng_state, counters,
+                             self.repetition_penalty, self.eos_token_id, self.pad_token_id, self.min_length, self.finished,
+                             sequences)
+        if self.finished is not None:
+            self.finished[picked == self.eos_token_id] = 1
         if tokens is not None:
             tokens.view(-1).copy_(picked)
         if sequences is not None:
@@ -243,11 +309,56 @@ class _Picker:
         return pick
 
 
-def _decode_cached_picked(input_ids, model, max_length, picker, cg=False):
+class _StopPoll:
+    """Whether every row has finished, asked without draining the queue.  Every `every` steps the flags are copied into
+    pinned host memory behind the steps queued so far, with an event behind the copy; the copy that is READ at that point is
+    the previous poll's, whose event is waited for.  So the host is never more than 2 * every steps ahead of the device,
+    the device has work queued while the host waits, and the loop ends at most 2 * every steps after the last row has
+    finished.  CPU flags are read directly."""
+
+    def __init__(self, finished, every):
+        self.finished, self.every, self.steps, self.pending = finished, every, 0, None
+        if finished.is_cuda:
+            self.host = [torch.zeros(finished.shape, dtype=finished.dtype).pin_memory() for _ in range(2)]
+
+    def all_finished(self):
+        """Called once per step; True when a poll shows every flag set."""
+        self.steps += 1
+        if self.steps % self.every:
+            return False
+        if not self.finished.is_cuda:
+            return bool(self.finished.all())
+        buf = self.host[(self.steps // self.every) & 1]
+        buf.copy_(self.finished, non_blocking=True)
+        event = torch.cuda.Event()
+        event.record()
+        previous, self.pending = self.pending, (buf, event)
+        if previous is None:
+            return False
+        previous[1].synchronize()
+        return bool(previous[0].all())
+
+
+def _trim_at_eos(sequences, seqlen_og, eos_token_id, pad_token_id):
+    """(sequences cut to max_b end_b columns with the pad behind every row's end_b, end_b (batch,) int64): end_b = 1 + the
+    first column >= seqlen_og of row b that holds the EOS id, the full width when there is none."""
+    batch, width = sequences.shape
+    cols = torch.arange(width, device=sequences.device)[None, :]
+    is_eos = (sequences == eos_token_id) & (cols >= seqlen_og)
+    first = torch.where(is_eos, cols, torch.full_like(cols, width - 1)).min(dim=1).values
+    lengths = first + 1
+    sequences = torch.where(cols < lengths[:, None], sequences, torch.full_like(sequences, pad_token_id))
+    return sequences[:, :int(lengths.max())].contiguous(), lengths
+
+
+def _decode_cached_picked(input_ids, model, max_length, picker, cg=False, stop_check_every=None):
     """_decode_cached with the pick on the device: the counter of a pick is `lengths_per_sample` after the step's
     increment, the pick writes the next step's input (`static_ids`) and column `position` of the preallocated `sequences`.
     With cg=True the captured graph is model step, length increment, pick: a generated token is one replay, with no launch
-    and no host read outside it.  Same index contract as _decode (the final pick lands outside `sequences` and is dropped)."""
+    and no host read outside it.  Same index contract as _decode (the final pick lands outside `sequences` and is dropped).
+    With an EOS id the loop ends once a poll (_StopPoll, every `stop_check_every` steps) shows every row finished; finished
+    rows keep stepping on the pad token until then.  The result is cut at the rows' ends (_trim_at_eos), so it depends
+    neither on the polling interval nor on how far the loop overran."""
     batch, seqlen_og = input_ids.shape
     width = max(seqlen_og, max_length - 1)
     ip = InferenceParams(max_sequence_len=width, max_batch_size=batch)
@@ -261,6 +372,9 @@ def _decode_cached_picked(input_ids, model, max_length, picker, cg=False):
         ip.sequence_len_offset = seqlen_og
         ip.lengths_per_sample.fill_(seqlen_og)
         picker(logits, ip.lengths_per_sample, tokens=static_ids, sequences=sequences)
+        poll = None
+        if picker.eos_token_id is not None:
+            poll = _StopPoll(picker.finished, _DEFAULT_STOP_CHECK_EVERY if stop_check_every is None else stop_check_every)
 
         def step():
             step_logits = model(static_ids, inference_params=ip).logits[:, -1]
@@ -281,13 +395,21 @@ def _decode_cached_picked(input_ids, model, max_length, picker, cg=False):
                     # the capture ran nothing: lengths, caches, static_ids and sequences are as the eager step left them
             ip.sequence_len_offset += 1
             seqlen += 1
-    return DecoderOnlyOutput(sequences=sequences.to(input_ids.dtype), scores=tuple(scores))
+            if poll is not None and poll.all_finished():
+                break
+        lengths = None
+        if picker.eos_token_id is not None:
+            sequences, lengths = _trim_at_eos(sequences, seqlen_og, picker.eos_token_id, picker.pad_token_id)
+    return DecoderOnlyOutput(sequences=sequences.to(input_ids.dtype), scores=tuple(scores), lengths=lengths)
 
 
-def _run_loop(input_ids, model, max_length, pick, cg, kv_cache, picker=None):
+def _run_loop(input_ids, model, max_length, pick, cg, kv_cache, picker=None, stop_check_every=None):
     if picker is not None:
         if kv_cache:
-            return _decode_cached_picked(input_ids, model, max_length, picker, cg=cg)
+            return _decode_cached_picked(input_ids, model, max_length, picker, cg=cg, stop_check_every=stop_check_every)
+        if picker.controlled:
+            raise ValueError('generation: repetition_penalty, eos_token_id, pad_token_id and min_length need kv_cache=True '
+                             '(the loops without a cache are the reference\'s, statement for statement)')
         pick = picker.loop_pick(input_ids)
     if kv_cache:
         return _decode_cached(input_ids, model, max_length, pick, cg=cg)
@@ -296,37 +418,55 @@ def _run_loop(input_ids, model, max_length, pick, cg, kv_cache, picker=None):
     return _decode(input_ids, model, max_length, pick)
 
 
-def _picker(input_ids, do_sample, temperature, top_k, top_p, rng_state, device_pick):
+def _picker(input_ids, do_sample, temperature, top_k, top_p, rng_state, device_pick, repetition_penalty=1.0,
+            eos_token_id=None, pad_token_id=None, min_length=0, stop_check_every=None):
     """None when no option of the device pick is given: the loops then run exactly as before."""
-    if not (device_pick or temperature != 1.0 or top_k != 0 or top_p != 1.0 or rng_state is not None):
+    if stop_check_every is not None and stop_check_every < 1:
+        raise ValueError('generation: stop_check_every must be >= 1')
+    if not (device_pick or temperature != 1.0 or top_k != 0 or top_p != 1.0 or rng_state is not None
+            or repetition_penalty != 1.0 or eos_token_id is not None or pad_token_id is not None or min_length != 0):
         return None
-    return _Picker(do_sample, temperature, top_k, top_p, rng_state, input_ids.device)
+    return _Picker(do_sample, temperature, top_k, top_p, rng_state, input_ids.device, repetition_penalty, eos_token_id,
+                   pad_token_id, min_length)
+
+
+_CONTROLS_DOC = """repetition_penalty, eos_token_id, pad_token_id (default: the EOS id), min_length (absolute, prompt included): the
+    controls of bp_pick_token_ctl, kv_cache=True only; any of them selects the device pick.  With an EOS id a row ends at its
+    first EOS behind the prompt, holds the pad behind it, `sequences` is cut to the longest row and `lengths` (batch,) int64
+    reports every row's end; the loop asks every `stop_check_every` steps whether all rows have ended (_StopPoll)."""
 
 
 def greedy_decode(input_ids, model, max_length, cg=False, kv_cache=False, temperature=1.0, top_k=0, top_p=1.0,
-                  rng_state=None, device_pick=False):
+                  rng_state=None, device_pick=False, repetition_penalty=1.0, eos_token_id=None, pad_token_id=None,
+                  min_length=0, stop_check_every=None):
     """input_ids (batch, seq_len) -> sequences (batch, max_length - 1): argmax continuation.
     cg=True: one captured full-width forward replayed per token (CUDA tensors only), see _decode_graphed.
     kv_cache=True: prefill once, then one cached step per token (with cg=True: one captured step), see _decode_cached.
     device_pick=True: the argmax runs in bp_pick_token (on CPU tensors: _eager_pick), with kv_cache and cg inside the
-    captured step (_decode_cached_picked); the sampling options are accepted for symmetry and do not change an argmax."""
-    picker = _picker(input_ids, False, temperature, top_k, top_p, rng_state, device_pick)
-    return _run_loop(input_ids, model, max_length, lambda logits: torch.argmax(logits, dim=-1), cg, kv_cache, picker)
+    captured step (_decode_cached_picked); the sampling options are accepted for symmetry and do not change an argmax.
+    repetition_penalty, eos_token_id, pad_token_id, min_length, stop_check_every: see _CONTROLS_DOC."""
+    picker = _picker(input_ids, False, temperature, top_k, top_p, rng_state, device_pick, repetition_penalty, eos_token_id,
+                     pad_token_id, min_length, stop_check_every)
+    return _run_loop(input_ids, model, max_length, lambda logits: torch.argmax(logits, dim=-1), cg, kv_cache, picker,
+                     stop_check_every)
 
 
 def sample(input_ids, model, max_length, cg=False, kv_cache=False, temperature=1.0, top_k=0, top_p=1.0, rng_state=None,
-           device_pick=False):
+           device_pick=False, repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, min_length=0,
+           stop_check_every=None):
     """Ancestral sampling from softmax(logits) (reference :23-48); cg / kv_cache as in greedy_decode.
     temperature, top_k (ties at the threshold kept, as the reference's top_k_filter, training/run_pplm.py:569-581), top_p:
     the usual filters; any of them, an `rng_state` or device_pick=True selects the device pick (bp_pick_token, contract in
     include/bp_hip.h; _eager_pick on CPU tensors).  rng_state: int64 {seed, offset} (bp_hip.new_rng_state), drawn from
     torch's generator when None; the token at sequence position t of row b is a pure function of (logits, rng_state, b, t),
-    so cached, graphed and growing-prefix runs under one rng_state draw the same numbers."""
-    picker = _picker(input_ids, True, temperature, top_k, top_p, rng_state, device_pick)
+    so cached, graphed and growing-prefix runs under one rng_state draw the same numbers.
+    repetition_penalty, eos_token_id, pad_token_id, min_length, stop_check_every: see _CONTROLS_DOC."""
+    picker = _picker(input_ids, True, temperature, top_k, top_p, rng_state, device_pick, repetition_penalty, eos_token_id,
+                     pad_token_id, min_length, stop_check_every)
 
     def pick(logits):
         return torch.distributions.Categorical(logits=torch.log_softmax(logits.float(), dim=-1)).sample()
-    return _run_loop(input_ids, model, max_length, pick, cg, kv_cache, picker)
+    return _run_loop(input_ids, model, max_length, pick, cg, kv_cache, picker, stop_check_every)
 
 
 class GenerationMixin:
@@ -338,13 +478,17 @@ class GenerationMixin:
         return output if return_dict_in_generate else output.sequences
 
     def generate(self, input_ids, max_length, return_dict_in_generate=False, output_scores=False, cg=False,
-                 kv_cache=False, temperature=1.0, top_k=0, top_p=1.0, rng_state=None, device_pick=False):
+                 kv_cache=False, temperature=1.0, top_k=0, top_p=1.0, rng_state=None, device_pick=False,
+                 repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, min_length=0, stop_check_every=None):
         return self._generate(greedy_decode, input_ids, max_length, return_dict_in_generate, output_scores, cg, kv_cache,
                               temperature=temperature, top_k=top_k, top_p=top_p, rng_state=rng_state,
-                              device_pick=device_pick)
+                              device_pick=device_pick, repetition_penalty=repetition_penalty, eos_token_id=eos_token_id,
+                              pad_token_id=pad_token_id, min_length=min_length, stop_check_every=stop_check_every)
 
     def sample(self, input_ids, max_length, return_dict_in_generate=False, output_scores=False, cg=False,
-               kv_cache=False, temperature=1.0, top_k=0, top_p=1.0, rng_state=None, device_pick=False):
+               kv_cache=False, temperature=1.0, top_k=0, top_p=1.0, rng_state=None, device_pick=False,
+               repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, min_length=0, stop_check_every=None):
         return self._generate(sample, input_ids, max_length, return_dict_in_generate, output_scores, cg, kv_cache,
                               temperature=temperature, top_k=top_k, top_p=top_p, rng_state=rng_state,
-                              device_pick=device_pick)
+                              device_pick=device_pick, repetition_penalty=repetition_penalty, eos_token_id=eos_token_id,
+                              pad_token_id=pad_token_id, min_length=min_length, stop_check_every=stop_check_every)

@@ -44,7 +44,9 @@ extern "C" {
                               bp_sense_rows_dot (dot products of the cached positions' sense vectors with one vector)
                               added: KV-cached decoding of the intervened Backpacks;
                               (still 11, a purely additive entry point: bp_pick_token, token selection on the device --
-                              argmax, temperature, top-k, top-p -- and BP_ERR_SAMPLING) */
+                              argmax, temperature, top-k, top-p -- and BP_ERR_SAMPLING;
+                              and another: bp_pick_token_ctl, the same pick with a repetition penalty, an EOS mask below
+                              a minimal length and finished flags) */
 
 /* element type of q/k/v/out/content tensors */
 #define BP_DTYPE_F16 0
@@ -61,7 +63,8 @@ extern "C" {
 #define BP_ERR_DROPOUT -7     /* p_dropout outside [0,1), rng_state NULL with p > 0, or a shape the dropout path lacks */
 #define BP_ERR_QUEUE_WS -8    /* persistent launch with queue_ws == NULL on a stream that is being captured            */
 #define BP_ERR_WORKSPACE -9   /* a caller-provided workspace is smaller than the entry point's *_ws_floats() query     */
-#define BP_ERR_SAMPLING -10   /* bp_pick_token: top_p outside (0, 1], or do_sample without an rng_state                */
+#define BP_ERR_SAMPLING -10   /* bp_pick_token: top_p outside (0, 1], or do_sample without an rng_state; bp_pick_token_ctl:
+                                 also a repetition_penalty not finite and > 0 or without sequences, an EOS id without flags */
 
 #define BP_QUEUE_WS_BYTES 64   /* `queue_ws` of the persistent sense-mix launches */
 
@@ -646,6 +649,43 @@ int bp_pick_token(const void *logits, int64_t *tokens, int64_t *sequences, float
                   const int32_t *counters, int batch, int vocab, int64_t row_stride, int64_t tokens_stride,
                   int64_t seq_stride, int seq_cols, int do_sample, float temperature, int top_k, float top_p, int dtype,
                   bp_stream_t stream);
+
+/*
+ * bp_pick_token_ctl -- bp_pick_token with the controls a generation loop needs to stop and not to loop: a repetition
+ * penalty over the row's history (the reference's control baseline samples with temperature, top_k and
+ * repetition_penalty, training/run_pplm.py:544-550, over set(output_so_far[0].tolist())), an EOS id that is masked below a
+ * minimal length, and per-row finished flags.  Arguments as bp_pick_token's, and
+ *   finished   optional int32 (batch) on the device, read and written
+ * Per row b, with c = counters[b] (0 when counters is NULL):
+ *   finished on entry (finished != NULL and finished[b] != 0): the token is pad_token_id, written to tokens and to column c
+ *           of sequences as usual; no draw is made; stats = {0, 0, 0, u} (u = 0 when not do_sample); finished[b] stays set
+ *   history H_b = the set of values of sequences[b, 0 : min(c, seq_cols)] inside [0, vocab): values outside are ignored,
+ *           duplicates count once, sequences == NULL or c <= 0 give the empty set -- the prompt plus what was generated
+ *   pen(z)  z for i not in H_b; for i in H_b: z * theta when z < 0, otherwise z * rtheta, theta = repetition_penalty,
+ *           rtheta = 1 / theta rounded to fp32 (as 1 / temperature is): ONE fp32 multiplication either way; a NaN or an
+ *           infinity passes through it.  theta == 1 skips the history altogether
+ *   EOS     eos_token_id >= 0 and c < min_length: the EOS entry counts as -inf, in the greedy answer, in top_k, in top_p
+ *           and in the draw.  min_length is the absolute sequence length, prompt included
+ *   greedy  (do_sample == 0, and the answer of degenerate rows) the lowest index of the maximum of pen(float(x_i)) under
+ *           the EOS mask, a NaN largest; temperature does not enter
+ *   sampling  z_i = pen(float(x_i) * (1 / temperature)) under the EOS mask, then top_k, top_p, u and the vocabulary-order
+ *           draw exactly as bp_pick_token states them, on 40-bit fixed-point masses; stats reports the lowest kept z, the
+ *           log-sum-exp, the kept count and u in terms of these z
+ *   after the pick: finished != NULL, eos_token_id >= 0 and token == eos_token_id set finished[b] = 1 (the EOS token
+ *           itself is written, not the pad)
+ * With every control off (repetition_penalty == 1, eos_token_id < 0, finished == NULL) tokens and stats are bp_pick_token's,
+ * bit for bit.  The history is a bitmap in LDS, one bit per vocabulary entry, which bounds vocab by 2^19 under a penalty.
+ * Errors, before any launch: everything bp_pick_token rejects, with its codes; BP_ERR_SAMPLING (repetition_penalty not
+ * finite or not > 0; repetition_penalty != 1 with sequences == NULL; eos_token_id >= 0 with finished == NULL);
+ * BP_ERR_SHAPE (eos_token_id >= vocab; pad_token_id outside [0, vocab) when finished != NULL; min_length < 0; a
+ * misaligned finished; vocab > 2^19 with repetition_penalty != 1).
+ */
+int bp_pick_token_ctl(const void *logits, int64_t *tokens, int64_t *sequences, float *stats, const uint64_t *rng_state,
+                      const int32_t *counters, int32_t *finished,
+                      int batch, int vocab, int64_t row_stride, int64_t tokens_stride, int64_t seq_stride, int seq_cols,
+                      int do_sample, float temperature, int top_k, float top_p,
+                      float repetition_penalty, int eos_token_id, int pad_token_id, int min_length,
+                      int dtype, bp_stream_t stream);
 
 #ifdef __cplusplus
 }

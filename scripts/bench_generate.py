@@ -5,13 +5,18 @@ generate(..., kv_cache=True) eagerly and with cg=True (one captured decode step 
     python scripts/bench_generate.py [--batch 1] [--prompt 16] [--max-length 128] [--model small] [--modes off,cached]
                                      [--legs full,kv] [--intervention none|weighted|weighted-anneal|replaced]
                                      [--pick torch|device|torch,device] [--sample] [--temperature T] [--top-k K] [--top-p P]
-                                     [--repeats N]
+                                     [--repetition-penalty R] [--eos ID] [--min-length L] [--stop-check-every N]
+                                     [--variant NAME:option=value,...] [--repeats N]
 
 --pick chooses how the next token is picked: `torch` is torch.argmax / torch.distributions.Categorical on the host side
 of the loop, `device` the bp_pick_token kernel (device_pick=True; with kv_cache and cg inside the captured step).  With
 both, the two picks alternate inside every leg, --repeats times each, in one process: the line then carries the median
 and every run of each (`<leg>_<pick>_ms`, `<leg>_<pick>_ms_runs`).  --sample times sample() instead of generate();
---temperature / --top-k / --top-p go to the device pick only (the torch pick has no such options).
+--temperature / --top-k / --top-p go to the device pick only (the torch pick has no such options), and so do the controls
+of bp_pick_token_ctl: --repetition-penalty, --eos (an id that never occurs, e.g. 50263 of the padded vocabulary, times the
+polling of the finished flags alone), --min-length and --stop-check-every (kv legs only).  --variant adds a further pick
+that alternates with the others: the device pick with some generation options replaced, e.g.
+`--variant pen:repetition_penalty=1.2 --variant n4:eos_token_id=50263,stop_check_every=4`.
 
 --intervention wraps the model in the control-experiment classes of src/models/intervened_models.py (seeded
 content_weights in [0, 3); for the annealed form a scale of 6 / median of the similarity sums at half the final length, so
@@ -43,6 +48,11 @@ def main():
     ap.add_argument('--temperature', type=float, default=1.0)
     ap.add_argument('--top-k', type=int, default=0)
     ap.add_argument('--top-p', type=float, default=1.0)
+    ap.add_argument('--repetition-penalty', type=float, default=1.0)
+    ap.add_argument('--eos', type=int, default=None, help='eos_token_id of the device pick')
+    ap.add_argument('--min-length', type=int, default=0)
+    ap.add_argument('--stop-check-every', type=int, default=None)
+    ap.add_argument('--variant', action='append', default=[], help='NAME:option=value,... : the device pick with these options')
     ap.add_argument('--repeats', type=int, default=1)
     a = ap.parse_args()
     from bench import MODELS
@@ -68,10 +78,22 @@ def main():
                    new_tokens=a.max_length - 1 - a.prompt, sense_table=mode, **extra)
         outs = {}
         picks = a.pick.split(',')
-        plain = picks == ['torch'] and not a.sample and a.repeats == 1      # the line of earlier revisions, key for key
+        plain = picks == ['torch'] and not a.sample and a.repeats == 1 and not a.variant   # the line of earlier revisions, key for key
         if not plain:
             res.update(sample=a.sample, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p)
         options = dict(torch={}, device=dict(device_pick=True, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p))
+        controls = dict(repetition_penalty=a.repetition_penalty, eos_token_id=a.eos, min_length=a.min_length,
+                        stop_check_every=a.stop_check_every)
+        controls = {k: v for k, v in controls.items() if v != dict(repetition_penalty=1.0, min_length=0).get(k)}
+        if controls:                                   # without them the call is the one of earlier revisions
+            options['device'].update(controls)
+            res.update(controls)
+        for spec in a.variant:
+            name, _, pairs = spec.partition(':')
+            changed = {k: json.loads(v) for k, v in (pair.split('=') for pair in pairs.split(',') if pair)}
+            options[name] = dict(options['device'], **changed)
+            res['variant_' + name] = changed
+            picks = picks + [name]
         decode = model.sample if a.sample else model.generate
         for key, cg, kv in legs:
             runs = {pick: [] for pick in picks}
