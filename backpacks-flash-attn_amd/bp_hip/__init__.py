@@ -90,6 +90,9 @@ SIGNATURES = {
     'bp_sense_rows_dot': (_i32, [_ptr] * 6 + [_i32] * 4 + [_i64] + [_i64] * 6 + [_i32, _ptr]),
     'bp_pick_token': (_i32, [_ptr] * 6 + [_i32] * 2 + [_i64] * 3 + [_i32] * 2 + [_f32, _i32, _f32, _i32, _ptr]),
     'bp_pick_token_ctl': (_i32, [_ptr] * 7 + [_i32] * 2 + [_i64] * 3 + [_i32] * 2 + [_f32, _i32, _f32, _f32] + [_i32] * 4 + [_ptr]),
+    'bp_beam_pick_ws_floats': (_i64, [_i32] * 2),
+    'bp_beam_pick': (_i32, [_ptr] * 8 + [_i64] + [_i32] * 3 + [_i64] * 3 + [_i32] * 4 + [_ptr]),
+    'bp_beam_copy_rows': (_i32, [_ptr] * 3 + [_i32] + [_ptr] * 2 + [_i32] * 3 + [_ptr]),
 }
 
 
@@ -1193,3 +1196,78 @@ def pick_token(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rng
           sequences.shape[1] if sequences is not None else 0, int(bool(do_sample)), float(temperature), int(top_k),
           float(top_p), _PICK_DTYPES[logits.dtype])
     return (tokens, stats) if return_stats else tokens
+
+
+# ---- beam search on the device (C ABI bp_beam_pick, bp_beam_copy_rows) ------------------------------------------------------------------------------------------------
+
+_beam_ws = {}   # (device, groups, beam_width) -> workspace: one per shape, so a captured step keeps reading its own
+
+
+def beam_pick(logits, beam_scores, parent, beam_width, finished=None, tokens=None, sequences=None, counters=None,
+              eos_token_id=None, pad_token_id=None):
+    """One beam-search step on the device (contract in include/bp_hip.h): logits (groups * W, vocab) fp16 / bf16 / fp32 (any
+    row stride), beam_scores (groups * W,) fp32 and finished (groups * W,) int32 read and written, parent (groups * W,) int32
+    written with the global row every slot continues.  tokens / sequences / counters as pick_token's.  Two launches that
+    read no host value (legal inside a HIP-graph capture).  Returns tokens."""
+    _require_cuda(logits, beam_scores, parent, finished, tokens, sequences, counters)
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.dtype not in _PICK_DTYPES:
+        raise RuntimeError('bp_hip.beam_pick: logits must be (groups * W, vocab) fp16 / bf16 / fp32 with a contiguous last dimension')
+    rows, vocab = logits.shape
+    beam_width = int(beam_width)
+    if beam_width < 1 or rows % beam_width:
+        raise RuntimeError('bp_hip.beam_pick: the rows of logits must be a multiple of beam_width >= 1')
+    groups = rows // beam_width
+    for name, t, dtype in (('beam_scores', beam_scores, torch.float32), ('parent', parent, torch.int32),
+                           ('finished', finished, torch.int32), ('counters', counters, torch.int32)):
+        if t is not None and (t.shape != (rows,) or t.dtype != dtype or not t.is_contiguous()):
+            raise RuntimeError(f'bp_hip.beam_pick: {name} must be a contiguous (groups * W,) {dtype} tensor')
+    if tokens is None:
+        tokens = torch.empty((rows,), dtype=torch.int64, device=logits.device)
+    if tokens.dtype != torch.int64 or tokens.numel() != rows or tokens.shape[0] != rows:
+        raise RuntimeError('bp_hip.beam_pick: tokens must be int64 with groups * W elements along its first dimension')
+    if sequences is not None and (sequences.dim() != 2 or sequences.shape[0] != rows or sequences.dtype != torch.int64
+                                  or sequences.stride(1) != 1):
+        raise RuntimeError('bp_hip.beam_pick: sequences must be (groups * W, cols) int64 with a contiguous last dimension')
+    if pad_token_id is None:
+        pad_token_id = eos_token_id if eos_token_id is not None else 0
+    key = (logits.device, groups, beam_width)
+    ws = _beam_ws.get(key)
+    if ws is None:
+        floats = lib().bp_beam_pick_ws_floats(groups, beam_width)
+        ws = _beam_ws[key] = torch.empty((max(int(floats), 4),), dtype=torch.float32, device=logits.device)
+    _call('bp_beam_pick', logits.device,
+          logits.data_ptr(), beam_scores.data_ptr(), finished.data_ptr() if finished is not None else None,
+          parent.data_ptr(), tokens.data_ptr(), sequences.data_ptr() if sequences is not None else None,
+          counters.data_ptr() if counters is not None else None, ws.data_ptr(), ws.numel(),
+          groups, beam_width, vocab, logits.stride(0), tokens.stride(0) if rows > 1 else 1,
+          sequences.stride(0) if sequences is not None else 0, sequences.shape[1] if sequences is not None else 0,
+          -1 if eos_token_id is None else int(eos_token_id), int(pad_token_id), _PICK_DTYPES[logits.dtype])
+    return tokens
+
+
+BEAM_COPY_MAX_SETS = 32
+
+
+def beam_copy_rows(tensors, parent, lengths, first_position):
+    """Rows r with parent[r] != r of every tensor take positions [first_position, lengths[r]) of row parent[r], in ONE
+    launch for all tensors (at most 32).  Each tensor is (rows, positions, ...) with everything behind the first
+    dimension contiguous; parent, lengths (rows,) int32 on the device.  The caller guarantees
+    parent[parent[r]] == parent[r] (beam_pick's slot rule does).  The tensors' addresses are read now: a captured graph
+    keeps copying THESE buffers."""
+    tensors = list(tensors)
+    _require_cuda(parent, lengths, *tensors)
+    if not tensors or len(tensors) > BEAM_COPY_MAX_SETS:
+        raise RuntimeError(f'bp_hip.beam_copy_rows: between 1 and {BEAM_COPY_MAX_SETS} tensors, got {len(tensors)}')
+    rows = parent.shape[0]
+    for name, t in (('parent', parent), ('lengths', lengths)):
+        if t.shape != (rows,) or t.dtype != torch.int32 or not t.is_contiguous():
+            raise RuntimeError(f'bp_hip.beam_copy_rows: {name} must be a contiguous (rows,) int32 tensor')
+    for t in tensors:
+        if t.dim() < 2 or t.shape[0] != rows or not t[0].is_contiguous():
+            raise RuntimeError('bp_hip.beam_copy_rows: every tensor must be (rows, positions, ...), contiguous behind the rows')
+    n = len(tensors)
+    bases = (ctypes.c_void_p * n)(*[t.data_ptr() for t in tensors])
+    strides = (ctypes.c_int64 * n)(*[t.stride(0) * t.element_size() for t in tensors])
+    pos_bytes = (ctypes.c_int64 * n)(*[t[0, 0].numel() * t.element_size() for t in tensors])
+    _call('bp_beam_copy_rows', parent.device, bases, strides, pos_bytes, n, parent.data_ptr(), lengths.data_ptr(), rows,
+          int(first_position), min(t.shape[1] for t in tensors))

@@ -956,4 +956,60 @@ int bp_pick_token_ctl(const void *logits, int64_t *tokens, int64_t *sequences, f
     return launch_status(bp::launch_pick_token_ctl(p, dtype, static_cast<hipStream_t>(stream)));
 }
 
+// ---- beam search (bp_beam_pick, bp_beam_copy_rows) ----
+
+int64_t bp_beam_pick_ws_floats(int groups, int beam_width) {
+    if (groups < 1 || beam_width < 1 || beam_width > 8) return 0;
+    return (int64_t)groups * beam_width * 16;   // eight 64-bit keys a row
+}
+
+int bp_beam_pick(const void *logits, float *beam_scores, int32_t *finished, int32_t *parent, int64_t *tokens,
+                 int64_t *sequences, const int32_t *counters, float *ws, int64_t ws_floats,
+                 int groups, int beam_width, int vocab, int64_t row_stride, int64_t tokens_stride, int64_t seq_stride,
+                 int seq_cols, int eos_token_id, int pad_token_id, int dtype, bp_stream_t stream) {
+    if (dtype != BP_DTYPE_F16 && dtype != BP_DTYPE_BF16 && dtype != BP_DTYPE_F32) return BP_ERR_DTYPE;
+    if (groups < 1 || beam_width < 1 || beam_width > 8 || (int64_t)groups * beam_width > 0x7fffffffLL) return BP_ERR_SHAPE;
+    if (vocab < beam_width || vocab > (1 << 23) || row_stride < vocab || tokens_stride < 1) return BP_ERR_SHAPE;
+    if (logits == nullptr || beam_scores == nullptr || parent == nullptr || tokens == nullptr || ws == nullptr)
+        return BP_ERR_SHAPE;
+    if (sequences != nullptr && (seq_cols < 1 || seq_stride < seq_cols)) return BP_ERR_SHAPE;
+    const uintptr_t elem = dtype == BP_DTYPE_F32 ? 4 : 2;
+    if (reinterpret_cast<uintptr_t>(logits) % elem || reinterpret_cast<uintptr_t>(beam_scores) % 4
+        || reinterpret_cast<uintptr_t>(finished) % 4 || reinterpret_cast<uintptr_t>(parent) % 4
+        || reinterpret_cast<uintptr_t>(tokens) % 8 || reinterpret_cast<uintptr_t>(sequences) % 8
+        || reinterpret_cast<uintptr_t>(counters) % 4 || reinterpret_cast<uintptr_t>(ws) % 8)
+        return BP_ERR_SHAPE;
+    if (eos_token_id >= vocab) return BP_ERR_SHAPE;
+    if (finished != nullptr && (pad_token_id < 0 || pad_token_id >= vocab)) return BP_ERR_SHAPE;
+    if (eos_token_id >= 0 && finished == nullptr) return BP_ERR_SAMPLING;
+    if (ws_floats < bp_beam_pick_ws_floats(groups, beam_width)) return BP_ERR_WORKSPACE;
+    bp::BeamPickParams p{};
+    p.logits = logits; p.beam_scores = beam_scores; p.finished = finished; p.parent = parent; p.tokens = tokens;
+    p.sequences = sequences; p.counters = counters; p.ws = ws;
+    p.row_stride = row_stride; p.tokens_stride = tokens_stride; p.seq_stride = seq_stride;
+    p.groups = groups; p.beam_width = beam_width; p.vocab = vocab; p.seq_cols = seq_cols;
+    p.eos = eos_token_id < 0 ? -1 : eos_token_id; p.pad = finished != nullptr ? pad_token_id : 0;
+    return launch_status(bp::launch_beam_pick(p, dtype, static_cast<hipStream_t>(stream)));
+}
+
+int bp_beam_copy_rows(const void *const *bases, const int64_t *row_strides, const int64_t *pos_bytes, int nsets,
+                      const int32_t *parent, const int32_t *lengths, int rows, int first_position, int max_positions,
+                      bp_stream_t stream) {
+    if (nsets < 1 || nsets > bp::kBeamCopyMaxSets || rows < 1 || rows > 65535) return BP_ERR_SHAPE;
+    if (bases == nullptr || row_strides == nullptr || pos_bytes == nullptr || parent == nullptr || lengths == nullptr)
+        return BP_ERR_SHAPE;
+    if (reinterpret_cast<uintptr_t>(parent) % 4 || reinterpret_cast<uintptr_t>(lengths) % 4) return BP_ERR_SHAPE;
+    if (first_position < 0 || max_positions < 0) return BP_ERR_SHAPE;
+    bp::BeamCopyParams p{};
+    for (int i = 0; i < nsets; ++i) {
+        if (bases[i] == nullptr || !aligned16(bases[i])) return BP_ERR_SHAPE;
+        if (pos_bytes[i] < 4 || pos_bytes[i] % 4 != 0 || row_strides[i] % 16 != 0) return BP_ERR_SHAPE;
+        if (row_strides[i] < pos_bytes[i] * (int64_t)max_positions) return BP_ERR_SHAPE;   // a row holds its positions
+        p.base[i] = const_cast<void *>(bases[i]); p.row_stride[i] = row_strides[i]; p.pos_bytes[i] = pos_bytes[i];
+    }
+    p.parent = parent; p.lengths = lengths;
+    p.nsets = nsets; p.rows = rows; p.first_position = first_position; p.max_positions = max_positions;
+    return launch_status(bp::launch_beam_copy_rows(p, static_cast<hipStream_t>(stream)));
+}
+
 }  // extern "C"

@@ -336,4 +336,31 @@ struct PickParams {
 hipError_t launch_pick_token(const PickParams &p, int dtype, hipStream_t stream);
 hipError_t launch_pick_token_ctl(const PickParams &p, int dtype, hipStream_t stream);
 
+// bp_beam_pick (beam_pick.hip): one beam-search step, rows r = g * beam_width + w
+struct BeamPickParams {
+    const void *logits;          // (groups * beam_width, vocab) 16-bit or fp32, element stride row_stride; only read
+    float *beam_scores;          // (rows) read and written
+    int32_t *finished;           // (rows) read and written; NULL only without an EOS id
+    int32_t *parent;             // (rows) written: the global row every slot continues
+    int64_t *tokens;             // token of slot r at tokens[r * tokens_stride]
+    int64_t *sequences;          // optional: row r, column counters[r] receives the token when 0 <= column < seq_cols
+    const int32_t *counters;     // optional (rows); NULL: 0
+    float *ws;                   // bp_beam_pick_ws_floats(groups, beam_width) floats, 8-byte aligned
+    int64_t row_stride, tokens_stride, seq_stride;
+    int groups, beam_width, vocab, seq_cols;
+    int eos, pad;                // eos < 0: none
+};
+hipError_t launch_beam_pick(const BeamPickParams &p, int dtype, hipStream_t stream);
+
+// bp_beam_copy_rows (beam_copy.hip): rows r with parent[r] != r take positions [first_position, lengths[r]) of row parent[r]
+constexpr int kBeamCopyMaxSets = 32;
+struct BeamCopyParams {
+    void *base[kBeamCopyMaxSets];
+    int64_t row_stride[kBeamCopyMaxSets];   // bytes
+    int64_t pos_bytes[kBeamCopyMaxSets];    // bytes per position, positions contiguous in a row
+    const int32_t *parent, *lengths;        // (rows)
+    int nsets, rows, first_position, max_positions;
+};
+hipError_t launch_beam_copy_rows(const BeamCopyParams &p, hipStream_t stream);
+
 }  // namespace bp

@@ -85,6 +85,12 @@ class _Intervened(nn.Module, GenerationMixin, SenseIntervention):
             cached(input_ids, position_ids, inference_params, intervention=self)
         return CausalLMOutput(logits=self.backpack_network.lm_head(mixed))
 
+    def beam_search(self, *args, **kwargs):
+        # the mixin's beam search reorders the wrapped network's caches between slots, not the wrapper's own per-row
+        # state (ids, sims, dots, weights)
+        raise NotImplementedError('beam_search is not available on the sense-intervened wrappers: their per-row cache '
+                                  'state is not reordered between beam slots')
+
     def _stages(self, input_ids, position_ids):
         t = self.backpack_network.transformer
         hidden = t.gpt2_model(input_ids, position_ids=position_ids, inference_params=None)

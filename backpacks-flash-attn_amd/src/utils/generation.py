@@ -469,6 +469,241 @@ def sample(input_ids, model, max_length, cg=False, kv_cache=False, temperature=1
     return _run_loop(input_ids, model, max_length, pick, cg, kv_cache, picker, stop_check_every)
 
 
+# ---- beam search on the KV cache: bp_beam_pick / bp_beam_copy_rows, or their torch restatements on CPU tensors -----------------
+
+@dataclass
+class BeamSearchOutput:
+    sequences: torch.Tensor            # (batch, cols): the best hypothesis of every prompt
+    scores: torch.Tensor               # (batch,) fp32: its sum of log-probabilities
+    lengths: torch.Tensor              # (batch,) int64: its length, prompt included (1 + the column of its EOS, if any)
+    beam_sequences: torch.Tensor       # (batch, num_beams, cols): every hypothesis, in slot order
+    beam_scores: torch.Tensor          # (batch, num_beams) fp32
+    beam_lengths: torch.Tensor         # (batch, num_beams) int64
+
+
+def _eager_beam_pick(logits, beam_scores, finished, beam_width, eos_token_id=None, pad_token_id=None):
+    """The contract of bp_beam_pick (include/bp_hip.h) in torch ops, for tensors the kernel does not take (CPU):
+    (parent int32, tokens int64, new beam_scores fp32, new finished int32 or None), all (groups * W,); nothing is written.
+    A live row's candidates score s_w + (float(x_v) - lse) in fp32 (all -inf for a row with a NaN or +inf, or without a
+    finite logit), a finished row has the one candidate (w, pad) at s_w; a NaN score counts as -inf; candidates rank by
+    (score descending, w ascending, v ascending); the W winners in rank order keep their parent's slot when it is free, the
+    rest take the lowest free slot, so parent[parent[r]] == parent[r].  The sum of exponentials is a plain fp32 sum here
+    and 40-bit fixed point in the kernel: the two agree wherever two candidates are not within rounding of each other."""
+    x = logits.float()
+    rows, vocab = x.shape
+    W = int(beam_width)
+    if not 1 <= W <= vocab:
+        raise ValueError('beam pick: beam_width must be in 1..vocab')
+    groups = rows // W
+    dev = x.device
+    neg_inf = torch.full((), float('-inf'), dtype=torch.float32, device=dev)
+    pad = pad_token_id if pad_token_id is not None else (eos_token_id if eos_token_id is not None else 0)
+    fin = finished != 0 if finished is not None else torch.zeros((rows,), dtype=torch.bool, device=dev)
+    m = x.max(dim=-1).values
+    degenerate = torch.isnan(x).any(dim=-1) | (m == float('inf')) | (m == float('-inf'))
+    safe_m = torch.where(degenerate, torch.zeros_like(m), m)
+    lse = safe_m + torch.log(torch.exp(x - safe_m[:, None]).sum(dim=-1))
+    cand = beam_scores.float()[:, None] + (x - lse[:, None])
+    cand = torch.where(degenerate[:, None] | torch.isnan(cand), neg_inf, cand) + 0.0
+    top_s, top_v = torch.sort(cand, dim=-1, descending=True, stable=True)       # ties: ascending v
+    top_s, top_v = top_s[:, :W].clone(), top_v[:, :W].clone()
+    valid = torch.ones((rows, W), dtype=torch.bool, device=dev)
+    frozen = beam_scores.float()
+    frozen = torch.where(torch.isnan(frozen), neg_inf, frozen) + 0.0
+    top_s[:, 0] = torch.where(fin, frozen, top_s[:, 0])
+    top_v[:, 0] = torch.where(fin, torch.full_like(top_v[:, 0], pad), top_v[:, 0])
+    valid[:, 1:] = ~fin[:, None]
+    # the group's candidates in (w, rank within w) order: a stable sort by score keeps (w, v) ascending among equals
+    g_s, g_v, g_ok = top_s.view(groups, W * W), top_v.view(groups, W * W), valid.view(groups, W * W)
+    g_w = torch.arange(W, device=dev).repeat_interleave(W).expand(groups, W * W)
+    order = torch.sort(g_s, dim=-1, descending=True, stable=True).indices
+    order = torch.gather(order, 1, torch.sort((~torch.gather(g_ok, 1, order)).int(), dim=-1, stable=True).indices)[:, :W]
+    win_s, win_v, win_w = torch.gather(g_s, 1, order), torch.gather(g_v, 1, order), torch.gather(g_w, 1, order)
+    # slots: winners that find their parent's slot free keep it, the rest take the lowest free one, both in rank order
+    ar = torch.arange(groups, device=dev)
+    free = torch.ones((groups, W), dtype=torch.bool, device=dev)
+    slot = torch.full((groups, W), -1, dtype=torch.int64, device=dev)
+    for j in range(W):
+        can = free[ar, win_w[:, j]]
+        slot[:, j] = torch.where(can, win_w[:, j], slot[:, j])
+        free[ar[can], win_w[can, j]] = False
+    for j in range(W):
+        need = slot[:, j] < 0
+        low = free.int().argmax(dim=1)
+        slot[:, j] = torch.where(need, low, slot[:, j])
+        free[ar[need], low[need]] = False
+    at = (ar[:, None] * W + slot).reshape(-1)
+    src = (ar[:, None] * W + win_w).reshape(-1)
+    parent = torch.empty((rows,), dtype=torch.int32, device=dev)
+    parent[at] = src.to(torch.int32)
+    tokens = torch.empty((rows,), dtype=torch.int64, device=dev)
+    tokens[at] = win_v.reshape(-1)
+    scores = torch.empty((rows,), dtype=torch.float32, device=dev)
+    scores[at] = win_s.reshape(-1)
+    new_finished = None
+    if finished is not None:
+        hit = fin[src]
+        if eos_token_id is not None and eos_token_id >= 0:
+            hit = hit | (win_v.reshape(-1) == eos_token_id)
+        new_finished = torch.empty((rows,), dtype=torch.int32, device=dev)
+        new_finished[at] = hit.to(torch.int32)
+    return parent, tokens, scores, new_finished
+
+
+def _eager_beam_copy_rows(tensors, parent, lengths, first_position):
+    """bp_beam_copy_rows in torch ops: rows r with parent[r] != r of every (rows, positions, ...) tensor take positions
+    [first_position, lengths[r]) of row parent[r]."""
+    rows = parent.shape[0]
+    moved = parent.long() != torch.arange(rows, device=parent.device)
+    if not bool(moved.any()):          # every hypothesis kept its slot, the common case late in a search
+        return
+    for t in tensors:
+        pos = torch.arange(t.shape[1], device=t.device)
+        take = moved[:, None] & (pos[None, :] >= first_position) & (pos[None, :] < lengths.long()[:, None])
+        take = take.view(rows, t.shape[1], *([1] * (t.dim() - 2)))
+        t.copy_(torch.where(take, t.index_select(0, parent.long()), t))
+
+
+_BEAM_OWN_CACHES = ('backpack_sense_k', 'backpack_rows', 'backpack_content')
+
+
+def _beam_row_sets(ip, sequences):
+    """What follows a hypothesis from slot to slot, as (rows, positions, ...) tensors: every trunk layer's K/V cache, the
+    sense keys, the sequence buffer, and the Backpack's content -- in table form `backpack_rows` (token ids), in content
+    form `backpack_content` and NOT `backpack_rows`: there it holds b * max_seqlen + j, a pointer into the row's OWN
+    content, which stays where it is while the content it points at is copied."""
+    caches = ip.key_value_memory_dict
+    unknown = [k for k in caches if not isinstance(k, int) and k not in _BEAM_OWN_CACHES]
+    if unknown:
+        raise NotImplementedError(f'beam_search: the cache entries {unknown} hold per-row state that is not reordered')
+    sets = [caches[k] for k in sorted(k for k in caches if isinstance(k, int))]
+    if 'backpack_sense_k' in caches:
+        sets.append(caches['backpack_sense_k'])
+        if 'backpack_content' in caches:
+            content = caches['backpack_content']
+            sets.append(content.view(ip.max_batch_size, ip.max_sequence_len, -1))
+        else:
+            sets.append(caches['backpack_rows'])
+    sets.append(sequences)
+    return sets
+
+
+def beam_search(input_ids, model, max_length, num_beams, eos_token_id=None, pad_token_id=None, length_penalty=0.0, cg=False,
+                stop_check_every=None, **sampling_options):
+    """Beam search on the KV cache: input_ids (batch, seq_len), prompts of equal length -> BeamSearchOutput.  The rows are
+    the prompts repeated num_beams (W, 1..8) times, prefilled once at batch B W (prefilling B rows and fanning out is a
+    later optimisation).  A step is: model step on the picked tokens, lengths + 1, bp_beam_pick (the W best of
+    the group's W x vocab continuations, on the device), bp_beam_copy_rows (the caches and the sequence buffer follow the
+    hypotheses that changed slot; the prompt region is the same within a group and is never copied).  With cg=True the
+    whole step is captured once, after one eager step.  Exactly width - seq_len picks are made, width = max(seq_len,
+    max_length - 1) as in the other loops, so the scores describe the returned tokens.
+    With an EOS id a hypothesis that picks it is frozen: it stays in the beam at its score and competes on it (the common
+    two-heap formulation moves it to a separate list and ranks that list by a length-normalised score; here
+    `length_penalty` acts on the final ranking only), its row keeps stepping on the pad, and the loop ends once a poll
+    (_StopPoll) shows every hypothesis frozen.  Best = the largest score / length ** length_penalty, length = the total
+    length, prompt included; ties go to the lowest slot.  With the default 0 that is the raw sum of log-probabilities, the
+    order used inside the beam.  CPU tensors take _eager_beam_pick / _eager_beam_copy_rows."""
+    if sampling_options:
+        raise ValueError(f'beam_search takes no sampling or penalty option, got {sorted(sampling_options)}')
+    W = int(num_beams)
+    if not 1 <= W <= 8:
+        raise ValueError('beam_search: num_beams must be in 1..8')
+    vocab = getattr(getattr(model, 'config', None), 'vocab_size', None)
+    if vocab is None:                                # a model without a config: its output layer tells, before any prefill
+        vocab = getattr(getattr(model, 'lm_head', None), 'out_features', None)
+    if vocab is not None and W > vocab:
+        raise ValueError('beam_search: num_beams exceeds the vocabulary')
+    if stop_check_every is not None and stop_check_every < 1:
+        raise ValueError('generation: stop_check_every must be >= 1')
+    if (eos_token_id is not None and eos_token_id < 0) or (pad_token_id is not None and pad_token_id < 0):
+        raise ValueError('generation: eos_token_id and pad_token_id must not be negative')
+    if pad_token_id is None:
+        pad_token_id = eos_token_id if eos_token_id is not None else 0
+    batch, seqlen_og = input_ids.shape
+    rows, dev = batch * W, input_ids.device
+    width = max(seqlen_og, max_length - 1)
+    ids = input_ids.repeat_interleave(W, dim=0)
+    # bp_beam_copy_rows wants rows that start on 16-byte boundaries: the cache capacity is rounded up to four positions (the
+    # int32 row index of the Backpack's cache is the narrowest row), the sequence buffer gets the same row stride
+    capacity = (width + 3) // 4 * 4
+    ip = InferenceParams(max_sequence_len=capacity, max_batch_size=rows)
+    ip.lengths_per_sample = torch.zeros((rows,), dtype=torch.int32, device=dev)
+    sequences = torch.zeros((rows, capacity), dtype=torch.int64, device=dev)[:, :width]
+    sequences[:, :seqlen_og] = ids
+    static_ids = torch.zeros((rows, 1), dtype=torch.int64, device=dev)
+    beam_scores = torch.full((rows,), float('-inf'), dtype=torch.float32, device=dev)
+    beam_scores[::W] = 0.0                          # the first pick takes all W winners from beam 0
+    finished = torch.zeros((rows,), dtype=torch.int32, device=dev) if eos_token_id is not None else None
+    parent = torch.arange(rows, dtype=torch.int32, device=dev)
+    with torch.inference_mode():
+        logits = model(ids, inference_params=ip).logits[:, -1]
+        if W > logits.shape[-1]:
+            raise ValueError('beam_search: num_beams exceeds the vocabulary')
+        ip.sequence_len_offset = seqlen_og
+        ip.lengths_per_sample.fill_(seqlen_og)
+        sets = _beam_row_sets(ip, sequences)
+
+        def pick(step_logits):
+            if step_logits.is_cuda:
+                import bp_hip
+                bp_hip.beam_pick(step_logits, beam_scores, parent, W, finished=finished, tokens=static_ids,
+                                 sequences=sequences, counters=ip.lengths_per_sample, eos_token_id=eos_token_id,
+                                 pad_token_id=pad_token_id)
+                bp_hip.beam_copy_rows(sets, parent, ip.lengths_per_sample, seqlen_og)
+                return
+            new_parent, tokens, scores, flags = _eager_beam_pick(step_logits, beam_scores, finished, W, eos_token_id,
+                                                                 pad_token_id)
+            parent.copy_(new_parent)
+            beam_scores.copy_(scores)
+            if finished is not None:
+                finished.copy_(flags)
+            static_ids.view(-1).copy_(tokens)
+            cols = ip.lengths_per_sample.long()
+            ok = cols < width
+            at = torch.arange(rows, device=dev)
+            sequences[at[ok], cols[ok]] = tokens[ok]
+            _eager_beam_copy_rows(sets, parent, ip.lengths_per_sample, seqlen_og)
+
+        def step():
+            step_logits = model(static_ids, inference_params=ip).logits[:, -1]
+            ip.lengths_per_sample += 1
+            pick(step_logits)
+
+        poll = None
+        if finished is not None:
+            poll = _StopPoll(finished, _DEFAULT_STOP_CHECK_EVERY if stop_check_every is None else stop_check_every)
+        graph = None
+        for column in range(seqlen_og, width):       # the pick of this iteration lands in `column`
+            if column == seqlen_og:
+                pick(logits)                         # on the prefill's logits; nothing to copy yet
+            elif graph is not None:
+                graph.replay()
+            else:
+                step()
+                if cg and dev.type == 'cuda' and column + 1 < width:
+                    graph = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(graph):
+                        step()
+                    # the capture ran nothing: lengths, caches, scores and sequences are as the eager step left them
+            if column > seqlen_og:
+                ip.sequence_len_offset += 1
+            if poll is not None and poll.all_finished():
+                break
+        if eos_token_id is not None:
+            sequences, lengths = _trim_at_eos(sequences, seqlen_og, eos_token_id, pad_token_id)
+        else:
+            lengths = torch.full((rows,), width, dtype=torch.int64, device=dev)
+        scores = beam_scores.view(batch, W).clone()
+        lengths = lengths.view(batch, W)
+        ranked = scores / lengths.float() ** float(length_penalty) if length_penalty != 0.0 else scores
+        slots = torch.arange(W, device=dev).expand(batch, W)
+        best = torch.where(ranked == ranked.max(dim=1, keepdim=True).values, slots, torch.full_like(slots, W - 1)).min(dim=1).values
+        beams = sequences.to(input_ids.dtype).view(batch, W, -1)
+        at = torch.arange(batch, device=dev)
+    return BeamSearchOutput(sequences=beams[at, best], scores=scores[at, best], lengths=lengths[at, best],
+                            beam_sequences=beams, beam_scores=scores, beam_lengths=lengths)
+
+
 class GenerationMixin:
 
     def _generate(self, decode, input_ids, max_length, return_dict_in_generate, output_scores, cg, kv_cache, **pick_options):
@@ -492,3 +727,10 @@ class GenerationMixin:
                               temperature=temperature, top_k=top_k, top_p=top_p, rng_state=rng_state,
                               device_pick=device_pick, repetition_penalty=repetition_penalty, eos_token_id=eos_token_id,
                               pad_token_id=pad_token_id, min_length=min_length, stop_check_every=stop_check_every)
+
+    def beam_search(self, input_ids, max_length, num_beams, return_dict_in_generate=False, eos_token_id=None,
+                    pad_token_id=None, length_penalty=0.0, cg=False, stop_check_every=None, **sampling_options):
+        """The best hypothesis of every prompt (batch, cols), or the BeamSearchOutput with return_dict_in_generate."""
+        output = beam_search(input_ids, self, max_length, num_beams, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
+                             length_penalty=length_penalty, cg=cg, stop_check_every=stop_check_every, **sampling_options)
+        return output if return_dict_in_generate else output.sequences

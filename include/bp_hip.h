@@ -46,7 +46,8 @@ extern "C" {
                               (still 11, a purely additive entry point: bp_pick_token, token selection on the device --
                               argmax, temperature, top-k, top-p -- and BP_ERR_SAMPLING;
                               and another: bp_pick_token_ctl, the same pick with a repetition penalty, an EOS mask below
-                              a minimal length and finished flags) */
+                              a minimal length and finished flags;
+                              and two more: bp_beam_pick / bp_beam_copy_rows, a beam-search step and the cache reorder) */
 
 /* element type of q/k/v/out/content tensors */
 #define BP_DTYPE_F16 0
@@ -686,6 +687,67 @@ int bp_pick_token_ctl(const void *logits, int64_t *tokens, int64_t *sequences, f
                       int do_sample, float temperature, int top_k, float top_p,
                       float repetition_penalty, int eos_token_id, int pad_token_id, int min_length,
                       int dtype, bp_stream_t stream);
+
+/*
+ * bp_beam_pick -- one decode step of beam search on the device for `groups` prompts x `beam_width` (W, 1..8) hypotheses,
+ * rows r = g * W + w.  No host value enters, so one captured launch serves every step.  (Additive, ABI still 11.)
+ *   logits       (groups * W, vocab) fp16 / bf16 / fp32, element stride row_stride >= vocab, last stride 1, any
+ *                element-aligned base, as bp_pick_token's.  Only read.
+ *   beam_scores  fp32 (groups * W), read and written: the sum of log-probabilities of every hypothesis
+ *   finished     int32 (groups * W), read and written; NULL is allowed only with eos_token_id < 0
+ *   parent       int32 (groups * W), written: the GLOBAL row index of the hypothesis every slot continues
+ *   tokens       int64, the token of slot r at tokens[r * tokens_stride]
+ *   sequences, seq_stride, seq_cols, counters   as bp_pick_token's: row r receives its token at column counters[r]; the
+ *                write is skipped when that column is outside [0, seq_cols)
+ *   ws, ws_floats  fp32 workspace of >= bp_beam_pick_ws_floats(groups, beam_width) elements, 8-byte aligned; contents
+ *                undefined on entry, it belongs to the call until the call has completed on the stream
+ * Per group g, with s_w = beam_scores[g W + w]:
+ *   1 candidates  a live row w (finished NULL or 0): m = max_v float(x_v), lse = m + log sum_v exp(float(x_v) - m) in fp32
+ *                 (the sum in 40-bit fixed point, as bp_pick_token's masses); candidate (w, v) has the score
+ *                 s_w + (float(x_v) - lse), the two fp32 operations in that order.  A finished row contributes exactly one
+ *                 candidate, (w, pad_token_id), with the score s_w unchanged: the frozen hypothesis.  A candidate whose score
+ *                 is NaN ranks, and is written, as -inf (and -0 as +0).  A live row with a NaN or +inf logit, or without a
+ *                 finite logit, has all its candidates at -inf.
+ *   2 selection   candidates are ranked by (score descending, w ascending, v ascending); the first W win (vocab >= W, so
+ *                 they exist).
+ *   3 slots       a surviving hypothesis never moves: the winners are walked in rank order, and a winner takes slot w, its
+ *                 parent's, if that slot is still free; then the rest, in rank order, each take the lowest free slot.
+ *                 CONSEQUENCE: every slot that another slot names as parent also names itself,
+ *                 parent[parent[r]] == parent[r] -- bp_beam_copy_rows relies on it.
+ *   4 writes      slot t holding the winner (w, v, score): parent[g W + t] = g W + w; tokens and column counters[g W + t] of
+ *                 sequences take v; beam_scores[g W + t] = score; finished[g W + t] = old finished[g W + w] | (w live and
+ *                 v == eos_token_id).  All old scores and flags of the group are read before any is written.
+ *   5 first step  needs no mode of its own: with beam_scores = {0, -inf, ..., -inf} all W winners come from beam 0.
+ * Integer keys and integer sums: the result is bit-identical across calls.
+ * Errors, before any launch: BP_ERR_DTYPE; BP_ERR_SHAPE (groups < 1, beam_width outside 1..8, vocab < beam_width or > 2^23,
+ * row_stride < vocab, tokens_stride < 1, sequences with seq_cols < 1 or seq_stride < seq_cols, a NULL logits / beam_scores /
+ * parent / tokens / ws, a misaligned pointer, eos_token_id >= vocab, pad_token_id outside [0, vocab) when finished != NULL);
+ * BP_ERR_SAMPLING (eos_token_id >= 0 with finished == NULL); BP_ERR_WORKSPACE.
+ */
+int64_t bp_beam_pick_ws_floats(int groups, int beam_width);
+int bp_beam_pick(const void *logits, float *beam_scores, int32_t *finished, int32_t *parent, int64_t *tokens,
+                 int64_t *sequences, const int32_t *counters, float *ws, int64_t ws_floats,
+                 int groups, int beam_width, int vocab, int64_t row_stride, int64_t tokens_stride, int64_t seq_stride,
+                 int seq_cols, int eos_token_id, int pad_token_id, int dtype, bp_stream_t stream);
+
+/*
+ * bp_beam_copy_rows -- the caches follow the hypotheses, in one launch for all of them.  A "row set" is a buffer of `rows`
+ * rows, row r at bases[i] + r * row_strides[i] bytes, holding max_positions positions of pos_bytes[i] contiguous bytes each
+ * (a KV cache, a sequence buffer).  For every set and every row r with parent[r] != r, the bytes of positions
+ * [first_position, lengths[r]) of row parent[r] are copied to row r.  Rows with parent[r] == r, and bytes outside the copied
+ * range, are not touched.  A length outside [0, max_positions] is clamped; a parent outside [0, rows) leaves its row alone.
+ *   bases, row_strides, pos_bytes   HOST arrays of nsets entries, read during the call and passed to the kernel by value
+ *                (a captured graph keeps them: the buffers must not move)
+ *   parent, lengths   int32 (rows) on the device; first_position, max_positions host values
+ * THE CALLER GUARANTEES parent[parent[r]] == parent[r] (bp_beam_pick's slot rule does): sources are then never written, and
+ * the plain copy is correct in place.
+ * Errors, before any launch: BP_ERR_SHAPE (nsets outside 1..32, rows outside 1..65535, a NULL argument, a base that is not
+ * 16-byte aligned, a row stride that is not a multiple of 16 or smaller than max_positions * pos_bytes, pos_bytes < 4 or not
+ * a multiple of 4, a negative first_position or max_positions).
+ */
+int bp_beam_copy_rows(const void *const *bases, const int64_t *row_strides, const int64_t *pos_bytes, int nsets,
+                      const int32_t *parent, const int32_t *lengths, int rows, int first_position, int max_positions,
+                      bp_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -6,7 +6,7 @@ generate(..., kv_cache=True) eagerly and with cg=True (one captured decode step 
                                      [--legs full,kv] [--intervention none|weighted|weighted-anneal|replaced]
                                      [--pick torch|device|torch,device] [--sample] [--temperature T] [--top-k K] [--top-p P]
                                      [--repetition-penalty R] [--eos ID] [--min-length L] [--stop-check-every N]
-                                     [--variant NAME:option=value,...] [--repeats N]
+                                     [--variant NAME:option=value,...] [--repeats N] [--beams W[,W...]]
 
 --pick chooses how the next token is picked: `torch` is torch.argmax / torch.distributions.Categorical on the host side
 of the loop, `device` the bp_pick_token kernel (device_pick=True; with kv_cache and cg inside the captured step).  With
@@ -17,6 +17,12 @@ of bp_pick_token_ctl: --repetition-penalty, --eos (an id that never occurs, e.g.
 polling of the finished flags alone), --min-length and --stop-check-every (kv legs only).  --variant adds a further pick
 that alternates with the others: the device pick with some generation options replaced, e.g.
 `--variant pen:repetition_penalty=1.2 --variant n4:eos_token_id=50263,stop_check_every=4`.
+
+--beams W[,W...] times beam search instead (its own line per sense_table mode): for every width W, beam_search(num_beams=W,
+cg=True) against the greedy device-pick leg generate(kv_cache=True, cg=True, device_pick=True) at the same number of rows
+(batch x W prompts), all legs alternating in one process, --repeats times each; then the two beam kernels alone at the
+final shape -- bp_beam_pick, and bp_beam_copy_rows with every row but one of each group moving -- in microseconds per call
+issued from Python (the `*_host_issue_us` keys: at these sizes the host's cost of a call, an upper bound on the kernel's).
 
 --intervention wraps the model in the control-experiment classes of src/models/intervened_models.py (seeded
 content_weights in [0, 3); for the annealed form a scale of 6 / median of the similarity sums at half the final length, so
@@ -54,6 +60,7 @@ def main():
     ap.add_argument('--stop-check-every', type=int, default=None)
     ap.add_argument('--variant', action='append', default=[], help='NAME:option=value,... : the device pick with these options')
     ap.add_argument('--repeats', type=int, default=1)
+    ap.add_argument('--beams', default=None, help='W[,W...]: time beam search against greedy at the same number of rows')
     a = ap.parse_args()
     from bench import MODELS
     from src.models.backpack import BackpackConfig, BackpackLMHeadModel
@@ -74,6 +81,9 @@ def main():
         legs += [('kv_cache_eager', False, True), ('kv_cache_graph', True, True)]
     for mode in a.modes.split(','):   # content network per position (the reference's order) / cached whole-vocabulary table
         getattr(model, 'backpack_network', model).transformer.sense_table_mode = mode
+        if a.beams:
+            print(json.dumps(beam_legs(model, ids, a, mode)), flush=True)
+            continue
         res = dict(model=a.model, batch=a.batch, prompt=a.prompt, max_length=a.max_length,
                    new_tokens=a.max_length - 1 - a.prompt, sense_table=mode, **extra)
         outs = {}
@@ -123,6 +133,73 @@ def main():
                 res['kv_tokens_equal_fraction'] = round(
                     (outs['kv_cache_eager'] == outs['eager_loop']).float().mean().item(), 4)
         print(json.dumps(res), flush=True)
+
+def _spread(runs):
+    runs = sorted(runs)
+    return dict(median=round(runs[len(runs) // 2], 2), min=round(runs[0], 2), max=round(runs[-1], 2))
+
+
+def beam_legs(model, ids, a, mode):
+    """The --beams line: beam search against greedy at the same number of rows, then the two beam kernels alone."""
+    import bp_hip
+    from src.utils.generation import InferenceParams, _beam_row_sets
+    widths = [int(w) for w in a.beams.split(',')]
+    new_tokens = a.max_length - 1 - a.prompt
+    res = dict(model=a.model, batch=a.batch, prompt=a.prompt, max_length=a.max_length, new_tokens=new_tokens,
+               sense_table=mode, beams=widths, repeats=a.repeats)
+    calls = {}
+    for W in widths:
+        wide = ids.repeat_interleave(W, dim=0)
+        calls['beam%d' % W] = lambda W=W: model.beam_search(ids, a.max_length, W, cg=True)
+        calls['greedy_rows%d' % wide.shape[0]] = lambda wide=wide: model.generate(wide, a.max_length, cg=True, kv_cache=True,
+                                                                                device_pick=True)
+    runs = {name: [] for name in calls}
+    for call in calls.values():                                             # warm-up (allocator, library handles)
+        call()
+    for _ in range(a.repeats):
+        for name, call in calls.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            call()
+            torch.cuda.synchronize()
+            runs[name].append((time.perf_counter() - t0) * 1e3)
+    for name in calls:
+        res[name + '_ms'] = _spread(runs[name])
+        res[name + '_ms_per_token'] = round(res[name + '_ms']['median'] / new_tokens, 3)
+        res[name + '_ms_runs'] = [round(r, 1) for r in runs[name]]
+
+    def per_call_us(fn, n=50):
+        # back-to-back calls from Python: at these sizes this is the host's cost of issuing a call, not the kernel's time
+        fn()
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        for _ in range(n):
+            fn()
+        end.record()
+        torch.cuda.synchronize()
+        return round(start.elapsed_time(end) * 1e3 / n, 1)
+
+    dev = ids.device
+    for W in widths:
+        rows, width = a.batch * W, a.max_length - 1
+        capacity = (width + 3) // 4 * 4
+        ip = InferenceParams(max_sequence_len=capacity, max_batch_size=rows)
+        ip.lengths_per_sample = torch.zeros((rows,), dtype=torch.int32, device=dev)
+        with torch.inference_mode():
+            logits = model(ids.repeat_interleave(W, dim=0), inference_params=ip).logits[:, -1]
+        sequences = torch.zeros((rows, capacity), dtype=torch.int64, device=dev)[:, :width]
+        sets = _beam_row_sets(ip, sequences)
+        scores = torch.zeros((rows,), dtype=torch.float32, device=dev)
+        parent = torch.empty((rows,), dtype=torch.int32, device=dev)
+        res['beam%d_pick_host_issue_us' % W] = per_call_us(lambda: bp_hip.beam_pick(logits, scores, parent, W))
+        first = (torch.arange(rows, device=dev) // W * W).to(torch.int32)   # every row continues slot 0 of its group
+        full = torch.full((rows,), width, dtype=torch.int32, device=dev)
+        res['beam%d_copy_host_issue_us_full_length' % W] = per_call_us(lambda: bp_hip.beam_copy_rows(sets, first, full, a.prompt))
+        moved = (rows - a.batch) * (width - a.prompt)
+        res['beam%d_copy_bytes_per_row_position' % W] = sum(t[0, 0].numel() * t.element_size() for t in sets)
+        res['beam%d_copy_positions_moved' % W] = moved
+    return res
+
 
 def intervene(model, kind, ids, middle):
     """The wrapper of `kind` around `model`, and what to report about it."""
