@@ -90,6 +90,8 @@ SIGNATURES = {
     'bp_sense_rows_dot': (_i32, [_ptr] * 6 + [_i32] * 4 + [_i64] + [_i64] * 6 + [_i32, _ptr]),
     'bp_pick_token': (_i32, [_ptr] * 6 + [_i32] * 2 + [_i64] * 3 + [_i32] * 2 + [_f32, _i32, _f32, _i32, _ptr]),
     'bp_pick_token_ctl': (_i32, [_ptr] * 7 + [_i32] * 2 + [_i64] * 3 + [_i32] * 2 + [_f32, _i32, _f32, _f32] + [_i32] * 4 + [_ptr]),
+    'bp_pick_token_lim': (_i32, [_ptr] * 7 + [_i32] * 2 + [_i64] * 3 + [_i32] * 2 + [_f32, _i32, _f32, _f32] + [_i32] * 3
+                          + [_i32, _f32, _f32, _i32, _ptr, _i32, _i32, _ptr]),
     'bp_beam_pick_ws_floats': (_i64, [_i32] * 2),
     'bp_beam_pick': (_i32, [_ptr] * 8 + [_i64] + [_i32] * 3 + [_i64] * 3 + [_i32] * 4 + [_ptr]),
     'bp_beam_copy_rows': (_i32, [_ptr] * 3 + [_i32] + [_ptr] * 2 + [_i32] * 3 + [_ptr]),
@@ -1130,14 +1132,15 @@ def sense_rows_dot(table, row_index, new_row, cache_seqlens, vec, out):
     return out
 
 
-# ---- token selection on the device (C ABI bp_pick_token, bp_pick_token_ctl) ---------------------------------------------------------------------------------------------
+# ---- token selection on the device (C ABI bp_pick_token, bp_pick_token_ctl, bp_pick_token_lim) ---------------------------------------------------------------------------------------------
 
 _PICK_DTYPES = {torch.float16: 0, torch.bfloat16: 1, torch.float32: 2}
 
 
 def pick_token(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rng_state=None, counters=None, tokens=None,
                sequences=None, return_stats=False, repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, min_length=0,
-               finished=None):
+               finished=None, no_repeat_ngram_size=0, frequency_penalty=0.0, presence_penalty=0.0, penalty_begin=0,
+               suppress_tokens=None):
     """The next token of every row of `logits` (B, vocab) fp16 / bf16 / fp32 (any row stride), chosen on the device by one
     launch that reads no host value (legal inside a HIP-graph capture): argmax (lowest index of the maximum, NaN largest),
     or with do_sample a draw after temperature, top-k (ties kept) and top-p -- the contract is in include/bp_hip.h.
@@ -1152,8 +1155,14 @@ def pick_token(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rng
     read and written) select bp_pick_token_ctl: tokens of the history sequences[b, :counters[b]] have their logit multiplied
     by the penalty (negative) or its reciprocal, the EOS entry is -inf while counters[b] < min_length, a row whose flag is
     set picks the pad, and a row that picks the EOS id has its flag set.  With all five at their defaults the call is
-    bp_pick_token's, argument for argument."""
-    _require_cuda(logits, rng_state, counters, tokens, sequences, finished)
+    bp_pick_token's, argument for argument.
+
+    no_repeat_ngram_size, frequency_penalty, presence_penalty, penalty_begin, suppress_tokens (an int32 tensor on the device)
+    select bp_pick_token_lim, the controlled pick with more limits: an id that would complete an n-gram the history already
+    holds and every id of suppress_tokens count as -inf, and an id that occurs n > 0 times at the history positions >=
+    penalty_begin loses frequency_penalty * n + presence_penalty.  With all of them at their defaults the call routes exactly as
+    described above."""
+    _require_cuda(logits, rng_state, counters, tokens, sequences, finished, suppress_tokens)
     if logits.dim() != 2 or logits.stride(1) != 1 or logits.dtype not in _PICK_DTYPES:
         raise RuntimeError('bp_hip.pick_token: logits must be (B, vocab) fp16 / bf16 / fp32 with a contiguous last dimension')
     batch, vocab = logits.shape
@@ -1171,6 +1180,28 @@ def pick_token(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rng
                                   or sequences.stride(1) != 1):
         raise RuntimeError('bp_hip.pick_token: sequences must be (B, cols) int64 with a contiguous last dimension')
     stats = torch.empty((batch, 4), dtype=torch.float32, device=logits.device) if return_stats else None
+    if not (no_repeat_ngram_size == 0 and frequency_penalty == 0.0 and presence_penalty == 0.0 and penalty_begin == 0
+            and suppress_tokens is None):
+        if finished is not None and (finished.shape != (batch,) or finished.dtype != torch.int32
+                                     or not finished.is_contiguous()):
+            raise RuntimeError('bp_hip.pick_token: finished must be a contiguous (B,) int32 tensor')
+        if suppress_tokens is not None and (suppress_tokens.dim() != 1 or suppress_tokens.dtype != torch.int32
+                                            or not suppress_tokens.is_contiguous()):
+            raise RuntimeError('bp_hip.pick_token: suppress_tokens must be a contiguous 1-d int32 tensor')
+        if pad_token_id is None:
+            pad_token_id = eos_token_id if eos_token_id is not None else 0
+        n_suppress = suppress_tokens.numel() if suppress_tokens is not None else 0
+        _call('bp_pick_token_lim', logits.device,
+              logits.data_ptr(), tokens.data_ptr(), sequences.data_ptr() if sequences is not None else None,
+              stats.data_ptr() if stats is not None else None, rng_state.data_ptr() if rng_state is not None else None,
+              counters.data_ptr() if counters is not None else None, finished.data_ptr() if finished is not None else None,
+              batch, vocab, logits.stride(0), tokens.stride(0) if batch > 1 else 1,
+              sequences.stride(0) if sequences is not None else 0, sequences.shape[1] if sequences is not None else 0,
+              int(bool(do_sample)), float(temperature), int(top_k), float(top_p), float(repetition_penalty),
+              -1 if eos_token_id is None else int(eos_token_id), int(pad_token_id), int(min_length),
+              int(no_repeat_ngram_size), float(frequency_penalty), float(presence_penalty), int(penalty_begin),
+              suppress_tokens.data_ptr() if n_suppress else None, n_suppress, _PICK_DTYPES[logits.dtype])
+        return (tokens, stats) if return_stats else tokens
     if not (repetition_penalty == 1.0 and eos_token_id is None and pad_token_id is None and min_length == 0
             and finished is None):
         if finished is not None and (finished.shape != (batch,) or finished.dtype != torch.int32

@@ -130,7 +130,8 @@ const char *bp_strerror(int code) {
         case BP_ERR_QUEUE_WS: return "queue_ws must be caller-owned (non-NULL) while the stream is being captured";
         case BP_ERR_WORKSPACE: return "workspace smaller than the *_ws_floats() query of this entry point";
         case BP_ERR_SAMPLING: return "token sampling: top_p must be in (0, 1], rng_state non-NULL when do_sample; repetition_penalty finite and > 0 and, "
-                                     "unless 1, with sequences; an eos_token_id with finished flags";
+                                     "unless 1, with sequences; an eos_token_id with finished flags; finite frequency / presence penalties and, like n-gram "
+                                     "blocking, with sequences; a non-NULL aligned suppress_ids when n_suppress > 0";
         default: return "unknown error";
     }
 }
@@ -894,7 +895,7 @@ int bp_sense_rows_dot(const void *table, const int32_t *row_index, const int32_t
     return launch_status(bp::launch_sense_rows_dot(p, dtype, static_cast<hipStream_t>(stream)));
 }
 
-// ---- token selection (bp_pick_token, bp_pick_token_ctl) ----
+// ---- token selection (bp_pick_token, bp_pick_token_ctl, bp_pick_token_lim) ----
 
 // the argument checks of bp_pick_token and the parameters they admit; bp_pick_token_ctl adds its own behind them
 static int pick_params(bp::PickParams &p, const void *logits, int64_t *tokens, int64_t *sequences, float *stats,
@@ -934,16 +935,9 @@ int bp_pick_token(const void *logits, int64_t *tokens, int64_t *sequences, float
     return launch_status(bp::launch_pick_token(p, dtype, static_cast<hipStream_t>(stream)));
 }
 
-int bp_pick_token_ctl(const void *logits, int64_t *tokens, int64_t *sequences, float *stats, const uint64_t *rng_state,
-                      const int32_t *counters, int32_t *finished,
-                      int batch, int vocab, int64_t row_stride, int64_t tokens_stride, int64_t seq_stride, int seq_cols,
-                      int do_sample, float temperature, int top_k, float top_p,
-                      float repetition_penalty, int eos_token_id, int pad_token_id, int min_length,
-                      int dtype, bp_stream_t stream) {
-    bp::PickParams p{};
-    const int e = pick_params(p, logits, tokens, sequences, stats, rng_state, counters, batch, vocab, row_stride,
-                              tokens_stride, seq_stride, seq_cols, do_sample, temperature, top_k, top_p, dtype);
-    if (e != BP_OK) return e;
+// the checks bp_pick_token_ctl adds behind pick_params, and its parameters
+static int pick_ctl_params(bp::PickParams &p, const int64_t *sequences, int32_t *finished, int vocab, float repetition_penalty,
+                           int eos_token_id, int pad_token_id, int min_length) {
     if (!scale_ok(repetition_penalty) || !scale_ok(1.f / repetition_penalty)) return BP_ERR_SAMPLING;
     if (repetition_penalty != 1.f && sequences == nullptr) return BP_ERR_SAMPLING;
     if (eos_token_id >= 0 && finished == nullptr) return BP_ERR_SAMPLING;
@@ -953,7 +947,52 @@ int bp_pick_token_ctl(const void *logits, int64_t *tokens, int64_t *sequences, f
     p.finished = finished;
     p.theta = repetition_penalty; p.inv_theta = 1.f / repetition_penalty;
     p.eos = eos_token_id < 0 ? -1 : eos_token_id; p.pad = pad_token_id; p.min_length = min_length;
+    return BP_OK;
+}
+
+int bp_pick_token_ctl(const void *logits, int64_t *tokens, int64_t *sequences, float *stats, const uint64_t *rng_state,
+                      const int32_t *counters, int32_t *finished,
+                      int batch, int vocab, int64_t row_stride, int64_t tokens_stride, int64_t seq_stride, int seq_cols,
+                      int do_sample, float temperature, int top_k, float top_p,
+                      float repetition_penalty, int eos_token_id, int pad_token_id, int min_length,
+                      int dtype, bp_stream_t stream) {
+    bp::PickParams p{};
+    int e = pick_params(p, logits, tokens, sequences, stats, rng_state, counters, batch, vocab, row_stride,
+                        tokens_stride, seq_stride, seq_cols, do_sample, temperature, top_k, top_p, dtype);
+    if (e != BP_OK) return e;
+    e = pick_ctl_params(p, sequences, finished, vocab, repetition_penalty, eos_token_id, pad_token_id, min_length);
+    if (e != BP_OK) return e;
     return launch_status(bp::launch_pick_token_ctl(p, dtype, static_cast<hipStream_t>(stream)));
+}
+
+int bp_pick_token_lim(const void *logits, int64_t *tokens, int64_t *sequences, float *stats, const uint64_t *rng_state,
+                      const int32_t *counters, int32_t *finished,
+                      int batch, int vocab, int64_t row_stride, int64_t tokens_stride, int64_t seq_stride, int seq_cols,
+                      int do_sample, float temperature, int top_k, float top_p,
+                      float repetition_penalty, int eos_token_id, int pad_token_id, int min_length,
+                      int no_repeat_ngram_size, float frequency_penalty, float presence_penalty, int penalty_begin,
+                      const int32_t *suppress_ids, int n_suppress, int dtype, bp_stream_t stream) {
+    bp::PickParams p{};
+    int e = pick_params(p, logits, tokens, sequences, stats, rng_state, counters, batch, vocab, row_stride,
+                        tokens_stride, seq_stride, seq_cols, do_sample, temperature, top_k, top_p, dtype);
+    if (e != BP_OK) return e;
+    e = pick_ctl_params(p, sequences, finished, vocab, repetition_penalty, eos_token_id, pad_token_id, min_length);
+    if (e != BP_OK) return e;
+    if (!(fabsf(frequency_penalty) < INFINITY) || !(fabsf(presence_penalty) < INFINITY)) return BP_ERR_SAMPLING;
+    const bool counted = frequency_penalty != 0.f || presence_penalty != 0.f;
+    if ((no_repeat_ngram_size > 0 || counted) && sequences == nullptr) return BP_ERR_SAMPLING;
+    if (n_suppress > 0 && (suppress_ids == nullptr || reinterpret_cast<uintptr_t>(suppress_ids) % 4)) return BP_ERR_SAMPLING;
+    if (no_repeat_ngram_size < 0 || no_repeat_ngram_size > BP_PICK_MAX_NGRAM || n_suppress < 0 || penalty_begin < 0)
+        return BP_ERR_SHAPE;
+    const bool limited = no_repeat_ngram_size > 0 || counted || n_suppress > 0;
+    if (limited && vocab > BP_PICK_MAX_LIMITED_VOCAB) return BP_ERR_SHAPE;   // 19 id bits of a table entry, 64 KB per bitmap
+    if (counted && seq_cols > BP_PICK_MAX_COUNTED_COLS) return BP_ERR_SHAPE;  // 13 count bits of a table entry
+    p.suppress = n_suppress > 0 ? suppress_ids : nullptr; p.n_suppress = n_suppress;
+    p.ngram = no_repeat_ngram_size; p.penalty_begin = penalty_begin;
+    p.freq_pen = frequency_penalty; p.pres_pen = presence_penalty;
+    p.table_shift = counted ? bp::lim_table_shift(seq_cols) : 31;
+    if (bp::pick_lim_lds_bytes(p) > BP_PICK_MAX_LDS_BYTES) return BP_ERR_SHAPE;
+    return launch_status(bp::launch_pick_token_lim(p, dtype, static_cast<hipStream_t>(stream)));
 }
 
 // ---- beam search (bp_beam_pick, bp_beam_copy_rows) ----

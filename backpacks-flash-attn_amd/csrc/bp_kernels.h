@@ -332,9 +332,23 @@ struct PickParams {
     int32_t *finished;           // optional (batch): a set flag turns the row's pick into `pad`; set when the pick is `eos`
     float theta, inv_theta;      // repetition penalty and its reciprocal
     int eos, pad, min_length;    // eos < 0: none; the EOS entry counts as -inf while counters[b] < min_length
+    // bp_pick_token_lim only (pick_token_lim.hip); the plain and the controlled kernels never read past min_length
+    const int32_t *suppress;     // n_suppress ids that count as -inf; ids outside [0, vocab) are ignored
+    int n_suppress, ngram;       // ngram: no_repeat_ngram_size, 0 = off
+    int penalty_begin;           // history positions at or behind it are counted
+    int table_shift;             // 32 - log2(slots of the count table)
+    float freq_pen, pres_pen;
 };
 hipError_t launch_pick_token(const PickParams &p, int dtype, hipStream_t stream);
 hipError_t launch_pick_token_ctl(const PickParams &p, int dtype, hipStream_t stream);
+hipError_t launch_pick_token_lim(const PickParams &p, int dtype, hipStream_t stream);
+// 32 - log2(slots), slots = the power of two >= 2 seq_cols (at least 2)
+inline int lim_table_shift(int seq_cols) {
+    int log2 = 1;
+    while ((1 << log2) < 2 * seq_cols) ++log2;
+    return 32 - log2;
+}
+size_t pick_lim_lds_bytes(const PickParams &p);   // static + dynamic LDS of a bp_pick_token_lim launch
 
 // bp_beam_pick (beam_pick.hip): one beam-search step, rows r = g * beam_width + w
 struct BeamPickParams {

@@ -1,5 +1,5 @@
 // Token selection on the device for the decode loops: one row of logits in, one token out.  The shared body of
-// bp_pick_token (csrc/pick_token.hip) and bp_pick_token_ctl (csrc/pick_token_ctl.hip).
+// bp_pick_token (csrc/pick_token.hip), bp_pick_token_ctl (csrc/pick_token_ctl.hip) and bp_pick_token_lim (csrc/pick_token_lim.hip).
 //
 // Replaces the host-driven picks of the generation loops (src/utils/generation.py: torch.argmax, and
 // torch.distributions.Categorical, whose argument validation reads a device value on the host) and adds the sampling
@@ -42,6 +42,21 @@
 //   2, 3  select on the 32-bit key of the fp32 z itself (four rounds for every element type): pen is not monotone across the
 //      two classes, so the key of the raw element no longer orders the row; the threshold is the z the key stands for
 //   5  after the token is written: finished[b] = 1 by that one lane when the token is the EOS id
+//
+// Limited form (bp_pick_token_lim, pick_token_lim.hip): pick_token_kernel<Limited<ET>> is the controlled form with n-gram
+// blocking, frequency / presence penalties and a list of suppressed ids (contract in include/bp_hip.h).  Again a tag and a
+// code object of its own.  What it adds, all of it in dynamic LDS (LimLayout) and built before pass 1 (Logits<Limited>::build):
+//   members  the history bitmap of the controlled form, also built when a frequency / presence penalty is on
+//   banned   a second bitmap of the same shape: the suppressed ids (thread-strided over the list), then the n-gram scan --
+//            thread-strided start positions i, each comparing at most n - 1 int64 pairs of the row of `sequences` against its
+//            last n - 1 entries and setting the bit of the id behind a match
+//   counts   an open-addressing table of 32-bit entries, id in the low 19 bits and count in the high 13, empty = all ones,
+//            slots = the power of two >= 2 seq_cols (load <= 0.5), slot of an id = lim_hash(id) then linear probing.  Every
+//            in-vocabulary id of the history is inserted (atomicCAS claims a slot), positions >= penalty_begin add 1 << 19:
+//            integer counts, so the result does not depend on which thread came first.  Only members are looked up, and a
+//            member's probe always ends on its id.  Every probe loop is bounded by the slot count.
+//   the helper applies, in this order: pen, v -= fmaf(frequency, count, presence) for a count > 0, -inf for a banned id or
+//   the masked EOS.  Everything behind the helper is the controlled form's.
 #pragma once
 #include <type_traits>
 
@@ -53,8 +68,32 @@ namespace bp {
 
 // Controlled form: the flag rides on the element tag (as Weighted<ET> in decode_core.h)
 template <class ET> struct Controlled {};
-template <class T> struct PickTag { using elem = T; static constexpr bool ctl = false; };
-template <class T> struct PickTag<Controlled<T>> { using elem = T; static constexpr bool ctl = true; };
+// Limited form: the controlled one with the row limits of bp_pick_token_lim
+template <class ET> struct Limited {};
+template <class T> struct PickTag { using elem = T; static constexpr bool ctl = false, lim = false; };
+template <class T> struct PickTag<Controlled<T>> { using elem = T; static constexpr bool ctl = true, lim = false; };
+template <class T> struct PickTag<Limited<T>> { using elem = T; static constexpr bool ctl = true, lim = true; };
+
+// Dynamic LDS of the limited form, in 32-bit words: [members][banned][count table], each only when its control is on.  The
+// switches depend on the arguments alone, never on a row, so the host sizes the allocation from the same struct.
+constexpr uint32_t kLimIdBits = 19, kLimIdMask = (1u << kLimIdBits) - 1u, kLimEmpty = 0xffffffffu;
+constexpr int kLimMaxCols = (1 << (32 - kLimIdBits)) - 1;   // 8191: what the 13 count bits hold
+// slot of an id in a table of 2^(32 - shift) slots: a multiplicative (Fibonacci) hash, tests/pick_lim_ref.py restates it
+__host__ __device__ inline uint32_t lim_hash(uint32_t id, int shift) { return (id * 2654435761u) >> shift; }
+struct LimLayout {
+    bool members_on, banned_on, counts_on;
+    int ban_at, table_at, slots, total_words;
+    __host__ __device__ explicit LimLayout(const PickParams &p) {
+        counts_on = p.freq_pen != 0.f || p.pres_pen != 0.f;
+        members_on = p.theta != 1.f || counts_on;
+        banned_on = p.ngram > 0 || p.n_suppress > 0;
+        const int words = (p.vocab + 31) / 32 + 1;
+        ban_at = members_on ? words : 0;
+        table_at = ban_at + (banned_on ? words : 0);
+        slots = counts_on ? 1 << (32 - p.table_shift) : 0;
+        total_words = table_at + slots;
+    }
+};
 
 namespace {
 
@@ -229,6 +268,134 @@ template <class ET> struct Logits<Controlled<ET>> {
     BP_DEV float z(uint32_t raw, Chunk ck, int i) const { return ctl(E::to_f32(raw) * inv_t, ck, i); }
 };
 
+// Limited rows: the controlled value, then the count penalty, then the ban (layout and build: header comment, LimLayout).
+template <class ET> struct Logits<Limited<ET>> {
+    using E = PickElem<ET>;
+    const uint32_t *members, *banned, *table;   // dynamic LDS; NULL: that control is off
+    float inv_t, theta, inv_theta, freq, pres;
+    int eos, shift;
+    BP_DEV Logits(const PickParams &p, int counter, const uint32_t *lds)
+        : inv_t(p.inv_t), theta(p.theta), inv_theta(p.inv_theta), freq(p.freq_pen), pres(p.pres_pen),
+          eos(p.eos >= 0 && counter < p.min_length ? p.eos : -1), shift(p.table_shift) {
+        const LimLayout lay(p);
+        members = lay.members_on ? lds : nullptr;
+        banned = lay.banned_on ? lds + lay.ban_at : nullptr;
+        table = lay.counts_on ? lds + lay.table_at : nullptr;
+    }
+    // counts: 16 bits per element of the chunk, looked up once per chunk in ONE loop over the members' bits (a probe loop per
+    // element of the unrolled passes costs a saved exec mask each, more scalar registers than there are)
+    struct Chunk { int col0; uint32_t members, banned; u64 counts[E::N / 4]; };
+    static BP_DEV uint32_t bits(const uint32_t *bitmap, int base, int col0) {
+        const u64 two = (u64)bitmap[base >> 5] | ((u64)bitmap[(base >> 5) + 1] << 32);
+        return (uint32_t)(two >> (base & 31)) << (base - col0);
+    }
+    BP_DEV Chunk chunk(const RowView<ET> &row, int c) const {
+        const int col0 = (c < 0 ? 0 : c) * E::N - row.head;
+        const int base = col0 < 0 ? 0 : col0;
+        Chunk ck{col0, members ? bits(members, base, col0) : 0u, banned ? bits(banned, base, col0) : 0u, {}};
+        if (eos >= col0 && eos < col0 + E::N) ck.banned |= 1u << (eos - col0);   // the masked EOS is one more banned id
+        if (table != nullptr) {
+            uint32_t todo = ck.members & ((1u << E::N) - 1u);   // bits of columns inside the row only: the rest of the bitmap is 0
+            while (todo) {
+                const int i = __ffs(todo) - 1;
+                todo &= todo - 1u;
+                const u64 n = (u64)count((uint32_t)(col0 + i)) << (16 * (i & 3));
+                if (E::N == 4 || i < 4) ck.counts[0] |= n; else ck.counts[E::N / 4 - 1] |= n;
+            }
+        }
+        return ck;
+    }
+    // count of a member of the history: its probe ends on its id (the trip bound is the slot count)
+    BP_DEV uint32_t count(uint32_t col) const {
+        const uint32_t mask = (1u << (32 - shift)) - 1u;
+        uint32_t slot = lim_hash(col, shift);
+        for (uint32_t t = 0; t <= mask; ++t) {
+            const uint32_t e = table[slot];
+            if (e == kLimEmpty) return 0u;
+            if ((e & kLimIdMask) == col) return e >> kLimIdBits;
+            slot = (slot + 1u) & mask;
+        }
+        return 0u;
+    }
+    BP_DEV float lim(float v, Chunk ck, int i) const {
+#pragma clang fp contract(off)   // pen's product is rounded before the subtraction: no fma of the two
+        if ((ck.members >> i) & 1u) {
+            v = v < 0.f ? v * theta : v * inv_theta;   // theta == 1: both factors are 1
+            const uint32_t n = (uint32_t)(ck.counts[i >> 2] >> (16 * (i & 3))) & 0xffffu;   // 0 without a table
+            if (n > 0u) v = v - __builtin_fmaf(freq, (float)n, pres);
+        }
+        return ((ck.banned >> i) & 1u) ? -INFINITY : v;
+    }
+    BP_DEV float x(uint32_t raw, Chunk ck, int i) const { return lim(E::to_f32(raw), ck, i); }
+    BP_DEV float z(uint32_t raw, Chunk ck, int i) const { return lim(E::to_f32(raw) * inv_t, ck, i); }
+
+    // One entry per in-vocabulary id of the history; counted: the position is at or behind penalty_begin
+    static BP_DEV void insert(uint32_t *table, uint32_t id, bool counted, int shift) {
+        const uint32_t mask = (1u << (32 - shift)) - 1u;
+        uint32_t slot = lim_hash(id, shift);
+        for (uint32_t t = 0; t <= mask; ++t) {
+            uint32_t e = table[slot];
+            if (e == kLimEmpty) e = atomicCAS(&table[slot], kLimEmpty, id);   // returns what was there: empty, or an owner
+            if (e == kLimEmpty || (e & kLimIdMask) == id) {
+                if (counted) atomicAdd(&table[slot], 1u << kLimIdBits);
+                return;
+            }
+            slot = (slot + 1u) & mask;
+        }
+    }
+    // Before pass 1, by the whole workgroup: hist = min(counter, seq_cols), possibly <= 0
+    static BP_DEV void build(const PickParams &p, int b, int hist, uint32_t *lds) {
+        const int tid = threadIdx.x;
+        const LimLayout lay(p);
+        for (int i = tid; i < lay.total_words; i += kPickThreads) lds[i] = i >= lay.table_at ? kLimEmpty : 0u;
+        __syncthreads();
+        uint32_t *members = lds, *banned = lds + lay.ban_at, *table = lds + lay.table_at;
+        for (int i = tid; i < p.n_suppress; i += kPickThreads) {
+            const int32_t id = p.suppress[i];
+            if (id >= 0 && id < p.vocab) atomicOr(&banned[id >> 5], 1u << (id & 31));
+        }
+        if (p.sequences && hist > 0) {
+            const int64_t *seq = p.sequences + (int64_t)b * p.seq_stride;
+            if (lay.members_on) {
+                for (int j = tid; j < hist; j += kPickThreads) {
+                    const int64_t id = seq[j];
+                    if (id >= 0 && id < (int64_t)p.vocab) {
+                        atomicOr(&members[id >> 5], 1u << (id & 31));
+                        if (lay.counts_on) insert(table, (uint32_t)id, j >= p.penalty_begin, p.table_shift);
+                    }
+                }
+            }
+            const int n = p.ngram;
+            if (n > 0 && hist >= n) {
+                const int64_t *suffix = seq + (hist - n + 1);   // the last n - 1 entries
+                for (int i = tid; i <= hist - n; i += kPickThreads) {
+                    bool match = true;
+                    for (int t = 0; t < n - 1 && match; ++t) match = seq[i + t] == suffix[t];
+                    const int64_t id = seq[i + n - 1];
+                    if (match && id >= 0 && id < (int64_t)p.vocab) atomicOr(&banned[id >> 5], 1u << (id & 31));
+                }
+            }
+        }
+        __syncthreads();
+    }
+};
+
+// Where a limited row's results go, worked out before pass 1 and parked in vector registers: the limited passes need every
+// scalar register the controlled ones leave, and these addresses are not read again before the last lines of the kernel.
+struct LimOutputs {
+    int64_t *token, *column;   // column: NULL when there is no column counters[b] of sequences
+    int32_t *flag;             // NULL without flags or without an EOS id
+    float *stats;
+    LimOutputs() = default;
+    BP_DEV LimOutputs(const PickParams &p, int b, int counter) {
+        token = p.tokens + (int64_t)b * p.tokens_stride;
+        column = p.sequences && counter >= 0 && counter < p.seq_cols ? p.sequences + (int64_t)b * p.seq_stride + counter : nullptr;
+        flag = p.finished && p.eos >= 0 ? p.finished + b : nullptr;
+        stats = p.stats ? p.stats + (int64_t)b * 4 : nullptr;
+        asm volatile("" : "+v"(token), "+v"(column), "+v"(flag), "+v"(stats));   // no instruction: pins them to vector registers
+    }
+};
+
 // Key source of the radix select.  Plain rows: the order-preserving key of the RAW element (x -> z is monotone), 16 or 32
 // bits.  Controlled rows: the 32-bit key of the fp32 z, whose threshold is z itself.
 template <class TAG> struct SelectKey {
@@ -242,6 +409,7 @@ template <class ET> struct SelectKey<Controlled<ET>> {
     static BP_DEV uint32_t key(uint32_t, float z) { return PickElem<float>::key(as_u32(z)); }
     static BP_DEV float threshold(uint32_t k, float) { return as_f32(PickElem<float>::unkey(k)); }
 };
+template <class ET> struct SelectKey<Limited<ET>> : SelectKey<Controlled<ET>> {};
 
 // Radix select, 8 bits a round from the top of the key: among the elements with z >= lo, the key K with
 //   weight{key > K} < target <= weight{key >= K}
@@ -332,8 +500,9 @@ __global__ __launch_bounds__(kPickThreads) void pick_token_kernel(const PickPara
     const int counter = p.counters ? p.counters[b] : 0;
 
     const uint32_t *bitmap = nullptr;
+    [[maybe_unused]] LimOutputs out;   // limited rows only
     if constexpr (CTL) {
-        extern __shared__ uint32_t pick_bitmap[];   // (vocab + 31) / 32 + 1 words when theta != 1, else none
+        extern __shared__ uint32_t pick_bitmap[];   // (vocab + 31) / 32 + 1 words when theta != 1, else none (limited: LimLayout)
         if (p.finished && p.finished[b] != 0) {     // workgroup-uniform: the pad, no draw, the flag stays
             if (tid == 0) {
                 p.tokens[(int64_t)b * p.tokens_stride] = p.pad;
@@ -353,7 +522,11 @@ __global__ __launch_bounds__(kPickThreads) void pick_token_kernel(const PickPara
             return;
         }
         const int hist = counter < p.seq_cols ? counter : p.seq_cols;
-        if (p.theta != 1.f && p.sequences && hist > 0) {
+        if constexpr (PickTag<TAG>::lim) {
+            Logits<TAG>::build(p, b, hist, pick_bitmap);
+            bitmap = pick_bitmap;
+            out = LimOutputs(p, b, counter);
+        } else if (p.theta != 1.f && p.sequences && hist > 0) {
             const int words = (p.vocab + 31) / 32 + 1;
             for (int i = tid; i < words; i += kPickThreads) pick_bitmap[i] = 0u;
             __syncthreads();
@@ -511,6 +684,17 @@ __global__ __launch_bounds__(kPickThreads) void pick_token_kernel(const PickPara
                 }
             }
         }
+    }
+    if constexpr (PickTag<TAG>::lim) {
+        if (sampled ? token >= 0 : tid == 0) {
+            *out.token = token;
+            if (out.column) *out.column = token;
+            if (out.flag && token == p.eos) *out.flag = 1;
+        }
+        if (out.stats && tid == 0) {
+            out.stats[0] = st_lo; out.stats[1] = st_lse; out.stats[2] = st_count; out.stats[3] = st_u;
+        }
+        return;
     }
     // the greedy answer is known to every thread (thread 0 writes it), a drawn token to the lane that found it
     if (sampled ? token >= 0 : tid == 0) {

@@ -5,6 +5,8 @@ HIP attention and sense-mix kernels); `kv_cache=True` decodes on the caches of I
 cg=True inside the captured step (_decode_cached_picked); without them the loops below run as they always did.
 `repetition_penalty`, `eos_token_id`, `pad_token_id` and `min_length` (kv_cache=True only) select the controlled pick
 (bp_pick_token_ctl): rows stop at their EOS, the loop ends once every row has, and `lengths` reports where.
+`no_repeat_ngram_size`, `frequency_penalty`, `presence_penalty` and `suppress_tokens` (kv_cache=True only) select its limited
+form (bp_pick_token_lim): no n-gram twice, counted penalties on what was generated, ids that never appear.
 Differences kept deliberately small: the result is a plain dataclass instead of the
 transformers `*DecoderOnlyOutput` classes (removed in transformers 5), and the appended token is
 `unsqueeze(1)` so batch sizes > 1 work (the reference's `unsqueeze(0)` in greedy_decode, :68, only
@@ -173,8 +175,33 @@ def _history_mask(sequences, counters, vocab):
     return member[:, :vocab]
 
 
+def _ngram_mask(sequences, counters, vocab, n):
+    """(batch, vocab) bool: the ids that would complete an n-gram the history sequences[b, :Lh] already holds, Lh =
+    min(max(counters[b], 0), cols): h[i + n - 1] for every i <= Lh - n whose n - 1 ids equal the last n - 1 of h."""
+    batch, cols = sequences.shape
+    banned = torch.zeros((batch, vocab), dtype=torch.bool, device=sequences.device)
+    for b in range(batch):
+        h = sequences[b, :min(max(int(counters[b]), 0), cols)].tolist()
+        tail = h[len(h) - n + 1:] if n > 1 else []
+        for i in range(len(h) - n + 1):
+            if h[i:i + n - 1] == tail and 0 <= h[i + n - 1] < vocab:
+                banned[b, h[i + n - 1]] = True
+    return banned
+
+
+def _history_counts(sequences, counters, vocab, begin):
+    """(batch, vocab) int64: how often an id occurs at the positions [min(begin, Lh), Lh) of sequences[b]."""
+    batch, cols = sequences.shape
+    at = torch.arange(cols, device=sequences.device)[None, :]
+    seen = (at >= begin) & (at < counters.long()[:, None]) & (sequences >= 0) & (sequences < vocab)
+    counts = torch.zeros((batch, vocab + 1), dtype=torch.int64, device=sequences.device)
+    counts.scatter_add_(1, torch.where(seen, sequences, torch.full_like(sequences, vocab)), seen.long())
+    return counts[:, :vocab]
+
+
 def _eager_pick(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rng_state=None, counters=None,
-                repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, min_length=0, finished=None, sequences=None):
+                repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, min_length=0, finished=None, sequences=None,
+                no_repeat_ngram_size=0, frequency_penalty=0.0, presence_penalty=0.0, penalty_begin=0, suppress_tokens=None):
     """The contract of bp_pick_token (include/bp_hip.h) in torch ops, for tensors the kernel does not take (CPU): tokens
     (batch,) int64 of logits (batch, vocab).  Greedy: torch.argmax (lowest index of the maximum, a NaN largest).  Sampling:
     z = float(x) / T in fp32; top-k keeps z >= the k-th largest (ties kept); top-p keeps a token iff the kept mass strictly
@@ -185,7 +212,13 @@ def _eager_pick(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rn
     The controls of bp_pick_token_ctl: ids of the history sequences[b, :counters[b]] have their value multiplied by
     repetition_penalty (negative values) or by its fp32 reciprocal (the others), in fp32, after the temperature; the EOS
     entry is -inf while counters[b] < min_length; rows whose `finished` flag is set take pad_token_id (default: the EOS
-    id).  `finished` is only read here: _Picker sets the flag of a row that picked the EOS id."""
+    id).  `finished` is only read here: _Picker sets the flag of a row that picked the EOS id.
+
+    The limits of bp_pick_token_lim, applied behind the repetition penalty in this order: an id that occurs n > 0 times at
+    the history positions >= penalty_begin loses fp32(frequency_penalty * n + presence_penalty) (float64 product and sum
+    rounded once: the kernel's fma wherever the float64 sum is exact); the ids of `suppress_tokens` (a list or a tensor; ids
+    outside the vocabulary are ignored) and the ids that would complete an n-gram (n = no_repeat_ngram_size) the history
+    already holds are -inf, like the masked EOS."""
     x = logits.float()
     batch, vocab = x.shape
     if counters is None:
@@ -198,10 +231,27 @@ def _eager_pick(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rn
     if eos_token_id is not None and eos_token_id >= 0:
         masked = torch.zeros((batch, vocab), dtype=torch.bool, device=x.device)
         masked[:, eos_token_id] = counters < min_length
+    if no_repeat_ngram_size > 0 and sequences is not None:
+        banned = _ngram_mask(sequences, counters, vocab, int(no_repeat_ngram_size))
+        masked = banned if masked is None else masked | banned
+    if suppress_tokens is not None:
+        ids = torch.as_tensor(suppress_tokens, dtype=torch.int64, device=x.device).view(-1)
+        ids = ids[(ids >= 0) & (ids < vocab)]
+        if masked is None:
+            masked = torch.zeros((batch, vocab), dtype=torch.bool, device=x.device)
+        masked[:, ids] = True
+    minus = None
+    if (frequency_penalty != 0.0 or presence_penalty != 0.0) and sequences is not None:
+        counts = _history_counts(sequences, counters, vocab, int(penalty_begin))
+        minus = (torch.tensor(frequency_penalty, dtype=torch.float32).double() * counts.double()
+                 + torch.tensor(presence_penalty, dtype=torch.float32).double()).float().to(x.device)
+        minus = torch.where(counts > 0, minus, torch.zeros_like(minus))
 
     def controlled(v):
         if member is not None:
             v = torch.where(member, torch.where(v < 0, v * repetition_penalty, v * (one / repetition_penalty)), v)
+        if minus is not None:
+            v = torch.where(minus != 0, v - minus, v)
         if masked is not None:
             v = torch.where(masked, torch.full_like(v, float('-inf')), v)
         return v
@@ -252,18 +302,28 @@ class _Picker:
     is set by the pick that returns the EOS id, and every later pick of that row returns the pad."""
 
     def __init__(self, do_sample, temperature, top_k, top_p, rng_state, device, repetition_penalty=1.0, eos_token_id=None,
-                 pad_token_id=None, min_length=0):
+                 pad_token_id=None, min_length=0, no_repeat_ngram_size=0, frequency_penalty=0.0, presence_penalty=0.0,
+                 penalty_begin=0, suppress_tokens=None):
         if not (temperature > 0.0 and temperature < float('inf')) or not 0.0 < top_p <= 1.0:
             raise ValueError('generation: temperature must be finite and > 0, top_p in (0, 1]')
         if not (repetition_penalty > 0.0 and repetition_penalty < float('inf')):
             raise ValueError('generation: repetition_penalty must be finite and > 0')
         if min_length < 0 or (eos_token_id is not None and eos_token_id < 0) or (pad_token_id is not None and pad_token_id < 0):
             raise ValueError('generation: min_length, eos_token_id and pad_token_id must not be negative')
+        if no_repeat_ngram_size < 0 or not all(abs(float(v)) < float('inf') for v in (frequency_penalty, presence_penalty)):
+            raise ValueError('generation: no_repeat_ngram_size must not be negative, frequency_penalty and presence_penalty finite')
+        self.no_repeat_ngram_size, self.penalty_begin = int(no_repeat_ngram_size), int(penalty_begin)
+        self.frequency_penalty, self.presence_penalty = float(frequency_penalty), float(presence_penalty)
+        self.suppress_tokens = None
+        if suppress_tokens is not None:               # a list or a tensor: on the device once, as the kernel reads it
+            self.suppress_tokens = torch.as_tensor(suppress_tokens).to(device=device, dtype=torch.int32).reshape(-1).contiguous()
+        self.limited = (self.no_repeat_ngram_size != 0 or self.frequency_penalty != 0.0 or self.presence_penalty != 0.0
+                        or self.suppress_tokens is not None)
         self.do_sample, self.temperature, self.top_k, self.top_p = do_sample, float(temperature), int(top_k), float(top_p)
         self.repetition_penalty, self.eos_token_id, self.min_length = float(repetition_penalty), eos_token_id, int(min_length)
         self.pad_token_id = pad_token_id if pad_token_id is not None else eos_token_id
         self.controlled = (repetition_penalty != 1.0 or eos_token_id is not None or pad_token_id is not None
-                           or min_length != 0)
+                           or min_length != 0 or self.limited)
         self.finished = None
         if do_sample and rng_state is None:       # from torch's generator: torch.manual_seed reproduces a run
             rng_state = torch.randint(-2 ** 63, 2 ** 63 - 1, (2,), dtype=torch.int64, device=device)
@@ -279,14 +339,21 @@ class _Picker:
                 out = bp_hip.pick_token(logits, self.do_sample, self.temperature, self.top_k, self.top_p, self.rng_state,
                                         counters, tokens=tokens, sequences=sequences)
             else:
+                limits = {}
+                if self.limited:                      # bp_pick_token_lim; without them the call is bp_pick_token_ctl's
+                    limits = dict(no_repeat_ngram_size=self.no_repeat_ngram_size, frequency_penalty=self.frequency_penalty,
+                                  presence_penalty=self.presence_penalty, penalty_begin=self.penalty_begin,
+                                  suppress_tokens=self.suppress_tokens)
                 out = bp_hip.pick_token(logits, self.do_sample, self.temperature, self.top_k, self.top_p, self.rng_state,
                                         counters, tokens=tokens, sequences=sequences,
                                         repetition_penalty=self.repetition_penalty, eos_token_id=self.eos_token_id,
-                                        pad_token_id=self.pad_token_id, min_length=self.min_length, finished=self.finished)
+                                        pad_token_id=self.pad_token_id, min_length=self.min_length, finished=self.finished,
+                                        **limits)
             return out.view(-1)
         picked = _eager_pick(logits, self.do_sample, self.temperature, self.top_k, self.top_p, self.rng_state, counters,
                              self.repetition_penalty, self.eos_token_id, self.pad_token_id, self.min_length, self.finished,
-                             sequences)
+                             sequences, self.no_repeat_ngram_size, self.frequency_penalty, self.presence_penalty,
+                             self.penalty_begin, self.suppress_tokens)
         if self.finished is not None:
             self.finished[picked == self.eos_token_id] = 1
         if tokens is not None:
@@ -408,7 +475,8 @@ def _run_loop(input_ids, model, max_length, pick, cg, kv_cache, picker=None, sto
         if kv_cache:
             return _decode_cached_picked(input_ids, model, max_length, picker, cg=cg, stop_check_every=stop_check_every)
         if picker.controlled:
-            raise ValueError('generation: repetition_penalty, eos_token_id, pad_token_id and min_length need kv_cache=True '
+            raise ValueError('generation: repetition_penalty, eos_token_id, pad_token_id, min_length, no_repeat_ngram_size, '
+                             'frequency_penalty, presence_penalty and suppress_tokens need kv_cache=True '
                              '(the loops without a cache are the reference\'s, statement for statement)')
         pick = picker.loop_pick(input_ids)
     if kv_cache:
@@ -419,50 +487,62 @@ def _run_loop(input_ids, model, max_length, pick, cg, kv_cache, picker=None, sto
 
 
 def _picker(input_ids, do_sample, temperature, top_k, top_p, rng_state, device_pick, repetition_penalty=1.0,
-            eos_token_id=None, pad_token_id=None, min_length=0, stop_check_every=None):
-    """None when no option of the device pick is given: the loops then run exactly as before."""
+            eos_token_id=None, pad_token_id=None, min_length=0, stop_check_every=None, no_repeat_ngram_size=0,
+            frequency_penalty=0.0, presence_penalty=0.0, suppress_tokens=None):
+    """None when no option of the device pick is given: the loops then run exactly as before.  The frequency / presence
+    penalties count from the prompt length on: generated tokens only."""
     if stop_check_every is not None and stop_check_every < 1:
         raise ValueError('generation: stop_check_every must be >= 1')
     if not (device_pick or temperature != 1.0 or top_k != 0 or top_p != 1.0 or rng_state is not None
-            or repetition_penalty != 1.0 or eos_token_id is not None or pad_token_id is not None or min_length != 0):
+            or repetition_penalty != 1.0 or eos_token_id is not None or pad_token_id is not None or min_length != 0
+            or no_repeat_ngram_size != 0 or frequency_penalty != 0.0 or presence_penalty != 0.0 or suppress_tokens is not None):
         return None
     return _Picker(do_sample, temperature, top_k, top_p, rng_state, input_ids.device, repetition_penalty, eos_token_id,
-                   pad_token_id, min_length)
+                   pad_token_id, min_length, no_repeat_ngram_size, frequency_penalty, presence_penalty, input_ids.shape[1],
+                   suppress_tokens)
 
 
 _CONTROLS_DOC = """repetition_penalty, eos_token_id, pad_token_id (default: the EOS id), min_length (absolute, prompt included): the
     controls of bp_pick_token_ctl, kv_cache=True only; any of them selects the device pick.  With an EOS id a row ends at its
     first EOS behind the prompt, holds the pad behind it, `sequences` is cut to the longest row and `lengths` (batch,) int64
-    reports every row's end; the loop asks every `stop_check_every` steps whether all rows have ended (_StopPoll)."""
+    reports every row's end; the loop asks every `stop_check_every` steps whether all rows have ended (_StopPoll).
+    no_repeat_ngram_size (no n-gram occurs twice, prompt included), frequency_penalty, presence_penalty (an id generated n > 0
+    times loses frequency_penalty * n + presence_penalty; the prompt is not counted), suppress_tokens (a list or tensor of ids
+    that are never picked): the limits of bp_pick_token_lim, under the same conditions."""
 
 
 def greedy_decode(input_ids, model, max_length, cg=False, kv_cache=False, temperature=1.0, top_k=0, top_p=1.0,
                   rng_state=None, device_pick=False, repetition_penalty=1.0, eos_token_id=None, pad_token_id=None,
-                  min_length=0, stop_check_every=None):
+                  min_length=0, stop_check_every=None, no_repeat_ngram_size=0, frequency_penalty=0.0, presence_penalty=0.0,
+                  suppress_tokens=None):
     """input_ids (batch, seq_len) -> sequences (batch, max_length - 1): argmax continuation.
     cg=True: one captured full-width forward replayed per token (CUDA tensors only), see _decode_graphed.
     kv_cache=True: prefill once, then one cached step per token (with cg=True: one captured step), see _decode_cached.
     device_pick=True: the argmax runs in bp_pick_token (on CPU tensors: _eager_pick), with kv_cache and cg inside the
     captured step (_decode_cached_picked); the sampling options are accepted for symmetry and do not change an argmax.
-    repetition_penalty, eos_token_id, pad_token_id, min_length, stop_check_every: see _CONTROLS_DOC."""
+    repetition_penalty, eos_token_id, pad_token_id, min_length, stop_check_every, no_repeat_ngram_size, frequency_penalty,
+    presence_penalty, suppress_tokens: see _CONTROLS_DOC."""
     picker = _picker(input_ids, False, temperature, top_k, top_p, rng_state, device_pick, repetition_penalty, eos_token_id,
-                     pad_token_id, min_length, stop_check_every)
+                     pad_token_id, min_length, stop_check_every, no_repeat_ngram_size, frequency_penalty, presence_penalty,
+                     suppress_tokens)
     return _run_loop(input_ids, model, max_length, lambda logits: torch.argmax(logits, dim=-1), cg, kv_cache, picker,
                      stop_check_every)
 
 
 def sample(input_ids, model, max_length, cg=False, kv_cache=False, temperature=1.0, top_k=0, top_p=1.0, rng_state=None,
            device_pick=False, repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, min_length=0,
-           stop_check_every=None):
+           stop_check_every=None, no_repeat_ngram_size=0, frequency_penalty=0.0, presence_penalty=0.0, suppress_tokens=None):
     """Ancestral sampling from softmax(logits) (reference :23-48); cg / kv_cache as in greedy_decode.
     temperature, top_k (ties at the threshold kept, as the reference's top_k_filter, training/run_pplm.py:569-581), top_p:
     the usual filters; any of them, an `rng_state` or device_pick=True selects the device pick (bp_pick_token, contract in
     include/bp_hip.h; _eager_pick on CPU tensors).  rng_state: int64 {seed, offset} (bp_hip.new_rng_state), drawn from
     torch's generator when None; the token at sequence position t of row b is a pure function of (logits, rng_state, b, t),
     so cached, graphed and growing-prefix runs under one rng_state draw the same numbers.
-    repetition_penalty, eos_token_id, pad_token_id, min_length, stop_check_every: see _CONTROLS_DOC."""
+    repetition_penalty, eos_token_id, pad_token_id, min_length, stop_check_every, no_repeat_ngram_size, frequency_penalty,
+    presence_penalty, suppress_tokens: see _CONTROLS_DOC."""
     picker = _picker(input_ids, True, temperature, top_k, top_p, rng_state, device_pick, repetition_penalty, eos_token_id,
-                     pad_token_id, min_length, stop_check_every)
+                     pad_token_id, min_length, stop_check_every, no_repeat_ngram_size, frequency_penalty, presence_penalty,
+                     suppress_tokens)
 
     def pick(logits):
         return torch.distributions.Categorical(logits=torch.log_softmax(logits.float(), dim=-1)).sample()
@@ -714,19 +794,25 @@ class GenerationMixin:
 
     def generate(self, input_ids, max_length, return_dict_in_generate=False, output_scores=False, cg=False,
                  kv_cache=False, temperature=1.0, top_k=0, top_p=1.0, rng_state=None, device_pick=False,
-                 repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, min_length=0, stop_check_every=None):
+                 repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, min_length=0, stop_check_every=None,
+                 no_repeat_ngram_size=0, frequency_penalty=0.0, presence_penalty=0.0, suppress_tokens=None):
         return self._generate(greedy_decode, input_ids, max_length, return_dict_in_generate, output_scores, cg, kv_cache,
                               temperature=temperature, top_k=top_k, top_p=top_p, rng_state=rng_state,
                               device_pick=device_pick, repetition_penalty=repetition_penalty, eos_token_id=eos_token_id,
-                              pad_token_id=pad_token_id, min_length=min_length, stop_check_every=stop_check_every)
+                              pad_token_id=pad_token_id, min_length=min_length, stop_check_every=stop_check_every,
+                              no_repeat_ngram_size=no_repeat_ngram_size, frequency_penalty=frequency_penalty,
+                              presence_penalty=presence_penalty, suppress_tokens=suppress_tokens)
 
     def sample(self, input_ids, max_length, return_dict_in_generate=False, output_scores=False, cg=False,
                kv_cache=False, temperature=1.0, top_k=0, top_p=1.0, rng_state=None, device_pick=False,
-               repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, min_length=0, stop_check_every=None):
+               repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, min_length=0, stop_check_every=None,
+               no_repeat_ngram_size=0, frequency_penalty=0.0, presence_penalty=0.0, suppress_tokens=None):
         return self._generate(sample, input_ids, max_length, return_dict_in_generate, output_scores, cg, kv_cache,
                               temperature=temperature, top_k=top_k, top_p=top_p, rng_state=rng_state,
                               device_pick=device_pick, repetition_penalty=repetition_penalty, eos_token_id=eos_token_id,
-                              pad_token_id=pad_token_id, min_length=min_length, stop_check_every=stop_check_every)
+                              pad_token_id=pad_token_id, min_length=min_length, stop_check_every=stop_check_every,
+                              no_repeat_ngram_size=no_repeat_ngram_size, frequency_penalty=frequency_penalty,
+                              presence_penalty=presence_penalty, suppress_tokens=suppress_tokens)
 
     def beam_search(self, input_ids, max_length, num_beams, return_dict_in_generate=False, eos_token_id=None,
                     pad_token_id=None, length_penalty=0.0, cg=False, stop_check_every=None, **sampling_options):

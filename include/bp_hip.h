@@ -47,7 +47,9 @@ extern "C" {
                               argmax, temperature, top-k, top-p -- and BP_ERR_SAMPLING;
                               and another: bp_pick_token_ctl, the same pick with a repetition penalty, an EOS mask below
                               a minimal length and finished flags;
-                              and two more: bp_beam_pick / bp_beam_copy_rows, a beam-search step and the cache reorder) */
+                              and two more: bp_beam_pick / bp_beam_copy_rows, a beam-search step and the cache reorder;
+                              and one more: bp_pick_token_lim, the controlled pick with n-gram blocking, frequency /
+                              presence penalties and a list of suppressed ids) */
 
 /* element type of q/k/v/out/content tensors */
 #define BP_DTYPE_F16 0
@@ -65,7 +67,15 @@ extern "C" {
 #define BP_ERR_QUEUE_WS -8    /* persistent launch with queue_ws == NULL on a stream that is being captured            */
 #define BP_ERR_WORKSPACE -9   /* a caller-provided workspace is smaller than the entry point's *_ws_floats() query     */
 #define BP_ERR_SAMPLING -10   /* bp_pick_token: top_p outside (0, 1], or do_sample without an rng_state; bp_pick_token_ctl:
-                                 also a repetition_penalty not finite and > 0 or without sequences, an EOS id without flags */
+                                 also a repetition_penalty not finite and > 0 or without sequences, an EOS id without flags;
+                                 bp_pick_token_lim: also a non-finite frequency / presence penalty, n-gram blocking or a
+                                 penalty without sequences, n_suppress > 0 with a NULL or misaligned list */
+
+/* bounds of bp_pick_token_lim (BP_ERR_SHAPE beyond them) */
+#define BP_PICK_MAX_NGRAM 64                  /* no_repeat_ngram_size */
+#define BP_PICK_MAX_LIMITED_VOCAB (1 << 19)   /* vocab with any of its controls on: 19 id bits of a count entry, 64 KB a bitmap */
+#define BP_PICK_MAX_COUNTED_COLS 8191         /* seq_cols under a frequency / presence penalty: 13 count bits of an entry */
+#define BP_PICK_MAX_LDS_BYTES (160 * 1024)    /* static + dynamic LDS of one launch: the LDS of a CU */
 
 #define BP_QUEUE_WS_BYTES 64   /* `queue_ws` of the persistent sense-mix launches */
 
@@ -687,6 +697,48 @@ int bp_pick_token_ctl(const void *logits, int64_t *tokens, int64_t *sequences, f
                       int do_sample, float temperature, int top_k, float top_p,
                       float repetition_penalty, int eos_token_id, int pad_token_id, int min_length,
                       int dtype, bp_stream_t stream);
+
+/*
+ * bp_pick_token_lim -- bp_pick_token_ctl with limits on what a row may say: n-gram blocking, frequency and presence
+ * penalties over the row's history, and a list of suppressed ids (the no_repeat_ngram_size, frequency_penalty /
+ * presence_penalty and suppress_tokens of the common generation libraries).  (Additive, ABI still 11.)  Arguments as
+ * bp_pick_token_ctl's, and
+ *   no_repeat_ngram_size  n, 0 = off
+ *   frequency_penalty, presence_penalty  fp32, any finite value (negative ones reward repetition); 0 and 0 = off
+ *   penalty_begin  the first history position that is counted: the generation loops pass the prompt length, so the
+ *                  penalties count generated tokens only; 0 counts the prompt too
+ *   suppress_ids, n_suppress  device int32 list of ids that are never picked; ids outside [0, vocab) are ignored
+ * Per row b, with c = counters[b], the history h = sequences[b, 0 : Lh], Lh = min(max(c, 0), seq_cols) (0 when sequences is
+ * NULL; when c > seq_cols the history is the clamped one, as for bp_pick_token_ctl):
+ *   finished on entry: the pad, exactly as bp_pick_token_ctl, before anything else
+ *   an element's value is v = float(x), or float(x) * (1 / temperature) for sampling, and then in this order
+ *   1  pen(v), bp_pick_token_ctl's repetition penalty over the set of h (prompt included), unchanged
+ *   2  counts: n_v = the number of j in [min(penalty_begin, Lh), Lh) with h[j] == the element's id; when n_v > 0,
+ *      v = v - fmaf(frequency_penalty, float(n_v), presence_penalty): one fp32 fma and one subtraction (the OpenAI / vLLM
+ *      form); a NaN or an infinity passes through
+ *   3  ban: v = -inf when the id is in suppress_ids, or in the n-gram set, or is the EOS id while c < min_length
+ *   n-gram set (n >= 1): { h[i + n - 1] : 0 <= i <= Lh - n, h[i + t] == h[Lh - n + 1 + t] for all 0 <= t <= n - 2 } inside
+ *      [0, vocab): the ids that would complete an n-gram the history already holds, prompt included.  The raw int64 values
+ *      are compared, so ids outside the vocabulary match each other; n = 1 bans every id of h; Lh < n bans nothing
+ *   the greedy answer, top_k, top_p, the draw and stats are bp_pick_token_ctl's on these values.  A row left without a
+ *   finite value is degenerate and takes the greedy answer, which for a row of -inf is index 0 -- also when 0 is banned
+ * With the controls off (n = 0, both penalties 0, n_suppress = 0) tokens and stats are bp_pick_token_ctl's, bit for bit.
+ * Per-row state lives in LDS: the history bitmap, a ban bitmap of the same shape, and for the counts an open-addressing
+ * table of 32-bit entries (id in the low 19 bits, count in the high 13) with the power of two >= 2 seq_cols slots.  No global
+ * workspace, no global atomics.
+ * Errors, before any launch: everything bp_pick_token_ctl rejects, with its codes; BP_ERR_SAMPLING (a non-finite penalty;
+ * n > 0 or a non-zero penalty with sequences == NULL; n_suppress > 0 with a NULL or misaligned list); BP_ERR_SHAPE (n outside
+ * 0..BP_PICK_MAX_NGRAM; n_suppress < 0; penalty_begin < 0; vocab > BP_PICK_MAX_LIMITED_VOCAB with any of these controls on;
+ * seq_cols > BP_PICK_MAX_COUNTED_COLS with a non-zero penalty; static + dynamic LDS above BP_PICK_MAX_LDS_BYTES: 68 112 bytes
+ * static, (vocab + 31) / 32 + 1 words per bitmap in use, 4 bytes per slot).
+ */
+int bp_pick_token_lim(const void *logits, int64_t *tokens, int64_t *sequences, float *stats, const uint64_t *rng_state,
+                      const int32_t *counters, int32_t *finished,
+                      int batch, int vocab, int64_t row_stride, int64_t tokens_stride, int64_t seq_stride, int seq_cols,
+                      int do_sample, float temperature, int top_k, float top_p,
+                      float repetition_penalty, int eos_token_id, int pad_token_id, int min_length,
+                      int no_repeat_ngram_size, float frequency_penalty, float presence_penalty, int penalty_begin,
+                      const int32_t *suppress_ids, int n_suppress, int dtype, bp_stream_t stream);
 
 /*
  * bp_beam_pick -- one decode step of beam search on the device for `groups` prompts x `beam_width` (W, 1..8) hypotheses,

@@ -16,7 +16,9 @@ and every run of each (`<leg>_<pick>_ms`, `<leg>_<pick>_ms_runs`).  --sample tim
 of bp_pick_token_ctl: --repetition-penalty, --eos (an id that never occurs, e.g. 50263 of the padded vocabulary, times the
 polling of the finished flags alone), --min-length and --stop-check-every (kv legs only).  --variant adds a further pick
 that alternates with the others: the device pick with some generation options replaced, e.g.
-`--variant pen:repetition_penalty=1.2 --variant n4:eos_token_id=50263,stop_check_every=4`.
+`--variant pen:repetition_penalty=1.2 --variant n4:eos_token_id=50263,stop_check_every=4`, or with the limits of
+bp_pick_token_lim `--variant all:no_repeat_ngram_size=3,frequency_penalty=0.5,presence_penalty=0.5,suppress_tokens=11+12+13`
+(a list is written a+b+c).
 
 --beams W[,W...] times beam search instead (its own line per sense_table mode): for every width W, beam_search(num_beams=W,
 cg=True) against the greedy device-pick leg generate(kv_cache=True, cg=True, device_pick=True) at the same number of rows
@@ -100,7 +102,9 @@ def main():
             res.update(controls)
         for spec in a.variant:
             name, _, pairs = spec.partition(':')
-            changed = {k: json.loads(v) for k, v in (pair.split('=') for pair in pairs.split(',') if pair)}
+            # suppress_tokens is a list, written a+b+c (the comma separates the options)
+            changed = {k: [int(t) for t in v.split('+')] if k == 'suppress_tokens' else json.loads(v)
+                       for k, v in (pair.split('=') for pair in pairs.split(',') if pair)}
             options[name] = dict(options['device'], **changed)
             res['variant_' + name] = changed
             picks = picks + [name]
