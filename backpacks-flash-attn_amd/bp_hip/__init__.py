@@ -95,6 +95,7 @@ SIGNATURES = {
     'bp_beam_pick_ws_floats': (_i64, [_i32] * 2),
     'bp_beam_pick': (_i32, [_ptr] * 8 + [_i64] + [_i32] * 3 + [_i64] * 3 + [_i32] * 4 + [_ptr]),
     'bp_beam_copy_rows': (_i32, [_ptr] * 3 + [_i32] + [_ptr] * 2 + [_i32] * 3 + [_ptr]),
+    'bp_row_extremes': (_i32, [_ptr] * 5 + [_i32] * 2 + [_i64] + [_i32] * 2 + [_ptr]),
 }
 
 
@@ -1302,3 +1303,42 @@ def beam_copy_rows(tensors, parent, lengths, first_position):
     pos_bytes = (ctypes.c_int64 * n)(*[t[0, 0].numel() * t.element_size() for t in tensors])
     _call('bp_beam_copy_rows', parent.device, bases, strides, pos_bytes, n, parent.data_ptr(), lengths.data_ptr(), rows,
           int(first_position), min(t.shape[1] for t in tensors))
+
+
+# ---- row extremes on the device (C ABI bp_row_extremes) ---------------------------------------------------------------------------------------------------------------
+
+ROW_EXTREMES_MAX_N = 64
+
+
+def row_extremes_supported(logits, n):
+    """Whether bp_row_extremes takes this call: a (rows, cols) fp16 / bf16 / fp32 CUDA tensor with a contiguous last
+    dimension and 1 <= n <= min(cols, 64)."""
+    return (logits.is_cuda and logits.dim() == 2 and logits.dtype in _PICK_DTYPES
+            and logits.shape[1] >= 1 and logits.stride(1) == 1 and (logits.shape[0] <= 1 or logits.stride(0) >= logits.shape[1])
+            and 1 <= int(n) <= min(logits.shape[1], ROW_EXTREMES_MAX_N))
+
+
+def row_extremes(logits, n, largest=True, smallest=True, out=None):
+    """The n largest and / or the n smallest elements of every row of `logits` (rows, cols) fp16 / bf16 / fp32 (any row
+    stride), in one launch that reads no host value (contract in include/bp_hip.h): elements are ordered by the integer key
+    of their raw bits (-0 < +0, NaNs at the ends by sign), ties by ascending column.  Returns (top_val, top_idx, bot_val,
+    bot_idx): fp32 values and int32 columns, (rows, n) each, largest / smallest first; None for an end not asked for.
+    `out`: the same four (contiguous, or None) to write into instead of allocating."""
+    _require_cuda(logits)
+    n = int(n)
+    if logits.dim() != 2 or logits.dtype not in _PICK_DTYPES or (logits.shape[1] > 0 and logits.stride(1) != 1):
+        raise RuntimeError('bp_hip.row_extremes: logits must be (rows, cols) fp16 / bf16 / fp32 with a contiguous last dimension')
+    rows, cols = logits.shape
+    want = (largest, largest, smallest, smallest)
+    dtypes = (torch.float32, torch.int32, torch.float32, torch.int32)
+    if out is None:
+        out = [torch.empty((rows, n), dtype=dt, device=logits.device) if w else None for w, dt in zip(want, dtypes)]
+    else:
+        out = [o if w else None for w, o in zip(want, out)]
+        _require_cuda(*out)
+        for o, dt in zip(out, dtypes):
+            if o is not None and (o.shape != (rows, n) or o.dtype != dt or not o.is_contiguous()):
+                raise RuntimeError(f'bp_hip.row_extremes: every output must be a contiguous ({rows}, {n}) fp32 / int32 tensor')
+    _call('bp_row_extremes', logits.device, logits.data_ptr(), *[o.data_ptr() if o is not None else None for o in out],
+          rows, cols, logits.stride(0) if rows > 1 else max(cols, logits.stride(0)), n, _PICK_DTYPES[logits.dtype])
+    return tuple(out)

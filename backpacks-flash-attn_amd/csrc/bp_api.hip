@@ -1051,4 +1051,26 @@ int bp_beam_copy_rows(const void *const *bases, const int64_t *row_strides, cons
     return launch_status(bp::launch_beam_copy_rows(p, static_cast<hipStream_t>(stream)));
 }
 
+// ---- row extremes (bp_row_extremes) ----
+
+int bp_row_extremes(const void *logits, float *top_val, int32_t *top_idx, float *bot_val, int32_t *bot_idx,
+                    int rows, int cols, int64_t row_stride, int n, int dtype, bp_stream_t stream) {
+    if (dtype != BP_DTYPE_F16 && dtype != BP_DTYPE_BF16 && dtype != BP_DTYPE_F32) return BP_ERR_DTYPE;
+    // (the row reader rounds cols up by a 16-byte chunk at either end in 32-bit arithmetic: 16 columns of head room)
+    if (rows < 0 || cols < 1 || cols > 0x7fffffff - 16 || row_stride < cols) return BP_ERR_SHAPE;
+    if (n < 1 || n > BP_ROW_EXTREMES_MAX_N || n > cols) return BP_ERR_SHAPE;
+    const uintptr_t elem = dtype == BP_DTYPE_F32 ? 4 : 2;
+    if (reinterpret_cast<uintptr_t>(logits) % elem || reinterpret_cast<uintptr_t>(top_val) % 4
+        || reinterpret_cast<uintptr_t>(top_idx) % 4 || reinterpret_cast<uintptr_t>(bot_val) % 4
+        || reinterpret_cast<uintptr_t>(bot_idx) % 4)
+        return BP_ERR_SHAPE;
+    if (rows == 0) return BP_OK;
+    if (logits == nullptr) return BP_ERR_SHAPE;
+    if (top_val == nullptr && top_idx == nullptr && bot_val == nullptr && bot_idx == nullptr) return BP_OK;   // nothing asked for
+    bp::RowExtremesParams p{};
+    p.logits = logits; p.top_val = top_val; p.top_idx = top_idx; p.bot_val = bot_val; p.bot_idx = bot_idx;
+    p.row_stride = row_stride; p.rows = rows; p.cols = cols; p.n = n;
+    return launch_status(bp::launch_row_extremes(p, dtype, static_cast<hipStream_t>(stream)));
+}
+
 }  // extern "C"

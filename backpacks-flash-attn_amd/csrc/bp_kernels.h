@@ -377,4 +377,15 @@ struct BeamCopyParams {
 };
 hipError_t launch_beam_copy_rows(const BeamCopyParams &p, hipStream_t stream);
 
+// bp_row_extremes (row_extremes.hip): the n largest / n smallest elements of every row, values and columns, in order
+constexpr int kRowExtremesMaxN = BP_ROW_EXTREMES_MAX_N;
+struct RowExtremesParams {
+    const void *logits;          // (rows, cols) 16-bit or fp32, element stride row_stride, last stride 1; only read
+    float *top_val, *bot_val;    // (rows, n) dense each; an end with both pointers NULL is skipped
+    int32_t *top_idx, *bot_idx;
+    int64_t row_stride;
+    int rows, cols, n;
+};
+hipError_t launch_row_extremes(const RowExtremesParams &p, int dtype, hipStream_t stream);
+
 }  // namespace bp

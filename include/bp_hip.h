@@ -49,7 +49,9 @@ extern "C" {
                               a minimal length and finished flags;
                               and two more: bp_beam_pick / bp_beam_copy_rows, a beam-search step and the cache reorder;
                               and one more: bp_pick_token_lim, the controlled pick with n-gram blocking, frequency /
-                              presence penalties and a list of suppressed ids) */
+                              presence penalties and a list of suppressed ids;
+                              and one more: bp_row_extremes, the n largest / n smallest elements of every row of a
+                              matrix, for the vocabulary projections of sense vectors) */
 
 /* element type of q/k/v/out/content tensors */
 #define BP_DTYPE_F16 0
@@ -76,6 +78,8 @@ extern "C" {
 #define BP_PICK_MAX_LIMITED_VOCAB (1 << 19)   /* vocab with any of its controls on: 19 id bits of a count entry, 64 KB a bitmap */
 #define BP_PICK_MAX_COUNTED_COLS 8191         /* seq_cols under a frequency / presence penalty: 13 count bits of an entry */
 #define BP_PICK_MAX_LDS_BYTES (160 * 1024)    /* static + dynamic LDS of one launch: the LDS of a CU */
+
+#define BP_ROW_EXTREMES_MAX_N 64              /* bp_row_extremes: elements kept per end of a row */
 
 #define BP_QUEUE_WS_BYTES 64   /* `queue_ws` of the persistent sense-mix launches */
 
@@ -800,6 +804,26 @@ int bp_beam_pick(const void *logits, float *beam_scores, int32_t *finished, int3
 int bp_beam_copy_rows(const void *const *bases, const int64_t *row_strides, const int64_t *pos_bytes, int nsets,
                       const int32_t *parent, const int32_t *lengths, int rows, int first_position, int max_positions,
                       bp_stream_t stream);
+
+/*
+ * bp_row_extremes -- the n largest and the n smallest elements of every row of a (rows, cols) matrix, with their columns,
+ * in order: what a full sort of C_l(x) @ E^T is read for (the reference's training/src/visualize_vocab.py:74-81) and, with
+ * n = 1, the row maximum of training/src/rank_vocab.py:84.  One launch that reads no host value.  (Additive, ABI still 11.)
+ *   logits       (rows, cols) fp16 / bf16 / fp32, element stride row_stride >= cols, last stride 1, any element-aligned
+ *                base.  Only read.
+ *   n            1 <= n <= min(cols, BP_ROW_EXTREMES_MAX_N)
+ *   top_val, top_idx   fp32 / int32 (rows, n) dense: the n largest elements of every row, largest first
+ *   bot_val, bot_idx   fp32 / int32 (rows, n) dense: the n smallest, smallest first
+ *                Any of the four may be NULL; an end whose two pointers are NULL is not computed.
+ * The row is a total order on integers: an element's key is the order-preserving integer key of its RAW bits (sign bit set:
+ * all bits flipped, else the sign bit flipped), so -0 < +0 and NaNs sit at the ends by their sign.  "Largest" ranks by (key
+ * descending, column ascending), "smallest" by (key ascending, column ascending); *_val is float(element).  The answer is
+ * unique and bit-identical across calls.
+ * Errors, before any launch: BP_ERR_DTYPE; BP_ERR_SHAPE (n out of range, cols < 1 or > 2^31 - 1 - 16, rows < 0,
+ * row_stride < cols, a NULL logits with rows > 0, a misaligned pointer).  rows == 0 is a successful no-op.
+ */
+int bp_row_extremes(const void *logits, float *top_val, int32_t *top_idx, float *bot_val, int32_t *bot_idx,
+                    int rows, int cols, int64_t row_stride, int n, int dtype, bp_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,7 @@
 """Micro-benchmark of the individual HIP kernels on synthetic N(0,1) data (never zeros: zero-filled
 inputs clock higher and flatter -- cdna_hip_programming.md section 5.4 rule 25).
 
-    python scripts/bench_kernels.py [--which flash,bwd,mix,mixgather,mixgatherref,lse,alpha,mixbwd,lnbwd,xent,gelu] [--batch 64] [--seq 1024] [--iters 20]
+    python scripts/bench_kernels.py [--which flash,bwd,mix,mixgather,mixgatherref,lse,alpha,mixbwd,lnbwd,xent,gelu,rowext] [--batch 64] [--seq 1024] [--iters 20]
 Prints one JSON line per kernel with avg ms, algorithmic TFLOP/s and GB/s (SURVEY section 8d figures)."""
 import argparse
 import json
@@ -175,6 +175,25 @@ def main():
         res.append(dict(kernel='column_sum', rows=rows, ms=ms, tflops=0.0, gbps=rows * cols * 2 / ms / 1e6))
         ms = timeit(lambda: g.sum(0), a.iters)
         res.append(dict(kernel='torch sum(0) (same bytes)', rows=rows, ms=ms, tflops=0.0, gbps=rows * cols * 2 / ms / 1e6))
+    if 'rowext' in which:
+        # bp_row_extremes alone over one block of the vocabulary projections (src/utils/sense_vocab.py): 8192 rows of Small's
+        # 50 264 logits, every element type, the row maximum (n = 1, one end) and the sense-table read (n = 20, both ends);
+        # bytes: the block once -- the later passes of n = 20 re-read it from cache
+        rows, V = 8192, 50264
+        for name, et in (('bf16', torch.bfloat16), ('fp16', torch.float16), ('fp32', torch.float32)):
+            x = torch.randn(rows, V, device=dev).to(et)
+            for n, both in ((1, False), (1, True), (20, True)):
+                out = bp_hip.row_extremes(x, n, smallest=both)
+                ms = timeit(lambda: bp_hip.row_extremes(x, n, smallest=both, out=out), a.iters)
+                res.append(dict(kernel='row_extremes', elem=name, rows=rows, cols=V, n=n, ends=2 if both else 1, ms=ms,
+                                tflops=0.0, gbps=rows * V * x.element_size() / ms / 1e6))
+            ms = timeit(lambda: x.max(-1), a.iters)
+            res.append(dict(kernel='torch max(-1) (same bytes)', elem=name, rows=rows, cols=V, ms=ms, tflops=0.0,
+                            gbps=rows * V * x.element_size() / ms / 1e6))
+            ms = timeit(lambda: (torch.topk(x, 20, largest=True), torch.topk(x, 20, largest=False)), max(2, a.iters // 4))
+            res.append(dict(kernel='torch topk(20) at both ends (same bytes)', elem=name, rows=rows, cols=V, ms=ms, tflops=0.0,
+                            gbps=rows * V * x.element_size() / ms / 1e6))
+            del x
     for r in res:
         r.update(batch=r.get('batch', B), seq=S, dtype=a.dtype)
         print(json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()}), flush=True)
