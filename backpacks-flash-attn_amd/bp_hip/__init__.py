@@ -1138,6 +1138,49 @@ def sense_rows_dot(table, row_index, new_row, cache_seqlens, vec, out):
 _PICK_DTYPES = {torch.float16: 0, torch.bfloat16: 1, torch.float32: 2}
 
 
+def pick_form(repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, min_length=0, finished=None,
+              no_repeat_ngram_size=0, frequency_penalty=0.0, presence_penalty=0.0, penalty_begin=0, suppress_tokens=None):
+    """The C ABI entry pick_token calls for these options: 'lim' (bp_pick_token_lim) when any limit is given, else 'ctl'
+    (bp_pick_token_ctl) when any control is, else 'plain' (bp_pick_token).  A non-zero penalty_begin counts as a limit."""
+    if not (no_repeat_ngram_size == 0 and frequency_penalty == 0.0 and presence_penalty == 0.0 and penalty_begin == 0
+            and suppress_tokens is None):
+        return 'lim'
+    if not (repetition_penalty == 1.0 and eos_token_id is None and pad_token_id is None and min_length == 0
+            and finished is None):
+        return 'ctl'
+    return 'plain'
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _pick_outputs(who, rows, logits, tokens, sequences, finished):
+    """What pick_token and beam_pick share: the checks of logits (rows, vocab), tokens (allocated when None), sequences and
+    finished, rows = B or groups * W.  Returns tokens and the arguments that place tokens and sequences in both ABIs."""
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.dtype not in _PICK_DTYPES:
+        raise RuntimeError(f'bp_hip.{who}: logits must be ({rows}, vocab) fp16 / bf16 / fp32 with a contiguous last dimension')
+    n = logits.shape[0]
+    if tokens is None:
+        tokens = torch.empty((n,), dtype=torch.int64, device=logits.device)
+    if tokens.dtype != torch.int64 or tokens.numel() != n or tokens.shape[0] != n:
+        raise RuntimeError(f'bp_hip.{who}: tokens must be int64 with {rows} elements along its first dimension')
+    if sequences is not None and (sequences.dim() != 2 or sequences.shape[0] != n or sequences.dtype != torch.int64
+                                  or sequences.stride(1) != 1):
+        raise RuntimeError(f'bp_hip.{who}: sequences must be ({rows}, cols) int64 with a contiguous last dimension')
+    if finished is not None and (finished.shape != (n,) or finished.dtype != torch.int32 or not finished.is_contiguous()):
+        raise RuntimeError(f'bp_hip.{who}: finished must be a contiguous ({rows},) int32 tensor')
+    strides = (logits.stride(0), tokens.stride(0) if n > 1 else 1, sequences.stride(0) if sequences is not None else 0,
+               sequences.shape[1] if sequences is not None else 0)
+    return tokens, strides
+
+
+def _pad_id(eos_token_id, pad_token_id):
+    if pad_token_id is not None:
+        return int(pad_token_id)
+    return int(eos_token_id) if eos_token_id is not None else 0
+
+
 def pick_token(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rng_state=None, counters=None, tokens=None,
                sequences=None, return_stats=False, repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, min_length=0,
                finished=None, no_repeat_ngram_size=0, frequency_penalty=0.0, presence_penalty=0.0, penalty_begin=0,
@@ -1162,10 +1205,9 @@ def pick_token(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rng
     select bp_pick_token_lim, the controlled pick with more limits: an id that would complete an n-gram the history already
     holds and every id of suppress_tokens count as -inf, and an id that occurs n > 0 times at the history positions >=
     penalty_begin loses frequency_penalty * n + presence_penalty.  With all of them at their defaults the call routes exactly as
-    described above."""
+    described above (pick_form is the rule)."""
     _require_cuda(logits, rng_state, counters, tokens, sequences, finished, suppress_tokens)
-    if logits.dim() != 2 or logits.stride(1) != 1 or logits.dtype not in _PICK_DTYPES:
-        raise RuntimeError('bp_hip.pick_token: logits must be (B, vocab) fp16 / bf16 / fp32 with a contiguous last dimension')
+    tokens, strides = _pick_outputs('pick_token', 'B', logits, tokens, sequences, finished)
     batch, vocab = logits.shape
     if do_sample and rng_state is None:
         rng_state = new_rng_state(logits.device)
@@ -1173,60 +1215,25 @@ def pick_token(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rng
         raise RuntimeError('bp_hip.pick_token: rng_state must be a contiguous int64 tensor of 2 elements')
     if counters is not None and (counters.shape != (batch,) or counters.dtype != torch.int32 or not counters.is_contiguous()):
         raise RuntimeError('bp_hip.pick_token: counters must be a contiguous (B,) int32 tensor')
-    if tokens is None:
-        tokens = torch.empty((batch,), dtype=torch.int64, device=logits.device)
-    if tokens.dtype != torch.int64 or tokens.numel() != batch or tokens.shape[0] != batch:
-        raise RuntimeError('bp_hip.pick_token: tokens must be int64 with B elements along its first dimension')
-    if sequences is not None and (sequences.dim() != 2 or sequences.shape[0] != batch or sequences.dtype != torch.int64
-                                  or sequences.stride(1) != 1):
-        raise RuntimeError('bp_hip.pick_token: sequences must be (B, cols) int64 with a contiguous last dimension')
+    if suppress_tokens is not None and (suppress_tokens.dim() != 1 or suppress_tokens.dtype != torch.int32
+                                        or not suppress_tokens.is_contiguous()):
+        raise RuntimeError('bp_hip.pick_token: suppress_tokens must be a contiguous 1-d int32 tensor')
     stats = torch.empty((batch, 4), dtype=torch.float32, device=logits.device) if return_stats else None
-    if not (no_repeat_ngram_size == 0 and frequency_penalty == 0.0 and presence_penalty == 0.0 and penalty_begin == 0
-            and suppress_tokens is None):
-        if finished is not None and (finished.shape != (batch,) or finished.dtype != torch.int32
-                                     or not finished.is_contiguous()):
-            raise RuntimeError('bp_hip.pick_token: finished must be a contiguous (B,) int32 tensor')
-        if suppress_tokens is not None and (suppress_tokens.dim() != 1 or suppress_tokens.dtype != torch.int32
-                                            or not suppress_tokens.is_contiguous()):
-            raise RuntimeError('bp_hip.pick_token: suppress_tokens must be a contiguous 1-d int32 tensor')
-        if pad_token_id is None:
-            pad_token_id = eos_token_id if eos_token_id is not None else 0
+    form = pick_form(repetition_penalty, eos_token_id, pad_token_id, min_length, finished, no_repeat_ngram_size,
+                     frequency_penalty, presence_penalty, penalty_begin, suppress_tokens)
+    args = [logits.data_ptr(), tokens.data_ptr(), _ptr(sequences), _ptr(stats), _ptr(rng_state), _ptr(counters)]
+    if form != 'plain':
+        args.append(_ptr(finished))
+    args += [batch, vocab, *strides, int(bool(do_sample)), float(temperature), int(top_k), float(top_p)]
+    if form != 'plain':
+        args += [float(repetition_penalty), -1 if eos_token_id is None else int(eos_token_id),
+                 _pad_id(eos_token_id, pad_token_id), int(min_length)]
+    if form == 'lim':
         n_suppress = suppress_tokens.numel() if suppress_tokens is not None else 0
-        _call('bp_pick_token_lim', logits.device,
-              logits.data_ptr(), tokens.data_ptr(), sequences.data_ptr() if sequences is not None else None,
-              stats.data_ptr() if stats is not None else None, rng_state.data_ptr() if rng_state is not None else None,
-              counters.data_ptr() if counters is not None else None, finished.data_ptr() if finished is not None else None,
-              batch, vocab, logits.stride(0), tokens.stride(0) if batch > 1 else 1,
-              sequences.stride(0) if sequences is not None else 0, sequences.shape[1] if sequences is not None else 0,
-              int(bool(do_sample)), float(temperature), int(top_k), float(top_p), float(repetition_penalty),
-              -1 if eos_token_id is None else int(eos_token_id), int(pad_token_id), int(min_length),
-              int(no_repeat_ngram_size), float(frequency_penalty), float(presence_penalty), int(penalty_begin),
-              suppress_tokens.data_ptr() if n_suppress else None, n_suppress, _PICK_DTYPES[logits.dtype])
-        return (tokens, stats) if return_stats else tokens
-    if not (repetition_penalty == 1.0 and eos_token_id is None and pad_token_id is None and min_length == 0
-            and finished is None):
-        if finished is not None and (finished.shape != (batch,) or finished.dtype != torch.int32
-                                     or not finished.is_contiguous()):
-            raise RuntimeError('bp_hip.pick_token: finished must be a contiguous (B,) int32 tensor')
-        if pad_token_id is None:
-            pad_token_id = eos_token_id if eos_token_id is not None else 0
-        _call('bp_pick_token_ctl', logits.device,
-              logits.data_ptr(), tokens.data_ptr(), sequences.data_ptr() if sequences is not None else None,
-              stats.data_ptr() if stats is not None else None, rng_state.data_ptr() if rng_state is not None else None,
-              counters.data_ptr() if counters is not None else None, finished.data_ptr() if finished is not None else None,
-              batch, vocab, logits.stride(0), tokens.stride(0) if batch > 1 else 1,
-              sequences.stride(0) if sequences is not None else 0, sequences.shape[1] if sequences is not None else 0,
-              int(bool(do_sample)), float(temperature), int(top_k), float(top_p), float(repetition_penalty),
-              -1 if eos_token_id is None else int(eos_token_id), int(pad_token_id), int(min_length),
-              _PICK_DTYPES[logits.dtype])
-        return (tokens, stats) if return_stats else tokens
-    _call('bp_pick_token', logits.device,
-          logits.data_ptr(), tokens.data_ptr(), sequences.data_ptr() if sequences is not None else None,
-          stats.data_ptr() if stats is not None else None, rng_state.data_ptr() if rng_state is not None else None,
-          counters.data_ptr() if counters is not None else None, batch, vocab, logits.stride(0),
-          tokens.stride(0) if batch > 1 else 1, sequences.stride(0) if sequences is not None else 0,
-          sequences.shape[1] if sequences is not None else 0, int(bool(do_sample)), float(temperature), int(top_k),
-          float(top_p), _PICK_DTYPES[logits.dtype])
+        args += [int(no_repeat_ngram_size), float(frequency_penalty), float(presence_penalty), int(penalty_begin),
+                 suppress_tokens.data_ptr() if n_suppress else None, n_suppress]
+    _call({'plain': 'bp_pick_token', 'ctl': 'bp_pick_token_ctl', 'lim': 'bp_pick_token_lim'}[form], logits.device,
+          *args, _PICK_DTYPES[logits.dtype])
     return (tokens, stats) if return_stats else tokens
 
 
@@ -1242,38 +1249,25 @@ def beam_pick(logits, beam_scores, parent, beam_width, finished=None, tokens=Non
     written with the global row every slot continues.  tokens / sequences / counters as pick_token's.  Two launches that
     read no host value (legal inside a HIP-graph capture).  Returns tokens."""
     _require_cuda(logits, beam_scores, parent, finished, tokens, sequences, counters)
-    if logits.dim() != 2 or logits.stride(1) != 1 or logits.dtype not in _PICK_DTYPES:
-        raise RuntimeError('bp_hip.beam_pick: logits must be (groups * W, vocab) fp16 / bf16 / fp32 with a contiguous last dimension')
+    tokens, strides = _pick_outputs('beam_pick', 'groups * W', logits, tokens, sequences, finished)
     rows, vocab = logits.shape
     beam_width = int(beam_width)
     if beam_width < 1 or rows % beam_width:
         raise RuntimeError('bp_hip.beam_pick: the rows of logits must be a multiple of beam_width >= 1')
     groups = rows // beam_width
     for name, t, dtype in (('beam_scores', beam_scores, torch.float32), ('parent', parent, torch.int32),
-                           ('finished', finished, torch.int32), ('counters', counters, torch.int32)):
+                           ('counters', counters, torch.int32)):
         if t is not None and (t.shape != (rows,) or t.dtype != dtype or not t.is_contiguous()):
             raise RuntimeError(f'bp_hip.beam_pick: {name} must be a contiguous (groups * W,) {dtype} tensor')
-    if tokens is None:
-        tokens = torch.empty((rows,), dtype=torch.int64, device=logits.device)
-    if tokens.dtype != torch.int64 or tokens.numel() != rows or tokens.shape[0] != rows:
-        raise RuntimeError('bp_hip.beam_pick: tokens must be int64 with groups * W elements along its first dimension')
-    if sequences is not None and (sequences.dim() != 2 or sequences.shape[0] != rows or sequences.dtype != torch.int64
-                                  or sequences.stride(1) != 1):
-        raise RuntimeError('bp_hip.beam_pick: sequences must be (groups * W, cols) int64 with a contiguous last dimension')
-    if pad_token_id is None:
-        pad_token_id = eos_token_id if eos_token_id is not None else 0
     key = (logits.device, groups, beam_width)
     ws = _beam_ws.get(key)
     if ws is None:
         floats = lib().bp_beam_pick_ws_floats(groups, beam_width)
         ws = _beam_ws[key] = torch.empty((max(int(floats), 4),), dtype=torch.float32, device=logits.device)
     _call('bp_beam_pick', logits.device,
-          logits.data_ptr(), beam_scores.data_ptr(), finished.data_ptr() if finished is not None else None,
-          parent.data_ptr(), tokens.data_ptr(), sequences.data_ptr() if sequences is not None else None,
-          counters.data_ptr() if counters is not None else None, ws.data_ptr(), ws.numel(),
-          groups, beam_width, vocab, logits.stride(0), tokens.stride(0) if rows > 1 else 1,
-          sequences.stride(0) if sequences is not None else 0, sequences.shape[1] if sequences is not None else 0,
-          -1 if eos_token_id is None else int(eos_token_id), int(pad_token_id), _PICK_DTYPES[logits.dtype])
+          logits.data_ptr(), beam_scores.data_ptr(), _ptr(finished), parent.data_ptr(), tokens.data_ptr(), _ptr(sequences),
+          _ptr(counters), ws.data_ptr(), ws.numel(), groups, beam_width, vocab, *strides,
+          -1 if eos_token_id is None else int(eos_token_id), _pad_id(eos_token_id, pad_token_id), _PICK_DTYPES[logits.dtype])
     return tokens
 
 

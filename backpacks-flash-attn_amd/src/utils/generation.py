@@ -199,6 +199,71 @@ def _history_counts(sequences, counters, vocab, begin):
     return counts[:, :vocab]
 
 
+@dataclass(frozen=True)
+class PickOptions:
+    """The options of the pick, as greedy_decode / sample and GenerationMixin.generate / .sample take them by keyword.
+    temperature, top_k (ties at the threshold kept), top_p: the usual filters of a draw; an argmax ignores them.
+    repetition_penalty, eos_token_id, pad_token_id (default: the EOS id), min_length (absolute, prompt included): the
+    controls of bp_pick_token_ctl, kv_cache=True only; any of them selects the device pick.  With an EOS id a row ends at its
+    first EOS behind the prompt, holds the pad behind it, `sequences` is cut to the longest row and `lengths` (batch,) int64
+    reports every row's end; the loop asks every `stop_check_every` steps whether all rows have ended (_StopPoll).
+    no_repeat_ngram_size (no n-gram occurs twice, prompt included), frequency_penalty, presence_penalty (an id generated n > 0
+    times loses frequency_penalty * n + presence_penalty; the prompt is not counted), suppress_tokens (a list or tensor of ids
+    that are never picked): the limits of bp_pick_token_lim, under the same conditions.
+    do_sample and penalty_begin (the first history position the two counted penalties see) are set by the entry points: sample()
+    draws, and the penalties count from the prompt length on."""
+    do_sample: bool = False
+    temperature: float = 1.0
+    top_k: int = 0
+    top_p: float = 1.0
+    repetition_penalty: float = 1.0
+    eos_token_id: Optional[int] = None
+    pad_token_id: Optional[int] = None
+    min_length: int = 0
+    no_repeat_ngram_size: int = 0
+    frequency_penalty: float = 0.0
+    presence_penalty: float = 0.0
+    penalty_begin: int = 0
+    suppress_tokens: object = None
+
+    def __post_init__(self):
+        if not (self.temperature > 0.0 and self.temperature < float('inf')) or not 0.0 < self.top_p <= 1.0:
+            raise ValueError('generation: temperature must be finite and > 0, top_p in (0, 1]')
+        if not (self.repetition_penalty > 0.0 and self.repetition_penalty < float('inf')):
+            raise ValueError('generation: repetition_penalty must be finite and > 0')
+        if self.min_length < 0 or (self.eos_token_id is not None and self.eos_token_id < 0) or (
+                self.pad_token_id is not None and self.pad_token_id < 0):
+            raise ValueError('generation: min_length, eos_token_id and pad_token_id must not be negative')
+        if self.no_repeat_ngram_size < 0 or not all(abs(float(v)) < float('inf')
+                                                    for v in (self.frequency_penalty, self.presence_penalty)):
+            raise ValueError('generation: no_repeat_ngram_size must not be negative, frequency_penalty and presence_penalty finite')
+
+    @property
+    def limited(self):
+        """Whether a limit of bp_pick_token_lim is given; penalty_begin alone is none."""
+        return (self.no_repeat_ngram_size != 0 or self.frequency_penalty != 0.0 or self.presence_penalty != 0.0
+                or self.suppress_tokens is not None)
+
+    @property
+    def controlled(self):
+        """Whether a control of bp_pick_token_ctl or a limit is given: the options that need kv_cache=True."""
+        return (self.repetition_penalty != 1.0 or self.eos_token_id is not None or self.pad_token_id is not None
+                or self.min_length != 0 or self.limited)
+
+    @property
+    def wants_device_pick(self):
+        """Whether any option asks for the device pick: without one (and without rng_state / device_pick=True) the loops pick
+        on the host, as the reference does."""
+        return self.temperature != 1.0 or self.top_k != 0 or self.top_p != 1.0 or self.controlled
+
+    @property
+    def pad(self):
+        """What a finished row holds: the pad id, else the EOS id, else 0."""
+        if self.pad_token_id is not None:
+            return self.pad_token_id
+        return self.eos_token_id if self.eos_token_id is not None else 0
+
+
 def _eager_pick(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rng_state=None, counters=None,
                 repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, min_length=0, finished=None, sequences=None,
                 no_repeat_ngram_size=0, frequency_penalty=0.0, presence_penalty=0.0, penalty_begin=0, suppress_tokens=None):
@@ -301,61 +366,37 @@ class _Picker:
     With an EOS id it owns `finished` (batch,) int32 on the logits' device, allocated by the first pick: the flag of a row
     is set by the pick that returns the EOS id, and every later pick of that row returns the pad."""
 
-    def __init__(self, do_sample, temperature, top_k, top_p, rng_state, device, repetition_penalty=1.0, eos_token_id=None,
-                 pad_token_id=None, min_length=0, no_repeat_ngram_size=0, frequency_penalty=0.0, presence_penalty=0.0,
-                 penalty_begin=0, suppress_tokens=None):
-        if not (temperature > 0.0 and temperature < float('inf')) or not 0.0 < top_p <= 1.0:
-            raise ValueError('generation: temperature must be finite and > 0, top_p in (0, 1]')
-        if not (repetition_penalty > 0.0 and repetition_penalty < float('inf')):
-            raise ValueError('generation: repetition_penalty must be finite and > 0')
-        if min_length < 0 or (eos_token_id is not None and eos_token_id < 0) or (pad_token_id is not None and pad_token_id < 0):
-            raise ValueError('generation: min_length, eos_token_id and pad_token_id must not be negative')
-        if no_repeat_ngram_size < 0 or not all(abs(float(v)) < float('inf') for v in (frequency_penalty, presence_penalty)):
-            raise ValueError('generation: no_repeat_ngram_size must not be negative, frequency_penalty and presence_penalty finite')
-        self.no_repeat_ngram_size, self.penalty_begin = int(no_repeat_ngram_size), int(penalty_begin)
-        self.frequency_penalty, self.presence_penalty = float(frequency_penalty), float(presence_penalty)
-        self.suppress_tokens = None
-        if suppress_tokens is not None:               # a list or a tensor: on the device once, as the kernel reads it
-            self.suppress_tokens = torch.as_tensor(suppress_tokens).to(device=device, dtype=torch.int32).reshape(-1).contiguous()
-        self.limited = (self.no_repeat_ngram_size != 0 or self.frequency_penalty != 0.0 or self.presence_penalty != 0.0
-                        or self.suppress_tokens is not None)
-        self.do_sample, self.temperature, self.top_k, self.top_p = do_sample, float(temperature), int(top_k), float(top_p)
-        self.repetition_penalty, self.eos_token_id, self.min_length = float(repetition_penalty), eos_token_id, int(min_length)
-        self.pad_token_id = pad_token_id if pad_token_id is not None else eos_token_id
-        self.controlled = (repetition_penalty != 1.0 or eos_token_id is not None or pad_token_id is not None
-                           or min_length != 0 or self.limited)
-        self.finished = None
-        if do_sample and rng_state is None:       # from torch's generator: torch.manual_seed reproduces a run
+    def __init__(self, options, rng_state, device):
+        self.options, self.finished = options, None
+        if options.do_sample and rng_state is None:       # from torch's generator: torch.manual_seed reproduces a run
             rng_state = torch.randint(-2 ** 63, 2 ** 63 - 1, (2,), dtype=torch.int64, device=device)
         self.rng_state = rng_state.to(device) if rng_state is not None else None
+        # the keywords of bp_hip.pick_token and of _eager_pick, by the entry they select (bp_hip.pick_form): the controls only
+        # for a controlled pick and the limits, penalty_begin among them, only for a limited one
+        o = options
+        self.keywords = dict(do_sample=o.do_sample, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p)
+        if o.controlled:
+            self.keywords.update(repetition_penalty=o.repetition_penalty, eos_token_id=o.eos_token_id, pad_token_id=o.pad,
+                                 min_length=o.min_length)
+        if o.limited:
+            suppress = o.suppress_tokens
+            if suppress is not None:                  # a list or a tensor: on the device once, as the kernel reads it
+                suppress = torch.as_tensor(suppress).to(device=device, dtype=torch.int32).reshape(-1).contiguous()
+            self.keywords.update(no_repeat_ngram_size=o.no_repeat_ngram_size, frequency_penalty=o.frequency_penalty,
+                                 presence_penalty=o.presence_penalty, penalty_begin=o.penalty_begin, suppress_tokens=suppress)
 
     def __call__(self, logits, counters, tokens=None, sequences=None):
         """tokens (batch,) int64; also stored into `tokens` (batch elements) and column counters[b] of `sequences`."""
-        if self.eos_token_id is not None and self.finished is None:
+        if self.options.eos_token_id is not None and self.finished is None:
             self.finished = torch.zeros((logits.shape[0],), dtype=torch.int32, device=logits.device)
         if logits.is_cuda:
             import bp_hip
-            if not self.controlled:
-                out = bp_hip.pick_token(logits, self.do_sample, self.temperature, self.top_k, self.top_p, self.rng_state,
-                                        counters, tokens=tokens, sequences=sequences)
-            else:
-                limits = {}
-                if self.limited:                      # bp_pick_token_lim; without them the call is bp_pick_token_ctl's
-                    limits = dict(no_repeat_ngram_size=self.no_repeat_ngram_size, frequency_penalty=self.frequency_penalty,
-                                  presence_penalty=self.presence_penalty, penalty_begin=self.penalty_begin,
-                                  suppress_tokens=self.suppress_tokens)
-                out = bp_hip.pick_token(logits, self.do_sample, self.temperature, self.top_k, self.top_p, self.rng_state,
-                                        counters, tokens=tokens, sequences=sequences,
-                                        repetition_penalty=self.repetition_penalty, eos_token_id=self.eos_token_id,
-                                        pad_token_id=self.pad_token_id, min_length=self.min_length, finished=self.finished,
-                                        **limits)
-            return out.view(-1)
-        picked = _eager_pick(logits, self.do_sample, self.temperature, self.top_k, self.top_p, self.rng_state, counters,
-                             self.repetition_penalty, self.eos_token_id, self.pad_token_id, self.min_length, self.finished,
-                             sequences, self.no_repeat_ngram_size, self.frequency_penalty, self.presence_penalty,
-                             self.penalty_begin, self.suppress_tokens)
+            return bp_hip.pick_token(logits, rng_state=self.rng_state, counters=counters, tokens=tokens, sequences=sequences,
+                                     finished=self.finished, **self.keywords).view(-1)
+        picked = _eager_pick(logits, rng_state=self.rng_state, counters=counters, finished=self.finished, sequences=sequences,
+                             **self.keywords)
         if self.finished is not None:
-            self.finished[picked == self.eos_token_id] = 1
+            self.finished[picked == self.options.eos_token_id] = 1
         if tokens is not None:
             tokens.view(-1).copy_(picked)
         if sequences is not None:
@@ -381,17 +422,18 @@ class _StopPoll:
     pinned host memory behind the steps queued so far, with an event behind the copy; the copy that is READ at that point is
     the previous poll's, whose event is waited for.  So the host is never more than 2 * every steps ahead of the device,
     the device has work queued while the host waits, and the loop ends at most 2 * every steps after the last row has
-    finished.  CPU flags are read directly."""
+    finished.  CPU flags are read directly; without flags (no EOS id) the answer is always no."""
 
-    def __init__(self, finished, every):
-        self.finished, self.every, self.steps, self.pending = finished, every, 0, None
-        if finished.is_cuda:
+    def __init__(self, finished, every=None):
+        self.finished, self.every = finished, _DEFAULT_STOP_CHECK_EVERY if every is None else every
+        self.steps, self.pending = 0, None
+        if finished is not None and finished.is_cuda:
             self.host = [torch.zeros(finished.shape, dtype=finished.dtype).pin_memory() for _ in range(2)]
 
     def all_finished(self):
         """Called once per step; True when a poll shows every flag set."""
         self.steps += 1
-        if self.steps % self.every:
+        if self.finished is None or self.steps % self.every:
             return False
         if not self.finished.is_cuda:
             return bool(self.finished.all())
@@ -418,6 +460,55 @@ def _trim_at_eos(sequences, seqlen_og, eos_token_id, pad_token_id):
     return sequences[:, :int(lengths.max())].contiguous(), lengths
 
 
+class _CachedSteps:
+    """What the loops with the pick on the device share: the InferenceParams with device lengths, the preallocated
+    `sequences` (rows, width) holding the prompt, width = max(prompt, max_length - 1) as in _decode, the one-token input
+    `static_ids` a pick writes for the next step, the prefill, and the loop over cached steps.  The cache capacity is `width`
+    rounded up to a multiple of `capacity_multiple` positions; `sequences` gets the same row stride."""
+
+    def __init__(self, input_ids, model, max_length, capacity_multiple=1):
+        rows, self.prompt = input_ids.shape
+        self.input_ids, self.model = input_ids, model
+        self.width = max(self.prompt, max_length - 1)
+        capacity = (self.width + capacity_multiple - 1) // capacity_multiple * capacity_multiple
+        self.ip = InferenceParams(max_sequence_len=capacity, max_batch_size=rows)
+        self.lengths = self.ip.lengths_per_sample = torch.zeros((rows,), dtype=torch.int32, device=input_ids.device)
+        self.sequences = torch.zeros((rows, capacity), dtype=torch.int64, device=input_ids.device)[:, :self.width]
+        self.sequences[:, :self.prompt] = input_ids
+        self.static_ids = torch.zeros((rows, 1), dtype=torch.int64, device=input_ids.device)
+
+    def prefill(self):
+        """The logits of the prompt's last position; the caches then hold the prompt."""
+        logits = self.model(self.input_ids, inference_params=self.ip).logits[:, -1]
+        self.ip.sequence_len_offset = self.prompt
+        self.lengths.fill_(self.prompt)
+        return logits
+
+    def step_logits(self):
+        """The head of every step: the model on `static_ids`, then lengths + 1 -- the counter of the step's pick."""
+        logits = self.model(self.static_ids, inference_params=self.ip).logits[:, -1]
+        self.lengths += 1
+        return logits
+
+    def run(self, step, steps, cg, poll):
+        """`steps` times step(), until `poll` (a _StopPoll, asked once per step) shows every row finished.  With cg on CUDA
+        tensors the step is captured once, after one eager step and only when a further step remains, and replayed."""
+        graph = None
+        for i in range(steps):
+            if graph is not None:
+                graph.replay()
+            else:
+                step()
+                if cg and self.input_ids.is_cuda and i + 1 < steps:
+                    graph = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(graph):
+                        step()
+                    # the capture ran nothing: lengths, caches, static_ids and sequences are as the eager step left them
+            self.ip.sequence_len_offset += 1
+            if poll.all_finished():
+                break
+
+
 def _decode_cached_picked(input_ids, model, max_length, picker, cg=False, stop_check_every=None):
     """_decode_cached with the pick on the device: the counter of a pick is `lengths_per_sample` after the step's
     increment, the pick writes the next step's input (`static_ids`) and column `position` of the preallocated `sequences`.
@@ -426,55 +517,34 @@ def _decode_cached_picked(input_ids, model, max_length, picker, cg=False, stop_c
     With an EOS id the loop ends once a poll (_StopPoll, every `stop_check_every` steps) shows every row finished; finished
     rows keep stepping on the pad token until then.  The result is cut at the rows' ends (_trim_at_eos), so it depends
     neither on the polling interval nor on how far the loop overran."""
-    batch, seqlen_og = input_ids.shape
-    width = max(seqlen_og, max_length - 1)
-    ip = InferenceParams(max_sequence_len=width, max_batch_size=batch)
-    ip.lengths_per_sample = torch.zeros((batch,), dtype=torch.int32, device=input_ids.device)
-    sequences = torch.zeros((batch, width), dtype=torch.int64, device=input_ids.device)
-    sequences[:, :seqlen_og] = input_ids
-    static_ids = torch.zeros((batch, 1), dtype=torch.int64, device=input_ids.device)
+    d = _CachedSteps(input_ids, model, max_length)
+
+    def pick(logits):
+        picker(logits, d.lengths, tokens=d.static_ids, sequences=d.sequences)
+
     with torch.inference_mode():
-        logits = model(input_ids, inference_params=ip).logits[:, -1]
-        scores = [logits]
-        ip.sequence_len_offset = seqlen_og
-        ip.lengths_per_sample.fill_(seqlen_og)
-        picker(logits, ip.lengths_per_sample, tokens=static_ids, sequences=sequences)
-        poll = None
-        if picker.eos_token_id is not None:
-            poll = _StopPoll(picker.finished, _DEFAULT_STOP_CHECK_EVERY if stop_check_every is None else stop_check_every)
-
-        def step():
-            step_logits = model(static_ids, inference_params=ip).logits[:, -1]
-            ip.lengths_per_sample += 1
-            picker(step_logits, ip.lengths_per_sample, tokens=static_ids, sequences=sequences)
-
-        seqlen = seqlen_og + 1
-        graph = None
-        while seqlen < max_length:
-            if graph is not None:
-                graph.replay()
-            else:
-                step()
-                if cg and input_ids.is_cuda and seqlen + 1 < max_length:
-                    graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(graph):
-                        step()
-                    # the capture ran nothing: lengths, caches, static_ids and sequences are as the eager step left them
-            ip.sequence_len_offset += 1
-            seqlen += 1
-            if poll is not None and poll.all_finished():
-                break
-        lengths = None
-        if picker.eos_token_id is not None:
-            sequences, lengths = _trim_at_eos(sequences, seqlen_og, picker.eos_token_id, picker.pad_token_id)
-    return DecoderOnlyOutput(sequences=sequences.to(input_ids.dtype), scores=tuple(scores), lengths=lengths)
+        logits = d.prefill()
+        pick(logits)
+        d.run(lambda: pick(d.step_logits()), max_length - d.prompt - 1, cg, _StopPoll(picker.finished, stop_check_every))
+        sequences, lengths, o = d.sequences, None, picker.options
+        if o.eos_token_id is not None:
+            sequences, lengths = _trim_at_eos(sequences, d.prompt, o.eos_token_id, o.pad)
+    return DecoderOnlyOutput(sequences=sequences.to(input_ids.dtype), scores=(logits,), lengths=lengths)
 
 
-def _run_loop(input_ids, model, max_length, pick, cg, kv_cache, picker=None, stop_check_every=None):
-    if picker is not None:
+def _run_loop(input_ids, model, max_length, pick, do_sample, cg, kv_cache, rng_state, device_pick, stop_check_every,
+              pick_options):
+    """The loop greedy_decode / sample select: with the device pick (_Picker) when device_pick, an rng_state or one of
+    `pick_options` asks for it, else with the host's `pick` exactly as the reference runs."""
+    if stop_check_every is not None and stop_check_every < 1:
+        raise ValueError('generation: stop_check_every must be >= 1')
+    # the frequency / presence penalties count from the prompt length on: generated tokens only
+    options = PickOptions(do_sample=do_sample, penalty_begin=input_ids.shape[1], **pick_options)
+    if device_pick or rng_state is not None or options.wants_device_pick:
+        picker = _Picker(options, rng_state, input_ids.device)
         if kv_cache:
             return _decode_cached_picked(input_ids, model, max_length, picker, cg=cg, stop_check_every=stop_check_every)
-        if picker.controlled:
+        if options.controlled:
             raise ValueError('generation: repetition_penalty, eos_token_id, pad_token_id, min_length, no_repeat_ngram_size, '
                              'frequency_penalty, presence_penalty and suppress_tokens need kv_cache=True '
                              '(the loops without a cache are the reference\'s, statement for statement)')
@@ -486,67 +556,31 @@ def _run_loop(input_ids, model, max_length, pick, cg, kv_cache, picker=None, sto
     return _decode(input_ids, model, max_length, pick)
 
 
-def _picker(input_ids, do_sample, temperature, top_k, top_p, rng_state, device_pick, repetition_penalty=1.0,
-            eos_token_id=None, pad_token_id=None, min_length=0, stop_check_every=None, no_repeat_ngram_size=0,
-            frequency_penalty=0.0, presence_penalty=0.0, suppress_tokens=None):
-    """None when no option of the device pick is given: the loops then run exactly as before.  The frequency / presence
-    penalties count from the prompt length on: generated tokens only."""
-    if stop_check_every is not None and stop_check_every < 1:
-        raise ValueError('generation: stop_check_every must be >= 1')
-    if not (device_pick or temperature != 1.0 or top_k != 0 or top_p != 1.0 or rng_state is not None
-            or repetition_penalty != 1.0 or eos_token_id is not None or pad_token_id is not None or min_length != 0
-            or no_repeat_ngram_size != 0 or frequency_penalty != 0.0 or presence_penalty != 0.0 or suppress_tokens is not None):
-        return None
-    return _Picker(do_sample, temperature, top_k, top_p, rng_state, input_ids.device, repetition_penalty, eos_token_id,
-                   pad_token_id, min_length, no_repeat_ngram_size, frequency_penalty, presence_penalty, input_ids.shape[1],
-                   suppress_tokens)
-
-
-_CONTROLS_DOC = """repetition_penalty, eos_token_id, pad_token_id (default: the EOS id), min_length (absolute, prompt included): the
-    controls of bp_pick_token_ctl, kv_cache=True only; any of them selects the device pick.  With an EOS id a row ends at its
-    first EOS behind the prompt, holds the pad behind it, `sequences` is cut to the longest row and `lengths` (batch,) int64
-    reports every row's end; the loop asks every `stop_check_every` steps whether all rows have ended (_StopPoll).
-    no_repeat_ngram_size (no n-gram occurs twice, prompt included), frequency_penalty, presence_penalty (an id generated n > 0
-    times loses frequency_penalty * n + presence_penalty; the prompt is not counted), suppress_tokens (a list or tensor of ids
-    that are never picked): the limits of bp_pick_token_lim, under the same conditions."""
-
-
-def greedy_decode(input_ids, model, max_length, cg=False, kv_cache=False, temperature=1.0, top_k=0, top_p=1.0,
-                  rng_state=None, device_pick=False, repetition_penalty=1.0, eos_token_id=None, pad_token_id=None,
-                  min_length=0, stop_check_every=None, no_repeat_ngram_size=0, frequency_penalty=0.0, presence_penalty=0.0,
-                  suppress_tokens=None):
+def greedy_decode(input_ids, model, max_length, cg=False, kv_cache=False, rng_state=None, device_pick=False,
+                  stop_check_every=None, **pick_options):
     """input_ids (batch, seq_len) -> sequences (batch, max_length - 1): argmax continuation.
     cg=True: one captured full-width forward replayed per token (CUDA tensors only), see _decode_graphed.
     kv_cache=True: prefill once, then one cached step per token (with cg=True: one captured step), see _decode_cached.
     device_pick=True: the argmax runs in bp_pick_token (on CPU tensors: _eager_pick), with kv_cache and cg inside the
     captured step (_decode_cached_picked); the sampling options are accepted for symmetry and do not change an argmax.
-    repetition_penalty, eos_token_id, pad_token_id, min_length, stop_check_every, no_repeat_ngram_size, frequency_penalty,
-    presence_penalty, suppress_tokens: see _CONTROLS_DOC."""
-    picker = _picker(input_ids, False, temperature, top_k, top_p, rng_state, device_pick, repetition_penalty, eos_token_id,
-                     pad_token_id, min_length, stop_check_every, no_repeat_ngram_size, frequency_penalty, presence_penalty,
-                     suppress_tokens)
-    return _run_loop(input_ids, model, max_length, lambda logits: torch.argmax(logits, dim=-1), cg, kv_cache, picker,
-                     stop_check_every)
+    pick_options: the keywords of PickOptions, see there."""
+    return _run_loop(input_ids, model, max_length, lambda logits: torch.argmax(logits, dim=-1), False, cg, kv_cache, rng_state,
+                     device_pick, stop_check_every, pick_options)
 
 
-def sample(input_ids, model, max_length, cg=False, kv_cache=False, temperature=1.0, top_k=0, top_p=1.0, rng_state=None,
-           device_pick=False, repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, min_length=0,
-           stop_check_every=None, no_repeat_ngram_size=0, frequency_penalty=0.0, presence_penalty=0.0, suppress_tokens=None):
+def sample(input_ids, model, max_length, cg=False, kv_cache=False, rng_state=None, device_pick=False, stop_check_every=None,
+           **pick_options):
     """Ancestral sampling from softmax(logits) (reference :23-48); cg / kv_cache as in greedy_decode.
     temperature, top_k (ties at the threshold kept, as the reference's top_k_filter, training/run_pplm.py:569-581), top_p:
     the usual filters; any of them, an `rng_state` or device_pick=True selects the device pick (bp_pick_token, contract in
     include/bp_hip.h; _eager_pick on CPU tensors).  rng_state: int64 {seed, offset} (bp_hip.new_rng_state), drawn from
     torch's generator when None; the token at sequence position t of row b is a pure function of (logits, rng_state, b, t),
     so cached, graphed and growing-prefix runs under one rng_state draw the same numbers.
-    repetition_penalty, eos_token_id, pad_token_id, min_length, stop_check_every, no_repeat_ngram_size, frequency_penalty,
-    presence_penalty, suppress_tokens: see _CONTROLS_DOC."""
-    picker = _picker(input_ids, True, temperature, top_k, top_p, rng_state, device_pick, repetition_penalty, eos_token_id,
-                     pad_token_id, min_length, stop_check_every, no_repeat_ngram_size, frequency_penalty, presence_penalty,
-                     suppress_tokens)
-
+    pick_options: the keywords of PickOptions, see there."""
     def pick(logits):
         return torch.distributions.Categorical(logits=torch.log_softmax(logits.float(), dim=-1)).sample()
-    return _run_loop(input_ids, model, max_length, pick, cg, kv_cache, picker, stop_check_every)
+    return _run_loop(input_ids, model, max_length, pick, True, cg, kv_cache, rng_state, device_pick, stop_check_every,
+                     pick_options)
 
 
 # ---- beam search on the KV cache: bp_beam_pick / bp_beam_copy_rows, or their torch restatements on CPU tensors -----------------
@@ -701,35 +735,27 @@ def beam_search(input_ids, model, max_length, num_beams, eos_token_id=None, pad_
         pad_token_id = eos_token_id if eos_token_id is not None else 0
     batch, seqlen_og = input_ids.shape
     rows, dev = batch * W, input_ids.device
-    width = max(seqlen_og, max_length - 1)
-    ids = input_ids.repeat_interleave(W, dim=0)
     # bp_beam_copy_rows wants rows that start on 16-byte boundaries: the cache capacity is rounded up to four positions (the
     # int32 row index of the Backpack's cache is the narrowest row), the sequence buffer gets the same row stride
-    capacity = (width + 3) // 4 * 4
-    ip = InferenceParams(max_sequence_len=capacity, max_batch_size=rows)
-    ip.lengths_per_sample = torch.zeros((rows,), dtype=torch.int32, device=dev)
-    sequences = torch.zeros((rows, capacity), dtype=torch.int64, device=dev)[:, :width]
-    sequences[:, :seqlen_og] = ids
-    static_ids = torch.zeros((rows, 1), dtype=torch.int64, device=dev)
+    d = _CachedSteps(input_ids.repeat_interleave(W, dim=0), model, max_length, capacity_multiple=4)
+    width, sequences, static_ids = d.width, d.sequences, d.static_ids
     beam_scores = torch.full((rows,), float('-inf'), dtype=torch.float32, device=dev)
     beam_scores[::W] = 0.0                          # the first pick takes all W winners from beam 0
     finished = torch.zeros((rows,), dtype=torch.int32, device=dev) if eos_token_id is not None else None
     parent = torch.arange(rows, dtype=torch.int32, device=dev)
     with torch.inference_mode():
-        logits = model(ids, inference_params=ip).logits[:, -1]
+        logits = d.prefill()
         if W > logits.shape[-1]:
             raise ValueError('beam_search: num_beams exceeds the vocabulary')
-        ip.sequence_len_offset = seqlen_og
-        ip.lengths_per_sample.fill_(seqlen_og)
-        sets = _beam_row_sets(ip, sequences)
+        sets = _beam_row_sets(d.ip, sequences)
 
         def pick(step_logits):
             if step_logits.is_cuda:
                 import bp_hip
                 bp_hip.beam_pick(step_logits, beam_scores, parent, W, finished=finished, tokens=static_ids,
-                                 sequences=sequences, counters=ip.lengths_per_sample, eos_token_id=eos_token_id,
+                                 sequences=sequences, counters=d.lengths, eos_token_id=eos_token_id,
                                  pad_token_id=pad_token_id)
-                bp_hip.beam_copy_rows(sets, parent, ip.lengths_per_sample, seqlen_og)
+                bp_hip.beam_copy_rows(sets, parent, d.lengths, seqlen_og)
                 return
             new_parent, tokens, scores, flags = _eager_beam_pick(step_logits, beam_scores, finished, W, eos_token_id,
                                                                  pad_token_id)
@@ -738,37 +764,17 @@ def beam_search(input_ids, model, max_length, num_beams, eos_token_id=None, pad_
             if finished is not None:
                 finished.copy_(flags)
             static_ids.view(-1).copy_(tokens)
-            cols = ip.lengths_per_sample.long()
+            cols = d.lengths.long()
             ok = cols < width
             at = torch.arange(rows, device=dev)
             sequences[at[ok], cols[ok]] = tokens[ok]
-            _eager_beam_copy_rows(sets, parent, ip.lengths_per_sample, seqlen_og)
+            _eager_beam_copy_rows(sets, parent, d.lengths, seqlen_og)
 
-        def step():
-            step_logits = model(static_ids, inference_params=ip).logits[:, -1]
-            ip.lengths_per_sample += 1
-            pick(step_logits)
-
-        poll = None
-        if finished is not None:
-            poll = _StopPoll(finished, _DEFAULT_STOP_CHECK_EVERY if stop_check_every is None else stop_check_every)
-        graph = None
-        for column in range(seqlen_og, width):       # the pick of this iteration lands in `column`
-            if column == seqlen_og:
-                pick(logits)                         # on the prefill's logits; nothing to copy yet
-            elif graph is not None:
-                graph.replay()
-            else:
-                step()
-                if cg and dev.type == 'cuda' and column + 1 < width:
-                    graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(graph):
-                        step()
-                    # the capture ran nothing: lengths, caches, scores and sequences are as the eager step left them
-            if column > seqlen_og:
-                ip.sequence_len_offset += 1
-            if poll is not None and poll.all_finished():
-                break
+        poll = _StopPoll(finished, stop_check_every)
+        if width > seqlen_og:                        # width - seqlen_og picks, the first on the prefill's logits: nothing to copy yet
+            pick(logits)
+            if not poll.all_finished():
+                d.run(lambda: pick(d.step_logits()), width - seqlen_og - 1, cg, poll)
         if eos_token_id is not None:
             sequences, lengths = _trim_at_eos(sequences, seqlen_og, eos_token_id, pad_token_id)
         else:
@@ -792,27 +798,17 @@ class GenerationMixin:
             output.scores = None
         return output if return_dict_in_generate else output.sequences
 
-    def generate(self, input_ids, max_length, return_dict_in_generate=False, output_scores=False, cg=False,
-                 kv_cache=False, temperature=1.0, top_k=0, top_p=1.0, rng_state=None, device_pick=False,
-                 repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, min_length=0, stop_check_every=None,
-                 no_repeat_ngram_size=0, frequency_penalty=0.0, presence_penalty=0.0, suppress_tokens=None):
+    def generate(self, input_ids, max_length, return_dict_in_generate=False, output_scores=False, cg=False, kv_cache=False,
+                 rng_state=None, device_pick=False, stop_check_every=None, **pick_options):
+        """greedy_decode on this model; pick_options: the keywords of PickOptions."""
         return self._generate(greedy_decode, input_ids, max_length, return_dict_in_generate, output_scores, cg, kv_cache,
-                              temperature=temperature, top_k=top_k, top_p=top_p, rng_state=rng_state,
-                              device_pick=device_pick, repetition_penalty=repetition_penalty, eos_token_id=eos_token_id,
-                              pad_token_id=pad_token_id, min_length=min_length, stop_check_every=stop_check_every,
-                              no_repeat_ngram_size=no_repeat_ngram_size, frequency_penalty=frequency_penalty,
-                              presence_penalty=presence_penalty, suppress_tokens=suppress_tokens)
+                              rng_state=rng_state, device_pick=device_pick, stop_check_every=stop_check_every, **pick_options)
 
-    def sample(self, input_ids, max_length, return_dict_in_generate=False, output_scores=False, cg=False,
-               kv_cache=False, temperature=1.0, top_k=0, top_p=1.0, rng_state=None, device_pick=False,
-               repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, min_length=0, stop_check_every=None,
-               no_repeat_ngram_size=0, frequency_penalty=0.0, presence_penalty=0.0, suppress_tokens=None):
+    def sample(self, input_ids, max_length, return_dict_in_generate=False, output_scores=False, cg=False, kv_cache=False,
+               rng_state=None, device_pick=False, stop_check_every=None, **pick_options):
+        """sample on this model; pick_options: the keywords of PickOptions."""
         return self._generate(sample, input_ids, max_length, return_dict_in_generate, output_scores, cg, kv_cache,
-                              temperature=temperature, top_k=top_k, top_p=top_p, rng_state=rng_state,
-                              device_pick=device_pick, repetition_penalty=repetition_penalty, eos_token_id=eos_token_id,
-                              pad_token_id=pad_token_id, min_length=min_length, stop_check_every=stop_check_every,
-                              no_repeat_ngram_size=no_repeat_ngram_size, frequency_penalty=frequency_penalty,
-                              presence_penalty=presence_penalty, suppress_tokens=suppress_tokens)
+                              rng_state=rng_state, device_pick=device_pick, stop_check_every=stop_check_every, **pick_options)
 
     def beam_search(self, input_ids, max_length, num_beams, return_dict_in_generate=False, eos_token_id=None,
                     pad_token_id=None, length_penalty=0.0, cg=False, stop_check_every=None, **sampling_options):

@@ -146,7 +146,7 @@ def _spread(runs):
 def beam_legs(model, ids, a, mode):
     """The --beams line: beam search against greedy at the same number of rows, then the two beam kernels alone."""
     import bp_hip
-    from src.utils.generation import InferenceParams, _beam_row_sets
+    from src.utils.generation import _beam_row_sets, _CachedSteps
     widths = [int(w) for w in a.beams.split(',')]
     new_tokens = a.max_length - 1 - a.prompt
     res = dict(model=a.model, batch=a.batch, prompt=a.prompt, max_length=a.max_length, new_tokens=new_tokens,
@@ -185,14 +185,11 @@ def beam_legs(model, ids, a, mode):
 
     dev = ids.device
     for W in widths:
-        rows, width = a.batch * W, a.max_length - 1
-        capacity = (width + 3) // 4 * 4
-        ip = InferenceParams(max_sequence_len=capacity, max_batch_size=rows)
-        ip.lengths_per_sample = torch.zeros((rows,), dtype=torch.int32, device=dev)
+        d = _CachedSteps(ids.repeat_interleave(W, dim=0), model, a.max_length, capacity_multiple=4)   # as beam_search sets up
+        rows, width = a.batch * W, d.width
         with torch.inference_mode():
-            logits = model(ids.repeat_interleave(W, dim=0), inference_params=ip).logits[:, -1]
-        sequences = torch.zeros((rows, capacity), dtype=torch.int64, device=dev)[:, :width]
-        sets = _beam_row_sets(ip, sequences)
+            logits = d.prefill()
+        sets = _beam_row_sets(d.ip, d.sequences)
         scores = torch.zeros((rows,), dtype=torch.float32, device=dev)
         parent = torch.empty((rows,), dtype=torch.int32, device=dev)
         res['beam%d_pick_host_issue_us' % W] = per_call_us(lambda: bp_hip.beam_pick(logits, scores, parent, W))

@@ -131,8 +131,8 @@ def test_finished_rows_give_the_pad_and_keep_their_flag():
         pad = kw.get('pad_token_id', 3)
         assert [got[b] for b in (1, 3, 5)] == [pad] * 3
     # _Picker owns the flags: set by the pick that returns the EOS id, kept afterwards
-    from src.utils.generation import _Picker
-    picker = _Picker(False, 1.0, 0, 1.0, None, torch.device('cpu'), eos_token_id=5, pad_token_id=9)
+    from src.utils.generation import PickOptions, _Picker
+    picker = _Picker(PickOptions(eos_token_id=5, pad_token_id=9), None, torch.device('cpu'))
     logits = torch.zeros(3, 12)
     logits[0, 5] = logits[1, 6] = logits[2, 5] = 1.0
     sequences = torch.full((3, 4), -1, dtype=torch.int64)
