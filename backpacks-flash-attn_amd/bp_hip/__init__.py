@@ -92,6 +92,8 @@ SIGNATURES = {
     'bp_pick_token_ctl': (_i32, [_ptr] * 7 + [_i32] * 2 + [_i64] * 3 + [_i32] * 2 + [_f32, _i32, _f32, _f32] + [_i32] * 4 + [_ptr]),
     'bp_pick_token_lim': (_i32, [_ptr] * 7 + [_i32] * 2 + [_i64] * 3 + [_i32] * 2 + [_f32, _i32, _f32, _f32] + [_i32] * 3
                           + [_i32, _f32, _f32, _i32, _ptr, _i32, _i32, _ptr]),
+    'bp_pick_token_lim_rows': (_i32, [_ptr] * 7 + [_i32] * 2 + [_i64] * 3 + [_i32] * 2 + [_f32, _i32, _f32, _f32] + [_i32] * 3
+                               + [_i32, _f32, _f32, _i32, _ptr, _i32, _ptr, _ptr, _i32, _ptr]),
     'bp_beam_pick_ws_floats': (_i64, [_i32] * 2),
     'bp_beam_pick': (_i32, [_ptr] * 8 + [_i64] + [_i32] * 3 + [_i64] * 3 + [_i32] * 4 + [_ptr]),
     'bp_beam_copy_rows': (_i32, [_ptr] * 3 + [_i32] + [_ptr] * 2 + [_i32] * 3 + [_ptr]),
@@ -1133,15 +1135,18 @@ def sense_rows_dot(table, row_index, new_row, cache_seqlens, vec, out):
     return out
 
 
-# ---- token selection on the device (C ABI bp_pick_token, bp_pick_token_ctl, bp_pick_token_lim) ---------------------------------------------------------------------------------------------
+# ---- token selection on the device (C ABI bp_pick_token, bp_pick_token_ctl, bp_pick_token_lim, bp_pick_token_lim_rows) ---------------------------------------------------------------------------------------------
 
 _PICK_DTYPES = {torch.float16: 0, torch.bfloat16: 1, torch.float32: 2}
 
 
 def pick_form(repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, min_length=0, finished=None,
               no_repeat_ngram_size=0, frequency_penalty=0.0, presence_penalty=0.0, penalty_begin=0, suppress_tokens=None):
-    """The C ABI entry pick_token calls for these options: 'lim' (bp_pick_token_lim) when any limit is given, else 'ctl'
-    (bp_pick_token_ctl) when any control is, else 'plain' (bp_pick_token).  A non-zero penalty_begin counts as a limit."""
+    """The C ABI entry pick_token calls for these options: 'rows' (bp_pick_token_lim_rows) when penalty_begin or min_length is a
+    tensor (one value per row), else 'lim' (bp_pick_token_lim) when any limit is given, else 'ctl' (bp_pick_token_ctl) when any
+    control is, else 'plain' (bp_pick_token).  A non-zero penalty_begin counts as a limit."""
+    if isinstance(penalty_begin, torch.Tensor) or isinstance(min_length, torch.Tensor):
+        return 'rows'
     if not (no_repeat_ngram_size == 0 and frequency_penalty == 0.0 and presence_penalty == 0.0 and penalty_begin == 0
             and suppress_tokens is None):
         return 'lim'
@@ -1205,8 +1210,13 @@ def pick_token(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rng
     select bp_pick_token_lim, the controlled pick with more limits: an id that would complete an n-gram the history already
     holds and every id of suppress_tokens count as -inf, and an id that occurs n > 0 times at the history positions >=
     penalty_begin loses frequency_penalty * n + presence_penalty.  With all of them at their defaults the call routes exactly as
-    described above (pick_form is the rule)."""
-    _require_cuda(logits, rng_state, counters, tokens, sequences, finished, suppress_tokens)
+    described above (pick_form is the rule).
+
+    penalty_begin and min_length each take an int, or a contiguous (B,) int32 tensor on the device with one value per row
+    (negative entries count as 0): a tensor selects bp_pick_token_lim_rows, the limited pick for rows that begin at different
+    positions.  The tensors are not read on the host."""
+    per_row = [v for v in (penalty_begin, min_length) if isinstance(v, torch.Tensor)]
+    _require_cuda(logits, rng_state, counters, tokens, sequences, finished, suppress_tokens, *per_row)
     tokens, strides = _pick_outputs('pick_token', 'B', logits, tokens, sequences, finished)
     batch, vocab = logits.shape
     if do_sample and rng_state is None:
@@ -1218,6 +1228,8 @@ def pick_token(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rng
     if suppress_tokens is not None and (suppress_tokens.dim() != 1 or suppress_tokens.dtype != torch.int32
                                         or not suppress_tokens.is_contiguous()):
         raise RuntimeError('bp_hip.pick_token: suppress_tokens must be a contiguous 1-d int32 tensor')
+    if any(v.shape != (batch,) or v.dtype != torch.int32 or not v.is_contiguous() for v in per_row):
+        raise RuntimeError('bp_hip.pick_token: a per-row penalty_begin / min_length must be a contiguous (B,) int32 tensor')
     stats = torch.empty((batch, 4), dtype=torch.float32, device=logits.device) if return_stats else None
     form = pick_form(repetition_penalty, eos_token_id, pad_token_id, min_length, finished, no_repeat_ngram_size,
                      frequency_penalty, presence_penalty, penalty_begin, suppress_tokens)
@@ -1227,13 +1239,16 @@ def pick_token(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rng
     args += [batch, vocab, *strides, int(bool(do_sample)), float(temperature), int(top_k), float(top_p)]
     if form != 'plain':
         args += [float(repetition_penalty), -1 if eos_token_id is None else int(eos_token_id),
-                 _pad_id(eos_token_id, pad_token_id), int(min_length)]
-    if form == 'lim':
+                 _pad_id(eos_token_id, pad_token_id), 0 if isinstance(min_length, torch.Tensor) else int(min_length)]
+    if form in ('lim', 'rows'):
         n_suppress = suppress_tokens.numel() if suppress_tokens is not None else 0
-        args += [int(no_repeat_ngram_size), float(frequency_penalty), float(presence_penalty), int(penalty_begin),
+        args += [int(no_repeat_ngram_size), float(frequency_penalty), float(presence_penalty),
+                 0 if isinstance(penalty_begin, torch.Tensor) else int(penalty_begin),
                  suppress_tokens.data_ptr() if n_suppress else None, n_suppress]
-    _call({'plain': 'bp_pick_token', 'ctl': 'bp_pick_token_ctl', 'lim': 'bp_pick_token_lim'}[form], logits.device,
-          *args, _PICK_DTYPES[logits.dtype])
+    if form == 'rows':
+        args += [v.data_ptr() if isinstance(v, torch.Tensor) else None for v in (penalty_begin, min_length)]
+    _call({'plain': 'bp_pick_token', 'ctl': 'bp_pick_token_ctl', 'lim': 'bp_pick_token_lim',
+           'rows': 'bp_pick_token_lim_rows'}[form], logits.device, *args, _PICK_DTYPES[logits.dtype])
     return (tokens, stats) if return_stats else tokens
 
 

@@ -895,7 +895,7 @@ int bp_sense_rows_dot(const void *table, const int32_t *row_index, const int32_t
     return launch_status(bp::launch_sense_rows_dot(p, dtype, static_cast<hipStream_t>(stream)));
 }
 
-// ---- token selection (bp_pick_token, bp_pick_token_ctl, bp_pick_token_lim) ----
+// ---- token selection (bp_pick_token, bp_pick_token_ctl, bp_pick_token_lim, bp_pick_token_lim_rows) ----
 
 // the argument checks of bp_pick_token and the parameters they admit; bp_pick_token_ctl adds its own behind them
 static int pick_params(bp::PickParams &p, const void *logits, int64_t *tokens, int64_t *sequences, float *stats,
@@ -965,14 +965,18 @@ int bp_pick_token_ctl(const void *logits, int64_t *tokens, int64_t *sequences, f
     return launch_status(bp::launch_pick_token_ctl(p, dtype, static_cast<hipStream_t>(stream)));
 }
 
-int bp_pick_token_lim(const void *logits, int64_t *tokens, int64_t *sequences, float *stats, const uint64_t *rng_state,
-                      const int32_t *counters, int32_t *finished,
-                      int batch, int vocab, int64_t row_stride, int64_t tokens_stride, int64_t seq_stride, int seq_cols,
-                      int do_sample, float temperature, int top_k, float top_p,
-                      float repetition_penalty, int eos_token_id, int pad_token_id, int min_length,
-                      int no_repeat_ngram_size, float frequency_penalty, float presence_penalty, int penalty_begin,
-                      const int32_t *suppress_ids, int n_suppress, int dtype, bp_stream_t stream) {
-    bp::PickParams p{};
+// bp_pick_token_lim and bp_pick_token_lim_rows: every check and every parameter; the two arrays are NULL for the former, and a
+// scalar is only read (and checked) where its array is NULL
+static int pick_lim_params(bp::PickParams &p, const void *logits, int64_t *tokens, int64_t *sequences, float *stats,
+                           const uint64_t *rng_state, const int32_t *counters, int32_t *finished,
+                           int batch, int vocab, int64_t row_stride, int64_t tokens_stride, int64_t seq_stride, int seq_cols,
+                           int do_sample, float temperature, int top_k, float top_p,
+                           float repetition_penalty, int eos_token_id, int pad_token_id, int min_length,
+                           int no_repeat_ngram_size, float frequency_penalty, float presence_penalty, int penalty_begin,
+                           const int32_t *suppress_ids, int n_suppress, const int32_t *penalty_begins,
+                           const int32_t *min_lengths, int dtype) {
+    if (penalty_begins != nullptr) penalty_begin = 0;
+    if (min_lengths != nullptr) min_length = 0;
     int e = pick_params(p, logits, tokens, sequences, stats, rng_state, counters, batch, vocab, row_stride,
                         tokens_stride, seq_stride, seq_cols, do_sample, temperature, top_k, top_p, dtype);
     if (e != BP_OK) return e;
@@ -984,6 +988,7 @@ int bp_pick_token_lim(const void *logits, int64_t *tokens, int64_t *sequences, f
     if (n_suppress > 0 && (suppress_ids == nullptr || reinterpret_cast<uintptr_t>(suppress_ids) % 4)) return BP_ERR_SAMPLING;
     if (no_repeat_ngram_size < 0 || no_repeat_ngram_size > BP_PICK_MAX_NGRAM || n_suppress < 0 || penalty_begin < 0)
         return BP_ERR_SHAPE;
+    if (reinterpret_cast<uintptr_t>(penalty_begins) % 4 || reinterpret_cast<uintptr_t>(min_lengths) % 4) return BP_ERR_SHAPE;
     const bool limited = no_repeat_ngram_size > 0 || counted || n_suppress > 0;
     if (limited && vocab > BP_PICK_MAX_LIMITED_VOCAB) return BP_ERR_SHAPE;   // 19 id bits of a table entry, 64 KB per bitmap
     if (counted && seq_cols > BP_PICK_MAX_COUNTED_COLS) return BP_ERR_SHAPE;  // 13 count bits of a table entry
@@ -991,8 +996,42 @@ int bp_pick_token_lim(const void *logits, int64_t *tokens, int64_t *sequences, f
     p.ngram = no_repeat_ngram_size; p.penalty_begin = penalty_begin;
     p.freq_pen = frequency_penalty; p.pres_pen = presence_penalty;
     p.table_shift = counted ? bp::lim_table_shift(seq_cols) : 31;
+    p.penalty_begins = penalty_begins; p.min_lengths = min_lengths;
     if (bp::pick_lim_lds_bytes(p) > BP_PICK_MAX_LDS_BYTES) return BP_ERR_SHAPE;
+    return BP_OK;
+}
+
+int bp_pick_token_lim(const void *logits, int64_t *tokens, int64_t *sequences, float *stats, const uint64_t *rng_state,
+                      const int32_t *counters, int32_t *finished,
+                      int batch, int vocab, int64_t row_stride, int64_t tokens_stride, int64_t seq_stride, int seq_cols,
+                      int do_sample, float temperature, int top_k, float top_p,
+                      float repetition_penalty, int eos_token_id, int pad_token_id, int min_length,
+                      int no_repeat_ngram_size, float frequency_penalty, float presence_penalty, int penalty_begin,
+                      const int32_t *suppress_ids, int n_suppress, int dtype, bp_stream_t stream) {
+    bp::PickParams p{};
+    const int e = pick_lim_params(p, logits, tokens, sequences, stats, rng_state, counters, finished, batch, vocab, row_stride,
+                                  tokens_stride, seq_stride, seq_cols, do_sample, temperature, top_k, top_p, repetition_penalty,
+                                  eos_token_id, pad_token_id, min_length, no_repeat_ngram_size, frequency_penalty,
+                                  presence_penalty, penalty_begin, suppress_ids, n_suppress, nullptr, nullptr, dtype);
+    if (e != BP_OK) return e;
     return launch_status(bp::launch_pick_token_lim(p, dtype, static_cast<hipStream_t>(stream)));
+}
+
+int bp_pick_token_lim_rows(const void *logits, int64_t *tokens, int64_t *sequences, float *stats, const uint64_t *rng_state,
+                           const int32_t *counters, int32_t *finished,
+                           int batch, int vocab, int64_t row_stride, int64_t tokens_stride, int64_t seq_stride, int seq_cols,
+                           int do_sample, float temperature, int top_k, float top_p,
+                           float repetition_penalty, int eos_token_id, int pad_token_id, int min_length,
+                           int no_repeat_ngram_size, float frequency_penalty, float presence_penalty, int penalty_begin,
+                           const int32_t *suppress_ids, int n_suppress, const int32_t *penalty_begins,
+                           const int32_t *min_lengths, int dtype, bp_stream_t stream) {
+    bp::PickParams p{};
+    const int e = pick_lim_params(p, logits, tokens, sequences, stats, rng_state, counters, finished, batch, vocab, row_stride,
+                                  tokens_stride, seq_stride, seq_cols, do_sample, temperature, top_k, top_p, repetition_penalty,
+                                  eos_token_id, pad_token_id, min_length, no_repeat_ngram_size, frequency_penalty,
+                                  presence_penalty, penalty_begin, suppress_ids, n_suppress, penalty_begins, min_lengths, dtype);
+    if (e != BP_OK) return e;
+    return launch_status(bp::launch_pick_token_rows(p, dtype, static_cast<hipStream_t>(stream)));
 }
 
 // ---- beam search (bp_beam_pick, bp_beam_copy_rows) ----

@@ -338,17 +338,21 @@ struct PickParams {
     int penalty_begin;           // history positions at or behind it are counted
     int table_shift;             // 32 - log2(slots of the count table)
     float freq_pen, pres_pen;
+    // bp_pick_token_lim_rows only (pick_token_rows.hip); no other kernel reads past pres_pen
+    const int32_t *penalty_begins;   // optional (batch): replaces penalty_begin for row b; negative entries count as 0
+    const int32_t *min_lengths;      // optional (batch): replaces min_length for row b; negative entries count as 0
 };
 hipError_t launch_pick_token(const PickParams &p, int dtype, hipStream_t stream);
 hipError_t launch_pick_token_ctl(const PickParams &p, int dtype, hipStream_t stream);
 hipError_t launch_pick_token_lim(const PickParams &p, int dtype, hipStream_t stream);
+hipError_t launch_pick_token_rows(const PickParams &p, int dtype, hipStream_t stream);
 // 32 - log2(slots), slots = the power of two >= 2 seq_cols (at least 2)
 inline int lim_table_shift(int seq_cols) {
     int log2 = 1;
     while ((1 << log2) < 2 * seq_cols) ++log2;
     return 32 - log2;
 }
-size_t pick_lim_lds_bytes(const PickParams &p);   // static + dynamic LDS of a bp_pick_token_lim launch
+size_t pick_lim_lds_bytes(const PickParams &p);   // static + dynamic LDS of a bp_pick_token_lim / _lim_rows launch
 
 // bp_beam_pick (beam_pick.hip): one beam-search step, rows r = g * beam_width + w
 struct BeamPickParams {

@@ -1,5 +1,6 @@
 // Token selection on the device for the decode loops: one row of logits in, one token out.  The shared body of
-// bp_pick_token (csrc/pick_token.hip), bp_pick_token_ctl (csrc/pick_token_ctl.hip) and bp_pick_token_lim (csrc/pick_token_lim.hip).
+// bp_pick_token (csrc/pick_token.hip), bp_pick_token_ctl (csrc/pick_token_ctl.hip), bp_pick_token_lim (csrc/pick_token_lim.hip) and
+// bp_pick_token_lim_rows (csrc/pick_token_rows.hip).
 //
 // Replaces the host-driven picks of the generation loops (src/utils/generation.py: torch.argmax, and
 // torch.distributions.Categorical, whose argument validation reads a device value on the host) and adds the sampling
@@ -57,6 +58,12 @@
 //            member's probe always ends on its id.  Every probe loop is bounded by the slot count.
 //   the helper applies, in this order: pen, v -= fmaf(frequency, count, presence) for a count > 0, -inf for a banned id or
 //   the masked EOS.  Everything behind the helper is the controlled form's.
+//
+// Row-limited form (bp_pick_token_lim_rows, pick_token_rows.hip): pick_token_kernel<RowLimited<ET>> is the limited form whose
+// penalty_begin and min_length may come from per-row device arrays (prompts of different lengths in one batch).  A third
+// tag and code object.  The two values of a row are resolved before pass 1 (row_params: a uniform load each, negative entries
+// clamped to 0, the scalar when the array is NULL) and are dead behind it: the first only feeds the `counted` flag of the
+// table build, the second only the choice of the masked column.  Nothing else differs from the limited form.
 #pragma once
 #include <type_traits>
 
@@ -70,9 +77,12 @@ namespace bp {
 template <class ET> struct Controlled {};
 // Limited form: the controlled one with the row limits of bp_pick_token_lim
 template <class ET> struct Limited {};
-template <class T> struct PickTag { using elem = T; static constexpr bool ctl = false, lim = false; };
-template <class T> struct PickTag<Controlled<T>> { using elem = T; static constexpr bool ctl = true, lim = false; };
-template <class T> struct PickTag<Limited<T>> { using elem = T; static constexpr bool ctl = true, lim = true; };
+// Row-limited form: the limited one with penalty_begin and min_length per row (bp_pick_token_lim_rows)
+template <class ET> struct RowLimited {};
+template <class T> struct PickTag { using elem = T; static constexpr bool ctl = false, lim = false, rows = false; };
+template <class T> struct PickTag<Controlled<T>> { using elem = T; static constexpr bool ctl = true, lim = false, rows = false; };
+template <class T> struct PickTag<Limited<T>> { using elem = T; static constexpr bool ctl = true, lim = true, rows = false; };
+template <class T> struct PickTag<RowLimited<T>> { using elem = T; static constexpr bool ctl = true, lim = true, rows = true; };
 
 // Dynamic LDS of the limited form, in 32-bit words: [members][banned][count table], each only when its control is on.  The
 // switches depend on the arguments alone, never on a row, so the host sizes the allocation from the same struct.
@@ -380,6 +390,26 @@ template <class ET> struct Logits<Limited<ET>> {
     }
 };
 
+// Row-limited rows: the limited form on the parameters of ITS row -- penalty_begin and min_length taken from the arrays where
+// they are given, one uniform load each, before pass 1 (both are dead behind it: the first feeds the `counted` flag of the
+// table build, the second the choice of the masked column).  The host never reads the arrays, so a negative entry is
+// clamped here.  The copy is of kernel arguments, i.e. of scalar registers that are loaded on use: no memory is involved.
+template <class TAG> BP_DEV PickParams row_params(const PickParams &p, int b) {
+    PickParams q = p;
+    if constexpr (PickTag<TAG>::rows) {
+        if (p.penalty_begins != nullptr) q.penalty_begin = p.penalty_begins[b] < 0 ? 0 : p.penalty_begins[b];
+        if (p.min_lengths != nullptr) q.min_length = p.min_lengths[b] < 0 ? 0 : p.min_lengths[b];
+    }
+    return q;
+}
+template <class ET> struct Logits<RowLimited<ET>> : Logits<Limited<ET>> {
+    BP_DEV Logits(const PickParams &p, int counter, const uint32_t *lds)
+        : Logits<Limited<ET>>(row_params<RowLimited<ET>>(p, blockIdx.x), counter, lds) {}
+    static BP_DEV void build(const PickParams &p, int b, int hist, uint32_t *lds) {
+        Logits<Limited<ET>>::build(row_params<RowLimited<ET>>(p, b), b, hist, lds);
+    }
+};
+
 // Where a limited row's results go, worked out before pass 1 and parked in vector registers: the limited passes need every
 // scalar register the controlled ones leave, and these addresses are not read again before the last lines of the kernel.
 struct LimOutputs {
@@ -410,6 +440,7 @@ template <class ET> struct SelectKey<Controlled<ET>> {
     static BP_DEV float threshold(uint32_t k, float) { return as_f32(PickElem<float>::unkey(k)); }
 };
 template <class ET> struct SelectKey<Limited<ET>> : SelectKey<Controlled<ET>> {};
+template <class ET> struct SelectKey<RowLimited<ET>> : SelectKey<Controlled<ET>> {};
 
 // Radix select, 8 bits a round from the top of the key: among the elements with z >= lo, the key K with
 //   weight{key > K} < target <= weight{key >= K}

@@ -121,7 +121,10 @@ class _Intervened(nn.Module, GenerationMixin, SenseIntervention):
 
 
 class WeightedBackpackLMHeadModel(_Intervened):
-    """Sense vectors re-weighted per (token, sense) before the contraction (reference :58-105)."""
+    """Sense vectors re-weighted per (token, sense) before the contraction (reference :58-105).
+    Generation from right-padded prompts of different lengths (`prompt_lengths`) is taken without annealing, where a
+    position's weight depends on its own token alone.  The annealed form raises NotImplementedError: its similarity sums
+    run over every position of the prefilled width, so they would count the pad columns behind a shorter prompt."""
 
     def __init__(self, backpack_network, content_weights, target_weight, annealing_scale, anneal=True,
                  upweight_nearby=True):
@@ -132,6 +135,12 @@ class WeightedBackpackLMHeadModel(_Intervened):
         self.annealing_scale = annealing_scale
         self.anneal = anneal
         self.upweight_nearby = upweight_nearby
+
+    def _ragged(self, prompt_lengths):
+        if prompt_lengths is not None and self.anneal:
+            raise NotImplementedError('prompt_lengths is not available with annealing: the similarity sums of the prefill '
+                                      'would count the pad columns behind a shorter prompt')
+        return super()._ragged(prompt_lengths)
 
     def _mixed(self, input_ids, position_ids):
         t, hidden, content = self._stages(input_ids, position_ids)

@@ -7,6 +7,8 @@ cg=True inside the captured step (_decode_cached_picked); without them the loops
 (bp_pick_token_ctl): rows stop at their EOS, the loop ends once every row has, and `lengths` reports where.
 `no_repeat_ngram_size`, `frequency_penalty`, `presence_penalty` and `suppress_tokens` (kv_cache=True only) select its limited
 form (bp_pick_token_lim): no n-gram twice, counted penalties on what was generated, ids that never appear.
+`prompt_lengths` (kv_cache=True only) takes a batch of right-padded prompts of different lengths: every row generates the same
+number of tokens behind ITS prompt (_CachedSteps; bp_pick_token_lim_rows where a limit or `min_new_tokens` needs the row's begin).
 Differences kept deliberately small: the result is a plain dataclass instead of the
 transformers `*DecoderOnlyOutput` classes (removed in transformers 5), and the appended token is
 `unsqueeze(1)` so batch sizes > 1 work (the reference's `unsqueeze(0)` in greedy_decode, :68, only
@@ -190,9 +192,12 @@ def _ngram_mask(sequences, counters, vocab, n):
 
 
 def _history_counts(sequences, counters, vocab, begin):
-    """(batch, vocab) int64: how often an id occurs at the positions [min(begin, Lh), Lh) of sequences[b]."""
+    """(batch, vocab) int64: how often an id occurs at the positions [min(begin, Lh), Lh) of sequences[b]; begin: an int, or
+    (batch,) with one value per row."""
     batch, cols = sequences.shape
     at = torch.arange(cols, device=sequences.device)[None, :]
+    if isinstance(begin, torch.Tensor):
+        begin = begin.to(sequences.device).long()[:, None]
     seen = (at >= begin) & (at < counters.long()[:, None]) & (sequences >= 0) & (sequences < vocab)
     counts = torch.zeros((batch, vocab + 1), dtype=torch.int64, device=sequences.device)
     counts.scatter_add_(1, torch.where(seen, sequences, torch.full_like(sequences, vocab)), seen.long())
@@ -210,8 +215,10 @@ class PickOptions:
     no_repeat_ngram_size (no n-gram occurs twice, prompt included), frequency_penalty, presence_penalty (an id generated n > 0
     times loses frequency_penalty * n + presence_penalty; the prompt is not counted), suppress_tokens (a list or tensor of ids
     that are never picked): the limits of bp_pick_token_lim, under the same conditions.
+    min_new_tokens: the EOS id is masked while a row has generated fewer tokens than that, i.e. below the absolute length
+    prompt + min_new_tokens of the row (with prompt_lengths: the row's own prompt); not together with min_length.
     do_sample and penalty_begin (the first history position the two counted penalties see) are set by the entry points: sample()
-    draws, and the penalties count from the prompt length on."""
+    draws, and the penalties count from the prompt length on (with prompt_lengths: from every row's own, _Picker)."""
     do_sample: bool = False
     temperature: float = 1.0
     top_k: int = 0
@@ -225,6 +232,7 @@ class PickOptions:
     presence_penalty: float = 0.0
     penalty_begin: int = 0
     suppress_tokens: object = None
+    min_new_tokens: int = 0
 
     def __post_init__(self):
         if not (self.temperature > 0.0 and self.temperature < float('inf')) or not 0.0 < self.top_p <= 1.0:
@@ -234,6 +242,8 @@ class PickOptions:
         if self.min_length < 0 or (self.eos_token_id is not None and self.eos_token_id < 0) or (
                 self.pad_token_id is not None and self.pad_token_id < 0):
             raise ValueError('generation: min_length, eos_token_id and pad_token_id must not be negative')
+        if self.min_new_tokens < 0 or (self.min_new_tokens != 0 and self.min_length != 0):
+            raise ValueError('generation: min_new_tokens must not be negative, and is not given together with min_length')
         if self.no_repeat_ngram_size < 0 or not all(abs(float(v)) < float('inf')
                                                     for v in (self.frequency_penalty, self.presence_penalty)):
             raise ValueError('generation: no_repeat_ngram_size must not be negative, frequency_penalty and presence_penalty finite')
@@ -248,7 +258,7 @@ class PickOptions:
     def controlled(self):
         """Whether a control of bp_pick_token_ctl or a limit is given: the options that need kv_cache=True."""
         return (self.repetition_penalty != 1.0 or self.eos_token_id is not None or self.pad_token_id is not None
-                or self.min_length != 0 or self.limited)
+                or self.min_length != 0 or self.min_new_tokens != 0 or self.limited)
 
     @property
     def wants_device_pick(self):
@@ -277,7 +287,8 @@ def _eager_pick(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rn
     The controls of bp_pick_token_ctl: ids of the history sequences[b, :counters[b]] have their value multiplied by
     repetition_penalty (negative values) or by its fp32 reciprocal (the others), in fp32, after the temperature; the EOS
     entry is -inf while counters[b] < min_length; rows whose `finished` flag is set take pad_token_id (default: the EOS
-    id).  `finished` is only read here: _Picker sets the flag of a row that picked the EOS id.
+    id).  `finished` is only read here: _Picker sets the flag of a row that picked the EOS id.  min_length and penalty_begin
+    each take an int or a (batch,) tensor with one value per row (bp_pick_token_lim_rows; negative entries count as 0).
 
     The limits of bp_pick_token_lim, applied behind the repetition penalty in this order: an id that occurs n > 0 times at
     the history positions >= penalty_begin loses fp32(frequency_penalty * n + presence_penalty) (float64 product and sum
@@ -295,6 +306,8 @@ def _eager_pick(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rn
     masked = None
     if eos_token_id is not None and eos_token_id >= 0:
         masked = torch.zeros((batch, vocab), dtype=torch.bool, device=x.device)
+        if isinstance(min_length, torch.Tensor):
+            min_length = min_length.to(x.device).clamp(min=0)
         masked[:, eos_token_id] = counters < min_length
     if no_repeat_ngram_size > 0 and sequences is not None:
         banned = _ngram_mask(sequences, counters, vocab, int(no_repeat_ngram_size))
@@ -307,7 +320,8 @@ def _eager_pick(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rn
         masked[:, ids] = True
     minus = None
     if (frequency_penalty != 0.0 or presence_penalty != 0.0) and sequences is not None:
-        counts = _history_counts(sequences, counters, vocab, int(penalty_begin))
+        counts = _history_counts(sequences, counters, vocab, penalty_begin.clamp(min=0) if isinstance(penalty_begin, torch.Tensor)
+                                 else int(penalty_begin))
         minus = (torch.tensor(frequency_penalty, dtype=torch.float32).double() * counts.double()
                  + torch.tensor(presence_penalty, dtype=torch.float32).double()).float().to(x.device)
         minus = torch.where(counts > 0, minus, torch.zeros_like(minus))
@@ -364,9 +378,12 @@ class _Picker:
     draw after temperature / top-k / top-p.  `counters` (batch,) int32 on the logits' device hold the 0-based sequence
     position of the token being picked: the Philox counter, and the column of `sequences` that receives the token.
     With an EOS id it owns `finished` (batch,) int32 on the logits' device, allocated by the first pick: the flag of a row
-    is set by the pick that returns the EOS id, and every later pick of that row returns the pad."""
+    is set by the pick that returns the EOS id, and every later pick of that row returns the pad.
+    `prompt_lengths` (batch,) int32 on that device, for prompts of different lengths: a row's counted penalties begin, and
+    its min_new_tokens count, at its own prompt length -- per-row values of the pick (bp_pick_token_lim_rows), passed only
+    where an option reads them."""
 
-    def __init__(self, options, rng_state, device):
+    def __init__(self, options, rng_state, device, prompt_lengths=None):
         self.options, self.finished = options, None
         if options.do_sample and rng_state is None:       # from torch's generator: torch.manual_seed reproduces a run
             rng_state = torch.randint(-2 ** 63, 2 ** 63 - 1, (2,), dtype=torch.int64, device=device)
@@ -378,12 +395,16 @@ class _Picker:
         if o.controlled:
             self.keywords.update(repetition_penalty=o.repetition_penalty, eos_token_id=o.eos_token_id, pad_token_id=o.pad,
                                  min_length=o.min_length)
+            if o.min_new_tokens:      # absolute, as min_length is: behind the prompt, the row's own where they differ
+                self.keywords['min_length'] = o.penalty_begin + o.min_new_tokens if prompt_lengths is None else \
+                    (prompt_lengths + o.min_new_tokens).to(torch.int32)
         if o.limited:
             suppress = o.suppress_tokens
             if suppress is not None:                  # a list or a tensor: on the device once, as the kernel reads it
                 suppress = torch.as_tensor(suppress).to(device=device, dtype=torch.int32).reshape(-1).contiguous()
             self.keywords.update(no_repeat_ngram_size=o.no_repeat_ngram_size, frequency_penalty=o.frequency_penalty,
-                                 presence_penalty=o.presence_penalty, penalty_begin=o.penalty_begin, suppress_tokens=suppress)
+                                 presence_penalty=o.presence_penalty, suppress_tokens=suppress,
+                                 penalty_begin=o.penalty_begin if prompt_lengths is None else prompt_lengths)
 
     def __call__(self, logits, counters, tokens=None, sequences=None):
         """tokens (batch,) int64; also stored into `tokens` (batch elements) and column counters[b] of `sequences`."""
@@ -460,14 +481,49 @@ def _trim_at_eos(sequences, seqlen_og, eos_token_id, pad_token_id):
     return sequences[:, :int(lengths.max())].contiguous(), lengths
 
 
+def _trim_rows_at_eos(sequences, prompt_lengths, new_tokens, eos_token_id, pad_token_id):
+    """_trim_at_eos for rows that begin at different positions: end_b = 1 + the first column >= prompt_lengths[b] of row b
+    that holds the EOS id, prompt_lengths[b] + new_tokens when there is none (or no EOS id); the pad behind every row's end.
+    Cut to max_b end_b columns only when an EOS id is given."""
+    batch, width = sequences.shape
+    cols = torch.arange(width, device=sequences.device)[None, :]
+    begin = prompt_lengths.long()[:, None]
+    lengths = begin[:, 0] + new_tokens
+    if eos_token_id is not None:
+        is_eos = (sequences == eos_token_id) & (cols >= begin) & (cols < lengths[:, None])
+        lengths = torch.where(is_eos, cols + 1, lengths[:, None]).min(dim=1).values
+    sequences = torch.where(cols < lengths[:, None], sequences, torch.full_like(sequences, pad_token_id))
+    if eos_token_id is not None:
+        sequences = sequences[:, :int(lengths.max())]
+    return sequences.contiguous(), lengths
+
+
+def _check_prompt_lengths(prompt_lengths, input_ids):
+    """prompt_lengths (a sequence or a tensor of `batch` integers in [1, seq_len]) as a (batch,) int32 tensor on the device of
+    input_ids, and its minimum: ONE copy to the host for the checks, one to the device; no step reads a host value."""
+    host = torch.as_tensor(prompt_lengths).detach().cpu()
+    batch, seqlen = input_ids.shape
+    if host.dim() != 1 or host.shape[0] != batch or host.is_floating_point() or host.dtype == torch.bool:
+        raise ValueError(f'generation: prompt_lengths must hold one integer per row of input_ids ({batch})')
+    values = host.tolist()
+    if not all(1 <= v <= seqlen for v in values):
+        raise ValueError(f'generation: prompt_lengths must lie in [1, seq_len = {seqlen}]: input_ids is right-padded')
+    return host.to(device=input_ids.device, dtype=torch.int32), min(values)
+
+
 class _CachedSteps:
     """What the loops with the pick on the device share: the InferenceParams with device lengths, the preallocated
     `sequences` (rows, width) holding the prompt, width = max(prompt, max_length - 1) as in _decode, the one-token input
     `static_ids` a pick writes for the next step, the prefill, and the loop over cached steps.  The cache capacity is `width`
-    rounded up to a multiple of `capacity_multiple` positions; `sequences` gets the same row stride."""
+    rounded up to a multiple of `capacity_multiple` positions; `sequences` gets the same row stride.
+    With `prompt_lengths` (rows,) int32 on the device, input_ids is right-padded: the columns behind a row's prompt are
+    overwritten with `pad` before anything reads them, the prefill runs over the padded width (causal: no real position sees
+    a pad) and returns the logits of every row's own last position, and the cached lengths start at the rows' own.  A step
+    appends at a row's length, so what the prefill cached for the pad columns is overwritten before it could be read."""
 
-    def __init__(self, input_ids, model, max_length, capacity_multiple=1):
+    def __init__(self, input_ids, model, max_length, capacity_multiple=1, prompt_lengths=None, pad=0):
         rows, self.prompt = input_ids.shape
+        self.prompt_lengths = prompt_lengths
         self.input_ids, self.model = input_ids, model
         self.width = max(self.prompt, max_length - 1)
         capacity = (self.width + capacity_multiple - 1) // capacity_multiple * capacity_multiple
@@ -476,13 +532,21 @@ class _CachedSteps:
         self.sequences = torch.zeros((rows, capacity), dtype=torch.int64, device=input_ids.device)[:, :self.width]
         self.sequences[:, :self.prompt] = input_ids
         self.static_ids = torch.zeros((rows, 1), dtype=torch.int64, device=input_ids.device)
+        if prompt_lengths is not None:
+            behind = torch.arange(self.width, device=input_ids.device)[None, :] >= prompt_lengths.long()[:, None]
+            self.sequences.masked_fill_(behind, pad)
+            self.input_ids = self.sequences[:, :self.prompt].to(input_ids.dtype).contiguous()
 
     def prefill(self):
-        """The logits of the prompt's last position; the caches then hold the prompt."""
-        logits = self.model(self.input_ids, inference_params=self.ip).logits[:, -1]
-        self.ip.sequence_len_offset = self.prompt
-        self.lengths.fill_(self.prompt)
-        return logits
+        """The logits of the prompt's last position (every row's own, under prompt_lengths); the caches then hold the prompt."""
+        logits = self.model(self.input_ids, inference_params=self.ip).logits
+        self.ip.sequence_len_offset = self.prompt                 # a host integer, read only as "after the prompt"
+        if self.prompt_lengths is None:
+            self.lengths.fill_(self.prompt)
+            return logits[:, -1]
+        self.lengths.copy_(self.prompt_lengths)
+        last = (self.prompt_lengths.long() - 1)[:, None, None].expand(-1, 1, logits.shape[-1])
+        return logits.gather(1, last)[:, 0].contiguous()
 
     def step_logits(self):
         """The head of every step: the model on `static_ids`, then lengths + 1 -- the counter of the step's pick."""
@@ -509,44 +573,59 @@ class _CachedSteps:
                 break
 
 
-def _decode_cached_picked(input_ids, model, max_length, picker, cg=False, stop_check_every=None):
+def _decode_cached_picked(input_ids, model, max_length, picker, cg=False, stop_check_every=None, prompt_lengths=None):
     """_decode_cached with the pick on the device: the counter of a pick is `lengths_per_sample` after the step's
     increment, the pick writes the next step's input (`static_ids`) and column `position` of the preallocated `sequences`.
     With cg=True the captured graph is model step, length increment, pick: a generated token is one replay, with no launch
     and no host read outside it.  Same index contract as _decode (the final pick lands outside `sequences` and is dropped).
     With an EOS id the loop ends once a poll (_StopPoll, every `stop_check_every` steps) shows every row finished; finished
     rows keep stepping on the pad token until then.  The result is cut at the rows' ends (_trim_at_eos), so it depends
-    neither on the polling interval nor on how far the loop overran."""
-    d = _CachedSteps(input_ids, model, max_length)
+    neither on the polling interval nor on how far the loop overran.
+    With `prompt_lengths` every row generates exactly width - prompt tokens behind its own prompt: that many picks and no
+    further one, which would land inside a shorter row; `lengths` is always returned (_trim_rows_at_eos)."""
+    d = _CachedSteps(input_ids, model, max_length, prompt_lengths=prompt_lengths, pad=picker.options.pad)
 
     def pick(logits):
         picker(logits, d.lengths, tokens=d.static_ids, sequences=d.sequences)
 
     with torch.inference_mode():
         logits = d.prefill()
+        sequences, lengths, o = d.sequences, None, picker.options
+        if prompt_lengths is not None:
+            new_tokens = d.width - d.prompt
+            if new_tokens > 0:
+                pick(logits)
+                d.run(lambda: pick(d.step_logits()), new_tokens - 1, cg, _StopPoll(picker.finished, stop_check_every))
+            sequences, lengths = _trim_rows_at_eos(sequences, prompt_lengths, new_tokens, o.eos_token_id, o.pad)
+            return DecoderOnlyOutput(sequences=sequences.to(input_ids.dtype), scores=(logits,), lengths=lengths)
         pick(logits)
         d.run(lambda: pick(d.step_logits()), max_length - d.prompt - 1, cg, _StopPoll(picker.finished, stop_check_every))
-        sequences, lengths, o = d.sequences, None, picker.options
         if o.eos_token_id is not None:
             sequences, lengths = _trim_at_eos(sequences, d.prompt, o.eos_token_id, o.pad)
     return DecoderOnlyOutput(sequences=sequences.to(input_ids.dtype), scores=(logits,), lengths=lengths)
 
 
 def _run_loop(input_ids, model, max_length, pick, do_sample, cg, kv_cache, rng_state, device_pick, stop_check_every,
-              pick_options):
-    """The loop greedy_decode / sample select: with the device pick (_Picker) when device_pick, an rng_state or one of
-    `pick_options` asks for it, else with the host's `pick` exactly as the reference runs."""
+              pick_options, prompt_lengths=None):
+    """The loop greedy_decode / sample select: with the device pick (_Picker) when device_pick, an rng_state, prompt_lengths
+    or one of `pick_options` asks for it, else with the host's `pick` exactly as the reference runs."""
     if stop_check_every is not None and stop_check_every < 1:
         raise ValueError('generation: stop_check_every must be >= 1')
     # the frequency / presence penalties count from the prompt length on: generated tokens only
     options = PickOptions(do_sample=do_sample, penalty_begin=input_ids.shape[1], **pick_options)
-    if device_pick or rng_state is not None or options.wants_device_pick:
-        picker = _Picker(options, rng_state, input_ids.device)
+    if prompt_lengths is not None:
+        if not kv_cache:
+            raise ValueError('generation: prompt_lengths needs kv_cache=True (the loops without a cache are the reference\'s, '
+                             'statement for statement)')
+        prompt_lengths, _ = _check_prompt_lengths(prompt_lengths, input_ids)
+    if device_pick or rng_state is not None or options.wants_device_pick or prompt_lengths is not None:
+        picker = _Picker(options, rng_state, input_ids.device, prompt_lengths)
         if kv_cache:
-            return _decode_cached_picked(input_ids, model, max_length, picker, cg=cg, stop_check_every=stop_check_every)
+            return _decode_cached_picked(input_ids, model, max_length, picker, cg=cg, stop_check_every=stop_check_every,
+                                         prompt_lengths=prompt_lengths)
         if options.controlled:
-            raise ValueError('generation: repetition_penalty, eos_token_id, pad_token_id, min_length, no_repeat_ngram_size, '
-                             'frequency_penalty, presence_penalty and suppress_tokens need kv_cache=True '
+            raise ValueError('generation: repetition_penalty, eos_token_id, pad_token_id, min_length, min_new_tokens, '
+                             'no_repeat_ngram_size, frequency_penalty, presence_penalty and suppress_tokens need kv_cache=True '
                              '(the loops without a cache are the reference\'s, statement for statement)')
         pick = picker.loop_pick(input_ids)
     if kv_cache:
@@ -557,30 +636,38 @@ def _run_loop(input_ids, model, max_length, pick, do_sample, cg, kv_cache, rng_s
 
 
 def greedy_decode(input_ids, model, max_length, cg=False, kv_cache=False, rng_state=None, device_pick=False,
-                  stop_check_every=None, **pick_options):
+                  stop_check_every=None, prompt_lengths=None, **pick_options):
     """input_ids (batch, seq_len) -> sequences (batch, max_length - 1): argmax continuation.
     cg=True: one captured full-width forward replayed per token (CUDA tensors only), see _decode_graphed.
     kv_cache=True: prefill once, then one cached step per token (with cg=True: one captured step), see _decode_cached.
     device_pick=True: the argmax runs in bp_pick_token (on CPU tensors: _eager_pick), with kv_cache and cg inside the
     captured step (_decode_cached_picked); the sampling options are accepted for symmetry and do not change an argmax.
+    prompt_lengths (kv_cache=True only; selects the device pick): a sequence or tensor of `batch` integers 1 <= L_b <= seq_len.
+    input_ids is then right-padded: row b's prompt is input_ids[b, :L_b], and what lies behind it is ignored.  With N =
+    max(seq_len, max_length - 1) - seq_len, every row generates exactly N tokens: `sequences` (batch, seq_len + N) holds row
+    b's prompt in [0, L_b), its tokens in [L_b, L_b + N) and the pad (PickOptions.pad) behind them; `lengths` (batch,) int64,
+    always returned, is 1 + the column of the row's first EOS behind its prompt, else L_b + N; `scores` holds the logits of
+    position L_b - 1 of every row; with an EOS id `sequences` is cut to the longest row.  With every L_b == seq_len the
+    sequences are those of the call without the argument.
     pick_options: the keywords of PickOptions, see there."""
     return _run_loop(input_ids, model, max_length, lambda logits: torch.argmax(logits, dim=-1), False, cg, kv_cache, rng_state,
-                     device_pick, stop_check_every, pick_options)
+                     device_pick, stop_check_every, pick_options, prompt_lengths)
 
 
 def sample(input_ids, model, max_length, cg=False, kv_cache=False, rng_state=None, device_pick=False, stop_check_every=None,
-           **pick_options):
+           prompt_lengths=None, **pick_options):
     """Ancestral sampling from softmax(logits) (reference :23-48); cg / kv_cache as in greedy_decode.
     temperature, top_k (ties at the threshold kept, as the reference's top_k_filter, training/run_pplm.py:569-581), top_p:
     the usual filters; any of them, an `rng_state` or device_pick=True selects the device pick (bp_pick_token, contract in
     include/bp_hip.h; _eager_pick on CPU tensors).  rng_state: int64 {seed, offset} (bp_hip.new_rng_state), drawn from
     torch's generator when None; the token at sequence position t of row b is a pure function of (logits, rng_state, b, t),
     so cached, graphed and growing-prefix runs under one rng_state draw the same numbers.
+    prompt_lengths: right-padded prompts of different lengths, as in greedy_decode; the position t of a draw is the row's own.
     pick_options: the keywords of PickOptions, see there."""
     def pick(logits):
         return torch.distributions.Categorical(logits=torch.log_softmax(logits.float(), dim=-1)).sample()
     return _run_loop(input_ids, model, max_length, pick, True, cg, kv_cache, rng_state, device_pick, stop_check_every,
-                     pick_options)
+                     pick_options, prompt_lengths)
 
 
 # ---- beam search on the KV cache: bp_beam_pick / bp_beam_copy_rows, or their torch restatements on CPU tensors -----------------
@@ -703,12 +790,15 @@ def _beam_row_sets(ip, sequences):
 
 
 def beam_search(input_ids, model, max_length, num_beams, eos_token_id=None, pad_token_id=None, length_penalty=0.0, cg=False,
-                stop_check_every=None, **sampling_options):
-    """Beam search on the KV cache: input_ids (batch, seq_len), prompts of equal length -> BeamSearchOutput.  The rows are
+                stop_check_every=None, prompt_lengths=None, **sampling_options):
+    """Beam search on the KV cache: input_ids (batch, seq_len), prompts of equal length, or right-padded ones with
+    `prompt_lengths` (as greedy_decode's: every hypothesis holds width - seq_len tokens behind its group's own prompt, the
+    pad behind them, and the lengths, prompt included, are the rows' own) -> BeamSearchOutput.  The rows are
     the prompts repeated num_beams (W, 1..8) times, prefilled once at batch B W (prefilling B rows and fanning out is a
     later optimisation).  A step is: model step on the picked tokens, lengths + 1, bp_beam_pick (the W best of
     the group's W x vocab continuations, on the device), bp_beam_copy_rows (the caches and the sequence buffer follow the
-    hypotheses that changed slot; the prompt region is the same within a group and is never copied).  With cg=True the
+    hypotheses that changed slot; the prompt region is the same within a group and is never copied -- with prompt_lengths
+    the copy starts at the shortest prompt: the columns up to a group's own prompt are equal within the group).  With cg=True the
     whole step is captured once, after one eager step.  Exactly width - seq_len picks are made, width = max(seq_len,
     max_length - 1) as in the other loops, so the scores describe the returned tokens.
     With an EOS id a hypothesis that picks it is frozen: it stays in the beam at its score and competes on it (the common
@@ -735,9 +825,14 @@ def beam_search(input_ids, model, max_length, num_beams, eos_token_id=None, pad_
         pad_token_id = eos_token_id if eos_token_id is not None else 0
     batch, seqlen_og = input_ids.shape
     rows, dev = batch * W, input_ids.device
+    first_copied = seqlen_og
+    if prompt_lengths is not None:
+        prompt_lengths, first_copied = _check_prompt_lengths(prompt_lengths, input_ids)
+        prompt_lengths = prompt_lengths.repeat_interleave(W)       # all W rows of a group share its length
     # bp_beam_copy_rows wants rows that start on 16-byte boundaries: the cache capacity is rounded up to four positions (the
     # int32 row index of the Backpack's cache is the narrowest row), the sequence buffer gets the same row stride
-    d = _CachedSteps(input_ids.repeat_interleave(W, dim=0), model, max_length, capacity_multiple=4)
+    d = _CachedSteps(input_ids.repeat_interleave(W, dim=0), model, max_length, capacity_multiple=4,
+                     prompt_lengths=prompt_lengths, pad=pad_token_id)
     width, sequences, static_ids = d.width, d.sequences, d.static_ids
     beam_scores = torch.full((rows,), float('-inf'), dtype=torch.float32, device=dev)
     beam_scores[::W] = 0.0                          # the first pick takes all W winners from beam 0
@@ -755,7 +850,7 @@ def beam_search(input_ids, model, max_length, num_beams, eos_token_id=None, pad_
                 bp_hip.beam_pick(step_logits, beam_scores, parent, W, finished=finished, tokens=static_ids,
                                  sequences=sequences, counters=d.lengths, eos_token_id=eos_token_id,
                                  pad_token_id=pad_token_id)
-                bp_hip.beam_copy_rows(sets, parent, d.lengths, seqlen_og)
+                bp_hip.beam_copy_rows(sets, parent, d.lengths, first_copied)
                 return
             new_parent, tokens, scores, flags = _eager_beam_pick(step_logits, beam_scores, finished, W, eos_token_id,
                                                                  pad_token_id)
@@ -768,14 +863,16 @@ def beam_search(input_ids, model, max_length, num_beams, eos_token_id=None, pad_
             ok = cols < width
             at = torch.arange(rows, device=dev)
             sequences[at[ok], cols[ok]] = tokens[ok]
-            _eager_beam_copy_rows(sets, parent, d.lengths, seqlen_og)
+            _eager_beam_copy_rows(sets, parent, d.lengths, first_copied)
 
         poll = _StopPoll(finished, stop_check_every)
         if width > seqlen_og:                        # width - seqlen_og picks, the first on the prefill's logits: nothing to copy yet
             pick(logits)
             if not poll.all_finished():
                 d.run(lambda: pick(d.step_logits()), width - seqlen_og - 1, cg, poll)
-        if eos_token_id is not None:
+        if prompt_lengths is not None:
+            sequences, lengths = _trim_rows_at_eos(sequences, prompt_lengths, width - seqlen_og, eos_token_id, pad_token_id)
+        elif eos_token_id is not None:
             sequences, lengths = _trim_at_eos(sequences, seqlen_og, eos_token_id, pad_token_id)
         else:
             lengths = torch.full((rows,), width, dtype=torch.int64, device=dev)
@@ -792,6 +889,11 @@ def beam_search(input_ids, model, max_length, num_beams, eos_token_id=None, pad_
 
 class GenerationMixin:
 
+    def _ragged(self, prompt_lengths):
+        """The keyword of a call with prompt_lengths, none without: such a call runs the statements it always ran.  A model
+        whose per-token state looks across positions overrides this to refuse."""
+        return {} if prompt_lengths is None else {'prompt_lengths': prompt_lengths}
+
     def _generate(self, decode, input_ids, max_length, return_dict_in_generate, output_scores, cg, kv_cache, **pick_options):
         output = decode(input_ids, self, max_length, cg=cg, kv_cache=kv_cache, **pick_options)
         if not output_scores:
@@ -799,20 +901,25 @@ class GenerationMixin:
         return output if return_dict_in_generate else output.sequences
 
     def generate(self, input_ids, max_length, return_dict_in_generate=False, output_scores=False, cg=False, kv_cache=False,
-                 rng_state=None, device_pick=False, stop_check_every=None, **pick_options):
-        """greedy_decode on this model; pick_options: the keywords of PickOptions."""
+                 rng_state=None, device_pick=False, stop_check_every=None, prompt_lengths=None, **pick_options):
+        """greedy_decode on this model; prompt_lengths: right-padded prompts of different lengths, see there; pick_options:
+        the keywords of PickOptions."""
         return self._generate(greedy_decode, input_ids, max_length, return_dict_in_generate, output_scores, cg, kv_cache,
-                              rng_state=rng_state, device_pick=device_pick, stop_check_every=stop_check_every, **pick_options)
+                              rng_state=rng_state, device_pick=device_pick, stop_check_every=stop_check_every,
+                              **self._ragged(prompt_lengths), **pick_options)
 
     def sample(self, input_ids, max_length, return_dict_in_generate=False, output_scores=False, cg=False, kv_cache=False,
-               rng_state=None, device_pick=False, stop_check_every=None, **pick_options):
-        """sample on this model; pick_options: the keywords of PickOptions."""
+               rng_state=None, device_pick=False, stop_check_every=None, prompt_lengths=None, **pick_options):
+        """sample on this model; prompt_lengths and pick_options as generate's."""
         return self._generate(sample, input_ids, max_length, return_dict_in_generate, output_scores, cg, kv_cache,
-                              rng_state=rng_state, device_pick=device_pick, stop_check_every=stop_check_every, **pick_options)
+                              rng_state=rng_state, device_pick=device_pick, stop_check_every=stop_check_every,
+                              **self._ragged(prompt_lengths), **pick_options)
 
     def beam_search(self, input_ids, max_length, num_beams, return_dict_in_generate=False, eos_token_id=None,
-                    pad_token_id=None, length_penalty=0.0, cg=False, stop_check_every=None, **sampling_options):
+                    pad_token_id=None, length_penalty=0.0, cg=False, stop_check_every=None, prompt_lengths=None,
+                    **sampling_options):
         """The best hypothesis of every prompt (batch, cols), or the BeamSearchOutput with return_dict_in_generate."""
         output = beam_search(input_ids, self, max_length, num_beams, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
-                             length_penalty=length_penalty, cg=cg, stop_check_every=stop_check_every, **sampling_options)
+                             length_penalty=length_penalty, cg=cg, stop_check_every=stop_check_every,
+                             **self._ragged(prompt_lengths), **sampling_options)
         return output if return_dict_in_generate else output.sequences

@@ -745,6 +745,30 @@ int bp_pick_token_lim(const void *logits, int64_t *tokens, int64_t *sequences, f
                       const int32_t *suppress_ids, int n_suppress, int dtype, bp_stream_t stream);
 
 /*
+ * bp_pick_token_lim_rows -- bp_pick_token_lim for a batch whose rows begin at different positions (right-padded prompts of
+ * different lengths): the two values that bp_pick_token_lim takes as one scalar for the whole batch may come per row.
+ * (Additive, ABI still 11.)  Arguments as bp_pick_token_lim's, and
+ *   penalty_begins  optional int32 (batch) on the device: row b counts its history from penalty_begins[b] on; replaces
+ *                   penalty_begin, which is then neither read nor checked
+ *   min_lengths     optional int32 (batch) on the device: the EOS id of row b is masked while c < min_lengths[b]; replaces
+ *                   min_length, which is then neither read nor checked
+ * The host never reads the arrays (one captured launch serves every step): a negative entry counts as 0, on the device.
+ * Everything else is bp_pick_token_lim's contract with the row's value in the scalar's place: the clamp min(begin, Lh), the
+ * order pen -> counts -> ban, stats, degenerate rows, finished rows, the bounds.  With both arrays NULL, or with arrays that
+ * hold the scalar in every row, tokens and stats are bp_pick_token_lim's, bit for bit.
+ * Errors, before any launch: everything bp_pick_token_lim rejects, with its codes, where penalty_begin < 0 and
+ * min_length < 0 are rejected only when the respective array is NULL; BP_ERR_SHAPE (a misaligned array).
+ */
+int bp_pick_token_lim_rows(const void *logits, int64_t *tokens, int64_t *sequences, float *stats, const uint64_t *rng_state,
+                           const int32_t *counters, int32_t *finished,
+                           int batch, int vocab, int64_t row_stride, int64_t tokens_stride, int64_t seq_stride, int seq_cols,
+                           int do_sample, float temperature, int top_k, float top_p,
+                           float repetition_penalty, int eos_token_id, int pad_token_id, int min_length,
+                           int no_repeat_ngram_size, float frequency_penalty, float presence_penalty, int penalty_begin,
+                           const int32_t *suppress_ids, int n_suppress, const int32_t *penalty_begins,
+                           const int32_t *min_lengths, int dtype, bp_stream_t stream);
+
+/*
  * bp_beam_pick -- one decode step of beam search on the device for `groups` prompts x `beam_width` (W, 1..8) hypotheses,
  * rows r = g * W + w.  No host value enters, so one captured launch serves every step.  (Additive, ABI still 11.)
  *   logits       (groups * W, vocab) fp16 / bf16 / fp32, element stride row_stride >= vocab, last stride 1, any

@@ -7,6 +7,7 @@ generate(..., kv_cache=True) eagerly and with cg=True (one captured decode step 
                                      [--pick torch|device|torch,device] [--sample] [--temperature T] [--top-k K] [--top-p P]
                                      [--repetition-penalty R] [--eos ID] [--min-length L] [--stop-check-every N]
                                      [--variant NAME:option=value,...] [--repeats N] [--beams W[,W...]]
+                                     [--prompt-lengths LO:HI[:SEED]]
 
 --pick chooses how the next token is picked: `torch` is torch.argmax / torch.distributions.Categorical on the host side
 of the loop, `device` the bp_pick_token kernel (device_pick=True; with kv_cache and cg inside the captured step).  With
@@ -19,6 +20,11 @@ that alternates with the others: the device pick with some generation options re
 `--variant pen:repetition_penalty=1.2 --variant n4:eos_token_id=50263,stop_check_every=4`, or with the limits of
 bp_pick_token_lim `--variant all:no_repeat_ngram_size=3,frequency_penalty=0.5,presence_penalty=0.5,suppress_tokens=11+12+13`
 (a list is written a+b+c).
+
+--prompt-lengths LO:HI[:SEED] (kv legs only) adds two further picks that alternate with the others: `ragged`, the device pick
+with prompt_lengths drawn once on the host, uniformly from LO..HI (seed SEED, default 0) with the maximum forced to --prompt,
+so that the padded width and the number of new tokens are those of the other picks; and `ragged_equal`, the same call with
+every length equal to --prompt, i.e. the work of the pick without the argument through the new path.
 
 --beams W[,W...] times beam search instead (its own line per sense_table mode): for every width W, beam_search(num_beams=W,
 cg=True) against the greedy device-pick leg generate(kv_cache=True, cg=True, device_pick=True) at the same number of rows
@@ -63,6 +69,7 @@ def main():
     ap.add_argument('--variant', action='append', default=[], help='NAME:option=value,... : the device pick with these options')
     ap.add_argument('--repeats', type=int, default=1)
     ap.add_argument('--beams', default=None, help='W[,W...]: time beam search against greedy at the same number of rows')
+    ap.add_argument('--prompt-lengths', default=None, help='LO:HI[:SEED]: add the picks ragged and ragged_equal (kv legs only)')
     a = ap.parse_args()
     from bench import MODELS
     from src.models.backpack import BackpackConfig, BackpackLMHeadModel
@@ -90,7 +97,7 @@ def main():
                    new_tokens=a.max_length - 1 - a.prompt, sense_table=mode, **extra)
         outs = {}
         picks = a.pick.split(',')
-        plain = picks == ['torch'] and not a.sample and a.repeats == 1 and not a.variant   # the line of earlier revisions, key for key
+        plain = picks == ['torch'] and not a.sample and a.repeats == 1 and not a.variant and not a.prompt_lengths   # the line of earlier revisions, key for key
         if not plain:
             res.update(sample=a.sample, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p)
         options = dict(torch={}, device=dict(device_pick=True, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p))
@@ -108,6 +115,17 @@ def main():
             options[name] = dict(options['device'], **changed)
             res['variant_' + name] = changed
             picks = picks + [name]
+        if a.prompt_lengths:
+            lo, hi, *seed = (int(v) for v in a.prompt_lengths.split(':'))
+            if not 1 <= lo <= hi <= a.prompt or 'full' in a.legs.split(','):
+                raise SystemExit('--prompt-lengths LO:HI needs 1 <= LO <= HI <= --prompt and --legs kv')
+            drawn = torch.randint(lo, hi + 1, (a.batch,), generator=torch.Generator().manual_seed(seed[0] if seed else 0))
+            drawn[int(drawn.argmax())] = a.prompt          # the longest row fills the padded width
+            options['ragged_equal'] = dict(options['device'], prompt_lengths=[a.prompt] * a.batch)
+            options['ragged'] = dict(options['device'], prompt_lengths=drawn.tolist())
+            res['prompt_lengths'] = dict(lo=lo, hi=hi, seed=seed[0] if seed else 0, min=int(drawn.min()),
+                                         mean=round(drawn.float().mean().item(), 2))
+            picks = picks + ['ragged_equal', 'ragged']
         decode = model.sample if a.sample else model.generate
         for key, cg, kv in legs:
             runs = {pick: [] for pick in picks}
