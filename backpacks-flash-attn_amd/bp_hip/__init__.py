@@ -98,6 +98,8 @@ SIGNATURES = {
     'bp_beam_pick': (_i32, [_ptr] * 8 + [_i64] + [_i32] * 3 + [_i64] * 3 + [_i32] * 4 + [_ptr]),
     'bp_beam_copy_rows': (_i32, [_ptr] * 3 + [_i32] + [_ptr] * 2 + [_i32] * 3 + [_ptr]),
     'bp_row_extremes': (_i32, [_ptr] * 5 + [_i32] * 2 + [_i64] + [_i32] * 2 + [_ptr]),
+    'bp_sense_attribute_ws_floats': (_i64, [_i32] * 2),
+    'bp_sense_attribute': (_i32, [_ptr] * 9 + [_i64] + [_i32] * 7 + [_i64] + [_i64] * 14 + [_f32, _i32, _ptr]),
 }
 
 
@@ -1351,3 +1353,71 @@ def row_extremes(logits, n, largest=True, smallest=True, out=None):
     _call('bp_row_extremes', logits.device, logits.data_ptr(), *[o.data_ptr() if o is not None else None for o in out],
           rows, cols, logits.stride(0) if rows > 1 else max(cols, logits.stride(0)), n, _PICK_DTYPES[logits.dtype])
     return tuple(out)
+
+
+# ---- sense attribution on the device (C ABI bp_sense_attribute) -------------------------------------------------------------------------------------------------------
+
+ATTRIBUTE_MAX_VECS = 4
+
+
+def sense_attribute_supported(qk, table, row_index, vec):
+    """Whether bp_sense_attribute takes these operands: qk (B, S, 2, k, d_k) and table (rows, k, d_out) 16-bit CUDA tensors of
+    one dtype in 16-byte friendly layouts, k <= 64, d_k % 8 == 0 and <= 640, d_out % 8 == 0 and <= 2048, row_index (B, S)
+    integers, vec (nq, nvec, d_out) with 1 <= nvec <= 4 and nq <= 65535."""
+    if not (qk.is_cuda and table.is_cuda and row_index.is_cuda and vec.is_cuda):
+        return False
+    if qk.dtype not in (torch.float16, torch.bfloat16) or table.dtype != qk.dtype:
+        return False
+    if qk.dim() != 5 or qk.shape[2] != 2 or table.dim() != 3 or vec.dim() != 3 or row_index.dim() != 2:
+        return False
+    b, s, _, k, dk = qk.shape
+    dout = table.shape[2]
+    return (b >= 1 and s >= 1 and table.shape[0] >= 1 and table.shape[1] == k and tuple(row_index.shape) == (b, s)
+            and 1 <= k <= SENSE_DECODE_MAX_SENSES and dk % 8 == 0 and 8 <= dk <= SENSE_MAX_DK
+            and dout % 8 == 0 and 8 <= dout <= SENSE_DECODE_MAX_DOUT and vec.shape[2] == dout
+            and 1 <= vec.shape[1] <= ATTRIBUTE_MAX_VECS and 1 <= vec.shape[0] <= 65535
+            and _vec16(qk, table) and qk.stride(2) % 8 == 0)
+
+
+def sense_attribute(qk, table, row_index, query_sample, query_pos, vec, scale, want_probs=False, out=None, probs=None):
+    """The share of every (position, sense) pair in the dot product of a position's output with `vec` (C ABI
+    bp_sense_attribute, contract in include/bp_hip.h): for query n = position query_pos[n] of sample query_sample[n],
+      out[n, v, l, j] = p_j * table[row_index[b_n, j], l, :] . vec[n, v, :],  p = softmax_{j <= i_n}(scale q_l(i_n) . k_l(j)),
+    exact zeros behind i_n; the probabilities stay fp32.  qk (B, S, 2, k, d_k) and table (rows, k, d_out) 16-bit;
+    row_index (B, S) int32; query_sample / query_pos (nq,) int32 on the device (clamped there, never read by the host);
+    vec (nq, nvec, d_out) fp32.  Returns (out (nq, nvec, k, S) fp32, probs (nq, k, S) fp32 or None).  `out` / `probs`:
+    fp32 tensors of those shapes with unit stride along S to write into (any other strides) instead of allocating."""
+    _require_cuda(qk, table, row_index, query_sample, query_pos, vec, out, probs)
+    b, s, k, dk = _check_qk(qk)
+    if table.dim() != 3 or table.shape[1] != k or table.dtype != qk.dtype or table.stride(-1) != 1:
+        raise RuntimeError('bp_hip.sense_attribute: table must be (rows, k, d_out) of the dtype of qk, contiguous last dim')
+    dout = table.shape[2]
+    if tuple(row_index.shape) != (b, s) or row_index.dtype != torch.int32 or row_index.stride(-1) != 1:
+        raise RuntimeError('bp_hip.sense_attribute: row_index must be (B, S) int32, unit stride along the sequence')
+    if vec.dim() != 3 or vec.shape[2] != dout or vec.dtype != torch.float32:
+        raise RuntimeError('bp_hip.sense_attribute: vec must be (nq, nvec, d_out) float32')
+    nq, nvec = vec.shape[:2]
+    for name, t in (('query_sample', query_sample), ('query_pos', query_pos)):
+        if tuple(t.shape) != (nq,) or t.dtype != torch.int32 or not t.is_contiguous():
+            raise RuntimeError(f'bp_hip.sense_attribute: {name} must be a contiguous ({nq},) int32 tensor')
+    if vec.stride(2) != 1 or vec.stride(0) % 4 or vec.stride(1) % 4 or vec.data_ptr() % 16:
+        vec = vec.contiguous()
+    if out is None:
+        out = torch.empty((nq, nvec, k, s), dtype=torch.float32, device=qk.device)
+    elif tuple(out.shape) != (nq, nvec, k, s) or out.dtype != torch.float32 or out.stride(-1) != 1:
+        raise RuntimeError(f'bp_hip.sense_attribute: out must be float32 ({nq}, {nvec}, {k}, {s}) with unit stride along S')
+    if probs is None and want_probs:
+        probs = torch.empty((nq, k, s), dtype=torch.float32, device=qk.device)
+    elif probs is not None and (tuple(probs.shape) != (nq, k, s) or probs.dtype != torch.float32 or probs.stride(-1) != 1):
+        raise RuntimeError(f'bp_hip.sense_attribute: probs must be float32 ({nq}, {k}, {s}) with unit stride along S')
+    ws_floats = lib().bp_sense_attribute_ws_floats(nq, k)
+    ws = torch.empty((max(ws_floats, 1),), dtype=torch.float32, device=qk.device)
+    _call('bp_sense_attribute', qk.device,
+          qk.data_ptr(), table.data_ptr(), row_index.data_ptr(), query_sample.data_ptr(), query_pos.data_ptr(),
+          vec.data_ptr(), out.data_ptr(), probs.data_ptr() if probs is not None else None, ws.data_ptr(), ws.numel(),
+          b, s, k, dk, dout, nq, nvec, table.shape[0],
+          qk.stride(0), qk.stride(1), qk.stride(2), qk.stride(3), table.stride(0), table.stride(1), row_index.stride(0),
+          vec.stride(0), vec.stride(1), out.stride(0), out.stride(1), out.stride(2),
+          probs.stride(0) if probs is not None else 0, probs.stride(1) if probs is not None else 0,
+          float(scale), _dtype_code(qk))
+    return out, probs

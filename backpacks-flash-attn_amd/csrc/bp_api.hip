@@ -1112,4 +1112,59 @@ int bp_row_extremes(const void *logits, float *top_val, int32_t *top_idx, float 
     return launch_status(bp::launch_row_extremes(p, dtype, static_cast<hipStream_t>(stream)));
 }
 
+// ---- sense attribution (bp_sense_attribute) ----
+
+int64_t bp_sense_attribute_ws_floats(int nq, int nsenses) {
+    if (nq <= 0 || nsenses <= 0) return 0;
+    return (int64_t)nq * nsenses * 2;
+}
+
+int bp_sense_attribute(const void *qk, const void *table, const int32_t *row_index, const int32_t *query_sample,
+                       const int32_t *query_pos, const float *vec, float *out, float *probs, float *ws, int64_t ws_floats,
+                       int batch, int seqlen, int nsenses, int d_k, int d_out, int nq, int nvec, int64_t table_rows,
+                       int64_t qk_batch_stride, int64_t qk_row_stride, int64_t qk_two_stride, int64_t qk_sense_stride,
+                       int64_t t_row_stride, int64_t t_sense_stride, int64_t idx_batch_stride,
+                       int64_t v_query_stride, int64_t v_vec_stride,
+                       int64_t o_query_stride, int64_t o_vec_stride, int64_t o_sense_stride,
+                       int64_t p_query_stride, int64_t p_sense_stride,
+                       float softmax_scale, int dtype, bp_stream_t stream) {
+    if (dtype != BP_DTYPE_F16 && dtype != BP_DTYPE_BF16) return BP_ERR_DTYPE;
+    if (d_k < 1 || d_k > bp::kWideMaxDk || d_k % 8 != 0) return BP_ERR_HEAD_DIM;
+    if (d_out < 1 || d_out % 8 != 0 || d_out > 2048) return BP_ERR_DOUT;
+    if (nq < 1 || nq > 65535 || nvec < 1 || nvec > bp::kAttributeMaxVecs || nsenses < 1 || nsenses > 64 || batch < 1
+        || seqlen < 1 || table_rows < 1 || table_rows > 0x7fffffffLL)
+        return BP_ERR_SHAPE;
+    if (qk == nullptr || table == nullptr || row_index == nullptr || query_sample == nullptr || query_pos == nullptr
+        || vec == nullptr || out == nullptr || ws == nullptr)
+        return BP_ERR_SHAPE;
+    const uint16_t *qp = static_cast<const uint16_t *>(qk);
+    if (!aligned16({qp, qp + qk_two_stride, table, vec})) return BP_ERR_SHAPE;
+    if (!strides8({qk_batch_stride, qk_row_stride, qk_two_stride, qk_sense_stride, t_row_stride, t_sense_stride}))
+        return BP_ERR_SHAPE;
+    if ((v_query_stride & 3) != 0 || (v_vec_stride & 3) != 0) return BP_ERR_SHAPE;
+    for (const void *p4 : {(const void *)row_index, (const void *)query_sample, (const void *)query_pos, (const void *)out,
+                           (const void *)probs, (const void *)ws})
+        if (reinterpret_cast<uintptr_t>(p4) % 4) return BP_ERR_SHAPE;
+    // rows of different (query, vector, sense) triples do not overlap
+    if (o_sense_stride < seqlen || (nvec > 1 && o_vec_stride < nsenses * o_sense_stride)
+        || (nq > 1 && o_query_stride < nvec * o_vec_stride))
+        return BP_ERR_SHAPE;
+    if (probs != nullptr && (p_sense_stride < seqlen || (nq > 1 && p_query_stride < nsenses * p_sense_stride)))
+        return BP_ERR_SHAPE;
+    if (!scale_ok(softmax_scale)) return BP_ERR_SCALE;
+    if (ws_floats < bp_sense_attribute_ws_floats(nq, nsenses)) return BP_ERR_WORKSPACE;
+    bp::AttributeParams p{};
+    p.q = qp; p.k = qp + qk_two_stride; p.table = table;
+    p.row_index = row_index; p.query_sample = query_sample; p.query_pos = query_pos;
+    p.vec = vec; p.out = out; p.probs = probs; p.ws = ws;
+    p.qk_bs = qk_batch_stride; p.qk_rs = qk_row_stride; p.qk_ss = qk_sense_stride;
+    p.t_rs = t_row_stride; p.t_gs = t_sense_stride; p.ri_bs = idx_batch_stride;
+    p.v_qs = v_query_stride; p.v_vs = v_vec_stride;
+    p.o_qs = o_query_stride; p.o_vs = o_vec_stride; p.o_gs = o_sense_stride;
+    p.p_qs = p_query_stride; p.p_gs = p_sense_stride; p.table_rows = table_rows;
+    p.b = batch; p.s = seqlen; p.groups = nsenses; p.dk = d_k; p.dout = d_out; p.nq = nq; p.nvec = nvec;
+    p.scale = softmax_scale;
+    return launch_status(bp::launch_sense_attribute(p, dtype, static_cast<hipStream_t>(stream)));
+}
+
 }  // extern "C"

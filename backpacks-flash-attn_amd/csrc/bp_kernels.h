@@ -392,4 +392,18 @@ struct RowExtremesParams {
 };
 hipError_t launch_row_extremes(const RowExtremesParams &p, int dtype, hipStream_t stream);
 
+// bp_sense_attribute (sense_attribute.hip): out[n, v, l, j] = p_j * table[row(b_n, j), l, :] . vec[n, v, :], p the causal
+// softmax row of query n = (query_sample[n], query_pos[n]) over keys 0 .. i_n; zeros behind i_n
+constexpr int kAttributeMaxVecs = BP_ATTRIBUTE_MAX_VECS;
+struct AttributeParams {
+    const void *q, *k, *table;   // q / k: the two halves of qk (B, S, 2, k, d_k); table (table_rows, k, d_out); 16-bit
+    const int32_t *row_index, *query_sample, *query_pos;
+    const float *vec;            // (nq, nvec, d_out)
+    float *out, *probs, *ws;     // probs optional; ws: (nq, k, 2) = (m, Z)
+    int64_t qk_bs, qk_rs, qk_ss, t_rs, t_gs, ri_bs, v_qs, v_vs, o_qs, o_vs, o_gs, p_qs, p_gs, table_rows;
+    int b, s, groups, dk, dout, nq, nvec;
+    float scale;
+};
+hipError_t launch_sense_attribute(const AttributeParams &p, int dtype, hipStream_t stream);
+
 }  // namespace bp

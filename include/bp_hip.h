@@ -51,7 +51,8 @@ extern "C" {
                               and one more: bp_pick_token_lim, the controlled pick with n-gram blocking, frequency /
                               presence penalties and a list of suppressed ids;
                               and one more: bp_row_extremes, the n largest / n smallest elements of every row of a
-                              matrix, for the vocabulary projections of sense vectors) */
+                              matrix, for the vocabulary projections of sense vectors;
+                              and one more: bp_sense_attribute, the shares of every (position, sense) pair in a logit) */
 
 /* element type of q/k/v/out/content tensors */
 #define BP_DTYPE_F16 0
@@ -80,6 +81,8 @@ extern "C" {
 #define BP_PICK_MAX_LDS_BYTES (160 * 1024)    /* static + dynamic LDS of one launch: the LDS of a CU */
 
 #define BP_ROW_EXTREMES_MAX_N 64              /* bp_row_extremes: elements kept per end of a row */
+
+#define BP_ATTRIBUTE_MAX_VECS 4                /* bp_sense_attribute: fp32 vectors per query */
 
 #define BP_QUEUE_WS_BYTES 64   /* `queue_ws` of the persistent sense-mix launches */
 
@@ -848,6 +851,51 @@ int bp_beam_copy_rows(const void *const *bases, const int64_t *row_strides, cons
  */
 int bp_row_extremes(const void *logits, float *top_val, int32_t *top_idx, float *bot_val, int32_t *bot_idx,
                     int rows, int cols, int64_t row_stride, int n, int dtype, bp_stream_t stream);
+
+/*
+ * bp_sense_attribute -- the share of every (context position, sense) pair in a logit.  The Backpack's logit of word w at
+ * position i is sum_l sum_{j<=i} alpha^l_ij <C_l(x_j), E[w]> (no norm and no bias lie between the combination and the tied
+ * LM head), and the summand is what the reference's training/src/localize_pred.py:25-65 reads off a (B, k, S, vocab)
+ * product and a full (B, k, S, S) alpha.  Here, for nq queries, query n = position i_n = query_pos[n] of sample
+ * b_n = query_sample[n], each with nvec fp32 vectors:
+ *   s_j  = scale * sum_c q_l[b_n, i_n, c] * k_l[b_n, j, c]         fp32, one accumulator, ascending c;  j = 0 .. i_n
+ *   m    = max_j s_j,  e_j = exp(s_j - m),  Z = sum_j e_j (fixed order),  p_j = e_j / Z
+ *   out[n, v, l, j] = p_j * sum_c table[row(b_n, j), l, c] * vec[n, v, c]      j <= i_n
+ *   out[n, v, l, j] = 0                                                        i_n < j < seqlen  (written: out may be
+ *                                                                              uninitialised memory)
+ *   probs[n, l, j]  = p_j, 0 behind i_n                                        when probs != NULL
+ * The probability stays fp32 (the reference rounds alpha to 16 bits before it multiplies).  (Additive, ABI still 11.)
+ *   qk           (batch, seqlen, 2, nsenses, d_k) 16-bit, the four element strides of bp_sense_alpha
+ *   table, row_index, table_rows   (table_rows, nsenses, d_out) 16-bit and (batch, seqlen) int32 with the strides and the
+ *                unsigned clamp of bp_sense_mix_gather: row(b, j) = min(unsigned(row_index[b, j]), table_rows - 1).  A
+ *                per-position content tensor is the same call: a (batch * seqlen, nsenses, d_out) table, row = b * seqlen + j
+ *   query_sample, query_pos   device int32 (nq), clamped on the device to [0, batch - 1] / [0, seqlen - 1]; the host never
+ *                reads them, so one captured launch serves any queries
+ *   vec          (nq, nvec, d_out) fp32 (E[w] exactly, or a sum of embedding rows that no 16-bit format holds), element
+ *                strides v_query / v_vec (multiples of 4), 16-byte aligned base, last stride 1
+ *   out          fp32, element strides o_query / o_vec / o_sense (o_sense >= seqlen, o_vec >= nsenses * o_sense when
+ *                nvec > 1, o_query >= nvec * o_vec when nq > 1), unit stride along j
+ *   probs        optional fp32, element strides p_query / p_sense (p_sense >= seqlen, p_query >= nsenses * p_sense)
+ *   ws           fp32 workspace of `ws_floats` >= bp_sense_attribute_ws_floats(nq, nsenses) elements: the (m, Z) pair of
+ *                every (query, sense); contents undefined on entry, it belongs to the call until the stream has run it
+ * Two launches (the pairs; the shares), no atomics, every reduction in a fixed order: two calls agree bit for bit.  Keys
+ * and table rows behind i_n, and other samples' rows, are never read.
+ * Errors, before any launch: BP_ERR_DTYPE; BP_ERR_HEAD_DIM (d_k < 1, d_k % 8 != 0 or d_k > 640); BP_ERR_DOUT (d_out < 1,
+ * d_out % 8 != 0 or d_out > 2048); BP_ERR_SHAPE (nq outside 1..65535, nvec outside 1..BP_ATTRIBUTE_MAX_VECS, nsenses outside
+ * 1..64, batch, seqlen or table_rows < 1, table_rows > 2^31 - 1, a NULL required pointer, a base that is not 16-byte aligned
+ * (qk, table, vec) or 4-byte aligned, a 16-bit stride that is no multiple of 8, an out / probs stride too small for its
+ * nesting); BP_ERR_SCALE; BP_ERR_WORKSPACE.
+ */
+int64_t bp_sense_attribute_ws_floats(int nq, int nsenses);
+int bp_sense_attribute(const void *qk, const void *table, const int32_t *row_index, const int32_t *query_sample,
+                       const int32_t *query_pos, const float *vec, float *out, float *probs, float *ws, int64_t ws_floats,
+                       int batch, int seqlen, int nsenses, int d_k, int d_out, int nq, int nvec, int64_t table_rows,
+                       int64_t qk_batch_stride, int64_t qk_row_stride, int64_t qk_two_stride, int64_t qk_sense_stride,
+                       int64_t t_row_stride, int64_t t_sense_stride, int64_t idx_batch_stride,
+                       int64_t v_query_stride, int64_t v_vec_stride,
+                       int64_t o_query_stride, int64_t o_vec_stride, int64_t o_sense_stride,
+                       int64_t p_query_stride, int64_t p_sense_stride,
+                       float softmax_scale, int dtype, bp_stream_t stream);
 
 #ifdef __cplusplus
 }
