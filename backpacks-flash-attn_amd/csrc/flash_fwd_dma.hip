@@ -368,8 +368,11 @@ BP_DEV void flash_fwd_tile(const FlashParams p, char *smem, const uint32_t lds0,
         // and l are "rescaled" harmlessly
         const float mc_new = !moves ? mc : (m_new == -INFINITY) ? 0.f : m_new * c2;
         // (a row that keeps its reference: 1 by construction, not by the exponent's arithmetic -- contracted into an fma,
-        // m_run * c2 - mc_new is the rounding error of the product, not 0)
-        const float alpha = moves ? fast_exp2(m_run * c2 - mc_new) : 1.f;
+        // m_run * c2 - mc_new is the rounding error of the product, not 0; for the same reason a row that moves but whose
+        // maximum this tile does not raise -- a key that ties with an earlier tile's best included -- takes 1 as well:
+        // 2^(half an ulp of m c2) is 1 + 2e-5 at m c2 ~ 500, and O = (a V1 + V2) / (a + 1) then leaves 1e-5 |V| where
+        // V1 = -V2; tests/test_gpu_prefill_needles.py, test_pair_flash_fwd_rows_are_the_means_of_their_needles)
+        const float alpha = (moves && m_new != m_run) ? fast_exp2(m_run * c2 - mc_new) : 1.f;
         l_run *= alpha;
         if (HAS_V) {
 #pragma unroll
