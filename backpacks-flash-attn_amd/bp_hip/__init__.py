@@ -74,6 +74,7 @@ SIGNATURES = {
     'bp_ln_bwd_ws_floats': (_i64, [_i32, _i32]),
     'bp_dropout_add_layer_norm_scaled': (_i32, [_ptr] * 9 + [_i64, _i32, _f32] + [_i32] * 5 + [_f32, _ptr, _ptr]),
     'bp_dropout_add_layer_norm_scaled_bwd': (_i32, [_ptr] * 13 + [_i64, _i64, _i32, _f32] + [_i32] * 4 + [_f32, _ptr, _ptr]),
+    'bp_add_layer_norm_chain': (_i32, [_ptr] * 11 + [_i64, _i32] + [_i64] * 3 + [_f32, _i32, _i32, _ptr]),
     'bp_softmax_bwd_causal': (_i32, [_ptr, _ptr, _i64, _i32, _f32, _i32, _ptr]),
     'bp_add_layer_norm_bwd': (_i32, [_ptr] * 9 + [_i64, _i32, _f32, _i32, _i32, _i32, _ptr]),
     'bp_xentropy_fwd': (_i32, [_ptr] * 4 + [_i64, _i32, _i64, _f32, _i32, _i32, _ptr]),
@@ -533,8 +534,82 @@ def _ln_scales(x0, weight, rowscale, colscale):
     return rowscale, colscale
 
 
+def _add_layer_norm_chain(x0, x1, weight, bias, eps, return_residual, x0b, embedding, out_residual):
+    """The inference-only forms of add_layer_norm (bp_add_layer_norm_chain); everything is checked before the launch."""
+    if embedding is not None:
+        if x0 is not None:
+            raise RuntimeError('bp_hip.add_layer_norm: give x0 or `embedding`, not both')
+        token_ids, position_ids, word, pos_table = embedding
+        _require_cuda(token_ids, position_ids, word, pos_table)
+        if word.dim() != 2 or word.dtype not in (torch.float16, torch.bfloat16) or not word.is_contiguous():
+            raise RuntimeError('bp_hip.add_layer_norm: the word table must be a contiguous 16-bit (rows, cols) matrix')
+        if token_ids.dtype != torch.int64 or not token_ids.is_contiguous() or token_ids.numel() == 0:
+            raise RuntimeError('bp_hip.add_layer_norm: token ids must be a contiguous, non-empty int64 tensor')
+        if x1 is not None:
+            raise RuntimeError('bp_hip.add_layer_norm: the embedding source takes no residual input (it is the stream so far)')
+        dt16, cols, shape, pos_len = word.dtype, word.shape[1], tuple(token_ids.shape) + (word.shape[1],), 0
+        if pos_table is not None:
+            if pos_table.dim() != 2 or pos_table.shape[1] != cols or pos_table.dtype != dt16 or not pos_table.is_contiguous():
+                raise RuntimeError('bp_hip.add_layer_norm: the position table must be a contiguous (rows, cols) matrix of '
+                                   'the word table\'s dtype')
+            pos_len = token_ids.shape[-1]
+            if position_ids is not None:
+                # what broadcasting against the ids allows here: one position per row, or one row of them shared by all
+                if position_ids.dtype != torch.int64 or not position_ids.is_contiguous() or \
+                        (tuple(position_ids.shape) != tuple(token_ids.shape) and position_ids.numel() != pos_len) or \
+                        position_ids.shape[-1] != pos_len:
+                    raise RuntimeError('bp_hip.add_layer_norm: position ids must be contiguous int64, shaped like the token '
+                                       'ids or like their last dimension')
+                pos_len = position_ids.numel()
+        elif position_ids is not None:
+            raise RuntimeError('bp_hip.add_layer_norm: position ids without a position table')
+    else:
+        _require_cuda(x0)
+        if x0 is None or x0.dtype not in (torch.float16, torch.bfloat16):
+            raise RuntimeError('bp_hip.add_layer_norm: the inference forms take a 16-bit x0')
+        dt16, cols, shape = x0.dtype, x0.shape[-1], tuple(x0.shape)
+        x0 = x0.contiguous()
+    _require_cuda(x1, x0b, weight, bias, out_residual)
+    if weight.shape != (cols,) or bias.shape != (cols,) or weight.dtype != bias.dtype or \
+            weight.dtype not in (torch.float32, dt16):
+        raise RuntimeError('bp_hip.add_layer_norm: weight/bias must be (cols,), both fp32 or both the 16-bit dtype in use')
+    if cols > 2048:
+        raise RuntimeError('bp_hip.add_layer_norm: the inference forms take rows of up to 2048 columns')
+    if x0b is not None:
+        if tuple(x0b.shape) != shape or x0b.dtype != dt16:
+            raise RuntimeError('bp_hip.add_layer_norm: x0b must have the shape and the 16-bit dtype of x0')
+        x0b = x0b.contiguous()
+    if x1 is not None:
+        if tuple(x1.shape) != shape or x1.dtype != torch.float32:
+            raise RuntimeError('bp_hip.add_layer_norm: the inference forms take an fp32 residual of x0\'s shape')
+        if out_residual is not x1:
+            x1 = x1.contiguous()
+    if out_residual is not None:
+        if not return_residual:
+            raise RuntimeError('bp_hip.add_layer_norm: out_residual without return_residual')
+        if tuple(out_residual.shape) != shape or out_residual.dtype != torch.float32 or not out_residual.is_contiguous():
+            raise RuntimeError('bp_hip.add_layer_norm: out_residual must be a contiguous fp32 tensor of x0\'s shape')
+    device = weight.device
+    z = torch.empty(shape, dtype=dt16, device=device)
+    xo = None
+    if return_residual:
+        xo = out_residual if out_residual is not None else torch.empty(shape, dtype=torch.float32, device=device)
+    wc, bc = weight.contiguous(), bias.contiguous()
+    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+    if embedding is not None:
+        source = (ptr(token_ids), ptr(position_ids), ptr(word), ptr(pos_table))
+        sizes = (word.shape[0], pos_table.shape[0] if pos_table is not None else 0, pos_len)
+    else:
+        source, sizes = (None, None, None, None), (0, 0, 0)
+    _call('bp_add_layer_norm_chain', device, ptr(x0), ptr(x0b), ptr(x1), *source, wc.data_ptr(), bc.data_ptr(),
+          z.data_ptr(), ptr(xo), z.numel() // cols, cols, *sizes, float(eps), _dtype_code(z),
+          int(weight.dtype == torch.float32))
+    return (z, xo) if return_residual else z
+
+
 def add_layer_norm(x0, x1, weight, bias, eps, residual_dtype=None, return_residual=True, dropout_p=0.0,
-                   rng_state=None, return_dropout_mask=False, rowscale=None, colscale=None):
+                   rng_state=None, return_dropout_mask=False, rowscale=None, colscale=None, x0b=None, embedding=None,
+                   out_residual=None, inference=False):
     """Fused z = LayerNorm(dropout(x0) / (1 - p) + x1) (fp32 math) and the updated residual stream
     x = dropout(x0) / (1 - p) + x1.
 
@@ -545,7 +620,23 @@ def add_layer_norm(x0, x1, weight, bias, eps, residual_dtype=None, return_residu
     dropout_p > 0 draws from `rng_state` (new_rng_state; pass your own to hand the same state to
     add_layer_norm_bwd).  rowscale (one value per row, x0's dtype) / colscale (cols, the weights' dtype): x0 is multiplied
     by rowscale[row] before and by colscale[col] after the dropout -- DropPath and LayerScale (`rowscale`, `layerscale` of
-    the reference's dropout_add_layer_norm)."""
+    the reference's dropout_add_layer_norm).
+
+    Inference-only forms (no dropout, no scales, no mask; 16-bit x0, fp32 residual), taken when one of these is given:
+    x0b          a second 16-bit branch output: x = (x0 + x1) + x0b, added in this order -- bit for bit what a launch
+                 that stores x0 + x1 in fp32 and a second one that adds x0b to it compute
+    embedding    (token_ids int64, position_ids int64 or None, word_table, position_table or None) with x0 = None:
+                 x0 is word_table[token_ids] (+ position_table[positions], one 16-bit add), gathered inside the kernel;
+                 without position_ids the position is the index along token_ids' last dimension
+    out_residual an fp32 tensor the residual stream is written to instead of a fresh one; it may be x1 itself
+    inference    True: the inference kernel also with none of the three (same bits; it has every load of a row in flight at
+                 once, where the general kernel decides operand by operand at run time)"""
+    if inference or x0b is not None or embedding is not None or out_residual is not None:
+        if dropout_p != 0.0 or return_dropout_mask or rowscale is not None or colscale is not None or \
+                residual_dtype not in (None, torch.float32):
+            raise RuntimeError('bp_hip.add_layer_norm: x0b / embedding / out_residual / inference are inference-only forms: no dropout, '
+                               'no mask, no scales, an fp32 residual stream')
+        return _add_layer_norm_chain(x0, x1, weight, bias, eps, return_residual, x0b, embedding, out_residual)
     _require_cuda(x0, x1, weight, bias)
     if x0.dtype not in (torch.float16, torch.bfloat16, torch.float32):
         raise RuntimeError(f'bp_hip.add_layer_norm: x0 must be fp16, bf16 or fp32, got {x0.dtype}')

@@ -200,6 +200,153 @@ hipError_t launch_add_layer_norm(const LnParams &p, int dtype, hipStream_t strea
 }
 
 // =====================================================================================================
+// Inference chain (bp_add_layer_norm_chain): the forms a chain of pre-norm blocks runs in eval() without an autograd
+// graph.  16-bit x0 / x0b / z, fp32 residual stream, no dropout, no scales, no mask -- and which operands exist is a
+// template parameter, not a branch.  In the kernel above every load sits behind a run-time branch and in front of a store it
+// may alias, so a wave's loads go out one after the other, each waiting for the one before (six round trips per 768-wide
+// row); here a wave first issues EVERY load of its row (phase 1), then does the arithmetic of the kernel above in the order
+// of the kernel above (phase 2: the same bits), then stores.
+//   EMB   x0 is not read but rebuilt from the embedding tables: word[tok[row]] (+ pos[position of row], added in fp32 and
+//         rounded once to ET, as torch's 16-bit add rounds); ids clamped to the tables as unsigned values; table rows stay
+//         cacheable (they repeat), the row streams are non-temporal as above
+//   X0B   a second 16-bit branch output joins last: x = (x0 + x1) + x0b -- what two launches compute when the first
+//         stores x0 + x1 exactly in fp32 and the second adds its own x0 to that, without the fp32 round trip
+//   X1 / XOUT   residual in / out present.  x_out may be x1 itself: a lane's store of an element depends on its own load
+//         of that element, and no other lane touches it.
+// =====================================================================================================
+template <bool NT> BP_DEV u32x2 ldg8(const void *base, int64_t idx) {   // four 16-bit elements from element idx
+    const u32x2 *at = reinterpret_cast<const u32x2 *>(static_cast<const char *>(base) + idx * 2);
+    if constexpr (NT) return __builtin_nontemporal_load(at);
+    else return *at;
+}
+template <class ET> BP_DEV void unpack4(u32x2 w, float (&v)[4]) {
+    v[0] = to_f32<ET>(w[0] & 0xffffu); v[1] = to_f32<ET>(w[0] >> 16);
+    v[2] = to_f32<ET>(w[1] & 0xffffu); v[3] = to_f32<ET>(w[1] >> 16);
+}
+
+template <class ET, int CH, bool W_F32, bool EMB, bool X0B, bool X1, bool XOUT>
+__global__ __launch_bounds__(256) void add_layer_norm_chain_kernel(const LnParams p) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= p.rows) return;
+    const int64_t base = row * p.cols;
+    const bool has_pos = EMB && p.wpe != nullptr;
+    int64_t tok_base = 0, pos_base = 0;
+    if constexpr (EMB) {
+        tok_base = (int64_t)min((uint64_t)p.tok[row], (uint64_t)p.last_tok) * p.cols;
+        if (has_pos) {
+            const uint32_t at = (uint32_t)row % p.pos_len;   // (rows < 2^32)
+            pos_base = (int64_t)min((uint64_t)(p.pos != nullptr ? p.pos[at] : (int64_t)at), (uint64_t)p.last_pos) * p.cols;
+        }
+    }
+
+    // phase 1: every load of the row in flight
+    u32x2 a[CH], e[CH], b2[CH];
+    u32x4 r[CH];
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+        const int col = (c * 64 + lane) * 4;
+        a[c] = u32x2{0u, 0u}; e[c] = u32x2{0u, 0u}; b2[c] = u32x2{0u, 0u}; r[c] = u32x4{0u, 0u, 0u, 0u};
+        if (col < p.cols) {
+            if constexpr (EMB) {
+                a[c] = ldg8<false>(p.wte, tok_base + col);
+                if (has_pos) e[c] = ldg8<false>(p.wpe, pos_base + col);
+            } else {
+                a[c] = ldg8<true>(p.x0, base + col);
+            }
+            if constexpr (X1)
+                r[c] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(static_cast<const char *>(p.x1) + (base + col) * 4));
+            if constexpr (X0B) b2[c] = ldg8<true>(p.x0b, base + col);
+        }
+    }
+
+    // phase 2: the sums, element by element in the order of add_layer_norm_kernel
+    float x[CH][4];
+    float sum = 0.f;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+        const int col = (c * 64 + lane) * 4;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) x[c][i] = 0.f;
+        if (col < p.cols) {
+            unpack4<ET>(a[c], x[c]);
+            if (has_pos) {
+                float q[4];
+                unpack4<ET>(e[c], q);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) x[c][i] = to_f32<ET>(Elem<ET>::from_float(x[c][i] + q[i]));
+            }
+            if constexpr (X1) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) x[c][i] += as_f32(r[c][i]);
+            }
+            if constexpr (X0B) {
+                float q[4];
+                unpack4<ET>(b2[c], q);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) x[c][i] += q[i];
+            }
+            if constexpr (XOUT) store4s<ET, true, true>(p.x_out, base + col, x[c]);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) sum += x[c][i];
+        }
+    }
+    const float inv_n = 1.f / (float)p.cols;
+    const float mu = wave_sum(sum) * inv_n;
+    float m2 = 0.f;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+        const int col = (c * 64 + lane) * 4;
+        if (col < p.cols) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float d = x[c][i] - mu;
+                m2 += d * d;
+            }
+        }
+    }
+    const float rs = rsqrtf(wave_sum(m2) * inv_n + p.eps);
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+        const int col = (c * 64 + lane) * 4;
+        if (col < p.cols) {
+            float g[4], b[4], z[4];
+            load4<ET, W_F32>(p.gamma, col, g);
+            load4<ET, W_F32>(p.beta, col, b);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) z[i] = (x[c][i] - mu) * rs * g[i] + b[i];
+            store4s<ET, false, false>(p.z, base + col, z);      // z stays cacheable for the GEMM that follows
+        }
+    }
+}
+
+// cols <= 2048 (the model widths): wider rows are hipErrorNotSupported
+hipError_t launch_add_layer_norm_chain(const LnParams &p, int dtype, hipStream_t stream) {
+    const dim3 g((unsigned)((p.rows + 3) / 4)), t(256);
+    const int chunks = (p.cols + 255) / 256;
+    const bool emb = p.wte != nullptr;
+    return with_dtype(dtype, [&](auto et) {
+        return with_flag(p.w_f32 != 0, [&](auto w) {
+            return with_flag(p.x0b != nullptr, [&](auto x0b) {
+                return with_flag(p.x_out != nullptr, [&](auto xout) {
+                    return with_bound<1, 2, 3, 4, 6, 8>(chunks, hipErrorNotSupported, [&](auto ch) {
+                        using ET = decltype(et);
+                        if (emb) {   // (bp_api.hip: the embedding source comes without a residual input)
+                            hipLaunchKernelGGL((add_layer_norm_chain_kernel<ET, ch, w, true, x0b, false, xout>), g, t, 0, stream, p);
+                            return hipGetLastError();
+                        }
+                        return with_flag(p.x1 != nullptr, [&](auto x1) {
+                            hipLaunchKernelGGL((add_layer_norm_chain_kernel<ET, ch, w, false, x0b, x1, xout>), g, t, 0, stream, p);
+                            return hipGetLastError();
+                        });
+                    });
+                });
+            });
+        });
+    });
+}
+
+// =====================================================================================================
 // Backward (reference: DropoutAddLayerNormFn.backward, flash_attn/ops/layer_norm.py:131-152;
 // csrc/layer_norm/ln_bwd_kernels.cuh, eval path: no dropout / rowscale / colscale)
 //

@@ -604,6 +604,46 @@ int bp_dropout_add_layer_norm_scaled(const void *x0, const void *x1, const void 
     return launch_status(bp::launch_add_layer_norm(p, dtype, static_cast<hipStream_t>(stream)));
 }
 
+int bp_add_layer_norm_chain(const void *x0a, const void *x0b, const void *x1, const int64_t *token_ids,
+                            const int64_t *position_ids, const void *word_table, const void *position_table,
+                            const void *gamma, const void *beta, void *z, void *x_out, int64_t rows, int cols,
+                            int64_t table_rows, int64_t position_rows, int64_t position_len, float epsilon, int dtype,
+                            int w_is_f32, bp_stream_t stream) {
+    if (dtype != BP_DTYPE_F16 && dtype != BP_DTYPE_BF16) return BP_ERR_DTYPE;
+    if (rows <= 0 || rows > 0xffffffffLL || cols <= 0 || cols % 4 != 0 || cols > 2048) return BP_ERR_SHAPE;
+    if (gamma == nullptr || beta == nullptr || z == nullptr) return BP_ERR_SHAPE;
+    // exactly one source of x0a: the tensor, or the tables with their ids
+    const bool emb = word_table != nullptr;
+    if (emb == (x0a != nullptr)) return BP_ERR_SHAPE;
+    if (emb) {
+        if (token_ids == nullptr || table_rows <= 0 || x1 != nullptr) return BP_ERR_SHAPE;   // (the embedding IS the stream so far)
+        if ((reinterpret_cast<uintptr_t>(token_ids) & 7u) != 0 || (reinterpret_cast<uintptr_t>(position_ids) & 7u) != 0)
+            return BP_ERR_SHAPE;
+        if (position_table != nullptr) {
+            if (position_rows <= 0 || position_len <= 0 || position_len > rows || rows % position_len != 0) return BP_ERR_SHAPE;
+        } else if (position_ids != nullptr) {
+            return BP_ERR_SHAPE;
+        }
+    } else if (token_ids != nullptr || position_ids != nullptr || position_table != nullptr) {
+        return BP_ERR_SHAPE;
+    }
+    // 8-byte chunks of the 16-bit operands, 16-byte chunks of the fp32 residual stream and of fp32 weights
+    if (!aligned16({gamma, beta, z}) || !aligned16_or_null({x0a, x0b, x1, x_out, word_table, position_table})) return BP_ERR_SHAPE;
+    if (!(isfinite(epsilon) && epsilon >= 0.f)) return BP_ERR_SCALE;
+    bp::LnParams p{};
+    p.x0 = x0a; p.x0b = x0b; p.x1 = x1; p.gamma = gamma; p.beta = beta; p.z = z; p.x_out = x_out;
+    p.rows = rows; p.cols = cols; p.eps = epsilon;
+    p.x1_f32 = 1; p.xo_f32 = 1; p.w_f32 = w_is_f32 ? 1 : 0; p.x0_f32 = 0;
+    if (emb) {
+        p.tok = token_ids; p.wte = word_table; p.last_tok = table_rows - 1;
+        if (position_table != nullptr) {
+            p.pos = position_ids; p.wpe = position_table; p.last_pos = position_rows - 1;
+            p.pos_len = (uint32_t)position_len;
+        }
+    }
+    return launch_status(bp::launch_add_layer_norm_chain(p, dtype, static_cast<hipStream_t>(stream)));
+}
+
 int bp_softmax_bwd_causal(const void *alpha, void *dalpha_inout, int64_t n_matrices, int seqlen,
                           float softmax_scale, int dtype, bp_stream_t stream) {
     if (dtype != BP_DTYPE_F16 && dtype != BP_DTYPE_BF16) return BP_ERR_DTYPE;

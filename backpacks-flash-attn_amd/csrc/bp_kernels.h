@@ -212,9 +212,17 @@ struct LnParams {
     float drop_scale;
     const void *rowscale;        // optional (rows) in x0's dtype: x0 row r is multiplied by rowscale[r] (DropPath)
     const void *colscale;        // optional (cols) in gamma's dtype: column c by colscale[c] (LayerScale)
+    // launch_add_layer_norm_chain only (the inference forms; NULL / 0 otherwise)
+    const void *x0b;             // optional (rows, cols) 16-bit second branch output: x = (x0 + x1) + x0b
+    const int64_t *tok;          // (rows) token ids: x0 = wte[tok] (+ wpe[position]) instead of the x0 pointer
+    const int64_t *pos;          // optional (pos_len) position ids; NULL: the position of row r is r % pos_len
+    const void *wte, *wpe;       // (last_tok + 1, cols) / optional (last_pos + 1, cols) 16-bit tables
+    uint32_t pos_len;            // row r takes position entry r % pos_len (rows for per-row ids, seqlen for shared ones)
+    int64_t last_tok, last_pos;  // ids are clamped to [0, last] as unsigned values
 };
 
 hipError_t launch_add_layer_norm(const LnParams &p, int dtype, hipStream_t stream);
+hipError_t launch_add_layer_norm_chain(const LnParams &p, int dtype, hipStream_t stream);
 
 constexpr int kLnBwdMaxWg = 1024;   // row-parallel workgroups of the backward = rows of its partial-sum workspace
 struct LnBwdParams {

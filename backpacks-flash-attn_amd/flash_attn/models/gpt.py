@@ -12,6 +12,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from transformers import GPT2Config
 
+import bp_hip
 from flash_attn.modules.block import Block
 from flash_attn.modules.embedding import GPT2Embeddings
 from flash_attn.modules.mha import MHA, cache_lengths
@@ -131,10 +132,47 @@ class GPTModel(GPTPreTrainedModel):
         self.apply(partial(_init_weights, n_layer=config.num_hidden_layers,
                            initializer_range=config.initializer_range))
 
+    # Inference forwards take the chained add + LayerNorm launches (`_forward_chained`); False: always the launches of
+    # `forward` below.  Same bits either way (tests/test_gpu_ln_chain.py compares the two in one process).
+    ln_chain = True
+
+    def _chain_applies(self, input_ids, inference_params):
+        if not self.ln_chain or self.training or torch.is_grad_enabled() or inference_params is not None:
+            return False
+        if not self.fused_dropout_add_ln or not input_ids.is_cuda or input_ids.dtype != torch.int64 \
+                or torch.is_autocast_enabled():
+            return False
+        word = self.embeddings.word_embeddings
+        if word.weight.dtype not in (torch.float16, torch.bfloat16) or word.max_norm is not None:
+            return False
+        return all(type(layer) is Block and layer.chain_supported() for layer in self.layers)
+
+    def _forward_chained(self, input_ids, position_ids):
+        """The forward of eval() without an autograd graph, 16-bit activations and an fp32 residual stream: the embedding
+        lookup happens inside ln_0's launch and again inside the first block's norm1 (no embedding tensor, no fp32 copy of
+        it), every norm2 stores z alone and the following norm1 settles the residual in place (Block._forward_chained),
+        and the last norm stores no residual at all.  Only launches are rearranged; every sum keeps its order."""
+        emb = self.embeddings
+        input_ids = input_ids.contiguous()
+        pos_table = emb.position_embeddings.weight if emb.max_position_embeddings > 0 else None
+        if pos_table is not None and position_ids is not None:
+            position_ids = position_ids.expand_as(input_ids).contiguous() \
+                if position_ids.shape[-1] != input_ids.shape[-1] else position_ids.contiguous()
+        source = (input_ids, position_ids if pos_table is not None else None, emb.word_embeddings.weight, pos_table)
+        hidden = bp_hip.add_layer_norm(None, None, self.ln_0.weight, self.ln_0.bias, self.ln_0.eps,
+                                       return_residual=False, embedding=source)
+        residual = pending = None
+        for i, layer in enumerate(self.layers):
+            hidden, residual, pending = layer._forward_chained(hidden, residual, pending,
+                                                               embedding=source if i == 0 else None)
+        return hidden
+
     def forward(self, input_ids, position_ids=None, inference_params=None):
         """`inference_params` (src/utils/generation.py InferenceParams): KV-cached generation, forwarded to every mixer
         (reference gpt.py:243).  In a decode step without `position_ids` the position of sample b is its cached length,
         read on the device."""
+        if self._chain_applies(input_ids, inference_params):
+            return self._forward_chained(input_ids, position_ids)
         if inference_params is not None and position_ids is None and inference_params.sequence_len_offset > 0:
             lengths = cache_lengths(inference_params, input_ids.shape[0], input_ids.device)
             position_ids = lengths.long().unsqueeze(1) + torch.arange(input_ids.shape[1], device=input_ids.device)

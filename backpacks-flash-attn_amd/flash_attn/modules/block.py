@@ -14,6 +14,7 @@ import torch
 import torch.nn as nn
 from torch import Tensor
 
+import bp_hip
 from flash_attn.modules.mha import MHA
 from flash_attn.modules.mlp import Mlp
 from flash_attn.ops.layer_norm import dropout_add_layer_norm
@@ -102,3 +103,31 @@ class Block(nn.Module):
                 residual = self.drop_path2(self.dropout2(mlp_out)) + residual
                 hidden_states = self.norm2(residual.to(dtype=self.norm2.weight.dtype))
         return hidden_states, residual
+
+    # ---- inference chain (GPTModel._forward_chained) ---------------------------------------------------------------
+    # Between this block's norm2 and the next block's norm1 the residual stream is only read back: norm2 therefore
+    # stores no residual (z alone), its branch output stays `pending`, and the next norm1 adds
+    # (pending + residual) + mixed in the order the two launches of `forward` add them -- same bits, 6 bytes per
+    # element less through memory -- writing the settled residual over the old one.
+
+    def chain_supported(self):
+        """What `_forward_chained` takes for granted besides the caller's own conditions (eval, no autograd)."""
+        return self.fused_dropout_add_ln and not isinstance(self.mlp, nn.Identity) \
+            and self.drop_path1.p == 0 and self.drop_path2.p == 0 and self.norm1.weight.shape[0] <= 2048
+
+    def _forward_chained(self, hidden_states, residual, pending, embedding=None, mixer_kwargs=None):
+        """One block of the chain.  `pending`: the previous block's MLP output, not yet part of `residual` (fp32) -- or, in
+        the first block, `embedding` (the source tuple of bp_hip.add_layer_norm) stands for both.  Returns
+        (hidden, residual, pending)."""
+        mixed = self.mixer(hidden_states, **(mixer_kwargs or {}))
+        if embedding is not None:
+            hidden_states, residual = bp_hip.add_layer_norm(None, None, self.norm1.weight, self.norm1.bias, self.norm1.eps,
+                                                            x0b=mixed, embedding=embedding)
+        else:
+            hidden_states, residual = bp_hip.add_layer_norm(pending, residual, self.norm1.weight, self.norm1.bias,
+                                                            self.norm1.eps, x0b=mixed, out_residual=residual)
+        del pending, mixed
+        mlp_out = self.mlp(hidden_states)
+        hidden_states = bp_hip.add_layer_norm(mlp_out, residual, self.norm2.weight, self.norm2.bias, self.norm2.eps,
+                                              return_residual=False, inference=True)
+        return hidden_states, residual, mlp_out

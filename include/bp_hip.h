@@ -52,7 +52,9 @@ extern "C" {
                               presence penalties and a list of suppressed ids;
                               and one more: bp_row_extremes, the n largest / n smallest elements of every row of a
                               matrix, for the vocabulary projections of sense vectors;
-                              and one more: bp_sense_attribute, the shares of every (position, sense) pair in a logit) */
+                              and one more: bp_sense_attribute, the shares of every (position, sense) pair in a logit;
+                              and one more: bp_add_layer_norm_chain, the inference-only forms of the fused add + LayerNorm
+                              -- a second branch input, x0 rebuilt from the embedding tables, residual written in place) */
 
 /* element type of q/k/v/out/content tensors */
 #define BP_DTYPE_F16 0
@@ -481,6 +483,30 @@ int bp_dropout_add_layer_norm_scaled_bwd(const void *dz, const void *dx_in, cons
                                          float *ws, int64_t ws_floats, int64_t rows, int cols, float epsilon, int dtype,
                                          int x0_is_f32, int res_is_f32, int w_is_f32, float p_dropout,
                                          const uint64_t *rng_state, bp_stream_t stream);
+
+/*
+ * bp_add_layer_norm_chain -- inference-only forms of bp_add_layer_norm for a chain of pre-norm blocks: no dropout, no
+ * scales, no mask; 16-bit x0a / x0b / z, fp32 residual stream (x1, x_out).
+ *   x = (x0a + x1) + x0b   in fp32, in exactly this order ;  z = LayerNorm(x) ;  x_out = x
+ * which is, bit for bit, what two bp_add_layer_norm launches give when the first stores x0a + x1 in fp32 and the second
+ * adds x0b to it -- without writing and re-reading that fp32 sum.
+ *   x0a       (rows, cols) 16-bit, or NULL when the embedding source below is given (exactly one of the two)
+ *   x0b, x1   (rows, cols) 16-bit / fp32, either may be NULL (no such term); x1 must be NULL with the embedding source
+ *   token_ids, word_table       the embedding source: x0a[r] = word_table[token_ids[r]]; (rows) int64 and
+ *                               (table_rows, cols) 16-bit
+ *   position_table, position_ids  optional (position_rows, cols) 16-bit: x0a[r] = word row + position row, added in fp32 and
+ *                               rounded once to the 16-bit type (a 16-bit add).  Row r takes entry r % position_len of
+ *                               position_ids ((position_len) int64), or the position r % position_len itself when
+ *                               position_ids is NULL; rows % position_len == 0.
+ *                               Ids are clamped, as unsigned values, to the last row of their table.
+ *   x_out     fp32 or NULL (z alone); may be x1 itself: every element is read before it is written, by the same lane
+ * cols % 4 == 0 and <= 2048, rows < 2^32, pointers 16-byte aligned (ids 8-byte).
+ */
+int bp_add_layer_norm_chain(const void *x0a, const void *x0b, const void *x1, const int64_t *token_ids,
+                            const int64_t *position_ids, const void *word_table, const void *position_table,
+                            const void *gamma, const void *beta, void *z, void *x_out, int64_t rows, int cols,
+                            int64_t table_rows, int64_t position_rows, int64_t position_len, float epsilon, int dtype,
+                            int w_is_f32, bp_stream_t stream);
 
 /*
  * bp_xentropy_fwd / bp_xentropy_bwd -- fused softmax cross-entropy over vocabulary-sized rows.
