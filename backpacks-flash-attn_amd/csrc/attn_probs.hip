@@ -16,16 +16,17 @@
 #include "bp_common.h"
 #include "bp_kernels.h"
 #include "bp_philox.h"
+#include "staged_tile.h"
 
 namespace bp {
 
 template <int KD>
 struct ProbsCfg {
     static constexpr int BM = 128, BN = 64, NT = 256;
-    static constexpr int KROW = KD * 32 + 16;
+    static constexpr int KROW = k_pitch(KD);
     static constexpr int KTILE = BN * KROW;
     static constexpr int KCH = KD * 2;
-    static constexpr int K_ITERS = (BN * KCH + NT - 1) / NT;
+    static constexpr int K_ITERS = tile_iters(BN, KCH, NT);
 };
 
 template <class ET, int KD, bool VEC>
@@ -34,11 +35,8 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(const ProbsParams p) {
     using E = Elem<ET>;
     __shared__ __attribute__((aligned(16))) char smem[2 * C::KTILE + 4 * 4096];
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l31 = lane & 31;
-    const int hh = lane >> 5;
+    const LaneCoord L = lane_coord();
+    const int lane = L.lane, wave = L.wave, l31 = L.l31, hh = L.hh;
 
     const int n_qtiles = (p.sq + C::BM - 1) / C::BM;
     int bh, qt;
@@ -50,9 +48,9 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(const ProbsParams p) {
     const uint16_t *kg = reinterpret_cast<const uint16_t *>(p.k) + batch * p.k_bs + (int64_t)head * p.k_hs;
     uint16_t *pg = reinterpret_cast<uint16_t *>(p.p) + batch * p.p_bs + (int64_t)head * p.p_hs;
 
-    const int q0 = qt * C::BM + wave * 32;
-    const int my_q = q0 + l31;
-    const bool wave_has_rows = q0 < p.sq;
+    const QueryRows R = query_rows(L, qt * C::BM, p.sq);
+    const int q0 = R.q0, my_q = R.my_q;
+    const bool wave_has_rows = R.wave_has_rows;
     const float c2 = p.scale_log2e;
     const int nkb_all = (p.sk + C::BN - 1) / C::BN;                 // blocks to WRITE
     int k_end = p.sk;
@@ -60,16 +58,7 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(const ProbsParams p) {
     const int nkb = (k_end + C::BN - 1) / C::BN;                    // blocks to COMPUTE (workgroup)
 
     u32x4 qf[KD];
-#pragma unroll
-    for (int s = 0; s < KD; ++s) {
-        const int col = 16 * s + 8 * hh;
-        u32x4 v = {0u, 0u, 0u, 0u};
-        if (my_q < p.sq && col < p.d) {
-            const uint16_t *row = qg + (int64_t)my_q * p.q_rs;
-            v = VEC ? ld_global_16B(row + col) : ld_global_8x2B(row, col, p.d);
-        }
-        qf[s] = v;
-    }
+    load_q_frags<VEC>(qf, qg, p.q_rs, my_q, p.sq, p.d, hh);
     // dropout report (bp_attn_probs_dropout): dropped entries get their sign bit set
     const bool drop = p.drop_thr != 0u;
     DropoutStream rng = {0u, 0u};
@@ -81,48 +70,19 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(const ProbsParams p) {
     float lse2 = 0.f;
     if (my_q < p.sq) lse2 = p.lse[((int64_t)batch * p.h + head) * p.lse_stride + my_q] * kLog2e;
 
+    constexpr std::integral_constant<int, KD> kd;
     u32x4 kreg[C::K_ITERS];
-    auto fetch = [&](int kb) {
-#pragma unroll
-        for (int i = 0; i < C::K_ITERS; ++i) {
-            const int c = tid + i * C::NT;
-            const int row = c / C::KCH, ch = c - row * C::KCH;
-            const int key = kb * C::BN + row;
-            u32x4 v = {0u, 0u, 0u, 0u};
-            if (c < C::BN * C::KCH && key < p.sk && ch * 8 < p.d) {
-                const uint16_t *r = kg + (int64_t)key * p.k_rs;
-                v = VEC ? ld_global_16B(r + ch * 8) : ld_global_8x2B(r, ch * 8, p.d);
-            }
-            kreg[i] = v;
-        }
-    };
-    auto stash = [&](int buf) {
-        char *kb_ = smem + buf * C::KTILE;
-#pragma unroll
-        for (int i = 0; i < C::K_ITERS; ++i) {
-            const int c = tid + i * C::NT;
-            const int row = c / C::KCH, ch = c - row * C::KCH;
-            if (c < C::BN * C::KCH) lds_write_16B(kb_, row * C::KROW + ch * 16, kreg[i]);
-        }
-    };
+    auto fetch = [&](int kb) { k_fetch<VEC, C::BN, C::NT>(kreg, kg, p.k_rs, kb * C::BN, p.sk, p.d, kd, L.tid); };
+    auto stash = [&](int buf) { k_stash<C::BN, C::NT>(kreg, smem + buf * C::KTILE, kd, L.tid); };
 
-    const int k_lane_off = l31 * C::KROW + hh * 16;
+    const int k_lane = k_lane_off(KD, l31, hh);
     // a lane writes 4 consecutive keys (8 bytes) of its own query row per (kk, g)
     uint16_t *prow = pg + (int64_t)my_q * p.p_rs;
     const bool row_ok = my_q < p.sq;
     const bool vec_store = p.p_vec != 0;   // every row start 8-byte aligned (checked on the host)
 
-    auto store4 = [&](int key0, float x0, float x1, float x2, float x3) {
-        if (!row_ok) return;
-        if (vec_store && key0 + 3 < p.sk) {
-            u32x2 w = {E::pack2(x0, x1), E::pack2(x2, x3)};
-            *reinterpret_cast<u32x2 *>(prow + key0) = w;
-        } else {
-            if (key0 + 0 < p.sk) prow[key0 + 0] = E::from_float(x0);
-            if (key0 + 1 < p.sk) prow[key0 + 1] = E::from_float(x1);
-            if (key0 + 2 < p.sk) prow[key0 + 2] = E::from_float(x2);
-            if (key0 + 3 < p.sk) prow[key0 + 3] = E::from_float(x3);
-        }
+    auto put4 = [&](int key0, float x0, float x1, float x2, float x3) {
+        if (row_ok) store4<ET>(prow, key0, p.sk, vec_store, x0, x1, x2, x3);
     };
 
     // ---- full-line path: tile -> wave-private LDS scratch -> 16-byte row-contiguous stores -------------
@@ -169,21 +129,14 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(const ProbsParams p) {
                 const char *kbuf = smem + cur * C::KTILE;
 #pragma unroll
                 for (int kk = 0; kk < 2; ++kk) {
-                    f32x16 st;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) st[r] = 0.f;
-#pragma unroll
-                    for (int s = 0; s < KD; ++s) {
-                        const u32x4 a = lds_read_16B(kbuf, k_lane_off + kk * 32 * C::KROW + s * 32);
-                        st = E::mfma(a, qf[s], st);
-                    }
+                    f32x16 st = st_half<ET>(kbuf, qf, k_lane, kk);
                     const uint32_t keep = keep_bits(kb, kk);
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
                         float e[4];
 #pragma unroll
                         for (int i = 0; i < 4; ++i) {
-                            const int key = kb * C::BN + kk * 32 + 8 * g + 4 * hh + i;
+                            const int key = st_key(kb * C::BN + kk * 32, 4 * g + i, hh);
                             e[i] = fast_exp2(fmaf(st[4 * g + i], c2, -lse2));
                             if (p.causal && key > my_q) e[i] = 0.f;
                             if (!((keep >> (4 * g + i)) & 1u)) e[i] = -e[i];
@@ -201,23 +154,16 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(const ProbsParams p) {
 #pragma unroll
                 for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
-                    for (int g = 0; g < 4; ++g) store4(kb * C::BN + kk * 32 + 8 * g + 4 * hh, 0.f, 0.f, 0.f, 0.f);
+                    for (int g = 0; g < 4; ++g) put4(st_key(kb * C::BN + kk * 32, 4 * g, hh), 0.f, 0.f, 0.f, 0.f);
             } else {
                 const char *kbuf = smem + cur * C::KTILE;
 #pragma unroll
                 for (int kk = 0; kk < 2; ++kk) {
-                    f32x16 st;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) st[r] = 0.f;
-#pragma unroll
-                    for (int s = 0; s < KD; ++s) {
-                        const u32x4 a = lds_read_16B(kbuf, k_lane_off + kk * 32 * C::KROW + s * 32);
-                        st = E::mfma(a, qf[s], st);
-                    }
+                    f32x16 st = st_half<ET>(kbuf, qf, k_lane, kk);
                     const uint32_t keep = keep_bits(kb, kk);
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int key = kb * C::BN + kk * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+                        const int key = st_key(kb * C::BN + kk * 32, r, hh);
                         float e = fast_exp2(fmaf(st[r], c2, -lse2));
                         if (key >= p.sk || (p.causal && key > my_q)) e = 0.f;
                         if (!((keep >> r) & 1u)) e = -e;
@@ -225,7 +171,7 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(const ProbsParams p) {
                     }
 #pragma unroll
                     for (int g = 0; g < 4; ++g)
-                        store4(kb * C::BN + kk * 32 + 8 * g + 4 * hh, st[4 * g], st[4 * g + 1], st[4 * g + 2], st[4 * g + 3]);
+                        put4(st_key(kb * C::BN + kk * 32, 4 * g, hh), st[4 * g], st[4 * g + 1], st[4 * g + 2], st[4 * g + 3]);
                 }
             }
         }
@@ -241,7 +187,7 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(const ProbsParams p) {
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) store4(kb * C::BN + kk * 32 + 8 * g + 4 * hh, 0.f, 0.f, 0.f, 0.f);
+                for (int g = 0; g < 4; ++g) put4(st_key(kb * C::BN + kk * 32, 4 * g, hh), 0.f, 0.f, 0.f, 0.f);
     }
 }
 

@@ -15,6 +15,7 @@
 //   * workgroups of one (batch, head) are placed on one XCD (shared L2 for K/V), heaviest first.
 #include "bp_common.h"
 #include "bp_kernels.h"
+#include "staged_tile.h"
 
 namespace bp {
 
@@ -23,7 +24,7 @@ struct FlashCfg {
     static constexpr int BM = 128;            // queries per workgroup
     static constexpr int BN = 64;             // keys per tile
     static constexpr int NT = 256;            // threads
-    static constexpr int KROW = KD * 32 + 16; // bytes per K row in LDS (16 B pad: conflict-free b128)
+    static constexpr int KROW = k_pitch(KD);  // bytes per K row in LDS
     static constexpr int VROW = NV * 64;      // bytes per V row in LDS (XOR-swizzled 64-B chunks)
     static constexpr int KTILE = BN * KROW;
     static constexpr int VTILE = HAS_V ? BN * VROW : 0;
@@ -40,11 +41,8 @@ __global__ __launch_bounds__(256) void flash_fwd_kernel(const FlashParams p) {
     using E = Elem<ET>;
     __shared__ __attribute__((aligned(16))) char smem[2 * C::STAGE];
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l31 = lane & 31;
-    const int hh = lane >> 5;
+    const LaneCoord L = lane_coord();
+    const int tid = L.tid, lane = L.lane, l31 = L.l31, hh = L.hh;
 
     int bh, slot;
     if (!xcd_map(blockIdx.x, p.b * p.h, p.n_qtiles, bh, slot)) return;
@@ -75,11 +73,15 @@ __global__ __launch_bounds__(256) void flash_fwd_kernel(const FlashParams p) {
     if (p.causal) k_end = min(seq_k, qt * C::BM + C::BM);
     const int nkb = (k_end + C::BN - 1) / C::BN;
 
-    const int q0 = qt * C::BM + wave * 32;   // first query row of this wave
-    const int my_q = q0 + l31;
-    const bool wave_has_rows = q0 < seq_q;
+    const QueryRows R = query_rows(L, qt * C::BM, seq_q);
+    const int q0 = R.q0, my_q = R.my_q;
+    const bool wave_has_rows = R.wave_has_rows;
     const float c2 = p.scale_log2e;
 
+    // The Q load, the K / V loaders, the P V loop and the O epilogue below are this kernel's own text although staged_tile.h
+    // holds the same steps for attn_probs.hip and the sense-mix kernels: on the shared functions the d = 36 instantiation
+    // missed its same-speed bound against the parent (0.7287 ms against 0.7239 + 0.0037, profiles/README.md "staged
+    // tiles"), so they went back.  What this kernel shares (coordinates, S^T, the key map) leaves its code as it was.
     // ---- Q fragments (B operand of S^T = K Q^T): query l31, d = 16*s + 8*hh .. +7 ----------------
     u32x4 qf[KD];
 #pragma unroll
@@ -152,7 +154,7 @@ __global__ __launch_bounds__(256) void flash_fwd_kernel(const FlashParams p) {
     float l_run = 0.f;         // running sum of exp over the keys THIS lane holds (halves add up)
 
     // lane-constant LDS offsets
-    const int k_lane_off = l31 * C::KROW + hh * 16;                   // + kk*32*KROW + s*32
+    const int k_lane = k_lane_off(KD, l31, hh);
     const int v_row_lane = 4 * hh + ((lane & 15) >> 2);               // + kk*32 + ks*16 (+8)
     const int v_ch_lane16 = ((lane >> 4) & 1) * 2;                    // 16-col group -> 16-B chunk pair
 
@@ -160,21 +162,13 @@ __global__ __launch_bounds__(256) void flash_fwd_kernel(const FlashParams p) {
         constexpr bool kMasked = decltype(MASKED)::value;
         f32x16 st[2];
 #pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) st[kk][r] = 0.f;
-#pragma unroll
-            for (int s = 0; s < KD; ++s) {
-                const u32x4 a = lds_read_16B(kbuf, k_lane_off + kk * 32 * C::KROW + s * 32);
-                st[kk] = E::mfma(a, qf[s], st[kk]);
-            }
-        }
+        for (int kk = 0; kk < 2; ++kk) st[kk] = st_half<ET>(kbuf, qf, k_lane, kk);
         if (kMasked) {
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int key = kb * C::BN + kk * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+                    const int key = st_key(kb * C::BN + kk * 32, r, hh);
                     const bool dead = key >= seq_k || (p.causal && key > my_q);
                     if (dead) st[kk][r] = -INFINITY;
                 }
@@ -264,7 +258,7 @@ __global__ __launch_bounds__(256) void flash_fwd_kernel(const FlashParams p) {
             for (int n = 0; n < NV; ++n)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    const int d0 = n * 32 + 8 * g + 4 * hh;
+                    const int d0 = st_key(n * 32, 4 * g, hh);
                     const float x0 = acc[n][4 * g + 0] * inv, x1 = acc[n][4 * g + 1] * inv;
                     const float x2 = acc[n][4 * g + 2] * inv, x3 = acc[n][4 * g + 3] * inv;
                     if (d0 + 0 < p.d) og[d0 + 0] = E::from_float(x0);

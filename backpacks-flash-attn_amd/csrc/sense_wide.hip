@@ -18,6 +18,7 @@
 //   sense_mix_wide_kernel    out = sum_l alpha_l C_l, alpha never stored               (backpack.py:313)
 #include "bp_common.h"
 #include "bp_kernels.h"
+#include "staged_tile.h"
 
 namespace bp {
 
@@ -33,17 +34,20 @@ struct WideCfgT {
     static constexpr int BK = 32;                  // keys per block
     static constexpr int NT = 256;
     static constexpr int KD_MAX = KDT;
-    static constexpr int KROW_MAX = KD_MAX * 32 + 16;
-    static constexpr int KTILE_MAX = BK * KROW_MAX;
-    static constexpr int K_ITERS_MAX = (BK * KD_MAX * 2 + NT - 1) / NT;   // 16-byte chunks per thread and tile
+    static constexpr int KTILE_MAX = BK * k_pitch(KD_MAX);
+    static constexpr int K_ITERS_MAX = tile_iters(BK, KD_MAX * 2, NT);
     static constexpr int NB = 4;                   // 32-column blocks of the output per workgroup (mix)
     static constexpr int CROW = NB * 64;
     static constexpr int CTILE = BK * CROW;        // 8 192 bytes
     static constexpr int CCH = NB * 4;
-    static constexpr int C_ITERS = (BK * CCH + NT - 1) / NT;   // 2
+    static constexpr int C_ITERS = tile_iters(BK, CCH, NT);   // 2
 };
 constexpr int kWideSmallKd = 12, kWideLargeKd = 40;
 
+// WideKLoader, wide_load_q and the alpha kernel's store4 serve sense_lse_wide_kernel and sense_alpha_wide_kernel only;
+// sense_mix_wide_kernel uses the same steps from staged_tile.h.  On the shared functions the two kernels missed their
+// same-speed bound against the parent at S = 1000, d_k = 160 (0.0416 against 0.0412 ms, 0.0555 against 0.0546 + 0.0005;
+// profiles/README.md "staged tiles"), so their text went back and their code is the parent's.
 // K rows [kb*32, kb*32+32) of one sense -> registers -> LDS image (row pitch krow = 32*KD + 16 bytes: conflict-free b128)
 template <bool VEC, int KDT>
 struct WideKLoader {
@@ -85,31 +89,6 @@ BP_DEV void wide_load_q(u32x4 (&qf)[KDT], const uint16_t *qrow, bool q_valid, in
         if (q_valid && col < dk) v = VEC ? ld_global_16B(qrow + col) : ld_global_8x2B(qrow, col, dk);
         qf[s] = v;
     }
-}
-
-// S^T (32 keys x 32 queries) of one key block for my wave's 32 queries: st[r] = q[my_q] . k[kb*32 + (r&3) + 8*(r>>2) + 4*hh].
-// Two accumulation chains (even / odd steps) so that consecutive MFMAs do not wait for each other; the fragments of the
-// steps >= kd hold zeros and are skipped.
-template <class ET, int KDT>
-BP_DEV f32x16 wide_scores(const char *kbuf, const u32x4 (&qf)[KDT], int kd, int l31, int hh) {
-    using E = Elem<ET>;
-    f32x16 st0, st1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { st0[r] = 0.f; st1[r] = 0.f; }
-    const int krow = kd * 32 + 16;
-    const int k_lane_off = l31 * krow + hh * 16;
-#pragma unroll
-    for (int s = 0; s < KDT; ++s)
-        if (s < kd) {
-            const u32x4 a = lds_read_16B(kbuf, k_lane_off + s * 32);
-            if (s & 1) st1 = E::mfma(a, qf[s], st1);
-            else st0 = E::mfma(a, qf[s], st0);
-        }
-    settle_acc(st1);   // the run-time bound `s < kd` puts a branch behind every MFMA: wait for the matrix pipe here (bp_common.h)
-    pin_acc(st0);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) st0[r] += st1[r];
-    return st0;
 }
 
 struct WideParams {          // the three kernels' common part (all strides in 16-bit elements)
@@ -156,11 +135,11 @@ __global__ __launch_bounds__(256) void sense_lse_wide_kernel(const WideParams p)
         const int cur = kb & 1;
         if (kb + 1 < nkb) ld.fetch(kg, p.qk_rs, kb + 1, S, dk, kd, tid);
         if (wave_has_rows && kb <= my_last_kb) {
-            f32x16 st = wide_scores<ET, KDT>(smem + cur * ktile, qf, kd, l31, hh);
-            const int lim = min(S - 1, my_q) - kb * WideCfg::BK - 4 * hh;   // last visible key of my row, block-relative
+            f32x16 st = st_half_wide<ET>(smem + cur * ktile, qf, kd, l31, hh);
+            const int lim = min(S - 1, my_q) - kb * WideCfg::BK - 4 * hh;   // last visible key of my row, as st_key(0, r, 0) of my half-wave
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                if ((r & 3) + 8 * (r >> 2) > lim) st[r] = -INFINITY;
+                if (st_key(0, r, 0) > lim) st[r] = -INFINITY;
             float mx = st[0];
 #pragma unroll
             for (int r = 1; r < 16; ++r) mx = fmaxf(mx, st[r]);
@@ -243,12 +222,12 @@ __global__ __launch_bounds__(256) void sense_alpha_wide_kernel(const WideAlphaPa
         const int cur = kb & 1;
         if (kb + 1 < nkb) ld.fetch(kg, p.qk_rs, kb + 1, S, dk, kd, tid);
         if (wave_has_rows && kb <= my_last_kb) {
-            f32x16 st = wide_scores<ET, KDT>(smem + cur * ktile, qf, kd, l31, hh);
+            f32x16 st = st_half_wide<ET>(smem + cur * ktile, qf, kd, l31, hh);
             const int lim = my_q - kb * WideCfg::BK - 4 * hh;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 float e = fast_exp2(fmaf(st[r], c2, -lse2));
-                if ((r & 3) + 8 * (r >> 2) > lim) e = 0.f;      // above the diagonal: exact zeros
+                if (st_key(0, r, 0) > lim) e = 0.f;      // above the diagonal: exact zeros
                 st[r] = e;
             }
             if (my_q < S) {
@@ -272,13 +251,12 @@ __global__ __launch_bounds__(256) void sense_alpha_wide_kernel(const WideAlphaPa
 // ---- fused mix -----------------------------------------------------------------------------------------------------------
 template <class ET, bool VEC_QK, bool VEC_C, int KDT>
 __global__ __launch_bounds__(256) void sense_mix_wide_kernel(const MixParams p) {
-    using E = Elem<ET>;
     using W = WideCfgT<KDT>;
     __shared__ __attribute__((aligned(16))) char smem[2 * (W::KTILE_MAX + W::CTILE)];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l31 = lane & 31, hh = lane >> 5;
+    const LaneCoord L = lane_coord();
+    const int tid = L.tid, l31 = L.l31, hh = L.hh;
     const int S = p.s, dk = p.dk, kd = (dk + 15) / 16;
-    const int ktile = W::BK * (kd * 32 + 16), stage = ktile + W::CTILE;
+    const int ktile = W::BK * k_pitch(kd), stage = ktile + W::CTILE;
     const int n_qtiles = (S + W::BM - 1) / W::BM;
     const int n_chunks = (p.dout + W::NB * 32 - 1) / (W::NB * 32);
     int grp, slot;
@@ -292,42 +270,25 @@ __global__ __launch_bounds__(256) void sense_mix_wide_kernel(const MixParams p) 
     const int k_end = min(S, qt * W::BM + W::BM);
     const int nkb = (k_end + W::BK - 1) / W::BK;
     const int nsteps = p.nsenses * nkb;
-    const int q0 = qt * W::BM + wave * 32, my_q = q0 + l31;
-    const bool wave_has_rows = q0 < S;
+    const QueryRows R = query_rows(L, qt * W::BM, S);
+    const int q0 = R.q0, my_q = R.my_q;
+    const bool wave_has_rows = R.wave_has_rows;
     const int my_last_kb = q0 / W::BK;
     const float c2 = p.scale_log2e;
     const int nb_live = min(W::NB, (p.dout - col_base + 31) / 32);
 
-    WideKLoader<VEC_QK, KDT> ld;
     u32x4 qf[KDT];
+    u32x4 kreg[W::K_ITERS_MAX];
     u32x4 creg[W::C_ITERS];
     auto fetch = [&](int step) {
         const int l = step / nkb, kb = step - l * nkb;
-        ld.fetch(kg + (int64_t)l * p.qk_ss, p.qk_rs, kb, S, dk, kd, tid);
-#pragma unroll
-        for (int i = 0; i < W::C_ITERS; ++i) {
-            const int c = tid + i * W::NT;
-            const int row = c / W::CCH, ch = c - row * W::CCH;
-            const int key = kb * W::BK + row;
-            const int col = col_base + ch * 8;
-            u32x4 v = {0u, 0u, 0u, 0u};   // keys past the sequence / columns past d_out are ZERO
-            if (key < S && col < p.dout) {
-                const uint16_t *r = cg + (int64_t)key * p.c_rs + (int64_t)l * p.c_ss;
-                v = VEC_C ? ld_global_16B(r + col) : ld_global_8x2B(r, col, p.dout);
-            }
-            creg[i] = v;
-        }
+        k_fetch<VEC_QK, W::BK, W::NT>(kreg, kg + (int64_t)l * p.qk_ss, p.qk_rs, kb * W::BK, S, dk, kd, tid);
+        c_fetch<VEC_C, W::NB, W::BK, W::NT>(creg, cg + (int64_t)l * p.c_ss, p.c_rs, kb * W::BK, S, col_base, p.dout, tid);
     };
     auto stash = [&](int buf) {
         char *kb_ = smem + buf * stage;
-        ld.stash(kb_, kd, tid);
-        char *cb_ = kb_ + ktile;
-#pragma unroll
-        for (int i = 0; i < W::C_ITERS; ++i) {
-            const int c = tid + i * W::NT;
-            const int row = c / W::CCH, ch = c - row * W::CCH;
-            lds_write_16B(cb_, v_lds_off<W::NB>(row, ch), creg[i]);
-        }
+        k_stash<W::BK, W::NT>(kreg, kb_, kd, tid);
+        c_stash<W::NB, W::BK, W::NT>(creg, kb_ + ktile, tid);
     };
 
     f32x16 acc[W::NB];
@@ -335,9 +296,7 @@ __global__ __launch_bounds__(256) void sense_mix_wide_kernel(const MixParams p) 
     for (int n = 0; n < W::NB; ++n)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[n][r] = 0.f;
-    const int c_row_lane = 4 * hh + ((lane & 15) >> 2);
-    const int c_ch_lane = ((lane >> 4) & 1) * 2 + ((lane & 3) >> 1);
-    const int c_sub = (lane & 1) * 8;
+    const TrLane tr = tr_lane(L);
     float lse2 = 0.f;
 
     fetch(0);
@@ -347,41 +306,25 @@ __global__ __launch_bounds__(256) void sense_mix_wide_kernel(const MixParams p) 
         const int cur = step & 1;
         const int l = step / nkb, kb = step - l * nkb;
         if (step + 1 < nsteps) fetch(step + 1);
-        const uint16_t *qrow = qg + (int64_t)min(my_q, S - 1) * p.qk_rs + (int64_t)l * p.qk_ss;
         if (kb == 0 && wave_has_rows) {   // new sense: my row's log-sum-exp (and its fragments, when they live in registers)
             lse2 = (my_q < S) ? p.lse[((int64_t)batch * p.nsenses + l) * p.lse_stride + my_q] * kLog2e : 0.f;
-            wide_load_q<VEC_QK, KDT>(qf, qrow, my_q < S, dk, hh);
+            load_q_frags<VEC_QK>(qf, qg + (int64_t)l * p.qk_ss, p.qk_rs, my_q, S, dk, hh);
         }
         if (wave_has_rows && kb <= my_last_kb) {
             const char *kbuf = smem + cur * stage;
             const char *cbuf = kbuf + ktile;
-            f32x16 st = wide_scores<ET, KDT>(kbuf, qf, kd, l31, hh);
+            f32x16 st = st_half_wide<ET>(kbuf, qf, kd, l31, hh);
             const int lim = my_q - kb * W::BK - 4 * hh;
             const float *kw = p.kw != nullptr ? p.kw + batch * p.kw_bs + (int64_t)l * p.kw_ss : nullptr;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int rel = (r & 3) + 8 * (r >> 2);
+                const int rel = st_key(0, r, 0);
                 float e = fast_exp2(fmaf(st[r], c2, -lse2));
                 if (rel > lim || my_q >= S) e = 0.f;
-                if (kw != nullptr) e *= kw[min(kb * W::BK + rel + 4 * hh, S - 1)];   // intervention hook
+                if (kw != nullptr) e *= kw[min(st_key(kb * W::BK, r, hh), S - 1)];   // intervention hook
                 st[r] = e;
             }
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                u32x4 pf;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) pf[i] = E::pack2(st[ks * 8 + 2 * i], st[ks * 8 + 2 * i + 1]);
-                const int row0 = ks * 16 + c_row_lane;
-#pragma unroll
-                for (int n = 0; n < W::NB; ++n)
-                    if (n < nb_live) {
-                        const int ch = n * 4 + c_ch_lane;
-                        const u32x2 lo = lds_read_tr16_8B(cbuf, v_lds_off<W::NB>(row0, ch) + c_sub);
-                        const u32x2 hi = lds_read_tr16_8B(cbuf, v_lds_off<W::NB>(row0 + 8, ch) + c_sub);
-                        const u32x4 a = {lo[0], lo[1], hi[0], hi[1]};
-                        acc[n] = E::mfma(a, pf, acc[n]);
-                    }
-            }
+            accumulate_pv<ET>(acc, st, cbuf, 0, tr, nb_live);
         }
         if (step + 1 < nsteps) stash(cur ^ 1);
         __syncthreads();
@@ -389,25 +332,7 @@ __global__ __launch_bounds__(256) void sense_mix_wide_kernel(const MixParams p) 
 
     if (!wave_has_rows || my_q >= S) return;
     uint16_t *og = reinterpret_cast<uint16_t *>(p.o) + batch * p.o_bs + (int64_t)my_q * p.o_rs;
-#pragma unroll
-    for (int n = 0; n < W::NB; ++n)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int col = col_base + n * 32 + 8 * g + 4 * hh;
-            const float x0 = acc[n][4 * g + 0], x1 = acc[n][4 * g + 1];
-            const float x2 = acc[n][4 * g + 2], x3 = acc[n][4 * g + 3];
-            if (VEC_C) {
-                if (col < p.dout) {
-                    u32x2 w = {E::pack2(x0, x1), E::pack2(x2, x3)};
-                    *reinterpret_cast<u32x2 *>(og + col) = w;
-                }
-            } else {
-                if (col + 0 < p.dout) og[col + 0] = E::from_float(x0);
-                if (col + 1 < p.dout) og[col + 1] = E::from_float(x1);
-                if (col + 2 < p.dout) og[col + 2] = E::from_float(x2);
-                if (col + 3 < p.dout) og[col + 3] = E::from_float(x3);
-            }
-        }
+    store_acc_row<ET, VEC_C>(og, acc, col_base, p.dout, hh);
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------
