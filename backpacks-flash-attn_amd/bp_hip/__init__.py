@@ -101,6 +101,7 @@ SIGNATURES = {
     'bp_row_extremes': (_i32, [_ptr] * 5 + [_i32] * 2 + [_i64] + [_i32] * 2 + [_ptr]),
     'bp_sense_attribute_ws_floats': (_i64, [_i32] * 2),
     'bp_sense_attribute': (_i32, [_ptr] * 9 + [_i64] + [_i32] * 7 + [_i64] + [_i64] * 14 + [_f32, _i32, _ptr]),
+    'bp_sense_similarity': (_i32, [_ptr] * 9 + [_i64] + [_i32] * 3 + [_i64] + [_i64] * 7 + [_i32, _ptr]),
 }
 
 
@@ -1512,3 +1513,69 @@ def sense_attribute(qk, table, row_index, query_sample, query_pos, vec, scale, w
           probs.stride(0) if probs is not None else 0, probs.stride(1) if probs is not None else 0,
           float(scale), _dtype_code(qk))
     return out, probs
+
+
+# ---- sense similarity on the device (C ABI bp_sense_similarity) -------------------------------------------------------------------------------------------------------
+
+SIMILARITY_MAX_QUERY_ROWS = 64
+SIMILARITY_OUTPUTS = ('flat', 'min_pair', 'max_pair', 'min_all', 'max_all', 'per_sense')
+
+
+def sense_similarity_supported(table, query):
+    """Whether bp_sense_similarity takes these operands: table (rows, k, d) and query (nq, k, d) 16-bit CUDA tensors of one
+    dtype in 16-byte friendly layouts, k a power of two <= 64, 1 <= nq and nq * k <= 64, d % 8 == 0 and 8 <= d <= 2048."""
+    if not (table.is_cuda and query.is_cuda) or table.dtype not in (torch.float16, torch.bfloat16) or query.dtype != table.dtype:
+        return False
+    if table.dim() != 3 or query.dim() != 3 or tuple(query.shape[1:]) != tuple(table.shape[1:]):
+        return False
+    rows, k, d = table.shape
+    nq = query.shape[0]
+    return (rows >= 1 and 1 <= k <= SENSE_DECODE_MAX_SENSES and k & (k - 1) == 0 and nq >= 1
+            and nq * k <= SIMILARITY_MAX_QUERY_ROWS and d % 8 == 0 and 8 <= d <= SENSE_DECODE_MAX_DOUT and _vec16(table, query))
+
+
+def sense_similarity(table, query, cand_index=None, want=SIMILARITY_OUTPUTS, out=None):
+    """The cosine measures of the sense vectors of nq query words against candidate words of `table`, in one launch that
+    reads every candidate's rows once (C ABI bp_sense_similarity, contract in include/bp_hip.h).  table (rows, k, d) and
+    query (nq, k, d) 16-bit; cand_index (ncand,) int32 on the device (clamped there, never read by the host) or None: the
+    candidates are rows 0 .. rows - 1.  Returns a dict over `want` (names of SIMILARITY_OUTPUTS): fp32 (nq, ncand) each --
+    'flat' the cosine of the concatenated senses, 'min_pair' / 'max_pair' over matched senses, 'min_all' / 'max_all' over all
+    sense pairs -- and 'per_sense' (nq, k, ncand), the cosine of every matched sense.  `out`: a dict of fp32 tensors of those
+    shapes with unit stride along the candidates (the (nq, ncand) ones sharing one query stride) to write into."""
+    _require_cuda(table, query, cand_index)
+    if table.dim() != 3 or query.dim() != 3 or tuple(query.shape[1:]) != tuple(table.shape[1:]) or query.dtype != table.dtype:
+        raise RuntimeError('bp_hip.sense_similarity: table must be (rows, k, d) and query (nq, k, d) of the same dtype')
+    rows, k, d = table.shape
+    nq = query.shape[0]
+    if cand_index is None:
+        ncand = rows
+    elif cand_index.dim() != 1 or cand_index.dtype != torch.int32 or not cand_index.is_contiguous():
+        raise RuntimeError('bp_hip.sense_similarity: cand_index must be a contiguous (ncand,) int32 tensor')
+    else:
+        ncand = cand_index.shape[0]
+    want = tuple(want)
+    if not want or any(w not in SIMILARITY_OUTPUTS for w in want):
+        raise RuntimeError(f'bp_hip.sense_similarity: want must name some of {SIMILARITY_OUTPUTS}')
+    res = {}
+    for name in want:
+        shape = (nq, k, ncand) if name == 'per_sense' else (nq, ncand)
+        if out is not None and out.get(name) is not None:
+            t = out[name]
+            _require_cuda(t)
+            if tuple(t.shape) != shape or t.dtype != torch.float32 or (ncand > 1 and t.stride(-1) != 1):
+                raise RuntimeError(f'bp_hip.sense_similarity: {name} must be float32 {shape} with unit stride along the candidates')
+            res[name] = t
+        else:
+            res[name] = torch.empty(shape, dtype=torch.float32, device=table.device)
+    pair = [res[n] for n in want if n != 'per_sense']
+    o_qs = max([ncand] + [t.stride(0) for t in pair]) if nq > 1 else ncand
+    if nq > 1 and any(t.stride(0) != o_qs for t in pair):
+        raise RuntimeError('bp_hip.sense_similarity: the (nq, ncand) outputs must share one query stride')
+    ps = res.get('per_sense')
+    ps_gs = ps.stride(1) if ps is not None and k > 1 else ncand
+    ps_qs = ps.stride(0) if ps is not None and nq > 1 else k * ps_gs
+    _call('bp_sense_similarity', table.device, table.data_ptr(), cand_index.data_ptr() if cand_index is not None else None,
+          query.data_ptr(), *[res[n].data_ptr() if n in res else None for n in SIMILARITY_OUTPUTS],
+          ncand, k, d, nq, rows, table.stride(0), table.stride(1), query.stride(0), query.stride(1), o_qs, ps_qs, ps_gs,
+          _dtype_code(table))
+    return res

@@ -1207,4 +1207,45 @@ int bp_sense_attribute(const void *qk, const void *table, const int32_t *row_ind
     return launch_status(bp::launch_sense_attribute(p, dtype, static_cast<hipStream_t>(stream)));
 }
 
+// ---- sense similarity (bp_sense_similarity) ----
+
+int bp_sense_similarity(const void *table, const int32_t *cand_index, const void *query,
+                        float *flat, float *min_pair, float *max_pair, float *min_all, float *max_all, float *per_sense,
+                        int64_t ncand, int nsenses, int d, int nq, int64_t table_rows,
+                        int64_t t_row_stride, int64_t t_sense_stride, int64_t q_query_stride, int64_t q_sense_stride,
+                        int64_t o_query_stride, int64_t ps_query_stride, int64_t ps_sense_stride,
+                        int dtype, bp_stream_t stream) {
+    if (dtype != BP_DTYPE_F16 && dtype != BP_DTYPE_BF16) return BP_ERR_DTYPE;
+    if (d < 1 || d % 8 != 0 || d > 2048) return BP_ERR_DOUT;
+    if (nsenses < 1 || nsenses > 64 || (nsenses & (nsenses - 1)) != 0) return BP_ERR_SHAPE;   // 1, 2, 4, ..., 64
+    if (nq < 1 || (int64_t)nq * nsenses > BP_SIMILARITY_MAX_QUERY_ROWS) return BP_ERR_SHAPE;
+    if (ncand < 0 || ncand > 0x7fffffffLL || table_rows < 1 || table_rows > 0x7fffffffLL) return BP_ERR_SHAPE;
+    if (flat == nullptr && min_pair == nullptr && max_pair == nullptr && min_all == nullptr && max_all == nullptr
+        && per_sense == nullptr)
+        return BP_ERR_SHAPE;
+    if (cand_index == nullptr && ncand > table_rows) return BP_ERR_SHAPE;
+    if (ncand == 0) return BP_OK;
+    if (table == nullptr || query == nullptr) return BP_ERR_SHAPE;
+    if (!aligned16({table, query})) return BP_ERR_SHAPE;
+    if (!strides8({t_row_stride, t_sense_stride, q_query_stride, q_sense_stride})) return BP_ERR_SHAPE;
+    for (const void *p4 : {(const void *)cand_index, (const void *)flat, (const void *)min_pair, (const void *)max_pair,
+                           (const void *)min_all, (const void *)max_all, (const void *)per_sense})
+        if (reinterpret_cast<uintptr_t>(p4) % 4) return BP_ERR_SHAPE;
+    const bool any_pair = flat != nullptr || min_pair != nullptr || max_pair != nullptr || min_all != nullptr || max_all != nullptr;
+    if (any_pair && o_query_stride < ncand) return BP_ERR_SHAPE;
+    // rows of different (query, sense) pairs do not overlap
+    if (per_sense != nullptr && (ps_sense_stride < ncand || (nq > 1 && ps_query_stride < nsenses * ps_sense_stride)))
+        return BP_ERR_SHAPE;
+    bp::SimilarityParams p{};
+    p.table = table; p.query = query; p.cand_index = cand_index;
+    p.flat = flat; p.min_pair = min_pair; p.max_pair = max_pair; p.min_all = min_all; p.max_all = max_all;
+    p.per_sense = per_sense;
+    p.t_rs = t_row_stride; p.t_gs = t_sense_stride; p.q_qs = q_query_stride; p.q_gs = q_sense_stride;
+    p.o_qs = o_query_stride; p.ps_qs = ps_query_stride; p.ps_gs = ps_sense_stride; p.table_rows = table_rows;
+    p.ncand = (int)ncand; p.groups = nsenses; p.d = d; p.nq = nq;
+    p.logk = 0;
+    while ((1 << p.logk) < nsenses) ++p.logk;
+    return launch_status(bp::launch_sense_similarity(p, dtype, static_cast<hipStream_t>(stream)));
+}
+
 }  // extern "C"

@@ -414,4 +414,17 @@ struct AttributeParams {
 };
 hipError_t launch_sense_attribute(const AttributeParams &p, int dtype, hipStream_t stream);
 
+// bp_sense_similarity (sense_similarity.hip): the cosine measures of nq query words' sense vectors against ncand candidate
+// words of the sense table -- cosines of matched senses, their min / max, min / max over all sense pairs, the flat cosine
+constexpr int kSimilarityMaxQueryRows = BP_SIMILARITY_MAX_QUERY_ROWS;
+struct SimilarityParams {
+    const void *table, *query;   // (table_rows, k, d) and (nq, k, d) 16-bit
+    const int32_t *cand_index;   // (ncand) or NULL: candidate c is row c
+    float *flat, *min_pair, *max_pair, *min_all, *max_all;   // (nq, ncand), query stride o_qs; any may be NULL
+    float *per_sense;            // (nq, k, ncand), strides ps_qs / ps_gs; may be NULL
+    int64_t t_rs, t_gs, q_qs, q_gs, o_qs, ps_qs, ps_gs, table_rows;
+    int ncand, groups, logk, d, nq;   // groups = k = 1 << logk
+};
+hipError_t launch_sense_similarity(const SimilarityParams &p, int dtype, hipStream_t stream);
+
 }  // namespace bp

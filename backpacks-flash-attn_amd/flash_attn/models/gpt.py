@@ -82,6 +82,8 @@ def _init_weights(module, n_layer, initializer_range=0.02, rescale_prenorm_resid
 
 def _pad_vocab(config):
     multiple = getattr(config, 'pad_vocab_size_multiple', 1)
+    if not hasattr(config, 'unpadded_vocab_size'):
+        config.unpadded_vocab_size = config.vocab_size   # the tokenizer's size: the embedding rows from here on are no words
     if config.vocab_size % multiple != 0:
         config.vocab_size += multiple - config.vocab_size % multiple
     return multiple

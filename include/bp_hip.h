@@ -54,7 +54,9 @@ extern "C" {
                               matrix, for the vocabulary projections of sense vectors;
                               and one more: bp_sense_attribute, the shares of every (position, sense) pair in a logit;
                               and one more: bp_add_layer_norm_chain, the inference-only forms of the fused add + LayerNorm
-                              -- a second branch input, x0 rebuilt from the embedding tables, residual written in place) */
+                              -- a second branch input, x0 rebuilt from the embedding tables, residual written in place;
+                              and one more: bp_sense_similarity, the cosine measures of sense vectors (lexical similarity,
+                              nearest words in sense space) in one pass over the sense table) */
 
 /* element type of q/k/v/out/content tensors */
 #define BP_DTYPE_F16 0
@@ -86,7 +88,9 @@ extern "C" {
 
 #define BP_ATTRIBUTE_MAX_VECS 4                /* bp_sense_attribute: fp32 vectors per query */
 
-#define BP_QUEUE_WS_BYTES 64   /* `queue_ws` of the persistent sense-mix launches */
+#define BP_SIMILARITY_MAX_QUERY_ROWS 64        /* bp_sense_similarity: nq * nsenses, the query rows of one call */
+
+#define BP_QUEUE_WS_BYTES 64  /* `queue_ws` of the persistent sense-mix launches */
 
 typedef void *bp_stream_t; /* a hipStream_t */
 
@@ -922,6 +926,48 @@ int bp_sense_attribute(const void *qk, const void *table, const int32_t *row_ind
                        int64_t o_query_stride, int64_t o_vec_stride, int64_t o_sense_stride,
                        int64_t p_query_stride, int64_t p_sense_stride,
                        float softmax_scale, int dtype, bp_stream_t stream);
+
+/*
+ * bp_sense_similarity -- the cosine measures of sense vectors between nq query words and ncand candidate words of the
+ * per-token sense table: the lexical-similarity measures of the reference's training/src/run_simlex.py:189-241 and the
+ * neighbour scores of training/src/visualize_sim.py:197-222, in ONE pass over the candidates' rows (each is read once per
+ * call, whatever nq is).  All arithmetic fp32.  For query n, candidate c, r = row(c):
+ *   g[l', l]   = sum_e query[n, l', e] * table[r, l, e]     products of 16-bit elements are exact; fp32 sums in a fixed order
+ *   A[l']      = sum_e query[n, l', e]^2,   B[l] = sum_e table[r, l, e]^2                          fixed order
+ *   cos[l', l] = g[l', l] / (sqrtf(A[l']) * sqrtf(B[l]))        the order of run_simlex.py:202-208: dot over the outer
+ *                                                               product of the norms; correctly rounded sqrtf and /
+ *   per_sense[n, l, c] = cos[l, l]                                                  CosSense_l  (:226-229)
+ *   min_pair / max_pair[n, c] = min / max over l of cos[l, l]                       MinPair / MaxPair  (:210-216)
+ *   min_all / max_all[n, c]   = min / max over all (l', l) of cos[l', l]            MinAll / MaxAll  (:218-224)
+ *   flat[n, c] = (sum_l g[l, l]) / (sqrtf(sum_l' A[l']) * sqrtf(sum_l B[l]))        Cos  (:194-200); sums ascending in l
+ * A zero vector gives 0 / 0 = NaN as in the reference, and a min / max measure whose set of cosines holds a NaN is NaN (the
+ * rule of torch.min / torch.max).  (Additive, ABI still 11.)
+ *   table        (table_rows, nsenses, d) fp16 / bf16, element strides t_row / t_sense (multiples of 8), 16-byte aligned
+ *                base, last stride 1: the rules of bp_sense_mix_gather.  Only read, and only the candidates' rows.
+ *   cand_index   device int32 (ncand), or NULL.  NULL: candidate c is row c (ncand <= table_rows).  Otherwise
+ *                row(c) = min(unsigned(cand_index[c]), table_rows - 1); the host never reads it, so one captured launch
+ *                serves any candidate list
+ *   query        (nq, nsenses, d) in the table's dtype, element strides q_query / q_sense (multiples of 8), 16-byte aligned
+ *                base, last stride 1; nq * nsenses <= BP_SIMILARITY_MAX_QUERY_ROWS
+ *   flat, min_pair, max_pair, min_all, max_all   fp32 (nq, ncand), ONE element stride o_query >= ncand between queries, unit
+ *                stride along the candidates
+ *   per_sense    fp32 (nq, nsenses, ncand), element strides ps_query / ps_sense (ps_sense >= ncand, ps_query >= nsenses *
+ *                ps_sense when nq > 1), unit stride along the candidates
+ *                Any of the six may be NULL (not written); all six NULL is BP_ERR_SHAPE.
+ *   nsenses      a power of two, 1 .. 64 (the reference's configurations: 1, 4, 16, 64); any other count is BP_ERR_SHAPE
+ * One launch, no workspace, no atomics, every reduction in a fixed order: two calls agree bit for bit.
+ * Errors, before any launch: BP_ERR_DTYPE; BP_ERR_DOUT (d < 1, d % 8 != 0 or d > 2048); BP_ERR_SHAPE (nsenses outside 1..64
+ * or no power of two, nq < 1, nq * nsenses > BP_SIMILARITY_MAX_QUERY_ROWS, ncand < 0 or > 2^31 - 1, table_rows < 1 or
+ * > 2^31 - 1, every output NULL, cand_index NULL with ncand > table_rows, a NULL table / query, a base that is not 16-byte
+ * aligned (table, query) or 4-byte aligned, a 16-bit stride that is no multiple of 8, an output stride too small).
+ * ncand == 0 is a successful no-op.
+ */
+int bp_sense_similarity(const void *table, const int32_t *cand_index, const void *query,
+                        float *flat, float *min_pair, float *max_pair, float *min_all, float *max_all, float *per_sense,
+                        int64_t ncand, int nsenses, int d, int nq, int64_t table_rows,
+                        int64_t t_row_stride, int64_t t_sense_stride, int64_t q_query_stride, int64_t q_sense_stride,
+                        int64_t o_query_stride, int64_t ps_query_stride, int64_t ps_sense_stride,
+                        int dtype, bp_stream_t stream);
 
 #ifdef __cplusplus
 }
