@@ -102,6 +102,7 @@ SIGNATURES = {
     'bp_sense_attribute_ws_floats': (_i64, [_i32] * 2),
     'bp_sense_attribute': (_i32, [_ptr] * 9 + [_i64] + [_i32] * 7 + [_i64] + [_i64] * 14 + [_f32, _i32, _ptr]),
     'bp_sense_similarity': (_i32, [_ptr] * 9 + [_i64] + [_i32] * 3 + [_i64] + [_i64] * 7 + [_i32, _ptr]),
+    'bp_score_rows': (_i32, [_ptr] * 7 + [_i64, _i32, _i32] + [_i64] * 3 + [_i32, _ptr]),
 }
 
 
@@ -1578,4 +1579,40 @@ def sense_similarity(table, query, cand_index=None, want=SIMILARITY_OUTPUTS, out
           query.data_ptr(), *[res[n].data_ptr() if n in res else None for n in SIMILARITY_OUTPUTS],
           ncand, k, d, nq, rows, table.stride(0), table.stride(1), query.stride(0), query.stride(1), o_qs, ps_qs, ps_gs,
           _dtype_code(table))
+    return res
+
+
+# ---- row scoring on the device (C ABI bp_score_rows) ------------------------------------------------------------------------------------------------------------------
+
+SCORE_MAX_TARGETS = 8
+SCORE_OUTPUTS = ('logprob', 'rank', 'lse', 'top1', 'entropy')
+_SCORE_DTYPES = {'logprob': torch.float32, 'rank': torch.int32, 'lse': torch.float32, 'top1': torch.int32, 'entropy': torch.float32}
+
+
+def score_rows(logits, targets, want=SCORE_OUTPUTS):
+    """What an evaluation keeps of every row of `logits` (rows, cols) fp16 / bf16 / fp32 (any row stride, unit last stride),
+    in one launch that reads the row once (C ABI bp_score_rows, contract in include/bp_hip.h).  targets: int64 (rows,) or
+    (rows, M), 1 <= M <= 8; a target outside [0, cols) (an ignore_index) scores logprob 0 and rank -1.  Returns a dict over
+    `want` (names of SCORE_OUTPUTS): 'logprob' fp32 and 'rank' int32 in the shape of `targets` (0-based, ties towards the lower
+    id), 'lse' fp32, 'top1' int32 (the greedy token of pick_token) and 'entropy' fp32, (rows,) each."""
+    _require_cuda(logits, targets)
+    want = tuple(want)
+    if not want or any(w not in SCORE_OUTPUTS for w in want):
+        raise RuntimeError(f'bp_hip.score_rows: want must name some of {SCORE_OUTPUTS}')
+    if logits.dim() != 2 or logits.dtype not in _PICK_DTYPES or logits.shape[1] < 1 or logits.stride(1) != 1:
+        raise RuntimeError('bp_hip.score_rows: logits must be (rows, cols) fp16 / bf16 / fp32 with a contiguous last dimension')
+    rows, cols = logits.shape
+    if targets.dim() not in (1, 2) or targets.shape[0] != rows or targets.dtype != torch.int64:
+        raise RuntimeError('bp_hip.score_rows: targets must be int64 (rows,) or (rows, M)')
+    flat = targets.reshape(rows, -1).contiguous()
+    m = flat.shape[1]
+    if not 1 <= m <= SCORE_MAX_TARGETS:
+        raise RuntimeError(f'bp_hip.score_rows: 1 .. {SCORE_MAX_TARGETS} targets per row, got {m}')
+    res = {n: torch.empty(tuple(targets.shape) if n in ('logprob', 'rank') else (rows,), dtype=_SCORE_DTYPES[n], device=logits.device)
+           for n in want}
+    if rows == 0:
+        return res
+    _call('bp_score_rows', logits.device, logits.data_ptr(), flat.data_ptr(),
+          *[res[n].data_ptr() if n in res else None for n in SCORE_OUTPUTS],
+          rows, cols, m, logits.stride(0) if rows > 1 else max(cols, logits.stride(0)), m, m, _PICK_DTYPES[logits.dtype])
     return res

@@ -1248,4 +1248,26 @@ int bp_sense_similarity(const void *table, const int32_t *cand_index, const void
     return launch_status(bp::launch_sense_similarity(p, dtype, static_cast<hipStream_t>(stream)));
 }
 
+// ---- row scoring (bp_score_rows) ----
+
+int bp_score_rows(const void *logits, const int64_t *targets, float *logprob, int32_t *rank, float *lse, int32_t *top1,
+                  float *entropy, int64_t rows, int cols, int ntargets, int64_t row_stride, int64_t target_stride,
+                  int64_t out_stride, int dtype, bp_stream_t stream) {
+    if (dtype != BP_DTYPE_F16 && dtype != BP_DTYPE_BF16 && dtype != BP_DTYPE_F32) return BP_ERR_DTYPE;
+    if (rows <= 0 || rows > 0x7fffffffLL || cols <= 0 || cols > 0x7fffffff - 16 || row_stride < cols) return BP_ERR_SHAPE;
+    if (ntargets < 1 || ntargets > BP_SCORE_MAX_TARGETS || target_stride < ntargets) return BP_ERR_SHAPE;
+    if (logits == nullptr || targets == nullptr) return BP_ERR_SHAPE;
+    if (logprob == nullptr && rank == nullptr && lse == nullptr && top1 == nullptr && entropy == nullptr) return BP_ERR_SHAPE;
+    if ((logprob != nullptr || rank != nullptr) && out_stride < ntargets) return BP_ERR_SHAPE;
+    const uintptr_t elem = dtype == BP_DTYPE_F32 ? 4 : 2;
+    if (reinterpret_cast<uintptr_t>(logits) % elem || reinterpret_cast<uintptr_t>(targets) % 8) return BP_ERR_SHAPE;
+    for (const void *p4 : {(const void *)logprob, (const void *)rank, (const void *)lse, (const void *)top1, (const void *)entropy})
+        if (reinterpret_cast<uintptr_t>(p4) % 4) return BP_ERR_SHAPE;
+    bp::ScoreParams p{};
+    p.logits = logits; p.targets = targets; p.logprob = logprob; p.rank = rank; p.lse = lse; p.top1 = top1; p.entropy = entropy;
+    p.rows = rows; p.row_stride = row_stride; p.target_stride = target_stride; p.out_stride = out_stride;
+    p.cols = cols; p.ntargets = ntargets;
+    return launch_status(bp::launch_score_rows(p, dtype, static_cast<hipStream_t>(stream)));
+}
+
 }  // extern "C"

@@ -427,4 +427,19 @@ struct SimilarityParams {
 };
 hipError_t launch_sense_similarity(const SimilarityParams &p, int dtype, hipStream_t stream);
 
+// bp_score_rows (score_rows.hip): per row of logits, the log-sum-exp, the entropy, the greedy token, and the log-probability and
+// rank of up to kScoreMaxTargets target columns, in one pass over the row
+constexpr int kScoreMaxTargets = BP_SCORE_MAX_TARGETS;
+struct ScoreParams {
+    const void *logits;          // (rows, cols) 16-bit or fp32, element stride row_stride, last stride 1; only read
+    const int64_t *targets;      // (rows, ntargets), element stride target_stride between rows
+    float *logprob;              // (rows, ntargets), element stride out_stride between rows; any output may be NULL
+    int32_t *rank;               // (rows, ntargets), the same stride
+    float *lse, *entropy;        // (rows) dense
+    int32_t *top1;               // (rows) dense
+    int64_t rows, row_stride, target_stride, out_stride;
+    int cols, ntargets;
+};
+hipError_t launch_score_rows(const ScoreParams &p, int dtype, hipStream_t stream);
+
 }  // namespace bp

@@ -289,3 +289,38 @@ class ReplacedWordLMHeadModel(_Intervened):
         if t.fused_senses and content.transpose(1, 2).stride(-1) != 1:
             content = content.contiguous()
         return self._mix(t, hidden, content)
+
+
+class ScaledSenseLMHeadModel(_Intervened):
+    """One sense of the listed words scaled by `percent` wherever they occur: the counterfactual of the reference's gender-bias
+    experiment (training/src/test_genderbias.py:71-78, compute_counterfactual: `contextualization[0, sense_index, :, j] *=
+    percent` for every position j whose token is one of `word_ids`).  The key weights are `percent` at (sense_index, those
+    positions) and 1 elsewhere, so on the HIP path the contraction stays one bp_sense_mix_weighted launch.  percent = 1 is
+    the wrapped network.  Full forward only: `inference_params` raises (read the result with src/utils/scoring.py:candidate_probs)."""
+
+    def __init__(self, backpack_network, word_ids, sense_index, percent):
+        super().__init__()
+        self.backpack_network = backpack_network
+        self.word_ids = [int(w) for w in (word_ids.tolist() if torch.is_tensor(word_ids) else word_ids)]
+        self.sense_index = int(sense_index)
+        self.percent = float(percent)
+        k = backpack_network.transformer.num_content_vectors
+        if not 0 <= self.sense_index < k:
+            raise ValueError(f'sense_index {sense_index} outside the {k} senses of the network')
+
+    def forward(self, input_ids, position_ids=None, inference_params=None):
+        if inference_params is not None:
+            raise NotImplementedError('ScaledSenseLMHeadModel has no KV-cached decoding: it is a full-forward readout')
+        return super().forward(input_ids, position_ids, None)
+
+    def key_weight(self, input_ids, nsenses):
+        """(B,k,S) fp32: `percent` at (sense_index, positions holding one of word_ids), 1 elsewhere."""
+        words = torch.as_tensor(self.word_ids, dtype=input_ids.dtype, device=input_ids.device)
+        hit = (input_ids.unsqueeze(-1) == words).any(dim=-1)                       # (B,S)
+        weight = torch.ones(input_ids.shape[0], nsenses, input_ids.shape[1], dtype=torch.float32, device=input_ids.device)
+        weight[:, self.sense_index] = torch.where(hit, self.percent, 1.0)
+        return weight
+
+    def _mixed(self, input_ids, position_ids):
+        t, hidden, content = self._stages(input_ids, position_ids)
+        return self._mix(t, hidden, content, self.key_weight(input_ids, content.shape[1]))

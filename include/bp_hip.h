@@ -56,7 +56,9 @@ extern "C" {
                               and one more: bp_add_layer_norm_chain, the inference-only forms of the fused add + LayerNorm
                               -- a second branch input, x0 rebuilt from the embedding tables, residual written in place;
                               and one more: bp_sense_similarity, the cosine measures of sense vectors (lexical similarity,
-                              nearest words in sense space) in one pass over the sense table) */
+                              nearest words in sense space) in one pass over the sense table;
+                              and one more: bp_score_rows, what an evaluation keeps of a row of logits -- log-probability and
+                              rank of the gold token, log-sum-exp, greedy token, entropy -- in one pass over the row) */
 
 /* element type of q/k/v/out/content tensors */
 #define BP_DTYPE_F16 0
@@ -89,6 +91,8 @@ extern "C" {
 #define BP_ATTRIBUTE_MAX_VECS 4                /* bp_sense_attribute: fp32 vectors per query */
 
 #define BP_SIMILARITY_MAX_QUERY_ROWS 64        /* bp_sense_similarity: nq * nsenses, the query rows of one call */
+
+#define BP_SCORE_MAX_TARGETS 8                 /* bp_score_rows: target columns per row */
 
 #define BP_QUEUE_WS_BYTES 64  /* `queue_ws` of the persistent sense-mix launches */
 
@@ -968,6 +972,46 @@ int bp_sense_similarity(const void *table, const int32_t *cand_index, const void
                         int64_t t_row_stride, int64_t t_sense_stride, int64_t q_query_stride, int64_t q_sense_stride,
                         int64_t o_query_stride, int64_t ps_query_stride, int64_t ps_sense_stride,
                         int dtype, bp_stream_t stream);
+
+/*
+ * bp_score_rows -- what an evaluation keeps of a row of logits, in ONE pass over the row: the log-probability and the rank
+ * of up to BP_SCORE_MAX_TARGETS target columns, the log-sum-exp, the greedy token and the predictive entropy.  Replaces the
+ * torch composition behind the reference's evaluation (training/src/metrics/perplexity.py, accuracy.py, tasks/seq.py; the
+ * p(' he') / p(' she') readout of training/src/test_genderbias.py:187-203): an fp32 log_softmax over (tokens, vocab) -- the
+ * full-logits tensor at twice its size -- a gather, an argmax, a comparison count and an entropy pass.  bp_xentropy_fwd reads
+ * the same bytes and keeps two floats of them.  (Additive, ABI still 11.)
+ * Per row, with x_j = float(logits[row, j]), all arithmetic fp32:
+ *   lse         = log sum_j exp(x_j), evaluated as m + log sum_j exp(x_j - m), m = max_j x_j
+ *   logprob[i]  = x_t - lse                         t = targets[row, i] in [0, cols)
+ *   rank[i]     = #{j : x_j > x_t} + #{j < t : x_j == x_t}    0-based, ties towards the lower id; comparisons of the converted
+ *                 floats (-0 == +0), so an exact integer.  A NaN compares false both ways: a NaN entry precedes nothing, and
+ *                 the rank of a NaN target is 0.
+ *   t outside [0, cols) (an ignore_index, as bp_xentropy_fwd treats it): logprob[i] = 0, rank[i] = -1
+ *   top1        = the greedy answer of bp_pick_token (do_sample == 0): the lowest index of the maximum, a NaN counting as
+ *                 larger than every number (-0 == +0).  On a NaN-free row, rank[i] == 0 <=> top1 == t.
+ *   entropy     = lse - (sum_j exp(x_j - m) x_j) / (sum_j exp(x_j - m)); a -inf entry contributes 0 to both sums, not a NaN
+ * Degenerate rows follow the arithmetic of the definitions in the extended reals:
+ *   a NaN anywhere      lse = entropy = NaN, every logprob NaN
+ *   a +inf entry        lse = +inf, entropy = NaN (exp(inf - inf)); logprob = x_t - inf: -inf, or NaN for a +inf target
+ *   no finite entry, all -inf   lse = -inf, entropy = NaN; logprob = -inf - -inf = NaN
+ * ranks and top1 are defined by comparisons alone and hold on every row.
+ *   logits   (rows, cols) fp16 / bf16 / fp32, element stride row_stride >= cols between rows, last stride 1; a row may start
+ *            at any element (2- / 4-byte alignment): the elements in front of the first 16-byte boundary and behind the last are
+ *            read one by one.  Only read.
+ *   targets  int64 (rows, ntargets), element stride target_stride >= ntargets between rows; 1 <= ntargets <=
+ *            BP_SCORE_MAX_TARGETS.  Repeated targets are fine.
+ *   logprob  fp32 and  rank  int32, (rows, ntargets) with ONE element stride out_stride >= ntargets between rows
+ *   lse, entropy  fp32 (rows);  top1  int32 (rows)
+ *            Any of the five may be NULL (not written); all five NULL is BP_ERR_SHAPE.
+ * One 256-thread workgroup per row, one launch, no workspace, no atomics, every reduction in a fixed order: two calls agree
+ * bit for bit.  ntargets == 1 is a kernel of its own.
+ * Errors, before any launch: BP_ERR_DTYPE; BP_ERR_SHAPE (rows <= 0 or > 2^31 - 1, cols <= 0 or > 2^31 - 17, row_stride < cols,
+ * ntargets outside 1 .. BP_SCORE_MAX_TARGETS, target_stride < ntargets, a NULL logits / targets, every output NULL, out_stride <
+ * ntargets with a logprob or rank, logits not aligned to its element, targets not 8-byte or an output not 4-byte aligned).
+ */
+int bp_score_rows(const void *logits, const int64_t *targets, float *logprob, int32_t *rank, float *lse, int32_t *top1,
+                  float *entropy, int64_t rows, int cols, int ntargets, int64_t row_stride, int64_t target_stride,
+                  int64_t out_stride, int dtype, bp_stream_t stream);
 
 #ifdef __cplusplus
 }
