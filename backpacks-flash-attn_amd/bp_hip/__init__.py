@@ -66,6 +66,9 @@ SIGNATURES = {
     'bp_sense_mix': (_i32, [_ptr] * 4 + [_i32] * 6 + [_i64] * 9 + [_f32, _i32, _ptr, _ptr]),
     'bp_sense_mix_weighted': (_i32, [_ptr] * 5 + [_i32] * 6 + [_i64] * 11 + [_f32, _i32, _ptr, _ptr]),
     'bp_sense_mix_gather': (_i32, [_ptr] * 5 + [_i32] * 6 + [_i64] * 10 + [_f32, _i32, _ptr, _ptr]),
+    'bp_sense_lse_varlen': (_i32, [_ptr] * 3 + [_i32] * 4 + [_i64] * 3 + [_f32, _i32, _ptr]),
+    'bp_sense_mix_varlen': (_i32, [_ptr] * 4 + [_i32, _ptr] + [_i32] * 5 + [_i64] * 6 + [_f32, _i32, _ptr, _ptr]),
+    'bp_sense_mix_gather_varlen': (_i32, [_ptr] * 5 + [_i32, _ptr] + [_i32] * 5 + [_i64] * 7 + [_f32, _i32, _ptr, _ptr]),
     'bp_sense_mix_dc': (_i32, [_ptr] * 4 + [_i32] * 5 + [_i64] * 9 + [_f32, _i32, _ptr, _ptr]),
     'bp_sense_dq_dk': (_i32, [_ptr] * 6 + [_i32] * 5 + [_i64] * 11 + [_f32, _i32, _ptr]),
     'bp_add_layer_norm': (_i32, [_ptr] * 6 + [_i64, _i32, _f32] + [_i32] * 4 + [_ptr]),
@@ -508,6 +511,126 @@ def sense_mix_gather(qk, table, row_index, softmax_scale=None, out=None, lse=Non
           qk.stride(0), qk.stride(1), qk.stride(2), qk.stride(3),
           table.stride(0), table.stride(1), row_index.stride(0),
           out.stride(0), out.stride(1), float(scale), _dtype_code(qk), queue_ws.data_ptr())
+    return out
+
+
+# ---- packed batches (C ABI bp_sense_*_varlen): sample b owns rows [cu_seqlens[b], cu_seqlens[b + 1]) -----------------------
+
+def _check_packed_qk(qk, cu_seqlens, max_seqlen, who):
+    _require_cuda(qk, cu_seqlens)
+    if qk.dim() != 4 or qk.shape[1] != 2 or qk.stride(-1) != 1:
+        raise RuntimeError(f'bp_hip.{who}: qk must be (total, 2, k, d_k) with a contiguous last dim')
+    if cu_seqlens.dim() != 1 or cu_seqlens.numel() < 2 or cu_seqlens.dtype != torch.int32 or not cu_seqlens.is_contiguous():
+        raise RuntimeError(f'bp_hip.{who}: cu_seqlens must be a contiguous (batch + 1,) int32 tensor')
+    if int(max_seqlen) < 1:
+        raise RuntimeError(f'bp_hip.{who}: max_seqlen must be >= 1')
+    return qk.shape[0], cu_seqlens.numel() - 1, qk.shape[2], qk.shape[3]
+
+
+def _varlen_limits(qk, values, max_seqlen, gather):
+    """(exceeded, reason) of every limit of bp_sense_mix_varlen / bp_sense_mix_gather_varlen (include/bp_hip.h): narrow senses
+    on the 16-byte vector path; the gathering form (`values` = the table) additionally bp_sense_mix_gather's own limits."""
+    rows = values.shape[0]
+    return (
+        (qk.shape[-1] > 128, f'sense width {qk.shape[-1]} > 128 (no packed wide kernels)'),
+        (qk.shape[-1] % 8 != 0, f'sense width {qk.shape[-1]} not a multiple of 8'),
+        (not (qk.is_cuda and values.is_cuda), 'qk or content not on the GPU'),
+        (qk.dtype not in (torch.float16, torch.bfloat16), f'dtype {qk.dtype} (fp16 / bf16 only)'),
+        (not _vec16(qk), 'qk layout (16-byte aligned rows required)'),
+        (values.dim() != 3 or values.shape[2] % 8 != 0 or not _vec16(values),
+         'content / table layout (last dim contiguous, 16-byte aligned rows, d % 8 == 0 required)'),
+        (max_seqlen > 65536, f'max_seqlen {max_seqlen} > 65536'),
+        (gather and max_seqlen > 4096, f'max_seqlen {max_seqlen} > 4096 (a job keeps its keys\' row indices in LDS)'),
+        (gather and rows > 65536, f'{rows} table rows > 65536 (u16 row indices)'),
+        (gather and rows * values.stride(0) * values.element_size() >= 2 ** 32, 'table of 4 GiB or more (32-bit byte offsets)'),
+    )
+
+
+def sense_mix_varlen_supported(qk, content, max_seqlen):
+    """Shapes bp_sense_mix_varlen takes (qk (total, 2, k, d_k), content (total, k, d_out))."""
+    return not any(exceeded for exceeded, _ in _varlen_limits(qk, content, max_seqlen, False))
+
+
+def sense_mix_varlen_limits(qk, content, max_seqlen):
+    """Which limits of bp_sense_mix_varlen a call exceeds, as text (callers name it when they pad the batch instead)."""
+    return '; '.join(reason for exceeded, reason in _varlen_limits(qk, content, max_seqlen, False) if exceeded)
+
+
+def sense_mix_gather_varlen_supported(qk, table, max_seqlen):
+    """Shapes bp_sense_mix_gather_varlen takes (qk (total, 2, k, d_k), table (rows, k, d_out))."""
+    return not any(exceeded for exceeded, _ in _varlen_limits(qk, table, max_seqlen, True))
+
+
+def sense_mix_gather_varlen_limits(qk, table, max_seqlen):
+    """Which limits of bp_sense_mix_gather_varlen a call exceeds, as text."""
+    return '; '.join(reason for exceeded, reason in _varlen_limits(qk, table, max_seqlen, True) if exceeded)
+
+
+def sense_lse_varlen(qk, cu_seqlens, max_seqlen, softmax_scale=None):
+    """qk (total,2,k,d_k), cu_seqlens (B+1,) int32 -> lse (B,k,roundup(max_seqlen,16)) fp32: log-sum-exp of every causal row
+    of every sequence of the packed batch; entries at or behind a sequence's length are not written.  cu_seqlens is not
+    validated (include/bp_hip.h); src/utils/packing.py builds checked ones."""
+    total, b, k, dk = _check_packed_qk(qk, cu_seqlens, max_seqlen, 'sense_lse_varlen')
+    scale = softmax_scale or dk ** -0.5
+    lse = torch.empty((b, k, round_up(int(max_seqlen), 16)), dtype=torch.float32, device=qk.device)
+    _call('bp_sense_lse_varlen', qk.device, qk.data_ptr(), lse.data_ptr(), cu_seqlens.data_ptr(), b, int(max_seqlen), k, dk,
+          qk.stride(0), qk.stride(1), qk.stride(2), float(scale), _dtype_code(qk))
+    return lse
+
+
+def _packed_out_lse(who, qk, total, b, k, max_seqlen, dout, out, lse):
+    if out is None:
+        out = torch.empty((total, dout), dtype=qk.dtype, device=qk.device)
+    elif out.shape != (total, dout) or out.dtype != qk.dtype or out.stride(-1) != 1 or not out.is_cuda:
+        raise RuntimeError(f'bp_hip.{who}: out must be (total, d_out) in qk\'s dtype on the GPU, last dim contiguous')
+    ws, ready = _lse_ws(qk, lse, b, int(max_seqlen), k)
+    return out, ws, ready
+
+
+def sense_mix_varlen(qk, content, cu_seqlens, max_seqlen, softmax_scale=None, out=None, lse=None):
+    """sense_mix on a packed batch: qk (total,2,k,d_k), content (total,k,d_out), cu_seqlens (B+1,) int32 -> (total,d_out).
+    Every sequence attends causally within its own rows; its output rows carry the bits of sense_mix on that sequence
+    alone.  `lse`: optional result of sense_lse_varlen.  Narrow senses on the 16-byte path only
+    (sense_mix_varlen_supported; C ABI bp_sense_mix_varlen)."""
+    total, b, k, dk = _check_packed_qk(qk, cu_seqlens, max_seqlen, 'sense_mix_varlen')
+    _require_cuda(content)
+    if content.dim() != 3 or content.shape[:2] != (total, k) or content.stride(-1) != 1:
+        raise RuntimeError('bp_hip.sense_mix_varlen: content must be (total, k, d_out), last dim contiguous')
+    if content.dtype != qk.dtype:
+        raise RuntimeError('bp_hip.sense_mix_varlen: qk and content dtypes differ')
+    scale = softmax_scale or dk ** -0.5
+    dout = content.shape[2]
+    out, ws, ready = _packed_out_lse('sense_mix_varlen', qk, total, b, k, max_seqlen, dout, out, lse)
+    queue_ws = _queue_ws(qk.device)   # alive until the launch call has returned
+    _call('bp_sense_mix_varlen', qk.device,
+          qk.data_ptr(), content.data_ptr(), out.data_ptr(), ws.data_ptr(), ready,
+          cu_seqlens.data_ptr(), b, int(max_seqlen), k, dk, dout,
+          qk.stride(0), qk.stride(1), qk.stride(2), content.stride(0), content.stride(1), out.stride(0),
+          float(scale), _dtype_code(qk), queue_ws.data_ptr())
+    return out
+
+
+def sense_mix_gather_varlen(qk, table, row_index, cu_seqlens, max_seqlen, softmax_scale=None, out=None, lse=None):
+    """sense_mix_gather on a packed batch: content[t, l, :] = table[row_index[t], l, :] for the packed row t.
+    qk (total,2,k,d_k), table (rows,k,d_out), row_index (total,) int32 -> (total,d_out)
+    (sense_mix_gather_varlen_supported; C ABI bp_sense_mix_gather_varlen)."""
+    total, b, k, dk = _check_packed_qk(qk, cu_seqlens, max_seqlen, 'sense_mix_gather_varlen')
+    _require_cuda(table, row_index)
+    if table.dim() != 3 or table.shape[1] != k or table.stride(-1) != 1:
+        raise RuntimeError('bp_hip.sense_mix_gather_varlen: table must be (rows, k, d_out), last dim contiguous')
+    if table.dtype != qk.dtype:
+        raise RuntimeError('bp_hip.sense_mix_gather_varlen: qk and table dtypes differ')
+    if row_index.shape != (total,) or row_index.dtype != torch.int32 or row_index.stride(-1) != 1:
+        raise RuntimeError('bp_hip.sense_mix_gather_varlen: row_index must be (total,) int32, unit stride')
+    scale = softmax_scale or dk ** -0.5
+    dout = table.shape[2]
+    out, ws, ready = _packed_out_lse('sense_mix_gather_varlen', qk, total, b, k, max_seqlen, dout, out, lse)
+    queue_ws = _queue_ws(qk.device)   # alive until the launch call has returned
+    _call('bp_sense_mix_gather_varlen', qk.device,
+          qk.data_ptr(), table.data_ptr(), row_index.data_ptr(), out.data_ptr(), ws.data_ptr(), ready,
+          cu_seqlens.data_ptr(), b, int(max_seqlen), k, dk, dout, table.shape[0],
+          qk.stride(0), qk.stride(1), qk.stride(2), table.stride(0), table.stride(1), out.stride(0),
+          float(scale), _dtype_code(qk), queue_ws.data_ptr())
     return out
 
 

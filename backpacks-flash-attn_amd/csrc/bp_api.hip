@@ -425,6 +425,107 @@ int bp_sense_mix_gather(const void *qk, const void *table, const int32_t *row_in
     return launch_status(wide ? bp::launch_sense_mix_wide_dma(p, dtype, st) : bp::launch_sense_mix_dma(p, dtype, st));
 }
 
+// ---- packed batches: sample b owns rows [cu_seqlens[b], cu_seqlens[b + 1]) of (total, ...) operands -----------------------
+// Narrow senses on the 16-byte path only (the ring kernels); cu_seqlens is never read on the host.
+namespace {
+
+// what the three packed entry points share: dtype, sense width, the qk layout.  BP_OK or the refusal.
+int varlen_qk_args(const void *qk, const int32_t *cu_seqlens, int batch, int max_seqlen, int nsenses, int d_k,
+                   int64_t qk_rs, int64_t qk_two, int64_t qk_ss, float softmax_scale, int dtype) {
+    if (dtype != BP_DTYPE_F16 && dtype != BP_DTYPE_BF16) return BP_ERR_DTYPE;
+    if (d_k < 8 || d_k > 128 || d_k % 8 != 0) return BP_ERR_HEAD_DIM;
+    if (batch <= 0 || nsenses <= 0 || max_seqlen <= 0) return BP_ERR_SHAPE;
+    if (qk == nullptr || cu_seqlens == nullptr) return BP_ERR_SHAPE;
+    if (!scale_ok(softmax_scale)) return BP_ERR_SCALE;
+    if (!qk_vec16(d_k, static_cast<const uint16_t *>(qk), qk_two, 0, qk_rs, qk_ss)) return BP_ERR_SHAPE;
+    return BP_OK;
+}
+
+// the flash ring kernel in LSE-only mode with the senses as heads, sequences from cu_seqlens (as the trunk's ragged calls)
+int sense_lse_varlen(const void *qk, float *lse_ws, const int32_t *cu_seqlens, int batch, int max_seqlen, int nsenses,
+                     int d_k, int64_t qk_rs, int64_t qk_two, int64_t qk_ss, float softmax_scale, int dtype,
+                     hipStream_t stream) {
+    const uint16_t *qp = static_cast<const uint16_t *>(qk);
+    bp::FlashParams p{};
+    p.q = qp; p.k = qp + qk_two; p.v = nullptr; p.o = nullptr; p.lse = lse_ws;
+    p.cu_q = cu_seqlens; p.cu_k = cu_seqlens;
+    p.q_rs = qk_rs; p.q_hs = qk_ss; p.k_rs = qk_rs; p.k_hs = qk_ss;
+    p.lse_stride = round_up(max_seqlen, 16);
+    p.b = batch; p.h = nsenses; p.d = d_k;
+    p.max_sq = max_seqlen; p.max_sk = max_seqlen;
+    p.n_qtiles = (max_seqlen + 127) / 128;
+    p.causal = 1;
+    p.pair = p.n_qtiles > 1 ? 1 : 0;
+    p.scale_log2e = softmax_scale * bp::kLog2e;
+    return launch_status(bp::launch_flash_fwd_dma(p, dtype, stream));
+}
+
+int sense_mix_varlen(const void *qk, const void *content, bool gather, const int32_t *row_index, void *out, float *lse_ws,
+                     int lse_ready, const int32_t *cu_seqlens, int batch, int max_seqlen, int nsenses, int d_k, int d_out,
+                     int64_t table_rows, int64_t qk_rs, int64_t qk_two, int64_t qk_ss, int64_t c_rs, int64_t c_ss,
+                     int64_t o_rs, float softmax_scale, int dtype, void *queue_ws, bp_stream_t stream) {
+    if (dtype != BP_DTYPE_F16 && dtype != BP_DTYPE_BF16) return BP_ERR_DTYPE;
+    if (d_k < 8 || d_k > 128 || d_k % 8 != 0) return BP_ERR_HEAD_DIM;
+    if (queue_ws != nullptr && !aligned16(queue_ws)) return BP_ERR_SHAPE;
+    if (d_out < 8 || d_out % 8 != 0) return BP_ERR_DOUT;
+    if (max_seqlen > bp::kMixMaxTiles * 256) return BP_ERR_SHAPE;
+    if (gather && (max_seqlen > bp::kMixGatherMaxKeys || table_rows <= 0 || table_rows > bp::kMixGatherMaxRows ||
+                   row_index == nullptr))
+        return BP_ERR_SHAPE;
+    if (content == nullptr || out == nullptr || lse_ws == nullptr) return BP_ERR_SHAPE;
+    const int rc = varlen_qk_args(qk, cu_seqlens, batch, max_seqlen, nsenses, d_k, qk_rs, qk_two, qk_ss, softmax_scale, dtype);
+    if (rc != BP_OK) return rc;
+    if (!aligned16({content, out}) || !strides8({c_rs, c_ss, o_rs})) return BP_ERR_SHAPE;
+    if (gather && (c_rs <= 0 || table_rows * c_rs * 2 >= (int64_t(1) << 32))) return BP_ERR_SHAPE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (null_queue_ws_on_capturing_stream(queue_ws, st)) return BP_ERR_QUEUE_WS;
+    if (!lse_ready) {
+        const int lse_rc = sense_lse_varlen(qk, lse_ws, cu_seqlens, batch, max_seqlen, nsenses, d_k, qk_rs, qk_two, qk_ss,
+                                            softmax_scale, dtype, st);
+        if (lse_rc != BP_OK) return lse_rc;
+    }
+    bp::MixParams p = mix_params(qk, content, out, lse_ws, batch, max_seqlen, nsenses, d_k, d_out, 0, qk_rs, qk_two, qk_ss,
+                                 0, c_rs, c_ss, 0, o_rs, softmax_scale, queue_ws);
+    p.cu = cu_seqlens;
+    if (gather) { p.row_index = row_index; p.last_table_row = (uint32_t)(table_rows - 1); }
+    return launch_status(bp::launch_sense_mix_varlen(p, dtype, st));
+}
+
+}  // namespace
+
+int bp_sense_lse_varlen(const void *qk, float *lse, const int32_t *cu_seqlens, int batch, int max_seqlen, int nsenses,
+                        int d_k, int64_t qk_row_stride, int64_t qk_two_stride, int64_t qk_sense_stride,
+                        float softmax_scale, int dtype, bp_stream_t stream) {
+    const int rc = varlen_qk_args(qk, cu_seqlens, batch, max_seqlen, nsenses, d_k, qk_row_stride, qk_two_stride,
+                                  qk_sense_stride, softmax_scale, dtype);
+    if (rc != BP_OK) return rc;
+    if (lse == nullptr) return BP_ERR_SHAPE;
+    return sense_lse_varlen(qk, lse, cu_seqlens, batch, max_seqlen, nsenses, d_k, qk_row_stride, qk_two_stride,
+                            qk_sense_stride, softmax_scale, dtype, static_cast<hipStream_t>(stream));
+}
+
+int bp_sense_mix_varlen(const void *qk, const void *content, void *out, float *lse_ws, int lse_ready,
+                        const int32_t *cu_seqlens, int batch, int max_seqlen, int nsenses, int d_k, int d_out,
+                        int64_t qk_row_stride, int64_t qk_two_stride, int64_t qk_sense_stride,
+                        int64_t c_row_stride, int64_t c_sense_stride, int64_t o_row_stride,
+                        float softmax_scale, int dtype, void *queue_ws, bp_stream_t stream) {
+    return sense_mix_varlen(qk, content, false, nullptr, out, lse_ws, lse_ready, cu_seqlens, batch, max_seqlen, nsenses, d_k,
+                            d_out, 0, qk_row_stride, qk_two_stride, qk_sense_stride, c_row_stride, c_sense_stride,
+                            o_row_stride, softmax_scale, dtype, queue_ws, stream);
+}
+
+int bp_sense_mix_gather_varlen(const void *qk, const void *table, const int32_t *row_index, void *out,
+                               float *lse_ws, int lse_ready,
+                               const int32_t *cu_seqlens, int batch, int max_seqlen, int nsenses, int d_k, int d_out,
+                               int64_t table_rows,
+                               int64_t qk_row_stride, int64_t qk_two_stride, int64_t qk_sense_stride,
+                               int64_t t_row_stride, int64_t t_sense_stride, int64_t o_row_stride,
+                               float softmax_scale, int dtype, void *queue_ws, bp_stream_t stream) {
+    return sense_mix_varlen(qk, table, true, row_index, out, lse_ws, lse_ready, cu_seqlens, batch, max_seqlen, nsenses, d_k,
+                            d_out, table_rows, qk_row_stride, qk_two_stride, qk_sense_stride, t_row_stride, t_sense_stride,
+                            o_row_stride, softmax_scale, dtype, queue_ws, stream);
+}
+
 int bp_sense_mix_dc(const void *qk, const void *dout, const float *lse, void *dcontent,
                     int batch, int seqlen, int nsenses, int d_k, int d_out,
                     int64_t qk_batch_stride, int64_t qk_row_stride, int64_t qk_two_stride, int64_t qk_sense_stride,

@@ -116,7 +116,14 @@ struct MixParams {
     const void *c;            // content[b, s, l, :] = c + b*c_bs + s*c_rs + l*c_ss
     void *o;                  // out[b, t, :] = o + b*o_bs + t*o_rs
     const float *lse;         // (b, k, lse_stride) natural-log LSE of every (sense, query)
-    const float *kw;          // optional key weights w[b, l, s] (fp32, unit stride along s): alpha[b,l,:,s] *= w
+    union {
+        const float *kw;      // optional key weights w[b, l, s] (fp32, unit stride along s): alpha[b,l,:,s] *= w
+        // launch_sense_mix_varlen only (packed batches; there is no weighted packed form, so the two never meet): sample b
+        // owns rows [cu[b], cu[b + 1]) of the operands; (b + 1) device ints, non-decreasing, every length in 0 .. s, not
+        // validated.  It shares the key weights' slot because a field of its own moves the arguments that kernels take
+        // BEHIND their MixParams (sense_lse_wide_dma_kernel's lse: other offsets in its text).
+        const int32_t *cu;
+    };
     int64_t kw_bs, kw_ss;
     const int32_t *row_index; // optional (bp_sense_mix_gather): content[b, s, l, :] = c + row_index[b*idx_bs + s]*c_rs + l*c_ss
     int64_t idx_bs;
@@ -131,6 +138,11 @@ struct MixParams {
     float scale_log2e;
     MixQueues *queues;        // caller's record (queue_ws) or NULL; armed by launch_sense_mix_dma
 };
+
+// Packed batches (bp_sense_mix_varlen / bp_sense_mix_gather_varlen; sense_mix_varlen.hip): MixParams with `cu` set.  The
+// operands are (total, ...) tensors, s = max_seqlen (n_qtiles counts its tiles), the batch strides and idx_bs are not
+// read, lse is (b, nsenses, lse_stride) as in the fixed form.
+hipError_t launch_sense_mix_varlen(const MixParams &p, int dtype, hipStream_t stream);
 
 // limits of the gathering sense mix: a job's row indices share the LDS with the ring as u16 (sense_mix_dma.hip)
 constexpr int kMixGatherMaxKeys = 4096;

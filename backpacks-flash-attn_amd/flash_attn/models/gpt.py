@@ -115,6 +115,21 @@ class GPTPreTrainedModel(nn.Module):
         return model
 
 
+def packed_coordinates(cu_seqlens, total):
+    """(sample, position), two (total,) int64 tensors: the sequence every row of a packed batch belongs to and its position
+    inside it, computed on cu_seqlens' device without a host read.  Row t belongs to the sample b with
+    cu[b] <= t < cu[b + 1], i.e. b = #{entries of cu[1:] <= t} (empty samples repeat an entry and own no row)."""
+    cu = cu_seqlens.long()
+    rows = torch.arange(total, device=cu.device)
+    sample = torch.bucketize(rows, cu[1:], right=True).clamp_(max=cu.numel() - 2)
+    return sample, rows - cu[sample]
+
+
+def packed_position_ids(cu_seqlens, total):
+    """Default position ids of a packed batch: they restart at 0 in every sequence."""
+    return packed_coordinates(cu_seqlens, total)[1]
+
+
 class GPTModel(GPTPreTrainedModel):
     """embeddings -> fp32 residual stream -> ln_0 -> n_layer pre-norm blocks.  gpt.py:175-246."""
 
@@ -169,16 +184,37 @@ class GPTModel(GPTPreTrainedModel):
                                                                embedding=source if i == 0 else None)
         return hidden
 
-    def forward(self, input_ids, position_ids=None, inference_params=None):
+    def forward(self, input_ids, position_ids=None, inference_params=None, cu_seqlens=None, max_seqlen=None):
         """`inference_params` (src/utils/generation.py InferenceParams): KV-cached generation, forwarded to every mixer
         (reference gpt.py:243).  In a decode step without `position_ids` the position of sample b is its cached length,
-        read on the device."""
+        read on the device.
+        `cu_seqlens` ((B + 1,) int32) + `max_seqlen` (int): a PACKED batch, `input_ids` (total,) -> (total, d); every mixer
+        receives the two (MHA.forward's ragged form), default positions restart at 0 in every sequence."""
+        if cu_seqlens is not None or max_seqlen is not None:
+            return self._forward_packed(input_ids, position_ids, inference_params, cu_seqlens, max_seqlen)
         if self._chain_applies(input_ids, inference_params):
             return self._forward_chained(input_ids, position_ids)
         if inference_params is not None and position_ids is None and inference_params.sequence_len_offset > 0:
             lengths = cache_lengths(inference_params, input_ids.shape[0], input_ids.device)
             position_ids = lengths.long().unsqueeze(1) + torch.arange(input_ids.shape[1], device=input_ids.device)
         mixer_kwargs = None if inference_params is None else {'inference_params': inference_params}
+        return self._embed_and_run(input_ids, position_ids, mixer_kwargs)
+
+    def _forward_packed(self, input_ids, position_ids, inference_params, cu_seqlens, max_seqlen):
+        """The packed form of `forward`: the unchained launches over (total, d) rows (every row-wise kernel takes any
+        number of rows), attention through the ragged flash call.  HIP trunk only: the eager attention has no ragged form
+        (BackpackModel pads such batches)."""
+        if inference_params is not None:
+            raise ValueError('a packed batch (cu_seqlens / max_seqlen) and inference_params exclude each other')
+        if cu_seqlens is None or max_seqlen is None or input_ids.dim() != 1:
+            raise ValueError('a packed batch needs input_ids (total,), cu_seqlens (B + 1,) int32 and max_seqlen (int)')
+        if not getattr(self.config, 'use_flash_attn', False):
+            raise NotImplementedError('a packed batch needs use_flash_attn=True: the eager attention has no ragged form')
+        if position_ids is None:
+            position_ids = packed_position_ids(cu_seqlens, input_ids.shape[0])
+        return self._embed_and_run(input_ids, position_ids, {'cu_seqlens': cu_seqlens, 'max_seqlen': int(max_seqlen)})
+
+    def _embed_and_run(self, input_ids, position_ids, mixer_kwargs):
         hidden = self.embeddings(input_ids, position_ids=position_ids)
         if self.fused_dropout_add_ln:
             # one HIP launch: residual (fp32) = hidden, hidden = LN(residual)   (reference gpt.py:236-240)

@@ -26,7 +26,7 @@ import torch.nn.functional as F
 from transformers import GPT2Config
 
 import bp_hip
-from flash_attn.models.gpt import GPTModel, GPTPreTrainedModel, _activation, _init_weights, _pad_vocab
+from flash_attn.models.gpt import GPTModel, GPTPreTrainedModel, _activation, _init_weights, _pad_vocab, packed_coordinates
 from flash_attn.modules.block import Block
 from flash_attn.modules.mha import cache_lengths, refuse_multi_token_step
 from flash_attn.modules.mlp import FusedDenseGeluDense, Mlp
@@ -119,15 +119,16 @@ class ContextSelfAttn(nn.Module):
         k=64 ablation: d_k = 10, training/configs/experiment/owt/backpack-mini-flash-vecs-64.yaml) is widened
         to the next multiple with ZERO columns: the LDS-DMA kernels move 16-byte chunks, zeros add nothing to
         q.k, and padding the projection's rows (1.3 M weights) instead of its output (2.6 KB per token, three
-        consumers) leaves autograd and the state-dict keys untouched.  Pair it with `scale()`."""
-        b, s, d = encoded.shape
+        consumers) leaves autograd and the state-dict keys untouched.  Pair it with `scale()`.
+        A packed batch: encoded (total,d) -> qk (total,2,k,d_k)."""
+        *lead, d = encoded.shape
         k = self.num_content_vectors
         dk = d // k
         pad = (-dk) % 8 if self.fused else 0
         if pad == 0:
-            return self.Wqkv(encoded).reshape(b, s, 2, k, dk)
+            return self.Wqkv(encoded).reshape(*lead, 2, k, dk)
         w, bias = self._padded_projection(k, dk, pad, d)
-        return fused_dense_func(encoded, w, bias).view(b, s, 2, k, dk + pad)
+        return fused_dense_func(encoded, w, bias).view(*lead, 2, k, dk + pad)
 
     def _padded_projection(self, k, dk, pad, d):
         """`Wqkv` with `pad` zero rows appended to every sense's q and k block.  Under autograd the pad is part of the
@@ -326,6 +327,7 @@ class BackpackModel(GPTPreTrainedModel):
         # positions, -6 % at 49 k, -12 % at 100 k; profiles/r05_a_content_modes_small.jsonl); text repeats tokens and pays earlier
         self.dedup_min_positions = int(getattr(config, 'dedup_min_positions', config.vocab_size))
         self._gather_fallback_said = False
+        self._packed_fallback_said = False
         self.gpt2_model = GPTModel(config, **factory_kwargs)
         self.content_model = BackpackContentModule(config, self.num_content_vectors,
                                                    self.gpt2_model.embeddings, **factory_kwargs)
@@ -582,7 +584,91 @@ class BackpackModel(GPTPreTrainedModel):
         return bp_hip.sense_decode(q, k_new, c.keys[c.b0:c.b1], table, c.rows[c.b0:c.b1], new_row, lengths, scale,
                                    key_weight=key_weight).unsqueeze(1)
 
-    def forward(self, input_ids, position_ids=None, inference_params=None):
+    # ---- packed (variable-length) batches --------------------------------------------------------------------------------
+    # input_ids (total,) + cu_seqlens ((B + 1,) int32 on the ids' device) + max_seqlen (int) -> (total, d): the sequences lie
+    # behind one another, nothing is padded (src/utils/packing.py builds the three).  The trunk runs its ragged flash call,
+    # the senses bp_sense_mix_varlen / bp_sense_mix_gather_varlen.  Inference only (no varlen backward), never with
+    # inference_params (a packed prefill would need a scatter into the KV caches), not under GraphedForward.
+    # What the packed kernels do not take -- wide or non-fused senses, use_flash_attn=False, the CPU -- is padded to
+    # (B, max_seqlen), run through the forward above and cut back to the real rows (`_forward_packed_padded`).
+
+    def _packed_limit(self, input_ids, max_seqlen):
+        """None when the packed kernels take this call, else the limit it exceeds (text)."""
+        if not self.use_hip:
+            return 'use_flash_attn=False'
+        if not input_ids.is_cuda:
+            return 'ids on the CPU'
+        d_k = -(-(self.config.n_embd // self.num_content_vectors) // 8) * 8
+        if not self.fused_senses:
+            return 'the senses do not run on the fused HIP kernels (ContextSelfAttn.fused is False)'
+        if d_k > 128:
+            return f'sense width {self.config.n_embd // self.num_content_vectors} > 128 (no packed wide sense kernels)'
+        if self.config.n_embd % 8 != 0:
+            return f'n_embd {self.config.n_embd} not a multiple of 8'
+        if max_seqlen > 65536:
+            return f'max_seqlen {max_seqlen} > 65536'
+        return None
+
+    def _forward_packed_padded(self, input_ids, position_ids, cu_seqlens, max_seqlen):
+        sample, position = packed_coordinates(cu_seqlens, input_ids.shape[0])
+        batch = cu_seqlens.numel() - 1
+        ids = input_ids.new_zeros((batch, max_seqlen))
+        ids[sample, position] = input_ids
+        pos = None
+        if position_ids is not None:
+            pos = position_ids.new_zeros((batch, max_seqlen))
+            pos[sample, position] = position_ids
+        return self.forward(ids, position_ids=pos)[sample, position]
+
+    def _mix_packed_from_table(self, qk, rows, index, cu_seqlens, max_seqlen):
+        scale = self.contextualization_attn.scale()
+        if bp_hip.sense_mix_gather_varlen_supported(qk, rows, max_seqlen):
+            return bp_hip.sense_mix_gather_varlen(qk, rows, index.to(torch.int32), cu_seqlens, max_seqlen, scale)
+        # as _mix_from_table: torch gathers the rows and the dense packed kernel runs -- said once per model
+        if not self._gather_fallback_said:
+            self._gather_fallback_said = True
+            warnings.warn('Backpack: the sense table is gathered by torch into a (total, k*d) tensor instead of inside the '
+                          'mix kernel: ' + bp_hip.sense_mix_gather_varlen_limits(qk, rows, max_seqlen))
+        content = torch.nn.functional.embedding(index, rows.reshape(rows.shape[0], -1))
+        return bp_hip.sense_mix_varlen(qk, content.view(index.shape[0], *rows.shape[1:]), cu_seqlens, max_seqlen, scale)
+
+    def _forward_packed(self, input_ids, position_ids, inference_params, cu_seqlens, max_seqlen):
+        if inference_params is not None:
+            raise ValueError('a packed batch (cu_seqlens / max_seqlen) and inference_params exclude each other: the '
+                             'KV-cached prefill takes padded prompts')
+        if torch.is_grad_enabled():
+            raise RuntimeError('the packed forward is inference-only (no varlen backward): run it under torch.no_grad() '
+                               'or torch.inference_mode()')
+        if cu_seqlens is None or max_seqlen is None or input_ids.dim() != 1 or cu_seqlens.dim() != 1 \
+                or cu_seqlens.dtype != torch.int32 or cu_seqlens.device != input_ids.device:
+            raise ValueError('a packed batch needs input_ids (total,), cu_seqlens (B + 1,) int32 on the ids\' device and '
+                             'max_seqlen (int): see src/utils/packing.pack_sequences')
+        max_seqlen = int(max_seqlen)
+        limit = self._packed_limit(input_ids, max_seqlen)
+        if limit is not None:
+            if self.use_hip and input_ids.is_cuda and not self._packed_fallback_said:
+                self._packed_fallback_said = True
+                warnings.warn('Backpack: the packed batch is padded to (B, max_seqlen) and run through the padded forward: '
+                              + limit)
+            return self._forward_packed_padded(input_ids, position_ids, cu_seqlens, max_seqlen)
+        hidden = self.gpt2_model(input_ids, position_ids=position_ids, cu_seqlens=cu_seqlens, max_seqlen=max_seqlen)
+        qk = self.contextualization_attn.project(hidden)                 # (total, 2, k, d_k)
+        if self._token_table_allowed(input_ids):
+            if self.sense_table_mode == 'cached':
+                rows = self.sense_table(verify=self._verify_applies(input_ids))
+                if rows is not None:
+                    return self._mix_packed_from_table(qk, rows, input_ids, cu_seqlens, max_seqlen)
+            if self._dedup_applies(input_ids):
+                rows, inverse = self._table_of_unique_tokens(input_ids)
+                return self._mix_packed_from_table(qk, rows, inverse, cu_seqlens, max_seqlen)
+        # every position through the content network, unchunked (chunks would have to end at sequence boundaries)
+        content = self.content_model(input_ids.unsqueeze(0))             # (1, k, total, d) view of (1, total, k*d)
+        return bp_hip.sense_mix_varlen(qk, content[0].transpose(0, 1), cu_seqlens, max_seqlen,
+                                       self.contextualization_attn.scale())
+
+    def forward(self, input_ids, position_ids=None, inference_params=None, cu_seqlens=None, max_seqlen=None):
+        if cu_seqlens is not None or max_seqlen is not None:
+            return self._forward_packed(input_ids, position_ids, inference_params, cu_seqlens, max_seqlen)
         if inference_params is not None:
             return self._forward_cached(input_ids, position_ids, inference_params)
         contextl_hidden_states = self.gpt2_model(input_ids, position_ids=position_ids, inference_params=None)
@@ -676,12 +762,18 @@ class BackpackLMHeadModel(BackpackPreTrainedModel, GenerationMixin):
         # tied with the word embeddings of both the trunk and the content model (reference :339-340)
         self.lm_head.weight = self.transformer.embeddings.word_embeddings.weight
 
-    def forward(self, input_ids, position_ids=None, inference_params=None, logits_out=None):
+    def forward(self, input_ids, position_ids=None, inference_params=None, logits_out=None, cu_seqlens=None,
+                max_seqlen=None):
         """`logits_out` (not in the reference's signature, :342-351): a caller-owned (B, S, vocab) buffer the LM head
         writes into -- inference at HBM-filling batches, where the logits are most of the memory (103 MB per sample at
-        Small / S = 1024) and a fresh allocation per step is what the caching allocator cannot re-place."""
-        hidden_states = self.transformer(input_ids, position_ids=position_ids,
-                                         inference_params=inference_params)
+        Small / S = 1024) and a fresh allocation per step is what the caching allocator cannot re-place.
+        `cu_seqlens` / `max_seqlen`: a packed batch (BackpackModel.forward), ids (total,) -> logits (total, vocab)."""
+        if cu_seqlens is not None or max_seqlen is not None:
+            hidden_states = self.transformer(input_ids, position_ids=position_ids, inference_params=inference_params,
+                                             cu_seqlens=cu_seqlens, max_seqlen=max_seqlen)
+        else:
+            hidden_states = self.transformer(input_ids, position_ids=position_ids,
+                                             inference_params=inference_params)
         CausalLMOutput = namedtuple('CausalLMOutput', ['logits'])
         if logits_out is None:
             return CausalLMOutput(logits=self.lm_head(hidden_states))

@@ -75,11 +75,20 @@ def _anneal_weights(sims, picked, annealing_scale, upweight_nearby, first_positi
     return picked * scores + (1 - scores)
 
 
+def _refuse_packed(model, cu_seqlens, max_seqlen):
+    """Packed batches (BackpackModel.forward's cu_seqlens / max_seqlen) stop at the wrappers: their edits -- per-position
+    weights, replaced rows, key weights -- are written for (B, S) ids, and the packed mix kernels have no weighted form."""
+    if cu_seqlens is not None or max_seqlen is not None:
+        raise NotImplementedError(f'{type(model).__name__} takes no packed batch (cu_seqlens / max_seqlen): pad the '
+                                  'sequences to (B, S), or score the wrapped network')
+
+
 class _Intervened(nn.Module, GenerationMixin, SenseIntervention):
     """Shared plumbing: the three stages of the wrapped network, the contraction, and where a call goes -- with
     `inference_params` to the cached path of the wrapped BackpackModel (its hook: this wrapper), else to `_mixed`."""
 
-    def forward(self, input_ids, position_ids=None, inference_params=None):
+    def forward(self, input_ids, position_ids=None, inference_params=None, cu_seqlens=None, max_seqlen=None):
+        _refuse_packed(self, cu_seqlens, max_seqlen)
         cached = self.backpack_network.transformer._forward_cached
         mixed = self._mixed(input_ids, position_ids) if inference_params is None else \
             cached(input_ids, position_ids, inference_params, intervention=self)
@@ -223,7 +232,8 @@ class NegativeWeightedBackpackLMHeadModel(WeightedBackpackLMHeadModel):
     """Per (sense, position) the 2 % most negative re-weighted vocabulary logits replace the plain ones,
     then the contraction runs on vocabulary-sized content (reference :108-165)."""
 
-    def forward(self, input_ids, position_ids=None, inference_params=None):
+    def forward(self, input_ids, position_ids=None, inference_params=None, cu_seqlens=None, max_seqlen=None):
+        _refuse_packed(self, cu_seqlens, max_seqlen)
         if inference_params is not None:
             raise NotImplementedError(
                 'NegativeWeightedBackpackLMHeadModel has no KV-cached decoding: its content is vocabulary-sized per '
@@ -308,7 +318,8 @@ class ScaledSenseLMHeadModel(_Intervened):
         if not 0 <= self.sense_index < k:
             raise ValueError(f'sense_index {sense_index} outside the {k} senses of the network')
 
-    def forward(self, input_ids, position_ids=None, inference_params=None):
+    def forward(self, input_ids, position_ids=None, inference_params=None, cu_seqlens=None, max_seqlen=None):
+        _refuse_packed(self, cu_seqlens, max_seqlen)
         if inference_params is not None:
             raise NotImplementedError('ScaledSenseLMHeadModel has no KV-cached decoding: it is a full-forward readout')
         return super().forward(input_ids, position_ids, None)

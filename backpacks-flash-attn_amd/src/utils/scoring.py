@@ -18,6 +18,7 @@ from collections import namedtuple
 import torch
 
 import bp_hip
+from src.utils.packing import pack_sequences
 
 TokenScores = namedtuple('TokenScores', ['logprobs', 'ranks', 'top1', 'entropy', 'lse', 'mask'])
 SequenceScores = namedtuple('SequenceScores', ['logprob', 'count', 'all_top1'])
@@ -84,14 +85,19 @@ def _network(model):
     return getattr(model, 'backpack_network', model)
 
 
-def _hidden_and_head(model, input_ids):
-    """(hidden states (B, S, d), LM head) of a plain model or of a sense-intervened wrapper."""
+def _hidden_and_head(model, input_ids, cu_seqlens=None, max_seqlen=None):
+    """(hidden states (B, S, d), LM head) of a plain model or of a sense-intervened wrapper.  With cu_seqlens / max_seqlen
+    the ids are a packed batch (total,) and the hidden states (total, d): BackpackModel's packed forward."""
     if hasattr(model, 'backpack_network') and hasattr(model, '_mixed'):
+        if cu_seqlens is not None:
+            raise NotImplementedError(f'{type(model).__name__} takes no packed batch: score with packed=False')
         if not _plain_wrapper_forward(model):
             raise NotImplementedError(f'{type(model).__name__} does not produce its logits as lm_head(hidden states): '
                                       'score its logits with bp_hip.score_rows instead')
         return model._mixed(input_ids, None), model.backpack_network.lm_head
     if hasattr(model, 'transformer') and hasattr(model, 'lm_head'):
+        if cu_seqlens is not None:
+            return model.transformer(input_ids, cu_seqlens=cu_seqlens, max_seqlen=max_seqlen), model.lm_head
         return model.transformer(input_ids), model.lm_head
     raise TypeError(f'{type(model).__name__}: expected a model with `transformer` and `lm_head`, or a sense-intervened wrapper')
 
@@ -126,7 +132,8 @@ def _shifted(input_ids, ignore_index):
 
 
 @torch.no_grad()
-def score_tokens(model, input_ids, labels=None, lengths=None, chunk_tokens=16384, ignore_index=-100, want=SCORE_OUTPUTS):
+def score_tokens(model, input_ids, labels=None, lengths=None, chunk_tokens=16384, ignore_index=-100, want=SCORE_OUTPUTS,
+                 packed=False):
     """Per-token scores of `input_ids` (B, S) under `model`: TokenScores of (B, S) tensors -- `logprobs` fp32 (the
     log-probability of the label), `ranks` int32 (0-based rank of the label among the logits, ties towards the lower id),
     `top1` int32 (the greedy token), `entropy` and `lse` fp32, and `mask` (bool: the position was scored).
@@ -136,7 +143,10 @@ def score_tokens(model, input_ids, labels=None, lengths=None, chunk_tokens=16384
     the scoring run over the scored rows only, gathered before the GEMM: the head in blocks of one fixed shape (_head_block, at
     most HEAD_BLOCK_ROWS rows -- the logits alive at once), the scoring at most `chunk_tokens` rows a launch.  The outputs do
     not depend on chunk_tokens, bit for bit.  Unscored positions hold 0 (logprobs, entropy, lse) and -1 (ranks, top1).
-    `want`: the subset of outputs to compute; the others are None."""
+    `want`: the subset of outputs to compute; the others are None.
+    packed=True (needs `lengths`): the model runs on the PACKED batch -- the rows' real tokens behind one another
+    (src/utils/packing.py, BackpackModel.forward's cu_seqlens form) -- so the pads cost no trunk, sense or head work; the
+    returned (B, S) tensors are laid out as without it.  The lengths are read on the host (one synchronisation)."""
     if labels is None:
         labels = _shifted(input_ids, ignore_index)
     batch, seqlen = input_ids.shape
@@ -144,9 +154,17 @@ def score_tokens(model, input_ids, labels=None, lengths=None, chunk_tokens=16384
     if lengths is not None:
         lengths = torch.as_tensor(lengths, device=input_ids.device)
         mask = mask & (torch.arange(seqlen, device=input_ids.device)[None, :] < (lengths[:, None] - 1))
-    hidden, head = _hidden_and_head(model, input_ids)
+    if packed:
+        if lengths is None:
+            raise ValueError('score_tokens: packed=True needs lengths')
+        ids, cu_seqlens, max_seqlen = pack_sequences(input_ids, lengths)
+        hidden, head = _hidden_and_head(model, ids, cu_seqlens, max_seqlen)
+    else:
+        hidden, head = _hidden_and_head(model, input_ids)
     rows = hidden.reshape(-1, hidden.shape[-1])
-    index = mask.reshape(-1).nonzero().squeeze(1)
+    index = mask.reshape(-1).nonzero().squeeze(1)       # the scored positions as b * S + s: where the outputs go
+    # ... and as rows of the hidden states: where the head reads
+    source = cu_seqlens.long()[index // seqlen] + index % seqlen if packed else index
     flat_labels = labels.reshape(-1).to(torch.int64)
     names = {'logprob': 'logprobs', 'rank': 'ranks', 'top1': 'top1', 'entropy': 'entropy', 'lse': 'lse'}
     want = tuple(want)
@@ -155,8 +173,8 @@ def score_tokens(model, input_ids, labels=None, lengths=None, chunk_tokens=16384
     chunk, total = max(1, int(chunk_tokens)), index.shape[0]
     block = _head_block(total)
     for b0 in range(0, total, block):
-        sel = index[b0:b0 + block]
-        take = sel if sel.shape[0] == block else torch.cat([sel, sel[-1:].expand(block - sel.shape[0])])   # the last block, padded
+        sel, src = index[b0:b0 + block], source[b0:b0 + block]
+        take = src if src.shape[0] == block else torch.cat([src, src[-1:].expand(block - src.shape[0])])   # the last block, padded
         logits = head(rows[take])[:sel.shape[0]]
         for lo in range(0, sel.shape[0], chunk):
             got = _score(model, logits[lo:lo + chunk], flat_labels[sel[lo:lo + chunk]], want)
@@ -167,17 +185,19 @@ def score_tokens(model, input_ids, labels=None, lengths=None, chunk_tokens=16384
 
 
 @torch.no_grad()
-def sequence_scores(model, input_ids, lengths=None, prefix_lengths=None, chunk_tokens=16384):
+def sequence_scores(model, input_ids, lengths=None, prefix_lengths=None, chunk_tokens=16384, packed=False):
     """Per row of `input_ids` (B, S), the score of its tokens [prefix, length): SequenceScores of (B,) tensors -- `logprob`
     float64 (the sum of their log-probabilities), `count` int64 and `all_top1` (bool: every one of them was the greedy
-    token).  Token j is predicted at position j - 1, so token 0 is never scored.  lengths default to S, prefix_lengths to 0."""
+    token).  Token j is predicted at position j - 1, so token 0 is never scored.  lengths default to S, prefix_lengths to 0.
+    `packed`: as in score_tokens."""
     batch, seqlen = input_ids.shape
     labels = _shifted(input_ids, -100)
     if prefix_lengths is not None:
         prefix = torch.as_tensor(prefix_lengths, device=input_ids.device)
         before = torch.arange(seqlen, device=input_ids.device)[None, :] < (prefix[:, None] - 1)
         labels = labels.masked_fill(before, -100)
-    got = score_tokens(model, input_ids, labels=labels, lengths=lengths, chunk_tokens=chunk_tokens, want=('logprob', 'rank'))
+    got = score_tokens(model, input_ids, labels=labels, lengths=lengths, chunk_tokens=chunk_tokens, want=('logprob', 'rank'),
+                       packed=packed)
     return SequenceScores(logprob=got.logprobs.double().sum(dim=1), count=got.mask.sum(dim=1),
                           all_top1=((got.ranks == 0) | ~got.mask).all(dim=1))
 
@@ -191,16 +211,17 @@ def _batch_of(batch):
 
 
 @torch.no_grad()
-def evaluate_lm(model, batches, chunk_tokens=16384, ignore_index=-100):
+def evaluate_lm(model, batches, chunk_tokens=16384, ignore_index=-100, packed=False):
     """Loss, perplexity and top-1 accuracy of `model` over `batches`: an iterable of (B, S) id tensors, of (input_ids, labels[,
     lengths]) tuples or of dicts with those names.  Returns {'loss', 'perplexity', 'accuracy', 'tokens'}.  Sums are float64
     and the perplexity is the exponential of the mean loss, as the reference's Perplexity metric
-    (training/src/metrics/perplexity.py); the accuracy counts positions whose label has rank 0 (metrics/accuracy.py)."""
+    (training/src/metrics/perplexity.py); the accuracy counts positions whose label has rank 0 (metrics/accuracy.py).
+    `packed`: batches that carry lengths run packed (score_tokens); the others as they are."""
     nll = correct = tokens = None
     for batch in batches:
         ids, labels, lengths = _batch_of(batch)
         got = score_tokens(model, ids, labels=labels, lengths=lengths, chunk_tokens=chunk_tokens, ignore_index=ignore_index,
-                           want=('logprob', 'rank'))
+                           want=('logprob', 'rank'), packed=packed and lengths is not None)
         part = (-got.logprobs.double().sum(), ((got.ranks == 0) & got.mask).sum(), got.mask.sum())
         nll, correct, tokens = part if nll is None else (nll + part[0], correct + part[1], tokens + part[2])
     if nll is None or int(tokens) == 0:
@@ -223,13 +244,14 @@ def _device_of(model):
     return _network(model).lm_head.weight.device
 
 
-def _ragged_scores(model, sequences, prefixes=None, batch_size=32):
-    """sequence_scores of a list of id sequences of different lengths, `batch_size` at a time, right-padded."""
+def _ragged_scores(model, sequences, prefixes=None, batch_size=32, packed=False):
+    """sequence_scores of a list of id sequences of different lengths, `batch_size` at a time, right-padded; `packed`: the
+    model runs on the packed batch instead (score_tokens).  last_word_eval, pair_accuracy and rank_choices pass it through."""
     device, parts = _device_of(model), []
     for lo in range(0, len(sequences), batch_size):
         ids, lengths = _padded(sequences[lo:lo + batch_size], device)
         prefix = None if prefixes is None else torch.tensor(prefixes[lo:lo + batch_size], dtype=torch.int64, device=device)
-        parts.append(sequence_scores(model, ids, lengths=lengths, prefix_lengths=prefix))
+        parts.append(sequence_scores(model, ids, lengths=lengths, prefix_lengths=prefix, packed=packed))
     return SequenceScores(*[torch.cat(field) for field in zip(*parts)])
 
 
@@ -237,36 +259,36 @@ def _ids(sequence):
     return list(map(int, sequence.tolist() if torch.is_tensor(sequence) else sequence))
 
 
-def last_word_eval(model, examples, batch_size=32):
+def last_word_eval(model, examples, batch_size=32, packed=False):
     """The LAMBADA protocol on (context ids, target ids) pairs: an example is right when every target token is the greedy
     token given what precedes it.  Returns {'accuracy', 'perplexity' (of the target tokens), 'examples', 'tokens'}."""
     examples = [(_ids(c), _ids(t)) for c, t in examples]
     if any(not c or not t for c, t in examples):
         raise ValueError('last_word_eval: every example needs a non-empty context and a non-empty target')
-    got = _ragged_scores(model, [c + t for c, t in examples], [len(c) for c, _ in examples], batch_size)
+    got = _ragged_scores(model, [c + t for c, t in examples], [len(c) for c, _ in examples], batch_size, packed)
     tokens = int(got.count.sum())
     return {'accuracy': float(got.all_top1.double().mean()), 'perplexity': math.exp(-float(got.logprob.sum()) / tokens),
             'examples': len(examples), 'tokens': tokens}
 
 
-def pair_accuracy(model, good, bad, batch_size=32):
+def pair_accuracy(model, good, bad, batch_size=32, packed=False):
     """Minimal pairs: the share of pairs whose `good` sequence scores a higher total log-probability than its `bad` one
     (tokens 1 .. of each).  Returns {'accuracy', 'good', 'bad'}, the last two the (N,) float64 scores."""
     if len(good) != len(bad) or not len(good):
         raise ValueError('pair_accuracy: good and bad must be two lists of the same, non-zero length')
-    a = _ragged_scores(model, [_ids(s) for s in good], None, batch_size).logprob
-    b = _ragged_scores(model, [_ids(s) for s in bad], None, batch_size).logprob
+    a = _ragged_scores(model, [_ids(s) for s in good], None, batch_size, packed).logprob
+    b = _ragged_scores(model, [_ids(s) for s in bad], None, batch_size, packed).logprob
     return {'accuracy': float((a > b).double().mean()), 'good': a, 'bad': b}
 
 
-def rank_choices(model, context, choices, normalize=False, batch_size=32):
+def rank_choices(model, context, choices, normalize=False, batch_size=32, packed=False):
     """Multiple choice: the log-probability of every continuation in `choices` after `context` (ids), divided by its token
     count with `normalize`.  Returns (order, scores): the indices of the choices best first (ties: the lower index) and the
     (len(choices),) float64 scores."""
     context, choices = _ids(context), [_ids(c) for c in choices]
     if not context or not choices or any(not c for c in choices):
         raise ValueError('rank_choices: a non-empty context and non-empty choices')
-    got = _ragged_scores(model, [context + c for c in choices], [len(context)] * len(choices), batch_size)
+    got = _ragged_scores(model, [context + c for c in choices], [len(context)] * len(choices), batch_size, packed)
     scores = got.logprob / got.count if normalize else got.logprob
     return torch.sort(scores, descending=True, stable=True).indices, scores
 

@@ -58,7 +58,9 @@ extern "C" {
                               and one more: bp_sense_similarity, the cosine measures of sense vectors (lexical similarity,
                               nearest words in sense space) in one pass over the sense table;
                               and one more: bp_score_rows, what an evaluation keeps of a row of logits -- log-probability and
-                              rank of the gold token, log-sum-exp, greedy token, entropy -- in one pass over the row) */
+                              rank of the gold token, log-sum-exp, greedy token, entropy -- in one pass over the row;
+                              and three more: bp_sense_lse_varlen / bp_sense_mix_varlen / bp_sense_mix_gather_varlen, the sense
+                              kernels on packed batches described by cu_seqlens) */
 
 /* element type of q/k/v/out/content tensors */
 #define BP_DTYPE_F16 0
@@ -296,6 +298,44 @@ int bp_sense_mix_gather(const void *qk, const void *table, const int32_t *row_in
                         int64_t t_row_stride, int64_t t_sense_stride, int64_t idx_batch_stride,
                         int64_t o_batch_stride, int64_t o_row_stride,
                         float softmax_scale, int dtype, void *queue_ws, bp_stream_t stream);
+
+/*
+ * bp_sense_lse_varlen, bp_sense_mix_varlen, bp_sense_mix_gather_varlen -- bp_sense_lse, bp_sense_mix and bp_sense_mix_gather on
+ * PACKED batches (added within ABI 11: additive).  The sequences of a batch lie behind one another without padding, as in
+ * the ragged calls of bp_flash_fwd: sample b owns rows [cu_seqlens[b], cu_seqlens[b + 1]) of every (total, ...) operand, and
+ * attends causally within them.  A sample's output rows carry the bits bp_sense_mix returns for that sample alone.
+ *   qk          (total, 2, nsenses, d_k) 16-bit, element strides qk_row/qk_two/qk_sense, last stride 1
+ *   content     (total, nsenses, d_out), strides c_row/c_sense;  table / row_index (total) int32 as in bp_sense_mix_gather
+ *   out         (total, d_out), stride o_row
+ *   lse, lse_ws (batch, nsenses, roundup(max_seqlen,16)) fp32 -- the layout of the trunk's ragged calls; entries at or
+ *               behind a sample's length are not written
+ *   cu_seqlens  batch + 1 device ints, non-decreasing, cu_seqlens[0] >= 0, every length in 0 .. max_seqlen (a zero-length
+ *               sample is legal and owns no rows).  NOT validated -- the host never reads the array (the contract of
+ *               bp_flash_fwd's arrays): a length beyond max_seqlen loses its last rows, a decreasing array reads and
+ *               writes rows of other samples.  NULL is BP_ERR_SHAPE.
+ *   max_seqlen  takes the place of seqlen: it sizes the launch and the lse rows, and may exceed the longest length
+ *   lse_ready, queue_ws (required on a capturing stream: BP_ERR_QUEUE_WS) and the error codes as in the fixed-length forms
+ * There are no batch strides, and no idx_batch_stride.
+ * Restrictions: narrow senses on the 16-byte vector path only, i.e. what bp_sense_mix_gather states -- d_k % 8 == 0 and
+ * d_k <= 128 (BP_ERR_HEAD_DIM otherwise), d_out % 8 == 0 (BP_ERR_DOUT), aligned bases and strides that are multiples of 8,
+ * max_seqlen <= 65536 (BP_ERR_SHAPE); the gathering form max_seqlen <= 4096, table_rows <= 65536 and a table below 4 GiB.
+ * No key-weighted, wide or element-wise-loader form and no backward exist: callers pad such batches.
+ */
+int bp_sense_lse_varlen(const void *qk, float *lse, const int32_t *cu_seqlens, int batch, int max_seqlen, int nsenses,
+                        int d_k, int64_t qk_row_stride, int64_t qk_two_stride, int64_t qk_sense_stride,
+                        float softmax_scale, int dtype, bp_stream_t stream);
+int bp_sense_mix_varlen(const void *qk, const void *content, void *out, float *lse_ws, int lse_ready,
+                        const int32_t *cu_seqlens, int batch, int max_seqlen, int nsenses, int d_k, int d_out,
+                        int64_t qk_row_stride, int64_t qk_two_stride, int64_t qk_sense_stride,
+                        int64_t c_row_stride, int64_t c_sense_stride, int64_t o_row_stride,
+                        float softmax_scale, int dtype, void *queue_ws, bp_stream_t stream);
+int bp_sense_mix_gather_varlen(const void *qk, const void *table, const int32_t *row_index, void *out,
+                               float *lse_ws, int lse_ready,
+                               const int32_t *cu_seqlens, int batch, int max_seqlen, int nsenses, int d_k, int d_out,
+                               int64_t table_rows,
+                               int64_t qk_row_stride, int64_t qk_two_stride, int64_t qk_sense_stride,
+                               int64_t t_row_stride, int64_t t_sense_stride, int64_t o_row_stride,
+                               float softmax_scale, int dtype, void *queue_ws, bp_stream_t stream);
 
 /*
  * bp_sense_mix_dc -- backward of bp_sense_mix with respect to the content:
