@@ -17,7 +17,8 @@ must return bit for bit and the sense backward within a derived rounding bound (
 tile) term of dK dropped or doubled, a dS term on the neighbouring key, scale misplaced in one tile and a wrong D for a slab
 all change bits.  Partly seen now: a row that takes the LSE of another row (row 0 has one needle, hence another LSE than the
 paired rows; among the paired rows of a call it is still one number); another row's D is seen (D_i = dO_i . O_i differs from
-row to row).  Still unseen: dropout in the backward (the pair problems run without), and key_weight in the fused sense
+row to row).  Dropout, forward and backward, has its own exact tests: the pair problems run under p = 1/2 in
+tests/test_gpu_dropout_exact.py (tests/dropout_exact.py).  Still unseen: key_weight in the fused sense
 backward, which has none (a weighted call takes the alpha-rebuilding route; the pair problem runs that route unweighted).
 tests/test_gpu_backward.py keeps the job on random data.
 
@@ -405,22 +406,36 @@ def _rows_of(x, js):
     return torch.gather(x, 1, js.permute(0, 2, 1)[..., None].expand(js.shape[0], js.shape[2], js.shape[1], x.shape[-1]))
 
 
-def _pair_closed_forms(q, k, v, dout, js, js2, s, sk):
-    """fp64 closed forms of a pair problem: q, dout (b, t, g, .), k, v (b, sk, g, .), js / js2 (b, g, t)."""
+def _pair_closed_forms(q, k, v, dout, js, js2, s, sk, keep=None):
+    """fp64 closed forms of a pair problem: q, dout (b, t, g, .), k, v (b, sk, g, .), js / js2 (b, g, t).
+
+    keep: None (no dropout) or the keep bits (k1, k2) of every row's two needles, bool (b, g, t), under dropout with p = 1/2
+    (tests/dropout_exact.py): Z = 2 k is 0 or 2 and, with P = w (1/2, 1/2; 1, 0 for a row without a partner),
+        O = w1 Z1 V[j1] + w2 Z2 V[j2]      D = dO . O = w1 Z1 dP1 + w2 Z2 dP2      dS_x = w_x (Z_x dP_x - D)
+        dQ = scale (dS1 K[j1] + dS2 K[j2])      dK_j = scale sum dS Q_i      dV_j = sum w Z dO_i
+    i.e. O = k1 V[j1] + k2 V[j2], dS1 = k1 dP1 - D / 2 for a paired row and O = 2 k V[j1], dS = 0 for an unpaired one.  Z = 1
+    gives the forms of the head of this section: dS1 = (dP1 - dP2) / 4 = -dS2."""
     q, k, v, dout = q.double(), k.double(), v.double(), dout.double()
     paired = (js2 != js).permute(0, 2, 1)[..., None]                                # (b, t, g, 1)
     w1, w2 = torch.where(paired, 0.5, 1.0), torch.where(paired, 0.5, 0.0)
+    z1 = z2 = torch.ones_like(w1)
+    if keep is not None:
+        z1, z2 = (2.0 * kk.permute(0, 2, 1)[..., None].to(w1) for kk in keep)
     v1, v2 = _rows_of(v, js), _rows_of(v, js2)
-    n = torch.where(paired, ((v1 - v2) * dout).sum(-1, keepdim=True), 0.0)          # dP[i, j1] - dP[i, j2]
-    dk1, _ = fan_in(js, n / 4 * q, sk)
-    dk2, _ = fan_in(js2, n / 4 * q * paired, sk)
-    dv1, c1 = fan_in(js, w1 * dout, sk)
-    dv2, c2 = fan_in(js2, w2 * dout, sk)
+    dp1, dp2 = (v1 * dout).sum(-1, keepdim=True), (v2 * dout).sum(-1, keepdim=True)
+    n = torch.where(paired, dp1 - dp2, 0.0)                                         # dP[i, j1] - dP[i, j2]
+    dd = w1 * z1 * dp1 + w2 * z2 * dp2                                              # D
+    ds1, ds2 = w1 * (z1 * dp1 - dd), w2 * (z2 * dp2 - dd)
+    dk1, _ = fan_in(js, ds1 * q, sk)
+    dk2, _ = fan_in(js2, ds2 * q, sk)
+    dv1, c1 = fan_in(js, w1 * z1 * dout, sk)
+    dv2, c2 = fan_in(js2, w2 * z2 * dout, sk)
     k1, k2 = _rows_of(k, js), _rows_of(k, js2)
-    abs_dk = fan_in(js, n.abs() / 4 * q.abs(), sk)[0] + fan_in(js2, n.abs() / 4 * q.abs() * paired, sk)[0]
-    return dict(want=w1 * v1 + w2 * v2, n=n[..., 0], want_dq=s * n / 4 * (k1 - k2), want_dk=s * (dk1 - dk2), want_dv=dv1 + dv2,
-                fan=c1 + c2, zero_out=DUST + FP32_SUM * (w1 * v1.abs() + w2 * v2.abs()),
-                zero_dq=GRAD_DUST + s * FP32_SUM * n.abs() / 4 * (k1.abs() + k2.abs()), zero_dk=GRAD_DUST + s * FP32_SUM * abs_dk)
+    abs_dk = fan_in(js, ds1.abs() * q.abs(), sk)[0] + fan_in(js2, ds2.abs() * q.abs(), sk)[0]
+    return dict(want=w1 * z1 * v1 + w2 * z2 * v2, n=n[..., 0], want_dq=s * (ds1 * k1 + ds2 * k2), want_dk=s * (dk1 + dk2),
+                want_dv=dv1 + dv2, fan=c1 + c2, zero_out=DUST + FP32_SUM * (w1 * z1 * v1.abs() + w2 * z2 * v2.abs()),
+                zero_dq=GRAD_DUST + s * FP32_SUM * (ds1.abs() * k1.abs() + ds2.abs() * k2.abs()),
+                zero_dk=GRAD_DUST + s * FP32_SUM * abs_dk)
 
 
 def pair_lse(js, js2, width, s):

@@ -36,7 +36,8 @@ First finding of the pair tests, fixed in csrc/flash_fwd_dma.hip: a masked (diag
 exp2(m c2 - fl(m c2)), the rounding error of the product, when the tile did not raise the row's maximum -- 1 + 2e-5 instead
 of 1 at m c2 ~ 500, which left 3e-5 where (V[j1] + V[j2]) / 2 = 0 with the needles in different tiles (d = 64, 128).
 
-NOT tested here: dropout in the backward, key_weight in the fused sense backward (it has none), and a paired row taking
+Dropout in the forward and the backward is tested exactly in tests/test_gpu_dropout_exact.py.
+NOT tested here: key_weight in the fused sense backward (it has none), and a paired row taking
 another paired row's LSE (they share one; row 0, with one needle, has another, and another row's D is seen).
 
 Two places where the kernels' own arithmetic is not exact on these inputs, each with a derived bound instead:
