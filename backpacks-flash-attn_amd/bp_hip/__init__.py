@@ -106,6 +106,7 @@ SIGNATURES = {
     'bp_sense_attribute': (_i32, [_ptr] * 9 + [_i64] + [_i32] * 7 + [_i64] + [_i64] * 14 + [_f32, _i32, _ptr]),
     'bp_sense_similarity': (_i32, [_ptr] * 9 + [_i64] + [_i32] * 3 + [_i64] + [_i64] * 7 + [_i32, _ptr]),
     'bp_score_rows': (_i32, [_ptr] * 7 + [_i64, _i32, _i32] + [_i64] * 3 + [_i32, _ptr]),
+    'bp_pick_report': (_i32, [_ptr] * 8 + [_i32] * 2 + [_i64] * 2 + [_i32, _i64, _i32, _i32, _ptr]),
 }
 
 
@@ -1739,3 +1740,70 @@ def score_rows(logits, targets, want=SCORE_OUTPUTS):
           *[res[n].data_ptr() if n in res else None for n in SCORE_OUTPUTS],
           rows, cols, m, logits.stride(0) if rows > 1 else max(cols, logits.stride(0)), m, m, _PICK_DTYPES[logits.dtype])
     return res
+
+
+# ---- the record of a pick on the device (C ABI bp_pick_report) ---------------------------------------------------------------------------------------------------------
+
+PICK_REPORT_MAX_TOP = 16
+PICK_REPORT_RECORDS = ('logprob', 'rank', 'entropy', 'top_idx', 'top_logprob')
+_REPORT_DTYPES = {'logprob': torch.float32, 'rank': torch.int32, 'entropy': torch.float32, 'top_idx': torch.int32,
+                  'top_logprob': torch.float32}
+
+
+def pick_report_supported(logits, n_top=0):
+    """Whether bp_pick_report takes this call: a (rows >= 1, vocab >= 1) fp16 / bf16 / fp32 CUDA tensor with a contiguous last
+    dimension and 0 <= n_top <= min(vocab, 16)."""
+    return (logits.is_cuda and logits.dim() == 2 and logits.dtype in _PICK_DTYPES and logits.shape[0] >= 1
+            and logits.shape[1] >= 1 and logits.stride(1) == 1 and (logits.shape[0] <= 1 or logits.stride(0) >= logits.shape[1])
+            and 0 <= int(n_top) <= min(logits.shape[1], PICK_REPORT_MAX_TOP))
+
+
+def pick_report(logits, tokens, counters, *, logprob=None, rank=None, entropy=None, top_idx=None, top_logprob=None):
+    """The record of a pick, in one launch that reads no host value (C ABI bp_pick_report, contract in include/bp_hip.h; legal
+    inside a HIP-graph capture): for every row b of `logits` (B, vocab) fp16 / bf16 / fp32 (any row stride), into column c =
+    counters[b] of the records that are given -- logprob fp32, rank int32 and entropy fp32 (B, cols): the log-probability and the
+    0-based rank of tokens[b] under the row and the row's entropy, as score_rows defines them; top_idx int32 and top_logprob fp32
+    (B, cols, n), n <= 16: the n most likely tokens in pick_token's greedy order and their log-probabilities.  A row whose c
+    lies outside [0, cols) is left alone; every other column too.  tokens: int64 with B elements (any stride along its first
+    dimension, e.g. the (B, 1) input of the next decode step); counters: contiguous (B,) int32.  The records are views with a
+    contiguous last dimension that share their width and ONE row stride (top_*: that stride times n), e.g. the leading
+    columns of buffers as wide as the cache.  Returns None."""
+    given = {'logprob': logprob, 'rank': rank, 'entropy': entropy, 'top_idx': top_idx, 'top_logprob': top_logprob}
+    _require_cuda(logits, tokens, counters, *given.values())
+    if logits.dim() != 2 or logits.dtype not in _PICK_DTYPES or logits.shape[0] < 1 or logits.shape[1] < 1 or logits.stride(1) != 1:
+        raise RuntimeError('bp_hip.pick_report: logits must be (B, vocab) fp16 / bf16 / fp32 with a contiguous last dimension')
+    batch, vocab = logits.shape
+    if tokens.dtype != torch.int64 or tokens.numel() != batch or tokens.shape[0] != batch:
+        raise RuntimeError('bp_hip.pick_report: tokens must be int64 with B elements along its first dimension')
+    if counters.shape != (batch,) or counters.dtype != torch.int32 or not counters.is_contiguous():
+        raise RuntimeError('bp_hip.pick_report: counters must be a contiguous (B,) int32 tensor')
+    if all(v is None for v in given.values()):
+        raise RuntimeError(f'bp_hip.pick_report: give at least one of {PICK_REPORT_RECORDS}')
+    n_top, places = 0, set()
+    for name, v in given.items():
+        if v is None:
+            continue
+        top = name.startswith('top_')
+        if v.dtype != _REPORT_DTYPES[name] or v.dim() != (3 if top else 2) or v.shape[0] != batch or v.shape[1] < 1:
+            raise RuntimeError(f'bp_hip.pick_report: {name} must be {_REPORT_DTYPES[name]} (B, cols' + (', n)' if top else ')'))
+        n = v.shape[2] if top else 1
+        if top and (not 1 <= n <= min(vocab, PICK_REPORT_MAX_TOP) or n_top not in (0, n)):
+            raise RuntimeError(f'bp_hip.pick_report: top_idx and top_logprob hold the same 1 .. min(vocab, {PICK_REPORT_MAX_TOP}) '
+                               'entries per pick')
+        if top:
+            n_top = n
+        cols = v.shape[1]
+        row = v.stride(0) if batch > 1 else max(cols * n, v.stride(0))
+        if v.stride(-1) != 1 or (top and cols > 1 and v.stride(1) != n) or row % n != 0:
+            raise RuntimeError(f'bp_hip.pick_report: {name} must be dense behind its first dimension')
+        places.add((cols, row // n if batch > 1 else None))
+    widths = {c for c, _ in places}
+    strides = {r for _, r in places if r is not None}
+    if len(widths) != 1 or len(strides) > 1:
+        raise RuntimeError('bp_hip.pick_report: the records must share their width and their row stride')
+    rec_cols = widths.pop()
+    rec_stride = strides.pop() if strides else rec_cols
+    _call('bp_pick_report', logits.device, logits.data_ptr(), tokens.data_ptr(), counters.data_ptr(),
+          *[_ptr(given[name]) for name in PICK_REPORT_RECORDS], batch, vocab,
+          logits.stride(0) if batch > 1 else max(vocab, logits.stride(0)), tokens.stride(0) if batch > 1 else 1,
+          rec_cols, rec_stride, n_top, _PICK_DTYPES[logits.dtype])

@@ -1371,4 +1371,30 @@ int bp_score_rows(const void *logits, const int64_t *targets, float *logprob, in
     return launch_status(bp::launch_score_rows(p, dtype, static_cast<hipStream_t>(stream)));
 }
 
+// ---- the record of a pick (bp_pick_report) ----
+
+int bp_pick_report(const void *logits, const int64_t *tokens, const int32_t *counters, float *logprob, int32_t *rank,
+                   float *entropy, int32_t *top_idx, float *top_logprob, int rows, int vocab, int64_t row_stride,
+                   int64_t tokens_stride, int rec_cols, int64_t rec_stride, int n_top, int dtype, bp_stream_t stream) {
+    if (dtype != BP_DTYPE_F16 && dtype != BP_DTYPE_BF16 && dtype != BP_DTYPE_F32) return BP_ERR_DTYPE;
+    if (rows < 1 || vocab < 1 || vocab > 0x7fffffff - 16 || row_stride < vocab || tokens_stride < 1) return BP_ERR_SHAPE;
+    if (rec_cols < 1 || rec_stride < rec_cols) return BP_ERR_SHAPE;
+    if (n_top < 0 || n_top > BP_PICK_REPORT_MAX_TOP || n_top > vocab) return BP_ERR_SHAPE;
+    if (logits == nullptr || tokens == nullptr || counters == nullptr) return BP_ERR_SHAPE;
+    if (logprob == nullptr && rank == nullptr && entropy == nullptr && top_idx == nullptr && top_logprob == nullptr)
+        return BP_ERR_SHAPE;
+    if (n_top > 0 && top_idx == nullptr && top_logprob == nullptr) return BP_ERR_SHAPE;
+    const uintptr_t elem = dtype == BP_DTYPE_F32 ? 4 : 2;
+    if (reinterpret_cast<uintptr_t>(logits) % elem || reinterpret_cast<uintptr_t>(tokens) % 8) return BP_ERR_SHAPE;
+    for (const void *p4 : {(const void *)counters, (const void *)logprob, (const void *)rank, (const void *)entropy,
+                           (const void *)top_idx, (const void *)top_logprob})
+        if (reinterpret_cast<uintptr_t>(p4) % 4) return BP_ERR_SHAPE;
+    bp::PickReportParams p{};
+    p.logits = logits; p.tokens = tokens; p.counters = counters;
+    p.logprob = logprob; p.rank = rank; p.entropy = entropy; p.top_idx = top_idx; p.top_logprob = top_logprob;
+    p.row_stride = row_stride; p.tokens_stride = tokens_stride; p.rec_stride = rec_stride;
+    p.rows = rows; p.vocab = vocab; p.rec_cols = rec_cols; p.n_top = n_top;
+    return launch_status(bp::launch_pick_report(p, dtype, static_cast<hipStream_t>(stream)));
+}
+
 }  // extern "C"

@@ -454,4 +454,20 @@ struct ScoreParams {
 };
 hipError_t launch_score_rows(const ScoreParams &p, int dtype, hipStream_t stream);
 
+// bp_pick_report (pick_report.hip): per row of logits and the token just picked from it, the token's log-probability and rank,
+// the row's entropy and its n_top most likely tokens, written into column counters[b] of the record buffers
+constexpr int kPickReportMaxTop = BP_PICK_REPORT_MAX_TOP;
+struct PickReportParams {
+    const void *logits;          // (rows, vocab) 16-bit or fp32, element stride row_stride, last stride 1; only read
+    const int64_t *tokens;       // (rows), element stride tokens_stride
+    const int32_t *counters;     // (rows): the column of the records; outside [0, rec_cols) nothing is written for the row
+    float *logprob, *entropy;    // (rows, rec_cols), element stride rec_stride between rows; any record may be NULL
+    int32_t *rank;               // the same
+    int32_t *top_idx;            // (rows, rec_stride, n_top), dense in the last axis
+    float *top_logprob;          // the same
+    int64_t row_stride, tokens_stride, rec_stride;
+    int rows, vocab, rec_cols, n_top;
+};
+hipError_t launch_pick_report(const PickReportParams &p, int dtype, hipStream_t stream);
+
 }  // namespace bp

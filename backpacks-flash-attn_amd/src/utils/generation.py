@@ -9,6 +9,8 @@ cg=True inside the captured step (_decode_cached_picked); without them the loops
 form (bp_pick_token_lim): no n-gram twice, counted penalties on what was generated, ids that never appear.
 `prompt_lengths` (kv_cache=True only) takes a batch of right-padded prompts of different lengths: every row generates the same
 number of tokens behind ITS prompt (_CachedSteps; bp_pick_token_lim_rows where a limit or `min_new_tokens` needs the row's begin).
+`output_logprobs` / `top_logprobs` (kv_cache=True only) record what the model thought of every token it produced: one more
+launch behind each pick (bp_pick_report; _eager_report on CPU tensors), with cg=True inside the captured step (_PickRecord).
 Differences kept deliberately small: the result is a plain dataclass instead of the
 transformers `*DecoderOnlyOutput` classes (removed in transformers 5), and the appended token is
 `unsqueeze(1)` so batch sizes > 1 work (the reference's `unsqueeze(0)` in greedy_decode, :68, only
@@ -46,6 +48,14 @@ class DecoderOnlyOutput:
     sequences: torch.Tensor
     scores: Optional[Tuple[torch.Tensor, ...]] = None
     lengths: Optional[torch.Tensor] = None      # (batch,) int64: 1 + the column of every row's first EOS, when an EOS id is given
+    # The record of the picks (output_logprobs / top_logprobs, _PickRecord), aligned with `sequences` column for column: entry
+    # [b, c] describes sequences[b, c] under the logits it was picked from.  Prompt columns and the columns at or behind a
+    # row's end hold 0 (floats) and -1 (ranks, ids).
+    token_logprobs: Optional[torch.Tensor] = None       # (batch, width) fp32: log-probability of the token, raw logits
+    token_ranks: Optional[torch.Tensor] = None          # (batch, width) int32: its 0-based rank, ties towards the lower id
+    token_entropies: Optional[torch.Tensor] = None      # (batch, width) fp32: entropy of the distribution it came from
+    top_token_ids: Optional[torch.Tensor] = None        # (batch, width, n) int32: the n most likely tokens, best first
+    top_token_logprobs: Optional[torch.Tensor] = None   # (batch, width, n) fp32: their log-probabilities
 
 
 def _decode(input_ids, model, max_length, pick):
@@ -438,6 +448,89 @@ class _Picker:
         return pick
 
 
+PICK_REPORT_MAX_TOP = 16      # bp_pick_report: BP_PICK_REPORT_MAX_TOP of include/bp_hip.h
+
+
+def _eager_report(logits, tokens, counters, *, logprob=None, rank=None, entropy=None, top_idx=None, top_logprob=None):
+    """The contract of bp_pick_report (include/bp_hip.h) in torch ops, for tensors the kernel does not take (CPU); the
+    signature of bp_hip.pick_report.  Per row b with c = counters[b] in [0, cols) -- other rows are left alone -- column c of
+    the records that are given receives: logprob, rank and entropy of tokens[b] as _eager_score_rows (src/utils/scoring.py)
+    defines them, fp32; top_idx[b, c, i] the column of position i in the order (float(x) descending with -0 == +0, a NaN above
+    every number, column ascending) and top_logprob[b, c, i] = float(x) - lse of that element."""
+    from src.utils.scoring import _eager_score_rows
+    given = {'logprob': logprob, 'rank': rank, 'entropy': entropy, 'top_idx': top_idx, 'top_logprob': top_logprob}
+    if all(v is None for v in given.values()):
+        raise RuntimeError('_eager_report: give at least one record')
+    batch, vocab = logits.shape
+    tops = [v for v in (top_idx, top_logprob) if v is not None]
+    n_top = tops[0].shape[2] if tops else 0
+    if any(v.shape[2] != n_top for v in tops) or (tops and not 1 <= n_top <= min(vocab, PICK_REPORT_MAX_TOP)):
+        raise RuntimeError(f'_eager_report: top_idx and top_logprob hold the same 1 .. min(vocab, {PICK_REPORT_MAX_TOP}) entries')
+    cols = next(v for v in given.values() if v is not None).shape[1]
+    at = counters.long()
+    ok = (at >= 0) & (at < cols)
+    rows, at = torch.arange(batch, device=logits.device)[ok], at[ok]
+    got = _eager_score_rows(logits, tokens.reshape(batch).long(), want=('logprob', 'rank', 'lse', 'entropy'))
+    for name in ('logprob', 'rank', 'entropy'):
+        if given[name] is not None:
+            given[name][rows, at] = got[name][ok]
+    if n_top:
+        x = logits.float()
+        # the order as one float64 key: a NaN above +inf, -0 == +0; the stable sort keeps the lower column of equals first
+        key = x.double().clamp(max=torch.finfo(torch.float64).max)
+        key = torch.where(torch.isnan(x), float('inf'), key)
+        order = torch.sort(key, dim=1, descending=True, stable=True).indices[:, :n_top]
+        if top_idx is not None:
+            top_idx[rows, at] = order[ok].to(torch.int32)
+        if top_logprob is not None:
+            top_logprob[rows, at] = (x.gather(1, order) - got['lse'][:, None])[ok]
+
+
+class _PickRecord:
+    """The record of a generation's picks (output_logprobs / top_logprobs): buffers next to the `sequences` of a _CachedSteps --
+    the same rows, row stride (the cache capacity) and width; floats start at 0, ranks and ids at -1 -- and the report behind
+    every pick: bp_pick_report on CUDA tensors (one launch, no host value: inside the captured step with cg=True), else
+    _eager_report.  It gets the pick's logits, its counters (the column) and the token the pick just wrote."""
+
+    def __init__(self, steps, output_logprobs, top_logprobs):
+        rows, capacity = steps.sequences.shape[0], steps.sequences.stride(0)
+        device, width = steps.sequences.device, steps.width
+        self.n_top, self.records = int(top_logprobs), {}
+
+        def buffer(fill, dtype, *last):
+            return torch.full((rows, capacity) + last, fill, dtype=dtype, device=device)[:, :width]
+        if output_logprobs:
+            self.records.update(logprob=buffer(0.0, torch.float32), rank=buffer(-1, torch.int32),
+                                entropy=buffer(0.0, torch.float32))
+        if self.n_top:
+            self.records.update(top_idx=buffer(-1, torch.int32, self.n_top), top_logprob=buffer(0.0, torch.float32, self.n_top))
+
+    def __call__(self, logits, counters, tokens):
+        if self.n_top > logits.shape[1]:
+            raise ValueError(f'generation: top_logprobs = {self.n_top} exceeds the vocabulary ({logits.shape[1]})')
+        if logits.is_cuda:
+            import bp_hip
+            bp_hip.pick_report(logits, tokens, counters, **self.records)
+        else:
+            _eager_report(logits, tokens, counters, **self.records)
+
+    _FIELDS = {'logprob': 'token_logprobs', 'rank': 'token_ranks', 'entropy': 'token_entropies', 'top_idx': 'top_token_ids',
+               'top_logprob': 'top_token_logprobs'}
+
+    def fields(self, lengths, width):
+        """The fields of DecoderOnlyOutput, cut to `width` columns; with `lengths` (the rows' ends, as _trim_at_eos /
+        _trim_rows_at_eos return them) the columns at or behind a row's end are reset by the mask that writes the pad."""
+        out = {}
+        for name, rec in self.records.items():
+            rec = rec[:, :width]
+            if lengths is not None:
+                live = torch.arange(width, device=rec.device)[None, :] < lengths[:, None]
+                rec = torch.where(live if rec.dim() == 2 else live[:, :, None], rec,
+                                  torch.full_like(rec, 0 if rec.dtype.is_floating_point else -1))
+            out[self._FIELDS[name]] = rec.contiguous()
+        return out
+
+
 class _StopPoll:
     """Whether every row has finished, asked without draining the queue.  Every `every` steps the flags are copied into
     pinned host memory behind the steps queued so far, with an event behind the copy; the copy that is READ at that point is
@@ -573,7 +666,8 @@ class _CachedSteps:
                 break
 
 
-def _decode_cached_picked(input_ids, model, max_length, picker, cg=False, stop_check_every=None, prompt_lengths=None):
+def _decode_cached_picked(input_ids, model, max_length, picker, cg=False, stop_check_every=None, prompt_lengths=None,
+                          report=None):
     """_decode_cached with the pick on the device: the counter of a pick is `lengths_per_sample` after the step's
     increment, the pick writes the next step's input (`static_ids`) and column `position` of the preallocated `sequences`.
     With cg=True the captured graph is model step, length increment, pick: a generated token is one replay, with no launch
@@ -582,11 +676,19 @@ def _decode_cached_picked(input_ids, model, max_length, picker, cg=False, stop_c
     rows keep stepping on the pad token until then.  The result is cut at the rows' ends (_trim_at_eos), so it depends
     neither on the polling interval nor on how far the loop overran.
     With `prompt_lengths` every row generates exactly width - prompt tokens behind its own prompt: that many picks and no
-    further one, which would land inside a shorter row; `lengths` is always returned (_trim_rows_at_eos)."""
+    further one, which would land inside a shorter row; `lengths` is always returned (_trim_rows_at_eos).
+    With `report` = (output_logprobs, top_logprobs) every pick is followed by its record (_PickRecord) -- the captured graph is
+    then model step, length increment, pick, report -- and the result carries the record's fields, trimmed as `sequences` is."""
     d = _CachedSteps(input_ids, model, max_length, prompt_lengths=prompt_lengths, pad=picker.options.pad)
+    record = _PickRecord(d, *report) if report is not None else None
 
     def pick(logits):
         picker(logits, d.lengths, tokens=d.static_ids, sequences=d.sequences)
+        if record is not None:
+            record(logits, d.lengths, d.static_ids)
+
+    def recorded(sequences, lengths):
+        return {} if record is None else record.fields(lengths, sequences.shape[1])
 
     with torch.inference_mode():
         logits = d.prefill()
@@ -597,20 +699,31 @@ def _decode_cached_picked(input_ids, model, max_length, picker, cg=False, stop_c
                 pick(logits)
                 d.run(lambda: pick(d.step_logits()), new_tokens - 1, cg, _StopPoll(picker.finished, stop_check_every))
             sequences, lengths = _trim_rows_at_eos(sequences, prompt_lengths, new_tokens, o.eos_token_id, o.pad)
-            return DecoderOnlyOutput(sequences=sequences.to(input_ids.dtype), scores=(logits,), lengths=lengths)
+            return DecoderOnlyOutput(sequences=sequences.to(input_ids.dtype), scores=(logits,), lengths=lengths,
+                                     **recorded(sequences, lengths))
         pick(logits)
         d.run(lambda: pick(d.step_logits()), max_length - d.prompt - 1, cg, _StopPoll(picker.finished, stop_check_every))
         if o.eos_token_id is not None:
             sequences, lengths = _trim_at_eos(sequences, d.prompt, o.eos_token_id, o.pad)
-    return DecoderOnlyOutput(sequences=sequences.to(input_ids.dtype), scores=(logits,), lengths=lengths)
+        return DecoderOnlyOutput(sequences=sequences.to(input_ids.dtype), scores=(logits,), lengths=lengths,
+                                 **recorded(sequences, lengths))
 
 
 def _run_loop(input_ids, model, max_length, pick, do_sample, cg, kv_cache, rng_state, device_pick, stop_check_every,
-              pick_options, prompt_lengths=None):
-    """The loop greedy_decode / sample select: with the device pick (_Picker) when device_pick, an rng_state, prompt_lengths
-    or one of `pick_options` asks for it, else with the host's `pick` exactly as the reference runs."""
+              pick_options, prompt_lengths=None, output_logprobs=False, top_logprobs=0):
+    """The loop greedy_decode / sample select: with the device pick (_Picker) when device_pick, an rng_state, prompt_lengths,
+    a record (output_logprobs / top_logprobs) or one of `pick_options` asks for it, else with the host's `pick` exactly as the
+    reference runs."""
     if stop_check_every is not None and stop_check_every < 1:
         raise ValueError('generation: stop_check_every must be >= 1')
+    report = None
+    if output_logprobs or top_logprobs:
+        if not 0 <= int(top_logprobs) <= PICK_REPORT_MAX_TOP:
+            raise ValueError(f'generation: top_logprobs must lie in [0, {PICK_REPORT_MAX_TOP}]')
+        if not kv_cache:
+            raise ValueError('generation: output_logprobs and top_logprobs need kv_cache=True (the loops without a cache are '
+                             'the reference\'s, statement for statement)')
+        report = (bool(output_logprobs), int(top_logprobs))
     # the frequency / presence penalties count from the prompt length on: generated tokens only
     options = PickOptions(do_sample=do_sample, penalty_begin=input_ids.shape[1], **pick_options)
     if prompt_lengths is not None:
@@ -618,11 +731,11 @@ def _run_loop(input_ids, model, max_length, pick, do_sample, cg, kv_cache, rng_s
             raise ValueError('generation: prompt_lengths needs kv_cache=True (the loops without a cache are the reference\'s, '
                              'statement for statement)')
         prompt_lengths, _ = _check_prompt_lengths(prompt_lengths, input_ids)
-    if device_pick or rng_state is not None or options.wants_device_pick or prompt_lengths is not None:
+    if device_pick or rng_state is not None or options.wants_device_pick or prompt_lengths is not None or report is not None:
         picker = _Picker(options, rng_state, input_ids.device, prompt_lengths)
         if kv_cache:
             return _decode_cached_picked(input_ids, model, max_length, picker, cg=cg, stop_check_every=stop_check_every,
-                                         prompt_lengths=prompt_lengths)
+                                         prompt_lengths=prompt_lengths, report=report)
         if options.controlled:
             raise ValueError('generation: repetition_penalty, eos_token_id, pad_token_id, min_length, min_new_tokens, '
                              'no_repeat_ngram_size, frequency_penalty, presence_penalty and suppress_tokens need kv_cache=True '
@@ -636,7 +749,7 @@ def _run_loop(input_ids, model, max_length, pick, do_sample, cg, kv_cache, rng_s
 
 
 def greedy_decode(input_ids, model, max_length, cg=False, kv_cache=False, rng_state=None, device_pick=False,
-                  stop_check_every=None, prompt_lengths=None, **pick_options):
+                  stop_check_every=None, prompt_lengths=None, output_logprobs=False, top_logprobs=0, **pick_options):
     """input_ids (batch, seq_len) -> sequences (batch, max_length - 1): argmax continuation.
     cg=True: one captured full-width forward replayed per token (CUDA tensors only), see _decode_graphed.
     kv_cache=True: prefill once, then one cached step per token (with cg=True: one captured step), see _decode_cached.
@@ -649,13 +762,18 @@ def greedy_decode(input_ids, model, max_length, cg=False, kv_cache=False, rng_st
     always returned, is 1 + the column of the row's first EOS behind its prompt, else L_b + N; `scores` holds the logits of
     position L_b - 1 of every row; with an EOS id `sequences` is cut to the longest row.  With every L_b == seq_len the
     sequences are those of the call without the argument.
+    output_logprobs, top_logprobs = n <= 16 (kv_cache=True only; either selects the device pick): the record of the picks, as
+    fields of the result aligned with `sequences` column for column (DecoderOnlyOutput): with output_logprobs the log-probability
+    and rank of every generated token under the logits it was picked from (the model's: before temperature, penalties and
+    filters) and the entropy of that distribution; with top_logprobs the n most likely tokens of every step and their
+    log-probabilities.  `sequences` and `lengths` are those of the call without the two.
     pick_options: the keywords of PickOptions, see there."""
     return _run_loop(input_ids, model, max_length, lambda logits: torch.argmax(logits, dim=-1), False, cg, kv_cache, rng_state,
-                     device_pick, stop_check_every, pick_options, prompt_lengths)
+                     device_pick, stop_check_every, pick_options, prompt_lengths, output_logprobs, top_logprobs)
 
 
 def sample(input_ids, model, max_length, cg=False, kv_cache=False, rng_state=None, device_pick=False, stop_check_every=None,
-           prompt_lengths=None, **pick_options):
+           prompt_lengths=None, output_logprobs=False, top_logprobs=0, **pick_options):
     """Ancestral sampling from softmax(logits) (reference :23-48); cg / kv_cache as in greedy_decode.
     temperature, top_k (ties at the threshold kept, as the reference's top_k_filter, training/run_pplm.py:569-581), top_p:
     the usual filters; any of them, an `rng_state` or device_pick=True selects the device pick (bp_pick_token, contract in
@@ -663,11 +781,12 @@ def sample(input_ids, model, max_length, cg=False, kv_cache=False, rng_state=Non
     torch's generator when None; the token at sequence position t of row b is a pure function of (logits, rng_state, b, t),
     so cached, graphed and growing-prefix runs under one rng_state draw the same numbers.
     prompt_lengths: right-padded prompts of different lengths, as in greedy_decode; the position t of a draw is the row's own.
+    output_logprobs, top_logprobs: the record of the picks, as in greedy_decode.
     pick_options: the keywords of PickOptions, see there."""
     def pick(logits):
         return torch.distributions.Categorical(logits=torch.log_softmax(logits.float(), dim=-1)).sample()
     return _run_loop(input_ids, model, max_length, pick, True, cg, kv_cache, rng_state, device_pick, stop_check_every,
-                     pick_options, prompt_lengths)
+                     pick_options, prompt_lengths, output_logprobs, top_logprobs)
 
 
 # ---- beam search on the KV cache: bp_beam_pick / bp_beam_copy_rows, or their torch restatements on CPU tensors -----------------
@@ -894,6 +1013,11 @@ class GenerationMixin:
         whose per-token state looks across positions overrides this to refuse."""
         return {} if prompt_lengths is None else {'prompt_lengths': prompt_lengths}
 
+    @staticmethod
+    def _recorded(output_logprobs, top_logprobs):
+        """The keywords of a call that asks for a record, none without: such a call runs the statements it always ran."""
+        return {'output_logprobs': output_logprobs, 'top_logprobs': top_logprobs} if output_logprobs or top_logprobs else {}
+
     def _generate(self, decode, input_ids, max_length, return_dict_in_generate, output_scores, cg, kv_cache, **pick_options):
         output = decode(input_ids, self, max_length, cg=cg, kv_cache=kv_cache, **pick_options)
         if not output_scores:
@@ -901,19 +1025,22 @@ class GenerationMixin:
         return output if return_dict_in_generate else output.sequences
 
     def generate(self, input_ids, max_length, return_dict_in_generate=False, output_scores=False, cg=False, kv_cache=False,
-                 rng_state=None, device_pick=False, stop_check_every=None, prompt_lengths=None, **pick_options):
-        """greedy_decode on this model; prompt_lengths: right-padded prompts of different lengths, see there; pick_options:
-        the keywords of PickOptions."""
+                 rng_state=None, device_pick=False, stop_check_every=None, prompt_lengths=None, output_logprobs=False,
+                 top_logprobs=0, **pick_options):
+        """greedy_decode on this model; prompt_lengths: right-padded prompts of different lengths, see there; output_logprobs,
+        top_logprobs: the record of the picks (with return_dict_in_generate), see there; pick_options: the keywords of
+        PickOptions."""
         return self._generate(greedy_decode, input_ids, max_length, return_dict_in_generate, output_scores, cg, kv_cache,
                               rng_state=rng_state, device_pick=device_pick, stop_check_every=stop_check_every,
-                              **self._ragged(prompt_lengths), **pick_options)
+                              **self._ragged(prompt_lengths), **self._recorded(output_logprobs, top_logprobs), **pick_options)
 
     def sample(self, input_ids, max_length, return_dict_in_generate=False, output_scores=False, cg=False, kv_cache=False,
-               rng_state=None, device_pick=False, stop_check_every=None, prompt_lengths=None, **pick_options):
-        """sample on this model; prompt_lengths and pick_options as generate's."""
+               rng_state=None, device_pick=False, stop_check_every=None, prompt_lengths=None, output_logprobs=False,
+               top_logprobs=0, **pick_options):
+        """sample on this model; prompt_lengths, output_logprobs, top_logprobs and pick_options as generate's."""
         return self._generate(sample, input_ids, max_length, return_dict_in_generate, output_scores, cg, kv_cache,
                               rng_state=rng_state, device_pick=device_pick, stop_check_every=stop_check_every,
-                              **self._ragged(prompt_lengths), **pick_options)
+                              **self._ragged(prompt_lengths), **self._recorded(output_logprobs, top_logprobs), **pick_options)
 
     def beam_search(self, input_ids, max_length, num_beams, return_dict_in_generate=False, eos_token_id=None,
                     pad_token_id=None, length_penalty=0.0, cg=False, stop_check_every=None, prompt_lengths=None,

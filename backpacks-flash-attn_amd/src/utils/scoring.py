@@ -22,6 +22,7 @@ from src.utils.packing import pack_sequences
 
 TokenScores = namedtuple('TokenScores', ['logprobs', 'ranks', 'top1', 'entropy', 'lse', 'mask'])
 SequenceScores = namedtuple('SequenceScores', ['logprob', 'count', 'all_top1'])
+GenerationScores = namedtuple('GenerationScores', ['logprob', 'count', 'perplexity'])
 
 SCORE_OUTPUTS = bp_hip.SCORE_OUTPUTS
 HEAD_BLOCK_ROWS = 2048       # rows of one LM-head GEMM of score_tokens (_head_block): 206 MB of bf16 logits at 50 264 columns
@@ -200,6 +201,27 @@ def sequence_scores(model, input_ids, lengths=None, prefix_lengths=None, chunk_t
                        packed=packed)
     return SequenceScores(logprob=got.logprobs.double().sum(dim=1), count=got.mask.sum(dim=1),
                           all_top1=((got.ranks == 0) | ~got.mask).all(dim=1))
+
+
+def generation_logprob(output, prompt_lengths=None):
+    """The likelihood a generation had when it was produced, from the record of its picks: `output` is the DecoderOnlyOutput of
+    greedy_decode / sample (or GenerationMixin.generate / .sample with return_dict_in_generate) under output_logprobs=True.
+    Per row, over its generated tokens -- the columns with a rank >= 0: behind the prompt and in front of the row's end, the EOS
+    itself included -- SequenceScores-like (logprob, count, perplexity): the float64 sum of `token_logprobs`, the int64 token
+    count and exp(-logprob / count) (NaN for a row that generated nothing).  Unlike a second pass with sequence_scores this is
+    the distribution each token was picked from, also for models whose cached step and full forward differ (the annealed
+    WeightedBackpackLMHeadModel).  prompt_lengths (B,): count only columns >= the row's prompt length (the record holds nothing
+    in front of it anyway; given for symmetry with greedy_decode)."""
+    if output.token_logprobs is None or output.token_ranks is None:
+        raise ValueError('generation_logprob: the output carries no record; generate with output_logprobs=True')
+    live = output.token_ranks >= 0
+    if prompt_lengths is not None:
+        begin = torch.as_tensor(prompt_lengths, device=live.device).long()
+        live = live & (torch.arange(live.shape[1], device=live.device)[None, :] >= begin[:, None])
+    logprob = torch.where(live, output.token_logprobs.double(), 0.0).sum(dim=1)
+    count = live.sum(dim=1)
+    perplexity = torch.where(count > 0, torch.exp(-logprob / count.clamp(min=1)), math.nan)
+    return GenerationScores(logprob=logprob, count=count, perplexity=perplexity)
 
 
 def _batch_of(batch):

@@ -60,7 +60,9 @@ extern "C" {
                               and one more: bp_score_rows, what an evaluation keeps of a row of logits -- log-probability and
                               rank of the gold token, log-sum-exp, greedy token, entropy -- in one pass over the row;
                               and three more: bp_sense_lse_varlen / bp_sense_mix_varlen / bp_sense_mix_gather_varlen, the sense
-                              kernels on packed batches described by cu_seqlens) */
+                              kernels on packed batches described by cu_seqlens;
+                              and one more: bp_pick_report, the record of a decode step's pick -- log-probability and rank of
+                              the token, entropy, the n most likely tokens -- in the record column the counter names) */
 
 /* element type of q/k/v/out/content tensors */
 #define BP_DTYPE_F16 0
@@ -95,6 +97,7 @@ extern "C" {
 #define BP_SIMILARITY_MAX_QUERY_ROWS 64        /* bp_sense_similarity: nq * nsenses, the query rows of one call */
 
 #define BP_SCORE_MAX_TARGETS 8                 /* bp_score_rows: target columns per row */
+#define BP_PICK_REPORT_MAX_TOP 16              /* bp_pick_report: most likely tokens recorded per pick */
 
 #define BP_QUEUE_WS_BYTES 64  /* `queue_ws` of the persistent sense-mix launches */
 
@@ -1052,6 +1055,38 @@ int bp_sense_similarity(const void *table, const int32_t *cand_index, const void
 int bp_score_rows(const void *logits, const int64_t *targets, float *logprob, int32_t *rank, float *lse, int32_t *top1,
                   float *entropy, int64_t rows, int cols, int ntargets, int64_t row_stride, int64_t target_stride,
                   int64_t out_stride, int dtype, bp_stream_t stream);
+
+/*
+ * bp_pick_report -- the record of a pick: what the model thought of the token a decode step just chose.  Per row b of logits,
+ * with c = counters[b], t = tokens[b * tokens_stride] and x_j = float(logits[b, j]), in ONE launch that reads no host value
+ * (legal inside a HIP-graph capture, right behind bp_pick_token* with the same logits, counters and tokens):
+ *   c outside [0, rec_cols)   nothing is written for the row -- the pick's rule for `sequences`, so the record of the final,
+ *                             dropped pick of a decode loop is dropped with it
+ *   lse, logprob[b, c], rank[b, c], entropy[b, c]   exactly bp_score_rows' definitions with the one target t, fp32: logprob =
+ *                             x_t - lse, rank = #{x_j > x_t} + #{j < t : x_j == x_t}; t outside [0, vocab) gives logprob 0 and
+ *                             rank -1; rows with a NaN, a +inf or nothing but -inf follow the extended reals as described there
+ *   top_idx[b, c, i]          the column of position i, 0 <= i < n_top, in the order (x descending as converted floats with
+ *                             -0 == +0, a NaN above every number, column ascending): bp_pick_token's greedy order, so
+ *                             top_idx[b, c, 0] is the greedy token on every row.  A total order on integers: the answer is
+ *                             unique.  On a NaN-free row the element at position i has rank i.
+ *   top_logprob[b, c, i]      float(x) - lse of that element: one fp32 subtraction against the lse of this call
+ * (The log-probabilities are the model's: of the raw logits, before temperature, penalties and filters.)
+ *   logits    (rows, vocab) fp16 / bf16 / fp32, element stride row_stride >= vocab, last stride 1; a row may start at any
+ *             element.  Only read.
+ *   tokens    int64, element stride tokens_stride >= 1;  counters  int32 (rows)
+ *   logprob, entropy  fp32 and  rank  int32: (rows, rec_cols) with ONE element stride rec_stride >= rec_cols between rows
+ *   top_idx   int32 and  top_logprob  fp32: (rows, rec_stride, n_top), dense in the last axis
+ *             Any of the five may be NULL (not written); all five NULL is BP_ERR_SHAPE.
+ *   n_top     0 <= n_top <= min(vocab, BP_PICK_REPORT_MAX_TOP)
+ * One 1024-thread workgroup per row, max(1, n_top) passes over the row, no workspace, no atomics, every reduction in a fixed
+ * order: two calls agree bit for bit.  (Additive, ABI still 11.)
+ * Errors, before any launch: BP_ERR_DTYPE; BP_ERR_SHAPE (rows < 1, vocab < 1 or > 2^31 - 17, row_stride < vocab, tokens_stride
+ * < 1, rec_cols < 1, rec_stride < rec_cols, n_top out of range, n_top > 0 with both top pointers NULL, a NULL logits / tokens /
+ * counters, every record NULL, logits not aligned to its element, tokens not 8-byte, counters or a record not 4-byte aligned).
+ */
+int bp_pick_report(const void *logits, const int64_t *tokens, const int32_t *counters, float *logprob, int32_t *rank,
+                   float *entropy, int32_t *top_idx, float *top_logprob, int rows, int vocab, int64_t row_stride,
+                   int64_t tokens_stride, int rec_cols, int64_t rec_stride, int n_top, int dtype, bp_stream_t stream);
 
 #ifdef __cplusplus
 }

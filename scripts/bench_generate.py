@@ -19,7 +19,8 @@ polling of the finished flags alone), --min-length and --stop-check-every (kv le
 that alternates with the others: the device pick with some generation options replaced, e.g.
 `--variant pen:repetition_penalty=1.2 --variant n4:eos_token_id=50263,stop_check_every=4`, or with the limits of
 bp_pick_token_lim `--variant all:no_repeat_ngram_size=3,frequency_penalty=0.5,presence_penalty=0.5,suppress_tokens=11+12+13`
-(a list is written a+b+c).
+(a list is written a+b+c), or with the record of the picks (bp_pick_report, one more launch per token; kv legs only)
+`--variant rec:output_logprobs=1 --variant rec5:output_logprobs=1,top_logprobs=5`.
 
 --prompt-lengths LO:HI[:SEED] (kv legs only) adds two further picks that alternate with the others: `ragged`, the device pick
 with prompt_lengths drawn once on the host, uniformly from LO..HI (seed SEED, default 0) with the maximum forced to --prompt,
