@@ -1,6 +1,6 @@
 // bp_beam_pick: one decode step of beam search for `groups` prompts x `beam_width` (W <= 8) beams, rows r = g W + w.  No host
-// value enters, so one captured launch pair serves every step.  The row reader (RowView, PickElem) and the 40-bit
-// fixed-point masses are pick_core.h's; nothing of the pick kernels is instantiated here.
+// value enters, so one captured launch pair serves every step.  The row reader (RowView, RowElem) and the 40-bit
+// fixed-point masses are vocab_row.h's.
 //
 // Contract per group g (restated by _eager_beam_pick, src/utils/generation.py, and by tests/beam_ref.py):
 //   candidates  a live row w (finished == NULL or finished[gW+w] == 0): m = max_v float(x_v), lse = m + log sum_v exp(float(x_v) - m)
@@ -24,7 +24,8 @@
 // 16 waves by wave 0.  W keys per row go to `ws`.  Stage 2, one wave per group: lane 8 w + i holds candidate i of row w,
 // W rounds of a wave maximum on (score, 7 - w, ~v) pick the winners, every lane runs the slot walk on two bit masks, and
 // lane j stores winner j.  Integer keys and integer sums: the result is bit-identical across calls.
-#include "pick_core.h"
+#include "bp_kernels.h"
+#include "vocab_row.h"
 
 namespace bp {
 
@@ -46,7 +47,7 @@ BP_DEV void cmp_swap(u64 &hi, u64 &lo) {
 
 template <class ET>
 __global__ __launch_bounds__(kPickThreads) void beam_rows_kernel(const BeamPickParams p) {
-    using E = PickElem<ET>;
+    using E = RowElem<ET>;
     __shared__ u64 sh_wave[kPickWaves];
     __shared__ u64 sh_best[kPickWaves * kBeamMax];
     const int r = blockIdx.x, W = p.beam_width;
@@ -215,8 +216,7 @@ hipError_t launch_beam_pick(const BeamPickParams &p, int dtype, hipStream_t stre
         hipLaunchKernelGGL(beam_merge_kernel, dim3((unsigned)p.groups), dim3(64), 0, stream, p);
         return hipGetLastError();
     };
-    if (dtype == BP_DTYPE_F32) return go(float{});
-    return with_dtype(dtype, go);
+    return with_row_dtype(dtype, go);
 }
 
 }  // namespace bp

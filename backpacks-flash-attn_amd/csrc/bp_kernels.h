@@ -14,6 +14,8 @@ namespace bp {
 // arguments as they are (`kernel<decltype(et), kd, vec>`).  Only what a lambda body names is instantiated: a restriction
 // of the instantiation set is an `if constexpr` in the body.
 template <class F> hipError_t with_dtype(int dtype, F &&f) { return dtype == BP_DTYPE_BF16 ? f(BF16{}) : f(F16{}); }
+// the kernels over rows of logits (vocab_row.h) also take fp32: f receives float{} then
+template <class F> hipError_t with_row_dtype(int dtype, F &&f) { return dtype == BP_DTYPE_F32 ? f(float{}) : with_dtype(dtype, f); }
 
 template <class F> hipError_t with_flag(bool b, F &&f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
 

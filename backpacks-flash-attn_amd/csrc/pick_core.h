@@ -67,12 +67,14 @@
 #pragma once
 #include <type_traits>
 
-#include "bp_common.h"
 #include "bp_kernels.h"
 #include "bp_philox.h"
+#include "vocab_row.h"
 
 namespace bp {
 
+// Plain form: the tag is the element type itself
+template <class ET> using Plain = ET;
 // Controlled form: the flag rides on the element tag (as Weighted<ET> in decode_core.h)
 template <class ET> struct Controlled {};
 // Limited form: the controlled one with the row limits of bp_pick_token_lim
@@ -107,89 +109,6 @@ struct LimLayout {
 
 namespace {
 
-constexpr int kPickThreads = 1024;
-constexpr int kPickWaves = kPickThreads / 64;
-constexpr int kHistCopies = 32;
-constexpr int kHistStride = 257;
-constexpr float kFixedOne = 1099511627776.f;   // 2^40
-
-typedef unsigned long long u64;
-
-template <class ET> struct PickElem;   // raw bits of an element <-> float, 16-byte loads, the order-preserving key
-template <> struct PickElem<float> {
-    static constexpr int N = 4, EB = 4, KEY_BITS = 32;
-    static BP_DEV float to_f32(uint32_t raw) { return as_f32(raw); }
-    static BP_DEV uint32_t one(const char *p) { return *reinterpret_cast<const uint32_t *>(p); }
-    static BP_DEV void load(const char *p, uint32_t (&raw)[8]) {
-        const u32x4 w = *reinterpret_cast<const u32x4 *>(p);
-        const uint32_t a = w[0], b = w[1], c = w[2], d = w[3];
-        raw[0] = a; raw[1] = b; raw[2] = c; raw[3] = d;
-    }
-    static BP_DEV uint32_t key(uint32_t raw) { return raw ^ ((raw & 0x80000000u) ? 0xffffffffu : 0x80000000u); }
-    static BP_DEV uint32_t unkey(uint32_t k) { return k ^ ((k & 0x80000000u) ? 0x80000000u : 0xffffffffu); }
-};
-template <class H> struct PickElem16 {
-    static constexpr int N = 8, EB = 2, KEY_BITS = 16;
-    static BP_DEV float to_f32(uint32_t raw) { return Elem<H>::lo_f32(raw); }
-    static BP_DEV uint32_t one(const char *p) { return *reinterpret_cast<const uint16_t *>(p); }
-    static BP_DEV void load(const char *p, uint32_t (&raw)[8]) {
-        const u32x4 w = *reinterpret_cast<const u32x4 *>(p);
-        const uint32_t a = w[0], b = w[1], c = w[2], d = w[3];
-        raw[0] = a & 0xffffu; raw[1] = a >> 16; raw[2] = b & 0xffffu; raw[3] = b >> 16;
-        raw[4] = c & 0xffffu; raw[5] = c >> 16; raw[6] = d & 0xffffu; raw[7] = d >> 16;
-    }
-    static BP_DEV uint32_t key(uint32_t raw) { return raw ^ ((raw & 0x8000u) ? 0xffffu : 0x8000u); }
-    static BP_DEV uint32_t unkey(uint32_t k) { return k ^ ((k & 0x8000u) ? 0x8000u : 0xffffu); }
-};
-template <> struct PickElem<BF16> : PickElem16<BF16> {};
-template <> struct PickElem<F16> : PickElem16<F16> {};
-
-BP_DEV u64 shfl_xor_u64(u64 v, int mask) {
-    const uint32_t lo = __shfl_xor((uint32_t)v, mask), hi = __shfl_xor((uint32_t)(v >> 32), mask);
-    return ((u64)hi << 32) | lo;
-}
-BP_DEV u64 shfl_up_u64(u64 v, int delta) {
-    const uint32_t lo = __shfl_up((uint32_t)v, delta), hi = __shfl_up((uint32_t)(v >> 32), delta);
-    return ((u64)hi << 32) | lo;
-}
-BP_DEV u64 shfl_u64(u64 v, int lane) {
-    const uint32_t lo = __shfl((uint32_t)v, lane), hi = __shfl((uint32_t)(v >> 32), lane);
-    return ((u64)hi << 32) | lo;
-}
-BP_DEV u64 wave_sum_u64(u64 v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += shfl_xor_u64(v, o);
-    return v;
-}
-BP_DEV u64 wave_max_u64(u64 v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const u64 w = shfl_xor_u64(v, o);
-        v = w > v ? w : v;
-    }
-    return v;
-}
-// inclusive prefix sum over the lanes of a wave
-BP_DEV u64 wave_scan_u64(u64 v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u64 w = shfl_up_u64(v, o);
-        if (lane >= o) v += w;
-    }
-    return v;
-}
-
-// value part of the argmax key: NaN above everything, -0 == +0, otherwise the order of the floats
-BP_DEV uint32_t greedy_key(float x) {
-    if (x != x) return 0xffffffffu;
-    const uint32_t raw = as_u32(x + 0.f);   // -0 + 0 = +0
-    return raw ^ ((raw & 0x80000000u) ? 0xffffffffu : 0x80000000u);
-}
-BP_DEV float greedy_unkey(uint32_t k) { return as_f32(k ^ ((k & 0x80000000u) ? 0x80000000u : 0xffffffffu)); }
-
-// exp(z - m) in fixed point; z <= m, m finite
-BP_DEV u64 fixed_mass(float z, float m) { return (u64)(fast_exp2((z - m) * kLog2e) * kFixedOne); }
-
 struct PickShared {
     u64 hist[kHistCopies * kHistStride];
     u64 bins[256];
@@ -200,49 +119,9 @@ struct PickShared {
     uint32_t sel_digit;
 };
 
-// The row as seen by one lane: chunks of N elements on 16-byte boundaries of the address space (chunk 0 starts at or
-// before the row), wave w owning the chunks [w cpw, (w + 1) cpw).  Chunks that reach outside the row are read element
-// by element; `mask` has a bit per valid element.
-template <class ET> struct RowView {
-    using E = PickElem<ET>;
-    const char *vbase;   // address of chunk 0
-    int head, vocab, nch, cpw;
-    BP_DEV RowView(const char *row, int vocab_) : vocab(vocab_) {
-        head = (int)((reinterpret_cast<uintptr_t>(row) & 15u) / E::EB);
-        vbase = row - head * E::EB;
-        nch = (vocab + head + E::N - 1) / E::N;
-        cpw = (nch + kPickWaves - 1) / kPickWaves;
-    }
-    BP_DEV int steps() const { return (cpw + 63) / 64; }
-    // chunk of (wave, step, lane), -1 past the wave's run
-    BP_DEV int chunk(int wave, int step, int lane) const {
-        const int local = step * 64 + lane;
-        const int c = wave * cpw + local;
-        return (local < cpw && c < nch) ? c : -1;
-    }
-    // returns the column of element 0 of the chunk (may be negative for chunk 0)
-    BP_DEV int load(int c, uint32_t (&raw)[8], uint32_t &mask) const {
-        const int col0 = c * E::N - head;
-        if (col0 >= 0 && col0 + E::N <= vocab) {
-            E::load(vbase + (int64_t)c * 16, raw);
-            mask = (1u << E::N) - 1u;
-        } else {
-            mask = 0;
-#pragma unroll
-            for (int i = 0; i < E::N; ++i) {
-                const int col = col0 + i;
-                const bool ok = col >= 0 && col < vocab;
-                raw[i] = ok ? E::one(vbase + ((int64_t)c * E::N + i) * E::EB) : 0u;
-                if (ok) mask |= 1u << i;
-            }
-        }
-        return col0;
-    }
-};
-
 // The value of an element as every pass sees it.  Plain rows: x = float(raw), z = x * (1 / T).
 template <class TAG> struct Logits {
-    using E = PickElem<typename PickTag<TAG>::elem>;
+    using E = RowElem<typename PickTag<TAG>::elem>;
     float inv_t;
     BP_DEV Logits(const PickParams &p, int, const uint32_t *) : inv_t(p.inv_t) {}
     struct Chunk {};
@@ -254,7 +133,7 @@ template <class TAG> struct Logits {
 // of chunk c and the membership bits of its elements, bit i for column col0 + i (the bitmap carries one spare word: two
 // words cover any chunk).
 template <class ET> struct Logits<Controlled<ET>> {
-    using E = PickElem<ET>;
+    using E = RowElem<ET>;
     const uint32_t *bitmap;   // NULL: no history (theta == 1, no sequences, or nothing in front of the position)
     float inv_t, theta, inv_theta;
     int eos;                  // the masked column, -1 for none
@@ -280,7 +159,7 @@ template <class ET> struct Logits<Controlled<ET>> {
 
 // Limited rows: the controlled value, then the count penalty, then the ban (layout and build: header comment, LimLayout).
 template <class ET> struct Logits<Limited<ET>> {
-    using E = PickElem<ET>;
+    using E = RowElem<ET>;
     const uint32_t *members, *banned, *table;   // dynamic LDS; NULL: that control is off
     float inv_t, theta, inv_theta, freq, pres;
     int eos, shift;
@@ -429,15 +308,15 @@ struct LimOutputs {
 // Key source of the radix select.  Plain rows: the order-preserving key of the RAW element (x -> z is monotone), 16 or 32
 // bits.  Controlled rows: the 32-bit key of the fp32 z, whose threshold is z itself.
 template <class TAG> struct SelectKey {
-    using E = PickElem<typename PickTag<TAG>::elem>;
+    using E = RowElem<typename PickTag<TAG>::elem>;
     static constexpr int BITS = E::KEY_BITS;
     static BP_DEV uint32_t key(uint32_t raw, float) { return E::key(raw); }
     static BP_DEV float threshold(uint32_t k, float inv_t) { return E::to_f32(E::unkey(k)) * inv_t; }
 };
 template <class ET> struct SelectKey<Controlled<ET>> {
     static constexpr int BITS = 32;
-    static BP_DEV uint32_t key(uint32_t, float z) { return PickElem<float>::key(as_u32(z)); }
-    static BP_DEV float threshold(uint32_t k, float) { return as_f32(PickElem<float>::unkey(k)); }
+    static BP_DEV uint32_t key(uint32_t, float z) { return RowElem<float>::key(as_u32(z)); }
+    static BP_DEV float threshold(uint32_t k, float) { return as_f32(RowElem<float>::unkey(k)); }
 };
 template <class ET> struct SelectKey<Limited<ET>> : SelectKey<Controlled<ET>> {};
 template <class ET> struct SelectKey<RowLimited<ET>> : SelectKey<Controlled<ET>> {};
@@ -449,7 +328,7 @@ template <class ET> struct SelectKey<RowLimited<ET>> : SelectKey<Controlled<ET>>
 template <class TAG, bool WEIGHTED>
 BP_DEV uint32_t radix_select(const RowView<typename PickTag<TAG>::elem> &row, PickShared &sh, const Logits<TAG> &lg, float zmax,
                              float lo, u64 target, float top_p) {
-    using E = PickElem<typename PickTag<TAG>::elem>;
+    using E = RowElem<typename PickTag<TAG>::elem>;
     using KEY = SelectKey<TAG>;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     uint32_t prefix = 0;
@@ -522,7 +401,7 @@ BP_DEV uint32_t radix_select(const RowView<typename PickTag<TAG>::elem> &row, Pi
 template <class TAG>
 __global__ __launch_bounds__(kPickThreads) void pick_token_kernel(const PickParams p) {
     using ET = typename PickTag<TAG>::elem;
-    using E = PickElem<ET>;
+    using E = RowElem<ET>;
     constexpr bool CTL = PickTag<TAG>::ctl;
     __shared__ PickShared sh;
     const int b = blockIdx.x;
@@ -739,6 +618,22 @@ __global__ __launch_bounds__(kPickThreads) void pick_token_kernel(const PickPara
         float *st = p.stats + (int64_t)b * 4;
         st[0] = st_lo; st[1] = st_lse; st[2] = st_count; st[3] = st_u;
     }
+}
+
+// One workgroup per row of pick_token_kernel<TAG<ET>> with `lds` bytes of dynamic LDS (none for the plain form,
+// TAG = Plain).  Each pick_token*.hip calls this once: the instantiations land in the caller's code object.
+template <template <class> class TAG>
+hipError_t launch_pick(const PickParams &p, size_t lds, int dtype, hipStream_t stream) {
+    return with_row_dtype(dtype, [&](auto et) {
+        auto kernel = pick_token_kernel<TAG<decltype(et)>>;
+        if (lds > 48 * 1024) {   // ask for the large dynamic allocation by name
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL(kernel, dim3((unsigned)p.batch), dim3(kPickThreads), lds, stream, p);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace bp

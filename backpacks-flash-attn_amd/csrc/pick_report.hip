@@ -4,8 +4,8 @@
 // log_softmax / topk readouts of the reference's scripts (training/src/interactive.py and modulate_generate.py: print_topk;
 // training/src/test_topic.py: the likelihood of a generation), which need a row of logits on the host that the captured
 // decode step never produces.  The contract is the comment of bp_pick_report in include/bp_hip.h; _eager_report
-// (src/utils/generation.py) and tests/pick_report_ref.py restate it.  The row reader (RowView, PickElem) and the argmax key
-// (greedy_key) are pick_core.h's; nothing of the pick kernels is instantiated here.
+// (src/utils/generation.py) and tests/pick_report_ref.py restate it.  The row reader (RowView, RowElem), the argmax key
+// (greedy_key) and the (m, s, t) statistics are vocab_row.h's.
 //
 // One 1024-thread workgroup per row, 16-byte loads, a row whose counter lies outside [0, rec_cols) returns at once.
 //   pass 1    the statistics of bp_score_rows with one target, per lane and online: (m, s, t) = the maximum, sum e^(x - m) and
@@ -20,7 +20,8 @@
 // Algorithmic bytes: the row max(1, n_top) times -- once from wherever the LM-head GEMM left it, the rest from L2 -- plus at
 // most 12 + 8 n_top bytes of stores per row.  No global workspace, no global atomics, vector stores only; every loop is
 // bounded by the row's steps or by n_top; no register array is indexed by a variable.
-#include "pick_core.h"
+#include "bp_kernels.h"
+#include "vocab_row.h"
 
 namespace bp {
 
@@ -31,19 +32,6 @@ struct ReportShared {
     int cnt[kPickWaves];
     u64 key[2][kPickWaves];   // by the parity of the pass: a pass writes while a slow wave may still read the previous one
 };
-
-constexpr uint32_t kReportLowestBits = 0xff7fffffu;   // -FLT_MAX
-
-// two partial (m, s, t): as score_rows.hip's score_merge
-BP_DEV void report_merge(float &m, float &s, float &t, float m2, float s2, float t2) {
-    const float mn = fmaxf(m, m2);
-    // exp2(-inf - -inf) would be NaN: an empty partial has s = t = 0 and is skipped by the select
-    const float a = (m == -INFINITY) ? 0.f : fast_exp2((m - mn) * kLog2e);
-    const float b = (m2 == -INFINITY) ? 0.f : fast_exp2((m2 - mn) * kLog2e);
-    s = s * a + s2 * b;
-    t = t * a + t2 * b;
-    m = mn;
-}
 
 // the maximum over the workgroup of a 64-bit key, to every thread; `slot` alternates between consecutive calls
 BP_DEV u64 report_block_max(ReportShared &sh, int slot, u64 v, int lane, int wave) {
@@ -60,7 +48,7 @@ BP_DEV u64 report_block_max(ReportShared &sh, int slot, u64 v, int lane, int wav
 
 template <class ET>
 __global__ __launch_bounds__(kPickThreads) void pick_report_kernel(const PickReportParams p) {
-    using E = PickElem<ET>;
+    using E = RowElem<ET>;
     __shared__ ReportShared sh;
     const int b = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -94,20 +82,12 @@ __global__ __launch_bounds__(kPickThreads) void pick_report_kernel(const PickRep
             v[i] = ((mask >> i) & 1u) ? E::to_f32(raw[i]) : -INFINITY;   // outside the row: adds nothing to s and t
             cm = fmaxf(cm, v[i]);
         }
-        if (cm > m) {   // the maximum moves: rescale (m = -inf: s = t = 0, exp2(-inf) = 0)
-            const float f = fast_exp2((m - cm) * kLog2e);
-            s *= f;
-            t *= f;
-            m = cm;
-        }
-        const float ms = (m == -INFINITY) ? 0.f : m;   // -inf - -inf would be a NaN
+        if (cm > m) online_rescale(m, s, t, cm);   // the maximum moves
+        const float ms = online_shift(m);
         float cs = 0.f, ct = 0.f;
 #pragma unroll
         for (int i = 0; i < E::N; ++i) {
-            const float e = fast_exp2((v[i] - ms) * kLog2e);
-            cs += e;
-            // a -inf entry has e = 0 and must add 0, not 0 * -inf: its bits are clamped to those of -FLT_MAX
-            ct = fmaf(e, as_f32(min(as_u32(v[i]), kReportLowestBits)), ct);
+            online_term(v[i], ms, cs, ct);
             const bool valid = (mask >> i) & 1u;
             cnt += (valid && (v[i] > xt || (v[i] == xt && col0 + i < tc))) ? 1 : 0;
             const u64 k = ((u64)greedy_key(v[i]) << 32) | (uint32_t)~(uint32_t)(col0 + i);
@@ -119,7 +99,7 @@ __global__ __launch_bounds__(kPickThreads) void pick_report_kernel(const PickRep
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) {
         const float m2 = __shfl_xor(m, o), s2 = __shfl_xor(s, o), t2 = __shfl_xor(t, o);
-        report_merge(m, s, t, m2, s2, t2);
+        merge_mst(m, s, t, m2, s2, t2);
         cnt += __shfl_xor(cnt, o);
     }
     if (lane == 0) { sh.m[wave] = m; sh.s[wave] = s; sh.t[wave] = t; sh.cnt[wave] = cnt; }
@@ -127,7 +107,7 @@ __global__ __launch_bounds__(kPickThreads) void pick_report_kernel(const PickRep
     m = sh.m[0]; s = sh.s[0]; t = sh.t[0]; cnt = sh.cnt[0];
 #pragma unroll
     for (int w = 1; w < kPickWaves; ++w) {
-        report_merge(m, s, t, sh.m[w], sh.s[w], sh.t[w]);
+        merge_mst(m, s, t, sh.m[w], sh.s[w], sh.t[w]);
         cnt += sh.cnt[w];
     }
     // The degenerate rows, by the arithmetic of the definitions (bp_score_rows): a NaN makes everything NaN; +inf gives
@@ -176,8 +156,7 @@ hipError_t launch_pick_report(const PickReportParams &p, int dtype, hipStream_t 
         hipLaunchKernelGGL((pick_report_kernel<decltype(et)>), dim3((unsigned)p.rows), dim3(kPickThreads), 0, stream, p);
         return hipGetLastError();
     };
-    if (dtype == BP_DTYPE_F32) return go(float{});
-    return with_dtype(dtype, go);
+    return with_row_dtype(dtype, go);
 }
 
 }  // namespace bp

@@ -4,13 +4,6 @@
 
 namespace bp {
 
-hipError_t launch_pick_token(const PickParams &p, int dtype, hipStream_t stream) {
-    auto go = [&](auto et) {
-        hipLaunchKernelGGL((pick_token_kernel<decltype(et)>), dim3((unsigned)p.batch), dim3(kPickThreads), 0, stream, p);
-        return hipGetLastError();
-    };
-    if (dtype == BP_DTYPE_F32) return go(float{});
-    return with_dtype(dtype, go);
-}
+hipError_t launch_pick_token(const PickParams &p, int dtype, hipStream_t stream) { return launch_pick<Plain>(p, 0, dtype, stream); }
 
 }  // namespace bp

@@ -6,23 +6,12 @@
 
 namespace bp {
 
-// dynamic LDS: the history bitmap, one bit per vocabulary entry and one spare word; none without a penalty
+// dynamic LDS: the history bitmap, one bit per vocabulary entry and one spare word; none without a penalty.  Above 48 KB
+// (vocabularies above 393 184) launch_pick asks for the large allocation.
 size_t pick_ctl_lds_bytes(const PickParams &p) { return p.theta != 1.f ? ((size_t)(p.vocab + 31) / 32 + 1) * 4 : 0; }
 
 hipError_t launch_pick_token_ctl(const PickParams &p, int dtype, hipStream_t stream) {
-    const size_t lds = pick_ctl_lds_bytes(p);
-    auto go = [&](auto et) {
-        auto kernel = pick_token_kernel<Controlled<decltype(et)>>;
-        if (lds > 48 * 1024) {   // vocabularies above 393 184: ask for the large dynamic allocation by name
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(kernel, dim3((unsigned)p.batch), dim3(kPickThreads), lds, stream, p);
-        return hipGetLastError();
-    };
-    if (dtype == BP_DTYPE_F32) return go(float{});
-    return with_dtype(dtype, go);
+    return launch_pick<Controlled>(p, pick_ctl_lds_bytes(p), dtype, stream);
 }
 
 }  // namespace bp

@@ -10,19 +10,7 @@ namespace bp {
 size_t pick_lim_lds_bytes(const PickParams &p) { return sizeof(PickShared) + (size_t)LimLayout(p).total_words * 4; }
 
 hipError_t launch_pick_token_lim(const PickParams &p, int dtype, hipStream_t stream) {
-    const size_t lds = (size_t)LimLayout(p).total_words * 4;
-    auto go = [&](auto et) {
-        auto kernel = pick_token_kernel<Limited<decltype(et)>>;
-        if (lds > 48 * 1024) {   // ask for the large dynamic allocation by name
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(kernel, dim3((unsigned)p.batch), dim3(kPickThreads), lds, stream, p);
-        return hipGetLastError();
-    };
-    if (dtype == BP_DTYPE_F32) return go(float{});
-    return with_dtype(dtype, go);
+    return launch_pick<Limited>(p, (size_t)LimLayout(p).total_words * 4, dtype, stream);
 }
 
 }  // namespace bp

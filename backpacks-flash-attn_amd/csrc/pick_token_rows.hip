@@ -6,19 +6,7 @@
 namespace bp {
 
 hipError_t launch_pick_token_rows(const PickParams &p, int dtype, hipStream_t stream) {
-    const size_t lds = (size_t)LimLayout(p).total_words * 4;   // the limited form's: the arrays add nothing to it
-    auto go = [&](auto et) {
-        auto kernel = pick_token_kernel<RowLimited<decltype(et)>>;
-        if (lds > 48 * 1024) {   // ask for the large dynamic allocation by name
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(kernel, dim3((unsigned)p.batch), dim3(kPickThreads), lds, stream, p);
-        return hipGetLastError();
-    };
-    if (dtype == BP_DTYPE_F32) return go(float{});
-    return with_dtype(dtype, go);
+    return launch_pick<RowLimited>(p, (size_t)LimLayout(p).total_words * 4, dtype, stream);   // the limited form's LDS: the arrays add nothing
 }
 
 }  // namespace bp

@@ -1,10 +1,10 @@
 // bp_row_extremes: the n largest and the n smallest elements of every row of a (rows, cols) matrix, values and columns, in
 // order.  Built for the vocabulary projections of sense vectors (src/utils/sense_vocab.py): a chunk of C_l(v) @ E^T is
 // reduced to its two ends the moment the GEMM has written it, so the (V k, V) matrix never exists as a whole.  The row
-// reader (RowView, PickElem) is pick_core.h's; nothing of the pick kernels is instantiated here.
+// reader (RowView, RowElem) and the wave helpers are vocab_row.h's.
 //
 // Contract (restated by _eager_row_extremes, src/utils/sense_vocab.py, and by tests/sense_vocab_ref.py):
-//   key       the order-preserving integer key of an element's RAW bits (PickElem<ET>::key): -0 < +0, NaNs at the ends by sign
+//   key       the order-preserving integer key of an element's RAW bits (RowElem<ET>::key): -0 < +0, NaNs at the ends by sign
 //   largest   ranked by (key descending, column ascending); smallest by (key ascending, column ascending)
 //   outputs   (rows, n) dense: *_val = float(element) fp32, *_idx = its column int32; an end whose two pointers are NULL is
 //             skipped.  A total order on integers: the answer is unique and two calls give the same bits.
@@ -24,7 +24,8 @@
 //             3  wave 0 (top) and wave 1 (bottom) rank the n held (key, ~column) values by counting and store them in order
 // No global workspace, no global atomics, vector stores only.  Every loop is bounded by the row's steps, by n or by a
 // constant; no register array is indexed by a variable.
-#include "pick_core.h"
+#include "bp_kernels.h"
+#include "vocab_row.h"
 
 namespace bp {
 
@@ -42,16 +43,6 @@ struct ExtShared {
     uint32_t n_items[2];
     uint32_t sel_digit[2], sel_above[2];
 };
-
-// inclusive prefix sum over the lanes of a wave
-BP_DEV uint32_t wave_scan_u32(uint32_t v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t w = __shfl_up(v, o);
-        if (lane >= o) v += w;
-    }
-    return v;
-}
 
 // an element strictly beyond the threshold: any free slot of the end's list (fewer than n <= kExtMax reach here)
 BP_DEV void ext_push(ExtShared &sh, int e, uint32_t ordered, int col) {
@@ -81,7 +72,7 @@ BP_DEV uint32_t ext_take(ExtShared &sh, int e, int wave, int lane, uint32_t tmas
 
 template <class ET>
 __global__ __launch_bounds__(kPickThreads) void row_extremes_kernel(const RowExtremesParams p) {
-    using E = PickElem<ET>;
+    using E = RowElem<ET>;
     __shared__ ExtShared sh;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t r = blockIdx.x;
@@ -271,8 +262,7 @@ hipError_t launch_row_extremes(const RowExtremesParams &p, int dtype, hipStream_
         hipLaunchKernelGGL((row_extremes_kernel<decltype(et)>), dim3((unsigned)p.rows), dim3(kPickThreads), 0, stream, p);
         return hipGetLastError();
     };
-    if (dtype == BP_DTYPE_F32) return go(float{});
-    return with_dtype(dtype, go);
+    return with_row_dtype(dtype, go);
 }
 
 }  // namespace bp

@@ -5,7 +5,7 @@
 // of bp_score_rows in include/bp_hip.h; _eager_score_rows (src/utils/scoring.py) and tests/score_ref.py restate it.
 //
 // One 256-thread workgroup per row, as xentropy_fwd_kernel: a thread walks the row in 16-byte chunks (head and tail
-// element-wise), ascending in the column.  It keeps
+// element-wise; vocab_row.h: RowSplit), ascending in the column.  It keeps
 //   (m, s, t)   the online maximum, s = sum e^(x - m), t = sum e^(x - m) x, rescaled only when the maximum moves
 //   best        the column of the first maximum it met (found inside the chunk only when the maximum moves; a thread that met
 //               only -inf answers with the first column it walked)
@@ -20,52 +20,18 @@
 
 #include "bp_common.h"
 #include "bp_kernels.h"
+#include "vocab_row.h"
 
 namespace bp {
 
 namespace {
 
-template <class ET> struct ScoreLoad;   // 16 bytes -> floats
-template <> struct ScoreLoad<float> {
-    static constexpr int N = 4, EB = 4;
-    static BP_DEV void load(const char *p, float (&v)[8]) {
-        const u32x4 w = *reinterpret_cast<const u32x4 *>(p);
-        const uint32_t a = w[0], b = w[1], c = w[2], d = w[3];
-        v[0] = as_f32(a); v[1] = as_f32(b); v[2] = as_f32(c); v[3] = as_f32(d);
-    }
-    static BP_DEV float one(const char *p) { return *reinterpret_cast<const float *>(p); }
-};
-template <class H> struct ScoreLoad16 {
-    static constexpr int N = 8, EB = 2;
-    static BP_DEV void load(const char *p, float (&v)[8]) {
-        const u32x4 w = *reinterpret_cast<const u32x4 *>(p);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint32_t x = w[i];
-            v[2 * i] = Elem<H>::lo_f32(x);
-            v[2 * i + 1] = Elem<H>::hi_f32(x);
-        }
-    }
-    static BP_DEV float one(const char *p) { return Elem<H>::lo_f32(*reinterpret_cast<const uint16_t *>(p)); }
-};
-template <> struct ScoreLoad<BF16> : ScoreLoad16<BF16> {};
-template <> struct ScoreLoad<F16> : ScoreLoad16<F16> {};
-
-typedef unsigned long long u64;
-
 constexpr int kNoCol = INT_MAX;
 constexpr int kAny = 0, kBelow = 1, kAbove = 2;   // ScoreState::absorb
-constexpr uint32_t kLowestBits = 0xff7fffffu;   // -FLT_MAX
-
-// value part of the argmax key: -0 == +0, otherwise the order of the floats (pick_core.h: greedy_key; NaNs are keyed apart)
-BP_DEV uint32_t order_key(float x) {
-    const uint32_t raw = as_u32(x + 0.f);
-    return raw ^ ((raw & 0x80000000u) ? 0xffffffffu : 0x80000000u);
-}
 
 // What a thread, a wave and the row know.  M targets: tc[] their columns (-1: out of range), xt[] their values (NaN then).
 template <int MT> struct ScoreState {
-    float m = -INFINITY, s = 0.f, t = 0.f;
+    float m = -INFINITY, s = 0.f, t = 0.f;   // rescaled only when the maximum moves
     int best = kNoCol, nan_col = kNoCol;
     int cnt[MT];
 
@@ -77,26 +43,17 @@ template <int MT> struct ScoreState {
 #pragma unroll
         for (int i = 1; i < NE; ++i) cm = fmaxf(cm, v[i]);
         if (cm > m) {   // the maximum moves: rescale, and find its first column in the chunk
-            const float f = fast_exp2((m - cm) * kLog2e);   // m = -inf: s = t = 0, exp2(-inf) = 0
-            s *= f;
-            t *= f;
-            m = cm;
+            online_rescale(m, s, t, cm);
             int at = NE - 1;
 #pragma unroll
             for (int i = NE - 2; i >= 0; --i) at = v[i] == cm ? i : at;
             best = col0 + at;
         }
         // straight-line from here to the NaN check: the comparisons fill the issue slots behind the exponentials
-        const float ms = (m == -INFINITY) ? 0.f : m;   // -inf - -inf would be a NaN
+        const float ms = online_shift(m);
         float cs = 0.f, ct = 0.f;
 #pragma unroll
-        for (int i = 0; i < NE; ++i) {
-            const float e = fast_exp2((v[i] - ms) * kLog2e);
-            cs += e;
-            // a -inf entry has e = 0 and must add 0, not 0 * -inf: its bits, the largest of the negative numbers as an unsigned
-            // integer, are clamped to those of -FLT_MAX (one v_min_u32; every other number keeps its bits)
-            ct = fmaf(e, as_f32(min(as_u32(v[i]), kLowestBits)), ct);
-        }
+        for (int i = 0; i < NE; ++i) online_term(v[i], ms, cs, ct);
 #pragma unroll
         for (int k = 0; k < MT; ++k) {
             if (MT > 1 && k >= ntargets) break;
@@ -130,26 +87,11 @@ template <int MT> struct ScoreState {
     }
 };
 
-BP_DEV void score_merge(float &m, float &s, float &t, float m2, float s2, float t2) {
-    const float mn = fmaxf(m, m2);
-    // exp2(-inf - -inf) would be NaN: an empty partial has s = t = 0 and is skipped by the select
-    const float a = (m == -INFINITY) ? 0.f : fast_exp2((m - mn) * kLog2e);
-    const float b = (m2 == -INFINITY) ? 0.f : fast_exp2((m2 - mn) * kLog2e);
-    s = s * a + s2 * b;
-    t = t * a + t2 * b;
-    m = mn;
-}
-
-BP_DEV u64 score_shfl_xor_u64(u64 v, int mask) {
-    const uint32_t lo = __shfl_xor((uint32_t)v, mask), hi = __shfl_xor((uint32_t)(v >> 32), mask);
-    return ((u64)hi << 32) | lo;
-}
-
 }  // namespace
 
 template <class ET, int MT>
 __global__ __launch_bounds__(256) void score_rows_kernel(const ScoreParams p) {
-    using L = ScoreLoad<ET>;
+    using L = RowElem<ET>;
     constexpr int EB = L::EB, N = L::N;
     __shared__ float red_f[3][4];
     __shared__ u64 red_k[4];
@@ -158,6 +100,7 @@ __global__ __launch_bounds__(256) void score_rows_kernel(const ScoreParams p) {
     const char *x = static_cast<const char *>(p.logits) + row * p.row_stride * EB;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int ntargets = MT == 1 ? 1 : p.ntargets;
+    const RowSplit<ET> sp(x, p.cols);   // (in front of the running state: behind it hipcc allocates the registers differently)
 
     // the targets: uniform loads, before the row is touched
     int tc[MT];
@@ -172,19 +115,16 @@ __global__ __launch_bounds__(256) void score_rows_kernel(const ScoreParams p) {
             const int64_t y = p.targets[row * p.target_stride + k];
             if (y >= 0 && y < (int64_t)p.cols) {
                 tc[k] = (int)y;
-                xt[k] = L::one(x + y * EB);
+                xt[k] = L::one_f32(x + y * EB);
             }
         }
     }
 
     // head: the elements before the first 16-byte boundary; then the vector body; then the tail -- ascending for every thread
-    const int head = (int)(((16 - (reinterpret_cast<uintptr_t>(x) & 15)) & 15) / EB);
-    const int nhead = min(head, p.cols);
-    const int nvec = (p.cols - nhead) / N;
-    const int tail0 = nhead + nvec * N;
+    const int nhead = sp.nhead, nvec = sp.nvec, tail0 = sp.tail0;
     float v[8];
     if (tid < nhead) {
-        v[0] = L::one(x + (int64_t)tid * EB);
+        v[0] = L::one_f32(x + (int64_t)tid * EB);
         st.template absorb<1, kAny>(v, tid, ntargets, tc, xt);
     }
     int c = tid;
@@ -194,30 +134,30 @@ __global__ __launch_bounds__(256) void score_rows_kernel(const ScoreParams p) {
         const int at = tc[0] >= nhead ? (tc[0] - nhead) / N : -1;   // the body chunk of the target; nvec or more: it is in the tail
         const int below = min(at, nvec);
         for (; c < below; c += 256) {
-            const int col0 = nhead + c * N;
-            L::load(x + (int64_t)col0 * EB, v);
+            const int col0 = sp.col0(c);
+            L::load_f32(x + (int64_t)col0 * EB, v);
             st.template absorb<N, kBelow>(v, col0, ntargets, tc, xt);
         }
         if (c == at && c < nvec) {
-            const int col0 = nhead + c * N;
-            L::load(x + (int64_t)col0 * EB, v);
+            const int col0 = sp.col0(c);
+            L::load_f32(x + (int64_t)col0 * EB, v);
             st.template absorb<N, kAny>(v, col0, ntargets, tc, xt);
             c += 256;
         }
         for (; c < nvec; c += 256) {
-            const int col0 = nhead + c * N;
-            L::load(x + (int64_t)col0 * EB, v);
+            const int col0 = sp.col0(c);
+            L::load_f32(x + (int64_t)col0 * EB, v);
             st.template absorb<N, kAbove>(v, col0, ntargets, tc, xt);
         }
     } else {
         for (; c < nvec; c += 256) {
-            const int col0 = nhead + c * N;
-            L::load(x + (int64_t)col0 * EB, v);
+            const int col0 = sp.col0(c);
+            L::load_f32(x + (int64_t)col0 * EB, v);
             st.template absorb<N, kAny>(v, col0, ntargets, tc, xt);
         }
     }
     if (tid < p.cols - tail0) {
-        v[0] = L::one(x + (int64_t)(tail0 + tid) * EB);
+        v[0] = L::one_f32(x + (int64_t)(tail0 + tid) * EB);
         st.template absorb<1, kAny>(v, tail0 + tid, ntargets, tc, xt);
     }
 
@@ -228,8 +168,8 @@ __global__ __launch_bounds__(256) void score_rows_kernel(const ScoreParams p) {
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) {
         const float m2 = __shfl_xor(m, o), s2 = __shfl_xor(s, o), t2 = __shfl_xor(t, o);
-        score_merge(m, s, t, m2, s2, t2);
-        const u64 k2 = score_shfl_xor_u64(key, o);
+        merge_mst(m, s, t, m2, s2, t2);
+        const u64 k2 = shfl_xor_u64(key, o);
         key = k2 > key ? k2 : key;
 #pragma unroll
         for (int k = 0; k < MT; ++k) st.cnt[k] += __shfl_xor(st.cnt[k], o);
@@ -245,7 +185,7 @@ __global__ __launch_bounds__(256) void score_rows_kernel(const ScoreParams p) {
     m = red_f[0][0]; s = red_f[1][0]; t = red_f[2][0];
     key = red_k[0];
     for (int w = 1; w < 4; ++w) {
-        score_merge(m, s, t, red_f[0][w], red_f[1][w], red_f[2][w]);
+        merge_mst(m, s, t, red_f[0][w], red_f[1][w], red_f[2][w]);
         key = red_k[w] > key ? red_k[w] : key;
     }
     // The degenerate rows, by the arithmetic of the definitions: a NaN makes all three NaN; +inf gives lse = +inf and
@@ -284,8 +224,7 @@ hipError_t launch_score_rows(const ScoreParams &p, int dtype, hipStream_t stream
             hipLaunchKernelGGL((score_rows_kernel<ET, kScoreMaxTargets>), dim3((unsigned)p.rows), dim3(256), 0, stream, p);
         return hipGetLastError();
     };
-    if (dtype == BP_DTYPE_F16 || dtype == BP_DTYPE_BF16) return with_dtype(dtype, go);
-    return go(float{});
+    return with_row_dtype(dtype, go);
 }
 
 }  // namespace bp

@@ -20,7 +20,7 @@ DEFAULT_CHUNK_ROWS = 8192   # 512 tokens x 16 senses, the reference's chunk (ran
 
 
 def _ordered_keys(x):
-    """The order-preserving integer key of every element's raw bits (csrc/pick_core.h, PickElem::key) as non-negative
+    """The order-preserving integer key of every element's raw bits (csrc/vocab_row.h, RowElem::key) as non-negative
     integers: sign bit set -> all bits flipped, else the sign bit flipped."""
     if x.dtype == torch.float32:
         raw = x.contiguous().view(torch.int32).to(torch.int64) & 0xffffffff

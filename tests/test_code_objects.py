@@ -163,3 +163,15 @@ def test_no_instruction_reads_m0_besides_the_lds_dma(obj):
             m0_users.add(ops[0])
     assert m0_users <= {'s_mov_b32'}, m0_users
     assert 'global_load_lds_dwordx4' in text
+
+
+def test_isa_diff_finds_a_build_equal_to_itself(table):
+    """scripts/isa_diff.py, the tool that shows a refactor left the generated code alone: score_rows.o of the current build
+    diffed against itself is `same` for every kernel, and the kernels it reports are exactly kernel_resources' list."""
+    import isa_diff as ID
+    if not ID.tools_available():
+        pytest.skip('llvm-objdump not found under /opt/rocm')
+    obj = os.path.join(KR.BUILD, 'score_rows.o')
+    rows = ID.diff_object(obj, obj)
+    assert rows and all(r['same'] for r in rows), [r for r in rows if not r['same']]
+    assert sorted(r['name'] for r in rows) == sorted(k['mangled'] for k in KR.kernels([obj]))

@@ -104,7 +104,7 @@ def test_drawn_groups_match_the_reference(vocab, W, dtype):
 
 # ---- planted groups: exact at every size ------------------------------------------------------------------------------------------------
 
-WAVES, LANES = 16, 64           # the 1024-thread workgroup of stage 1 (csrc/pick_core.h: kPickWaves, RowView)
+WAVES, LANES = 16, 64           # the 1024-thread workgroup of stage 1 (csrc/vocab_row.h: kPickWaves, RowView)
 ALL_EDGES_BUDGET = 80_000_000   # logits of one needle case: below it every chunk edge is planted, above it the classes
 
 

@@ -107,7 +107,7 @@ def _bits_equal(got, want):
 # ---- exact ------------------------------------------------------------------------------------------------------------------------
 
 def seam_columns(vocab, per16):
-    """Columns worth a spike or a token: score_ref's (ends, head / body / tail seams) and the seams of pick_core.h's RowView --
+    """Columns worth a spike or a token: score_ref's (ends, head / body / tail seams) and the seams of vocab_row.h's RowView --
     wave w owns the chunks [w cpw, (w + 1) cpw), lane l of step s the chunk 64 s + l of them -- for every row alignment."""
     picks = set()
     for head in range(per16):
