@@ -107,6 +107,10 @@ SIGNATURES = {
     'bp_sense_similarity': (_i32, [_ptr] * 9 + [_i64] + [_i32] * 3 + [_i64] + [_i64] * 7 + [_i32, _ptr]),
     'bp_score_rows': (_i32, [_ptr] * 7 + [_i64, _i32, _i32] + [_i64] * 3 + [_i32, _ptr]),
     'bp_pick_report': (_i32, [_ptr] * 8 + [_i32] * 2 + [_i64] * 2 + [_i32, _i64, _i32, _i32, _ptr]),
+    'bp_gemm_bf16': (_i32, [_ptr] * 4 + [_i64, _i32, _i32] + [_i64] * 3 + [_i32, _ptr, _i32, _ptr, _ptr]),
+    'bp_gemm_f16': (_i32, [_ptr] * 4 + [_i64, _i32, _i32] + [_i64] * 3 + [_i32, _ptr, _i32, _ptr, _ptr]),
+    'bp_gemm_library': (_i32, [_ptr, _ptr, _i32]),
+    'bp_gemm_heuristic': (_i32, [_i32, _i32, _i64, _i32, _i32] + [_i64] * 3 + [_ptr, _i32, _ptr]),
 }
 
 
@@ -1807,3 +1811,7 @@ def pick_report(logits, tokens, counters, *, logprob=None, rank=None, entropy=No
           *[_ptr(given[name]) for name in PICK_REPORT_RECORDS], batch, vocab,
           logits.stride(0) if batch > 1 else max(vocab, logits.stride(0)), tokens.stride(0) if batch > 1 else 1,
           rec_cols, rec_stride, n_top, _PICK_DTYPES[logits.dtype])
+
+
+# ---- dense layers by a pinned hipBLASLt solution (C ABI bp_gemm_*): bp_hip/gemm.py ---------------------------------------------
+from .gemm import GemmTable, linear, lm_head_chunk_rows   # noqa: E402,F401

@@ -132,6 +132,7 @@ const char *bp_strerror(int code) {
         case BP_ERR_SAMPLING: return "token sampling: top_p must be in (0, 1], rng_state non-NULL when do_sample; repetition_penalty finite and > 0 and, "
                                      "unless 1, with sequences; an eos_token_id with finished flags; finite frequency / presence penalties and, like n-gram "
                                      "blocking, with sequences; a non-NULL aligned suppress_ids when n_suppress > 0";
+        case BP_ERR_GEMM: return "a call into hipBLASLt or the HIP runtime failed";
         default: return "unknown error";
     }
 }

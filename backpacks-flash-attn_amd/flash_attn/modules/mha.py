@@ -137,7 +137,22 @@ class LinearResidual(nn.Linear):
     """nn.Linear that also hands back its input (reference mha.py:279-284)."""
 
     def forward(self, input):
-        return super().forward(input), input
+        return _linear_forward(self, input), input
+
+
+def _linear_forward(layer, x):
+    """nn.Linear.forward; without autograd through bp_hip.linear, the helper FusedDense uses as well (a pinned library
+    solution for the few large shapes with one, F.linear otherwise)."""
+    if torch.is_grad_enabled():
+        return nn.Linear.forward(layer, x)
+    return bp_hip.linear(x, layer.weight, layer.bias)
+
+
+class _Linear(nn.Linear):
+    """nn.Linear (same parameters and state-dict keys) whose inference forward goes through bp_hip.linear."""
+
+    def forward(self, input):
+        return _linear_forward(self, input)
 
 
 class MHA(nn.Module):
@@ -167,7 +182,7 @@ class MHA(nn.Module):
         assert embed_dim % num_heads == 0, 'embed_dim must be divisible by num_heads'
         self.head_dim = embed_dim // num_heads
         # fused_bias_fc selects FusedDense, as upstream (mha.py:330-337): same parameters, bias gradient by bp_column_sum
-        linear_cls = FusedDense if fused_bias_fc else nn.Linear
+        linear_cls = FusedDense if fused_bias_fc else _Linear
         if return_residual:
             qkv_cls = partial(FusedDense, return_residual=True) if fused_bias_fc else LinearResidual
         else:

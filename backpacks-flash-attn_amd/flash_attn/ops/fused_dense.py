@@ -85,7 +85,7 @@ def fused_dense_func(x, weight, bias=None, return_residual=False, process_group=
     if _eligible(x, weight, bias) and torch.is_grad_enabled() and (
             x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
         return FusedDenseFunc.apply(x, weight, bias, return_residual, None)
-    out = F.linear(x, weight, bias)
+    out = bp_hip.linear(x, weight, bias)    # inference: a pinned library solution for the few shapes with one, else F.linear
     return out if not return_residual else (out, x)
 
 
@@ -197,10 +197,10 @@ def fused_dense_gelu_dense_func(x, weight1, weight2, bias1=None, bias2=None, sav
             bias1 = bias1.to(cast) if bias1 is not None else None
             bias2 = bias2.to(cast) if bias2 is not None else None
         if bias1 is not None:
-            hidden = torch._addmm_activation(bias1, x2, weight1.t(), use_gelu=True)   # tanh GELU in the epilogue
+            hidden = bp_hip.linear(x2, weight1, bias1, gelu=True)   # tanh GELU in the epilogue (torch._addmm_activation)
         else:
             hidden = _gelu(x2 @ weight1.t())
-        out = F.linear(hidden, weight2, bias2).reshape(*x.shape[:-1], weight2.shape[0])
+        out = bp_hip.linear(hidden, weight2, bias2).reshape(*x.shape[:-1], weight2.shape[0])
         return out if not return_residual else (out, x)
     out = F.linear(F.gelu(F.linear(x, weight1, bias1), approximate='tanh'), weight2, bias2)
     return out if not return_residual else (out, x)

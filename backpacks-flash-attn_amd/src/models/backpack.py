@@ -789,12 +789,16 @@ class BackpackLMHeadModel(BackpackPreTrainedModel, GenerationMixin):
             raise RuntimeError(f'logits_out needs a bias-free lm_head whose weight has the activation dtype '
                                f'({self.lm_head.weight.dtype} vs {hidden_states.dtype}); call model.to(dtype) first')
         x2, o2 = hidden_states.reshape(-1, hidden_states.shape[-1]), logits_out.view(-1, want[-1])
-        rows = int(getattr(self, 'lm_head_chunk_rows', 0) or 0)    # 0: one GEMM; else row chunks into the same block
+        # 0: one GEMM; else row chunks into the same block.  Unset: what the pinned-solution table measured for this row
+        # count (bp_hip/gemm_solutions.json; 0 for every row count it does not name)
+        rows = getattr(self, 'lm_head_chunk_rows', None)
+        rows = bp_hip.lm_head_chunk_rows(x2.shape[0]) if rows is None else int(rows or 0)
+        # bp_hip.linear: the pinned library solution where the table has one for this shape, else torch.mm as before
         if rows <= 0 or rows >= x2.shape[0]:
-            torch.mm(x2, self.lm_head.weight.t(), out=o2)
+            bp_hip.linear(x2, self.lm_head.weight, out=o2)
         else:
             for r0 in range(0, x2.shape[0], rows):
-                torch.mm(x2[r0:r0 + rows], self.lm_head.weight.t(), out=o2[r0:r0 + rows])
+                bp_hip.linear(x2[r0:r0 + rows], self.lm_head.weight, out=o2[r0:r0 + rows])
         return CausalLMOutput(logits=logits_out)
 
     def refresh_inference_caches(self):

@@ -62,7 +62,9 @@ extern "C" {
                               and three more: bp_sense_lse_varlen / bp_sense_mix_varlen / bp_sense_mix_gather_varlen, the sense
                               kernels on packed batches described by cu_seqlens;
                               and one more: bp_pick_report, the record of a decode step's pick -- log-probability and rank of
-                              the token, entropy, the n most likely tokens -- in the record column the counter names) */
+                              the token, entropy, the n most likely tokens -- in the record column the counter names);
+                              and four more: bp_gemm_bf16 / bp_gemm_f16, a dense layer by a pinned hipBLASLt solution, with
+                              bp_gemm_library / bp_gemm_heuristic, BP_ERR_GEMM and the BP_GEMM_* statuses) */
 
 /* element type of q/k/v/out/content tensors */
 #define BP_DTYPE_F16 0
@@ -83,6 +85,7 @@ extern "C" {
                                  also a repetition_penalty not finite and > 0 or without sequences, an EOS id without flags;
                                  bp_pick_token_lim: also a non-finite frequency / presence penalty, n-gram blocking or a
                                  penalty without sequences, n_suppress > 0 with a NULL or misaligned list */
+#define BP_ERR_GEMM -11       /* bp_gemm_*: a call into hipBLASLt or the HIP runtime failed                          */
 
 /* bounds of bp_pick_token_lim (BP_ERR_SHAPE beyond them) */
 #define BP_PICK_MAX_NGRAM 64                  /* no_repeat_ngram_size */
@@ -1087,6 +1090,62 @@ int bp_score_rows(const void *logits, const int64_t *targets, float *logprob, in
 int bp_pick_report(const void *logits, const int64_t *tokens, const int32_t *counters, float *logprob, int32_t *rank,
                    float *entropy, int32_t *top_idx, float *top_logprob, int rows, int vocab, int64_t row_stride,
                    int64_t tokens_stride, int rec_cols, int64_t rec_stride, int n_top, int dtype, bp_stream_t stream);
+
+/* ---- dense layers by a pinned hipBLASLt solution (additive, ABI still 11; csrc/bp_gemm.hip, host code) ------------------------------
+ *
+ *   D[M,N] = A[M,K] . W[N,K]^T (+ bias[N]) (-> tanh-GELU),  row-major 16-bit operands, fp32 accumulation
+ *
+ * Which algorithm runs is a function of `table` alone.  The row used is the one with the call's dtype, epilogue, N and K and
+ * the largest m_min <= M; its `solution` is a hipBLASLt solution index, valid for ONE library version (hipblasLtGetVersion)
+ * on ONE architecture ("gfx950"), both stated in the row.  The index is turned into an algorithm, checked against the actual
+ * problem and launched on `stream`.  Every other outcome is one of the BP_GEMM_* statuses below (> 0, not an error): NOTHING
+ * was launched, D is untouched, and the caller runs the GEMM it would have run without this entry.  The library's heuristic
+ * is never consulted by bp_gemm_*.
+ *
+ * The library is the libhipblaslt the process has already loaded (PyTorch's); this one is never the cause of a second copy
+ * (BP_GEMM_NO_LIBRARY when none is loaded).  Handle and a 128 MiB workspace exist once per device from the first call on and
+ * are never freed; launches on different streams that need the workspace are ordered by an event.
+ *
+ *   a, w, d      16-bit matrices with element strides lda >= K, ldw >= K, ldd >= N between rows (d: columns >= N of a wider
+ *                buffer are not written)
+ *   bias         (N,) in the operands' dtype; non-NULL exactly when epilogue != BP_GEMM_EPILOGUE_NONE
+ *   table        n_rows rows, only read; n_rows == 0 is BP_GEMM_MISS
+ *   solution_out optional: the index that ran, -1 otherwise
+ * Errors: BP_ERR_SHAPE (a NULL operand, M / N / K < 1, a stride below its row, a bias without an epilogue or the reverse, an
+ * epilogue out of range), BP_ERR_GEMM.
+ */
+#define BP_GEMM_EPILOGUE_NONE 0
+#define BP_GEMM_EPILOGUE_BIAS 1
+#define BP_GEMM_EPILOGUE_BIAS_GELU 2
+
+#define BP_GEMM_MISS 1         /* no row for this (dtype, epilogue, N, K) with m_min <= M, or the row keeps the heuristic   */
+#define BP_GEMM_VERSION 2      /* the row was measured with another library version or on another architecture           */
+#define BP_GEMM_UNSUPPORTED 3  /* the library does not know the index, or the solution does not take this problem         */
+#define BP_GEMM_CAPTURING 4    /* the stream is being captured into a graph                                               */
+#define BP_GEMM_NO_LIBRARY 5   /* no libhipblaslt is loaded in this process                                               */
+
+typedef struct {
+    int32_t dtype;      /* BP_DTYPE_F16 / BP_DTYPE_BF16 */
+    int32_t epilogue;   /* BP_GEMM_EPILOGUE_* */
+    int32_t n, k;
+    int64_t m_min;      /* the row applies to M >= m_min (>= 1) */
+    int32_t version;    /* hipblasLtGetVersion of the library the index was measured with */
+    int32_t solution;   /* solution index; < 0: keep the heuristic (BP_GEMM_MISS) */
+    char arch[16];      /* "gfx950", NUL-terminated */
+} bp_gemm_row;
+
+int bp_gemm_bf16(const void *a, const void *w, const void *bias, void *d, int64_t M, int N, int K,
+                 int64_t lda, int64_t ldw, int64_t ldd, int epilogue, const bp_gemm_row *table, int n_rows,
+                 int *solution_out, bp_stream_t stream);
+int bp_gemm_f16(const void *a, const void *w, const void *bias, void *d, int64_t M, int N, int K,
+                int64_t lda, int64_t ldw, int64_t ldd, int epilogue, const bp_gemm_row *table, int n_rows,
+                int *solution_out, bp_stream_t stream);
+/* Version of the loaded library and the architecture of the current device as the table rows state them. */
+int bp_gemm_library(int *version, char *arch, int arch_len);
+/* For the tuning tool (scripts/tune_gemm.py) and tests: the solution indices of the heuristic's first `max_solutions`
+ * candidates for a problem, best first; *count of them are written.  dtype: BP_DTYPE_F16 / BP_DTYPE_BF16. */
+int bp_gemm_heuristic(int dtype, int epilogue, int64_t M, int N, int K, int64_t lda, int64_t ldw, int64_t ldd,
+                      int *solutions, int max_solutions, int *count);
 
 #ifdef __cplusplus
 }
