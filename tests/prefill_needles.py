@@ -18,8 +18,12 @@ tile) term of dK dropped or doubled, a dS term on the neighbouring key, scale mi
 all change bits.  Partly seen now: a row that takes the LSE of another row (row 0 has one needle, hence another LSE than the
 paired rows; among the paired rows of a call it is still one number); another row's D is seen (D_i = dO_i . O_i differs from
 row to row).  Dropout, forward and backward, has its own exact tests: the pair problems run under p = 1/2 in
-tests/test_gpu_dropout_exact.py (tests/dropout_exact.py).  Still unseen: key_weight in the fused sense
-backward, which has none (a weighted call takes the alpha-rebuilding route; the pair problem runs that route unweighted).
+tests/test_gpu_dropout_exact.py (tests/dropout_exact.py).  A key tile with non-negligible weight that does not hold a needle --
+the P V accumulation of a steady-state tile with 64 live probabilities, alpha = 1 across several live tiles, the ring
+accumulation of the mix, more than one decode split that matters, dV / dC sums over dense P -- is what tests/tie_blocks.py builds
+(tests/test_gpu_tie_blocks.py): up to 2048 keys tied bit for bit.  Still unseen: key_weight in the fused sense
+backward, which has none (a weighted call takes the alpha-rebuilding route; the pair problem runs that route unweighted), and
+non-unit rescale factors between live tiles (score steps between tiles are not exact powers of two under fl(scale log2e)).
 tests/test_gpu_backward.py keeps the job on random data.
 
 Everything is a fixed integer function of its indices (no generator state), on any device.

@@ -38,7 +38,10 @@ of 1 at m c2 ~ 500, which left 3e-5 where (V[j1] + V[j2]) / 2 = 0 with the needl
 
 Dropout in the forward and the backward is tested exactly in tests/test_gpu_dropout_exact.py.
 NOT tested here: key_weight in the fused sense backward (it has none), and a paired row taking
-another paired row's LSE (they share one; row 0, with one needle, has another, and another row's D is seen).
+another paired row's LSE (they share one; row 0, with one needle, has another, and another row's D is seen).  A live key tile
+that holds no needle (mutant 7 below) is the subject of tests/test_gpu_tie_blocks.py: rows whose weight lies on 16 ... 2048 keys
+tied bit for bit, where that mutant fails every forward case of the LDS-DMA kernel.  Non-unit rescale factors between live tiles
+stay parity-only there as well: score steps between tiles are not exact powers of two under fl(scale log2e).
 
 Two places where the kernels' own arithmetic is not exact on these inputs, each with a derived bound instead:
   * flash_fwd_dma.hip:282-285 and 487: the LSE is the logarithm of the sum of ROUNDED p.  In the stale-reference case that
