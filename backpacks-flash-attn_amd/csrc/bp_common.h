@@ -15,6 +15,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lds_image.h"
+
 namespace bp {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -148,6 +150,13 @@ BP_DEV u32x2 lds_read_tr16_8B(const char *smem, int off) {
     s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr_t)(smem + off));
     return __builtin_bit_cast(u32x2, v);
 }
+// The A operand of O^T += V^T P^T: two such reads, at `off` and 8 rows (of `pitch` bytes) further down (lds_image.h, TrLane)
+BP_DEV u32x4 tr_operand_at(const char *smem, int off_lo, int off_hi) {
+    const u32x2 lo = lds_read_tr16_8B(smem, off_lo);
+    const u32x2 hi = lds_read_tr16_8B(smem, off_hi);
+    return u32x4{lo[0], lo[1], hi[0], hi[1]};
+}
+BP_DEV u32x4 tr_operand(const char *smem, int off, int pitch) { return tr_operand_at(smem, off, off + 8 * pitch); }
 
 // A run of N MFMAs whose LDS operands are requested two MFMAs ahead.  hipcc's own order is "read, s_waitcnt
 // lgkmcnt(0), MFMA" per MFMA -- a full LDS round trip in front of each, 75-85 clocks per MFMA where the pipe needs 32
@@ -165,17 +174,6 @@ template <int N, class Fetch, class Use> BP_DEV void mfma_stream(Fetch &&fetch, 
         a0 = a1;
         a1 = a2;
     }
-}
-
-// Byte offset of 16-B chunk `ch` of row `row` in a V / content tile whose rows hold NV 64-byte
-// chunks.  ds_read_b64_tr_b16 serves 32 lanes at once = 4 consecutive rows x 64 B; the XOR on the
-// 64-B chunk index puts those 4 row segments in the 4 different quarters of the 64 banks.
-//   NV=1: rows are 64 B, quarters differ by construction;  NV=3: 192-B rows rotate by 3 quarters.
-template <int NV> BP_DEV int v_lds_off(int row, int ch) {
-    int c64 = ch >> 2;
-    if (NV == 2) c64 ^= (row >> 1) & 1;
-    if (NV == 4 || NV == 8) c64 ^= row & 3;
-    return row * (NV * 64) + ((c64 << 2) | (ch & 3)) * 16;
 }
 
 BP_DEV float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }

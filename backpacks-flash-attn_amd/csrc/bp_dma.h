@@ -1,4 +1,5 @@
-// LDS-DMA ring helpers shared by the fast-path kernels (flash_fwd_dma.hip, sense_mix_dma.hip).
+// LDS-DMA instructions and counted waits of the kernels that stream tiles into LDS without register staging:
+// flash_fwd_dma.hip, flash_bwd.hip, mix_ring.h (sense_mix_dma_kernel.h, sense_mix_bwd.hip), sense_wide_dma.hip.
 //
 // Tiles reach LDS with `global_load_lds_dwordx4` (64 lanes x 16 B per instruction, LDS destination
 // = wave-uniform base + lane*16, per-lane global source), completion is tracked by hand:
@@ -7,7 +8,7 @@
 //   * one raw `s_barrier` per tile then makes everybody's share visible and, at the same time,
 //     retires the ring slot that was read during the previous step (it is refilled right after).
 // Because the DMA writes LDS linearly, the XOR swizzles that make the MFMA operand reads
-// bank-conflict free are applied to the per-lane SOURCE address.
+// bank-conflict free are applied to the per-lane SOURCE address (lds_image.h).
 #pragma once
 #include "bp_common.h"
 
@@ -88,10 +89,5 @@ BP_DEV void dma16_s_nt(const uint16_t *uniform_base, uint32_t lane_byte_off, uin
 BP_DEV uint32_t lds_base_addr(char *smem) { return (uint32_t)(uintptr_t)(lmem_v *)smem; }
 
 template <int N> BP_DEV void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-// K rows live in LDS with a power-of-two pitch (128 or 256 B) and XOR-swizzled 16-B slots:
-// ds_read_b128 by 32 lanes at 32 consecutive rows and one logical slot touches every bank once.
-// Only row bits 0..3 enter, so adding 32 rows keeps a lane's swizzle.
-template <int KROW> BP_DEV int k_swz(int row) { return KROW == 128 ? ((row >> 1) & 7) : (row & 15); }
 
 }  // namespace bp

@@ -153,7 +153,7 @@ __global__ __launch_bounds__(256) void flash_fwd_kernel(const FlashParams p) {
     float m_run = -INFINITY;   // running max of the raw scores of my query (same in both halves)
     float l_run = 0.f;         // running sum of exp over the keys THIS lane holds (halves add up)
 
-    // lane-constant LDS offsets
+    // lane-constant LDS offsets (TrLane's geometry, spelled here: through tr_lane / tr_operand the V kernels' code differed)
     const int k_lane = k_lane_off(KD, l31, hh);
     const int v_row_lane = 4 * hh + ((lane & 15) >> 2);               // + kk*32 + ks*16 (+8)
     const int v_ch_lane16 = ((lane >> 4) & 1) * 2;                    // 16-col group -> 16-B chunk pair

@@ -54,7 +54,7 @@ struct FlashDmaCfg {
     static constexpr int NWAVE = 4;
     static constexpr int BM = 32 * NWAVE, BN = 64, NT = 64 * NWAVE, NSTAGE = 2;
     // K row pitch in LDS.  Head dims 64 and 128 fill a power-of-two pitch (128 / 256 bytes) and XOR-swizzle the
-    // 16-byte slots (k_swz); every other width (d_h = 80: Mini; the senses' d_k = 48 / 24 / 16) takes an ODD number of slots,
+    // 16-byte slots (RowImage, lds_image.h); every other width (d_h = 80: Mini; the senses' d_k = 48 / 24 / 16) takes an ODD number of slots,
     // 2 KD + 1 (a narrow K tile is also fewer DMA pieces: d_k = 16 moves 3 KB per tile instead of 8): the
     // quad-bank of (row, slot) is (row * KSLOTS + slot) mod 16, distinct for the 16 rows of every ds_read_b128 lane group
     // without any swizzle, and the tile shrinks from 16 KB to 11 / 13 / 15 KB -- at d_h = 80 that is 47 KB per workgroup
@@ -81,6 +81,7 @@ template <> struct ProbLimit<F16> { static constexpr float value = 16384.f; };  
 template <class ET, int KD, int NV, bool HAS_V, bool FULLD, bool DROP>
 BP_DEV void flash_fwd_tile(const FlashParams p, char *smem, const uint32_t lds0, const int bh, const int qt) {
     using C = FlashDmaCfg<KD, NV, HAS_V>;
+    using KI = RowImage<C::KROW>;   // K image: swizzled for the two power-of-two pitches, plain for the odd ones
     using E = Elem<ET>;
     constexpr float kLimit = ProbLimit<ET>::value;
 
@@ -159,18 +160,18 @@ BP_DEV void flash_fwd_tile(const FlashParams p, char *smem, const uint32_t lds0,
     uint32_t k_voff[C::K_DMA];
 #pragma unroll
     for (int j = 0; j < C::K_DMA; ++j) {
-        // lane's 16 bytes of piece (wave * K_DMA + j): linear 16-byte slot g of the tile image -> (row, stored slot)
-        const int g = (wave * C::K_DMA + j) * 64 + lane;
-        const int row = g / C::KSLOTS;
-        k_row[j] = row;
-        k_col[j] = (C::ODD ? g - row * C::KSLOTS : (g - row * C::KSLOTS) ^ k_swz<C::KROW>(row)) * 8;
-        k_voff[j] = (uint32_t)(row * p.k_rs + k_col[j]) * 2u;
+        // lane's 16 bytes of piece (wave * K_DMA + j): linear 16-byte slot of the tile image (lds_image.h)
+        const TileSrc s = KI::src((wave * C::K_DMA + j) * 64 + lane);
+        k_row[j] = s.row;
+        k_col[j] = s.col;
+        k_voff[j] = (uint32_t)(s.row * p.k_rs + s.col) * 2u;
     }
     int v_row[HAS_V ? C::V_DMA : 1], v_col[HAS_V ? C::V_DMA : 1];
     uint32_t v_voff[HAS_V ? C::V_DMA : 1];
     if (HAS_V) {
 #pragma unroll
         for (int j = 0; j < C::V_DMA; ++j) {
+            // (TrImage<NV>::src spelled here, as are tr_lane and the read pairs below: through the header the V kernels' code differed)
             const int c = (wave * C::V_DMA + j) * 64 + lane;   // linear 16-B chunk of the tile
             const int row = c / C::VCH, stored = c - row * C::VCH;
             int c64 = stored >> 2;
@@ -238,7 +239,7 @@ BP_DEV void flash_fwd_tile(const FlashParams p, char *smem, const uint32_t lds0,
     int k_read_off[KD];
 #pragma unroll
     for (int s = 0; s < KD; ++s)
-        k_read_off[s] = l31 * C::KROW + (C::ODD ? 2 * s + hh : (2 * s + hh) ^ k_swz<C::KROW>(l31)) * 16;
+        k_read_off[s] = KI::read_off(l31, hh, s);
     int v_read_off[HAS_V ? NV : 1];
     if (HAS_V) {
         const int v_row_lane = 4 * hh + ((lane & 15) >> 2);

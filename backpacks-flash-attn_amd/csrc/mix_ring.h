@@ -105,7 +105,7 @@ template <class C> struct MixTileReader {
     BP_DEV MixTileReader(int lane) {
         const int l31 = lane & 31, hh = lane >> 5;
 #pragma unroll
-        for (int s = 0; s < C::KD; ++s) a_off[s] = l31 * C::AROW + (((2 * s + hh) ^ k_swz<C::AROW>(l31)) * 16);
+        for (int s = 0; s < C::KD; ++s) a_off[s] = RowImage<C::AROW>::read_off(l31, hh, s);
         // (k_swz only looks at row bits 0..3, so +32 rows keeps the same swizzle)
         const int row_lane = 4 * hh + ((lane & 15) >> 2);
         const int ch_lane = ((lane >> 4) & 1) * 2 + ((lane & 3) >> 1);
@@ -118,11 +118,7 @@ template <class C> struct MixTileReader {
     // A operand of column step s, 32-row half kk of the tile at ring byte offset `stage`
     BP_DEV u32x4 a_operand(const char *smem, int stage, int s, int kk) const { return lds_read_16B(smem, a_off[s] + stage + kk * 32 * C::AROW); }
     // B^T operand of column block n at LDS byte offset `rows` (16 rows x 256 columns)
-    BP_DEV u32x4 b_operand(const char *smem, int rows, int n) const {
-        const u32x2 lo = lds_read_tr16_8B(smem, b_off[n & 3] + (n >> 2) * 256 + rows);
-        const u32x2 hi = lds_read_tr16_8B(smem, b_off[n & 3] + (n >> 2) * 256 + rows + 8 * C::BROW);
-        return u32x4{lo[0], lo[1], hi[0], hi[1]};
-    }
+    BP_DEV u32x4 b_operand(const char *smem, int rows, int n) const { return tr_operand(smem, b_off[n & 3] + (n >> 2) * 256 + rows, C::BROW); }
 };
 
 // scores of the 32-row half kk of the tile at `stage` against my fragments `frag`: tile rows along the registers
@@ -212,7 +208,8 @@ template <class E, class C> BP_DEV void mix_store_row(uint16_t *row, const f32x1
 // The DMA side of one job: tiles [t_begin, t_end) of every sense in turn, two tiles in flight.  A step past the end
 // re-fetches the last tile (harmless, keeps every wave's DMA count per step constant so the counted wait never changes).
 //
-// Per-lane byte offsets of my DMA pieces inside a tile (the scalar tile base is added by the DMA instruction).  A piece
+// Per-lane byte offsets of my DMA pieces inside a tile (the scalar tile base is added by the DMA instruction; the piece rows
+// and tr_lane stay spelled here: RowImage / TrImage::src on the opaque lane copy changed the generated code).  A piece
 // j of this wave: rows (wave*A_DMA + j)*A_ROWS_PER_DMA + lane/ASLOTS, stored slot lane%ASLOTS; B piece j: rows
 // (wave*B_DMA + j)*2 + lane/32, stored chunk lane%32.  They are rebuilt PER JOB from an opaque copy of the lane
 // index: as loop invariants hipcc hoists the row / column tables to kernel entry and keeps them alive across
@@ -266,8 +263,7 @@ template <class C> struct MixStream {
 #pragma unroll
         for (int j = 0; j < C::B_DMA; ++j) {
             const int row = b_piece_row(j);
-            const int stored = lane_o & 31;
-            const int logical = (((stored >> 2) ^ (row & 3)) << 2) | (stored & 3);
+            const int logical = TrImage<C::NB>::flip(row, lane_o & 31);   // stored chunk -> logical chunk
             const int col = (FULL || col_base + logical * 8 < ncols) ? col_base + logical * 8 : col_base;
             b_voff[j] = (uint32_t)(row * row_stride + col) * 2u;
         }

@@ -314,7 +314,8 @@ __global__ __launch_bounds__(256) void sense_dq_kernel(const SenseGradParams p) 
         settle(lse2);
     }
 
-    // DMA descriptors: K row image, K transposed-read image, dP^T rows
+    // DMA descriptors: K row image, K transposed-read image, dP^T rows (RowImage / TrImage::src and tr_lane of lds_image.h,
+    // spelled here in dq and dk: through the header both kernels' code differed)
     int rr[R_DMA], rc[R_DMA], tr[T_DMA], tc[T_DMA], pr[P_DMA], pc[P_DMA];
 #pragma unroll
     for (int j = 0; j < R_DMA; ++j) {
@@ -368,7 +369,7 @@ __global__ __launch_bounds__(256) void sense_dq_kernel(const SenseGradParams p) 
 
     int r_read_off[KD];
 #pragma unroll
-    for (int s = 0; s < KD; ++s) r_read_off[s] = l31 * C::KROW + (((2 * s + hh) ^ k_swz<C::KROW>(l31)) * 16);
+    for (int s = 0; s < KD; ++s) r_read_off[s] = RowImage<C::KROW>::read_off(l31, hh, s);
     const int t_row_lane = 4 * hh + ((lane & 15) >> 2);
     const int t_ch_lane = ((lane >> 4) & 1) * 2 + ((lane & 3) >> 1);
     int t_read_off[NVK];
@@ -573,7 +574,7 @@ __global__ __launch_bounds__(256) void sense_dk_kernel(const SenseGradParams p) 
 
     int r_read_off[KD];
 #pragma unroll
-    for (int s = 0; s < KD; ++s) r_read_off[s] = l31 * C::KROW + (((2 * s + hh) ^ k_swz<C::KROW>(l31)) * 16);
+    for (int s = 0; s < KD; ++s) r_read_off[s] = RowImage<C::KROW>::read_off(l31, hh, s);
     const int t_row_lane = 4 * hh + ((lane & 15) >> 2);
     const int t_ch_lane = ((lane >> 4) & 1) * 2 + ((lane & 3) >> 1);
     int t_read_off[NVK];
@@ -625,9 +626,7 @@ __global__ __launch_bounds__(256) void sense_dk_kernel(const SenseGradParams p) 
             const int rows = (qb * 32 + ks * 16) * C::TROW;
 #pragma unroll
             for (int n = 0; n < NVK; ++n) {
-                const u32x2 lo = lds_read_tr16_8B(q_t, t_read_off[n] + rows);
-                const u32x2 hi = lds_read_tr16_8B(q_t, t_read_off[n] + rows + 8 * C::TROW);
-                dk[n] = E::mfma(u32x4{lo[0], lo[1], hi[0], hi[1]}, dsf[ks], dk[n]);
+                dk[n] = E::mfma(tr_operand(q_t, t_read_off[n] + rows, C::TROW), dsf[ks], dk[n]);
             }
         }
     }

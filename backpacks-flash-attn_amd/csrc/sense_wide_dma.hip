@@ -45,17 +45,6 @@ struct WideDmaCfg {
     static_assert(RING * STAGE <= 160 * 1024, "LDS budget");
 };
 
-// byte offset of (row, logical 16-byte chunk ch) in a content image of NB 64-byte chunks per row; ds_read_b64_tr_b16 serves
-// 32 lanes = 4 consecutive rows x 64 B at once, the four row segments must lie in four different quarters of the banks:
-//   NB = 5: rows are 320 B = 5 quarters apart -- distinct by construction;
-//   NB = 10: 640 B = 10 quarters -- rows r and r + 2 would collide: chunk index XOR ((row >> 1) & 1).
-template <int NB> BP_DEV int wide_c_off(int row, int ch) {
-    static_assert(NB == 5 || NB == 10, "swizzle derived for 5 and 10 column blocks");
-    int c64 = ch >> 2;
-    if (NB == 10) c64 ^= (row >> 1) & 1;
-    return row * (NB * 64) + ((c64 << 2) | (ch & 3)) * 16;
-}
-
 // The ring: per-lane source offsets of my DMA pieces (constant over the sweep), and the issue of one step's pieces.
 template <int KD, int NW, int NB>
 struct WideRing {
@@ -75,9 +64,7 @@ struct WideRing {
             if constexpr (NB > 0) if (pi >= C::K_PIECES && pi < C::PIECES) {
                 const int c = (pi - C::K_PIECES) * 64 + lane;
                 const int row = c / C::CSLOTS, stored = c - row * C::CSLOTS;
-                int c64 = stored >> 2;
-                if (NB == 10) c64 ^= (row >> 1) & 1;
-                int col = col_base + ((c64 << 2) | (stored & 3)) * 8;
+                int col = col_base + TrImage<NB>::flip(row, stored) * 8;   // content image (lds_image.h)
                 if (col >= dout) col = col_base;              // columns past d_out: any finite data (never stored)
                 off = gather ? ((uint32_t)row << 16) | (uint32_t)((col - col_base) * 2)
                              : (uint32_t)(row * c_rs + col) * 2u;
@@ -202,13 +189,11 @@ __global__ __launch_bounds__(NW * 64) void sense_mix_wide_dma_kernel(const MixPa
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[n][r] = 0.f;
     // content fragments (A operand of O^T = C^T P^T): lane -> (row, 16-byte chunk) of the 4 x 64 B a tr read serves
-    const int c_row_lane = 4 * hh + ((lane & 15) >> 2);
-    const int c_ch_lane = ((lane >> 4) & 1) * 2 + ((lane & 3) >> 1);
-    const int c_sub = (lane & 1) * 8;
+    const TrLane t = tr_lane(lane, hh);
     // block n's chunk index is n ^ b (NB = 10; b = (row >> 1) & 1, the same for row + 8 and row + 16): two lane offsets,
     // the rest are instruction offsets
-    const int c_off_even = wide_c_off<NB>(c_row_lane, c_ch_lane) + c_sub;
-    const int c_off_odd = wide_c_off<NB>(c_row_lane, 4 + c_ch_lane) + c_sub - 64;
+    const int c_off_even = v_lds_off<NB>(t.row, t.ch) + t.sub;
+    const int c_off_odd = v_lds_off<NB>(t.row, 4 + t.ch) + t.sub - 64;
     auto c_read_off = [&](int n) { return ((NB == 10 && (n & 1)) ? c_off_odd : c_off_even) + n * 64; };
 
     u32x4 qf[KD];
@@ -258,10 +243,7 @@ __global__ __launch_bounds__(NW * 64) void sense_mix_wide_dma_kernel(const MixPa
             mfma_stream<2 * NB>(
                 [&](int i) {
                     const int ks = i / NB, n = i - ks * NB;
-                    const int off = c_read_off(n) + ks * 16 * C::CROW;
-                    const u32x2 lo = lds_read_tr16_8B(cbuf, off);
-                    const u32x2 hi = lds_read_tr16_8B(cbuf, off + 8 * C::CROW);
-                    return u32x4{lo[0], lo[1], hi[0], hi[1]};
+                    return tr_operand(cbuf, c_read_off(n) + ks * 16 * C::CROW, C::CROW);
                 },
                 [&](int i, const u32x4 &a) {
                     const int ks = i / NB, n = i - ks * NB;

@@ -51,15 +51,8 @@ BP_DEV QueryRows query_rows(const LaneCoord &L, int tile_q0, int nq) {
 // compiler keeps one lane-dependent value per register live across the key loop (+30 VGPRs in attn_probs_kernel).
 constexpr int st_key(int base, int r, int hh) { return base + (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
-// Where a lane points ds_read_b64_tr_b16 so that it receives, for its column of a 32-column block, the keys that its
-// P^T registers hold (bp_common.h): row within 16 keys (+8 for the second read), 16-byte chunk within the block's
-// four, byte offset within the chunk.
-struct TrLane {
-    int row, ch, sub;
-};
-BP_DEV TrLane tr_lane(const LaneCoord &L) {
-    return TrLane{4 * L.hh + ((L.lane & 15) >> 2), ((L.lane >> 4) & 1) * 2 + ((L.lane & 3) >> 1), (L.lane & 1) * 8};
-}
+// where the lane points its transposed reads (lds_image.h)
+BP_DEV TrLane tr_lane(const LaneCoord &L) { return tr_lane(L.lane, L.hh); }
 
 // ---- K tile -------------------------------------------------------------------------------------------------------------
 // LDS image of a K tile: row pitch 32 bytes per 16-column step plus 16 (conflict-free ds_read_b128)
@@ -206,10 +199,7 @@ BP_DEV void accumulate_pv(f32x16 (&acc)[NB], const f32x16 &p, const char *cbuf, 
         for (int n = 0; n < NB; ++n)
             if (n < nb_live) {
                 const int ch = n * 4 + t.ch;
-                const u32x2 lo = lds_read_tr16_8B(cbuf, v_lds_off<NB>(row0, ch) + t.sub);
-                const u32x2 hi = lds_read_tr16_8B(cbuf, v_lds_off<NB>(row0 + 8, ch) + t.sub);
-                const u32x4 a = {lo[0], lo[1], hi[0], hi[1]};
-                acc[n] = E::mfma(a, pf, acc[n]);
+                acc[n] = E::mfma(tr_operand_at(cbuf, v_lds_off<NB>(row0, ch) + t.sub, v_lds_off<NB>(row0 + 8, ch) + t.sub), pf, acc[n]);
             }
     }
 }
