@@ -8,6 +8,7 @@ RuntimeError in the same situations, flash_attn/flash_attn_interface.py:5).
 """
 import contextlib
 import ctypes
+import math
 import os
 
 import torch
@@ -101,6 +102,7 @@ SIGNATURES = {
     'bp_beam_pick_ws_floats': (_i64, [_i32] * 2),
     'bp_beam_pick': (_i32, [_ptr] * 8 + [_i64] + [_i32] * 3 + [_i64] * 3 + [_i32] * 4 + [_ptr]),
     'bp_beam_copy_rows': (_i32, [_ptr] * 3 + [_i32] + [_ptr] * 2 + [_i32] * 3 + [_ptr]),
+    'bp_scatter_packed_rows': (_i32, [_ptr] * 6 + [_i32, _ptr, _i32, _i64, _i32, _i32, _ptr]),
     'bp_row_extremes': (_i32, [_ptr] * 5 + [_i32] * 2 + [_i64] + [_i32] * 2 + [_ptr]),
     'bp_sense_attribute_ws_floats': (_i64, [_i32] * 2),
     'bp_sense_attribute': (_i32, [_ptr] * 9 + [_i64] + [_i32] * 7 + [_i64] + [_i64] * 14 + [_f32, _i32, _ptr]),
@@ -1535,6 +1537,64 @@ def beam_copy_rows(tensors, parent, lengths, first_position):
     pos_bytes = (ctypes.c_int64 * n)(*[t[0, 0].numel() * t.element_size() for t in tensors])
     _call('bp_beam_copy_rows', parent.device, bases, strides, pos_bytes, n, parent.data_ptr(), lengths.data_ptr(), rows,
           int(first_position), min(t.shape[1] for t in tensors))
+
+
+# ---- packed rows into padded buffers (C ABI bp_scatter_packed_rows) ----------------------------------------------------------------------------------------------------
+
+SCATTER_MAX_SETS = 32
+SCATTER_POSITIONS = 32      # positions one workgroup of the kernel owns (csrc/bp_kernels.h kScatterPositions)
+
+
+def _dense_behind(t, lead):
+    """Whether everything behind the first `lead` dimensions of `t` lies contiguously."""
+    want = 1
+    for size, stride in zip(reversed(t.shape[lead:]), reversed(t.stride()[lead:])):
+        if size != 1 and stride != want:
+            return False
+        want *= size
+    return True
+
+
+def scatter_packed_rows(pairs, cu_seqlens, max_seqlen):
+    """Row cu_seqlens[b] + j of every `src` lands at [b, j] of its `dst`, for j < min(len_b, max_seqlen, dst.shape[1]), in ONE
+    launch for all pairs (at most 32); nothing else of a `dst` is written (contract in include/bp_hip.h).  `pairs`: a list of
+    (src (total, ...), dst (batch, positions, ...)) with one dtype and one trailing shape per pair, everything behind src's
+    first and dst's second dimension contiguous -- src may be a strided slice (qkv[:, 1:] of a (total, 3, H, D) tensor), dst
+    a batch slice of a cache (cache[b0:b1]).  cu_seqlens (batch + 1,) int32 on the device is read there only: no host read,
+    legal inside a HIP-graph capture.  The tensors' addresses are read now: a captured graph keeps copying THESE buffers."""
+    pairs = [tuple(pair) for pair in pairs]
+    _require_cuda(cu_seqlens, *[t for pair in pairs for t in pair])
+    if not pairs or len(pairs) > SCATTER_MAX_SETS:
+        raise RuntimeError(f'bp_hip.scatter_packed_rows: between 1 and {SCATTER_MAX_SETS} pairs, got {len(pairs)}')
+    if cu_seqlens.dim() != 1 or cu_seqlens.numel() < 2 or cu_seqlens.dtype != torch.int32 or not cu_seqlens.is_contiguous():
+        raise RuntimeError('bp_hip.scatter_packed_rows: cu_seqlens must be a contiguous (batch + 1,) int32 tensor')
+    batch, total = cu_seqlens.numel() - 1, pairs[0][0].shape[0] if pairs[0][0].dim() else -1
+    for src, dst in pairs:
+        if src.dim() < 1 or dst.dim() != src.dim() + 1 or src.dtype != dst.dtype or src.shape[1:] != dst.shape[2:]:
+            raise RuntimeError('bp_hip.scatter_packed_rows: a pair is src (total, ...) and dst (batch, positions, ...) of one '
+                               'dtype and one trailing shape')
+        if src.shape[0] != total or dst.shape[0] != batch or src.device != cu_seqlens.device or dst.device != src.device:
+            raise RuntimeError('bp_hip.scatter_packed_rows: every src holds the same `total` rows, every dst `batch` rows, '
+                               'all on the device of cu_seqlens')
+        if not _dense_behind(src, 1) or not _dense_behind(dst, 2):
+            raise RuntimeError('bp_hip.scatter_packed_rows: everything behind src\'s first and dst\'s second dimension '
+                               'must be contiguous')
+    n = len(pairs)
+
+    def array(kind, values):
+        return (kind * n)(*values)
+    row_bytes = [math.prod(src.shape[1:]) * src.element_size() for src, _ in pairs]
+
+    def stride_bytes(t, dim, single):      # the stride of a dimension of one entry says nothing: `single` stands in
+        return t.stride(dim) * t.element_size() if t.shape[dim] > 1 else single
+    _call('bp_scatter_packed_rows', cu_seqlens.device,
+          array(ctypes.c_void_p, [src.data_ptr() for src, _ in pairs]),
+          array(ctypes.c_int64, [stride_bytes(src, 0, rb) for (src, _), rb in zip(pairs, row_bytes)]),
+          array(ctypes.c_void_p, [dst.data_ptr() for _, dst in pairs]),
+          array(ctypes.c_int64, [stride_bytes(dst, 0, 0) for _, dst in pairs]),
+          array(ctypes.c_int64, [stride_bytes(dst, 1, rb) for (_, dst), rb in zip(pairs, row_bytes)]),
+          array(ctypes.c_int64, row_bytes), n, cu_seqlens.data_ptr(), batch, total, int(max_seqlen),
+          min(dst.shape[1] for _, dst in pairs))
 
 
 # ---- row extremes on the device (C ABI bp_row_extremes) ---------------------------------------------------------------------------------------------------------------

@@ -1232,6 +1232,35 @@ int bp_beam_copy_rows(const void *const *bases, const int64_t *row_strides, cons
     return launch_status(bp::launch_beam_copy_rows(p, static_cast<hipStream_t>(stream)));
 }
 
+// ---- packed rows into padded buffers (bp_scatter_packed_rows) ----
+
+int bp_scatter_packed_rows(const void *const *src, const int64_t *src_row_strides, void *const *dst,
+                           const int64_t *dst_batch_strides, const int64_t *dst_pos_strides, const int64_t *row_bytes,
+                           int nsets, const int32_t *cu_seqlens, int batch, int64_t total_rows, int max_seqlen,
+                           int max_positions, bp_stream_t stream) {
+    if (nsets < 1 || nsets > bp::kScatterMaxSets || batch < 1 || batch > 65535) return BP_ERR_SHAPE;
+    if (src == nullptr || src_row_strides == nullptr || dst == nullptr || dst_batch_strides == nullptr
+        || dst_pos_strides == nullptr || row_bytes == nullptr || cu_seqlens == nullptr)
+        return BP_ERR_SHAPE;
+    if (reinterpret_cast<uintptr_t>(cu_seqlens) % 4) return BP_ERR_SHAPE;
+    if (max_seqlen < 0 || max_positions < 0 || total_rows < 0) return BP_ERR_SHAPE;
+    bp::ScatterRowsParams p{};
+    for (int i = 0; i < nsets; ++i) {
+        if (src[i] == nullptr || dst[i] == nullptr) return BP_ERR_SHAPE;
+        const uintptr_t all = reinterpret_cast<uintptr_t>(src[i]) | reinterpret_cast<uintptr_t>(dst[i])
+            | (uintptr_t)src_row_strides[i] | (uintptr_t)dst_batch_strides[i] | (uintptr_t)dst_pos_strides[i]
+            | (uintptr_t)row_bytes[i];
+        if (all % 4 != 0 || row_bytes[i] < 4 || dst_batch_strides[i] < 0) return BP_ERR_SHAPE;
+        if (row_bytes[i] > src_row_strides[i] || row_bytes[i] > dst_pos_strides[i]) return BP_ERR_SHAPE;
+        p.src[i] = src[i]; p.dst[i] = dst[i]; p.src_row_stride[i] = src_row_strides[i];
+        p.dst_batch_stride[i] = dst_batch_strides[i]; p.dst_pos_stride[i] = dst_pos_strides[i]; p.row_bytes[i] = row_bytes[i];
+        if (all % 16 == 0) p.wide |= 1u << i;
+    }
+    p.cu_seqlens = cu_seqlens; p.total_rows = total_rows;
+    p.nsets = nsets; p.batch = batch; p.limit = max_seqlen < max_positions ? max_seqlen : max_positions;
+    return launch_status(bp::launch_scatter_packed_rows(p, static_cast<hipStream_t>(stream)));
+}
+
 // ---- row extremes (bp_row_extremes) ----
 
 int bp_row_extremes(const void *logits, float *top_val, int32_t *top_idx, float *bot_val, int32_t *bot_idx,

@@ -403,6 +403,22 @@ struct BeamCopyParams {
 };
 hipError_t launch_beam_copy_rows(const BeamCopyParams &p, hipStream_t stream);
 
+// bp_scatter_packed_rows (scatter_rows.hip): row cu_seqlens[b] + j of a packed source lands at [b][j] of a padded destination
+constexpr int kScatterMaxSets = 32;
+constexpr int kScatterPositions = 32;       // positions a workgroup owns
+struct ScatterRowsParams {
+    const void *src[kScatterMaxSets];
+    void *dst[kScatterMaxSets];
+    int64_t src_row_stride[kScatterMaxSets];                                   // bytes
+    int64_t dst_batch_stride[kScatterMaxSets], dst_pos_stride[kScatterMaxSets];
+    int64_t row_bytes[kScatterMaxSets];
+    const int32_t *cu_seqlens;              // (batch + 1), on the device; not trusted
+    int64_t total_rows;
+    uint32_t wide;                          // bit i: set i moves 16-byte words (everything of it a multiple of 16)
+    int nsets, batch, limit;                // limit = min(max_seqlen, max_positions)
+};
+hipError_t launch_scatter_packed_rows(const ScatterRowsParams &p, hipStream_t stream);
+
 // bp_row_extremes (row_extremes.hip): the n largest / n smallest elements of every row, values and columns, in order
 constexpr int kRowExtremesMaxN = BP_ROW_EXTREMES_MAX_N;
 struct RowExtremesParams {

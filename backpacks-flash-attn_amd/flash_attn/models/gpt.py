@@ -15,7 +15,7 @@ from transformers import GPT2Config
 import bp_hip
 from flash_attn.modules.block import Block
 from flash_attn.modules.embedding import GPT2Embeddings
-from flash_attn.modules.mha import MHA, cache_lengths
+from flash_attn.modules.mha import MHA, cache_lengths, refuse_packed_step
 from flash_attn.modules.mlp import FusedDenseGeluDense, Mlp
 from flash_attn.ops.layer_norm import dropout_add_layer_norm
 from flash_attn.utils.pretrained import state_dict_from_pretrained
@@ -203,16 +203,25 @@ class GPTModel(GPTPreTrainedModel):
     def _forward_packed(self, input_ids, position_ids, inference_params, cu_seqlens, max_seqlen):
         """The packed form of `forward`: the unchained launches over (total, d) rows (every row-wise kernel takes any
         number of rows), attention through the ragged flash call.  HIP trunk only: the eager attention has no ragged form
-        (BackpackModel pads such batches)."""
+        (BackpackModel pads such batches).
+        With `inference_params` at sequence_len_offset == 0 it is the PACKED PREFILL: every mixer also scatters its K/V into
+        the rows of its cache (MHA._forward_packed_prefill).  At a non-zero offset it stays refused: cached steps take one
+        token per sample as (B, 1) ids."""
         if inference_params is not None:
-            raise ValueError('a packed batch (cu_seqlens / max_seqlen) and inference_params exclude each other')
+            refuse_packed_step(inference_params)
         if cu_seqlens is None or max_seqlen is None or input_ids.dim() != 1:
             raise ValueError('a packed batch needs input_ids (total,), cu_seqlens (B + 1,) int32 and max_seqlen (int)')
         if not getattr(self.config, 'use_flash_attn', False):
+            if inference_params is not None:
+                raise ValueError('a packed batch with inference_params (a packed prefill) needs use_flash_attn=True: the '
+                                 'eager attention has no ragged form')
             raise NotImplementedError('a packed batch needs use_flash_attn=True: the eager attention has no ragged form')
         if position_ids is None:
             position_ids = packed_position_ids(cu_seqlens, input_ids.shape[0])
-        return self._embed_and_run(input_ids, position_ids, {'cu_seqlens': cu_seqlens, 'max_seqlen': int(max_seqlen)})
+        mixer_kwargs = {'cu_seqlens': cu_seqlens, 'max_seqlen': int(max_seqlen)}
+        if inference_params is not None:
+            mixer_kwargs['inference_params'] = inference_params
+        return self._embed_and_run(input_ids, position_ids, mixer_kwargs)
 
     def _embed_and_run(self, input_ids, position_ids, mixer_kwargs):
         hidden = self.embeddings(input_ids, position_ids=position_ids)

@@ -199,7 +199,9 @@ class MHA(nn.Module):
                 inference_params=None, **kwargs):
         """x (batch, seqlen, hidden) or, with cu_seqlens/max_seqlen, (total, hidden)."""
         if inference_params is not None:
-            assert key_padding_mask is None and cu_seqlens is None and max_seqlen is None
+            assert key_padding_mask is None
+            if cu_seqlens is not None or max_seqlen is not None:
+                return self._forward_packed_prefill(x, inference_params, cu_seqlens, max_seqlen)
             return self._forward_cached(x, inference_params)
         if cu_seqlens is not None:
             assert max_seqlen is not None and key_padding_mask is None and self.use_flash_attn
@@ -229,6 +231,10 @@ class MHA(nn.Module):
     # The HIP path decodes with bp_flash_decode (append + attention in one call, no host read of the lengths); the eager
     # twin does the same bookkeeping in torch.  More than one new token at a non-zero offset is refused: the reference
     # runs that case without a causal mask among the new tokens.
+    #   packed prefill (sequence_len_offset == 0, x (total, hidden) + cu_seqlens + max_seqlen; HIP path only): the ragged
+    #           flash call over the packed prompts, their K/V scattered to [b, 0:len_b) by one bp_scatter_packed_rows launch
+    #           that reads cu_seqlens on the device; positions at or behind len_b are not written.  A packed call at a
+    #           non-zero offset is refused: cached steps stay one token per sample on (B, 1) inputs.
 
     def _kv_cache(self, inference_params, like):
         assert self.layer_idx is not None, 'generation requires layer_idx in the constructor'
@@ -269,6 +275,37 @@ class MHA(nn.Module):
                 context = _eager_decode(q, qkv[:, 0, 1:], cache, b0, lengths, scale).unsqueeze(1)
         out = self.out_proj(context.flatten(-2))
         return out if not self.return_residual else (out, x)
+
+    def _forward_packed_prefill(self, x, inference_params, cu_seqlens, max_seqlen):
+        """x (total, hidden): the prompts of a packed batch.  Their K/V go to [b, 0:len_b) of the cache rows of this call."""
+        if torch.is_grad_enabled() and (x.requires_grad or self.Wqkv.weight.requires_grad):
+            raise RuntimeError('KV-cached decoding is inference-only: run it under torch.no_grad() or '
+                               'torch.inference_mode()')
+        refuse_packed_step(inference_params)
+        assert cu_seqlens is not None and max_seqlen is not None and x.dim() == 2 and self.use_flash_attn, \
+            'a packed prefill takes x (total, hidden), cu_seqlens, max_seqlen and use_flash_attn=True'
+        if self.return_residual:
+            qkv, x = self.Wqkv(x)
+        else:
+            qkv = self.Wqkv(x)
+        qkv = qkv.unflatten(-1, (3, self.num_heads, self.head_dim))      # (total, 3, H, D)
+        batch = cu_seqlens.numel() - 1
+        cache = self._kv_cache(inference_params, qkv)
+        b0 = inference_params.batch_size_offset
+        assert b0 + batch <= cache.shape[0], 'batch_size_offset + batch exceeds max_batch_size'
+        assert max_seqlen <= cache.shape[1], 'prompt longer than max_sequence_len'
+        bp_hip.scatter_packed_rows([(qkv[:, 1:], cache[b0:b0 + batch])], cu_seqlens, max_seqlen)
+        context = self.inner_attn(qkv, cu_seqlens=cu_seqlens, max_seqlen=max_seqlen)   # the ragged causal flash call
+        out = self.out_proj(context.flatten(-2))
+        return out if not self.return_residual else (out, x)
+
+
+def refuse_packed_step(inference_params):
+    """A packed batch with `inference_params` is a PREFILL: after the prompt a cached call takes (B, 1) ids."""
+    if inference_params.sequence_len_offset != 0:
+        raise ValueError('a packed batch (cu_seqlens / max_seqlen) with inference_params is a prefill '
+                         f'(sequence_len_offset == 0, got {inference_params.sequence_len_offset}): cached steps take one '
+                         'token per sample as (B, 1) ids')
 
 
 def cache_lengths(inference_params, batch, device):

@@ -28,7 +28,7 @@ from transformers import GPT2Config
 import bp_hip
 from flash_attn.models.gpt import GPTModel, GPTPreTrainedModel, _activation, _init_weights, _pad_vocab, packed_coordinates
 from flash_attn.modules.block import Block
-from flash_attn.modules.mha import cache_lengths, refuse_multi_token_step
+from flash_attn.modules.mha import cache_lengths, refuse_multi_token_step, refuse_packed_step
 from flash_attn.modules.mlp import FusedDenseGeluDense, Mlp
 from flash_attn.ops.fused_dense import FusedDense, fused_dense_func
 from flash_attn.ops.layer_norm import dropout_add_layer_norm
@@ -500,10 +500,11 @@ class BackpackModel(GPTPreTrainedModel):
     # A wrapper that changes what enters the contraction passes itself as `intervention` (a SenseIntervention, below).
     # Without one nothing here differs from the plain model, call for call.
 
-    def _decode_caches(self, ip, qk, content_form, like):
-        """The Backpack's caches (created by the first prefill) and the batch rows b0:b1 of this call."""
+    def _decode_caches(self, ip, qk, content_form, like, batch=None):
+        """The Backpack's caches (created by the first prefill) and the batch rows b0:b1 of this call; `batch`: of a packed
+        qk (total, 2, k, d_k), whose first dimension does not tell."""
         caches = ip.key_value_memory_dict
-        batch, k, dk = qk.shape[0], qk.shape[3], qk.shape[4]
+        batch, (k, dk) = qk.shape[0] if batch is None else batch, qk.shape[-2:]
         mb, ms = ip.max_batch_size, ip.max_sequence_len
         if 'backpack_sense_k' not in caches:
             caches['backpack_sense_k'] = torch.zeros(mb, ms, k, dk, dtype=qk.dtype, device=qk.device)
@@ -587,10 +588,21 @@ class BackpackModel(GPTPreTrainedModel):
     # ---- packed (variable-length) batches --------------------------------------------------------------------------------
     # input_ids (total,) + cu_seqlens ((B + 1,) int32 on the ids' device) + max_seqlen (int) -> (total, d): the sequences lie
     # behind one another, nothing is padded (src/utils/packing.py builds the three).  The trunk runs its ragged flash call,
-    # the senses bp_sense_mix_varlen / bp_sense_mix_gather_varlen.  Inference only (no varlen backward), never with
-    # inference_params (a packed prefill would need a scatter into the KV caches), not under GraphedForward.
+    # the senses bp_sense_mix_varlen / bp_sense_mix_gather_varlen.  Inference only (no varlen backward), not under
+    # GraphedForward.
     # What the packed kernels do not take -- wide or non-fused senses, use_flash_attn=False, the CPU -- is padded to
     # (B, max_seqlen), run through the forward above and cut back to the real rows (`_forward_packed_padded`).
+    # With inference_params at sequence_len_offset == 0 the call is the PACKED PREFILL of the KV caches (`_packed_prefill`):
+    # the same launches, every trunk layer scatters its K/V (MHA._forward_packed_prefill) and ONE bp_scatter_packed_rows
+    # launch fills the Backpack's caches at [b, 0:len_b), in the form `_cached_prefill` would have chosen; `_cached_step`
+    # then runs unchanged.  It returns the mix of every packed row (total, d).  There is no padded route for it: where
+    # `packed_limit` names a limit the combination is a ValueError (the generation loops then prefill padded prompts), and
+    # at a non-zero offset it always is -- cached steps stay one token per sample on (B, 1) ids.
+
+    def packed_limit(self, input_ids, max_seqlen):
+        """None when the packed kernels -- and with them the packed prefill -- take ids on this device at this longest
+        sequence, else the limit that stands in the way (text)."""
+        return self._packed_limit(input_ids, max_seqlen)
 
     def _packed_limit(self, input_ids, max_seqlen):
         """None when the packed kernels take this call, else the limit it exceeds (text)."""
@@ -632,10 +644,30 @@ class BackpackModel(GPTPreTrainedModel):
         content = torch.nn.functional.embedding(index, rows.reshape(rows.shape[0], -1))
         return bp_hip.sense_mix_varlen(qk, content.view(index.shape[0], *rows.shape[1:]), cu_seqlens, max_seqlen, scale)
 
+    def _packed_prefill(self, input_ids, hidden, qk, ip, cu_seqlens, max_seqlen):
+        """The packed prompts: fills the caches at [b, 0:len_b) (and fixes their form, as `_cached_prefill` does), returns
+        the mix of every packed row (total, d) by the launches of the packed forward."""
+        batch = cu_seqlens.numel() - 1
+        table = self.sense_table() if self._table_mode() == 'cached' else None
+        c = self._decode_caches(ip, qk, table is None, hidden, batch=batch)
+        if max_seqlen > c.keys.shape[1]:
+            raise ValueError(f'packed prefill: max_seqlen {max_seqlen} exceeds max_sequence_len {c.keys.shape[1]}')
+        pairs = [(qk[:, 1], c.keys[c.b0:c.b1])]
+        if table is not None:
+            pairs.append((input_ids.to(torch.int32), c.rows[c.b0:c.b1]))
+            bp_hip.scatter_packed_rows(pairs, cu_seqlens, max_seqlen)
+            return self._mix_packed_from_table(qk, table, input_ids, cu_seqlens, max_seqlen)
+        content = self.content_model(input_ids.unsqueeze(0))[0].transpose(0, 1)    # (total, k, d): the block as it lies
+        ms = ip.max_sequence_len
+        # every entry of a row would hold this eventually: the whole row at once, no length read
+        c.rows[c.b0:c.b1] = c.sample[:, None] * ms + torch.arange(ms, device=qk.device)
+        pairs.append((content, c.content.view(-1, ms, *c.content.shape[1:])[c.b0:c.b1]))
+        bp_hip.scatter_packed_rows(pairs, cu_seqlens, max_seqlen)
+        return bp_hip.sense_mix_varlen(qk, content, cu_seqlens, max_seqlen, self.contextualization_attn.scale())
+
     def _forward_packed(self, input_ids, position_ids, inference_params, cu_seqlens, max_seqlen):
         if inference_params is not None:
-            raise ValueError('a packed batch (cu_seqlens / max_seqlen) and inference_params exclude each other: the '
-                             'KV-cached prefill takes padded prompts')
+            refuse_packed_step(inference_params)
         if torch.is_grad_enabled():
             raise RuntimeError('the packed forward is inference-only (no varlen backward): run it under torch.no_grad() '
                                'or torch.inference_mode()')
@@ -646,13 +678,19 @@ class BackpackModel(GPTPreTrainedModel):
         max_seqlen = int(max_seqlen)
         limit = self._packed_limit(input_ids, max_seqlen)
         if limit is not None:
+            if inference_params is not None:
+                raise ValueError('a packed batch (cu_seqlens / max_seqlen) with inference_params -- a packed prefill -- is '
+                                 f'not available here: {limit}; the KV-cached prefill then takes padded prompts')
             if self.use_hip and input_ids.is_cuda and not self._packed_fallback_said:
                 self._packed_fallback_said = True
                 warnings.warn('Backpack: the packed batch is padded to (B, max_seqlen) and run through the padded forward: '
                               + limit)
             return self._forward_packed_padded(input_ids, position_ids, cu_seqlens, max_seqlen)
-        hidden = self.gpt2_model(input_ids, position_ids=position_ids, cu_seqlens=cu_seqlens, max_seqlen=max_seqlen)
+        hidden = self.gpt2_model(input_ids, position_ids=position_ids, inference_params=inference_params,
+                                 cu_seqlens=cu_seqlens, max_seqlen=max_seqlen)
         qk = self.contextualization_attn.project(hidden)                 # (total, 2, k, d_k)
+        if inference_params is not None:
+            return self._packed_prefill(input_ids, hidden, qk, inference_params, cu_seqlens, max_seqlen)
         if self._token_table_allowed(input_ids):
             if self.sense_table_mode == 'cached':
                 rows = self.sense_table(verify=self._verify_applies(input_ids))

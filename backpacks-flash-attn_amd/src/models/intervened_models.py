@@ -94,6 +94,12 @@ class _Intervened(nn.Module, GenerationMixin, SenseIntervention):
             cached(input_ids, position_ids, inference_params, intervention=self)
         return CausalLMOutput(logits=self.backpack_network.lm_head(mixed))
 
+    def _packed(self, packed_prefill):
+        if packed_prefill:
+            raise NotImplementedError(f'packed_prefill=True is not available on {type(self).__name__}: the edits of the '
+                                      'sense-intervened wrappers are written for (B, S) ids (see _refuse_packed)')
+        return super()._packed(packed_prefill)
+
     def beam_search(self, *args, **kwargs):
         # the mixin's beam search reorders the wrapped network's caches between slots, not the wrapper's own per-row
         # state (ids, sims, dots, weights)

@@ -20,6 +20,7 @@ Index contract kept bit for bit: the reference never appends the LAST token it p
 starts at prompt + 1 and the loop appends only while `seqlen < max_length`), so `sequences` has
 max(prompt_len, max_length - 1) columns, not max_length as its docstring says; `scores` holds the first
 step's logits only (:59).  Same here."""
+import warnings
 from dataclasses import dataclass, field
 from typing import Optional, Tuple
 
@@ -594,6 +595,11 @@ def _trim_rows_at_eos(sequences, prompt_lengths, new_tokens, eos_token_id, pad_t
 def _check_prompt_lengths(prompt_lengths, input_ids):
     """prompt_lengths (a sequence or a tensor of `batch` integers in [1, seq_len]) as a (batch,) int32 tensor on the device of
     input_ids, and its minimum: ONE copy to the host for the checks, one to the device; no step reads a host value."""
+    return _checked_prompt_lengths(prompt_lengths, input_ids)[:2]
+
+
+def _checked_prompt_lengths(prompt_lengths, input_ids):
+    """_check_prompt_lengths, and the host copy it checked (a list): what a packed prefill packs by."""
     host = torch.as_tensor(prompt_lengths).detach().cpu()
     batch, seqlen = input_ids.shape
     if host.dim() != 1 or host.shape[0] != batch or host.is_floating_point() or host.dtype == torch.bool:
@@ -601,7 +607,7 @@ def _check_prompt_lengths(prompt_lengths, input_ids):
     values = host.tolist()
     if not all(1 <= v <= seqlen for v in values):
         raise ValueError(f'generation: prompt_lengths must lie in [1, seq_len = {seqlen}]: input_ids is right-padded')
-    return host.to(device=input_ids.device, dtype=torch.int32), min(values)
+    return host.to(device=input_ids.device, dtype=torch.int32), min(values), values
 
 
 class _CachedSteps:
@@ -612,11 +618,14 @@ class _CachedSteps:
     With `prompt_lengths` (rows,) int32 on the device, input_ids is right-padded: the columns behind a row's prompt are
     overwritten with `pad` before anything reads them, the prefill runs over the padded width (causal: no real position sees
     a pad) and returns the logits of every row's own last position, and the cached lengths start at the rows' own.  A step
-    appends at a row's length, so what the prefill cached for the pad columns is overwritten before it could be read."""
+    appends at a row's length, so what the prefill cached for the pad columns is overwritten before it could be read.
+    With `packed_lengths` too (the host copy of prompt_lengths, a list: `packed_prefill=True` on a model that takes it) the
+    prefill runs over the prompts' own positions instead, packed behind one another (_prefill_packed): nothing is computed
+    for a pad column, and nothing is cached for one."""
 
-    def __init__(self, input_ids, model, max_length, capacity_multiple=1, prompt_lengths=None, pad=0):
+    def __init__(self, input_ids, model, max_length, capacity_multiple=1, prompt_lengths=None, pad=0, packed_lengths=None):
         rows, self.prompt = input_ids.shape
-        self.prompt_lengths = prompt_lengths
+        self.prompt_lengths, self.packed_lengths = prompt_lengths, packed_lengths
         self.input_ids, self.model = input_ids, model
         self.width = max(self.prompt, max_length - 1)
         capacity = (self.width + capacity_multiple - 1) // capacity_multiple * capacity_multiple
@@ -632,6 +641,8 @@ class _CachedSteps:
 
     def prefill(self):
         """The logits of the prompt's last position (every row's own, under prompt_lengths); the caches then hold the prompt."""
+        if self.packed_lengths is not None:
+            return self._prefill_packed()
         logits = self.model(self.input_ids, inference_params=self.ip).logits
         self.ip.sequence_len_offset = self.prompt                 # a host integer, read only as "after the prompt"
         if self.prompt_lengths is None:
@@ -640,6 +651,25 @@ class _CachedSteps:
         self.lengths.copy_(self.prompt_lengths)
         last = (self.prompt_lengths.long() - 1)[:, None, None].expand(-1, 1, logits.shape[-1])
         return logits.gather(1, last)[:, 0].contiguous()
+
+    def _prefill_packed(self):
+        """`prefill` over the packed prompts: the pad-cleaned ids without their pad columns, the model's packed prefill
+        (inference_params + cu_seqlens + max_seqlen: the caches take every row's own positions), and the LM head over the
+        rows' last positions alone where the model is a trunk and a head.  The row index and cu_seqlens are built from the
+        HOST copy of the lengths: no value is read back from the device."""
+        lens, device = self.packed_lengths, self.input_ids.device
+        index = torch.cat([torch.arange(b * self.prompt, b * self.prompt + n) for b, n in enumerate(lens)]).to(device)
+        ids = self.input_ids.reshape(-1).index_select(0, index).to(torch.int64)
+        cu = torch.tensor([0] + lens, dtype=torch.int64).cumsum(0).to(device=device, dtype=torch.int32)
+        last = cu[1:].long() - 1
+        packed = dict(inference_params=self.ip, cu_seqlens=cu, max_seqlen=max(lens))
+        if hasattr(self.model, 'transformer') and hasattr(self.model, 'lm_head'):
+            logits = self.model.lm_head(self.model.transformer(ids, **packed).index_select(0, last))
+        else:
+            logits = self.model(ids, **packed).logits.index_select(0, last)
+        self.ip.sequence_len_offset = self.prompt                 # a host integer, read only as "after the prompt"
+        self.lengths.copy_(self.prompt_lengths)
+        return logits.contiguous()
 
     def step_logits(self):
         """The head of every step: the model on `static_ids`, then lengths + 1 -- the counter of the step's pick."""
@@ -667,7 +697,7 @@ class _CachedSteps:
 
 
 def _decode_cached_picked(input_ids, model, max_length, picker, cg=False, stop_check_every=None, prompt_lengths=None,
-                          report=None):
+                          report=None, packed_lengths=None):
     """_decode_cached with the pick on the device: the counter of a pick is `lengths_per_sample` after the step's
     increment, the pick writes the next step's input (`static_ids`) and column `position` of the preallocated `sequences`.
     With cg=True the captured graph is model step, length increment, pick: a generated token is one replay, with no launch
@@ -678,8 +708,10 @@ def _decode_cached_picked(input_ids, model, max_length, picker, cg=False, stop_c
     With `prompt_lengths` every row generates exactly width - prompt tokens behind its own prompt: that many picks and no
     further one, which would land inside a shorter row; `lengths` is always returned (_trim_rows_at_eos).
     With `report` = (output_logprobs, top_logprobs) every pick is followed by its record (_PickRecord) -- the captured graph is
-    then model step, length increment, pick, report -- and the result carries the record's fields, trimmed as `sequences` is."""
-    d = _CachedSteps(input_ids, model, max_length, prompt_lengths=prompt_lengths, pad=picker.options.pad)
+    then model step, length increment, pick, report -- and the result carries the record's fields, trimmed as `sequences` is.
+    With `packed_lengths` (prompt_lengths on the host) the prefill is the packed one (_CachedSteps); nothing behind it differs."""
+    d = _CachedSteps(input_ids, model, max_length, prompt_lengths=prompt_lengths, pad=picker.options.pad,
+                     packed_lengths=packed_lengths)
     record = _PickRecord(d, *report) if report is not None else None
 
     def pick(logits):
@@ -709,8 +741,34 @@ def _decode_cached_picked(input_ids, model, max_length, picker, cg=False, stop_c
                                  **recorded(sequences, lengths))
 
 
+def packed_prefill_limit(model, input_ids, max_seqlen):
+    """None when `model` takes a packed prefill of `input_ids`' device with `max_seqlen` as the longest prompt, else what
+    stands in the way (text): BackpackModel.packed_limit's answer for a model that is a `transformer` with one."""
+    limit_of = getattr(getattr(model, 'transformer', None), 'packed_limit', None)
+    if limit_of is None:
+        return f'{type(model).__name__} has no packed forward'
+    return limit_of(input_ids, max_seqlen)
+
+
+def _packed_lengths(model, input_ids, kv_cache, prompt_lengths, host_lengths):
+    """packed_prefill=True: the host lengths the prefill packs by, or None -- with one warning per model that names the
+    limit -- where the model takes no packed prefill and the loop runs the padded one."""
+    if prompt_lengths is None or not kv_cache:
+        raise ValueError('generation: packed_prefill needs prompt_lengths and kv_cache=True (it is the prefill of '
+                         'right-padded prompts of different lengths into the KV caches)')
+    if hasattr(model, '_packed'):
+        model._packed(True)               # a model that cannot take it refuses here, before any launch
+    limit = packed_prefill_limit(model, input_ids, max(host_lengths))
+    if limit is None:
+        return host_lengths
+    if not getattr(model, '_packed_prefill_fallback_said', False):
+        model._packed_prefill_fallback_said = True
+        warnings.warn('generation: packed_prefill=True runs the padded prefill on this model: ' + limit)
+    return None
+
+
 def _run_loop(input_ids, model, max_length, pick, do_sample, cg, kv_cache, rng_state, device_pick, stop_check_every,
-              pick_options, prompt_lengths=None, output_logprobs=False, top_logprobs=0):
+              pick_options, prompt_lengths=None, output_logprobs=False, top_logprobs=0, packed_prefill=False):
     """The loop greedy_decode / sample select: with the device pick (_Picker) when device_pick, an rng_state, prompt_lengths,
     a record (output_logprobs / top_logprobs) or one of `pick_options` asks for it, else with the host's `pick` exactly as the
     reference runs."""
@@ -730,12 +788,16 @@ def _run_loop(input_ids, model, max_length, pick, do_sample, cg, kv_cache, rng_s
         if not kv_cache:
             raise ValueError('generation: prompt_lengths needs kv_cache=True (the loops without a cache are the reference\'s, '
                              'statement for statement)')
-        prompt_lengths, _ = _check_prompt_lengths(prompt_lengths, input_ids)
+        prompt_lengths, _, host_lengths = _checked_prompt_lengths(prompt_lengths, input_ids)
+    packed = {}
+    if packed_prefill:
+        lens = _packed_lengths(model, input_ids, kv_cache, prompt_lengths, None if prompt_lengths is None else host_lengths)
+        packed = {} if lens is None else {'packed_lengths': lens}
     if device_pick or rng_state is not None or options.wants_device_pick or prompt_lengths is not None or report is not None:
         picker = _Picker(options, rng_state, input_ids.device, prompt_lengths)
         if kv_cache:
             return _decode_cached_picked(input_ids, model, max_length, picker, cg=cg, stop_check_every=stop_check_every,
-                                         prompt_lengths=prompt_lengths, report=report)
+                                         prompt_lengths=prompt_lengths, report=report, **packed)
         if options.controlled:
             raise ValueError('generation: repetition_penalty, eos_token_id, pad_token_id, min_length, min_new_tokens, '
                              'no_repeat_ngram_size, frequency_penalty, presence_penalty and suppress_tokens need kv_cache=True '
@@ -749,7 +811,8 @@ def _run_loop(input_ids, model, max_length, pick, do_sample, cg, kv_cache, rng_s
 
 
 def greedy_decode(input_ids, model, max_length, cg=False, kv_cache=False, rng_state=None, device_pick=False,
-                  stop_check_every=None, prompt_lengths=None, output_logprobs=False, top_logprobs=0, **pick_options):
+                  stop_check_every=None, prompt_lengths=None, output_logprobs=False, top_logprobs=0, packed_prefill=False,
+                  **pick_options):
     """input_ids (batch, seq_len) -> sequences (batch, max_length - 1): argmax continuation.
     cg=True: one captured full-width forward replayed per token (CUDA tensors only), see _decode_graphed.
     kv_cache=True: prefill once, then one cached step per token (with cg=True: one captured step), see _decode_cached.
@@ -767,13 +830,20 @@ def greedy_decode(input_ids, model, max_length, cg=False, kv_cache=False, rng_st
     and rank of every generated token under the logits it was picked from (the model's: before temperature, penalties and
     filters) and the entropy of that distribution; with top_logprobs the n most likely tokens of every step and their
     log-probabilities.  `sequences` and `lengths` are those of the call without the two.
+    packed_prefill=True (needs prompt_lengths and kv_cache=True, else ValueError): the prefill runs over the prompts' own
+    positions, packed behind one another, instead of the padded width -- the model's packed prefill (BackpackModel: the ragged
+    flash call, the packed sense kernels, bp_scatter_packed_rows into the caches), and the LM head over the B last rows alone.
+    Everything behind the prefill is the same loop.  The logits are those of other GEMM shapes: tokens can differ from the padded
+    prefill's where two logits are within rounding.  A model that takes no packed prefill (packed_prefill_limit) runs the
+    padded one, with one warning per model; the sense-intervened wrappers raise NotImplementedError.
     pick_options: the keywords of PickOptions, see there."""
     return _run_loop(input_ids, model, max_length, lambda logits: torch.argmax(logits, dim=-1), False, cg, kv_cache, rng_state,
-                     device_pick, stop_check_every, pick_options, prompt_lengths, output_logprobs, top_logprobs)
+                     device_pick, stop_check_every, pick_options, prompt_lengths, output_logprobs, top_logprobs,
+                     **({'packed_prefill': True} if packed_prefill else {}))
 
 
 def sample(input_ids, model, max_length, cg=False, kv_cache=False, rng_state=None, device_pick=False, stop_check_every=None,
-           prompt_lengths=None, output_logprobs=False, top_logprobs=0, **pick_options):
+           prompt_lengths=None, output_logprobs=False, top_logprobs=0, packed_prefill=False, **pick_options):
     """Ancestral sampling from softmax(logits) (reference :23-48); cg / kv_cache as in greedy_decode.
     temperature, top_k (ties at the threshold kept, as the reference's top_k_filter, training/run_pplm.py:569-581), top_p:
     the usual filters; any of them, an `rng_state` or device_pick=True selects the device pick (bp_pick_token, contract in
@@ -782,11 +852,13 @@ def sample(input_ids, model, max_length, cg=False, kv_cache=False, rng_state=Non
     so cached, graphed and growing-prefix runs under one rng_state draw the same numbers.
     prompt_lengths: right-padded prompts of different lengths, as in greedy_decode; the position t of a draw is the row's own.
     output_logprobs, top_logprobs: the record of the picks, as in greedy_decode.
+    packed_prefill: the prefill over the packed prompts, as in greedy_decode.
     pick_options: the keywords of PickOptions, see there."""
     def pick(logits):
         return torch.distributions.Categorical(logits=torch.log_softmax(logits.float(), dim=-1)).sample()
     return _run_loop(input_ids, model, max_length, pick, True, cg, kv_cache, rng_state, device_pick, stop_check_every,
-                     pick_options, prompt_lengths, output_logprobs, top_logprobs)
+                     pick_options, prompt_lengths, output_logprobs, top_logprobs,
+                     **({'packed_prefill': True} if packed_prefill else {}))
 
 
 # ---- beam search on the KV cache: bp_beam_pick / bp_beam_copy_rows, or their torch restatements on CPU tensors -----------------
@@ -1018,6 +1090,11 @@ class GenerationMixin:
         """The keywords of a call that asks for a record, none without: such a call runs the statements it always ran."""
         return {'output_logprobs': output_logprobs, 'top_logprobs': top_logprobs} if output_logprobs or top_logprobs else {}
 
+    def _packed(self, packed_prefill):
+        """The keyword of a call with packed_prefill=True, none without: such a call runs the statements it always ran.  A
+        model whose prefill is written for (B, S) ids overrides this to refuse."""
+        return {'packed_prefill': True} if packed_prefill else {}
+
     def _generate(self, decode, input_ids, max_length, return_dict_in_generate, output_scores, cg, kv_cache, **pick_options):
         output = decode(input_ids, self, max_length, cg=cg, kv_cache=kv_cache, **pick_options)
         if not output_scores:
@@ -1026,21 +1103,23 @@ class GenerationMixin:
 
     def generate(self, input_ids, max_length, return_dict_in_generate=False, output_scores=False, cg=False, kv_cache=False,
                  rng_state=None, device_pick=False, stop_check_every=None, prompt_lengths=None, output_logprobs=False,
-                 top_logprobs=0, **pick_options):
+                 top_logprobs=0, packed_prefill=False, **pick_options):
         """greedy_decode on this model; prompt_lengths: right-padded prompts of different lengths, see there; output_logprobs,
-        top_logprobs: the record of the picks (with return_dict_in_generate), see there; pick_options: the keywords of
-        PickOptions."""
+        top_logprobs: the record of the picks (with return_dict_in_generate), see there; packed_prefill: the prefill over the
+        packed prompts (with prompt_lengths and kv_cache=True), see there; pick_options: the keywords of PickOptions."""
         return self._generate(greedy_decode, input_ids, max_length, return_dict_in_generate, output_scores, cg, kv_cache,
                               rng_state=rng_state, device_pick=device_pick, stop_check_every=stop_check_every,
-                              **self._ragged(prompt_lengths), **self._recorded(output_logprobs, top_logprobs), **pick_options)
+                              **self._ragged(prompt_lengths), **self._recorded(output_logprobs, top_logprobs),
+                              **self._packed(packed_prefill), **pick_options)
 
     def sample(self, input_ids, max_length, return_dict_in_generate=False, output_scores=False, cg=False, kv_cache=False,
                rng_state=None, device_pick=False, stop_check_every=None, prompt_lengths=None, output_logprobs=False,
-               top_logprobs=0, **pick_options):
-        """sample on this model; prompt_lengths, output_logprobs, top_logprobs and pick_options as generate's."""
+               top_logprobs=0, packed_prefill=False, **pick_options):
+        """sample on this model; prompt_lengths, output_logprobs, top_logprobs, packed_prefill and pick_options as generate's."""
         return self._generate(sample, input_ids, max_length, return_dict_in_generate, output_scores, cg, kv_cache,
                               rng_state=rng_state, device_pick=device_pick, stop_check_every=stop_check_every,
-                              **self._ragged(prompt_lengths), **self._recorded(output_logprobs, top_logprobs), **pick_options)
+                              **self._ragged(prompt_lengths), **self._recorded(output_logprobs, top_logprobs),
+                              **self._packed(packed_prefill), **pick_options)
 
     def beam_search(self, input_ids, max_length, num_beams, return_dict_in_generate=False, eos_token_id=None,
                     pad_token_id=None, length_penalty=0.0, cg=False, stop_check_every=None, prompt_lengths=None,

@@ -64,7 +64,9 @@ extern "C" {
                               and one more: bp_pick_report, the record of a decode step's pick -- log-probability and rank of
                               the token, entropy, the n most likely tokens -- in the record column the counter names);
                               and four more: bp_gemm_bf16 / bp_gemm_f16, a dense layer by a pinned hipBLASLt solution, with
-                              bp_gemm_library / bp_gemm_heuristic, BP_ERR_GEMM and the BP_GEMM_* statuses) */
+                              bp_gemm_library / bp_gemm_heuristic, BP_ERR_GEMM and the BP_GEMM_* statuses;
+                              and one more: bp_scatter_packed_rows, the rows of a packed batch into (batch, positions, ...)
+                              buffers -- the prefill of the KV caches from packed prompts) */
 
 /* element type of q/k/v/out/content tensors */
 #define BP_DTYPE_F16 0
@@ -911,6 +913,31 @@ int bp_beam_pick(const void *logits, float *beam_scores, int32_t *finished, int3
 int bp_beam_copy_rows(const void *const *bases, const int64_t *row_strides, const int64_t *pos_bytes, int nsets,
                       const int32_t *parent, const int32_t *lengths, int rows, int first_position, int max_positions,
                       bp_stream_t stream);
+
+/*
+ * bp_scatter_packed_rows -- the rows of a packed batch land in padded buffers, in one launch for all of them: the prefill of
+ * the KV caches from packed prompts.  A "row set" is a source of total_rows rows, row t at src[i] + t * src_row_strides[i]
+ * bytes, and a destination whose entry [b][j] lies at dst[i] + b * dst_batch_strides[i] + j * dst_pos_strides[i]; a row is
+ * row_bytes[i] contiguous bytes at both ends.  For every set i, every sample b < batch and every position
+ * j < min(len_b, max_seqlen, max_positions), len_b = cu_seqlens[b + 1] - cu_seqlens[b], row cu_seqlens[b] + j of the source
+ * is copied to [b][j] of the destination.  No other byte of any destination is written.  (Additive, ABI still 11.)
+ *   src, src_row_strides, dst, dst_batch_strides, dst_pos_strides, row_bytes   HOST arrays of nsets entries, read during
+ *                the call and passed to the kernel by value (a captured graph keeps them: the buffers must not move)
+ *   cu_seqlens   int32 (batch + 1) on the device, read on the device only: the call reads no host value that depends on
+ *                it and is legal while a stream is capturing.  It is NOT trusted: a negative length counts as 0, a length
+ *                is clamped as above, and a source row outside [0, total_rows) is skipped -- whatever cu_seqlens holds,
+ *                nothing is read outside the sources and nothing is written outside [b][0, max_positions) of a destination.
+ *   total_rows, max_seqlen, max_positions   host values; min(max_seqlen, max_positions) == 0 is a successful no-op
+ * A set whose bases, strides and row_bytes are all multiples of 16 moves 16-byte words, any other set dwords.
+ * Sources and destinations must not overlap.
+ * Errors, before any launch: BP_ERR_SHAPE (nsets outside 1..32, batch outside 1..65535, a NULL argument or entry, a base, a
+ * stride or a row_bytes that is not a multiple of 4, row_bytes < 4 or larger than the set's source row stride or destination
+ * position stride, a negative destination batch stride, a negative max_seqlen, max_positions or total_rows).
+ */
+int bp_scatter_packed_rows(const void *const *src, const int64_t *src_row_strides, void *const *dst,
+                           const int64_t *dst_batch_strides, const int64_t *dst_pos_strides, const int64_t *row_bytes,
+                           int nsets, const int32_t *cu_seqlens, int batch, int64_t total_rows, int max_seqlen,
+                           int max_positions, bp_stream_t stream);
 
 /*
  * bp_row_extremes -- the n largest and the n smallest elements of every row of a (rows, cols) matrix, with their columns,

@@ -25,7 +25,9 @@ bp_pick_token_lim `--variant all:no_repeat_ngram_size=3,frequency_penalty=0.5,pr
 --prompt-lengths LO:HI[:SEED] (kv legs only) adds two further picks that alternate with the others: `ragged`, the device pick
 with prompt_lengths drawn once on the host, uniformly from LO..HI (seed SEED, default 0) with the maximum forced to --prompt,
 so that the padded width and the number of new tokens are those of the other picks; and `ragged_equal`, the same call with
-every length equal to --prompt, i.e. the work of the pick without the argument through the new path.
+every length equal to --prompt, i.e. the work of the pick without the argument through the new path; and the two again with
+packed_prefill=True, `ragged_packed` and `ragged_equal_packed`: the prefill over the prompts' own positions against the prefill
+over the padded width (with --max-length = --prompt + 2 one token is generated behind the prefill: the time is the prefill's).
 
 --beams W[,W...] times beam search instead (its own line per sense_table mode): for every width W, beam_search(num_beams=W,
 cg=True) against the greedy device-pick leg generate(kv_cache=True, cg=True, device_pick=True) at the same number of rows
@@ -126,7 +128,10 @@ def main():
             options['ragged'] = dict(options['device'], prompt_lengths=drawn.tolist())
             res['prompt_lengths'] = dict(lo=lo, hi=hi, seed=seed[0] if seed else 0, min=int(drawn.min()),
                                          mean=round(drawn.float().mean().item(), 2))
-            picks = picks + ['ragged_equal', 'ragged']
+            options['ragged_equal_packed'] = dict(options['ragged_equal'], packed_prefill=True)
+            options['ragged_packed'] = dict(options['ragged'], packed_prefill=True)
+            res['prompt_lengths']['sum'] = int(drawn.sum())
+            picks = picks + ['ragged_equal', 'ragged', 'ragged_equal_packed', 'ragged_packed']
         decode = model.sample if a.sample else model.generate
         for key, cg, kv in legs:
             runs = {pick: [] for pick in picks}
