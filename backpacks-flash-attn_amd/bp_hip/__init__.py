@@ -99,6 +99,9 @@ SIGNATURES = {
                           + [_i32, _f32, _f32, _i32, _ptr, _i32, _i32, _ptr]),
     'bp_pick_token_lim_rows': (_i32, [_ptr] * 7 + [_i32] * 2 + [_i64] * 3 + [_i32] * 2 + [_f32, _i32, _f32, _f32] + [_i32] * 3
                                + [_i32, _f32, _f32, _i32, _ptr, _i32, _ptr, _ptr, _i32, _ptr]),
+    'bp_pick_token_phrases': (_i32, [_ptr] * 7 + [_i32] * 2 + [_i64] * 3 + [_i32] * 2 + [_f32, _i32, _f32, _f32] + [_i32] * 3
+                              + [_i32, _f32, _f32, _i32, _ptr, _i32, _ptr, _ptr] + [_ptr, _ptr, _i32, _i32] * 2
+                              + [_ptr, _ptr, _i32, _ptr]),
     'bp_beam_pick_ws_floats': (_i64, [_i32] * 2),
     'bp_beam_pick': (_i32, [_ptr] * 8 + [_i64] + [_i32] * 3 + [_i64] * 3 + [_i32] * 4 + [_ptr]),
     'bp_beam_copy_rows': (_i32, [_ptr] * 3 + [_i32] + [_ptr] * 2 + [_i32] * 3 + [_ptr]),
@@ -1360,16 +1363,47 @@ def sense_rows_dot(table, row_index, new_row, cache_seqlens, vec, out):
     return out
 
 
-# ---- token selection on the device (C ABI bp_pick_token, bp_pick_token_ctl, bp_pick_token_lim, bp_pick_token_lim_rows) ---------------------------------------------------------------------------------------------
+# ---- token selection on the device (C ABI bp_pick_token, bp_pick_token_ctl, bp_pick_token_lim, bp_pick_token_lim_rows, bp_pick_token_phrases) ---------------------------------------------------------------------------------------------
 
 _PICK_DTYPES = {torch.float16: 0, torch.bfloat16: 1, torch.float32: 2}
 
 
+PICK_MAX_PHRASE_LEN = 64      # BP_PICK_MAX_PHRASE_LEN of include/bp_hip.h
+PICK_MAX_PHRASES = 1024       # BP_PICK_MAX_PHRASES
+
+
+def pack_phrases(phrases, device, what='phrases'):
+    """A list of token-id lists as the (ids, offsets) pair of int32 tensors on `device` that bp_pick_token_phrases reads: phrase
+    j is ids[offsets[j] : offsets[j + 1]].  An already packed pair passes through (checked for form, not read).  ValueError for
+    an empty phrase, one longer than PICK_MAX_PHRASE_LEN, and more than PICK_MAX_PHRASES phrases."""
+    if isinstance(phrases, tuple) and len(phrases) == 2 and all(isinstance(t, torch.Tensor) for t in phrases):   # a TUPLE
+        ids, offsets = phrases
+        if any(t.dim() != 1 or t.dtype != torch.int32 or not t.is_contiguous() for t in (ids, offsets)) or offsets.numel() < 1:
+            raise RuntimeError(f'bp_hip.pick_token: packed {what} must be contiguous 1-d int32 tensors (ids, offsets)')
+        if offsets.numel() - 1 > PICK_MAX_PHRASES:
+            raise ValueError(f'bp_hip.pick_token: at most {PICK_MAX_PHRASES} {what}')
+        return ids, offsets
+    rows = [[int(t) for t in (ph.tolist() if isinstance(ph, torch.Tensor) else ph)] for ph in phrases]
+    if len(rows) > PICK_MAX_PHRASES:
+        raise ValueError(f'bp_hip.pick_token: at most {PICK_MAX_PHRASES} {what}')
+    if any(not 1 <= len(r) <= PICK_MAX_PHRASE_LEN for r in rows):
+        raise ValueError(f'bp_hip.pick_token: every one of {what} must hold 1 to {PICK_MAX_PHRASE_LEN} ids')
+    offsets = [0]
+    for r in rows:
+        offsets.append(offsets[-1] + len(r))
+    ids = torch.tensor([t for r in rows for t in r], dtype=torch.int32).to(device)
+    return ids, torch.tensor(offsets, dtype=torch.int32).to(device)
+
+
 def pick_form(repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, min_length=0, finished=None,
-              no_repeat_ngram_size=0, frequency_penalty=0.0, presence_penalty=0.0, penalty_begin=0, suppress_tokens=None):
-    """The C ABI entry pick_token calls for these options: 'rows' (bp_pick_token_lim_rows) when penalty_begin or min_length is a
+              no_repeat_ngram_size=0, frequency_penalty=0.0, presence_penalty=0.0, penalty_begin=0, suppress_tokens=None,
+              bad_words_ids=None, stop_sequences=None):
+    """The C ABI entry pick_token calls for these options: 'phrases' (bp_pick_token_phrases) when bad_words_ids or stop_sequences
+    is given, else 'rows' (bp_pick_token_lim_rows) when penalty_begin or min_length is a
     tensor (one value per row), else 'lim' (bp_pick_token_lim) when any limit is given, else 'ctl' (bp_pick_token_ctl) when any
     control is, else 'plain' (bp_pick_token).  A non-zero penalty_begin counts as a limit."""
+    if bad_words_ids is not None or stop_sequences is not None:
+        return 'phrases'
     if isinstance(penalty_begin, torch.Tensor) or isinstance(min_length, torch.Tensor):
         return 'rows'
     if not (no_repeat_ngram_size == 0 and frequency_penalty == 0.0 and presence_penalty == 0.0 and penalty_begin == 0
@@ -1414,7 +1448,7 @@ def _pad_id(eos_token_id, pad_token_id):
 def pick_token(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rng_state=None, counters=None, tokens=None,
                sequences=None, return_stats=False, repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, min_length=0,
                finished=None, no_repeat_ngram_size=0, frequency_penalty=0.0, presence_penalty=0.0, penalty_begin=0,
-               suppress_tokens=None):
+               suppress_tokens=None, bad_words_ids=None, stop_sequences=None, ends=None, reasons=None):
     """The next token of every row of `logits` (B, vocab) fp16 / bf16 / fp32 (any row stride), chosen on the device by one
     launch that reads no host value (legal inside a HIP-graph capture): argmax (lowest index of the maximum, NaN largest),
     or with do_sample a draw after temperature, top-k (ties kept) and top-p -- the contract is in include/bp_hip.h.
@@ -1439,9 +1473,23 @@ def pick_token(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rng
 
     penalty_begin and min_length each take an int, or a contiguous (B,) int32 tensor on the device with one value per row
     (negative entries count as 0): a tensor selects bp_pick_token_lim_rows, the limited pick for rows that begin at different
-    positions.  The tensors are not read on the host."""
+    positions.  The tensors are not read on the host.
+
+    bad_words_ids, stop_sequences (each a list of token-id lists, packed here once per call, or an already packed (ids,
+    offsets) pair of int32 tensors on the device: pack_phrases) select bp_pick_token_phrases, the row-limited pick with phrases:
+    the last id of a bad word is -inf while the row's history ends with the ids in front of it, and a row whose text behind
+    penalty_begin ends with a stop sequence has its flag set (needs `sequences` and `finished`), once counters[b] >= min_length.
+    ends, reasons: optional contiguous (B,) int32 tensors on the device, written for the rows this call finishes: counters[b] + 1,
+    and 0 for the EOS id or 1 + the index of the stop sequence.  Both need one of the two lists."""
     per_row = [v for v in (penalty_begin, min_length) if isinstance(v, torch.Tensor)]
-    _require_cuda(logits, rng_state, counters, tokens, sequences, finished, suppress_tokens, *per_row)
+    form = pick_form(repetition_penalty, eos_token_id, pad_token_id, min_length, finished, no_repeat_ngram_size,
+                     frequency_penalty, presence_penalty, penalty_begin, suppress_tokens, bad_words_ids, stop_sequences)
+    if form != 'phrases' and (ends is not None or reasons is not None):
+        raise RuntimeError('bp_hip.pick_token: ends and reasons need bad_words_ids or stop_sequences')
+    ban = pack_phrases(bad_words_ids, logits.device, 'bad_words_ids') if bad_words_ids is not None else None
+    stop = pack_phrases(stop_sequences, logits.device, 'stop_sequences') if stop_sequences is not None else None
+    _require_cuda(logits, rng_state, counters, tokens, sequences, finished, suppress_tokens, *per_row, *(ban or ()), *(stop or ()),
+                  ends, reasons)
     tokens, strides = _pick_outputs('pick_token', 'B', logits, tokens, sequences, finished)
     batch, vocab = logits.shape
     if do_sample and rng_state is None:
@@ -1455,9 +1503,9 @@ def pick_token(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rng
         raise RuntimeError('bp_hip.pick_token: suppress_tokens must be a contiguous 1-d int32 tensor')
     if any(v.shape != (batch,) or v.dtype != torch.int32 or not v.is_contiguous() for v in per_row):
         raise RuntimeError('bp_hip.pick_token: a per-row penalty_begin / min_length must be a contiguous (B,) int32 tensor')
+    if any(v is not None and (v.shape != (batch,) or v.dtype != torch.int32 or not v.is_contiguous()) for v in (ends, reasons)):
+        raise RuntimeError('bp_hip.pick_token: ends and reasons must be contiguous (B,) int32 tensors')
     stats = torch.empty((batch, 4), dtype=torch.float32, device=logits.device) if return_stats else None
-    form = pick_form(repetition_penalty, eos_token_id, pad_token_id, min_length, finished, no_repeat_ngram_size,
-                     frequency_penalty, presence_penalty, penalty_begin, suppress_tokens)
     args = [logits.data_ptr(), tokens.data_ptr(), _ptr(sequences), _ptr(stats), _ptr(rng_state), _ptr(counters)]
     if form != 'plain':
         args.append(_ptr(finished))
@@ -1465,15 +1513,20 @@ def pick_token(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rng
     if form != 'plain':
         args += [float(repetition_penalty), -1 if eos_token_id is None else int(eos_token_id),
                  _pad_id(eos_token_id, pad_token_id), 0 if isinstance(min_length, torch.Tensor) else int(min_length)]
-    if form in ('lim', 'rows'):
+    if form in ('lim', 'rows', 'phrases'):
         n_suppress = suppress_tokens.numel() if suppress_tokens is not None else 0
         args += [int(no_repeat_ngram_size), float(frequency_penalty), float(presence_penalty),
                  0 if isinstance(penalty_begin, torch.Tensor) else int(penalty_begin),
                  suppress_tokens.data_ptr() if n_suppress else None, n_suppress]
-    if form == 'rows':
+    if form in ('rows', 'phrases'):
         args += [v.data_ptr() if isinstance(v, torch.Tensor) else None for v in (penalty_begin, min_length)]
-    _call({'plain': 'bp_pick_token', 'ctl': 'bp_pick_token_ctl', 'lim': 'bp_pick_token_lim',
-           'rows': 'bp_pick_token_lim_rows'}[form], logits.device, *args, _PICK_DTYPES[logits.dtype])
+    if form == 'phrases':
+        for packed in (ban, stop):
+            n = packed[1].numel() - 1 if packed is not None else 0
+            args += [packed[0].data_ptr(), packed[1].data_ptr(), n, packed[0].numel()] if n > 0 else [None, None, 0, 0]
+        args += [_ptr(ends), _ptr(reasons)]
+    _call({'plain': 'bp_pick_token', 'ctl': 'bp_pick_token_ctl', 'lim': 'bp_pick_token_lim', 'rows': 'bp_pick_token_lim_rows',
+           'phrases': 'bp_pick_token_phrases'}[form], logits.device, *args, _PICK_DTYPES[logits.dtype])
     return (tokens, stats) if return_stats else tokens
 
 

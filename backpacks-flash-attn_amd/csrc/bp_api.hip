@@ -131,7 +131,8 @@ const char *bp_strerror(int code) {
         case BP_ERR_WORKSPACE: return "workspace smaller than the *_ws_floats() query of this entry point";
         case BP_ERR_SAMPLING: return "token sampling: top_p must be in (0, 1], rng_state non-NULL when do_sample; repetition_penalty finite and > 0 and, "
                                      "unless 1, with sequences; an eos_token_id with finished flags; finite frequency / presence penalties and, like n-gram "
-                                     "blocking, with sequences; a non-NULL aligned suppress_ids when n_suppress > 0";
+                                     "blocking, with sequences; a non-NULL aligned suppress_ids when n_suppress > 0; phrase lists with non-NULL ids and offsets and "
+                                     "with sequences, stop phrases with finished flags";
         case BP_ERR_GEMM: return "a call into hipBLASLt or the HIP runtime failed";
         default: return "unknown error";
     }
@@ -1174,6 +1175,48 @@ int bp_pick_token_lim_rows(const void *logits, int64_t *tokens, int64_t *sequenc
                                   presence_penalty, penalty_begin, suppress_ids, n_suppress, penalty_begins, min_lengths, dtype);
     if (e != BP_OK) return e;
     return launch_status(bp::launch_pick_token_rows(p, dtype, static_cast<hipStream_t>(stream)));
+}
+
+// one phrase list of bp_pick_token_phrases: the checks the host can make (the contents stay on the device, unread)
+static int pick_phrase_list(const int32_t *ids, const int32_t *offsets, int n, int total, const int64_t *sequences) {
+    if (n < 0 || total < 0 || n > BP_PICK_MAX_PHRASES) return BP_ERR_SHAPE;
+    if (reinterpret_cast<uintptr_t>(ids) % 4 || reinterpret_cast<uintptr_t>(offsets) % 4) return BP_ERR_SHAPE;
+    if (n > 0 && (ids == nullptr || offsets == nullptr || sequences == nullptr)) return BP_ERR_SAMPLING;
+    return BP_OK;
+}
+
+int bp_pick_token_phrases(const void *logits, int64_t *tokens, int64_t *sequences, float *stats, const uint64_t *rng_state,
+                          const int32_t *counters, int32_t *finished,
+                          int batch, int vocab, int64_t row_stride, int64_t tokens_stride, int64_t seq_stride, int seq_cols,
+                          int do_sample, float temperature, int top_k, float top_p,
+                          float repetition_penalty, int eos_token_id, int pad_token_id, int min_length,
+                          int no_repeat_ngram_size, float frequency_penalty, float presence_penalty, int penalty_begin,
+                          const int32_t *suppress_ids, int n_suppress, const int32_t *penalty_begins,
+                          const int32_t *min_lengths,
+                          const int32_t *ban_ids, const int32_t *ban_offsets, int n_ban, int ban_total,
+                          const int32_t *stop_ids, const int32_t *stop_offsets, int n_stop, int stop_total,
+                          int32_t *ends, int32_t *reasons, int dtype, bp_stream_t stream) {
+    static_assert(BP_PICK_MAX_PHRASE_LEN == bp::kMaxPhraseLen && BP_PICK_MAX_PHRASES == bp::kMaxPhrases, "bp_hip.h and bp_kernels.h");
+    bp::PickParams p{};
+    int e = pick_lim_params(p, logits, tokens, sequences, stats, rng_state, counters, finished, batch, vocab, row_stride,
+                            tokens_stride, seq_stride, seq_cols, do_sample, temperature, top_k, top_p, repetition_penalty,
+                            eos_token_id, pad_token_id, min_length, no_repeat_ngram_size, frequency_penalty,
+                            presence_penalty, penalty_begin, suppress_ids, n_suppress, penalty_begins, min_lengths, dtype);
+    if (e != BP_OK) return e;
+    e = pick_phrase_list(ban_ids, ban_offsets, n_ban, ban_total, sequences);
+    if (e != BP_OK) return e;
+    e = pick_phrase_list(stop_ids, stop_offsets, n_stop, stop_total, sequences);
+    if (e != BP_OK) return e;
+    if (n_stop > 0 && finished == nullptr) return BP_ERR_SAMPLING;
+    if (reinterpret_cast<uintptr_t>(ends) % 4 || reinterpret_cast<uintptr_t>(reasons) % 4) return BP_ERR_SHAPE;
+    if (n_ban > 0 && vocab > BP_PICK_MAX_LIMITED_VOCAB) return BP_ERR_SHAPE;   // the ban bitmap: 64 KB of LDS at most
+    p.ban_ids = n_ban > 0 ? ban_ids : nullptr; p.ban_offsets = n_ban > 0 ? ban_offsets : nullptr;
+    p.n_ban = n_ban; p.ban_total = ban_total;
+    p.stop_ids = n_stop > 0 ? stop_ids : nullptr; p.stop_offsets = n_stop > 0 ? stop_offsets : nullptr;
+    p.n_stop = n_stop; p.stop_total = stop_total;
+    p.ends = ends; p.reasons = reasons;
+    if (bp::pick_phrases_lds_bytes(p) > BP_PICK_MAX_LDS_BYTES) return BP_ERR_SHAPE;
+    return launch_status(bp::launch_pick_token_phrases(p, dtype, static_cast<hipStream_t>(stream)));
 }
 
 // ---- beam search (bp_beam_pick, bp_beam_copy_rows) ----

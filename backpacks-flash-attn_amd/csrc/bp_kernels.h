@@ -363,11 +363,20 @@ struct PickParams {
     // bp_pick_token_lim_rows only (pick_token_rows.hip); no other kernel reads past pres_pen
     const int32_t *penalty_begins;   // optional (batch): replaces penalty_begin for row b; negative entries count as 0
     const int32_t *min_lengths;      // optional (batch): replaces min_length for row b; negative entries count as 0
+    // bp_pick_token_phrases only (pick_token_phrases.hip); no other kernel reads past min_lengths.  Phrase j of a list is
+    // ids[offsets[j] : offsets[j + 1]]; the kernel checks every offset against `total` and every length against kMaxPhraseLen
+    const int32_t *ban_ids, *ban_offsets;     // n_ban phrases: the last id is banned behind the others
+    const int32_t *stop_ids, *stop_offsets;   // n_stop phrases: generated text that ends with one finishes the row
+    int32_t *ends, *reasons;                  // optional (batch) each: written when this call sets finished[b]
+    int n_ban, ban_total, n_stop, stop_total;
 };
+constexpr int kMaxPhraseLen = 64;    // BP_PICK_MAX_PHRASE_LEN
+constexpr int kMaxPhrases = 1024;    // BP_PICK_MAX_PHRASES: one phrase per thread of the pick's workgroup
 hipError_t launch_pick_token(const PickParams &p, int dtype, hipStream_t stream);
 hipError_t launch_pick_token_ctl(const PickParams &p, int dtype, hipStream_t stream);
 hipError_t launch_pick_token_lim(const PickParams &p, int dtype, hipStream_t stream);
 hipError_t launch_pick_token_rows(const PickParams &p, int dtype, hipStream_t stream);
+hipError_t launch_pick_token_phrases(const PickParams &p, int dtype, hipStream_t stream);
 // 32 - log2(slots), slots = the power of two >= 2 seq_cols (at least 2)
 inline int lim_table_shift(int seq_cols) {
     int log2 = 1;
@@ -375,6 +384,7 @@ inline int lim_table_shift(int seq_cols) {
     return 32 - log2;
 }
 size_t pick_lim_lds_bytes(const PickParams &p);   // static + dynamic LDS of a bp_pick_token_lim / _lim_rows launch
+size_t pick_phrases_lds_bytes(const PickParams &p);   // of a bp_pick_token_phrases launch: the ban bitmap is on for a ban list too
 
 // bp_beam_pick (beam_pick.hip): one beam-search step, rows r = g * beam_width + w
 struct BeamPickParams {

@@ -1,6 +1,6 @@
 // Token selection on the device for the decode loops: one row of logits in, one token out.  The shared body of
 // bp_pick_token (csrc/pick_token.hip), bp_pick_token_ctl (csrc/pick_token_ctl.hip), bp_pick_token_lim (csrc/pick_token_lim.hip) and
-// bp_pick_token_lim_rows (csrc/pick_token_rows.hip).
+// bp_pick_token_lim_rows (csrc/pick_token_rows.hip) and bp_pick_token_phrases (csrc/pick_token_phrases.hip).
 //
 // Replaces the host-driven picks of the generation loops (src/utils/generation.py: torch.argmax, and
 // torch.distributions.Categorical, whose argument validation reads a device value on the host) and adds the sampling
@@ -64,6 +64,17 @@
 // tag and code object.  The two values of a row are resolved before pass 1 (row_params: a uniform load each, negative entries
 // clamped to 0, the scalar when the array is NULL) and are dead behind it: the first only feeds the `counted` flag of the
 // table build, the second only the choice of the masked column.  Nothing else differs from the limited form.
+//
+// Phrased form (bp_pick_token_phrases, pick_token_phrases.hip): pick_token_kernel<Phrased<ET>> is the row-limited form with two
+// lists of phrases (ids + offsets on the device, never read by the host, so every entry is checked here).  A fifth tag and
+// code object.  What it adds:
+//   ban   in `build`, behind the suppressed ids: thread-strided over the phrases, each comparing at most L - 1 int64 entries
+//         of the end of the history against its first L - 1 ids and setting the `banned` bit of its last id on a match.  The
+//         bitmap is on when n_ban > 0 (the second argument of LimLayout: the other forms never read the field)
+//   stop  behind the token's write, by the whole workgroup: the writing lane leaves the token in sel_digit and ~0 in sel_above
+//         (both dead behind the selects, whose last barrier every thread has passed), a barrier, thread-strided over the phrases
+//         each compares BACKWARDS from the new token and leaves at the first mismatch, atomicMin of the matching index on
+//         sel_above, a barrier, and thread 0 writes the flag, `ends` and `reasons` -- for the EOS id too, which wins
 #pragma once
 #include <type_traits>
 
@@ -81,13 +92,17 @@ template <class ET> struct Controlled {};
 template <class ET> struct Limited {};
 // Row-limited form: the limited one with penalty_begin and min_length per row (bp_pick_token_lim_rows)
 template <class ET> struct RowLimited {};
-template <class T> struct PickTag { using elem = T; static constexpr bool ctl = false, lim = false, rows = false; };
-template <class T> struct PickTag<Controlled<T>> { using elem = T; static constexpr bool ctl = true, lim = false, rows = false; };
-template <class T> struct PickTag<Limited<T>> { using elem = T; static constexpr bool ctl = true, lim = true, rows = false; };
-template <class T> struct PickTag<RowLimited<T>> { using elem = T; static constexpr bool ctl = true, lim = true, rows = true; };
+// Phrased form: the row-limited one with banned and stop phrases (bp_pick_token_phrases)
+template <class ET> struct Phrased {};
+template <class T> struct PickTag { using elem = T; static constexpr bool ctl = false, lim = false, rows = false, phrases = false; };
+template <class T> struct PickTag<Controlled<T>> { using elem = T; static constexpr bool ctl = true, lim = false, rows = false, phrases = false; };
+template <class T> struct PickTag<Limited<T>> { using elem = T; static constexpr bool ctl = true, lim = true, rows = false, phrases = false; };
+template <class T> struct PickTag<RowLimited<T>> { using elem = T; static constexpr bool ctl = true, lim = true, rows = true, phrases = false; };
+template <class T> struct PickTag<Phrased<T>> { using elem = T; static constexpr bool ctl = true, lim = true, rows = true, phrases = true; };
 
 // Dynamic LDS of the limited form, in 32-bit words: [members][banned][count table], each only when its control is on.  The
-// switches depend on the arguments alone, never on a row, so the host sizes the allocation from the same struct.
+// switches depend on the arguments alone, never on a row, so the host sizes the allocation from the same struct.  `phrase_ban`
+// is the phrased form's own switch of the ban bitmap (n_ban > 0): a constant false everywhere else.
 constexpr uint32_t kLimIdBits = 19, kLimIdMask = (1u << kLimIdBits) - 1u, kLimEmpty = 0xffffffffu;
 constexpr int kLimMaxCols = (1 << (32 - kLimIdBits)) - 1;   // 8191: what the 13 count bits hold
 // slot of an id in a table of 2^(32 - shift) slots: a multiplicative (Fibonacci) hash, tests/pick_lim_ref.py restates it
@@ -95,10 +110,10 @@ __host__ __device__ inline uint32_t lim_hash(uint32_t id, int shift) { return (i
 struct LimLayout {
     bool members_on, banned_on, counts_on;
     int ban_at, table_at, slots, total_words;
-    __host__ __device__ explicit LimLayout(const PickParams &p) {
+    __host__ __device__ explicit LimLayout(const PickParams &p, bool phrase_ban = false) {
         counts_on = p.freq_pen != 0.f || p.pres_pen != 0.f;
         members_on = p.theta != 1.f || counts_on;
-        banned_on = p.ngram > 0 || p.n_suppress > 0;
+        banned_on = p.ngram > 0 || p.n_suppress > 0 || phrase_ban;
         const int words = (p.vocab + 31) / 32 + 1;
         ban_at = members_on ? words : 0;
         table_at = ban_at + (banned_on ? words : 0);
@@ -163,10 +178,11 @@ template <class ET> struct Logits<Limited<ET>> {
     const uint32_t *members, *banned, *table;   // dynamic LDS; NULL: that control is off
     float inv_t, theta, inv_theta, freq, pres;
     int eos, shift;
-    BP_DEV Logits(const PickParams &p, int counter, const uint32_t *lds)
+    // phrase_ban: LimLayout's, true only from the phrased form
+    BP_DEV Logits(const PickParams &p, int counter, const uint32_t *lds, bool phrase_ban = false)
         : inv_t(p.inv_t), theta(p.theta), inv_theta(p.inv_theta), freq(p.freq_pen), pres(p.pres_pen),
           eos(p.eos >= 0 && counter < p.min_length ? p.eos : -1), shift(p.table_shift) {
-        const LimLayout lay(p);
+        const LimLayout lay(p, phrase_ban);
         members = lay.members_on ? lds : nullptr;
         banned = lay.banned_on ? lds + lay.ban_at : nullptr;
         table = lay.counts_on ? lds + lay.table_at : nullptr;
@@ -232,16 +248,35 @@ template <class ET> struct Logits<Limited<ET>> {
             slot = (slot + 1u) & mask;
         }
     }
-    // Before pass 1, by the whole workgroup: hist = min(counter, seq_cols), possibly <= 0
-    static BP_DEV void build(const PickParams &p, int b, int hist, uint32_t *lds) {
+    // Before pass 1, by the whole workgroup: hist = min(counter, seq_cols), possibly <= 0.  PHRASES: the phrased form's ban list
+    template <bool PHRASES = false> static BP_DEV void build(const PickParams &p, int b, int hist, uint32_t *lds) {
         const int tid = threadIdx.x;
-        const LimLayout lay(p);
+        const LimLayout lay(p, PHRASES && p.n_ban > 0);
         for (int i = tid; i < lay.total_words; i += kPickThreads) lds[i] = i >= lay.table_at ? kLimEmpty : 0u;
         __syncthreads();
         uint32_t *members = lds, *banned = lds + lay.ban_at, *table = lds + lay.table_at;
         for (int i = tid; i < p.n_suppress; i += kPickThreads) {
             const int32_t id = p.suppress[i];
             if (id >= 0 && id < p.vocab) atomicOr(&banned[id >> 5], 1u << (id & 31));
+        }
+        if constexpr (PHRASES) {
+            // phrase j = ban_ids[lo : hi]; one whose offsets leave [0, ban_total] or whose length leaves 1 .. kMaxPhraseLen is
+            // ignored.  Its first L - 1 ids against the last L - 1 entries of the history, raw values; L = 1 always matches
+            if (p.sequences != nullptr) {
+                const int64_t *seq = p.sequences + (int64_t)b * p.seq_stride;
+                const int len = hist < 0 ? 0 : hist;
+                for (int j = tid; j < p.n_ban; j += kPickThreads) {
+                    const int lo = p.ban_offsets[j], hi = p.ban_offsets[j + 1];
+                    if (lo < 0 || hi > p.ban_total || hi <= lo || hi - lo > kMaxPhraseLen || len < hi - lo - 1) continue;
+                    const int n = hi - lo;
+                    const int32_t *w = p.ban_ids + lo;
+                    const int64_t *suffix = seq + (len - n + 1);   // the last n - 1 entries
+                    bool match = true;
+                    for (int t = 0; t < n - 1 && match; ++t) match = suffix[t] == (int64_t)w[t];
+                    const int32_t id = w[n - 1];
+                    if (match && id >= 0 && id < p.vocab) atomicOr(&banned[id >> 5], 1u << (id & 31));
+                }
+            }
         }
         if (p.sequences && hist > 0) {
             const int64_t *seq = p.sequences + (int64_t)b * p.seq_stride;
@@ -288,6 +323,14 @@ template <class ET> struct Logits<RowLimited<ET>> : Logits<Limited<ET>> {
         Logits<Limited<ET>>::build(row_params<RowLimited<ET>>(p, b), b, hist, lds);
     }
 };
+// Phrased rows: the row-limited form whose ban bitmap is also on for a ban list, and whose build scans that list
+template <class ET> struct Logits<Phrased<ET>> : Logits<Limited<ET>> {
+    BP_DEV Logits(const PickParams &p, int counter, const uint32_t *lds)
+        : Logits<Limited<ET>>(row_params<Phrased<ET>>(p, blockIdx.x), counter, lds, p.n_ban > 0) {}
+    static BP_DEV void build(const PickParams &p, int b, int hist, uint32_t *lds) {
+        Logits<Limited<ET>>::template build<true>(row_params<Phrased<ET>>(p, b), b, hist, lds);
+    }
+};
 
 // Where a limited row's results go, worked out before pass 1 and parked in vector registers: the limited passes need every
 // scalar register the controlled ones leave, and these addresses are not read again before the last lines of the kernel.
@@ -302,6 +345,41 @@ struct LimOutputs {
         flag = p.finished && p.eos >= 0 ? p.finished + b : nullptr;
         stats = p.stats ? p.stats + (int64_t)b * 4 : nullptr;
         asm volatile("" : "+v"(token), "+v"(column), "+v"(flag), "+v"(stats));   // no instruction: pins them to vector registers
+    }
+};
+
+// What the tail of a phrased row reads, worked out before pass 1 and parked in vector registers like LimOutputs: the flag,
+// `ends` and `reasons` of the row, the stop list, and the row's own begin.  n == 0: the row cannot end at a phrase in this call --
+// no list, or no column for the token (so the history would be clamped), or the EOS id still masked (c < the row's minimum).
+struct PhraseTail {
+    int32_t *flag, *ends, *reasons;   // NULL: not given
+    const int32_t *ids, *offsets;
+    int n, total, begin, eos, c;
+    PhraseTail() = default;
+    BP_DEV PhraseTail(const PickParams &p, const PickParams &q, int b, int counter) {   // q: row_params of the row
+        flag = p.finished ? p.finished + b : nullptr;
+        ends = p.ends ? p.ends + b : nullptr;
+        reasons = p.reasons ? p.reasons + b : nullptr;
+        ids = p.stop_ids; offsets = p.stop_offsets; total = p.stop_total;
+        n = p.finished && p.sequences && counter >= 0 && counter < p.seq_cols && counter >= q.min_length ? p.n_stop : 0;
+        begin = q.penalty_begin; eos = p.eos; c = counter;
+        asm volatile("" : "+v"(flag), "+v"(ends), "+v"(reasons), "+v"(ids), "+v"(offsets));   // no instruction, as in LimOutputs
+        asm volatile("" : "+v"(n), "+v"(total), "+v"(begin), "+v"(eos), "+v"(c));
+    }
+    // By the whole workgroup behind the token's write (header comment).  `token` sits at column c of the row, `column` points
+    // at it: the columns in front are read, never column c itself (another lane has just written it).  Phrase j matches when
+    // it lies in [begin, c] and equals the text that ends with the token; the lowest matching j goes into `low`.
+    BP_DEV void scan(const int64_t *column, int token, u64 *low) const {
+        for (int j = threadIdx.x; j < n; j += kPickThreads) {
+            const int lo = offsets[j], hi = offsets[j + 1];
+            if (lo < 0 || hi > total || hi <= lo || hi - lo > kMaxPhraseLen) continue;
+            const int len = hi - lo;
+            const int32_t *w = ids + lo;
+            if (c + 1 - len < begin || w[len - 1] != token) continue;
+            bool match = true;
+            for (int k = 1; k < len && match; ++k) match = column[-k] == (int64_t)w[len - 1 - k];
+            if (match) atomicMin(low, (u64)j);
+        }
     }
 };
 
@@ -320,6 +398,7 @@ template <class ET> struct SelectKey<Controlled<ET>> {
 };
 template <class ET> struct SelectKey<Limited<ET>> : SelectKey<Controlled<ET>> {};
 template <class ET> struct SelectKey<RowLimited<ET>> : SelectKey<Controlled<ET>> {};
+template <class ET> struct SelectKey<Phrased<ET>> : SelectKey<Controlled<ET>> {};
 
 // Radix select, 8 bits a round from the top of the key: among the elements with z >= lo, the key K with
 //   weight{key > K} < target <= weight{key >= K}
@@ -411,6 +490,7 @@ __global__ __launch_bounds__(kPickThreads) void pick_token_kernel(const PickPara
 
     const uint32_t *bitmap = nullptr;
     [[maybe_unused]] LimOutputs out;   // limited rows only
+    [[maybe_unused]] PhraseTail tail;  // phrased rows only
     if constexpr (CTL) {
         extern __shared__ uint32_t pick_bitmap[];   // (vocab + 31) / 32 + 1 words when theta != 1, else none (limited: LimLayout)
         if (p.finished && p.finished[b] != 0) {     // workgroup-uniform: the pad, no draw, the flag stays
@@ -436,6 +516,7 @@ __global__ __launch_bounds__(kPickThreads) void pick_token_kernel(const PickPara
             Logits<TAG>::build(p, b, hist, pick_bitmap);
             bitmap = pick_bitmap;
             out = LimOutputs(p, b, counter);
+            if constexpr (PickTag<TAG>::phrases) tail = PhraseTail(p, row_params<TAG>(p, b), b, counter);
         } else if (p.theta != 1.f && p.sequences && hist > 0) {
             const int words = (p.vocab + 31) / 32 + 1;
             for (int i = tid; i < words; i += kPickThreads) pick_bitmap[i] = 0u;
@@ -595,7 +676,32 @@ __global__ __launch_bounds__(kPickThreads) void pick_token_kernel(const PickPara
             }
         }
     }
-    if constexpr (PickTag<TAG>::lim) {
+    if constexpr (PickTag<TAG>::phrases) {
+        // the flag, `ends` and `reasons` wait for the stop phrases: thread 0 writes them behind the scan
+        if (sampled ? token >= 0 : tid == 0) {
+            *out.token = token;
+            if (out.column) *out.column = token;
+            sh.sel_digit = (uint32_t)token;
+            sh.sel_above = ~0ull;
+        }
+        if (out.stats && tid == 0) {
+            out.stats[0] = st_lo; out.stats[1] = st_lse; out.stats[2] = st_count; out.stats[3] = st_u;
+        }
+        __syncthreads();
+        const int picked = (int)sh.sel_digit;
+        if (tail.n > 0) tail.scan(out.column, picked, &sh.sel_above);   // workgroup-uniform
+        __syncthreads();
+        if (tid == 0 && tail.flag) {
+            const bool eos = tail.eos >= 0 && picked == tail.eos;
+            const u64 low = sh.sel_above;
+            if (eos || low != ~0ull) {
+                *tail.flag = 1;
+                if (tail.ends) *tail.ends = tail.c + 1;
+                if (tail.reasons) *tail.reasons = eos ? 0 : 1 + (int)low;
+            }
+        }
+        return;
+    } else if constexpr (PickTag<TAG>::lim) {
         if (sampled ? token >= 0 : tid == 0) {
             *out.token = token;
             if (out.column) *out.column = token;

@@ -7,6 +7,9 @@ cg=True inside the captured step (_decode_cached_picked); without them the loops
 (bp_pick_token_ctl): rows stop at their EOS, the loop ends once every row has, and `lengths` reports where.
 `no_repeat_ngram_size`, `frequency_penalty`, `presence_penalty` and `suppress_tokens` (kv_cache=True only) select its limited
 form (bp_pick_token_lim): no n-gram twice, counted penalties on what was generated, ids that never appear.
+`bad_words_ids` and `stop_sequences` (kv_cache=True only), lists of token-id lists, select its phrased form
+(bp_pick_token_phrases): a banned phrase never appears, a row ends where its generated text ends with a stop sequence, and
+`stop_reasons` tells what ended it.
 `prompt_lengths` (kv_cache=True only) takes a batch of right-padded prompts of different lengths: every row generates the same
 number of tokens behind ITS prompt (_CachedSteps; bp_pick_token_lim_rows where a limit or `min_new_tokens` needs the row's begin).
 `output_logprobs` / `top_logprobs` (kv_cache=True only) record what the model thought of every token it produced: one more
@@ -57,6 +60,9 @@ class DecoderOnlyOutput:
     token_entropies: Optional[torch.Tensor] = None      # (batch, width) fp32: entropy of the distribution it came from
     top_token_ids: Optional[torch.Tensor] = None        # (batch, width, n) int32: the n most likely tokens, best first
     top_token_logprobs: Optional[torch.Tensor] = None   # (batch, width, n) fp32: their log-probabilities
+    # (batch,) int64, when stop sequences are given: -1 the row ran to its full length, 0 its EOS id ended it, 1 + j its stop
+    # sequence j did (the lowest j where several end at the same token)
+    stop_reasons: Optional[torch.Tensor] = None
 
 
 def _decode(input_ids, model, max_length, pick):
@@ -215,6 +221,57 @@ def _history_counts(sequences, counters, vocab, begin):
     return counts[:, :vocab]
 
 
+PICK_MAX_PHRASE_LEN = 64      # bp_pick_token_phrases: BP_PICK_MAX_PHRASE_LEN of include/bp_hip.h
+PICK_MAX_PHRASES = 1024       # BP_PICK_MAX_PHRASES
+
+
+def _phrase_lists(phrases, name):
+    """`phrases` (a sequence of sequences or tensors of token ids) as a list of lists of ints, within the bounds of
+    bp_pick_token_phrases: 1 to 64 ids a phrase, at most 1024 phrases."""
+    rows = [[int(t) for t in (ph.tolist() if isinstance(ph, torch.Tensor) else ph)] for ph in phrases]
+    if len(rows) > PICK_MAX_PHRASES or any(not 1 <= len(r) <= PICK_MAX_PHRASE_LEN for r in rows):
+        raise ValueError(f'generation: {name} takes at most {PICK_MAX_PHRASES} phrases of 1 to {PICK_MAX_PHRASE_LEN} token ids')
+    return rows
+
+
+def _phrase_ban_mask(sequences, counters, vocab, phrases):
+    """(batch, vocab) bool: the last id of every phrase whose other ids are the end of the history sequences[b, :Lh], Lh =
+    min(max(counters[b], 0), cols) -- raw values compared, the prompt included; a last id outside [0, vocab) bans nothing."""
+    batch, cols = sequences.shape
+    banned = torch.zeros((batch, vocab), dtype=torch.bool, device=sequences.device)
+    for b in range(batch):
+        h = sequences[b, :min(max(int(counters[b]), 0), cols)].tolist()
+        for w in phrases:
+            if len(h) >= len(w) - 1 and h[len(h) - len(w) + 1:] == w[:-1] and 0 <= w[-1] < vocab:
+                banned[b, w[-1]] = True
+    return banned
+
+
+def _eager_stop(picked, counters, sequences, finished, begin, minimum, stop_sequences, eos_token_id):
+    """What ends a row at this pick, bp_pick_token_phrases's rule: (batch,) int64 on the CPU, -1 nothing, 0 the EOS id, 1 + j
+    stop sequence j (the lowest).  `picked` is the token of column c = counters[b]; rows whose flag is set on entry end
+    nowhere.  A stop sequence of L ids counts when the token has a column (0 <= c < cols), c >= minimum, c + 1 - L >= begin
+    and sequences[b, c + 1 - L : c] ++ [picked] equals it; begin and minimum: an int or one value per row, negatives are 0."""
+    batch = picked.shape[0]
+    reasons = torch.full((batch,), -1, dtype=torch.int64)
+    per_row = lambda v, b: max(int(v[b]) if isinstance(v, torch.Tensor) else int(v), 0)
+    for b in range(batch):
+        if finished is not None and int(finished[b]) != 0:
+            continue
+        token, c = int(picked[b]), int(counters[b])
+        if eos_token_id is not None and eos_token_id >= 0 and token == eos_token_id:
+            reasons[b] = 0
+            continue
+        if sequences is None or not 0 <= c < sequences.shape[1] or c < per_row(minimum, b):
+            continue
+        text = sequences[b, :c].tolist() + [token]
+        for j, w in enumerate(stop_sequences or ()):
+            if c + 1 - len(w) >= per_row(begin, b) and text[c + 1 - len(w):] == w:
+                reasons[b] = 1 + j
+                break
+    return reasons
+
+
 @dataclass(frozen=True)
 class PickOptions:
     """The options of the pick, as greedy_decode / sample and GenerationMixin.generate / .sample take them by keyword.
@@ -226,6 +283,11 @@ class PickOptions:
     no_repeat_ngram_size (no n-gram occurs twice, prompt included), frequency_penalty, presence_penalty (an id generated n > 0
     times loses frequency_penalty * n + presence_penalty; the prompt is not counted), suppress_tokens (a list or tensor of ids
     that are never picked): the limits of bp_pick_token_lim, under the same conditions.
+    bad_words_ids, stop_sequences (each a list of lists of token ids, 1 to 64 ids a phrase, at most 1024 phrases): the phrases of
+    bp_pick_token_phrases, under the same conditions.  The last id of a bad word is never picked while the row's text, prompt
+    included, ends with the ids in front of it.  A row whose GENERATED text ends with a stop sequence ends there like a row at
+    its EOS id (the sequence stays in the output; min_length / min_new_tokens delay it as they delay the EOS); `lengths` then
+    reports every row's end and `stop_reasons` what ended it: -1 the full length, 0 the EOS id, 1 + j stop sequence j.
     min_new_tokens: the EOS id is masked while a row has generated fewer tokens than that, i.e. below the absolute length
     prompt + min_new_tokens of the row (with prompt_lengths: the row's own prompt); not together with min_length.
     do_sample and penalty_begin (the first history position the two counted penalties see) are set by the entry points: sample()
@@ -244,6 +306,8 @@ class PickOptions:
     penalty_begin: int = 0
     suppress_tokens: object = None
     min_new_tokens: int = 0
+    bad_words_ids: object = None
+    stop_sequences: object = None
 
     def __post_init__(self):
         if not (self.temperature > 0.0 and self.temperature < float('inf')) or not 0.0 < self.top_p <= 1.0:
@@ -258,18 +322,26 @@ class PickOptions:
         if self.no_repeat_ngram_size < 0 or not all(abs(float(v)) < float('inf')
                                                     for v in (self.frequency_penalty, self.presence_penalty)):
             raise ValueError('generation: no_repeat_ngram_size must not be negative, frequency_penalty and presence_penalty finite')
+        for name in ('bad_words_ids', 'stop_sequences'):
+            if getattr(self, name) is not None:
+                _phrase_lists(getattr(self, name), name)
 
     @property
     def limited(self):
         """Whether a limit of bp_pick_token_lim is given; penalty_begin alone is none."""
         return (self.no_repeat_ngram_size != 0 or self.frequency_penalty != 0.0 or self.presence_penalty != 0.0
-                or self.suppress_tokens is not None)
+                or self.suppress_tokens is not None or self.bad_words_ids is not None)
 
     @property
     def controlled(self):
-        """Whether a control of bp_pick_token_ctl or a limit is given: the options that need kv_cache=True."""
+        """Whether a control of bp_pick_token_ctl, a limit or a stop sequence is given: the options that need kv_cache=True."""
         return (self.repetition_penalty != 1.0 or self.eos_token_id is not None or self.pad_token_id is not None
-                or self.min_length != 0 or self.min_new_tokens != 0 or self.limited)
+                or self.min_length != 0 or self.min_new_tokens != 0 or self.limited or self.stop_sequences is not None)
+
+    @property
+    def phrased(self):
+        """Whether a phrase list of bp_pick_token_phrases is given."""
+        return self.bad_words_ids is not None or self.stop_sequences is not None
 
     @property
     def wants_device_pick(self):
@@ -287,7 +359,8 @@ class PickOptions:
 
 def _eager_pick(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rng_state=None, counters=None,
                 repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, min_length=0, finished=None, sequences=None,
-                no_repeat_ngram_size=0, frequency_penalty=0.0, presence_penalty=0.0, penalty_begin=0, suppress_tokens=None):
+                no_repeat_ngram_size=0, frequency_penalty=0.0, presence_penalty=0.0, penalty_begin=0, suppress_tokens=None,
+                bad_words_ids=None, stop_sequences=None, ends=None, reasons=None):
     """The contract of bp_pick_token (include/bp_hip.h) in torch ops, for tensors the kernel does not take (CPU): tokens
     (batch,) int64 of logits (batch, vocab).  Greedy: torch.argmax (lowest index of the maximum, a NaN largest).  Sampling:
     z = float(x) / T in fp32; top-k keeps z >= the k-th largest (ties kept); top-p keeps a token iff the kept mass strictly
@@ -305,7 +378,13 @@ def _eager_pick(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rn
     the history positions >= penalty_begin loses fp32(frequency_penalty * n + presence_penalty) (float64 product and sum
     rounded once: the kernel's fma wherever the float64 sum is exact); the ids of `suppress_tokens` (a list or a tensor; ids
     outside the vocabulary are ignored) and the ids that would complete an n-gram (n = no_repeat_ngram_size) the history
-    already holds are -inf, like the masked EOS."""
+    already holds are -inf, like the masked EOS.
+
+    The phrases of bp_pick_token_phrases (lists of lists of ids): the last id of a phrase of `bad_words_ids` is -inf, too, while
+    the history ends with the ids in front of it (_phrase_ban_mask).  With `stop_sequences` (not None) this function also does
+    what the kernel does behind the pick: a row that was not finished on entry and picks the EOS id, or whose text behind
+    penalty_begin now ends with a stop sequence (_eager_stop), has its flag in `finished` set, its `ends` entry set to
+    counters[b] + 1 and its `reasons` entry to 0 (EOS) or 1 + the sequence's index; other rows' entries are left alone."""
     x = logits.float()
     batch, vocab = x.shape
     if counters is None:
@@ -329,6 +408,9 @@ def _eager_pick(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rn
         if masked is None:
             masked = torch.zeros((batch, vocab), dtype=torch.bool, device=x.device)
         masked[:, ids] = True
+    if bad_words_ids is not None and sequences is not None:
+        banned = _phrase_ban_mask(sequences, counters, vocab, _phrase_lists(bad_words_ids, 'bad_words_ids'))
+        masked = banned if masked is None else masked | banned
     minus = None
     if (frequency_penalty != 0.0 or presence_penalty != 0.0) and sequences is not None:
         counts = _history_counts(sequences, counters, vocab, penalty_begin.clamp(min=0) if isinstance(penalty_begin, torch.Tensor)
@@ -350,7 +432,17 @@ def _eager_pick(logits, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, rn
         if finished is None:
             return picked
         pad = pad_token_id if pad_token_id is not None else (eos_token_id if eos_token_id is not None else 0)
-        return torch.where(finished != 0, torch.full_like(picked, pad), picked)
+        picked = torch.where(finished != 0, torch.full_like(picked, pad), picked)
+        if stop_sequences is not None:
+            why = _eager_stop(picked, counters, sequences, finished, penalty_begin, min_length,
+                              _phrase_lists(stop_sequences, 'stop_sequences'), eos_token_id).to(picked.device)
+            ended = why >= 0
+            finished[ended] = 1
+            if ends is not None:
+                ends[ended] = (counters[ended] + 1).to(ends.dtype)
+            if reasons is not None:
+                reasons[ended] = why[ended].to(reasons.dtype)
+        return picked
 
     greedy = torch.argmax(controlled(x), dim=-1)
     if not do_sample:
@@ -388,14 +480,16 @@ class _Picker:
     """The pick of the decode loops through bp_pick_token (CUDA tensors) or _eager_pick: argmax when not do_sample, else a
     draw after temperature / top-k / top-p.  `counters` (batch,) int32 on the logits' device hold the 0-based sequence
     position of the token being picked: the Philox counter, and the column of `sequences` that receives the token.
-    With an EOS id it owns `finished` (batch,) int32 on the logits' device, allocated by the first pick: the flag of a row
-    is set by the pick that returns the EOS id, and every later pick of that row returns the pad.
+    With an EOS id or stop sequences it owns `finished` (batch,) int32 on the logits' device, allocated by the first pick: the
+    flag of a row is set by the pick that returns the EOS id or completes a stop sequence, and every later pick of that row
+    returns the pad.  With stop sequences it also owns `ends` and `reasons` (batch,) int32, -1 until the pick that ends the row
+    writes them (bp_pick_token_phrases).  The phrase lists are packed and copied to the device once, here.
     `prompt_lengths` (batch,) int32 on that device, for prompts of different lengths: a row's counted penalties begin, and
-    its min_new_tokens count, at its own prompt length -- per-row values of the pick (bp_pick_token_lim_rows), passed only
-    where an option reads them."""
+    its min_new_tokens count, and the text a stop sequence is looked for in begins, at its own prompt length -- per-row values
+    of the pick (bp_pick_token_lim_rows), passed only where an option reads them."""
 
     def __init__(self, options, rng_state, device, prompt_lengths=None):
-        self.options, self.finished = options, None
+        self.options, self.finished, self.ends, self.reasons = options, None, None, None
         if options.do_sample and rng_state is None:       # from torch's generator: torch.manual_seed reproduces a run
             rng_state = torch.randint(-2 ** 63, 2 ** 63 - 1, (2,), dtype=torch.int64, device=device)
         self.rng_state = rng_state.to(device) if rng_state is not None else None
@@ -416,18 +510,30 @@ class _Picker:
             self.keywords.update(no_repeat_ngram_size=o.no_repeat_ngram_size, frequency_penalty=o.frequency_penalty,
                                  presence_penalty=o.presence_penalty, suppress_tokens=suppress,
                                  penalty_begin=o.penalty_begin if prompt_lengths is None else prompt_lengths)
+        if o.phrased:
+            phrases = {name: _phrase_lists(getattr(o, name), name) for name in ('bad_words_ids', 'stop_sequences')
+                       if getattr(o, name) is not None}
+            if torch.device(device).type == 'cuda':
+                import bp_hip
+                phrases = {name: bp_hip.pack_phrases(rows, device, name) for name, rows in phrases.items()}
+            self.keywords.update(penalty_begin=o.penalty_begin if prompt_lengths is None else prompt_lengths, **phrases)
 
     def __call__(self, logits, counters, tokens=None, sequences=None):
         """tokens (batch,) int64; also stored into `tokens` (batch elements) and column counters[b] of `sequences`."""
-        if self.options.eos_token_id is not None and self.finished is None:
+        stops = self.options.stop_sequences is not None
+        if (self.options.eos_token_id is not None or stops) and self.finished is None:
             self.finished = torch.zeros((logits.shape[0],), dtype=torch.int32, device=logits.device)
+            if stops:
+                self.ends = torch.full((logits.shape[0],), -1, dtype=torch.int32, device=logits.device)
+                self.reasons = torch.full((logits.shape[0],), -1, dtype=torch.int32, device=logits.device)
+        outputs = {'ends': self.ends, 'reasons': self.reasons} if stops else {}
         if logits.is_cuda:
             import bp_hip
             return bp_hip.pick_token(logits, rng_state=self.rng_state, counters=counters, tokens=tokens, sequences=sequences,
-                                     finished=self.finished, **self.keywords).view(-1)
+                                     finished=self.finished, **outputs, **self.keywords).view(-1)
         picked = _eager_pick(logits, rng_state=self.rng_state, counters=counters, finished=self.finished, sequences=sequences,
-                             **self.keywords)
-        if self.finished is not None:
+                             **outputs, **self.keywords)
+        if self.finished is not None and not stops:       # with stop sequences _eager_pick has set the flags, as the kernel does
             self.finished[picked == self.options.eos_token_id] = 1
         if tokens is not None:
             tokens.view(-1).copy_(picked)
@@ -592,6 +698,21 @@ def _trim_rows_at_eos(sequences, prompt_lengths, new_tokens, eos_token_id, pad_t
     return sequences.contiguous(), lengths
 
 
+def _trim_at_ends(sequences, full, ends, reasons, pad_token_id):
+    """_trim_at_eos / _trim_rows_at_eos where the pick itself recorded the rows' ends (stop sequences; _Picker.ends / .reasons,
+    -1 for a row that did not end): end_b = ends[b] when 0 <= ends[b] <= full[b], else full[b], the row's full length ((batch,)
+    int64) -- the last pick of a uniform batch lands behind `sequences` and is dropped, so an end there is none.  Returns
+    (sequences cut to max_b end_b columns with the pad behind every row's end, end_b, the reasons with -1 for a full row)."""
+    if ends is None:            # no pick was made
+        ends = reasons = torch.full_like(full, -1)
+    ends, reasons = ends.long(), reasons.long()
+    ended = (ends >= 0) & (ends <= full)
+    lengths = torch.where(ended, ends, full)
+    cols = torch.arange(sequences.shape[1], device=sequences.device)[None, :]
+    sequences = torch.where(cols < lengths[:, None], sequences, torch.full_like(sequences, pad_token_id))
+    return sequences[:, :int(lengths.max())].contiguous(), lengths, torch.where(ended, reasons, torch.full_like(reasons, -1))
+
+
 def _check_prompt_lengths(prompt_lengths, input_ids):
     """prompt_lengths (a sequence or a tensor of `batch` integers in [1, seq_len]) as a (batch,) int32 tensor on the device of
     input_ids, and its minimum: ONE copy to the host for the checks, one to the device; no step reads a host value."""
@@ -709,7 +830,9 @@ def _decode_cached_picked(input_ids, model, max_length, picker, cg=False, stop_c
     further one, which would land inside a shorter row; `lengths` is always returned (_trim_rows_at_eos).
     With `report` = (output_logprobs, top_logprobs) every pick is followed by its record (_PickRecord) -- the captured graph is
     then model step, length increment, pick, report -- and the result carries the record's fields, trimmed as `sequences` is.
-    With `packed_lengths` (prompt_lengths on the host) the prefill is the packed one (_CachedSteps); nothing behind it differs."""
+    With `packed_lengths` (prompt_lengths on the host) the prefill is the packed one (_CachedSteps); nothing behind it differs.
+    With stop sequences the rows' ends are the pick's own (`ends`, `reasons` of _Picker; _trim_at_ends): `lengths` is always
+    returned, `stop_reasons` too, and `sequences` is cut to the longest row."""
     d = _CachedSteps(input_ids, model, max_length, prompt_lengths=prompt_lengths, pad=picker.options.pad,
                      packed_lengths=packed_lengths)
     record = _PickRecord(d, *report) if report is not None else None
@@ -730,11 +853,20 @@ def _decode_cached_picked(input_ids, model, max_length, picker, cg=False, stop_c
             if new_tokens > 0:
                 pick(logits)
                 d.run(lambda: pick(d.step_logits()), new_tokens - 1, cg, _StopPoll(picker.finished, stop_check_every))
+            if o.stop_sequences is not None:
+                sequences, lengths, why = _trim_at_ends(sequences, prompt_lengths.long() + new_tokens, picker.ends, picker.reasons, o.pad)
+                return DecoderOnlyOutput(sequences=sequences.to(input_ids.dtype), scores=(logits,), lengths=lengths,
+                                         stop_reasons=why, **recorded(sequences, lengths))
             sequences, lengths = _trim_rows_at_eos(sequences, prompt_lengths, new_tokens, o.eos_token_id, o.pad)
             return DecoderOnlyOutput(sequences=sequences.to(input_ids.dtype), scores=(logits,), lengths=lengths,
                                      **recorded(sequences, lengths))
         pick(logits)
         d.run(lambda: pick(d.step_logits()), max_length - d.prompt - 1, cg, _StopPoll(picker.finished, stop_check_every))
+        if o.stop_sequences is not None:
+            full = torch.full((sequences.shape[0],), d.width, dtype=torch.int64, device=sequences.device)
+            sequences, lengths, why = _trim_at_ends(sequences, full, picker.ends, picker.reasons, o.pad)
+            return DecoderOnlyOutput(sequences=sequences.to(input_ids.dtype), scores=(logits,), lengths=lengths,
+                                     stop_reasons=why, **recorded(sequences, lengths))
         if o.eos_token_id is not None:
             sequences, lengths = _trim_at_eos(sequences, d.prompt, o.eos_token_id, o.pad)
         return DecoderOnlyOutput(sequences=sequences.to(input_ids.dtype), scores=(logits,), lengths=lengths,
@@ -800,7 +932,8 @@ def _run_loop(input_ids, model, max_length, pick, do_sample, cg, kv_cache, rng_s
                                          prompt_lengths=prompt_lengths, report=report, **packed)
         if options.controlled:
             raise ValueError('generation: repetition_penalty, eos_token_id, pad_token_id, min_length, min_new_tokens, '
-                             'no_repeat_ngram_size, frequency_penalty, presence_penalty and suppress_tokens need kv_cache=True '
+                             'no_repeat_ngram_size, frequency_penalty, presence_penalty, suppress_tokens, bad_words_ids and '
+                             'stop_sequences need kv_cache=True '
                              '(the loops without a cache are the reference\'s, statement for statement)')
         pick = picker.loop_pick(input_ids)
     if kv_cache:

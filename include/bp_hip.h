@@ -66,7 +66,9 @@ extern "C" {
                               and four more: bp_gemm_bf16 / bp_gemm_f16, a dense layer by a pinned hipBLASLt solution, with
                               bp_gemm_library / bp_gemm_heuristic, BP_ERR_GEMM and the BP_GEMM_* statuses;
                               and one more: bp_scatter_packed_rows, the rows of a packed batch into (batch, positions, ...)
-                              buffers -- the prefill of the KV caches from packed prompts) */
+                              buffers -- the prefill of the KV caches from packed prompts;
+                              and one more: bp_pick_token_phrases, the row-limited pick with banned phrases and stop phrases
+                              of several tokens, matched against the row's history on the device) */
 
 /* element type of q/k/v/out/content tensors */
 #define BP_DTYPE_F16 0
@@ -86,7 +88,9 @@ extern "C" {
 #define BP_ERR_SAMPLING -10   /* bp_pick_token: top_p outside (0, 1], or do_sample without an rng_state; bp_pick_token_ctl:
                                  also a repetition_penalty not finite and > 0 or without sequences, an EOS id without flags;
                                  bp_pick_token_lim: also a non-finite frequency / presence penalty, n-gram blocking or a
-                                 penalty without sequences, n_suppress > 0 with a NULL or misaligned list */
+                                 penalty without sequences, n_suppress > 0 with a NULL or misaligned list;
+                                 bp_pick_token_phrases: also a phrase list with a NULL array or without sequences, stop
+                                 phrases without flags */
 #define BP_ERR_GEMM -11       /* bp_gemm_*: a call into hipBLASLt or the HIP runtime failed                          */
 
 /* bounds of bp_pick_token_lim (BP_ERR_SHAPE beyond them) */
@@ -94,6 +98,9 @@ extern "C" {
 #define BP_PICK_MAX_LIMITED_VOCAB (1 << 19)   /* vocab with any of its controls on: 19 id bits of a count entry, 64 KB a bitmap */
 #define BP_PICK_MAX_COUNTED_COLS 8191         /* seq_cols under a frequency / presence penalty: 13 count bits of an entry */
 #define BP_PICK_MAX_LDS_BYTES (160 * 1024)    /* static + dynamic LDS of one launch: the LDS of a CU */
+/* bounds of bp_pick_token_phrases */
+#define BP_PICK_MAX_PHRASE_LEN 64             /* ids of one phrase (= BP_PICK_MAX_NGRAM); longer ones are ignored on the device */
+#define BP_PICK_MAX_PHRASES 1024              /* phrases of one list: one per thread of the pick's workgroup */
 
 #define BP_ROW_EXTREMES_MAX_N 64              /* bp_row_extremes: elements kept per end of a row */
 
@@ -852,6 +859,53 @@ int bp_pick_token_lim_rows(const void *logits, int64_t *tokens, int64_t *sequenc
                            int no_repeat_ngram_size, float frequency_penalty, float presence_penalty, int penalty_begin,
                            const int32_t *suppress_ids, int n_suppress, const int32_t *penalty_begins,
                            const int32_t *min_lengths, int dtype, bp_stream_t stream);
+
+/*
+ * bp_pick_token_phrases -- bp_pick_token_lim_rows with two lists of phrases of token ids: banned phrases (the bad_words_ids of
+ * the common generation libraries: the LAST id of a phrase is banned while the row's text ends with the ids in front of it)
+ * and stop phrases (a row whose generated text ends with one is finished, as by its EOS id).  (Additive, ABI still 11.)
+ * Arguments as bp_pick_token_lim_rows's, and
+ *   ban_ids, ban_offsets, n_ban, ban_total      int32 arrays on the device: phrase j is ban_ids[ban_offsets[j] :
+ *                   ban_offsets[j + 1]], ban_offsets has n_ban + 1 entries, ban_ids has ban_total
+ *   stop_ids, stop_offsets, n_stop, stop_total  the stop phrases, in the same form
+ *   ends, reasons   optional int32 (batch) each, written for the rows this call finishes
+ * The host never reads the arrays (one captured launch serves every step), so the device checks them: a phrase whose offsets
+ * leave [0, total] or whose length lies outside 1..BP_PICK_MAX_PHRASE_LEN is ignored (decreasing offsets among them).
+ * Per row b, with c, h, Lh as bp_pick_token_lim defines them, g_b = penalty_begins[b], else penalty_begin, clamped at 0, and
+ * m_b = min_lengths[b], else min_length, clamped at 0:
+ *   ban     a ban phrase w[0..L) matches when Lh >= L - 1 and h[Lh - L + 1 + t] == w[t] for all 0 <= t <= L - 2 (prompt
+ *           included, as for the n-gram set; the int64 history against the sign-extended int32 id, so ids outside the
+ *           vocabulary match by value).  A match adds w[L - 1] to the banned ids of step 3 of bp_pick_token_lim when it lies
+ *           in [0, vocab); L = 1 always bans its id.  Everything behind the ban is the limited form's: the order pen ->
+ *           counts -> ban, the degenerate row of -inf taking index 0, stats
+ *   stop    after the token t of a row that was not finished on entry has been written, only when sequences != NULL and
+ *           0 <= c < seq_cols (h is unclamped and the token has a column) and c >= m_b (the EOS id is no longer masked):
+ *           with h' = h ++ [t], stop phrase j of length L matches when c + 1 - L >= g_b (the whole match is generated text: a
+ *           prompt that ends with the phrase, or a match across the prompt's end, stops nothing) and h'[c + 1 - L + i] == w[i]
+ *           for all 0 <= i < L.  Any match sets finished[b] = 1; the token stays, as the EOS token does, and later picks of
+ *           the row write the pad
+ *   ends, reasons   whenever this call sets finished[b], for the EOS id or a stop phrase: ends[b] = c + 1 and reasons[b] = 0
+ *           for the EOS id, else 1 + j for the lowest matching j (the EOS id wins).  Neither is touched for a row that does
+ *           not finish in this call or was finished on entry
+ * With n_ban == n_stop == 0 and ends == reasons == NULL tokens, stats, the written column and the flags are
+ * bp_pick_token_lim_rows's, bit for bit.  The stop phrases are matched by the whole workgroup, one phrase per thread, each
+ * comparing backwards from the new token; the ban list is scanned the same way before the first pass over the row.
+ * Errors, before any launch: everything bp_pick_token_lim_rows rejects, with its codes; BP_ERR_SAMPLING (a list with n > 0
+ * whose ids or offsets are NULL, or with sequences == NULL; n_stop > 0 with finished == NULL); BP_ERR_SHAPE (n or total
+ * negative; n > BP_PICK_MAX_PHRASES; a misaligned ids, offsets, ends or reasons; vocab > BP_PICK_MAX_LIMITED_VOCAB with
+ * n_ban > 0; the LDS bound, where n_ban > 0 counts a ban bitmap).
+ */
+int bp_pick_token_phrases(const void *logits, int64_t *tokens, int64_t *sequences, float *stats, const uint64_t *rng_state,
+                          const int32_t *counters, int32_t *finished,
+                          int batch, int vocab, int64_t row_stride, int64_t tokens_stride, int64_t seq_stride, int seq_cols,
+                          int do_sample, float temperature, int top_k, float top_p,
+                          float repetition_penalty, int eos_token_id, int pad_token_id, int min_length,
+                          int no_repeat_ngram_size, float frequency_penalty, float presence_penalty, int penalty_begin,
+                          const int32_t *suppress_ids, int n_suppress, const int32_t *penalty_begins,
+                          const int32_t *min_lengths,
+                          const int32_t *ban_ids, const int32_t *ban_offsets, int n_ban, int ban_total,
+                          const int32_t *stop_ids, const int32_t *stop_offsets, int n_stop, int stop_total,
+                          int32_t *ends, int32_t *reasons, int dtype, bp_stream_t stream);
 
 /*
  * bp_beam_pick -- one decode step of beam search on the device for `groups` prompts x `beam_width` (W, 1..8) hypotheses,

@@ -20,7 +20,8 @@ that alternates with the others: the device pick with some generation options re
 `--variant pen:repetition_penalty=1.2 --variant n4:eos_token_id=50263,stop_check_every=4`, or with the limits of
 bp_pick_token_lim `--variant all:no_repeat_ngram_size=3,frequency_penalty=0.5,presence_penalty=0.5,suppress_tokens=11+12+13`
 (a list is written a+b+c), or with the record of the picks (bp_pick_report, one more launch per token; kv legs only)
-`--variant rec:output_logprobs=1 --variant rec5:output_logprobs=1,top_logprobs=5`.
+`--variant rec:output_logprobs=1 --variant rec5:output_logprobs=1,top_logprobs=5`, or with the phrases of bp_pick_token_phrases
+`--variant phr:stop_sequences=1+2+3/4+5+6,bad_words_ids=7+8+9` (phrases separated by /, the ids of one by +).
 
 --prompt-lengths LO:HI[:SEED] (kv legs only) adds two further picks that alternate with the others: `ragged`, the device pick
 with prompt_lengths drawn once on the host, uniformly from LO..HI (seed SEED, default 0) with the maximum forced to --prompt,
@@ -112,9 +113,12 @@ def main():
             res.update(controls)
         for spec in a.variant:
             name, _, pairs = spec.partition(':')
-            # suppress_tokens is a list, written a+b+c (the comma separates the options)
-            changed = {k: [int(t) for t in v.split('+')] if k == 'suppress_tokens' else json.loads(v)
-                       for k, v in (pair.split('=') for pair in pairs.split(',') if pair)}
+            # suppress_tokens is a list, written a+b+c (the comma separates the options); a list of phrases is a+b+c/d+e+f
+            def value(k, v):
+                if k in ('bad_words_ids', 'stop_sequences'):
+                    return [[int(t) for t in phrase.split('+')] for phrase in v.split('/')]
+                return [int(t) for t in v.split('+')] if k == 'suppress_tokens' else json.loads(v)
+            changed = {k: value(k, v) for k, v in (pair.split('=') for pair in pairs.split(',') if pair)}
             options[name] = dict(options['device'], **changed)
             res['variant_' + name] = changed
             picks = picks + [name]
