@@ -106,6 +106,7 @@ SIGNATURES = {
     'bp_beam_pick': (_i32, [_ptr] * 8 + [_i64] + [_i32] * 3 + [_i64] * 3 + [_i32] * 4 + [_ptr]),
     'bp_beam_copy_rows': (_i32, [_ptr] * 3 + [_i32] + [_ptr] * 2 + [_i32] * 3 + [_ptr]),
     'bp_scatter_packed_rows': (_i32, [_ptr] * 6 + [_i32, _ptr, _i32, _i64, _i32, _i32, _ptr]),
+    'bp_segment_sum_rows': (_i32, [_ptr] * 4 + [_i64, _i64, _i32, _i64, _i64, _i32, _i32, _ptr]),
     'bp_row_extremes': (_i32, [_ptr] * 5 + [_i32] * 2 + [_i64] + [_i32] * 2 + [_ptr]),
     'bp_sense_attribute_ws_floats': (_i64, [_i32] * 2),
     'bp_sense_attribute': (_i32, [_ptr] * 9 + [_i64] + [_i32] * 7 + [_i64] + [_i64] * 14 + [_f32, _i32, _ptr]),
@@ -837,11 +838,16 @@ def softmax_bwd_causal_(alpha, dalpha, softmax_scale):
 SLAB = 128   # queries per slab of the dq / dk backward (fixed by the kernels)
 
 
-def sense_mix_dc(qk, dout, lse, softmax_scale, like):
+def sense_mix_dc(qk, dout, lse, softmax_scale, like, out=None):
     """dcontent (B,S,k,d_out) of sense_mix: bp_sense_mix_dc (alpha recomputed from the saved lse, never stored).
-    `like`: the forward's content tensor (shape / dtype / device of the result)."""
+    `like`: the forward's content tensor (last dimension / dtype / device of the result); `out`: a contiguous
+    (B,S,k,d_out) buffer to write instead of a fresh one."""
     b, s, k, dk = _check_qk(qk)
-    dcontent = torch.empty((b, s, k, like.shape[-1]), dtype=like.dtype, device=like.device)
+    if out is None:
+        out = torch.empty((b, s, k, like.shape[-1]), dtype=like.dtype, device=like.device)
+    elif out.shape != (b, s, k, like.shape[-1]) or out.dtype != like.dtype or not out.is_contiguous() or not out.is_cuda:
+        raise RuntimeError('bp_hip.sense_mix_dc: out must be a contiguous (B, S, k, d_out) GPU tensor of the content\'s dtype')
+    dcontent = out
     queue_ws = _queue_ws(qk.device)
     _call('bp_sense_mix_dc', qk.device,
           qk.data_ptr(), dout.data_ptr(), lse.data_ptr(), dcontent.data_ptr(), b, s, k, dk, like.shape[-1],
@@ -851,15 +857,20 @@ def sense_mix_dc(qk, dout, lse, softmax_scale, like):
     return dcontent
 
 
-def sense_dqk(qk, content, dout, lse, softmax_scale):
+def sense_dqk(qk, content, dout, lse, softmax_scale, out=None):
     """dqk (like qk) of sense_mix.  The 768-deep product dP_l[t,s] = dout[t].C[s,l] is a plain GEMM and goes to the
     BLAS library, slab by slab (128 queries), TRANSPOSED into a (B, S*k, 128) buffer that is reused: the content's
     own storage (B, S*k, d) is its left operand as it stands, so nothing is copied or permuted.  bp_sense_dq_dk then
-    turns each slab into dq rows and dk contributions (softmax backward + the two thin products) on the fly."""
+    turns each slab into dq rows and dk contributions (softmax backward + the two thin products) on the fly.
+    `out`: a contiguous tensor like qk to write instead of a fresh one."""
     b, s, k, dk = _check_qk(qk)
     d = content.shape[-1]
     c_flat = content.reshape(b, s * k, d)                      # a view for the (B,S,k,d) storage layout
-    dqk = torch.empty_like(qk)
+    if out is None:
+        out = torch.empty_like(qk)
+    elif out.shape != qk.shape or out.dtype != qk.dtype or not out.is_contiguous() or not out.is_cuda:
+        raise RuntimeError('bp_hip.sense_dqk: out must be a contiguous GPU tensor of qk\'s shape and dtype')
+    dqk = out
     dk_acc = torch.zeros((b, s, k, dk), dtype=torch.float32, device=qk.device)
     dsum = torch.empty((b, k, round_up(s, 16)), dtype=torch.float32, device=qk.device)
     buf = torch.empty(b * s * k * SLAB, dtype=qk.dtype, device=qk.device)
@@ -966,6 +977,143 @@ def sense_mix_autograd(qk, content, softmax_scale=None, key_weight=None):
     if torch.is_grad_enabled() and (qk.requires_grad or content.requires_grad):
         return SenseMixFn.apply(qk, content, softmax_scale, key_weight)
     return sense_mix(qk, content, softmax_scale, key_weight=key_weight)
+
+
+# ---- the sense mix over a table of rows, with a backward (training with the content network once per distinct token) -------
+
+SEGMENT_LONG_ROWS = 32      # segments of at least this many rows take the kernel's second route (csrc/bp_kernels.h kSegLongRows)
+SEGMENT_ROW_LANES = 16      # ... where 16 lanes take rows r, r + 16, ... each (csrc/segment_sum_rows.hip kSegRowLanes)
+SEGMENT_UNROLL = 8          # rows a thread loads ahead on either route (kSegUnroll)
+
+
+def segment_sum_rows(rows, order, seg_begin, acc, accumulate=False):
+    """acc[u] (= or +=, `accumulate`) the fp32 sum of rows[order[i]] over i in [seg_begin[u], seg_begin[u + 1]): C ABI
+    bp_segment_sum_rows, deterministic (no atomics; the bits depend on the inputs only).
+    rows (n_rows, cols) fp16 / bf16, unit last stride, cols and the row stride multiples of 8; order (n_rows,) int32: the row
+    numbers grouped by segment, ascending inside a segment; seg_begin (n_segments + 1,) int32, non-decreasing; acc
+    (n_segments, cols) fp32, unit last stride.  With accumulate=False an empty segment's row is zeroed, with True it is
+    left as it is.  Returns acc."""
+    _require_cuda(rows, order, seg_begin, acc)
+    if rows.dim() != 2 or rows.stride(1) != 1 or rows.shape[0] < 1 or rows.shape[1] % 8 or rows.stride(0) % 8 \
+            or rows.data_ptr() % 16:
+        raise RuntimeError('bp_hip.segment_sum_rows: rows must be (n_rows >= 1, cols), last dim contiguous, 16-byte aligned, '
+                           'cols and the row stride multiples of 8')
+    n_rows, cols = rows.shape
+    if order.shape != (n_rows,) or order.dtype != torch.int32 or not order.is_contiguous():
+        raise RuntimeError('bp_hip.segment_sum_rows: order must be a contiguous (n_rows,) int32 tensor')
+    if seg_begin.dim() != 1 or seg_begin.shape[0] < 1 or seg_begin.dtype != torch.int32 or not seg_begin.is_contiguous():
+        raise RuntimeError('bp_hip.segment_sum_rows: seg_begin must be a contiguous (n_segments + 1,) int32 tensor')
+    n_segments = seg_begin.shape[0] - 1
+    if acc.shape != (n_segments, cols) or acc.dtype != torch.float32 or acc.stride(1) != 1 or acc.stride(0) % 4 \
+            or acc.data_ptr() % 16 or acc.stride(0) < cols:
+        raise RuntimeError('bp_hip.segment_sum_rows: acc must be (n_segments, cols) fp32, last dim contiguous, 16-byte '
+                           'aligned, rows that do not overlap, a row stride that is a multiple of 4')
+    if len({rows.device, order.device, seg_begin.device, acc.device}) != 1:
+        raise RuntimeError('bp_hip.segment_sum_rows: all tensors must live on one device')
+    if n_segments:
+        _call('bp_segment_sum_rows', rows.device, rows.data_ptr(), order.data_ptr(), seg_begin.data_ptr(), acc.data_ptr(),
+              n_rows, n_segments, cols, rows.stride(0), acc.stride(0), int(bool(accumulate)), _dtype_code(rows))
+    return acc
+
+
+def row_segments(row_index, n_segments):
+    """(order, seg_begin) of bp_segment_sum_rows for `row_index` (any shape, integer, values in [0, n_segments)): the
+    positions grouped by the row they read, ascending inside a group (one STABLE sort), and where every row's group begins
+    in that list.  All on the device, no host value read."""
+    flat = row_index.reshape(-1)
+    ordered, order = torch.sort(flat, stable=True)
+    bounds = torch.arange(n_segments + 1, dtype=ordered.dtype, device=flat.device)
+    return order.to(torch.int32), torch.searchsorted(ordered, bounds, out_int32=True)
+
+
+def _gather_train_limits(qk, table, seqlen):
+    b, s, _, k, dk = qk.shape
+    return _gather_limits(qk, table, seqlen) + (
+        (dk % 8 != 0 or dk > 128, f'sense width {dk} not a multiple of 8 or > 128 (the fused backward kernels)'),
+        (not qk.is_contiguous() or not table.is_contiguous(), 'qk or table not contiguous'),
+        (s > 65536, f'sequence length {s} > 65536'),
+    )
+
+
+def sense_mix_gather_train_shape_limits(d_k, seqlen):
+    """What the sense width (before it is widened to a multiple of 8) and the sequence length alone rule out, as text: a
+    caller can tell before it builds the table."""
+    return '; '.join(reason for exceeded, reason in (
+        (round_up(d_k, 8) > 128, f'sense width {d_k} > 128 (the fused backward kernels)'),
+        (seqlen > 4096, f'sequence length {seqlen} > 4096 (bp_sense_mix_gather keeps a job\'s row indices in LDS)'),
+    ) if exceeded)
+
+
+def sense_mix_gather_train_supported(qk, table, seqlen):
+    """Shapes SenseMixGatherFn takes: those of bp_sense_mix_gather that the fused backward kernels (bp_sense_mix_dc,
+    bp_sense_dq_dk: _fused_mix_backward_ok) take as well."""
+    return not any(exceeded for exceeded, _ in _gather_train_limits(qk, table, seqlen))
+
+
+def sense_mix_gather_train_limits(qk, table, seqlen):
+    """Which of those limits a call exceeds, as text."""
+    return '; '.join(reason for exceeded, reason in _gather_train_limits(qk, table, seqlen) if exceeded)
+
+
+class SenseMixGatherFn(torch.autograd.Function):
+    """SenseMixFn with the content rows read from a table: content[b, s] = table[row_index[b, s]] is never materialised
+    for the whole batch, neither in the forward (bp_sense_mix_gather) nor as a gradient.  The backward runs over chunks of
+    `chunk_samples` samples and reuses two chunk-sized buffers:
+        dcontent_c = bp_sense_mix_dc(qk[c], dout[c], lse[c])                  (c, S, k, d)
+        dtable    += bp_segment_sum_rows(dcontent_c, positions grouped by row)  fp32 (U, k d), deterministic, no atomics
+        content_c  = table[row_index[c]] (a torch gather)  ->  dqk[c] = sense_dqk(qk[c], content_c, dout[c], lse[c])
+    dtable is rounded to the table's dtype once, at the end.  The grouping is one stable sort and one searchsorted per
+    chunk, on the device.  The sum over the chunks is in ascending chunk order, so the result is the same bits in every
+    run; a different `chunk_samples` associates the sum differently."""
+
+    @staticmethod
+    def forward(ctx, qk, table, row_index, softmax_scale, chunk_samples):
+        scale = softmax_scale or qk.shape[-1] ** -0.5
+        row_index = row_index.to(torch.int32)
+        lse = sense_lse(qk, scale)
+        out = sense_mix_gather(qk, table, row_index, scale, lse=lse)
+        ctx.save_for_backward(qk, table, row_index, lse)
+        ctx.scale = scale
+        ctx.chunk_samples = max(1, int(chunk_samples))
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qk, table, row_index, lse = ctx.saved_tensors
+        dout = dout.contiguous()
+        (b, s, _, k, dk), (u, _, d) = qk.shape, table.shape
+        step = min(ctx.chunk_samples, b)
+        want_qk, want_table = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dqk = torch.empty_like(qk) if want_qk else None
+        dtable = torch.empty((u, k * d), dtype=torch.float32, device=table.device) if want_table else None
+        dc_buf = torch.empty((step, s, k, d), dtype=table.dtype, device=table.device) if want_table else None
+        c_buf = torch.empty((step * s, k * d), dtype=table.dtype, device=table.device) if want_qk else None
+        flat_table = table.view(u, k * d)
+        for n, b0 in enumerate(range(0, b, step)):
+            sl = slice(b0, min(b0 + step, b))
+            c = sl.stop - sl.start
+            if want_table:
+                dcontent = sense_mix_dc(qk[sl], dout[sl], lse[sl], ctx.scale, table, out=dc_buf[:c])
+                order, seg_begin = row_segments(row_index[sl], u)
+                segment_sum_rows(dcontent.view(c * s, k * d), order, seg_begin, dtable, accumulate=n > 0)
+            if want_qk:
+                content = torch.index_select(flat_table, 0, row_index[sl].reshape(-1), out=c_buf[:c * s])
+                sense_dqk(qk[sl], content.view(c, s, k, d), dout[sl], lse[sl], ctx.scale, out=dqk[sl])
+        return dqk, (dtable.to(table.dtype).view(u, k, d) if want_table else None), None, None, None
+
+
+SENSE_TABLE_TRAIN_CHUNK_SAMPLES = 8     # samples per chunk of SenseMixGatherFn's backward: a guess, NOT measured
+
+
+def sense_mix_gather_autograd(qk, table, row_index, softmax_scale=None, chunk_samples=SENSE_TABLE_TRAIN_CHUNK_SAMPLES):
+    """sense_mix_gather that records a backward when gradients are enabled (training), the plain kernel otherwise.  Shapes
+    its backward does not take (sense_mix_gather_train_supported) raise: callers choose the per-position order for them."""
+    if torch.is_grad_enabled() and (qk.requires_grad or table.requires_grad):
+        _require_cuda(qk, table, row_index)
+        if not sense_mix_gather_train_supported(qk, table, qk.shape[1]):
+            raise RuntimeError('bp_hip.sense_mix_gather_autograd: ' + sense_mix_gather_train_limits(qk, table, qk.shape[1]))
+        return SenseMixGatherFn.apply(qk, table, row_index, softmax_scale, chunk_samples)
+    return sense_mix_gather(qk, table, row_index.to(torch.int32), softmax_scale)
 
 
 class SenseAlphaFn(torch.autograd.Function):

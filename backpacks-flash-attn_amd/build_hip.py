@@ -18,7 +18,7 @@ OUT_DIR = os.path.join(CSRC, 'build')
 LIB = os.path.join(HERE, 'bp_hip', 'libbackpack_hip.so')
 SOURCES = ['flash_fwd.hip', 'flash_fwd_dma.hip', 'flash_bwd.hip', 'sense_mix.hip', 'sense_mix_dma.hip', 'sense_mix_varlen.hip', 'sense_mix_bwd.hip', 'sense_wide.hip', 'sense_wide_dma.hip', 'attn_probs.hip',
            'add_layer_norm.hip', 'xentropy.hip', 'softmax_bwd.hip', 'bias_gelu.hip', 'flash_decode.hip', 'sense_decode.hip', 'sense_decode_weighted.hip', 'sense_rows_dot.hip',
-           'pick_token.hip', 'pick_token_ctl.hip', 'pick_token_lim.hip', 'pick_token_rows.hip', 'pick_token_phrases.hip', 'beam_pick.hip', 'beam_copy.hip', 'scatter_rows.hip', 'row_extremes.hip', 'sense_attribute.hip', 'sense_similarity.hip',
+           'pick_token.hip', 'pick_token_ctl.hip', 'pick_token_lim.hip', 'pick_token_rows.hip', 'pick_token_phrases.hip', 'beam_pick.hip', 'beam_copy.hip', 'scatter_rows.hip', 'segment_sum_rows.hip', 'row_extremes.hip', 'sense_attribute.hip', 'sense_similarity.hip',
            'score_rows.hip', 'pick_report.hip', 'bp_gemm.hip', 'bp_api.hip']
 HEADERS = ['bp_common.h', 'lds_image.h', 'bp_dma.h', 'decode_core.h', 'bp_kernels.h', 'bp_philox.h', 'mix_ring.h', 'sense_mix_dma_kernel.h', 'pick_core.h', 'staged_tile.h', 'vocab_row.h', os.path.join('..', '..', 'include', 'bp_hip.h')]
 # -amdgpu-mfma-vgpr-form: keep MFMA accumulators in VGPRs (gfx950 has one unified file); without it

@@ -1304,6 +1304,26 @@ int bp_scatter_packed_rows(const void *const *src, const int64_t *src_row_stride
     return launch_status(bp::launch_scatter_packed_rows(p, static_cast<hipStream_t>(stream)));
 }
 
+// ---- segmented row sums (bp_segment_sum_rows) ----
+
+int bp_segment_sum_rows(const void *rows, const int32_t *order, const int32_t *seg_begin, float *acc, int64_t n_rows,
+                        int64_t n_segments, int cols, int64_t rows_stride, int64_t acc_stride, int accumulate, int dtype,
+                        bp_stream_t stream) {
+    if (dtype != BP_DTYPE_F16 && dtype != BP_DTYPE_BF16) return BP_ERR_DTYPE;
+    if (n_rows < 0 || n_rows > 0x7fffffffLL || n_segments < 0 || n_segments > BP_SEGMENT_SUM_MAX_SEGMENTS) return BP_ERR_SHAPE;
+    if (cols < 8 || cols > BP_SEGMENT_SUM_MAX_COLS || !mult8(cols)) return BP_ERR_SHAPE;
+    if (rows_stride < cols || !mult8(rows_stride) || acc_stride < cols || acc_stride % 4 != 0) return BP_ERR_SHAPE;
+    if (accumulate != 0 && accumulate != 1) return BP_ERR_SHAPE;
+    if (rows == nullptr || order == nullptr || seg_begin == nullptr || acc == nullptr) return BP_ERR_SHAPE;
+    if (!aligned16({rows, acc}) || reinterpret_cast<uintptr_t>(order) % 4 || reinterpret_cast<uintptr_t>(seg_begin) % 4)
+        return BP_ERR_SHAPE;
+    bp::SegmentSumParams p{};
+    p.rows = static_cast<const uint16_t *>(rows); p.order = order; p.seg_begin = seg_begin; p.acc = acc;
+    p.rows_stride = rows_stride; p.acc_stride = acc_stride;
+    p.n_rows = (int)n_rows; p.n_segments = (int)n_segments; p.cols = cols; p.accumulate = accumulate;
+    return launch_status(bp::launch_segment_sum_rows(p, dtype, static_cast<hipStream_t>(stream)));
+}
+
 // ---- row extremes (bp_row_extremes) ----
 
 int bp_row_extremes(const void *logits, float *top_val, int32_t *top_idx, float *bot_val, int32_t *bot_idx,

@@ -429,6 +429,19 @@ struct ScatterRowsParams {
 };
 hipError_t launch_scatter_packed_rows(const ScatterRowsParams &p, hipStream_t stream);
 
+// bp_segment_sum_rows (segment_sum_rows.hip): acc[u] (= or +=) the fp32 sum of rows order[seg_begin[u]] .. order[seg_begin[u + 1] - 1]
+constexpr int kSegLongRows = 32;            // segments of at least this many rows are cut into column slabs, 16 row lanes each
+constexpr int kSegSlabCols = 128;           // columns of a slab
+struct SegmentSumParams {
+    const uint16_t *rows;                   // (n_rows, cols) 16-bit, element stride rows_stride
+    const int32_t *order, *seg_begin;       // (n_rows), (n_segments + 1); on the device, not trusted
+    float *acc;                             // (n_segments, cols), element stride acc_stride
+    int64_t rows_stride, acc_stride;
+    int n_rows, n_segments, cols, accumulate;
+    int n_slabs;                            // set by the launcher
+};
+hipError_t launch_segment_sum_rows(SegmentSumParams p, int dtype, hipStream_t stream);
+
 // bp_row_extremes (row_extremes.hip): the n largest / n smallest elements of every row, values and columns, in order
 constexpr int kRowExtremesMaxN = BP_ROW_EXTREMES_MAX_N;
 struct RowExtremesParams {

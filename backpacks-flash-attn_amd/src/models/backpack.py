@@ -328,6 +328,15 @@ class BackpackModel(GPTPreTrainedModel):
         self.dedup_min_positions = int(getattr(config, 'dedup_min_positions', config.vocab_size))
         self._gather_fallback_said = False
         self._packed_fallback_said = False
+        # training with the content network once per distinct token: 'off' (default) | 'batch', see `_train_table_mode`
+        self.sense_table_train = getattr(config, 'sense_table_train', 'off')
+        self._train_table_mode()
+        # samples per chunk of the table order's backward (bp_hip.SenseMixGatherFn): two (chunk, S, k*d) buffers live at a
+        # time.  The default of 8 is a guess that nobody has measured.
+        self.sense_table_train_chunk_samples = int(getattr(config, 'sense_table_train_chunk_samples',
+                                                           bp_hip.SENSE_TABLE_TRAIN_CHUNK_SAMPLES))
+        self._train_table_fallback_said = False
+        self._train_table_dropout_said = False
         self.gpt2_model = GPTModel(config, **factory_kwargs)
         self.content_model = BackpackContentModule(config, self.num_content_vectors,
                                                    self.gpt2_model.embeddings, **factory_kwargs)
@@ -354,7 +363,65 @@ class BackpackModel(GPTPreTrainedModel):
     #                       `dedup_min_positions` positions up (default: one per vocabulary entry; below, per position is as fast).
     #   'off'               every position through the content network (the reference's order; also `dedup_content=False`).
     # Mathematically identical to the per-position order; bits can differ where the BLAS GEMMs round a row differently
-    # when the row count changes.  Training always runs per position (dropout inside the content network, autograd).
+    # when the row count changes.
+    #
+    # ---- training: per position by default, once per distinct token as an option ------------------------------------------
+    # `_table_mode()` is 'off' while `self.training`: by default a training step runs every position through the content
+    # network, as the reference does.  `config.sense_table_train` / `self.sense_table_train` = 'batch' (default 'off') lets
+    # a step in train() mode with gradients enabled run the content network over the sorted distinct ids of the batch
+    # instead, WITH autograd (`_mix_train_from_table`): on the HIP path the forward mix reads the rows through the index
+    # (bp_sense_mix_gather) and the backward sums dcontent into the table's rows on the device, in fp32 and without atomics
+    # (bp_hip.SenseMixGatherFn, bp_segment_sum_rows) -- no (B,S,k*d) tensor exists in either direction; off the HIP path
+    # the rows are gathered by torch into the eager combination.  With zero dropout this is the same mathematics as 'off'
+    # (sums in another order).  With `embd_pdrop` or `resid_pdrop` > 0 it is NOT the reference's regulariser: the content
+    # network draws one dropout mask per distinct token, so all occurrences of a token in a step share it, where the
+    # per-position order draws one per occurrence (one warning per model).  Shapes the fused route does not take -- senses
+    # wider than 128, S > 4096, more than 65 536 distinct ids -- train per position, with one warning that names the limit;
+    # nothing ever goes through a 16-bit torch index-add on the HIP path.  Packed batches, the KV-cached path, the
+    # intervened wrappers and GraphedForward are inference-only and unaffected.
+
+    def _train_table_mode(self):
+        mode = self.sense_table_train
+        if mode not in ('off', 'batch'):
+            raise ValueError("sense_table_train must be 'off' or 'batch', got %r" % (mode,))
+        return mode
+
+    def _train_table_applies(self, input_ids):
+        return self._train_table_mode() == 'batch' and self.training and torch.is_grad_enabled() and input_ids.dim() == 2
+
+    def _say_shared_dropout_once(self):
+        if not self._train_table_dropout_said and (self.config.embd_pdrop > 0 or self.config.resid_pdrop > 0):
+            self._train_table_dropout_said = True
+            warnings.warn("Backpack: sense_table_train='batch' with dropout in the content network: all occurrences of a "
+                          'token in a step share its dropout masks (the per-position order draws one per occurrence)')
+
+    def _mix_train_from_table(self, hidden, input_ids):
+        """The mix of a training step in the table order, or None where this model / shape trains per position."""
+        if not self.use_hip:
+            self._say_shared_dropout_once()
+            content = self._content_of_unique_tokens(input_ids)          # torch gathers the rows; autograd sums them back
+            return _combine_senses(self.contextualization_attn(hidden), content)
+        if not self.fused_senses:
+            limit = 'senses wider than %d (no fused sense kernels)' % bp_hip.SENSE_MAX_DK
+        elif not input_ids.is_cuda:
+            limit = 'ids not on the GPU'
+        else:
+            # what the shape alone tells, before anything runs
+            limit = bp_hip.sense_mix_gather_train_shape_limits(self.config.n_embd // self.num_content_vectors,
+                                                               input_ids.shape[1])
+            if not limit:
+                self._say_shared_dropout_once()
+                qk = self.contextualization_attn.project(hidden)
+                rows, inverse = self._table_of_unique_tokens(input_ids)
+                limit = bp_hip.sense_mix_gather_train_limits(qk, rows, input_ids.shape[1])
+                if not limit:
+                    return bp_hip.sense_mix_gather_autograd(qk, rows, inverse, self.contextualization_attn.scale(),
+                                                            chunk_samples=self.sense_table_train_chunk_samples)
+        if not self._train_table_fallback_said:
+            self._train_table_fallback_said = True
+            warnings.warn("Backpack: sense_table_train='batch' does not take this shape, the step runs the content network "
+                          'per position: ' + limit)
+        return None
 
     def _table_mode(self):
         """`sense_table_mode` as it applies now: 'off' while no token table may be used; callers add autograd, device, capture."""
@@ -710,6 +777,10 @@ class BackpackModel(GPTPreTrainedModel):
         if inference_params is not None:
             return self._forward_cached(input_ids, position_ids, inference_params)
         contextl_hidden_states = self.gpt2_model(input_ids, position_ids=position_ids, inference_params=None)
+        if self._train_table_applies(input_ids):
+            mixed = self._mix_train_from_table(contextl_hidden_states, input_ids)
+            if mixed is not None:
+                return mixed
         if self._token_table_allowed(input_ids):
             if self.sense_table_mode == 'cached':
                 rows = self.sense_table(verify=self._verify_applies(input_ids))

@@ -68,7 +68,9 @@ extern "C" {
                               and one more: bp_scatter_packed_rows, the rows of a packed batch into (batch, positions, ...)
                               buffers -- the prefill of the KV caches from packed prompts;
                               and one more: bp_pick_token_phrases, the row-limited pick with banned phrases and stop phrases
-                              of several tokens, matched against the row's history on the device) */
+                              of several tokens, matched against the row's history on the device;
+                              and one more: bp_segment_sum_rows, fp32 sums of 16-bit rows over the segments of a sorted index --
+                              the gradient of the rows of a sense table that several positions read) */
 
 /* element type of q/k/v/out/content tensors */
 #define BP_DTYPE_F16 0
@@ -992,6 +994,36 @@ int bp_scatter_packed_rows(const void *const *src, const int64_t *src_row_stride
                            const int64_t *dst_batch_strides, const int64_t *dst_pos_strides, const int64_t *row_bytes,
                            int nsets, const int32_t *cu_seqlens, int batch, int64_t total_rows, int max_seqlen,
                            int max_positions, bp_stream_t stream);
+
+/*
+ * bp_segment_sum_rows -- deterministic fp32 sums of 16-bit rows over the segments of a sorted index:
+ *     acc[u, c]  (= or +=)  sum over i in [seg_begin[u], seg_begin[u + 1])  of  rows[order[i], c]
+ * The gradient of a table row that several positions read (an embedding-style backward): torch's index_add_ does this sum
+ * with atomics, in the tensor's 16-bit dtype.  Here the sum is kept in fp32, no atomic is used, and every (segment, column)
+ * has one owner: the bits of the result depend on the inputs only -- on a segment's rows and their order, not on the grid,
+ * the schedule, the run, or where the segment stands among the others.  (Additive, ABI still 11.)
+ *   rows         (n_rows, cols) fp16 / bf16, element stride rows_stride >= cols, last stride 1, 16-byte aligned base,
+ *                cols and rows_stride multiples of 8, 8 <= cols <= BP_SEGMENT_SUM_MAX_COLS.  Only read.
+ *   order        int32 (n_rows): the row numbers grouped by segment, ascending inside a segment (what a stable sort of the
+ *                rows' segment numbers returns).  NOT validated: a value is clamped, unsigned, to n_rows - 1.
+ *   seg_begin    int32 (n_segments + 1), non-decreasing.  NOT validated either: a value is clamped to [0, n_rows], a
+ *                decreasing pair is an empty segment -- nothing is read outside rows / order.
+ *   acc          fp32 (n_segments, cols), element stride acc_stride >= cols, a multiple of 4, 16-byte aligned base.  No
+ *                element outside rows [0, n_segments), columns [0, cols) is written.
+ *   accumulate   0: acc is overwritten, an empty segment writes zeros; 1: the sum is added to acc (one fp32 add per element),
+ *                an empty segment leaves its row untouched
+ *   n_rows >= 0, 0 <= n_segments <= BP_SEGMENT_SUM_MAX_SEGMENTS; n_segments == 0 is a successful no-op
+ * A segment of fewer than 32 rows is summed row after row; a longer one by 16 lanes that take rows r, r + 16, ... each, whose
+ * partial sums are added in ascending r.  One launch, no workspace, no host value read from the device.
+ * Errors, before any launch: BP_ERR_DTYPE; BP_ERR_SHAPE (a NULL or misaligned pointer, cols outside its range or not a
+ * multiple of 8, a stride below cols or not a multiple of 8 / 4, n_rows outside [0, 2^31 - 1], n_segments outside its range,
+ * accumulate not 0 / 1).
+ */
+#define BP_SEGMENT_SUM_MAX_COLS (1 << 24)
+#define BP_SEGMENT_SUM_MAX_SEGMENTS (0x7fffffff - 4096)
+int bp_segment_sum_rows(const void *rows, const int32_t *order, const int32_t *seg_begin, float *acc, int64_t n_rows,
+                        int64_t n_segments, int cols, int64_t rows_stride, int64_t acc_stride, int accumulate, int dtype,
+                        bp_stream_t stream);
 
 /*
  * bp_row_extremes -- the n largest and the n smallest elements of every row of a (rows, cols) matrix, with their columns,

@@ -2,7 +2,7 @@
 backward (+ gradient all-reduce under DDP) + AdamW step, timed.  NOT the headline bench (that is bench.py, the
 forward metric); this script records what the training path costs on the HIP kernels.
 
-    python scripts/bench_train_step.py [--batch 16] [--steps 5] [--model small]
+    python scripts/bench_train_step.py [--batch 16] [--steps 5] [--model small] [--sense-table off|batch] [--ids uniform|zipf]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 scripts/bench_train_step.py
 Default = the reference's recipe: fp32 parameters under 16-bit autocast (trainer precision 16,
 training/configs/trainer/default.yaml + experiment/owt/base.yaml), so DDP all-reduces 170.48 M fp32 gradients
@@ -47,6 +47,11 @@ def main():
     ap.add_argument('--grad-compress', default='none', choices=['none', 'fp16', 'bf16'],
                     help="DDP comm hook: all-reduce the gradient buckets in a 16-bit wire format (reference: "
                          "training/src/distributed/ddp_comm_hooks.py fp16_compress_hook)")
+    ap.add_argument('--sense-table', default='off', choices=['off', 'batch'],
+                    help="config.sense_table_train: 'batch' runs the content network once per distinct token of the batch")
+    ap.add_argument('--ids', default='uniform', choices=['uniform', 'zipf'],
+                    help="'zipf': token r + 1 of the vocabulary with probability ~ 1 / (r + 1) (exponent 1, seeded), so tokens "
+                         "repeat as they do in text; uniform ids over 50 k tokens barely repeat")
     ap.add_argument('--dist-backend', default='nccl', choices=['nccl', 'gloo'],
                     help="'gloo': the collectives go through host memory and ranks may share a GPU (test-suite only)")
     a = ap.parse_args()
@@ -69,7 +74,7 @@ def main():
     cfg = BackpackConfig(vocab_size=50257, n_positions=a.seq, scale_attn_by_inverse_layer_idx=True,
                          use_flash_attn=True, fused_bias_fc=True, fused_dense_gelu_dense=True,
                          fused_dropout_add_ln=True, pad_vocab_size_multiple=8, resid_pdrop=a.dropout,
-                         embd_pdrop=a.dropout, attn_pdrop=a.dropout, **MODELS[a.model])
+                         embd_pdrop=a.dropout, attn_pdrop=a.dropout, sense_table_train=a.sense_table, **MODELS[a.model])
     torch.manual_seed(0)
     model = BackpackLMHeadModel(cfg, device=dev, dtype=torch.bfloat16 if a.pure_bf16 else torch.float32).train()
     net = model
@@ -81,7 +86,12 @@ def main():
             net.register_comm_hook(None, HOOKS[a.grad_compress])
     opt = torch.optim.AdamW(model.parameters(), lr=1e-4, fused=True)
     loss_fn = CrossEntropyLoss(inplace_backward=True)
-    ids = torch.randint(0, 50257, (a.batch, a.seq), device=dev, generator=torch.Generator(device=dev).manual_seed(rank))
+    gen = torch.Generator(device=dev).manual_seed(rank)
+    if a.ids == 'zipf':
+        weights = 1.0 / torch.arange(1, 50257 + 1, device=dev, dtype=torch.float64)
+        ids = torch.multinomial(weights, a.batch * a.seq, replacement=True, generator=gen).view(a.batch, a.seq)
+    else:
+        ids = torch.randint(0, 50257, (a.batch, a.seq), device=dev, generator=gen)
     labels = torch.roll(ids, -1, 1)
 
     import contextlib
@@ -148,6 +158,7 @@ def main():
                           'value': round(world * a.batch * a.seq * a.steps / dt, 1), 'unit': 'tokens/s',
                           'n_gpus': world, 'ms_per_step': round(dt / a.steps * 1e3, 2), 'batch_per_gpu': a.batch,
                           'dtype': 'bf16' if a.pure_bf16 else 'bf16 autocast over fp32 parameters', 'dropout': a.dropout,
+                          'sense_table_train': a.sense_table, 'ids': a.ids, 'distinct_ids': int(ids.unique().numel()),
                           'grad_allreduce_bytes': wire_bytes, 'grad_compress': a.grad_compress,
                           'allreduce_ms': round(allreduce_ms, 3),
                           'bus_gbps': round(2 * (world - 1) / world * wire_bytes / (allreduce_ms * 1e-3) / 1e9, 1) if allreduce_ms else 0.0,
