@@ -72,6 +72,9 @@ SIGNATURES = {
     'bp_sense_mix_gather_varlen': (_i32, [_ptr] * 5 + [_i32, _ptr] + [_i32] * 5 + [_i64] * 7 + [_f32, _i32, _ptr, _ptr]),
     'bp_sense_mix_dc': (_i32, [_ptr] * 4 + [_i32] * 5 + [_i64] * 9 + [_f32, _i32, _ptr, _ptr]),
     'bp_sense_dq_dk': (_i32, [_ptr] * 6 + [_i32] * 5 + [_i64] * 11 + [_f32, _i32, _ptr]),
+    'bp_sense_mix_dc_varlen': (_i32, [_ptr] * 5 + [_i32] * 5 + [_i64] * 6 + [_f32, _i32, _ptr, _ptr]),
+    'bp_sense_dp_slab_varlen': (_i32, [_ptr] * 4 + [_i32] * 5 + [_i64] * 3 + [_i32, _ptr]),
+    'bp_sense_dq_dk_varlen': (_i32, [_ptr] * 7 + [_i32] * 5 + [_i64] * 7 + [_f32, _i32, _ptr]),
     'bp_add_layer_norm': (_i32, [_ptr] * 6 + [_i64, _i32, _f32] + [_i32] * 4 + [_ptr]),
     'bp_dropout_add_layer_norm': (_i32, [_ptr] * 7 + [_i64, _i32, _f32] + [_i32] * 5 + [_f32, _ptr, _ptr]),
     'bp_dropout_add_layer_norm_bwd': (_i32, [_ptr] * 9 + [_i64, _i32, _f32] + [_i32] * 4 + [_f32, _ptr, _ptr]),
@@ -977,6 +980,126 @@ def sense_mix_autograd(qk, content, softmax_scale=None, key_weight=None):
     if torch.is_grad_enabled() and (qk.requires_grad or content.requires_grad):
         return SenseMixFn.apply(qk, content, softmax_scale, key_weight)
     return sense_mix(qk, content, softmax_scale, key_weight=key_weight)
+
+
+# ---- the sense mix on packed batches, with a backward (training on packed batches) -----------------------------------------
+
+def _varlen_train_limits(qk, content, max_seqlen):
+    """(exceeded, reason) of every limit of the packed backward (bp_sense_mix_dc_varlen / _dp_slab_varlen / _dq_dk_varlen): the
+    packed forward's (max_seqlen <= 65536 among them), plus dense operands: the slab product reads the content as a
+    (total * k, d_out) matrix."""
+    return _varlen_limits(qk, content, max_seqlen, False) + (
+        (not qk.is_contiguous(), 'qk not contiguous'),
+        (not content.is_contiguous(), 'content not contiguous'),
+    )
+
+
+def sense_mix_varlen_train_supported(qk, content, max_seqlen):
+    """Shapes sense_mix_varlen_autograd takes (qk (total, 2, k, d_k), content (total, k, d_out))."""
+    return not any(exceeded for exceeded, _ in _varlen_train_limits(qk, content, max_seqlen))
+
+
+def sense_mix_varlen_train_limits(qk, content, max_seqlen):
+    """Which limits of sense_mix_varlen_autograd a call exceeds, as text."""
+    return '; '.join(reason for exceeded, reason in _varlen_train_limits(qk, content, max_seqlen) if exceeded)
+
+
+def _packed_backward_args(who, qk, dout, lse, cu_seqlens, max_seqlen, d_out):
+    total, b, k, dk = _check_packed_qk(qk, cu_seqlens, max_seqlen, who)
+    _require_cuda(dout, lse)
+    if dout.shape != (total, d_out) or dout.dtype != qk.dtype or dout.stride(-1) != 1:
+        raise RuntimeError(f'bp_hip.{who}: dout must be (total, d_out) in qk\'s dtype, last dim contiguous')
+    _lse_ws(qk, lse, b, int(max_seqlen), k)
+    return total, b, k, dk
+
+
+def sense_mix_dc_varlen(qk, dout, lse, cu_seqlens, max_seqlen, softmax_scale, like, out=None):
+    """dcontent (total,k,d_out) of sense_mix_varlen: bp_sense_mix_dc_varlen, a sample's rows with the bits of sense_mix_dc on
+    that sample alone.  `lse`: sense_lse_varlen's result; `like`: the forward's content; `out`: a contiguous buffer to write."""
+    d = like.shape[-1]
+    _require_cuda(like)   # (the result is allocated on its device: a CPU one would hand the kernel a host pointer)
+    total, b, k, dk = _packed_backward_args('sense_mix_dc_varlen', qk, dout, lse, cu_seqlens, max_seqlen, d)
+    if out is None:
+        out = torch.empty((total, k, d), dtype=like.dtype, device=like.device)
+    elif out.shape != (total, k, d) or out.dtype != like.dtype or not out.is_contiguous() or not out.is_cuda:
+        raise RuntimeError('bp_hip.sense_mix_dc_varlen: out must be a contiguous (total, k, d_out) GPU tensor of the content\'s dtype')
+    queue_ws = _queue_ws(qk.device)
+    _call('bp_sense_mix_dc_varlen', qk.device,
+          qk.data_ptr(), dout.data_ptr(), lse.data_ptr(), out.data_ptr(), cu_seqlens.data_ptr(), b, int(max_seqlen), k, dk, d,
+          qk.stride(0), qk.stride(1), qk.stride(2), dout.stride(0), out.stride(0), out.stride(1),
+          float(softmax_scale), _dtype_code(qk), queue_ws.data_ptr())
+    return out
+
+
+def sense_dqk_varlen(qk, content, dout, lse, cu_seqlens, max_seqlen, softmax_scale, out=None):
+    """dqk (like qk) of sense_mix_varlen, slab by slab (128 in-sample queries) as sense_dqk -- but the ragged product
+    dP^T = C_flat dout^T of a slab is bp_sense_dp_slab_varlen (no BLAS call serves it without padding the content), into one
+    reused (total * k, 128) buffer; bp_sense_dq_dk_varlen turns it into dq rows and dk contributions.  Three launches per
+    slab of max_seqlen, no host read of cu_seqlens."""
+    d = content.shape[-1]
+    _require_cuda(content)
+    total, b, k, dk = _packed_backward_args('sense_dqk_varlen', qk, dout, lse, cu_seqlens, max_seqlen, d)
+    if content.shape != (total, k, d) or content.dtype != qk.dtype or not content.is_contiguous() or not qk.is_contiguous():
+        raise RuntimeError('bp_hip.sense_dqk_varlen: ' + (sense_mix_varlen_train_limits(qk, content, int(max_seqlen))
+                                                        or 'content must be (total, k, d_out) in qk\'s dtype'))
+    if out is None:
+        out = torch.empty_like(qk)
+    elif out.shape != qk.shape or out.dtype != qk.dtype or not out.is_contiguous() or not out.is_cuda:
+        raise RuntimeError('bp_hip.sense_dqk_varlen: out must be a contiguous GPU tensor of qk\'s shape and dtype')
+    dqk = out
+    dk_acc = torch.zeros((total, k, dk), dtype=torch.float32, device=qk.device)
+    dsum = torch.empty((b, k, round_up(int(max_seqlen), 16)), dtype=torch.float32, device=qk.device)
+    dpt = torch.empty((total * k, SLAB), dtype=qk.dtype, device=qk.device)
+    code_dt = _dtype_code(qk)
+    for t0 in range(0, int(max_seqlen), SLAB):
+        _call('bp_sense_dp_slab_varlen', qk.device,
+              content.data_ptr(), dout.data_ptr(), dpt.data_ptr(), cu_seqlens.data_ptr(), b, int(max_seqlen), k, d, t0,
+              content.stride(0), content.stride(1), dout.stride(0), code_dt)
+        _call('bp_sense_dq_dk_varlen', qk.device,
+              qk.data_ptr(), dpt.data_ptr(), lse.data_ptr(), dsum.data_ptr(), dqk.data_ptr(), dk_acc.data_ptr(),
+              cu_seqlens.data_ptr(), b, int(max_seqlen), k, dk, t0, qk.stride(0), qk.stride(1), qk.stride(2),
+              dqk.stride(0), dqk.stride(2), dk_acc.stride(0), dk_acc.stride(1), float(softmax_scale), code_dt)
+    dqk[:, 1] = dk_acc
+    return dqk
+
+
+class SenseMixVarlenFn(torch.autograd.Function):
+    """Differentiable sense mix on a packed batch.  Forward: sense_lse_varlen + sense_mix_varlen.  Backward: SenseMixFn's
+    algebra with every kernel in its packed form -- bp_sense_mix_dc_varlen, and per slab bp_sense_dp_slab_varlen (in the
+    place of the BLAS GEMM) + bp_sense_dq_dk_varlen.  What the kernels do not take raises: there is no other route."""
+
+    @staticmethod
+    def forward(ctx, qk, content, cu_seqlens, max_seqlen, softmax_scale):
+        max_seqlen = int(max_seqlen)
+        _check_packed_qk(qk, cu_seqlens, max_seqlen, 'sense_mix_varlen_autograd')
+        if content.dim() != 3 or not sense_mix_varlen_train_supported(qk, content, max_seqlen):
+            raise RuntimeError('bp_hip.sense_mix_varlen_autograd: ' + (
+                'content must be (total, k, d_out)' if content.dim() != 3 else sense_mix_varlen_train_limits(qk, content, max_seqlen)))
+        scale = softmax_scale or qk.shape[-1] ** -0.5
+        lse = sense_lse_varlen(qk, cu_seqlens, max_seqlen, scale)
+        out = sense_mix_varlen(qk, content, cu_seqlens, max_seqlen, scale, lse=lse)
+        ctx.save_for_backward(qk, content, lse, cu_seqlens)
+        ctx.scale, ctx.max_seqlen = scale, max_seqlen
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qk, content, lse, cu_seqlens = ctx.saved_tensors
+        dout = dout.contiguous()
+        dcontent = dqk = None
+        if ctx.needs_input_grad[1]:
+            dcontent = sense_mix_dc_varlen(qk, dout, lse, cu_seqlens, ctx.max_seqlen, ctx.scale, content)
+        if ctx.needs_input_grad[0]:
+            dqk = sense_dqk_varlen(qk, content, dout, lse, cu_seqlens, ctx.max_seqlen, ctx.scale)
+        return dqk, dcontent, None, None, None
+
+
+def sense_mix_varlen_autograd(qk, content, cu_seqlens, max_seqlen, softmax_scale=None):
+    """sense_mix_varlen that records a backward when gradients are enabled (training on packed batches), the plain kernel
+    otherwise.  qk (total,2,k,d_k) and content (total,k,d_out) contiguous (sense_mix_varlen_train_supported)."""
+    if torch.is_grad_enabled() and (qk.requires_grad or content.requires_grad):
+        return SenseMixVarlenFn.apply(qk, content, cu_seqlens, max_seqlen, softmax_scale)
+    return sense_mix_varlen(qk, content, cu_seqlens, max_seqlen, softmax_scale)
 
 
 # ---- the sense mix over a table of rows, with a backward (training with the content network once per distinct token) -------

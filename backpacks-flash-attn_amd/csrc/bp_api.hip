@@ -589,6 +589,78 @@ int bp_sense_dq_dk(const void *qk, const void *dpt, const float *lse, float *dsu
     return launch_status(bp::launch_sense_dq_dk(p, dtype, static_cast<hipStream_t>(stream)));
 }
 
+// ---- the backward on packed batches: the fixed-length parameter blocks with `cu` set, s = max_seqlen, no batch strides --------
+int bp_sense_mix_dc_varlen(const void *qk, const void *dout, const float *lse, void *dcontent, const int32_t *cu_seqlens,
+                           int batch, int max_seqlen, int nsenses, int d_k, int d_out,
+                           int64_t qk_row_stride, int64_t qk_two_stride, int64_t qk_sense_stride, int64_t do_row_stride,
+                           int64_t c_row_stride, int64_t c_sense_stride,
+                           float softmax_scale, int dtype, void *queue_ws, bp_stream_t stream) {
+    const int rc = varlen_qk_args(qk, cu_seqlens, batch, max_seqlen, nsenses, d_k, qk_row_stride, qk_two_stride,
+                                  qk_sense_stride, softmax_scale, dtype);
+    if (rc != BP_OK) return rc;
+    if (queue_ws != nullptr && !aligned16(queue_ws)) return BP_ERR_SHAPE;
+    if (d_out < 8 || d_out % 8 != 0) return BP_ERR_DOUT;
+    if (max_seqlen > bp::kMixMaxTiles * 256) return BP_ERR_SHAPE;
+    if (dout == nullptr || lse == nullptr || dcontent == nullptr) return BP_ERR_SHAPE;
+    if (!aligned16({dout, dcontent}) || !strides8({do_row_stride, c_row_stride, c_sense_stride})) return BP_ERR_SHAPE;
+    if (null_queue_ws_on_capturing_stream(queue_ws, static_cast<hipStream_t>(stream))) return BP_ERR_QUEUE_WS;
+    const uint16_t *qp = static_cast<const uint16_t *>(qk);
+    bp::MixBwdParams p{};
+    p.q = qp; p.k = qp + qk_two_stride; p.dout = dout; p.dc = dcontent; p.lse = lse; p.cu = cu_seqlens;
+    p.qk_rs = qk_row_stride; p.qk_ss = qk_sense_stride;
+    p.do_rs = do_row_stride;
+    p.c_rs = c_row_stride; p.c_ss = c_sense_stride;
+    p.lse_stride = round_up(max_seqlen, 16);
+    p.b = batch; p.s = max_seqlen; p.nsenses = nsenses; p.dk = d_k; p.dout_cols = d_out;
+    p.n_ktiles = (max_seqlen + 255) / 256;
+    p.n_chunks = (d_out + 255) / 256;
+    p.scale_log2e = softmax_scale * bp::kLog2e;
+    p.queues = static_cast<bp::MixQueues *>(queue_ws);
+    return launch_status(bp::launch_sense_mix_dc_varlen(p, dtype, static_cast<hipStream_t>(stream)));
+}
+
+int bp_sense_dp_slab_varlen(const void *content, const void *dout, void *dpt, const int32_t *cu_seqlens,
+                            int batch, int max_seqlen, int nsenses, int d_out, int t0,
+                            int64_t c_row_stride, int64_t c_sense_stride, int64_t do_row_stride, int dtype, bp_stream_t stream) {
+    if (dtype != BP_DTYPE_F16 && dtype != BP_DTYPE_BF16) return BP_ERR_DTYPE;
+    if (d_out < 8 || d_out % 8 != 0) return BP_ERR_DOUT;
+    if (batch <= 0 || batch > 65535 || nsenses <= 0 || max_seqlen <= 0 || max_seqlen > 65536) return BP_ERR_SHAPE;
+    if (t0 < 0 || t0 >= max_seqlen || t0 % 128 != 0) return BP_ERR_SHAPE;
+    if (!content || !dout || !dpt || !cu_seqlens) return BP_ERR_SHAPE;
+    if (!aligned16({content, dout, dpt}) || !strides8({c_sense_stride, do_row_stride})) return BP_ERR_SHAPE;
+    if (c_row_stride != nsenses * c_sense_stride || c_sense_stride < d_out || do_row_stride < d_out) return BP_ERR_SHAPE;
+    bp::DpSlabParams p{};
+    p.c = content; p.dout = dout; p.dpt = dpt; p.cu = cu_seqlens;
+    p.c_rs = c_sense_stride; p.do_rs = do_row_stride;
+    p.b = batch; p.max_s = max_seqlen; p.nsenses = nsenses; p.dout_cols = d_out; p.t0 = t0;
+    return launch_status(bp::launch_sense_dp_slab_varlen(p, dtype, static_cast<hipStream_t>(stream)));
+}
+
+int bp_sense_dq_dk_varlen(const void *qk, const void *dpt, const float *lse, float *dsum_ws, void *dqk, float *dk_acc,
+                          const int32_t *cu_seqlens, int batch, int max_seqlen, int nsenses, int d_k, int t0,
+                          int64_t qk_row_stride, int64_t qk_two_stride, int64_t qk_sense_stride,
+                          int64_t dqk_row_stride, int64_t dqk_sense_stride, int64_t dka_row_stride, int64_t dka_sense_stride,
+                          float softmax_scale, int dtype, bp_stream_t stream) {
+    const int rc = varlen_qk_args(qk, cu_seqlens, batch, max_seqlen, nsenses, d_k, qk_row_stride, qk_two_stride,
+                                  qk_sense_stride, softmax_scale, dtype);
+    if (rc != BP_OK) return rc;
+    if (max_seqlen > 65536 || t0 < 0 || t0 >= max_seqlen || t0 % 128 != 0) return BP_ERR_SHAPE;
+    if (!dpt || !lse || !dsum_ws || !dqk || !dk_acc) return BP_ERR_SHAPE;
+    if (!aligned16({dpt, dqk, dk_acc}) || !strides8({dqk_row_stride, dqk_sense_stride})) return BP_ERR_SHAPE;
+    if ((dka_row_stride | dka_sense_stride) & 3) return BP_ERR_SHAPE;
+    const uint16_t *qp = static_cast<const uint16_t *>(qk);
+    bp::SenseGradParams p{};
+    p.q = qp; p.k = qp + qk_two_stride; p.dpt = dpt; p.lse = lse; p.dsum = dsum_ws; p.dq = dqk; p.dk_acc = dk_acc;
+    p.cu = cu_seqlens;
+    p.qk_rs = qk_row_stride; p.qk_ss = qk_sense_stride;
+    p.dq_rs = dqk_row_stride; p.dq_ss = dqk_sense_stride;
+    p.dka_rs = dka_row_stride; p.dka_ss = dka_sense_stride;
+    p.lse_stride = round_up(max_seqlen, 16);
+    p.b = batch; p.s = max_seqlen; p.nsenses = nsenses; p.dk = d_k; p.t0 = t0;
+    p.scale = softmax_scale;
+    return launch_status(bp::launch_sense_dq_dk_varlen(p, dtype, static_cast<hipStream_t>(stream)));
+}
+
 int64_t bp_flash_bwd_ws_floats(int batch, int nheads, int64_t lse_stride) {
     if (batch <= 0 || nheads <= 0 || lse_stride <= 0) return 0;
     return (int64_t)batch * nheads * 2 * lse_stride;

@@ -165,8 +165,12 @@ struct MixBwdParams {
     int n_chunks;             // ceil(dout_cols / 256)
     float scale_log2e;
     MixQueues *queues;        // caller's record (queue_ws) or NULL; armed by launch_sense_mix_dc
+    // launch_sense_mix_dc_varlen only (last: the fixed-length kernels never read it): sample b owns rows [cu[b], cu[b + 1]) of
+    // (total, ...) operands, s = max_seqlen, the batch strides are not read; as MixParams::cu
+    const int32_t *cu;
 };
 hipError_t launch_sense_mix_dc(const MixBwdParams &p, int dtype, hipStream_t stream);
+hipError_t launch_sense_mix_dc_varlen(const MixBwdParams &p, int dtype, hipStream_t stream);   // sense_mix_bwd_varlen.hip
 
 struct SenseGradParams {
     const void *q, *k;        // as MixParams
@@ -183,8 +187,24 @@ struct SenseGradParams {
     int b, s, nsenses, dk;
     int t0;                   // first query of the slab (multiple of 128)
     float scale;
+    // launch_sense_dq_dk_varlen only (last, as in MixBwdParams): dpt is (total * nsenses, 128), dk_acc (total, nsenses, dk)
+    const int32_t *cu;
 };
 hipError_t launch_sense_dq_dk(const SenseGradParams &p, int dtype, hipStream_t stream);
+hipError_t launch_sense_dq_dk_varlen(const SenseGradParams &p, int dtype, hipStream_t stream);   // sense_mix_bwd_varlen.hip
+
+// The ragged dP^T slab product of the packed backward (sense_dp_slab_varlen.hip): for every sample b with len_b > t0, rows
+// r < min(len_b, t0 + 128) * nsenses of   dpt[cu[b] * nsenses + r, q] = C_flat[cu[b] * nsenses + r, :] . dout[cu[b] + t0 + q, :]
+// (q < 128; queries at or behind len_b give zeros), fp32 accumulation, one rounding.  C_flat: the (total * nsenses, d_out)
+// view of the packed content, row stride c_rs.  Requires d_out % 8 == 0, 16-byte aligned bases, strides multiples of 8.
+struct DpSlabParams {
+    const void *c, *dout;     // 16-bit
+    void *dpt;                // (total * nsenses, 128) 16-bit, dense
+    const int32_t *cu;        // (b + 1) device ints, as MixParams::cu
+    int64_t c_rs, do_rs;
+    int b, max_s, nsenses, dout_cols, t0;
+};
+hipError_t launch_sense_dp_slab_varlen(const DpSlabParams &p, int dtype, hipStream_t stream);
 
 struct SoftmaxBwdParams {
     const void *alpha;   // (n, s, s) 16-bit causal softmax output (zeros above the diagonal)

@@ -20,6 +20,10 @@
 
 namespace bp {
 
+// Tag of the packed (variable-length) instantiations: Varlen<BF16> / Varlen<F16> in the place of the element type
+// (sense_mix_dma_kernel.h, sense_mix_bwd_kernel.h), so that the fixed-length instantiations keep their names and their text
+template <class ET> struct Varlen {};
+
 template <int KD_, bool AUX_>
 struct MixRingCfg {
     static constexpr int KD = KD_;

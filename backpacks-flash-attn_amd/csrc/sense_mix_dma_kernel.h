@@ -55,7 +55,7 @@ namespace bp {
 //     rows carry the bits of the fixed-length launch on that sample alone.  Rows behind the sample's end belong to the
 //     NEXT sample of the packed tensor: nothing is stored at my_q >= S, and every clamped read (my_q_clamped, the partial
 //     tile of MixStream, the index table of the gathering form) stays inside rows [cu[b], cu[b + 1]).
-template <class ET> struct Varlen {};
+// (Varlen<ET> itself: mix_ring.h, shared with the backward kernels)
 template <class ET> struct MixTag {
     using elem = ET;
     static constexpr bool varlen = false;

@@ -39,8 +39,11 @@ from src.utils.hf_convert import gpt2_trunk_state_dict, remap_state_dict_gpt2  #
 
 class BackpackConfig(GPT2Config):
 
-    def __init__(self, num_content_vectors=16, **kwargs):
+    def __init__(self, num_content_vectors=16, packed_train=False, **kwargs):
         self.num_content_vectors = num_content_vectors
+        # True: packed batches (cu_seqlens) are trainable -- BackpackModel._forward_packed records a backward through the packed
+        # sense kernels instead of refusing gradients
+        self.packed_train = packed_train
         super().__init__(**kwargs)
 
 
@@ -328,6 +331,7 @@ class BackpackModel(GPTPreTrainedModel):
         self.dedup_min_positions = int(getattr(config, 'dedup_min_positions', config.vocab_size))
         self._gather_fallback_said = False
         self._packed_fallback_said = False
+        self.packed_train = bool(getattr(config, 'packed_train', False))
         # training with the content network once per distinct token: 'off' (default) | 'batch', see `_train_table_mode`
         self.sense_table_train = getattr(config, 'sense_table_train', 'off')
         self._train_table_mode()
@@ -655,8 +659,8 @@ class BackpackModel(GPTPreTrainedModel):
     # ---- packed (variable-length) batches --------------------------------------------------------------------------------
     # input_ids (total,) + cu_seqlens ((B + 1,) int32 on the ids' device) + max_seqlen (int) -> (total, d): the sequences lie
     # behind one another, nothing is padded (src/utils/packing.py builds the three).  The trunk runs its ragged flash call,
-    # the senses bp_sense_mix_varlen / bp_sense_mix_gather_varlen.  Inference only (no varlen backward), not under
-    # GraphedForward.
+    # the senses bp_sense_mix_varlen / bp_sense_mix_gather_varlen.  Inference only unless config.packed_train is set
+    # (`_forward_packed_train`: the packed backward kernels), not under GraphedForward.
     # What the packed kernels do not take -- wide or non-fused senses, use_flash_attn=False, the CPU -- is padded to
     # (B, max_seqlen), run through the forward above and cut back to the real rows (`_forward_packed_padded`).
     # With inference_params at sequence_len_offset == 0 the call is the PACKED PREFILL of the KV caches (`_packed_prefill`):
@@ -735,15 +739,20 @@ class BackpackModel(GPTPreTrainedModel):
     def _forward_packed(self, input_ids, position_ids, inference_params, cu_seqlens, max_seqlen):
         if inference_params is not None:
             refuse_packed_step(inference_params)
-        if torch.is_grad_enabled():
+        train = torch.is_grad_enabled() and self.packed_train
+        if torch.is_grad_enabled() and not train:
             raise RuntimeError('the packed forward is inference-only (no varlen backward): run it under torch.no_grad() '
-                               'or torch.inference_mode()')
+                               'or torch.inference_mode(), or build the model with packed_train=True')
+        if train and inference_params is not None:
+            raise RuntimeError('KV-cached decoding is inference-only: run the packed prefill under torch.no_grad()')
         if cu_seqlens is None or max_seqlen is None or input_ids.dim() != 1 or cu_seqlens.dim() != 1 \
                 or cu_seqlens.dtype != torch.int32 or cu_seqlens.device != input_ids.device:
             raise ValueError('a packed batch needs input_ids (total,), cu_seqlens (B + 1,) int32 on the ids\' device and '
                              'max_seqlen (int): see src/utils/packing.pack_sequences')
         max_seqlen = int(max_seqlen)
         limit = self._packed_limit(input_ids, max_seqlen)
+        if train:
+            return self._forward_packed_train(input_ids, position_ids, cu_seqlens, max_seqlen, limit)
         if limit is not None:
             if inference_params is not None:
                 raise ValueError('a packed batch (cu_seqlens / max_seqlen) with inference_params -- a packed prefill -- is '
@@ -770,6 +779,22 @@ class BackpackModel(GPTPreTrainedModel):
         content = self.content_model(input_ids.unsqueeze(0))             # (1, k, total, d) view of (1, total, k*d)
         return bp_hip.sense_mix_varlen(qk, content[0].transpose(0, 1), cu_seqlens, max_seqlen,
                                        self.contextualization_attn.scale())
+
+    def _forward_packed_train(self, input_ids, position_ids, cu_seqlens, max_seqlen, limit):
+        """The packed forward with gradients (config.packed_train): the trunk on the packed rows through its ragged autograd
+        path, the content network over every packed position (the 'off' order, unchunked; dropout as in the padded training
+        forward), the mix through bp_hip.sense_mix_varlen_autograd.  Nothing is padded silently in training: a limit raises."""
+        if self.sense_table_train != 'off':
+            raise NotImplementedError("packed_train with sense_table_train='batch': the table form of the packed backward "
+                                      'does not exist')
+        if limit is not None:
+            raise RuntimeError('packed_train: the packed kernels do not take this batch: ' + limit)
+        hidden = self.gpt2_model(input_ids, position_ids=position_ids, cu_seqlens=cu_seqlens, max_seqlen=max_seqlen)
+        qk = self.contextualization_attn.project(hidden).contiguous()                      # (total, 2, k, d_k)
+        content = self.content_model(input_ids.unsqueeze(0))[0].transpose(0, 1).contiguous()   # (total, k, d) as it lies
+        if not bp_hip.sense_mix_varlen_train_supported(qk, content, max_seqlen):
+            raise RuntimeError('packed_train: ' + bp_hip.sense_mix_varlen_train_limits(qk, content, max_seqlen))
+        return bp_hip.sense_mix_varlen_autograd(qk, content, cu_seqlens, max_seqlen, self.contextualization_attn.scale())
 
     def forward(self, input_ids, position_ids=None, inference_params=None, cu_seqlens=None, max_seqlen=None):
         if cu_seqlens is not None or max_seqlen is not None:

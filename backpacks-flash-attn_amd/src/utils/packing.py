@@ -77,3 +77,16 @@ def pad_rows(values, cu_seqlens, max_seqlen, fill=0):
     out = values.new_full((cu_seqlens.numel() - 1, int(max_seqlen)) + tuple(values.shape[1:]), fill)
     out[sample, position] = values
     return out
+
+
+def packed_lm_labels(packed_ids, cu_seqlens, ignore_index=-100):
+    """Next-token labels of a packed batch: labels[t] = packed_ids[t + 1], and `ignore_index` at every sequence's last
+    position -- a packed loss never predicts across a boundary (nor the first token of the next sequence from the last of
+    this one).  No host read: a zero-length sequence owns no position and marks none."""
+    total = packed_ids.shape[0]
+    labels = torch.cat([packed_ids[1:], packed_ids.new_full((1,), ignore_index)])
+    # the last position of every sequence.  An empty sequence repeats the end of the one before it; empty ones at the very
+    # front give -1, taken as the batch's last position, which is a sequence's end anyway
+    ends = (cu_seqlens.to(device=packed_ids.device, dtype=torch.int64)[1:] - 1) % total
+    labels[ends] = ignore_index
+    return labels

@@ -70,7 +70,9 @@ extern "C" {
                               and one more: bp_pick_token_phrases, the row-limited pick with banned phrases and stop phrases
                               of several tokens, matched against the row's history on the device;
                               and one more: bp_segment_sum_rows, fp32 sums of 16-bit rows over the segments of a sorted index --
-                              the gradient of the rows of a sense table that several positions read) */
+                              the gradient of the rows of a sense table that several positions read;
+                              and three more: bp_sense_mix_dc_varlen / bp_sense_dp_slab_varlen / bp_sense_dq_dk_varlen, the
+                              backward of the sense mix on packed batches) */
 
 /* element type of q/k/v/out/content tensors */
 #define BP_DTYPE_F16 0
@@ -336,7 +338,8 @@ int bp_sense_mix_gather(const void *qk, const void *table, const int32_t *row_in
  * Restrictions: narrow senses on the 16-byte vector path only, i.e. what bp_sense_mix_gather states -- d_k % 8 == 0 and
  * d_k <= 128 (BP_ERR_HEAD_DIM otherwise), d_out % 8 == 0 (BP_ERR_DOUT), aligned bases and strides that are multiples of 8,
  * max_seqlen <= 65536 (BP_ERR_SHAPE); the gathering form max_seqlen <= 4096, table_rows <= 65536 and a table below 4 GiB.
- * No key-weighted, wide or element-wise-loader form and no backward exist: callers pad such batches.
+ * No key-weighted, wide or element-wise-loader form exists: callers pad such batches.  The backward of the plain form:
+ * bp_sense_mix_dc_varlen and its companions below; the gathering form has none.
  */
 int bp_sense_lse_varlen(const void *qk, float *lse, const int32_t *cu_seqlens, int batch, int max_seqlen, int nsenses,
                         int d_k, int64_t qk_row_stride, int64_t qk_two_stride, int64_t qk_sense_stride,
@@ -393,6 +396,36 @@ int bp_sense_dq_dk(const void *qk, const void *dpt, const float *lse, float *dsu
                    int64_t dqk_batch_stride, int64_t dqk_row_stride, int64_t dqk_sense_stride,
                    int64_t dka_batch_stride, int64_t dka_row_stride, int64_t dka_sense_stride,
                    float softmax_scale, int dtype, bp_stream_t stream);
+
+/*
+ * bp_sense_mix_dc_varlen, bp_sense_dp_slab_varlen, bp_sense_dq_dk_varlen -- the backward of bp_sense_mix_varlen: training on
+ * PACKED batches (added within ABI 11: additive).  Operands, cu_seqlens (device only, NOT validated), max_seqlen and lse as
+ * in bp_sense_mix_varlen; dout (total, d_out) with row stride do_row.  A sample's gradients carry the bits of the
+ * fixed-length entry points on that sample alone; zero-length samples are skipped.
+ *   bp_sense_mix_dc_varlen   dcontent (total, nsenses, d_out), strides c_row / c_sense: bp_sense_mix_dc per sample.
+ *   bp_sense_dp_slab_varlen  the transposed dP slab of queries [t0, t0 + 128) of every sample that has them, which the
+ *       fixed-length path takes from a BLAS GEMM:  dpt[cu[b]*nsenses + r, j] = content_flat[cu[b]*nsenses + r, :] . dout[cu[b] + t0 + j, :]
+ *       for r < min(len_b, t0 + 128) * nsenses, j < 128 (zeros where t0 + j >= len_b), fp32 accumulation, one rounding.
+ *       dpt is a dense (total * nsenses, 128) 16-bit buffer; rows of other samples and rows behind r are not touched.  The
+ *       content must be dense over (row, sense): c_row_stride == nsenses * c_sense_stride (BP_ERR_SHAPE otherwise).
+ *   bp_sense_dq_dk_varlen    bp_sense_dq_dk for that slab on every sample: dqk like qk (strides dqk_row / dqk_sense), dk_acc
+ *       (total, nsenses, d_k) fp32 (strides dka_row / dka_sense; zero it before the first slab, slabs in order on one
+ *       stream), dsum_ws (batch, nsenses, roundup(max_seqlen,16)) fp32.  t0 % 128 == 0, 0 <= t0 < max_seqlen.
+ * Restrictions and error codes as bp_sense_mix_varlen's plain form; batch <= 65535 for the slab product.
+ */
+int bp_sense_mix_dc_varlen(const void *qk, const void *dout, const float *lse, void *dcontent, const int32_t *cu_seqlens,
+                           int batch, int max_seqlen, int nsenses, int d_k, int d_out,
+                           int64_t qk_row_stride, int64_t qk_two_stride, int64_t qk_sense_stride, int64_t do_row_stride,
+                           int64_t c_row_stride, int64_t c_sense_stride,
+                           float softmax_scale, int dtype, void *queue_ws, bp_stream_t stream);
+int bp_sense_dp_slab_varlen(const void *content, const void *dout, void *dpt, const int32_t *cu_seqlens,
+                            int batch, int max_seqlen, int nsenses, int d_out, int t0,
+                            int64_t c_row_stride, int64_t c_sense_stride, int64_t do_row_stride, int dtype, bp_stream_t stream);
+int bp_sense_dq_dk_varlen(const void *qk, const void *dpt, const float *lse, float *dsum_ws, void *dqk, float *dk_acc,
+                          const int32_t *cu_seqlens, int batch, int max_seqlen, int nsenses, int d_k, int t0,
+                          int64_t qk_row_stride, int64_t qk_two_stride, int64_t qk_sense_stride,
+                          int64_t dqk_row_stride, int64_t dqk_sense_stride, int64_t dka_row_stride, int64_t dka_sense_stride,
+                          float softmax_scale, int dtype, bp_stream_t stream);
 
 /*
  * bp_flash_bwd -- attention backward: dq, dk, dv from q, k, v, dout and the forward's out and softmax_lse.

@@ -3,6 +3,7 @@ backward (+ gradient all-reduce under DDP) + AdamW step, timed.  NOT the headlin
 forward metric); this script records what the training path costs on the HIP kernels.
 
     python scripts/bench_train_step.py [--batch 16] [--steps 5] [--model small] [--sense-table off|batch] [--ids uniform|zipf]
+    python scripts/bench_train_step.py --lengths 16:1024 [--packed]     ragged batch: padded to --seq, or packed (packed_train)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 scripts/bench_train_step.py
 Default = the reference's recipe: fp32 parameters under 16-bit autocast (trainer precision 16,
 training/configs/trainer/default.yaml + experiment/owt/base.yaml), so DDP all-reduces 170.48 M fp32 gradients
@@ -52,6 +53,11 @@ def main():
     ap.add_argument('--ids', default='uniform', choices=['uniform', 'zipf'],
                     help="'zipf': token r + 1 of the vocabulary with probability ~ 1 / (r + 1) (exponent 1, seeded), so tokens "
                          "repeat as they do in text; uniform ids over 50 k tokens barely repeat")
+    ap.add_argument('--lengths', default=None, metavar='LO:HI',
+                    help='seeded sequence lengths, uniform in [LO, HI] (HI <= --seq): the batch is right-padded to --seq with '
+                         'the pads ignored by the loss, or, with --packed, packed without padding')
+    ap.add_argument('--packed', action='store_true',
+                    help='config.packed_train: the step runs on the packed rows (cu_seqlens); needs --lengths')
     ap.add_argument('--dist-backend', default='nccl', choices=['nccl', 'gloo'],
                     help="'gloo': the collectives go through host memory and ranks may share a GPU (test-suite only)")
     a = ap.parse_args()
@@ -74,7 +80,8 @@ def main():
     cfg = BackpackConfig(vocab_size=50257, n_positions=a.seq, scale_attn_by_inverse_layer_idx=True,
                          use_flash_attn=True, fused_bias_fc=True, fused_dense_gelu_dense=True,
                          fused_dropout_add_ln=True, pad_vocab_size_multiple=8, resid_pdrop=a.dropout,
-                         embd_pdrop=a.dropout, attn_pdrop=a.dropout, sense_table_train=a.sense_table, **MODELS[a.model])
+                         embd_pdrop=a.dropout, attn_pdrop=a.dropout, sense_table_train=a.sense_table, packed_train=a.packed,
+                         **MODELS[a.model])
     torch.manual_seed(0)
     model = BackpackLMHeadModel(cfg, device=dev, dtype=torch.bfloat16 if a.pure_bf16 else torch.float32).train()
     net = model
@@ -93,6 +100,21 @@ def main():
     else:
         ids = torch.randint(0, 50257, (a.batch, a.seq), device=dev, generator=gen)
     labels = torch.roll(ids, -1, 1)
+    real_tokens, forward_args = a.batch * a.seq, {}
+    if a.packed and not a.lengths:
+        ap.error('--packed needs --lengths')
+    if a.lengths:
+        from src.utils.packing import pack_sequences, packed_lm_labels
+        lo, hi = (int(x) for x in a.lengths.split(':'))
+        lens = torch.randint(lo, hi + 1, (a.batch,), generator=torch.Generator().manual_seed(1000 + rank)).tolist()
+        real_tokens = sum(lens)
+        if a.packed:
+            ids, cu, longest = pack_sequences(ids, lens)
+            labels, forward_args = packed_lm_labels(ids, cu), {'cu_seqlens': cu, 'max_seqlen': longest}
+        else:
+            labels = labels.clone()
+            for b, n in enumerate(lens):
+                labels[b, max(n - 1, 0):] = -100
 
     import contextlib
 
@@ -100,7 +122,7 @@ def main():
         opt.zero_grad(set_to_none=True)
         with (contextlib.nullcontext() if (sync or not ddp) else net.no_sync()):
             with torch.autocast('cuda', dtype=torch.bfloat16, enabled=not a.pure_bf16):
-                logits = net(ids).logits
+                logits = net(ids, **forward_args).logits
             loss = loss_fn(logits.view(-1, logits.shape[-1]), labels.view(-1))
             loss.backward()
         opt.step()
@@ -155,7 +177,8 @@ def main():
     mesh_ms = ring_ms / (world - 1) if world > 1 else 0.0
     if rank == 0:
         print(json.dumps({'metric': f'tokens/sec train step (fwd+loss+bwd+AdamW), Backpack-{a.model} seq={a.seq}',
-                          'value': round(world * a.batch * a.seq * a.steps / dt, 1), 'unit': 'tokens/s',
+                          'value': round(world * real_tokens * a.steps / dt, 1), 'unit': 'tokens/s',
+                          'lengths': a.lengths, 'packed': a.packed, 'real_token_share': round(real_tokens / (a.batch * a.seq), 4),
                           'n_gpus': world, 'ms_per_step': round(dt / a.steps * 1e3, 2), 'batch_per_gpu': a.batch,
                           'dtype': 'bf16' if a.pure_bf16 else 'bf16 autocast over fp32 parameters', 'dropout': a.dropout,
                           'sense_table_train': a.sense_table, 'ids': a.ids, 'distinct_ids': int(ids.unique().numel()),
