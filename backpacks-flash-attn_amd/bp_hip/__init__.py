@@ -95,6 +95,9 @@ SIGNATURES = {
     'bp_sense_decode_ws_floats': (_i64, [_i32] * 4),
     'bp_sense_decode': (_i32, [_ptr] * 9 + [_i64] + [_i32] * 5 + [_i64] + [_i64] * 11 + [_f32, _i32, _ptr]),
     'bp_sense_decode_weighted': (_i32, [_ptr] * 10 + [_i64] + [_i32] * 5 + [_i64] + [_i64] * 13 + [_f32, _i32, _ptr]),
+    'bp_sense_table_quantize': (_i32, [_ptr] * 3 + [_i64] + [_i32] * 2 + [_i64] * 6 + [_i32, _ptr]),
+    'bp_sense_table_dequantize': (_i32, [_ptr] * 3 + [_i64] + [_i32] * 2 + [_i64] * 6 + [_i32, _ptr]),
+    'bp_sense_decode_mx8': (_i32, [_ptr] * 11 + [_i64] + [_i32] * 5 + [_i64] + [_i64] * 15 + [_f32, _i32, _ptr]),
     'bp_sense_rows_dot': (_i32, [_ptr] * 6 + [_i32] * 4 + [_i64] + [_i64] * 6 + [_i32, _ptr]),
     'bp_pick_token': (_i32, [_ptr] * 6 + [_i32] * 2 + [_i64] * 3 + [_i32] * 2 + [_f32, _i32, _f32, _i32, _ptr]),
     'bp_pick_token_ctl': (_i32, [_ptr] * 7 + [_i32] * 2 + [_i64] * 3 + [_i32] * 2 + [_f32, _i32, _f32, _f32] + [_i32] * 4 + [_ptr]),
@@ -1594,6 +1597,145 @@ def sense_decode(q, k_new, k_cache, table, row_index, new_row, cache_seqlens, so
           b, k, dk, dout, max_s, table.shape[0], q.stride(0), q.stride(1), k_new.stride(0), k_new.stride(1),
           k_cache.stride(0), k_cache.stride(1), k_cache.stride(2), table.stride(0), table.stride(1),
           row_index.stride(0), out.stride(0), float(scale), _dtype_code(q))
+    return out
+
+
+# ---- MXFP8 sense table (C ABI bp_sense_table_quantize / bp_sense_table_dequantize / bp_sense_decode_mx8) -------------------
+# The format is specified in include/bp_hip.h ("MXFP8 sense table"): q8 (rows, k, d_out) uint8 holds OCP E4M3 elements,
+# scale8 (rows, k, d_out / 32) uint8 one E8M0 scale per block of 32 columns; value = e4m3(q8) * 2^(scale8 - 127).
+
+MX8_BLOCK = 32
+
+
+def _mx8_pair_ok(q8, scale8):
+    return (q8.dim() == 3 and scale8.dim() == 3 and q8.dtype == torch.uint8 and scale8.dtype == torch.uint8
+            and q8.shape[2] % MX8_BLOCK == 0 and tuple(scale8.shape) == (q8.shape[0], q8.shape[1], q8.shape[2] // MX8_BLOCK)
+            and q8.stride(2) == 1 and scale8.stride(2) == 1)
+
+
+def _mx8_table_args(what, table, q8, scale8):
+    _require_cuda(table, q8, scale8)
+    if table.dim() != 3 or table.shape[2] % MX8_BLOCK != 0 or table.stride(2) != 1 or table.numel() == 0:
+        raise RuntimeError(f'bp_hip.{what}: the table must be (rows, k, d_out), d_out % {MX8_BLOCK} == 0, unit last stride')
+    if not _mx8_pair_ok(q8, scale8) or q8.shape != table.shape:
+        raise RuntimeError(f'bp_hip.{what}: q8 must be uint8 of the table\'s shape {tuple(table.shape)} and scale8 uint8 '
+                           f'(rows, k, d_out / {MX8_BLOCK}), unit last strides')
+    if not 1 <= table.shape[1] <= SENSE_DECODE_MAX_SENSES or not _vec16(table) or q8.data_ptr() % 16 \
+            or q8.stride(0) % 16 or q8.stride(1) % 16:
+        raise RuntimeError(f'bp_hip.{what}: at most {SENSE_DECODE_MAX_SENSES} senses, 16-byte aligned rows of table and q8')
+    return (table.shape[0], table.shape[1], table.shape[2], table.stride(0), table.stride(1), q8.stride(0), q8.stride(1),
+            scale8.stride(0), scale8.stride(1), _dtype_code(table))
+
+
+def sense_table_quantize(table):
+    """(q8, scale8): the MXFP8 twin of a 16-bit sense table (rows, k, d_out), d_out % 32 == 0 (bp_sense_table_quantize)."""
+    _require_cuda(table)
+    if table.dim() != 3:
+        raise RuntimeError('bp_hip.sense_table_quantize: the table must be (rows, k, d_out)')
+    rows, k, d = table.shape
+    q8 = torch.empty((rows, k, d), dtype=torch.uint8, device=table.device)
+    scale8 = torch.empty((rows, k, d // MX8_BLOCK), dtype=torch.uint8, device=table.device)
+    return sense_table_quantize_into(table, q8, scale8)
+
+
+def sense_table_quantize_into(table, q8, scale8):
+    """sense_table_quantize into an existing pair (a rebuild in place: captured graphs keep the addresses)."""
+    args = _mx8_table_args('sense_table_quantize', table, q8, scale8)
+    _call('bp_sense_table_quantize', table.device, table.data_ptr(), q8.data_ptr(), scale8.data_ptr(), *args)
+    return q8, scale8
+
+
+def sense_table_dequantize(q8, scale8, dtype, out=None):
+    """The 16-bit table (fp16 / bf16) an MXFP8 pair stands for, exact wherever `dtype` holds the value
+    (bp_sense_table_dequantize); `out`: written in place and returned."""
+    if out is None:
+        out = torch.empty(q8.shape, dtype=dtype, device=q8.device)
+    if out.dtype != dtype:
+        raise RuntimeError('bp_hip.sense_table_dequantize: out must be of the requested dtype')
+    args = _mx8_table_args('sense_table_dequantize', out, q8, scale8)
+    _call('bp_sense_table_dequantize', q8.device, q8.data_ptr(), scale8.data_ptr(), out.data_ptr(), *args)
+    return out
+
+
+def _eager_sense_table_quantize(table):
+    """Torch twin of sense_table_quantize (any device): the OCP MX rule of include/bp_hip.h, step by step."""
+    rows, k, d = table.shape
+    if d % MX8_BLOCK != 0:
+        raise RuntimeError(f'bp_hip: an MXFP8 table needs d_out % {MX8_BLOCK} == 0')
+    x = table.float().reshape(rows, k, d // MX8_BLOCK, MX8_BLOCK)
+    amax = x.abs().amax(dim=-1)
+    exponent = (torch.frexp(amax)[1] - 1 - 8).clamp(min=-127)          # floor(log2(amax)) - emax, held at E8M0's lowest
+    exponent = torch.where(amax == 0, torch.zeros_like(exponent), exponent)
+    scaled = torch.ldexp(x, -exponent.unsqueeze(-1)).clamp(-448.0, 448.0)
+    q8 = scaled.to(torch.float8_e4m3fn).view(torch.uint8).reshape(rows, k, d)
+    return q8, (exponent + 127).to(torch.uint8)
+
+
+def _eager_sense_table_dequantize(q8, scale8, dtype, out=None):
+    """Torch twin of sense_table_dequantize (any device)."""
+    rows, k, d = q8.shape
+    # E4M3 by hand (no float8 tensor type needed on the device): 1 sign, 4 exponent (bias 7), 3 mantissa bits
+    bits = q8.to(torch.int32)
+    exp, man = (bits >> 3) & 15, (bits & 7).float()
+    e = torch.where(exp == 0, torch.ldexp(man, torch.full_like(exp, -9)), torch.ldexp(8 + man, exp - 10))
+    e = torch.where(bits >= 128, -e, e).reshape(rows, k, d // MX8_BLOCK, MX8_BLOCK)
+    table = torch.ldexp(e, (scale8.to(torch.int32) - 127).unsqueeze(-1)).reshape(rows, k, d).to(dtype)
+    return table if out is None else out.copy_(table)
+
+
+def sense_decode_mx8_supported(q, k_cache, q8, scale8, key_weight=None):
+    """Whether bp_sense_decode_mx8 takes these operands: sense_decode_supported's limits with d_out % 32 == 0, a well-formed
+    (q8, scale8) pair with 16-byte aligned rows, and sense_decode_weighted_supported's contract for the weights."""
+    if not (q.is_cuda and k_cache.is_cuda and q8.is_cuda and scale8.is_cuda) or q.dtype not in (torch.float16, torch.bfloat16):
+        return False
+    if k_cache.dtype != q.dtype or q.dim() != 3 or k_cache.dim() != 4 or not _mx8_pair_ok(q8, scale8):
+        return False
+    k, dk, dout = q.shape[1], q.shape[2], q8.shape[2]
+    if key_weight is not None and not _decode_key_weight_ok(key_weight, q.shape[0], k, k_cache.shape[1]):
+        return False
+    return (dk % 8 == 0 and dk <= SENSE_MAX_DK and 1 <= k <= SENSE_DECODE_MAX_SENSES and q8.shape[1] == k
+            and dout <= SENSE_DECODE_MAX_DOUT and _vec16(q, k_cache) and q8.data_ptr() % 16 == 0
+            and q8.stride(0) % 16 == 0 and q8.stride(1) % 16 == 0)
+
+
+def sense_decode_mx8(q, k_new, k_cache, q8, scale8, row_index, new_row, cache_seqlens, softmax_scale=None, out=None,
+                     key_weight=None):
+    """sense_decode with the table given by its MXFP8 twin (q8, scale8) -- sense_table_quantize's pair: the value rows cost
+    1 byte per element plus 1 per 32.  Everything else, key_weight included, as sense_decode; the result is that of
+    sense_decode on the dequantised table up to the order of the fp32 sums (C ABI bp_sense_decode_mx8)."""
+    _require_cuda(q, k_new, k_cache, q8, scale8, row_index, new_row, cache_seqlens)
+    if q.dim() != 3 or k_new.shape != q.shape:
+        raise RuntimeError('bp_hip.sense_decode_mx8: q and k_new must be (B, k, d_k) of one shape')
+    b, k, dk = q.shape
+    if k_cache.dim() != 4 or k_cache.shape[0] != b or tuple(k_cache.shape[2:]) != (k, dk):
+        raise RuntimeError(f'bp_hip.sense_decode_mx8: k_cache must be (B, max_seqlen, k, d_k) = ({b}, *, {k}, {dk}), '
+                           f'got {tuple(k_cache.shape)}')
+    max_s = k_cache.shape[1]
+    if not _mx8_pair_ok(q8, scale8) or q8.shape[1] != k:
+        raise RuntimeError(f'bp_hip.sense_decode_mx8: q8 must be uint8 (rows, k, d_out), d_out % {MX8_BLOCK} == 0, and scale8 '
+                           f'uint8 (rows, k, d_out / {MX8_BLOCK}), unit last strides')
+    if k_new.dtype != q.dtype or k_cache.dtype != q.dtype:
+        raise RuntimeError('bp_hip.sense_decode_mx8: q, k_new and k_cache dtypes differ')
+    if row_index.shape != (b, max_s) or row_index.dtype != torch.int32 or row_index.stride(-1) != 1:
+        raise RuntimeError('bp_hip.sense_decode_mx8: row_index must be (B, max_seqlen) int32, unit stride along the sequence')
+    for name, t in (('new_row', new_row), ('cache_seqlens', cache_seqlens)):
+        if t.shape != (b,) or t.dtype != torch.int32 or not t.is_contiguous():
+            raise RuntimeError(f'bp_hip.sense_decode_mx8: {name} must be a contiguous (B,) int32 tensor')
+    if key_weight is not None and not _decode_key_weight_ok(key_weight, b, k, max_s):
+        raise RuntimeError(f'bp_hip.sense_decode_mx8: key_weight must be a float32 CUDA tensor of shape ({b}, {k}, {max_s}) '
+                           'with unit stride along the positions')
+    dout = q8.shape[2]
+    scale = softmax_scale or dk ** -0.5
+    if out is None:
+        out = torch.empty((b, dout), dtype=q.dtype, device=q.device)
+    ws = _decode_ws(lib().bp_sense_decode_ws_floats(b, k, dout, max_s), q.device)
+    kw = (key_weight.data_ptr(), key_weight.stride(0), key_weight.stride(1)) if key_weight is not None else (None, 0, 0)
+    _call('bp_sense_decode_mx8', q.device,
+          q.data_ptr(), k_new.data_ptr(), k_cache.data_ptr(), q8.data_ptr(), scale8.data_ptr(), row_index.data_ptr(),
+          new_row.data_ptr(), cache_seqlens.data_ptr(), kw[0], out.data_ptr(), ws.data_ptr(), ws.numel(),
+          b, k, dk, dout, max_s, q8.shape[0], q.stride(0), q.stride(1), k_new.stride(0), k_new.stride(1),
+          k_cache.stride(0), k_cache.stride(1), k_cache.stride(2), q8.stride(0), q8.stride(1), scale8.stride(0),
+          scale8.stride(1), row_index.stride(0), out.stride(0), kw[1], kw[2], float(scale), _dtype_code(q))
     return out
 
 

@@ -1085,6 +1085,100 @@ int bp_sense_decode_weighted(const void *q, const void *k_new, void *k_cache, co
     return launch_status(bp::launch_sense_decode_weighted(p, dtype, static_cast<hipStream_t>(stream)));
 }
 
+// ---- MXFP8 sense table (bp_sense_table_quantize / _dequantize / bp_sense_decode_mx8) ----
+
+static int mx8_table_params(bp::Mx8TableParams &p, const void *table, const void *q8, const void *scale8, int64_t rows,
+                            int k, int d_out, int64_t t_row_stride, int64_t t_sense_stride, int64_t q_row_stride,
+                            int64_t q_sense_stride, int64_t s_row_stride, int64_t s_sense_stride, int dtype) {
+    if (dtype != BP_DTYPE_F16 && dtype != BP_DTYPE_BF16) return BP_ERR_DTYPE;
+    if (d_out < 1) return BP_ERR_DOUT;
+    if (d_out % 32 != 0 || rows <= 0 || rows > 0x7fffffffLL || k <= 0 || k > 64) return BP_ERR_SHAPE;
+    if (table == nullptr || q8 == nullptr || scale8 == nullptr || !aligned16({table, q8})) return BP_ERR_SHAPE;
+    if (!strides8({t_row_stride, t_sense_stride}) || q_row_stride % 16 != 0 || q_sense_stride % 16 != 0)
+        return BP_ERR_SHAPE;
+    // rows of different (row, sense) pairs do not overlap
+    if (t_sense_stride < d_out || t_row_stride < d_out || q_sense_stride < d_out || q_row_stride < d_out
+        || s_sense_stride < d_out / 32 || s_row_stride < d_out / 32)
+        return BP_ERR_SHAPE;
+    p.table = const_cast<void *>(table);
+    p.q8 = static_cast<uint8_t *>(const_cast<void *>(q8));
+    p.scale8 = static_cast<uint8_t *>(const_cast<void *>(scale8));
+    p.t_rs = t_row_stride; p.t_gs = t_sense_stride; p.q_rs = q_row_stride; p.q_gs = q_sense_stride;
+    p.s_rs = s_row_stride; p.s_gs = s_sense_stride;
+    p.rows = rows; p.k = k; p.d = d_out;
+    return BP_OK;
+}
+
+int bp_sense_table_quantize(const void *table, void *q8, void *scale8, int64_t rows, int nsenses, int d_out,
+                            int64_t t_row_stride, int64_t t_sense_stride, int64_t q_row_stride, int64_t q_sense_stride,
+                            int64_t s_row_stride, int64_t s_sense_stride, int dtype, bp_stream_t stream) {
+    bp::Mx8TableParams p{};
+    const int rc = mx8_table_params(p, table, q8, scale8, rows, nsenses, d_out, t_row_stride, t_sense_stride, q_row_stride,
+                                    q_sense_stride, s_row_stride, s_sense_stride, dtype);
+    if (rc != BP_OK) return rc;
+    return launch_status(bp::launch_sense_table_quantize(p, dtype, static_cast<hipStream_t>(stream)));
+}
+
+int bp_sense_table_dequantize(const void *q8, const void *scale8, void *table, int64_t rows, int nsenses, int d_out,
+                              int64_t t_row_stride, int64_t t_sense_stride, int64_t q_row_stride, int64_t q_sense_stride,
+                              int64_t s_row_stride, int64_t s_sense_stride, int dtype, bp_stream_t stream) {
+    bp::Mx8TableParams p{};
+    const int rc = mx8_table_params(p, table, q8, scale8, rows, nsenses, d_out, t_row_stride, t_sense_stride, q_row_stride,
+                                    q_sense_stride, s_row_stride, s_sense_stride, dtype);
+    if (rc != BP_OK) return rc;
+    return launch_status(bp::launch_sense_table_dequantize(p, dtype, static_cast<hipStream_t>(stream)));
+}
+
+int bp_sense_decode_mx8(const void *q, const void *k_new, void *k_cache, const void *q8, const void *scale8,
+                        int32_t *row_index, const int32_t *new_row, const int32_t *cache_seqlens, const float *key_weight,
+                        void *out, float *ws, int64_t ws_floats,
+                        int batch, int nsenses, int d_k, int d_out, int max_seqlen, int64_t table_rows,
+                        int64_t q_batch_stride, int64_t q_sense_stride,
+                        int64_t knew_batch_stride, int64_t knew_sense_stride,
+                        int64_t kc_batch_stride, int64_t kc_row_stride, int64_t kc_sense_stride,
+                        int64_t q8_row_stride, int64_t q8_sense_stride, int64_t s8_row_stride, int64_t s8_sense_stride,
+                        int64_t idx_batch_stride, int64_t o_batch_stride, int64_t kw_batch_stride, int64_t kw_sense_stride,
+                        float softmax_scale, int dtype, bp_stream_t stream) {
+    if (dtype != BP_DTYPE_F16 && dtype != BP_DTYPE_BF16) return BP_ERR_DTYPE;
+    if (d_k < 1 || d_k > bp::kWideMaxDk || d_k % 8 != 0) return BP_ERR_HEAD_DIM;
+    if (d_out < 1) return BP_ERR_DOUT;
+    if (d_out % 32 != 0 || d_out > 2048) return BP_ERR_SHAPE;
+    if (batch <= 0 || batch > 65535 || nsenses <= 0 || nsenses > 64 || max_seqlen <= 0 || table_rows <= 0
+        || table_rows > 0x7fffffffLL)
+        return BP_ERR_SHAPE;
+    if (q == nullptr || k_new == nullptr || k_cache == nullptr || q8 == nullptr || scale8 == nullptr || row_index == nullptr
+        || new_row == nullptr || cache_seqlens == nullptr || out == nullptr || ws == nullptr)
+        return BP_ERR_SHAPE;
+    if (!aligned16({q, k_new, k_cache, q8, out, ws})) return BP_ERR_SHAPE;
+    if (!strides8({q_batch_stride, q_sense_stride, knew_batch_stride, knew_sense_stride, kc_batch_stride, kc_row_stride,
+                   kc_sense_stride, o_batch_stride}))
+        return BP_ERR_SHAPE;
+    if (q8_row_stride % 16 != 0 || q8_sense_stride % 16 != 0 || q8_row_stride < d_out || q8_sense_stride < d_out
+        || s8_row_stride < d_out / 32 || s8_sense_stride < d_out / 32)
+        return BP_ERR_SHAPE;
+    if (key_weight != nullptr && (kw_sense_stride < max_seqlen || kw_batch_stride < max_seqlen)) return BP_ERR_SHAPE;
+    if (!scale_ok(softmax_scale)) return BP_ERR_SCALE;
+    if (ws_floats < bp_sense_decode_ws_floats(batch, nsenses, d_out, max_seqlen)) return BP_ERR_WORKSPACE;
+    bp::DecodeMx8Params pp{};
+    bp::DecodeParams &p = pp.d;
+    p.q = q; p.k_new = k_new; p.k_cache = k_cache; p.v = const_cast<void *>(q8);
+    p.q_bs = q_batch_stride; p.q_gs = q_sense_stride;
+    p.kn_bs = knew_batch_stride; p.kn_gs = knew_sense_stride;
+    p.kc_bs = kc_batch_stride; p.kc_rs = kc_row_stride; p.kc_gs = kc_sense_stride;
+    p.vc_rs = q8_row_stride; p.vc_gs = q8_sense_stride;
+    p.row_index = row_index; p.ri_bs = idx_batch_stride; p.new_row = new_row; p.table_rows = table_rows;
+    p.seqlens = cache_seqlens;
+    p.b = batch; p.groups = nsenses; p.dk = d_k; p.dv = d_out; p.max_seqlen = max_seqlen;
+    p.nsplit = bp::decode_nsplit(batch, nsenses, max_seqlen);
+    p.ws_acc = ws;
+    p.ws_ml = ws + (int64_t)batch * nsenses * p.nsplit * d_out;
+    p.o = out; p.o_bs = o_batch_stride;
+    p.scale_log2e = softmax_scale * bp::kLog2e;
+    if (key_weight != nullptr) { p.key_weight = key_weight; p.kw_bs = kw_batch_stride; p.kw_gs = kw_sense_stride; }
+    pp.scale8 = static_cast<const uint8_t *>(scale8); pp.s_rs = s8_row_stride; pp.s_gs = s8_sense_stride;
+    return launch_status(bp::launch_sense_decode_mx8(pp, dtype, static_cast<hipStream_t>(stream)));
+}
+
 int bp_sense_rows_dot(const void *table, const int32_t *row_index, const int32_t *new_row, const int32_t *cache_seqlens,
                       const void *vec, float *out,
                       int batch, int nsenses, int d_out, int max_seqlen, int64_t table_rows,

@@ -348,6 +348,27 @@ hipError_t launch_sense_decode(const DecodeParams &p, int dtype, hipStream_t str
 hipError_t launch_sense_decode_combine(const DecodeParams &p, int dtype, hipStream_t stream);
 hipError_t launch_sense_decode_weighted(const DecodeParams &p, int dtype, hipStream_t stream);
 
+// MXFP8 sense table (include/bp_hip.h, "MXFP8 sense table"): q8 holds E4M3 elements, scale8 one E8M0 byte per block of 32
+// columns.  sense_table_mx8.hip converts a 16-bit table to and from the pair; sense_decode_mx8.hip is bp_sense_decode's
+// step with the pair as its value stream.
+struct Mx8TableParams {
+    void *table;                      // 16-bit (rows, k, d): read by the quantiser, written by the dequantiser
+    uint8_t *q8, *scale8;
+    int64_t t_rs, t_gs;               // elements
+    int64_t q_rs, q_gs, s_rs, s_gs;   // bytes
+    int64_t rows;
+    int k, d;
+};
+hipError_t launch_sense_table_quantize(const Mx8TableParams &p, int dtype, hipStream_t stream);
+hipError_t launch_sense_table_dequantize(const Mx8TableParams &p, int dtype, hipStream_t stream);
+// d.v = q8 with d.vc_rs / d.vc_gs its row / sense strides in bytes; everything else as bp_sense_decode{,_weighted} fills it
+struct DecodeMx8Params {
+    DecodeParams d;
+    const uint8_t *scale8;
+    int64_t s_rs, s_gs;               // bytes
+};
+hipError_t launch_sense_decode_mx8(const DecodeMx8Params &p, int dtype, hipStream_t stream);
+
 // bp_sense_rows_dot (sense_rows_dot.hip): out[b, l, j] = table[row(b, j), l, :] . vec[b, :] for j = 0 .. seqlens[b]
 struct RowsDotParams {
     const void *table, *vec;

@@ -39,8 +39,11 @@ from src.utils.hf_convert import gpt2_trunk_state_dict, remap_state_dict_gpt2  #
 
 class BackpackConfig(GPT2Config):
 
-    def __init__(self, num_content_vectors=16, packed_train=False, **kwargs):
+    def __init__(self, num_content_vectors=16, packed_train=False, sense_table_dtype=None, **kwargs):
         self.num_content_vectors = num_content_vectors
+        # None | 'mxfp8': the cached whole-vocabulary sense table also kept in the MXFP8 block format (include/bp_hip.h) and
+        # rounded to the values that format holds; KV-cached decode steps then read the 8-bit twin (bp_sense_decode_mx8)
+        self.sense_table_dtype = sense_table_dtype
         # True: packed batches (cu_seqlens) are trainable -- BackpackModel._forward_packed records a backward through the packed
         # sense kernels instead of refusing gradients
         self.packed_train = packed_train
@@ -247,8 +250,12 @@ class _SenseTable:
     """The whole-vocabulary sense table of one content model and everything that decides whether it may be served.
     A plain object: it registers nothing with the model and is no part of its state dict."""
 
-    def __init__(self, content_model):
+    def __init__(self, content_model, mx8=False):
         self.content_model = content_model
+        # mx8: the rows hold exactly the values of their MXFP8 twin (q8, scale8), which shares their key, fingerprint and
+        # pinned lifetime and is rebuilt in place with them; None without it
+        self.mx8 = bool(mx8)
+        self.q8 = self.scale8 = None
         self.rows = None            # (V, k, d) storage; kept when the table goes stale: a rebuild lands in the SAME storage
         self.key = None             # `_version_key` of the parameters the rows were built from; None = stale (or no rows)
         self.fingerprint = None     # `key` + the sums of the parameter values, when the build was asked to `verify`
@@ -274,7 +281,7 @@ class _SenseTable:
         # training runs per position; do not hold 1-4 GB of stale rows -- unless a captured graph reads this storage
         self.invalidate()
         if not self.pinned:
-            self.rows = None
+            self.rows = self.q8 = self.scale8 = None
 
     def lookup(self, verify=False):
         """The rows, rebuilt in place first when the parameters moved on, or None: see BackpackModel.sense_table."""
@@ -300,6 +307,8 @@ class _SenseTable:
                 if self.rows is not None and (self.rows.shape, self.rows.dtype, self.rows.device) == \
                         (rows.shape, rows.dtype, rows.device):
                     rows = self.rows.copy_(rows)
+                if self.mx8:
+                    self._round_to_mx8(rows)
             except torch.OutOfMemoryError:
                 if not self.oom_warned:
                     warnings.warn('Backpack: not enough memory for the whole-vocabulary sense table; the forward runs '
@@ -310,6 +319,19 @@ class _SenseTable:
                 self.content_model.train(was_training)
         self.rows, self.key, self.fingerprint = rows, key, fingerprint
         return rows
+
+    def _round_to_mx8(self, rows):
+        """Quantise `rows` into the 8-bit twin (in place when it is there) and write the twin's values back into `rows`:
+        every reader of the 16-bit table then serves exactly what the 8-bit one encodes."""
+        if not rows.is_cuda:
+            self.q8, self.scale8 = bp_hip._eager_sense_table_quantize(rows)
+            bp_hip._eager_sense_table_dequantize(self.q8, self.scale8, rows.dtype, out=rows)
+        elif self.q8 is not None and self.q8.shape == rows.shape and self.q8.device == rows.device:
+            bp_hip.sense_table_quantize_into(rows, self.q8, self.scale8)
+            bp_hip.sense_table_dequantize(self.q8, self.scale8, rows.dtype, out=rows)
+        else:
+            self.q8, self.scale8 = bp_hip.sense_table_quantize(rows)
+            bp_hip.sense_table_dequantize(self.q8, self.scale8, rows.dtype, out=rows)
 
 
 class BackpackModel(GPTPreTrainedModel):
@@ -344,7 +366,12 @@ class BackpackModel(GPTPreTrainedModel):
         self.gpt2_model = GPTModel(config, **factory_kwargs)
         self.content_model = BackpackContentModule(config, self.num_content_vectors,
                                                    self.gpt2_model.embeddings, **factory_kwargs)
-        self._sense_table = _SenseTable(self.content_model)
+        self.sense_table_dtype = getattr(config, 'sense_table_dtype', None)
+        if self.sense_table_dtype not in (None, 'mxfp8'):
+            raise ValueError("sense_table_dtype must be None or 'mxfp8', got %r" % (self.sense_table_dtype,))
+        if self.sense_table_dtype == 'mxfp8' and config.n_embd % bp_hip.MX8_BLOCK != 0:
+            raise ValueError("sense_table_dtype='mxfp8' needs n_embd %% %d == 0, got %d" % (bp_hip.MX8_BLOCK, config.n_embd))
+        self._sense_table = _SenseTable(self.content_model, mx8=self.sense_table_dtype == 'mxfp8')
         self.embeddings = self.gpt2_model.embeddings   # shared with the contextualisation model
         self.contextualization_attn = ContextSelfAttn(self.num_content_vectors, config.n_embd,
                                                       use_hip=self.use_hip, **factory_kwargs)
@@ -650,6 +677,11 @@ class BackpackModel(GPTPreTrainedModel):
         if not self.fused_senses:
             return _eager_sense_decode(q, k_new, c.keys, table, c.rows, new_row, c.b0, lengths, scale,
                                        key_weight=key_weight).unsqueeze(1)
+        twin = self._sense_table
+        if twin.q8 is not None and table is twin.rows and \
+                bp_hip.sense_decode_mx8_supported(q, c.keys, twin.q8, twin.scale8, key_weight):
+            return bp_hip.sense_decode_mx8(q, k_new, c.keys[c.b0:c.b1], twin.q8, twin.scale8, c.rows[c.b0:c.b1], new_row,
+                                           lengths, scale, key_weight=key_weight).unsqueeze(1)
         if not bp_hip.sense_decode_supported(q, c.keys, table):
             raise RuntimeError(f'Backpack decode: bp_sense_decode does not take k = {q.shape[1]} senses of width '
                                f'{q.shape[2]} with {table.shape[2]} output columns (include/bp_hip.h)')
@@ -863,6 +895,12 @@ def _eager_sense_decode(q, k_new, key_cache, table, rows, new_row, b0, lengths, 
         weights = weights * torch.where(visible[:, None, :], key_weight, 0.0).to(weights.dtype)
     content = table[rows[b0:b0 + batch].long()]                            # (B, M, k, d)
     return torch.einsum('bls,bsld->bd', weights, content)
+
+
+def _eager_sense_decode_mx8(q, k_new, key_cache, q8, scale8, rows, new_row, b0, lengths, scale, key_weight=None):
+    """Eager restatement of bp_sense_decode_mx8: _eager_sense_decode on the table the MXFP8 pair stands for."""
+    table = bp_hip._eager_sense_table_dequantize(q8, scale8, q.dtype)
+    return _eager_sense_decode(q, k_new, key_cache, table, rows, new_row, b0, lengths, scale, key_weight=key_weight)
 
 
 def _combine_senses(contextualization, content):

@@ -72,7 +72,9 @@ extern "C" {
                               and one more: bp_segment_sum_rows, fp32 sums of 16-bit rows over the segments of a sorted index --
                               the gradient of the rows of a sense table that several positions read;
                               and three more: bp_sense_mix_dc_varlen / bp_sense_dp_slab_varlen / bp_sense_dq_dk_varlen, the
-                              backward of the sense mix on packed batches) */
+                              backward of the sense mix on packed batches;
+                              and three more: bp_sense_table_quantize / bp_sense_table_dequantize / bp_sense_decode_mx8, the
+                              MXFP8 twin of the sense table and the decode step that reads it) */
 
 /* element type of q/k/v/out/content tensors */
 #define BP_DTYPE_F16 0
@@ -735,6 +737,55 @@ int bp_sense_decode_weighted(const void *q, const void *k_new, void *k_cache, co
                              int64_t t_row_stride, int64_t t_sense_stride, int64_t idx_batch_stride,
                              int64_t o_batch_stride, int64_t kw_batch_stride, int64_t kw_sense_stride,
                              float softmax_scale, int dtype, bp_stream_t stream);
+
+/*
+ * MXFP8 sense table -- an 8-bit twin of a 16-bit sense table (rows, nsenses, d_out), d_out % 32 == 0, in the OCP MX block
+ * format:
+ *   q8       (rows, nsenses, d_out) bytes: OCP E4M3 elements (1 sign, 4 exponent, 3 mantissa bits, bias 7, largest finite
+ *            value 448, no infinities; the encoding of torch.float8_e4m3fn)
+ *   scale8   (rows, nsenses, d_out / 32) bytes: one E8M0 scale per block of 32 consecutive columns, byte s = 2^(s - 127)
+ * The value an element stands for is e4m3(q8) * 2^(scale8 - 127): at most 4 significant bits times a power of two, so it is
+ * exactly representable in bf16, and in fp16 whenever it is a multiple of 2^-24 below 65504.
+ * Quantisation of a block (the OCP MX rule): amax = its largest magnitude; the scale exponent is floor(log2(amax)) - 8 (8 =
+ * the E4M3 emax), held at -127 from below; every element is value * 2^-exponent, clamped in fp32 to +-448 and rounded to
+ * nearest even -- the clamp means that no NaN code comes from a finite input (elements between 448 and 512 times the scale
+ * saturate).  An all-zero block takes scale byte 127 and zero elements.  The answer for a non-finite input is undefined.
+ *
+ * bp_sense_table_quantize   table (16-bit, only read) -> q8, scale8;  bp_sense_table_dequantize   q8, scale8 -> table (the
+ * value above converted to the 16-bit type, round to nearest even: exact wherever the type holds it).
+ *   strides  t_* in elements (multiples of 8), q_* in bytes (multiples of 16), s_* in bytes; last strides 1; table and q8
+ *            16-byte aligned; no row of one operand overlaps another (every stride at least the row's length)
+ * 1 <= nsenses <= 64, d_out >= 1 (BP_ERR_DOUT), d_out % 32 == 0, rows <= 2^31 - 1 (BP_ERR_SHAPE), dtype BP_DTYPE_F16 / _BF16.
+ */
+int bp_sense_table_quantize(const void *table, void *q8, void *scale8, int64_t rows, int nsenses, int d_out,
+                            int64_t t_row_stride, int64_t t_sense_stride, int64_t q_row_stride, int64_t q_sense_stride,
+                            int64_t s_row_stride, int64_t s_sense_stride, int dtype, bp_stream_t stream);
+int bp_sense_table_dequantize(const void *q8, const void *scale8, void *table, int64_t rows, int nsenses, int d_out,
+                              int64_t t_row_stride, int64_t t_sense_stride, int64_t q_row_stride, int64_t q_sense_stride,
+                              int64_t s_row_stride, int64_t s_sense_stride, int dtype, bp_stream_t stream);
+
+/*
+ * bp_sense_decode_mx8 -- bp_sense_decode_weighted with the table read from its MXFP8 twin:
+ *   out[b,:] = sum_l sum_{j<=t} softmax_j(scale q[b,l,:].k_l(j)) key_weight[b,l,j] e4m3(q8[row(b,j),l,:]) 2^(scale8[..] - 127)
+ *   q8, scale8   as above, byte strides q8_row / q8_sense (multiples of 16, q8 16-byte aligned) and s8_row / s8_sense
+ *   key_weight   NULL: the plain form (the kw strides are then ignored)
+ * Every other operand, the append of key and row index, the clamps, the split, its fixed-order combine and the error
+ * codes are bp_sense_decode_weighted's; q, k_new, k_cache and out are 16-bit of type `dtype`; the workspace is sized by
+ * bp_sense_decode_ws_floats.  fp32 accumulation; bit-identical across calls.  The keys of a split are summed in another
+ * order than in bp_sense_decode, so the two agree to rounding on the dequantised table, not bit for bit.
+ * 1 <= nsenses <= 64, d_k % 8 == 0 and <= 640 (BP_ERR_HEAD_DIM), d_out >= 1 (BP_ERR_DOUT), d_out % 32 == 0 and <= 2048
+ * (BP_ERR_SHAPE).
+ */
+int bp_sense_decode_mx8(const void *q, const void *k_new, void *k_cache, const void *q8, const void *scale8,
+                        int32_t *row_index, const int32_t *new_row, const int32_t *cache_seqlens, const float *key_weight,
+                        void *out, float *ws, int64_t ws_floats,
+                        int batch, int nsenses, int d_k, int d_out, int max_seqlen, int64_t table_rows,
+                        int64_t q_batch_stride, int64_t q_sense_stride,
+                        int64_t knew_batch_stride, int64_t knew_sense_stride,
+                        int64_t kc_batch_stride, int64_t kc_row_stride, int64_t kc_sense_stride,
+                        int64_t q8_row_stride, int64_t q8_sense_stride, int64_t s8_row_stride, int64_t s8_sense_stride,
+                        int64_t idx_batch_stride, int64_t o_batch_stride, int64_t kw_batch_stride, int64_t kw_sense_stride,
+                        float softmax_scale, int dtype, bp_stream_t stream);
 
 /*
  * bp_sense_rows_dot -- dot products of the sense vectors of every cached position, and of the new one, with one vector

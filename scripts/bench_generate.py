@@ -7,7 +7,7 @@ generate(..., kv_cache=True) eagerly and with cg=True (one captured decode step 
                                      [--pick torch|device|torch,device] [--sample] [--temperature T] [--top-k K] [--top-p P]
                                      [--repetition-penalty R] [--eos ID] [--min-length L] [--stop-check-every N]
                                      [--variant NAME:option=value,...] [--repeats N] [--beams W[,W...]]
-                                     [--prompt-lengths LO:HI[:SEED]]
+                                     [--prompt-lengths LO:HI[:SEED]] [--sense-table-dtype mxfp8]
 
 --pick chooses how the next token is picked: `torch` is torch.argmax / torch.distributions.Categorical on the host side
 of the loop, `device` the bp_pick_token kernel (device_pick=True; with kv_cache and cg inside the captured step).  With
@@ -29,6 +29,10 @@ so that the padded width and the number of new tokens are those of the other pic
 every length equal to --prompt, i.e. the work of the pick without the argument through the new path; and the two again with
 packed_prefill=True, `ragged_packed` and `ragged_equal_packed`: the prefill over the prompts' own positions against the prefill
 over the padded width (with --max-length = --prompt + 2 one token is generated behind the prefill: the time is the prefill's).
+
+--sense-table-dtype mxfp8 adds the pick `mxfp8` that alternates with the others: the device pick on a second model of the same
+seed whose config asks for sense_table_dtype='mxfp8' (the cached table rounded to the MXFP8 format, cached steps through
+bp_sense_decode_mx8); only the `cached` sense_table mode differs from the default with it.
 
 --beams W[,W...] times beam search instead (its own line per sense_table mode): for every width W, beam_search(num_beams=W,
 cg=True) against the greedy device-pick leg generate(kv_cache=True, cg=True, device_pick=True) at the same number of rows
@@ -74,19 +78,28 @@ def main():
     ap.add_argument('--repeats', type=int, default=1)
     ap.add_argument('--beams', default=None, help='W[,W...]: time beam search against greedy at the same number of rows')
     ap.add_argument('--prompt-lengths', default=None, help='LO:HI[:SEED]: add the picks ragged and ragged_equal (kv legs only)')
+    ap.add_argument('--sense-table-dtype', default=None, choices=['mxfp8'], help='add the pick `mxfp8`: a second model with this config')
     a = ap.parse_args()
     from bench import MODELS
     from src.models.backpack import BackpackConfig, BackpackLMHeadModel
     dev = torch.device('cuda', 0)
-    cfg = BackpackConfig(vocab_size=50257, n_positions=max(a.max_length, 128), scale_attn_by_inverse_layer_idx=True,
-                         use_flash_attn=True, fused_bias_fc=True, fused_dense_gelu_dense=True, fused_dropout_add_ln=True,
-                         pad_vocab_size_multiple=8, **MODELS[a.model])
+    cfg_kw = dict(vocab_size=50257, n_positions=max(a.max_length, 128), scale_attn_by_inverse_layer_idx=True,
+                  use_flash_attn=True, fused_bias_fc=True, fused_dense_gelu_dense=True, fused_dropout_add_ln=True,
+                  pad_vocab_size_multiple=8, **MODELS[a.model])
+    cfg = BackpackConfig(**cfg_kw)
     torch.manual_seed(0)
     model = BackpackLMHeadModel(cfg, device=dev, dtype=torch.bfloat16).eval()
     ids = torch.randint(0, 50257, (a.batch, a.prompt), device=dev)
     extra = {}
     if a.intervention != 'none':
         model, extra = intervene(model, a.intervention, ids, (a.prompt + a.max_length) // 2)
+    twin = None
+    if a.sense_table_dtype:
+        if a.intervention != 'none' or a.beams:
+            raise SystemExit('--sense-table-dtype goes with neither --intervention nor --beams')
+        torch.manual_seed(0)
+        twin = BackpackLMHeadModel(BackpackConfig(sense_table_dtype=a.sense_table_dtype, **cfg_kw), device=dev,
+                                   dtype=torch.bfloat16).eval()
     legs = []
     if 'full' in a.legs.split(','):
         legs += [('eager_loop', False, False), ('graph_replay', True, False)]
@@ -94,6 +107,8 @@ def main():
         legs += [('kv_cache_eager', False, True), ('kv_cache_graph', True, True)]
     for mode in a.modes.split(','):   # content network per position (the reference's order) / cached whole-vocabulary table
         getattr(model, 'backpack_network', model).transformer.sense_table_mode = mode
+        if twin is not None:
+            twin.transformer.sense_table_mode = mode
         if a.beams:
             print(json.dumps(beam_legs(model, ids, a, mode)), flush=True)
             continue
@@ -101,7 +116,7 @@ def main():
                    new_tokens=a.max_length - 1 - a.prompt, sense_table=mode, **extra)
         outs = {}
         picks = a.pick.split(',')
-        plain = picks == ['torch'] and not a.sample and a.repeats == 1 and not a.variant and not a.prompt_lengths   # the line of earlier revisions, key for key
+        plain = picks == ['torch'] and not a.sample and a.repeats == 1 and not a.variant and not a.prompt_lengths and twin is None   # the line of earlier revisions, key for key
         if not plain:
             res.update(sample=a.sample, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p)
         options = dict(torch={}, device=dict(device_pick=True, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p))
@@ -136,16 +151,23 @@ def main():
             options['ragged_packed'] = dict(options['ragged'], packed_prefill=True)
             res['prompt_lengths']['sum'] = int(drawn.sum())
             picks = picks + ['ragged_equal', 'ragged', 'ragged_equal_packed', 'ragged_packed']
-        decode = model.sample if a.sample else model.generate
+        if twin is not None:
+            options[a.sense_table_dtype] = dict(options['device'])
+            res['sense_table_dtype_pick'] = a.sense_table_dtype
+            picks = picks + [a.sense_table_dtype]
+
+        def decode(*args, pick=None, **kw):
+            m = twin if pick == a.sense_table_dtype and twin is not None else model
+            return (m.sample if a.sample else m.generate)(*args, **kw)
         for key, cg, kv in legs:
             runs = {pick: [] for pick in picks}
             for pick in picks:                                               # warm-up (allocator, library handles)
-                decode(ids, max_length=a.max_length, cg=cg, kv_cache=kv, **options[pick])
+                decode(ids, max_length=a.max_length, cg=cg, kv_cache=kv, pick=pick, **options[pick])
             for _ in range(a.repeats):
                 for pick in picks:
                     torch.cuda.synchronize()
                     t0 = time.perf_counter()
-                    out = decode(ids, max_length=a.max_length, cg=cg, kv_cache=kv, **options[pick])
+                    out = decode(ids, max_length=a.max_length, cg=cg, kv_cache=kv, pick=pick, **options[pick])
                     torch.cuda.synchronize()
                     runs[pick].append((time.perf_counter() - t0) * 1e3)
                     outs[key if pick == picks[0] else key + '_' + pick] = out
