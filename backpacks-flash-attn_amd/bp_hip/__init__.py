@@ -99,6 +99,8 @@ SIGNATURES = {
     'bp_sense_table_dequantize': (_i32, [_ptr] * 3 + [_i64] + [_i32] * 2 + [_i64] * 6 + [_i32, _ptr]),
     'bp_sense_decode_mx8': (_i32, [_ptr] * 11 + [_i64] + [_i32] * 5 + [_i64] + [_i64] * 15 + [_f32, _i32, _ptr]),
     'bp_sense_rows_dot': (_i32, [_ptr] * 6 + [_i32] * 4 + [_i64] + [_i64] * 6 + [_i32, _ptr]),
+    'bp_sense_anneal_step_ws_floats': (_i64, [_i32] * 3),
+    'bp_sense_anneal_step': (_i32, [_ptr] * 11 + [_i64] + [_i32] * 4 + [_i64] * 3 + [_i64] * 14 + [_f32, _i32, _i32, _ptr]),
     'bp_pick_token': (_i32, [_ptr] * 6 + [_i32] * 2 + [_i64] * 3 + [_i32] * 2 + [_f32, _i32, _f32, _i32, _ptr]),
     'bp_pick_token_ctl': (_i32, [_ptr] * 7 + [_i32] * 2 + [_i64] * 3 + [_i32] * 2 + [_f32, _i32, _f32, _f32] + [_i32] * 4 + [_ptr]),
     'bp_pick_token_lim': (_i32, [_ptr] * 7 + [_i32] * 2 + [_i64] * 3 + [_i32] * 2 + [_f32, _i32, _f32, _f32] + [_i32] * 3
@@ -1774,6 +1776,71 @@ def sense_rows_dot(table, row_index, new_row, cache_seqlens, vec, out):
           out.data_ptr(), b, k, dout, max_s, table.shape[0], table.stride(0), table.stride(1), row_index.stride(0),
           vec.stride(0), out.stride(0), out.stride(1), _dtype_code(table))
     return out
+
+
+ANNEAL_STEP_MAX_LDS = 160 * 1024   # the new token's sense rows are staged in LDS (include/bp_hip.h, bp_sense_anneal_step)
+
+
+def sense_anneal_step_supported(table, emb):
+    """Whether bp_sense_anneal_step takes this sense table (rows, k, d_out) and LM head (vocab, d_out): sense_rows_dot's
+    limits, and the k x d_out block of one token fits the LDS staging (d_out <= 728 at 64 senses)."""
+    if not (table.is_cuda and emb.is_cuda) or table.dtype not in (torch.float16, torch.bfloat16) or emb.dtype != table.dtype:
+        return False
+    if table.dim() != 3 or emb.dim() != 2 or emb.shape[1] != table.shape[2]:
+        return False
+    k, dout = table.shape[1], table.shape[2]
+    return (1 <= k <= SENSE_DECODE_MAX_SENSES and dout % 8 == 0 and dout <= SENSE_DECODE_MAX_DOUT and _vec16(table, emb)
+            and round_up(k, 16) * (2 * dout + 1104) <= ANNEAL_STEP_MAX_LDS)
+
+
+def sense_anneal_step_ws_floats(batch, nsenses, max_seqlen):
+    """fp32 elements of bp_sense_anneal_step's workspace (one partial per sample, block of 16 positions and sense)."""
+    return int(lib().bp_sense_anneal_step_ws_floats(batch, nsenses, max_seqlen))
+
+
+def sense_anneal_step(table, row_index, new_row, cache_seqlens, emb, ids, new_ids, content_weights, sims, weight,
+                      annealing_scale, upweight_nearby):
+    """One cached step of the annealed sense weights, in place (C ABI bp_sense_anneal_step; the reference's mask_annealing +
+    create_content_soft_mask as running sums).  With L = cache_seqlens[b] and x = new_ids[b]: sims[b, l, i] gains
+    relu(table[row(b, i), l] . emb[x]) for the cached i < L, sims[b, l, L] becomes the new position's own sum over the tokens
+    0 .. L, ids[b, L] = x, and weight[b, l, i] = content_weights[ids[b, i], l] s + (1 - s) with s = sigmoid(6 -
+    annealing_scale sims[b, l, i]) (times 1 + i / 100 with upweight_nearby) for i <= L.  table (rows, k, d_out) and emb
+    (vocab, d_out) 16-bit; row_index (B, max_seqlen) int32; ids (B, max_seqlen) and new_ids (B,) int64; content_weights
+    (vocab, k) fp32; sims and weight (B, k, max_seqlen) fp32 with unit stride along the positions.  Nothing behind position
+    L is written; the lengths stay on the device.  Returns weight."""
+    _require_cuda(table, row_index, new_row, cache_seqlens, emb, ids, new_ids, content_weights, sims, weight)
+    if table.dim() != 3 or emb.dim() != 2 or emb.shape[1] != table.shape[2] or emb.dtype != table.dtype:
+        raise RuntimeError('bp_hip.sense_anneal_step: table must be (rows, k, d_out) and emb (vocab, d_out) of the same dtype')
+    b, (k, dout) = new_ids.shape[0], table.shape[1:]
+    if not sense_anneal_step_supported(table, emb):
+        raise RuntimeError(f'bp_hip.sense_anneal_step: bp_sense_anneal_step does not take {k} senses with {dout} output '
+                           'columns in this layout (include/bp_hip.h)')
+    if row_index.dim() != 2 or row_index.shape[0] != b or row_index.dtype != torch.int32 or row_index.stride(-1) != 1:
+        raise RuntimeError('bp_hip.sense_anneal_step: row_index must be (B, max_seqlen) int32, unit stride along the sequence')
+    max_s = row_index.shape[1]
+    for name, t in (('new_row', new_row), ('cache_seqlens', cache_seqlens)):
+        if t.shape != (b,) or t.dtype != torch.int32 or not t.is_contiguous():
+            raise RuntimeError(f'bp_hip.sense_anneal_step: {name} must be a contiguous (B,) int32 tensor')
+    if ids.shape != (b, max_s) or ids.dtype != torch.int64 or ids.stride(-1) != 1 or new_ids.shape != (b,) \
+            or new_ids.dtype != torch.int64:
+        raise RuntimeError(f'bp_hip.sense_anneal_step: ids must be ({b}, {max_s}) int64 with unit stride along the sequence '
+                           'and new_ids (B,) int64')
+    if content_weights.dim() != 2 or content_weights.shape[1] != k or content_weights.dtype != torch.float32 \
+            or content_weights.stride(-1) != 1:
+        raise RuntimeError(f'bp_hip.sense_anneal_step: content_weights must be a float32 (vocab, {k}) tensor, unit last stride')
+    for name, t in (('sims', sims), ('weight', weight)):
+        if not _decode_key_weight_ok(t, b, k, max_s):
+            raise RuntimeError(f'bp_hip.sense_anneal_step: {name} must be a float32 CUDA tensor of shape ({b}, {k}, {max_s}) '
+                               'with unit stride along the positions')
+    ws = _decode_ws(sense_anneal_step_ws_floats(b, k, max_s), table.device)
+    _call('bp_sense_anneal_step', table.device,
+          table.data_ptr(), row_index.data_ptr(), new_row.data_ptr(), cache_seqlens.data_ptr(), emb.data_ptr(),
+          ids.data_ptr(), new_ids.data_ptr(), content_weights.data_ptr(), sims.data_ptr(), weight.data_ptr(), ws.data_ptr(),
+          ws.numel(), b, k, dout, max_s, table.shape[0], emb.shape[0], content_weights.shape[0], table.stride(0),
+          table.stride(1), row_index.stride(0), emb.stride(0), ids.stride(0), ids.stride(1), new_ids.stride(0),
+          content_weights.stride(0), sims.stride(0), sims.stride(1), sims.stride(2), weight.stride(0), weight.stride(1),
+          weight.stride(2), float(annealing_scale), int(bool(upweight_nearby)), _dtype_code(table))
+    return weight
 
 
 # ---- token selection on the device (C ABI bp_pick_token, bp_pick_token_ctl, bp_pick_token_lim, bp_pick_token_lim_rows, bp_pick_token_phrases) ---------------------------------------------------------------------------------------------

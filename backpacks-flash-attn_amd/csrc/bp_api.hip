@@ -1204,6 +1204,54 @@ int bp_sense_rows_dot(const void *table, const int32_t *row_index, const int32_t
     return launch_status(bp::launch_sense_rows_dot(p, dtype, static_cast<hipStream_t>(stream)));
 }
 
+int64_t bp_sense_anneal_step_ws_floats(int batch, int nsenses, int max_seqlen) {
+    if (batch <= 0 || nsenses <= 0 || max_seqlen <= 0) return 0;
+    return (int64_t)batch * ((max_seqlen + bp::AS_POS - 1) / bp::AS_POS) * nsenses;
+}
+
+int bp_sense_anneal_step(const void *table, const int32_t *row_index, const int32_t *new_row, const int32_t *cache_seqlens,
+                         const void *emb, int64_t *ids, const int64_t *new_ids, const float *content_weights,
+                         float *sims, float *weight, float *ws, int64_t ws_floats,
+                         int batch, int nsenses, int d_out, int max_seqlen, int64_t table_rows, int64_t vocab,
+                         int64_t cw_rows, int64_t t_row_stride, int64_t t_sense_stride, int64_t idx_batch_stride,
+                         int64_t emb_row_stride, int64_t ids_batch_stride, int64_t ids_pos_stride, int64_t new_ids_stride,
+                         int64_t cw_row_stride, int64_t sims_batch_stride, int64_t sims_sense_stride,
+                         int64_t sims_pos_stride, int64_t weight_batch_stride, int64_t weight_sense_stride,
+                         int64_t weight_pos_stride, float annealing_scale, int upweight_nearby, int dtype,
+                         bp_stream_t stream) {
+    if (dtype != BP_DTYPE_F16 && dtype != BP_DTYPE_BF16) return BP_ERR_DTYPE;
+    if (d_out < 1) return BP_ERR_DOUT;
+    if (d_out % 8 != 0 || d_out > 2048) return BP_ERR_SHAPE;
+    if (batch <= 0 || batch > 65535 || nsenses <= 0 || nsenses > 64 || max_seqlen <= 0 || table_rows <= 0
+        || table_rows > 0x7fffffffLL || vocab <= 0 || cw_rows <= 0)
+        return BP_ERR_SHAPE;
+    if (table == nullptr || row_index == nullptr || new_row == nullptr || cache_seqlens == nullptr || emb == nullptr
+        || ids == nullptr || new_ids == nullptr || content_weights == nullptr || sims == nullptr || weight == nullptr
+        || ws == nullptr)
+        return BP_ERR_SHAPE;
+    if (!aligned16({table, emb})) return BP_ERR_SHAPE;
+    if (!strides8({t_row_stride, t_sense_stride, emb_row_stride})) return BP_ERR_SHAPE;
+    if (ids_pos_stride != 1 || sims_pos_stride != 1 || weight_pos_stride != 1) return BP_ERR_SHAPE;
+    // rows of different (sample, sense) pairs do not overlap
+    if (sims_sense_stride < max_seqlen || sims_batch_stride < max_seqlen || weight_sense_stride < max_seqlen
+        || weight_batch_stride < max_seqlen || ids_batch_stride < max_seqlen || cw_row_stride < nsenses)
+        return BP_ERR_SHAPE;
+    if (bp::anneal_step_lds_bytes(nsenses, d_out) > 160 * 1024) return BP_ERR_SHAPE;   // the staged block of the new token
+    if (!(annealing_scale == annealing_scale) || annealing_scale - annealing_scale != 0.f) return BP_ERR_SCALE;
+    if (ws_floats < bp_sense_anneal_step_ws_floats(batch, nsenses, max_seqlen)) return BP_ERR_WORKSPACE;
+    bp::AnnealStepParams p{};
+    p.table = table; p.emb = emb; p.row_index = row_index; p.new_row = new_row; p.seqlens = cache_seqlens;
+    p.ids = ids; p.new_ids = new_ids; p.cw = content_weights; p.sims = sims; p.weight = weight; p.ws = ws;
+    p.t_rs = t_row_stride; p.t_gs = t_sense_stride; p.ri_bs = idx_batch_stride; p.e_rs = emb_row_stride;
+    p.ids_bs = ids_batch_stride; p.nid_s = new_ids_stride; p.cw_rs = cw_row_stride;
+    p.s_bs = sims_batch_stride; p.s_gs = sims_sense_stride; p.w_bs = weight_batch_stride; p.w_gs = weight_sense_stride;
+    p.table_rows = table_rows; p.vocab = vocab; p.cw_rows = cw_rows;
+    p.b = batch; p.groups = nsenses; p.dout = d_out; p.max_seqlen = max_seqlen;
+    p.nblk = (max_seqlen + bp::AS_POS - 1) / bp::AS_POS;
+    p.upweight = upweight_nearby != 0; p.scale = annealing_scale;
+    return launch_status(bp::launch_sense_anneal_step(p, dtype, static_cast<hipStream_t>(stream)));
+}
+
 // ---- token selection (bp_pick_token, bp_pick_token_ctl, bp_pick_token_lim, bp_pick_token_lim_rows) ----
 
 // the argument checks of bp_pick_token and the parameters they admit; bp_pick_token_ctl adds its own behind them

@@ -379,6 +379,23 @@ struct RowsDotParams {
 };
 hipError_t launch_sense_rows_dot(const RowsDotParams &p, int dtype, hipStream_t stream);
 
+// bp_sense_anneal_step (sense_anneal_step.hip): the annealed sense weights of one cached step -- sims, weight and ids
+// advance in place at positions 0 .. seqlens[b]
+constexpr int AS_POS = 16;            // positions per workgroup; ws holds one fp32 per (sample, block of 16, sense)
+struct AnnealStepParams {
+    const void *table, *emb;          // 16-bit (table_rows, groups, dout) and (vocab, dout)
+    const int32_t *row_index, *new_row, *seqlens;
+    int64_t *ids;                     // (b, max_seqlen) token ids of the cached positions; entry seqlens[b] is written
+    const int64_t *new_ids;           // new token of sample b at new_ids[b * nid_s]
+    const float *cw;                  // (cw_rows, groups) fp32 content weights
+    float *sims, *weight, *ws;
+    int64_t t_rs, t_gs, ri_bs, e_rs, ids_bs, nid_s, cw_rs, s_bs, s_gs, w_bs, w_gs, table_rows, vocab, cw_rows;
+    int b, groups, dout, max_seqlen, nblk, upweight;
+    float scale;
+};
+int64_t anneal_step_lds_bytes(int nsenses, int d_out);
+hipError_t launch_sense_anneal_step(const AnnealStepParams &p, int dtype, hipStream_t stream);
+
 // bp_pick_token (pick_token.hip): one token per row of logits -- argmax, or a draw after temperature / top-k / top-p
 struct PickParams {
     const void *logits;          // (batch, vocab) 16-bit or fp32, element stride row_stride, last stride 1; only read

@@ -141,6 +141,11 @@ class WeightedBackpackLMHeadModel(_Intervened):
     position's weight depends on its own token alone.  The annealed form raises NotImplementedError: its similarity sums
     run over every position of the prefilled width, so they would count the pad columns behind a shorter prompt."""
 
+    # Set `wrapper.fused_anneal_step = True` before the prefill (the constructor keeps the reference's argument list): annealed
+    # cached steps are then ONE bp_sense_anneal_step call instead of bp_sense_rows_dot + torch ops.  HIP path only: a step
+    # raises where the kernel cannot serve; ignored without annealing.  Its own-row products stay fp32 before the relu.
+    fused_anneal_step = False
+
     def __init__(self, backpack_network, content_weights, target_weight, annealing_scale, anneal=True,
                  upweight_nearby=True):
         super().__init__()
@@ -169,7 +174,9 @@ class WeightedBackpackLMHeadModel(_Intervened):
             mb, ms = ip.max_batch_size, ip.max_sequence_len
             state = {'intervened_ids': ((mb, ms), torch.long), 'intervened_weight': ((mb, k, ms), torch.float32)}
             if self.anneal:
-                state.update(intervened_sims=((mb, k, ms), torch.float32), intervened_dots=((mb, k, ms), torch.float32))
+                state.update(intervened_sims=((mb, k, ms), torch.float32))
+                if not self.fused_anneal_step:
+                    state.update(intervened_dots=((mb, k, ms), torch.float32))
             for name, (shape, dtype) in state.items():
                 if name not in caches:
                     caches[name] = torch.zeros(shape, dtype=dtype, device=device)
@@ -195,6 +202,16 @@ class WeightedBackpackLMHeadModel(_Intervened):
         batch = input_ids.shape[0]
         b0, ms = ip.batch_size_offset, ip.max_sequence_len
         ids, weight, sims, dots, cw = self._cached_state(ip)
+        if self.anneal and self.fused_anneal_step:
+            emb_w = self.backpack_network.lm_head.weight
+            if not (model.fused_senses and table.is_cuda and bp_hip.sense_anneal_step_supported(table, emb_w)):
+                raise RuntimeError('fused_anneal_step = True needs the fused sense path on the GPU and a shape '
+                                   f'bp_sense_anneal_step takes (include/bp_hip.h); got fused_senses={model.fused_senses}, '
+                                   f'a {table.device.type} table of {table.shape[1]} senses with {table.shape[2]} output '
+                                   'columns: leave the flag off')
+            return bp_hip.sense_anneal_step(table, rows, new_row, lengths, emb_w, ids[b0:b0 + batch], input_ids[:, 0], cw,
+                                            sims[b0:b0 + batch], weight[b0:b0 + batch], self.annealing_scale,
+                                            self.upweight_nearby)
         sample = torch.arange(b0, b0 + batch, device=input_ids.device)
         at = lengths.long()
         ids[sample, at] = input_ids[:, 0]

@@ -74,7 +74,9 @@ extern "C" {
                               and three more: bp_sense_mix_dc_varlen / bp_sense_dp_slab_varlen / bp_sense_dq_dk_varlen, the
                               backward of the sense mix on packed batches;
                               and three more: bp_sense_table_quantize / bp_sense_table_dequantize / bp_sense_decode_mx8, the
-                              MXFP8 twin of the sense table and the decode step that reads it) */
+                              MXFP8 twin of the sense table and the decode step that reads it;
+                              and one more: bp_sense_anneal_step with bp_sense_anneal_step_ws_floats, the annealed sense
+                              weights of a cached step in one fused update) */
 
 /* element type of q/k/v/out/content tensors */
 #define BP_DTYPE_F16 0
@@ -805,6 +807,45 @@ int bp_sense_rows_dot(const void *table, const int32_t *row_index, const int32_t
                       int batch, int nsenses, int d_out, int max_seqlen, int64_t table_rows,
                       int64_t t_row_stride, int64_t t_sense_stride, int64_t idx_batch_stride, int64_t vec_batch_stride,
                       int64_t o_batch_stride, int64_t o_sense_stride, int dtype, bp_stream_t stream);
+
+/*
+ * bp_sense_anneal_step -- the annealed sense weights of one KV-cached step in two launches: what
+ * WeightedBackpackLMHeadModel(anneal=True).step_key_weight (src/models/intervened_models.py) computes from
+ * bp_sense_rows_dot and torch ops, i.e. the running form of the reference's mask_annealing and create_content_soft_mask
+ * (training/src/models/intervened_models.py:29-53, :9-20).  Per sample b, with L = cache_seqlens[b] clamped to
+ * [0, max_seqlen - 1], x_L = new_ids[b], row(b,j) = row_index[b,j] for j < L and new_row[b] for j == L (clamped as unsigned to
+ * the last table row, as in bp_sense_rows_dot), T the table, E the LM head `emb`; token ids are clamped the same unsigned way
+ * to the rows of `emb` and of `content_weights`:
+ *   i <  L:   sims[b,l,i] += relu(T[row(b,i),l,:] . E[x_L])
+ *   i == L:   sims[b,l,L]  = relu(T[new_row[b],l,:] . E[x_L]) + sum_{j<L} relu(T[new_row[b],l,:] . E[ids[b,j]])
+ *   ids[b,L] = x_L
+ *   i <= L:   s = sigmoid(6 - annealing_scale sims[b,l,i]);  upweight_nearby != 0: s *= 1 + float(i) / 100
+ *             weight[b,l,i] = content_weights[ids[b,i], l] s + (1 - s)
+ *   table (table_rows, nsenses, d_out) and emb (vocab, d_out)   16-bit of type `dtype`, last stride 1, only read
+ *   ids          int64 (batch, max_seqlen), batch stride ids_batch >= max_seqlen; new_ids int64, sample b at new_ids[b new_ids_stride]
+ *   content_weights   fp32 (cw_rows, nsenses), row stride cw_row >= nsenses, only read
+ *   sims, weight fp32 (batch, nsenses, max_seqlen), element strides *_batch / *_sense (each >= max_seqlen); nothing at
+ *                positions > L is written, in sims, weight or ids
+ *   ws           bp_sense_anneal_step_ws_floats(batch, nsenses, max_seqlen) floats (BP_ERR_WORKSPACE); needs no zeroing
+ *   ids_pos / sims_pos / weight_pos   the strides along the sequence: they must be 1 (BP_ERR_SHAPE)
+ * All products and sums are fp32 (the own-row products are not rounded to 16 bits before the relu, unlike the torch
+ * path); no atomics and a fixed order: bit-identical across calls from the same state.  The lengths are read on the device
+ * and the grid depends on max_seqlen alone, so one captured graph serves every later step.
+ * 1 <= nsenses <= 64, d_out >= 1 (BP_ERR_DOUT), d_out % 8 == 0 and <= 2048, table and emb 16-byte aligned with strides that
+ * are multiples of 8, and the new token's rows staged in LDS: 16 ceil(nsenses / 16) (2 d_out + 1104) bytes <= 160 KB, i.e.
+ * d_out <= 728 at 64 senses, <= 2008 at 32 and any d_out at 16 or fewer (all BP_ERR_SHAPE); annealing_scale finite (BP_ERR_SCALE).
+ */
+int64_t bp_sense_anneal_step_ws_floats(int batch, int nsenses, int max_seqlen);
+int bp_sense_anneal_step(const void *table, const int32_t *row_index, const int32_t *new_row, const int32_t *cache_seqlens,
+                         const void *emb, int64_t *ids, const int64_t *new_ids, const float *content_weights,
+                         float *sims, float *weight, float *ws, int64_t ws_floats,
+                         int batch, int nsenses, int d_out, int max_seqlen, int64_t table_rows, int64_t vocab,
+                         int64_t cw_rows, int64_t t_row_stride, int64_t t_sense_stride, int64_t idx_batch_stride,
+                         int64_t emb_row_stride, int64_t ids_batch_stride, int64_t ids_pos_stride, int64_t new_ids_stride,
+                         int64_t cw_row_stride, int64_t sims_batch_stride, int64_t sims_sense_stride,
+                         int64_t sims_pos_stride, int64_t weight_batch_stride, int64_t weight_sense_stride,
+                         int64_t weight_pos_stride, float annealing_scale, int upweight_nearby, int dtype,
+                         bp_stream_t stream);
 
 /*
  * bp_pick_token -- the next token of every row of logits, chosen on the device: the pick of a decode step (the

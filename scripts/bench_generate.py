@@ -43,7 +43,9 @@ issued from Python (the `*_host_issue_us` keys: at these sizes the host's cost o
 --intervention wraps the model in the control-experiment classes of src/models/intervened_models.py (seeded
 content_weights in [0, 3); for the annealed form a scale of 6 / median of the similarity sums at half the final length, so
 that the scores are not saturated; eight replaced tokens, four of them in the prompt) and times the same legs on the
-wrapper."""
+wrapper.  --fused-anneal-step (with weighted-anneal) adds the pick `fused_anneal` that alternates with the others: the first
+pick's call on a second wrapper of the same network with fused_anneal_step = True (bp_sense_anneal_step); `--fused-anneal-step
+only` times that wrapper alone, for a kernel trace of its own."""
 import argparse
 import json
 import os
@@ -79,6 +81,9 @@ def main():
     ap.add_argument('--beams', default=None, help='W[,W...]: time beam search against greedy at the same number of rows')
     ap.add_argument('--prompt-lengths', default=None, help='LO:HI[:SEED]: add the picks ragged and ragged_equal (kv legs only)')
     ap.add_argument('--sense-table-dtype', default=None, choices=['mxfp8'], help='add the pick `mxfp8`: a second model with this config')
+    ap.add_argument('--fused-anneal-step', nargs='?', const='alternate', default=None, choices=['alternate', 'only'],
+                    help='with --intervention weighted-anneal: add the pick `fused_anneal`, the same wrapper with '
+                         'fused_anneal_step = True, alternating with the others; `only`: time that wrapper alone (for a trace)')
     a = ap.parse_args()
     from bench import MODELS
     from src.models.backpack import BackpackConfig, BackpackLMHeadModel
@@ -93,6 +98,16 @@ def main():
     extra = {}
     if a.intervention != 'none':
         model, extra = intervene(model, a.intervention, ids, (a.prompt + a.max_length) // 2)
+    fused = None
+    if a.fused_anneal_step:
+        if a.intervention != 'weighted-anneal':
+            raise SystemExit('--fused-anneal-step goes with --intervention weighted-anneal')
+        from src.models.intervened_models import WeightedBackpackLMHeadModel
+        fused = WeightedBackpackLMHeadModel(model.backpack_network, model.content_weights, None, model.annealing_scale,
+                                            anneal=True).eval()
+        fused.fused_anneal_step = True
+        if a.fused_anneal_step == 'only':
+            model, fused, extra = fused, None, dict(extra, fused_anneal_step=True)
     twin = None
     if a.sense_table_dtype:
         if a.intervention != 'none' or a.beams:
@@ -116,7 +131,7 @@ def main():
                    new_tokens=a.max_length - 1 - a.prompt, sense_table=mode, **extra)
         outs = {}
         picks = a.pick.split(',')
-        plain = picks == ['torch'] and not a.sample and a.repeats == 1 and not a.variant and not a.prompt_lengths and twin is None   # the line of earlier revisions, key for key
+        plain = picks == ['torch'] and not a.sample and a.repeats == 1 and not a.variant and not a.prompt_lengths and twin is None and fused is None   # the line of earlier revisions, key for key
         if not plain:
             res.update(sample=a.sample, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p)
         options = dict(torch={}, device=dict(device_pick=True, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p))
@@ -155,9 +170,12 @@ def main():
             options[a.sense_table_dtype] = dict(options['device'])
             res['sense_table_dtype_pick'] = a.sense_table_dtype
             picks = picks + [a.sense_table_dtype]
+        if fused is not None:                          # the first pick's call on the wrapper with the fused weight update
+            options['fused_anneal'] = dict(options[picks[0]])
+            picks = picks + ['fused_anneal']
 
         def decode(*args, pick=None, **kw):
-            m = twin if pick == a.sense_table_dtype and twin is not None else model
+            m = twin if pick == a.sense_table_dtype and twin is not None else fused if pick == 'fused_anneal' else model
             return (m.sample if a.sample else m.generate)(*args, **kw)
         for key, cg, kv in legs:
             runs = {pick: [] for pick in picks}
