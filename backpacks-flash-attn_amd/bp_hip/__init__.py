@@ -98,6 +98,8 @@ SIGNATURES = {
     'bp_sense_table_quantize': (_i32, [_ptr] * 3 + [_i64] + [_i32] * 2 + [_i64] * 6 + [_i32, _ptr]),
     'bp_sense_table_dequantize': (_i32, [_ptr] * 3 + [_i64] + [_i32] * 2 + [_i64] * 6 + [_i32, _ptr]),
     'bp_sense_decode_mx8': (_i32, [_ptr] * 11 + [_i64] + [_i32] * 5 + [_i64] + [_i64] * 15 + [_f32, _i32, _ptr]),
+    'bp_flash_decode_mx8': (_i32, [_ptr] * 8 + [_i64] + [_i32] * 4 + [_i64] * 11 + [_f32, _i32, _ptr]),
+    'bp_kv_cache_quantize': (_i32, [_ptr] * 3 + [_i32, _i32, _i64] + [_i32] * 3 + [_i64] * 6 + [_i32, _ptr]),
     'bp_sense_rows_dot': (_i32, [_ptr] * 6 + [_i32] * 4 + [_i64] + [_i64] * 6 + [_i32, _ptr]),
     'bp_sense_anneal_step_ws_floats': (_i64, [_i32] * 3),
     'bp_sense_anneal_step': (_i32, [_ptr] * 11 + [_i64] + [_i32] * 4 + [_i64] * 3 + [_i64] * 14 + [_f32, _i32, _i32, _ptr]),
@@ -1739,6 +1741,126 @@ def sense_decode_mx8(q, k_new, k_cache, q8, scale8, row_index, new_row, cache_se
           k_cache.stride(0), k_cache.stride(1), k_cache.stride(2), q8.stride(0), q8.stride(1), scale8.stride(0),
           scale8.stride(1), row_index.stride(0), out.stride(0), kw[1], kw[2], float(scale), _dtype_code(q))
     return out
+
+
+# ---- MXFP8 KV cache of the trunk (C ABI bp_flash_decode_mx8 / bp_kv_cache_quantize) ---------------------------------------
+# One uint8 tensor (max_batch, max_seqlen, row_bytes) per layer; a position's row = K elements (H, D), V elements (H, D),
+# K scales (H, D / 32), V scales (H, D / 32), rounded up to 16 bytes (include/bp_hip.h, "MXFP8 KV cache").
+
+KV_MX8_MAX_HEAD_DIM = 128
+
+
+def _kv_mx8_used_bytes(nheads, head_dim):
+    return 2 * nheads * head_dim + 2 * nheads * (head_dim // MX8_BLOCK)
+
+
+def kv_cache_mx8_row_bytes(nheads, head_dim):
+    """Bytes of one position of an MXFP8 KV cache: elements and scales of K and V, rounded up to a multiple of 16."""
+    if head_dim % MX8_BLOCK != 0:
+        raise RuntimeError(f'bp_hip: an MXFP8 KV cache needs head_dim % {MX8_BLOCK} == 0, got {head_dim}')
+    return round_up(_kv_mx8_used_bytes(nheads, head_dim), 16)
+
+
+def _kv_mx8_cache_ok(cache, nheads, head_dim):
+    return (cache.dim() == 3 and cache.dtype == torch.uint8 and cache.stride(2) == 1 and head_dim % MX8_BLOCK == 0
+            and cache.shape[2] >= kv_cache_mx8_row_bytes(nheads, head_dim) and cache.data_ptr() % 16 == 0
+            and cache.stride(0) % 16 == 0 and cache.stride(1) % 16 == 0)
+
+
+def _eager_kv_cache_quantize(kv):
+    """Torch twin of kv_cache_quantize (any device): kv (..., 2, H, D) -> uint8 rows (..., row_bytes) in the cache's layout,
+    pad bytes zero."""
+    h, d = kv.shape[-2:]
+    lead = kv.shape[:-3]
+    q8, scale8 = _eager_sense_table_quantize(kv.reshape(-1, 2 * h, d))
+    rows = torch.zeros((q8.shape[0], kv_cache_mx8_row_bytes(h, d)), dtype=torch.uint8, device=kv.device)
+    rows[:, :2 * h * d] = q8.flatten(1)
+    rows[:, 2 * h * d:_kv_mx8_used_bytes(h, d)] = scale8.flatten(1)
+    return rows.reshape(*lead, -1)
+
+
+def _eager_kv_cache_dequantize(rows, nheads, head_dim, dtype):
+    """Torch twin of the kernels' read (any device): uint8 rows (..., row_bytes) -> (..., 2, H, D) of `dtype` (fp32 too)."""
+    lead, hd = rows.shape[:-1], nheads * head_dim
+    flat = rows.reshape(-1, rows.shape[-1])
+    q8 = flat[:, :2 * hd].reshape(-1, 2 * nheads, head_dim)
+    scale8 = flat[:, 2 * hd:_kv_mx8_used_bytes(nheads, head_dim)].reshape(-1, 2 * nheads, head_dim // MX8_BLOCK)
+    return _eager_sense_table_dequantize(q8, scale8, dtype).reshape(*lead, 2, nheads, head_dim)
+
+
+def flash_decode_mx8_supported(q, cache):
+    """Whether bp_flash_decode_mx8 takes these operands: 16-bit CUDA q (B, H, D), head_dim % 32 == 0 and <= 128, a uint8
+    cache (B, max_seqlen, >= row_bytes) with 16-byte aligned rows."""
+    if not (q.is_cuda and cache.is_cuda) or q.dtype not in (torch.float16, torch.bfloat16) or q.dim() != 3:
+        return False
+    h, d = q.shape[1:]
+    return d <= KV_MX8_MAX_HEAD_DIM and _kv_mx8_cache_ok(cache, h, d) and _vec16(q)
+
+
+def flash_decode_mx8(q, k_new, v_new, cache, cache_seqlens, softmax_scale=None, out=None, return_lse=False):
+    """flash_decode on an MXFP8 KV cache: cache (B, max_seqlen, row_bytes) uint8 (already offset to the batch rows of this
+    call).  k_new / v_new are quantised by the MX block rule and stored into row cache_seqlens[b]; the query attends to the
+    rounded values (C ABI bp_flash_decode_mx8).  Everything else as flash_decode."""
+    _require_cuda(q, k_new, v_new, cache, cache_seqlens)
+    if q.dim() != 3 or k_new.shape != q.shape or v_new.shape != q.shape:
+        raise RuntimeError('bp_hip.flash_decode_mx8: q, k_new, v_new must be (B, H, D) of one shape')
+    b, h, d = q.shape
+    if k_new.dtype != q.dtype or v_new.dtype != q.dtype:
+        raise RuntimeError('bp_hip.flash_decode_mx8: q, k_new and v_new dtypes differ')
+    if d % MX8_BLOCK != 0 or d > KV_MX8_MAX_HEAD_DIM:
+        raise RuntimeError(f'bp_hip.flash_decode_mx8: head_dim % {MX8_BLOCK} == 0 and <= {KV_MX8_MAX_HEAD_DIM}, got {d}')
+    if cache.dim() != 3 or cache.shape[0] != b or not _kv_mx8_cache_ok(cache, h, d):
+        raise RuntimeError(f'bp_hip.flash_decode_mx8: the cache must be uint8 (B, max_seqlen, row_bytes) = ({b}, *, >= '
+                           f'{kv_cache_mx8_row_bytes(h, d)}) with 16-byte aligned rows, got {cache.dtype} {tuple(cache.shape)}')
+    if cache_seqlens.shape != (b,) or cache_seqlens.dtype != torch.int32 or not cache_seqlens.is_contiguous():
+        raise RuntimeError('bp_hip.flash_decode_mx8: cache_seqlens must be a contiguous (B,) int32 tensor')
+    scale = softmax_scale or d ** -0.5
+    max_s = cache.shape[1]
+    if out is None:
+        out = torch.empty((b, h, d), dtype=q.dtype, device=q.device)
+    if out.dtype != q.dtype or out.shape != q.shape:
+        raise RuntimeError('bp_hip.flash_decode_mx8: out must be (B, H, D) of q\'s dtype')
+    lse = torch.empty((b, h), dtype=torch.float32, device=q.device) if return_lse else None
+    ws = _decode_ws(lib().bp_flash_decode_ws_floats(b, h, d, max_s), q.device)
+    _call('bp_flash_decode_mx8', q.device,
+          q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(), cache.data_ptr(), cache_seqlens.data_ptr(),
+          out.data_ptr(), lse.data_ptr() if lse is not None else None, ws.data_ptr(), ws.numel(),
+          b, h, d, max_s, q.stride(0), q.stride(1), k_new.stride(0), k_new.stride(1), v_new.stride(0), v_new.stride(1),
+          cache.stride(0), cache.stride(1), out.stride(0), out.stride(1), h, float(scale), _dtype_code(q))
+    return (out, lse) if return_lse else out
+
+
+def kv_cache_quantize(kv, cache, cu_seqlens=None, max_seqlen=None):
+    """The prefill's fill of an MXFP8 KV cache (C ABI bp_kv_cache_quantize): kv (B, S, 2, H, D) -- a strided view such as
+    qkv[:, :, 1:] -- goes to cache[b, 0:S); with cu_seqlens (B + 1,) int32 on the device and max_seqlen, kv is the packed
+    (total, 2, H, D) view and sample b's rows go to cache[b, 0:len_b).  cache (B, positions, row_bytes) uint8, a batch slice
+    of a layer cache.  Nothing else of the cache is written; cu_seqlens is read on the device only."""
+    _require_cuda(kv, cache, cu_seqlens)
+    packed = cu_seqlens is not None
+    if kv.dim() != (4 if packed else 5) or kv.shape[-3] != 2 or kv.stride(-1) != 1 or kv.dtype not in (torch.float16, torch.bfloat16):
+        raise RuntimeError('bp_hip.kv_cache_quantize: kv must be 16-bit (B, S, 2, H, D), or (total, 2, H, D) with cu_seqlens, '
+                           'unit last stride')
+    h, d = kv.shape[-2:]
+    if packed:
+        if cu_seqlens.dim() != 1 or cu_seqlens.numel() < 2 or cu_seqlens.dtype != torch.int32 or not cu_seqlens.is_contiguous():
+            raise RuntimeError('bp_hip.kv_cache_quantize: cu_seqlens must be a contiguous (batch + 1,) int32 tensor')
+        if max_seqlen is None:
+            raise RuntimeError('bp_hip.kv_cache_quantize: a packed source needs max_seqlen')
+        batch, seqlen, total, strides = cu_seqlens.numel() - 1, int(max_seqlen), kv.shape[0], (0,) + tuple(kv.stride()[:3])
+    else:
+        batch, seqlen, total, strides = kv.shape[0], kv.shape[1], 0, tuple(kv.stride()[:4])
+    if d % MX8_BLOCK != 0 or d > KV_MX8_MAX_HEAD_DIM:
+        raise RuntimeError(f'bp_hip.kv_cache_quantize: head_dim % {MX8_BLOCK} == 0 and <= {KV_MX8_MAX_HEAD_DIM}, got {d}')
+    if cache.dim() != 3 or cache.shape[0] != batch or not _kv_mx8_cache_ok(cache, h, d) or cache.device != kv.device:
+        raise RuntimeError(f'bp_hip.kv_cache_quantize: the cache must be uint8 (B, positions, row_bytes) = ({batch}, *, >= '
+                           f'{kv_cache_mx8_row_bytes(h, d)}) with 16-byte aligned rows, got {cache.dtype} {tuple(cache.shape)}')
+    if not _vec16(kv):
+        raise RuntimeError('bp_hip.kv_cache_quantize: kv needs a 16-byte aligned base and strides that are multiples of 8')
+    if batch == 0 or kv.numel() == 0:
+        return cache
+    _call('bp_kv_cache_quantize', kv.device, kv.data_ptr(), cache.data_ptr(), cu_seqlens.data_ptr() if packed else None,
+          batch, seqlen, total, h, d, cache.shape[1], *strides, cache.stride(0), cache.stride(1), _dtype_code(kv))
+    return cache
 
 
 def sense_rows_dot_supported(table, vec):

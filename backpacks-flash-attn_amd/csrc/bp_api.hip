@@ -10,6 +10,7 @@
 #include "../../include/bp_hip.h"
 #include "bp_common.h"
 #include "bp_kernels.h"
+#include "mx8_block.h"
 
 namespace {
 
@@ -1177,6 +1178,79 @@ int bp_sense_decode_mx8(const void *q, const void *k_new, void *k_cache, const v
     if (key_weight != nullptr) { p.key_weight = key_weight; p.kw_bs = kw_batch_stride; p.kw_gs = kw_sense_stride; }
     pp.scale8 = static_cast<const uint8_t *>(scale8); pp.s_rs = s8_row_stride; pp.s_gs = s8_sense_stride;
     return launch_status(bp::launch_sense_decode_mx8(pp, dtype, static_cast<hipStream_t>(stream)));
+}
+
+// ---- MXFP8 KV cache of the trunk (bp_flash_decode_mx8 / bp_kv_cache_quantize) ----
+
+// what both entry points ask of the byte cache: 16-byte aligned base, strides multiples of 16, a row stride that holds a row
+static int kv_mx8_cache_ok(const void *cache, int nheads, int head_dim, int64_t batch_stride, int64_t row_stride) {
+    if (!aligned16(cache) || batch_stride % 16 != 0 || row_stride % 16 != 0 || batch_stride < 0) return BP_ERR_SHAPE;
+    if (row_stride < bp::kv_mx8_row_bytes(nheads, head_dim)) return BP_ERR_SHAPE;
+    return BP_OK;
+}
+
+int bp_flash_decode_mx8(const void *q, const void *k_new, const void *v_new, void *kv_cache, const int32_t *cache_seqlens,
+                        void *out, float *softmax_lse, float *ws, int64_t ws_floats,
+                        int batch, int nheads, int head_dim, int max_seqlen,
+                        int64_t q_batch_stride, int64_t q_head_stride,
+                        int64_t knew_batch_stride, int64_t knew_head_stride,
+                        int64_t vnew_batch_stride, int64_t vnew_head_stride,
+                        int64_t cache_batch_stride, int64_t cache_row_stride,
+                        int64_t o_batch_stride, int64_t o_head_stride, int64_t lse_batch_stride,
+                        float softmax_scale, int dtype, bp_stream_t stream) {
+    if (dtype != BP_DTYPE_F16 && dtype != BP_DTYPE_BF16) return BP_ERR_DTYPE;
+    if (head_dim < 32 || head_dim > 128 || head_dim % 32 != 0) return BP_ERR_HEAD_DIM;
+    if (batch <= 0 || batch > 65535 || nheads <= 0 || nheads > 65535 || max_seqlen <= 0) return BP_ERR_SHAPE;
+    if (q == nullptr || k_new == nullptr || v_new == nullptr || kv_cache == nullptr || cache_seqlens == nullptr
+        || out == nullptr || ws == nullptr)
+        return BP_ERR_SHAPE;
+    if (!aligned16({q, k_new, v_new, out, ws})) return BP_ERR_SHAPE;
+    if (!strides8({q_batch_stride, q_head_stride, knew_batch_stride, knew_head_stride, vnew_batch_stride,
+                   vnew_head_stride, o_batch_stride, o_head_stride}))
+        return BP_ERR_SHAPE;
+    if (kv_mx8_cache_ok(kv_cache, nheads, head_dim, cache_batch_stride, cache_row_stride) != BP_OK) return BP_ERR_SHAPE;
+    if (softmax_lse != nullptr && lse_batch_stride < nheads) return BP_ERR_SHAPE;
+    if (!scale_ok(softmax_scale)) return BP_ERR_SCALE;
+    if (ws_floats < bp_flash_decode_ws_floats(batch, nheads, head_dim, max_seqlen)) return BP_ERR_WORKSPACE;
+    bp::KvDecodeMx8Params pp{};
+    bp::DecodeParams &p = pp.d;
+    p.q = q; p.k_new = k_new; p.v_new = v_new;
+    p.q_bs = q_batch_stride; p.q_gs = q_head_stride;
+    p.kn_bs = knew_batch_stride; p.kn_gs = knew_head_stride;
+    p.vn_bs = vnew_batch_stride; p.vn_gs = vnew_head_stride;
+    p.seqlens = cache_seqlens;
+    p.b = batch; p.groups = nheads; p.dk = p.dv = head_dim; p.max_seqlen = max_seqlen;
+    p.nsplit = bp::decode_nsplit(batch, nheads, max_seqlen);
+    p.ws_acc = ws;
+    p.ws_ml = ws + (int64_t)batch * nheads * p.nsplit * head_dim;
+    p.o = out; p.o_bs = o_batch_stride; p.o_gs = o_head_stride;
+    p.lse = softmax_lse; p.lse_bs = lse_batch_stride;
+    p.scale_log2e = softmax_scale * bp::kLog2e;
+    pp.cache = static_cast<uint8_t *>(kv_cache); pp.c_bs = cache_batch_stride; pp.c_rs = cache_row_stride;
+    return launch_status(bp::launch_flash_decode_mx8(pp, dtype, static_cast<hipStream_t>(stream)));
+}
+
+int bp_kv_cache_quantize(const void *kv, void *kv_cache, const int32_t *cu_seqlens, int batch, int seqlen, int64_t total_rows,
+                         int nheads, int head_dim, int max_positions,
+                         int64_t kv_batch_stride, int64_t kv_row_stride, int64_t kv_two_stride, int64_t kv_head_stride,
+                         int64_t cache_batch_stride, int64_t cache_row_stride, int dtype, bp_stream_t stream) {
+    if (dtype != BP_DTYPE_F16 && dtype != BP_DTYPE_BF16) return BP_ERR_DTYPE;
+    if (head_dim < 32 || head_dim > 128 || head_dim % 32 != 0) return BP_ERR_HEAD_DIM;
+    if (batch <= 0 || batch > 65535 || nheads <= 0 || nheads > 65535 || seqlen < 0 || max_positions < 0 || total_rows < 0)
+        return BP_ERR_SHAPE;
+    if (kv == nullptr || kv_cache == nullptr || !aligned16(kv)) return BP_ERR_SHAPE;
+    if (cu_seqlens != nullptr && reinterpret_cast<uintptr_t>(cu_seqlens) % 4) return BP_ERR_SHAPE;
+    if (!strides8({kv_batch_stride, kv_row_stride, kv_two_stride, kv_head_stride}) || kv_head_stride < head_dim)
+        return BP_ERR_SHAPE;
+    if (kv_mx8_cache_ok(kv_cache, nheads, head_dim, cache_batch_stride, cache_row_stride) != BP_OK) return BP_ERR_SHAPE;
+    bp::KvQuantParams p{};
+    p.kv = kv; p.cache = static_cast<uint8_t *>(kv_cache); p.cu = cu_seqlens;
+    p.kv_bs = kv_batch_stride; p.kv_rs = kv_row_stride; p.kv_ts = kv_two_stride; p.kv_hs = kv_head_stride;
+    p.c_bs = cache_batch_stride; p.c_rs = cache_row_stride;
+    p.total_rows = total_rows;
+    p.b = batch; p.h = nheads; p.d = head_dim;
+    p.limit = seqlen < max_positions ? seqlen : max_positions;
+    return launch_status(bp::launch_kv_cache_quantize(p, dtype, static_cast<hipStream_t>(stream)));
 }
 
 int bp_sense_rows_dot(const void *table, const int32_t *row_index, const int32_t *new_row, const int32_t *cache_seqlens,

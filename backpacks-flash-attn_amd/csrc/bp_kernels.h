@@ -369,6 +369,29 @@ struct DecodeMx8Params {
 };
 hipError_t launch_sense_decode_mx8(const DecodeMx8Params &p, int dtype, hipStream_t stream);
 
+// MXFP8 KV cache of the trunk (include/bp_hip.h, "MXFP8 KV cache"): one byte tensor per layer, a position's row = K elements,
+// V elements, K scales, V scales.  flash_decode_mx8.hip is bp_flash_decode on it (d: q / k_new / v_new / seqlens / workspace /
+// out / lse as bp_flash_decode fills them; k_cache and v are not read), kv_cache_mx8.hip the prefill's fill.
+struct KvDecodeMx8Params {
+    DecodeParams d;
+    uint8_t *cache;
+    int64_t c_bs, c_rs;               // bytes
+};
+// the trunk's combine alone (flash_decode.hip's code object): second launch of bp_flash_decode_mx8
+hipError_t launch_flash_decode_combine(const DecodeParams &p, int dtype, hipStream_t stream);
+hipError_t launch_flash_decode_mx8(const KvDecodeMx8Params &p, int dtype, hipStream_t stream);
+struct KvQuantParams {
+    const void *kv;                   // 16-bit (B, S, 2, H, D) view, or (total, 2, H, D) with cu
+    uint8_t *cache;
+    const int32_t *cu;                // (b + 1) device ints or NULL; not trusted
+    int64_t kv_bs, kv_rs, kv_ts, kv_hs;   // elements; kv_bs is not read with cu
+    int64_t c_bs, c_rs;               // bytes
+    int64_t total_rows;               // rows of a packed source
+    int b, h, d;
+    int limit;                        // positions a sample may fill: min(S or max_seqlen, max_positions)
+};
+hipError_t launch_kv_cache_quantize(const KvQuantParams &p, int dtype, hipStream_t stream);
+
 // bp_sense_rows_dot (sense_rows_dot.hip): out[b, l, j] = table[row(b, j), l, :] . vec[b, :] for j = 0 .. seqlens[b]
 struct RowsDotParams {
     const void *table, *vec;

@@ -11,4 +11,8 @@ hipError_t launch_flash_decode(const DecodeParams &p, int dtype, hipStream_t str
     return launch_decode<false>(p, dtype, p.b * p.groups, stream);
 }
 
+hipError_t launch_flash_decode_combine(const DecodeParams &p, int dtype, hipStream_t stream) {
+    return with_dtype(dtype, [&](auto et) { return launch_decode_combine<decltype(et), false>(p, p.b * p.groups, stream); });
+}
+
 }  // namespace bp

@@ -33,6 +33,7 @@ def create_mixer_cls(config, layer_idx=None, process_group=None, device=None, dt
                    softmax_scale=softmax_scale, causal=True, layer_idx=layer_idx,
                    use_flash_attn=getattr(config, 'use_flash_attn', False),
                    fused_bias_fc=getattr(config, 'fused_bias_fc', False),
+                   kv_cache_dtype=getattr(config, 'kv_cache_dtype', None),
                    device=device, dtype=dtype)
 
 

@@ -163,7 +163,7 @@ class MHA(nn.Module):
     def __init__(self, embed_dim, num_heads, cross_attn=False, bias=True, dropout=0.0,
                  softmax_scale=None, causal=False, layer_idx=None, dwconv=False, rotary_emb_dim=0,
                  rotary_emb_scale_base=0, fused_bias_fc=False, use_flash_attn=False,
-                 return_residual=False, checkpointing=False, device=None, dtype=None):
+                 return_residual=False, checkpointing=False, kv_cache_dtype=None, device=None, dtype=None):
         factory_kwargs = {'device': device, 'dtype': dtype}
         super().__init__()
         if cross_attn or dwconv or rotary_emb_dim > 0:
@@ -181,6 +181,14 @@ class MHA(nn.Module):
         self.num_heads = num_heads
         assert embed_dim % num_heads == 0, 'embed_dim must be divisible by num_heads'
         self.head_dim = embed_dim // num_heads
+        # None: the reference's 16-bit (.., 2, H, D) cache; 'mxfp8': one byte tensor per layer in the MXFP8 block format
+        if kv_cache_dtype not in (None, 'mxfp8'):
+            raise ValueError("kv_cache_dtype must be None or 'mxfp8', got %r" % (kv_cache_dtype,))
+        if kv_cache_dtype == 'mxfp8' and (self.head_dim % bp_hip.MX8_BLOCK != 0
+                                          or (use_flash_attn and self.head_dim > bp_hip.KV_MX8_MAX_HEAD_DIM)):
+            raise ValueError("kv_cache_dtype='mxfp8' needs head_dim %% %d == 0 (and <= %d on the HIP path), got %d"
+                             % (bp_hip.MX8_BLOCK, bp_hip.KV_MX8_MAX_HEAD_DIM, self.head_dim))
+        self.kv_cache_dtype = kv_cache_dtype
         # fused_bias_fc selects FusedDense, as upstream (mha.py:330-337): same parameters, bias gradient by bp_column_sum
         linear_cls = FusedDense if fused_bias_fc else _Linear
         if return_residual:
@@ -235,11 +243,22 @@ class MHA(nn.Module):
     #           flash call over the packed prompts, their K/V scattered to [b, 0:len_b) by one bp_scatter_packed_rows launch
     #           that reads cu_seqlens on the device; positions at or behind len_b are not written.  A packed call at a
     #           non-zero offset is refused: cached steps stay one token per sample on (B, 1) inputs.
+    # kv_cache_dtype='mxfp8' (opt-in): the layer's cache is ONE uint8 tensor (max_batch, max_seqlen, row_bytes) in the MXFP8
+    # block format (include/bp_hip.h, "MXFP8 KV cache"; 0.516 of the 16-bit cache's bytes).  The prefill's own attention
+    # still runs on the 16-bit K/V and bp_kv_cache_quantize fills the cache from them (padded or packed); a step is
+    # bp_flash_decode_mx8, which quantises the new K/V, appends it and attends to the rounded values.  The eager twin
+    # (_eager_decode_mx8) does the same bookkeeping in torch on any device.
 
     def _kv_cache(self, inference_params, like):
         assert self.layer_idx is not None, 'generation requires layer_idx in the constructor'
         cache = inference_params.key_value_memory_dict.get(self.layer_idx)
-        if cache is None:
+        if cache is None and self.kv_cache_dtype == 'mxfp8':
+            # zero bytes stand for zeros (E4M3 0 at scale byte 0): the eager twin may read the whole (masked) cache
+            cache = torch.zeros(inference_params.max_batch_size, inference_params.max_sequence_len,
+                                bp_hip.kv_cache_mx8_row_bytes(self.num_heads, self.head_dim), dtype=torch.uint8,
+                                device=like.device)
+            inference_params.key_value_memory_dict[self.layer_idx] = cache
+        elif cache is None:
             # zeros, not empty: the eager twin reads the whole (masked) cache, never garbage
             cache = torch.zeros(inference_params.max_batch_size, inference_params.max_sequence_len, 2, self.num_heads,
                                 self.head_dim, dtype=like.dtype, device=like.device)
@@ -262,14 +281,24 @@ class MHA(nn.Module):
         assert b1 <= cache.shape[0], 'batch_size_offset + batch exceeds max_batch_size'
         if inference_params.sequence_len_offset == 0:
             assert seqlen <= cache.shape[1], 'prompt longer than max_sequence_len'
-            cache[b0:b1, :seqlen] = qkv[:, :, 1:]
+            if self.kv_cache_dtype != 'mxfp8':
+                cache[b0:b1, :seqlen] = qkv[:, :, 1:]
+            elif self.use_flash_attn:
+                bp_hip.kv_cache_quantize(qkv[:, :, 1:], cache[b0:b1])
+            else:
+                cache[b0:b1, :seqlen] = bp_hip._eager_kv_cache_quantize(qkv[:, :, 1:])
             context = self.inner_attn(qkv)                                  # causal flash kernel / eager twin
         else:
             refuse_multi_token_step(seqlen, inference_params)
             lengths = cache_lengths(inference_params, batch, qkv.device)
             scale = self.inner_attn.softmax_scale or self.head_dim ** -0.5
             q, k_new, v_new = qkv[:, 0].unbind(dim=1)                       # (B, H, D) each
-            if self.use_flash_attn:
+            if self.kv_cache_dtype == 'mxfp8':
+                if self.use_flash_attn:
+                    context = bp_hip.flash_decode_mx8(q, k_new, v_new, cache[b0:b1], lengths, scale).unsqueeze(1)
+                else:
+                    context = _eager_decode_mx8(q, qkv[:, 0, 1:], cache, b0, lengths, scale).unsqueeze(1)
+            elif self.use_flash_attn:
                 context = bp_hip.flash_decode(q, k_new, v_new, cache[b0:b1], lengths, scale).unsqueeze(1)
             else:
                 context = _eager_decode(q, qkv[:, 0, 1:], cache, b0, lengths, scale).unsqueeze(1)
@@ -294,7 +323,10 @@ class MHA(nn.Module):
         b0 = inference_params.batch_size_offset
         assert b0 + batch <= cache.shape[0], 'batch_size_offset + batch exceeds max_batch_size'
         assert max_seqlen <= cache.shape[1], 'prompt longer than max_sequence_len'
-        bp_hip.scatter_packed_rows([(qkv[:, 1:], cache[b0:b0 + batch])], cu_seqlens, max_seqlen)
+        if self.kv_cache_dtype == 'mxfp8':
+            bp_hip.kv_cache_quantize(qkv[:, 1:], cache[b0:b0 + batch], cu_seqlens, max_seqlen)
+        else:
+            bp_hip.scatter_packed_rows([(qkv[:, 1:], cache[b0:b0 + batch])], cu_seqlens, max_seqlen)
         context = self.inner_attn(qkv, cu_seqlens=cu_seqlens, max_seqlen=max_seqlen)   # the ragged causal flash call
         out = self.out_proj(context.flatten(-2))
         return out if not self.return_residual else (out, x)
@@ -333,6 +365,23 @@ def _eager_decode(q, kv_new, cache, b0, lengths, scale):
     rows = torch.arange(b0, b0 + batch, device=q.device)
     cache[rows, lengths.long()] = kv_new
     k, v = cache[b0:b0 + batch].unbind(dim=2)                              # (B, M, H, D)
+    scores = torch.einsum('bhd,bshd->bhs', q, k * scale)
+    visible = torch.arange(cache.shape[1], device=q.device)[None, :] <= lengths[:, None].long()
+    scores = scores.masked_fill(~visible[:, None, :], float('-inf'))
+    attn = torch.softmax(scores, dim=-1, dtype=v.dtype)
+    return torch.einsum('bhs,bshd->bhd', attn, v)
+
+
+def _eager_decode_mx8(q, kv_new, cache, b0, lengths, scale):
+    """Eager twin of bp_flash_decode_mx8 on the byte cache (max_batch, max_seqlen, row_bytes): quantise kv_new (B, 2, H, D),
+    append its bytes (not the row's pad) at row lengths[b], attend to the DEQUANTISED rows [0, lengths[b]] in q's dtype --
+    fp32 operands make it the kernel's fp32 reference."""
+    batch, (h, d) = q.shape[0], q.shape[1:]
+    rows = torch.arange(b0, b0 + batch, device=q.device)
+    new = bp_hip._eager_kv_cache_quantize(kv_new)
+    used = bp_hip._kv_mx8_used_bytes(h, d)
+    cache[rows, lengths.long(), :used] = new[:, :used]
+    k, v = bp_hip._eager_kv_cache_dequantize(cache[b0:b0 + batch], h, d, q.dtype).unbind(dim=2)   # (B, M, H, D)
     scores = torch.einsum('bhd,bshd->bhs', q, k * scale)
     visible = torch.arange(cache.shape[1], device=q.device)[None, :] <= lengths[:, None].long()
     scores = scores.masked_fill(~visible[:, None, :], float('-inf'))

@@ -76,7 +76,9 @@ extern "C" {
                               and three more: bp_sense_table_quantize / bp_sense_table_dequantize / bp_sense_decode_mx8, the
                               MXFP8 twin of the sense table and the decode step that reads it;
                               and one more: bp_sense_anneal_step with bp_sense_anneal_step_ws_floats, the annealed sense
-                              weights of a cached step in one fused update) */
+                              weights of a cached step in one fused update;
+                              and two more: bp_flash_decode_mx8 / bp_kv_cache_quantize, the trunk's decode step and prefill
+                              fill on an MXFP8 KV cache) */
 
 /* element type of q/k/v/out/content tensors */
 #define BP_DTYPE_F16 0
@@ -788,6 +790,57 @@ int bp_sense_decode_mx8(const void *q, const void *k_new, void *k_cache, const v
                         int64_t q8_row_stride, int64_t q8_sense_stride, int64_t s8_row_stride, int64_t s8_sense_stride,
                         int64_t idx_batch_stride, int64_t o_batch_stride, int64_t kw_batch_stride, int64_t kw_sense_stride,
                         float softmax_scale, int dtype, bp_stream_t stream);
+
+/*
+ * MXFP8 KV cache -- the trunk's K/V cache of one layer as ONE byte tensor (max_batch, max_seqlen, row_bytes), byte strides
+ * cache_batch / cache_row, last stride 1.  The row of a position holds, in this order,
+ *   K elements  (nheads, head_dim)       E4M3 bytes
+ *   V elements  (nheads, head_dim)       E4M3 bytes
+ *   K scales    (nheads, head_dim / 32)  E8M0 bytes
+ *   V scales    (nheads, head_dim / 32)  E8M0 bytes
+ * and is rounded up to a multiple of 16 bytes: row_bytes = round_up(2 nheads head_dim (1 + 1/32), 16) (1584 at 12 x 64); the
+ * pad bytes are never written.  Elements, scales and the quantisation rule are exactly those of "MXFP8 sense table" above; a
+ * block is 32 consecutive columns of one head's K or V row.  Anything that treats a layer cache as (rows, positions, bytes)
+ * -- bp_beam_copy_rows, slices of the batch rows -- serves it without knowing the format.
+ * Both entry points: head_dim % 32 == 0 and <= 128 (BP_ERR_HEAD_DIM otherwise); the cache base 16-byte aligned, cache_batch
+ * and cache_row multiples of 16, cache_row >= row_bytes (BP_ERR_SHAPE otherwise); the 16-bit operands are of type `dtype`.
+ *
+ * bp_flash_decode_mx8 -- bp_flash_decode on that cache.  q, k_new, v_new, out, softmax_lse, cache_seqlens (clamped the same
+ * way), ws (sized by bp_flash_decode_ws_floats) and the error codes are bp_flash_decode's.  k_new / v_new are quantised by the
+ * rule above (a block's maximum is taken over its 32 columns) and their bytes and scale bytes are stored into row L_b; the
+ * query attends to the ROUNDED values, so a position contributes the same numbers in the step that appends it and in every
+ * later one:
+ *   out[b,h,:] = sum_{j<=L_b} softmax_j(scale q[b,h,:] . K8(b,j,h)) V8(b,j,h),   X8 = e4m3(element) 2^(scale byte - 127)
+ * Softmax and accumulation in fp32, split over the keys with a fixed-order combine: bit-identical across calls.
+ */
+int bp_flash_decode_mx8(const void *q, const void *k_new, const void *v_new, void *kv_cache, const int32_t *cache_seqlens,
+                        void *out, float *softmax_lse, float *ws, int64_t ws_floats,
+                        int batch, int nheads, int head_dim, int max_seqlen,
+                        int64_t q_batch_stride, int64_t q_head_stride,
+                        int64_t knew_batch_stride, int64_t knew_head_stride,
+                        int64_t vnew_batch_stride, int64_t vnew_head_stride,
+                        int64_t cache_batch_stride, int64_t cache_row_stride,
+                        int64_t o_batch_stride, int64_t o_head_stride, int64_t lse_batch_stride,
+                        float softmax_scale, int dtype, bp_stream_t stream);
+
+/*
+ * bp_kv_cache_quantize -- the prefill's fill of that cache: the K/V of the prompts, quantised into rows [b, 0:len_b).
+ *   kv           16-bit, element strides kv_batch / kv_row / kv_two / kv_head (multiples of 8, kv_head >= head_dim), last
+ *                stride 1, 16-byte aligned: cu_seqlens == NULL: the (batch, seqlen, 2, nheads, head_dim) view of the
+ *                prompts' K/V (qkv[:, :, 1:]), len_b = seqlen; else the packed (total_rows, 2, nheads, head_dim) view
+ *                (kv_batch is not read), sample b owning rows [cu_seqlens[b], cu_seqlens[b + 1]), len_b their number
+ *                clamped to [0, seqlen] (seqlen = max_seqlen of the packed batch)
+ *   cu_seqlens   (batch + 1) int32 DEVICE array or NULL.  Read on the device only and not trusted: a source row outside
+ *                [0, total_rows) is skipped
+ *   kv_cache     as above, already offset to the batch rows of this call; positions at or behind min(len_b, max_positions)
+ *                and the pad bytes of a row are not written
+ * One pass over the source.  Errors, before any launch: BP_ERR_DTYPE; BP_ERR_HEAD_DIM; BP_ERR_SHAPE (batch or nheads outside
+ * 1..65535, a negative seqlen / max_positions / total_rows, a NULL or misaligned pointer, a stride off its multiple).
+ */
+int bp_kv_cache_quantize(const void *kv, void *kv_cache, const int32_t *cu_seqlens, int batch, int seqlen, int64_t total_rows,
+                         int nheads, int head_dim, int max_positions,
+                         int64_t kv_batch_stride, int64_t kv_row_stride, int64_t kv_two_stride, int64_t kv_head_stride,
+                         int64_t cache_batch_stride, int64_t cache_row_stride, int dtype, bp_stream_t stream);
 
 /*
  * bp_sense_rows_dot -- dot products of the sense vectors of every cached position, and of the new one, with one vector

@@ -34,6 +34,10 @@ over the padded width (with --max-length = --prompt + 2 one token is generated b
 seed whose config asks for sense_table_dtype='mxfp8' (the cached table rounded to the MXFP8 format, cached steps through
 bp_sense_decode_mx8); only the `cached` sense_table mode differs from the default with it.
 
+--kv-cache-dtype mxfp8 adds the pick `kv_mxfp8` that alternates with the others: the device pick on a second model of the same
+seed whose config asks for kv_cache_dtype='mxfp8' (the trunk's K/V caches in the MXFP8 format: bp_kv_cache_quantize in the
+prefill, bp_flash_decode_mx8 in every cached step).
+
 --beams W[,W...] times beam search instead (its own line per sense_table mode): for every width W, beam_search(num_beams=W,
 cg=True) against the greedy device-pick leg generate(kv_cache=True, cg=True, device_pick=True) at the same number of rows
 (batch x W prompts), all legs alternating in one process, --repeats times each; then the two beam kernels alone at the
@@ -81,6 +85,7 @@ def main():
     ap.add_argument('--beams', default=None, help='W[,W...]: time beam search against greedy at the same number of rows')
     ap.add_argument('--prompt-lengths', default=None, help='LO:HI[:SEED]: add the picks ragged and ragged_equal (kv legs only)')
     ap.add_argument('--sense-table-dtype', default=None, choices=['mxfp8'], help='add the pick `mxfp8`: a second model with this config')
+    ap.add_argument('--kv-cache-dtype', default=None, choices=['mxfp8'], help='add the pick `kv_mxfp8`: a second model with this config')
     ap.add_argument('--fused-anneal-step', nargs='?', const='alternate', default=None, choices=['alternate', 'only'],
                     help='with --intervention weighted-anneal: add the pick `fused_anneal`, the same wrapper with '
                          'fused_anneal_step = True, alternating with the others; `only`: time that wrapper alone (for a trace)')
@@ -115,6 +120,13 @@ def main():
         torch.manual_seed(0)
         twin = BackpackLMHeadModel(BackpackConfig(sense_table_dtype=a.sense_table_dtype, **cfg_kw), device=dev,
                                    dtype=torch.bfloat16).eval()
+    kv_twin = None
+    if a.kv_cache_dtype:
+        if a.intervention != 'none' or a.beams:
+            raise SystemExit('--kv-cache-dtype goes with neither --intervention nor --beams')
+        torch.manual_seed(0)
+        kv_twin = BackpackLMHeadModel(BackpackConfig(kv_cache_dtype=a.kv_cache_dtype, **cfg_kw), device=dev,
+                                      dtype=torch.bfloat16).eval()
     legs = []
     if 'full' in a.legs.split(','):
         legs += [('eager_loop', False, False), ('graph_replay', True, False)]
@@ -122,8 +134,9 @@ def main():
         legs += [('kv_cache_eager', False, True), ('kv_cache_graph', True, True)]
     for mode in a.modes.split(','):   # content network per position (the reference's order) / cached whole-vocabulary table
         getattr(model, 'backpack_network', model).transformer.sense_table_mode = mode
-        if twin is not None:
-            twin.transformer.sense_table_mode = mode
+        for other in (twin, kv_twin):
+            if other is not None:
+                other.transformer.sense_table_mode = mode
         if a.beams:
             print(json.dumps(beam_legs(model, ids, a, mode)), flush=True)
             continue
@@ -131,7 +144,7 @@ def main():
                    new_tokens=a.max_length - 1 - a.prompt, sense_table=mode, **extra)
         outs = {}
         picks = a.pick.split(',')
-        plain = picks == ['torch'] and not a.sample and a.repeats == 1 and not a.variant and not a.prompt_lengths and twin is None and fused is None   # the line of earlier revisions, key for key
+        plain = picks == ['torch'] and not a.sample and a.repeats == 1 and not a.variant and not a.prompt_lengths and twin is None and kv_twin is None and fused is None   # the line of earlier revisions, key for key
         if not plain:
             res.update(sample=a.sample, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p)
         options = dict(torch={}, device=dict(device_pick=True, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p))
@@ -170,12 +183,18 @@ def main():
             options[a.sense_table_dtype] = dict(options['device'])
             res['sense_table_dtype_pick'] = a.sense_table_dtype
             picks = picks + [a.sense_table_dtype]
+        if kv_twin is not None:
+            options['kv_' + a.kv_cache_dtype] = dict(options['device'])
+            res['kv_cache_dtype_pick'] = 'kv_' + a.kv_cache_dtype
+            picks = picks + ['kv_' + a.kv_cache_dtype]
         if fused is not None:                          # the first pick's call on the wrapper with the fused weight update
             options['fused_anneal'] = dict(options[picks[0]])
             picks = picks + ['fused_anneal']
 
         def decode(*args, pick=None, **kw):
             m = twin if pick == a.sense_table_dtype and twin is not None else fused if pick == 'fused_anneal' else model
+            if kv_twin is not None and pick == 'kv_' + a.kv_cache_dtype:
+                m = kv_twin
             return (m.sample if a.sample else m.generate)(*args, **kw)
         for key, cg, kv in legs:
             runs = {pick: [] for pick in picks}
