@@ -98,6 +98,7 @@ SIGNATURES = {
     'bp_sense_table_quantize': (_i32, [_ptr] * 3 + [_i64] + [_i32] * 2 + [_i64] * 6 + [_i32, _ptr]),
     'bp_sense_table_dequantize': (_i32, [_ptr] * 3 + [_i64] + [_i32] * 2 + [_i64] * 6 + [_i32, _ptr]),
     'bp_sense_decode_mx8': (_i32, [_ptr] * 11 + [_i64] + [_i32] * 5 + [_i64] + [_i64] * 15 + [_f32, _i32, _ptr]),
+    'bp_sense_mix_gather_mx8': (_i32, [_ptr] * 6 + [_i32] * 6 + [_i64] * 12 + [_f32, _i32, _ptr]),
     'bp_flash_decode_mx8': (_i32, [_ptr] * 8 + [_i64] + [_i32] * 4 + [_i64] * 11 + [_f32, _i32, _ptr]),
     'bp_kv_cache_quantize': (_i32, [_ptr] * 3 + [_i32, _i32, _i64] + [_i32] * 3 + [_i64] * 6 + [_i32, _ptr]),
     'bp_sense_rows_dot': (_i32, [_ptr] * 6 + [_i32] * 4 + [_i64] + [_i64] * 6 + [_i32, _ptr]),
@@ -1740,6 +1741,81 @@ def sense_decode_mx8(q, k_new, k_cache, q8, scale8, row_index, new_row, cache_se
           b, k, dk, dout, max_s, q8.shape[0], q.stride(0), q.stride(1), k_new.stride(0), k_new.stride(1),
           k_cache.stride(0), k_cache.stride(1), k_cache.stride(2), q8.stride(0), q8.stride(1), scale8.stride(0),
           scale8.stride(1), row_index.stride(0), out.stride(0), kw[1], kw[2], float(scale), _dtype_code(q))
+    return out
+
+
+def _gather_mx8_limits(qk, q8, scale8, seqlen):
+    """(exceeded, reason) of every limit of bp_sense_mix_gather_mx8 (include/bp_hip.h).  Row offsets are 64-bit, so the 16-bit
+    gather's limits on the table's size and row count are not among them."""
+    dk = round_up(qk.shape[-1], 8)
+    pair = _mx8_pair_ok(q8, scale8)
+    dout = q8.shape[2] if q8.dim() == 3 else 0
+    blocks = (qk.shape[0] * ((dout + 255) // 256) + 7) // 8 * 8 * ((seqlen + 255) // 256)
+    return (
+        (qk.dtype not in (torch.float16, torch.bfloat16), f'dtype {qk.dtype} (fp16 or bf16 required)'),
+        (dk > 128, f'sense width {qk.shape[-1]} > 128'),
+        (not pair or dout % MX8_BLOCK != 0 or dout < MX8_BLOCK,
+         f'(q8, scale8) must be uint8 (rows, k, d_out) and (rows, k, d_out / {MX8_BLOCK}) with d_out % {MX8_BLOCK} == 0, unit last strides'),
+        (not (qk.is_cuda and q8.is_cuda and scale8.is_cuda), 'qk, q8 or scale8 not on the GPU'),
+        (q8.data_ptr() % 16 != 0 or (q8.dim() == 3 and (q8.stride(0) % 16 != 0 or q8.stride(1) % 16 != 0)),
+         'q8 layout (16-byte aligned rows required)'),
+        (blocks > 2 ** 31 - 1, f'sequence length {seqlen}: the launch would need {blocks} workgroups (> 2^31 - 1)'),
+        (not 1 <= q8.shape[0] <= 2 ** 31 - 1, f'{q8.shape[0]} table rows (1 .. 2^31 - 1 required)'),
+    )
+
+
+def sense_mix_gather_mx8_supported(qk, q8, scale8, seqlen):
+    """Shapes bp_sense_mix_gather_mx8 takes: those that exceed none of its limits (_gather_mx8_limits)."""
+    return not any(exceeded for exceeded, _ in _gather_mx8_limits(qk, q8, scale8, seqlen))
+
+
+def sense_mix_gather_mx8_limits(qk, q8, scale8, seqlen):
+    """Which limits of bp_sense_mix_gather_mx8 a call exceeds, as text."""
+    return '; '.join(reason for exceeded, reason in _gather_mx8_limits(qk, q8, scale8, seqlen) if exceeded)
+
+
+def _eager_sense_mix_gather_mx8(qk, q8, scale8, row_index, softmax_scale=None):
+    """Torch twin of sense_mix_gather_mx8 (any device): sense_mix's arithmetic -- causal softmax in fp32, probabilities and
+    sum in the operands' dtype -- on the rows of the dequantised table; indices clamped as the kernel clamps them."""
+    b, s, _, k, dk = qk.shape
+    scale = softmax_scale or dk ** -0.5
+    rows = row_index.long().clamp(max=q8.shape[0] - 1)
+    rows = torch.where(rows < 0, torch.full_like(rows, q8.shape[0] - 1), rows)
+    flat = rows.reshape(-1)                                                                # gather, then dequantise B*S rows
+    content = _eager_sense_table_dequantize(q8[flat], scale8[flat], qk.dtype).view(b, s, k, -1)   # (B, S, k, d_out)
+    q, key = qk[:, :, 0].transpose(1, 2), qk[:, :, 1].transpose(1, 2)                      # (B, k, S, d_k)
+    scores = torch.matmul(q, key.transpose(-1, -2)).float() * scale
+    mask = torch.ones(s, s, dtype=torch.bool, device=qk.device).tril()
+    alpha = torch.softmax(scores.masked_fill(~mask, float('-inf')), dim=-1).to(qk.dtype)
+    return torch.matmul(alpha, content.transpose(1, 2)).sum(dim=1)
+
+
+def sense_mix_gather_mx8(qk, q8, scale8, row_index, softmax_scale=None, out=None, lse=None):
+    """sense_mix_gather with the table given by its MXFP8 twin (q8, scale8) -- sense_table_quantize's pair:
+    content[b, s, l, :] = dequantised(q8, scale8)[row_index[b, s], l, :], widened inside the kernel to the bits
+    sense_table_dequantize gives, so no 16-bit table is needed.  Allocates like sense_mix_gather (out and the LSE workspace,
+    from torch's stream-ordered allocator: legal under graph capture) and reads nothing on the host
+    (C ABI bp_sense_mix_gather_mx8)."""
+    qk, b, s, k, dk, scale = _sense_qk(qk, softmax_scale)
+    _require_cuda(q8, scale8, row_index)
+    if not _mx8_pair_ok(q8, scale8) or q8.shape[1] != k:
+        raise RuntimeError(f'bp_hip.sense_mix_gather_mx8: q8 must be uint8 (rows, k, d_out), d_out % {MX8_BLOCK} == 0, and scale8 '
+                           f'uint8 (rows, k, d_out / {MX8_BLOCK}), unit last strides')
+    if row_index.shape != (b, s) or row_index.dtype != torch.int32 or row_index.stride(-1) != 1:
+        raise RuntimeError('bp_hip.sense_mix_gather_mx8: row_index must be (B, S) int32, unit stride along S')
+    dout = q8.shape[2]
+    if out is None:
+        out = torch.empty((b, s, dout), dtype=qk.dtype, device=qk.device)
+    elif out.shape != (b, s, dout) or out.dtype != qk.dtype or out.device != qk.device or out.stride(-1) != 1:
+        raise RuntimeError(f'bp_hip.sense_mix_gather_mx8: out must be ({b}, {s}, {dout}) of qk\'s dtype on its device, last dim '
+                           'contiguous')
+    ws, ready = _lse_ws(qk, lse, b, s, k)
+    _call('bp_sense_mix_gather_mx8', qk.device,
+          qk.data_ptr(), q8.data_ptr(), scale8.data_ptr(), row_index.data_ptr(), out.data_ptr(), ws.data_ptr(), ready,
+          b, s, k, dk, dout, q8.shape[0],
+          qk.stride(0), qk.stride(1), qk.stride(2), qk.stride(3),
+          q8.stride(0), q8.stride(1), scale8.stride(0), scale8.stride(1), row_index.stride(0),
+          out.stride(0), out.stride(1), float(scale), _dtype_code(qk))
     return out
 
 

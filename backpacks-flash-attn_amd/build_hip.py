@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, 'csrc')
 OUT_DIR = os.path.join(CSRC, 'build')
 LIB = os.path.join(HERE, 'bp_hip', 'libbackpack_hip.so')
 SOURCES = ['flash_fwd.hip', 'flash_fwd_dma.hip', 'flash_bwd.hip', 'sense_mix.hip', 'sense_mix_dma.hip', 'sense_mix_varlen.hip', 'sense_mix_bwd.hip', 'sense_mix_bwd_varlen.hip', 'sense_dp_slab_varlen.hip', 'sense_wide.hip', 'sense_wide_dma.hip', 'attn_probs.hip',
-           'add_layer_norm.hip', 'xentropy.hip', 'softmax_bwd.hip', 'bias_gelu.hip', 'flash_decode.hip', 'sense_decode.hip', 'sense_decode_weighted.hip', 'sense_decode_mx8.hip', 'sense_table_mx8.hip', 'flash_decode_mx8.hip', 'kv_cache_mx8.hip', 'sense_rows_dot.hip', 'sense_anneal_step.hip',
+           'add_layer_norm.hip', 'xentropy.hip', 'softmax_bwd.hip', 'bias_gelu.hip', 'flash_decode.hip', 'sense_decode.hip', 'sense_decode_weighted.hip', 'sense_decode_mx8.hip', 'sense_table_mx8.hip', 'sense_mix_gather_mx8.hip', 'flash_decode_mx8.hip', 'kv_cache_mx8.hip', 'sense_rows_dot.hip', 'sense_anneal_step.hip',
            'pick_token.hip', 'pick_token_ctl.hip', 'pick_token_lim.hip', 'pick_token_rows.hip', 'pick_token_phrases.hip', 'beam_pick.hip', 'beam_copy.hip', 'scatter_rows.hip', 'segment_sum_rows.hip', 'row_extremes.hip', 'sense_attribute.hip', 'sense_similarity.hip',
            'score_rows.hip', 'pick_report.hip', 'bp_gemm.hip', 'bp_api.hip']
 HEADERS = ['bp_common.h', 'lds_image.h', 'bp_dma.h', 'decode_core.h', 'bp_kernels.h', 'bp_philox.h', 'mix_ring.h', 'sense_mix_dma_kernel.h', 'sense_mix_bwd_kernel.h', 'pick_core.h', 'staged_tile.h', 'vocab_row.h', 'mx8_block.h', os.path.join('..', '..', 'include', 'bp_hip.h')]
@@ -33,7 +33,7 @@ NO_PACKED_FP32 = ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
 SOURCE_FLAGS = {'sense_mix_bwd_varlen.hip': NO_PACKED_FP32, 'sense_dp_slab_varlen.hip': NO_PACKED_FP32,
                 'sense_decode_mx8.hip': NO_PACKED_FP32, 'sense_table_mx8.hip': NO_PACKED_FP32,
                 'sense_anneal_step.hip': NO_PACKED_FP32, 'flash_decode_mx8.hip': NO_PACKED_FP32,
-                'kv_cache_mx8.hip': NO_PACKED_FP32}
+                'kv_cache_mx8.hip': NO_PACKED_FP32, 'sense_mix_gather_mx8.hip': NO_PACKED_FP32}
 
 
 def _hipcc():

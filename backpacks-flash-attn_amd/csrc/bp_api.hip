@@ -1180,6 +1180,43 @@ int bp_sense_decode_mx8(const void *q, const void *k_new, void *k_cache, const v
     return launch_status(bp::launch_sense_decode_mx8(pp, dtype, static_cast<hipStream_t>(stream)));
 }
 
+int bp_sense_mix_gather_mx8(const void *qk, const void *q8, const void *scale8, const int32_t *row_index, void *out,
+                            float *lse_ws, int lse_ready,
+                            int batch, int seqlen, int nsenses, int d_k, int d_out, int64_t table_rows,
+                            int64_t qk_batch_stride, int64_t qk_row_stride, int64_t qk_two_stride, int64_t qk_sense_stride,
+                            int64_t q8_row_stride, int64_t q8_sense_stride, int64_t s8_row_stride, int64_t s8_sense_stride,
+                            int64_t idx_batch_stride, int64_t o_batch_stride, int64_t o_row_stride,
+                            float softmax_scale, int dtype, bp_stream_t stream) {
+    if (dtype != BP_DTYPE_F16 && dtype != BP_DTYPE_BF16) return BP_ERR_DTYPE;
+    if (d_k < 8 || d_k > 128 || d_k % 8 != 0) return BP_ERR_HEAD_DIM;
+    if (d_out < 32 || d_out % 32 != 0) return BP_ERR_DOUT;
+    if (batch <= 0 || nsenses <= 0 || seqlen <= 0 || table_rows <= 0 || table_rows > 0x7fffffffLL) return BP_ERR_SHAPE;
+    if (qk == nullptr || q8 == nullptr || scale8 == nullptr || row_index == nullptr || out == nullptr || lse_ws == nullptr)
+        return BP_ERR_SHAPE;
+    if (!scale_ok(softmax_scale)) return BP_ERR_SCALE;
+    if (!qk_vec16(d_k, static_cast<const uint16_t *>(qk), qk_two_stride, qk_batch_stride, qk_row_stride, qk_sense_stride) ||
+        !aligned16({q8, out}) || !strides8({o_batch_stride, o_row_stride}))
+        return BP_ERR_SHAPE;
+    if (q8_row_stride % 16 != 0 || q8_sense_stride % 16 != 0 || q8_row_stride < d_out || q8_sense_stride < d_out
+        || s8_row_stride < d_out / 32 || s8_sense_stride < d_out / 32 || idx_batch_stride < 0)
+        return BP_ERR_SHAPE;
+    // the launch geometry: one workgroup per (sample, 256-column chunk, 256-query tile), whole XCD rounds of them
+    const int64_t groups = (int64_t)batch * ((d_out + 255) / 256), qtiles = (seqlen + 255) / 256;
+    if (groups > 0x7fffffffLL - 7 || (groups + 7) / 8 * 8 * qtiles > 0x7fffffffLL) return BP_ERR_SHAPE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!lse_ready) {
+        int rc = sense_lse(qk, lse_ws, batch, seqlen, nsenses, d_k, qk_batch_stride, qk_row_stride,
+                           qk_two_stride, qk_sense_stride, softmax_scale, dtype, st);
+        if (rc != BP_OK) return rc;
+    }
+    bp::MixMx8Params pp{};
+    pp.m = mix_params(qk, q8, out, lse_ws, batch, seqlen, nsenses, d_k, d_out, qk_batch_stride, qk_row_stride, qk_two_stride,
+                      qk_sense_stride, 0, q8_row_stride, q8_sense_stride, o_batch_stride, o_row_stride, softmax_scale, nullptr);
+    pp.m.row_index = row_index; pp.m.idx_bs = idx_batch_stride; pp.m.last_table_row = (uint32_t)(table_rows - 1);
+    pp.scale8 = static_cast<const uint8_t *>(scale8); pp.s_rs = s8_row_stride; pp.s_ss = s8_sense_stride;
+    return launch_status(bp::launch_sense_mix_gather_mx8(pp, dtype, st));
+}
+
 // ---- MXFP8 KV cache of the trunk (bp_flash_decode_mx8 / bp_kv_cache_quantize) ----
 
 // what both entry points ask of the byte cache: 16-byte aligned base, strides multiples of 16, a row stride that holds a row

@@ -368,6 +368,14 @@ struct DecodeMx8Params {
     int64_t s_rs, s_gs;               // bytes
 };
 hipError_t launch_sense_decode_mx8(const DecodeMx8Params &p, int dtype, hipStream_t stream);
+// bp_sense_mix_gather_mx8 (sense_mix_gather_mx8.hip): m as bp_sense_mix_gather fills it, except that m.c = q8 with m.c_rs /
+// m.c_ss its row / sense strides in BYTES (64-bit offsets: no table-size limit); m.kw and m.queues are not read
+struct MixMx8Params {
+    MixParams m;
+    const uint8_t *scale8;
+    int64_t s_rs, s_ss;               // bytes
+};
+hipError_t launch_sense_mix_gather_mx8(const MixMx8Params &p, int dtype, hipStream_t stream);
 
 // MXFP8 KV cache of the trunk (include/bp_hip.h, "MXFP8 KV cache"): one byte tensor per layer, a position's row = K elements,
 // V elements, K scales, V scales.  flash_decode_mx8.hip is bp_flash_decode on it (d: q / k_new / v_new / seqlens / workspace /

@@ -32,6 +32,24 @@ BP_DEV void mx8_unpack4(uint32_t w, float (&f)[4]) {
     f[0] = lo[0]; f[1] = lo[1]; f[2] = up[0]; f[3] = up[1];
 }
 
+// 16 E4M3 bytes of one block (half of it) with scale exponent ex = scale byte - 127 as 16 values of the 16-bit type E:
+// elements 0..7 in lo, 8..15 in hi.  The instruction sequence of sense_table_dequantize_kernel (two v_cvt_pk_f32_fp8, an
+// exact v_ldexp_f32 per element, one pack per pair), so the bits are bp_sense_table_dequantize's: exact wherever the type
+// holds the value (always in bf16), round to nearest even elsewhere.
+template <class E> BP_DEV void mx8_widen16(u32x4 w, int ex, u32x4 &lo, u32x4 &hi) {
+    uint32_t o[8];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        float f[4];
+        const uint32_t wi = w[i];                 // by value: see as_f32
+        mx8_unpack4(wi, f);
+        o[2 * i] = E::pack2(ldexpf(f[0], ex), ldexpf(f[1], ex));
+        o[2 * i + 1] = E::pack2(ldexpf(f[2], ex), ldexpf(f[3], ex));
+    }
+    lo = u32x4{o[0], o[1], o[2], o[3]};
+    hi = u32x4{o[4], o[5], o[6], o[7]};
+}
+
 // 8 consecutive 16-bit elements as fp32, and their largest magnitude
 template <class E> BP_DEV float mx8_unpack8_amax(u32x4 w, float *f) {
     float amax = 0.f;

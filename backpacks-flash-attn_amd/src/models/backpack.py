@@ -43,6 +43,8 @@ class BackpackConfig(GPT2Config):
         self.num_content_vectors = num_content_vectors
         # None | 'mxfp8': the cached whole-vocabulary sense table also kept in the MXFP8 block format (include/bp_hip.h) and
         # rounded to the values that format holds; KV-cached decode steps then read the 8-bit twin (bp_sense_decode_mx8)
+        # 'mxfp8_only': the 8-bit pair ALONE, built chunk by chunk (config.sense_table_build_rows, 4096); the table-form forward
+        # and prefill read it through bp_sense_mix_gather_mx8 -- a third of the memory, a 2.5-3x slower prefill mix
         self.sense_table_dtype = sense_table_dtype
         # True: packed batches (cu_seqlens) are trainable -- BackpackModel._forward_packed records a backward through the packed
         # sense kernels instead of refusing gradients
@@ -250,11 +252,15 @@ class _SenseTable:
     """The whole-vocabulary sense table of one content model and everything that decides whether it may be served.
     A plain object: it registers nothing with the model and is no part of its state dict."""
 
-    def __init__(self, content_model, mx8=False):
+    def __init__(self, content_model, mx8=False, mx8_only=False, build_rows=4096):
         self.content_model = content_model
+        # mx8_only: the 8-bit pair IS the table.  It is built chunk by chunk (`build_rows` vocabulary rows through the content
+        # network at a time, each quantised straight into its slice), `rows` stays None and `lookup` returns (q8, scale8)
+        self.mx8_only = bool(mx8_only)
+        self.build_rows = int(build_rows)
         # mx8: the rows hold exactly the values of their MXFP8 twin (q8, scale8), which shares their key, fingerprint and
         # pinned lifetime and is rebuilt in place with them; None without it
-        self.mx8 = bool(mx8)
+        self.mx8 = bool(mx8) or self.mx8_only
         self.q8 = self.scale8 = None
         self.rows = None            # (V, k, d) storage; kept when the table goes stale: a rebuild lands in the SAME storage
         self.key = None             # `_version_key` of the parameters the rows were built from; None = stale (or no rows)
@@ -283,16 +289,38 @@ class _SenseTable:
         if not self.pinned:
             self.rows = self.q8 = self.scale8 = None
 
+    def served(self):
+        """What the table serves as it stands: the 16-bit rows, or the pair (q8, scale8) of an 8-bit-only table."""
+        return (self.q8, self.scale8) if self.mx8_only else self.rows
+
+    def _build_pair(self, weight):
+        """The 8-bit-only build: no whole-vocabulary 16-bit tensor exists at any time, the peak extra memory is one chunk."""
+        vocab, k, d = weight.shape[0], self.content_model.num_content_vectors, self.content_model.n_embd
+        if self.q8 is None or self.q8.shape != (vocab, k, d) or self.q8.device != weight.device:
+            self.q8 = torch.empty((vocab, k, d), dtype=torch.uint8, device=weight.device)
+            self.scale8 = torch.empty((vocab, k, d // bp_hip.MX8_BLOCK), dtype=torch.uint8, device=weight.device)
+        for r0 in range(0, vocab, self.build_rows):
+            r1 = min(r0 + self.build_rows, vocab)
+            ids = torch.arange(r0, r1, device=weight.device).unsqueeze(0)
+            chunk = self.content_model(ids)[0].transpose(0, 1)         # (rows, k, d): the block as it lies
+            if weight.is_cuda:
+                bp_hip.sense_table_quantize_into(chunk, self.q8[r0:r1], self.scale8[r0:r1])
+            else:
+                q8, scale8 = bp_hip._eager_sense_table_quantize(chunk)
+                self.q8[r0:r1], self.scale8[r0:r1] = q8, scale8
+            del chunk
+
     def lookup(self, verify=False):
-        """The rows, rebuilt in place first when the parameters moved on, or None: see BackpackModel.sense_table."""
+        """The rows (the pair of an 8-bit-only table), rebuilt in place first when the parameters moved on, or None: see
+        BackpackModel.sense_table."""
         key = self.version_key()
         if key is None:
             return None
         if self.key == key:
             if not verify:
-                return self.rows
+                return self.served()
             if self.fingerprint is not None and self.fingerprint == self.version_key(fingerprint=True):
-                return self.rows
+                return self.served()
             # (a table built without a fingerprint cannot vouch for the values: rebuild once, then it can)
         weight = self.content_model.embeddings.word_embeddings.weight
         if weight.is_cuda and torch.cuda.is_current_stream_capturing():
@@ -302,6 +330,10 @@ class _SenseTable:
             was_training = self.content_model.training
             self.content_model.eval()                 # (also the embedding module it shares with the trunk)
             try:
+                if self.mx8_only:
+                    self._build_pair(weight)
+                    self.rows, self.key, self.fingerprint = None, key, fingerprint
+                    return self.served()
                 ids = torch.arange(weight.shape[0], device=weight.device).unsqueeze(0)
                 rows = self.content_model(ids)[0].transpose(0, 1)      # (V,k,d): the (1,V,k*d) block as it lies
                 if self.rows is not None and (self.rows.shape, self.rows.dtype, self.rows.device) == \
@@ -367,11 +399,16 @@ class BackpackModel(GPTPreTrainedModel):
         self.content_model = BackpackContentModule(config, self.num_content_vectors,
                                                    self.gpt2_model.embeddings, **factory_kwargs)
         self.sense_table_dtype = getattr(config, 'sense_table_dtype', None)
-        if self.sense_table_dtype not in (None, 'mxfp8'):
-            raise ValueError("sense_table_dtype must be None or 'mxfp8', got %r" % (self.sense_table_dtype,))
-        if self.sense_table_dtype == 'mxfp8' and config.n_embd % bp_hip.MX8_BLOCK != 0:
-            raise ValueError("sense_table_dtype='mxfp8' needs n_embd %% %d == 0, got %d" % (bp_hip.MX8_BLOCK, config.n_embd))
-        self._sense_table = _SenseTable(self.content_model, mx8=self.sense_table_dtype == 'mxfp8')
+        if self.sense_table_dtype not in (None, 'mxfp8', 'mxfp8_only'):
+            raise ValueError("sense_table_dtype must be None, 'mxfp8' or 'mxfp8_only', got %r" % (self.sense_table_dtype,))
+        if self.sense_table_dtype is not None and config.n_embd % bp_hip.MX8_BLOCK != 0:
+            raise ValueError("sense_table_dtype=%r needs n_embd %% %d == 0, got %d"
+                             % (self.sense_table_dtype, bp_hip.MX8_BLOCK, config.n_embd))
+        # 'mxfp8_only': the pair (q8, scale8) is the ONLY whole-vocabulary table; the table-form forward and prefill read it
+        # through bp_sense_mix_gather_mx8, cached steps through bp_sense_decode_mx8 ("Sense mix from the MXFP8 table")
+        self._mx8_only = self.sense_table_dtype == 'mxfp8_only'
+        self._sense_table = _SenseTable(self.content_model, mx8=self.sense_table_dtype == 'mxfp8', mx8_only=self._mx8_only,
+                                        build_rows=getattr(config, 'sense_table_build_rows', 4096))
         self.embeddings = self.gpt2_model.embeddings   # shared with the contextualisation model
         self.contextualization_attn = ContextSelfAttn(self.num_content_vectors, config.n_embd,
                                                       use_hip=self.use_hip, **factory_kwargs)
@@ -467,7 +504,7 @@ class BackpackModel(GPTPreTrainedModel):
         data-dependent shape."""
         if not self._token_table_allowed(input_ids) or torch.cuda.is_current_stream_capturing():
             return False
-        if self.sense_table_mode == 'cached' and self.sense_table() is not None:
+        if self.sense_table_mode == 'cached' and self._sense_table.lookup() is not None:
             return False
         return input_ids.numel() >= self.dedup_min_positions
 
@@ -507,18 +544,35 @@ class BackpackModel(GPTPreTrainedModel):
         (inference-mode parameters), when the table would have to be built while a stream is capturing, or when the
         build runs out of memory (one warning; the forward then takes the per-position order).  1.2 GB at
         Backpack-Small, 4.1 GB at Mini k = 64; ~5 ms to build."""
+        got = self._sense_table.lookup(verify)
+        if got is None or not self._mx8_only:
+            return got
+        # 'mxfp8_only' keeps no 16-bit rows: the analysis utilities get a TRANSIENT dequantisation, built per call and never
+        # kept (1.2 GB at Small); never while a stream is capturing
+        if got[0].is_cuda and torch.cuda.is_current_stream_capturing():
+            return None
+        dtype = self.content_model.embeddings.word_embeddings.weight.dtype
+        if not got[0].is_cuda:
+            return bp_hip._eager_sense_table_dequantize(got[0], got[1], dtype)
+        return bp_hip.sense_table_dequantize(got[0], got[1], dtype)
+
+    def _sense_pair(self, verify=False):
+        """(q8, scale8) of an 'mxfp8_only' model, rebuilt in place first when the weights moved on, or None."""
         return self._sense_table.lookup(verify)
 
     def sense_table_rows(self, stale_too=False):
-        """The rows the table vouches for as it stands (no lookup, no rebuild), or None; `stale_too`: its storage, stale or not."""
-        return self._sense_table.rows if stale_too or self._sense_table.key is not None else None
+        """The rows the table vouches for as it stands (no lookup, no rebuild), or None; `stale_too`: its storage, stale or
+        not.  'mxfp8_only': the q8 tensor, the storage a captured graph reads."""
+        table = self._sense_table
+        rows = table.q8 if self._mx8_only else table.rows
+        return rows if stale_too or table.key is not None else None
 
     def refresh_inference_caches(self):
         """Bring the cached sense table up to date with the weights (a no-op when it is); call in front of replaying a
         captured graph of this model after an in-place weight update (after a `.data` update: `invalidate_sense_table()`
         first)."""
         if self._table_mode() == 'cached':
-            self.sense_table()
+            self._sense_table.lookup()
 
     def train(self, mode=True):
         if mode:
@@ -539,6 +593,13 @@ class BackpackModel(GPTPreTrainedModel):
 
     def _mix_from_table(self, hidden, rows, index, qk=None):
         qk = self.contextualization_attn.project(hidden) if qk is None else qk
+        if isinstance(rows, tuple):
+            # 'mxfp8_only': rows = (q8, scale8).  A shape the 8-bit gather refuses is an error, never a 16-bit table in passing
+            if not bp_hip.sense_mix_gather_mx8_supported(qk, *rows, index.shape[1]):
+                raise NotImplementedError("sense_table_dtype='mxfp8_only': bp_sense_mix_gather_mx8 does not take this call ("
+                                          + bp_hip.sense_mix_gather_mx8_limits(qk, *rows, index.shape[1])
+                                          + "); sense_table_dtype='mxfp8' keeps 16-bit rows for it")
+            return bp_hip.sense_mix_gather_mx8(qk, *rows, index.to(torch.int32), self.contextualization_attn.scale())
         if bp_hip.sense_mix_gather_supported(qk, rows, index.shape[1]):
             # the mix kernel reads the table rows itself: no (B,S,k,d) content tensor at all
             return bp_hip.sense_mix_gather(qk, rows, index.to(torch.int32), self.contextualization_attn.scale())
@@ -628,7 +689,11 @@ class BackpackModel(GPTPreTrainedModel):
         """The prompt: fills the caches (and fixes their form), returns the mix of every prompt position (B, S, d)."""
         batch, seqlen = input_ids.shape
         cache_form_only = intervention is not None and intervention.cache_form_only
-        table = self.sense_table() if self._table_mode() == 'cached' and input_ids.is_cuda and not cache_form_only else None
+        table = self._sense_table.lookup() if self._table_mode() == 'cached' and input_ids.is_cuda and not cache_form_only \
+            else None
+        if isinstance(table, tuple) and intervention is not None:
+            raise NotImplementedError("sense_table_dtype='mxfp8_only': the table-form prefill of an intervened model gathers "
+                                      "16-bit rows; use sense_table_dtype='mxfp8'")
         c = self._decode_caches(ip, qk, table is None, hidden)
         c.keys[c.b0:c.b1, :seqlen] = qk[:, :, 1]
         if table is not None:
@@ -655,7 +720,7 @@ class BackpackModel(GPTPreTrainedModel):
 
     def _cached_step(self, input_ids, hidden, qk, ip, intervention):
         """One new token per sample: appends its key and row to the caches, returns its mix (B, 1, d)."""
-        table = None if 'backpack_content' in ip.key_value_memory_dict else self.sense_table()
+        table = None if 'backpack_content' in ip.key_value_memory_dict else self._sense_table.lookup()
         if table is None and 'backpack_content' not in ip.key_value_memory_dict:
             raise RuntimeError('Backpack decode: the cache was filled in table form but the sense table is gone '
                                '(weights changed, or .train() was called, since the prefill)')
@@ -677,6 +742,12 @@ class BackpackModel(GPTPreTrainedModel):
         if not self.fused_senses:
             return _eager_sense_decode(q, k_new, c.keys, table, c.rows, new_row, c.b0, lengths, scale,
                                        key_weight=key_weight).unsqueeze(1)
+        if isinstance(table, tuple):        # 'mxfp8_only' (interventions were refused by the prefill)
+            if not bp_hip.sense_decode_mx8_supported(q, c.keys, *table):
+                raise NotImplementedError("sense_table_dtype='mxfp8_only': bp_sense_decode_mx8 does not take this shape; "
+                                          "use sense_table_dtype='mxfp8'")
+            return bp_hip.sense_decode_mx8(q, k_new, c.keys[c.b0:c.b1], *table, c.rows[c.b0:c.b1], new_row, lengths,
+                                           scale).unsqueeze(1)
         twin = self._sense_table
         if twin.q8 is not None and table is twin.rows and \
                 bp_hip.sense_decode_mx8_supported(q, c.keys, twin.q8, twin.scale8, key_weight):
@@ -716,6 +787,8 @@ class BackpackModel(GPTPreTrainedModel):
         d_k = -(-(self.config.n_embd // self.num_content_vectors) // 8) * 8
         if not self.fused_senses:
             return 'the senses do not run on the fused HIP kernels (ContextSelfAttn.fused is False)'
+        if self._mx8_only:
+            return "sense_table_dtype='mxfp8_only' (there is no packed 8-bit gather; 'mxfp8' keeps 16-bit rows for the packed one)"
         if d_k > 128:
             return f'sense width {self.config.n_embd // self.num_content_vectors} > 128 (no packed wide sense kernels)'
         if self.config.n_embd % 8 != 0:
@@ -840,7 +913,7 @@ class BackpackModel(GPTPreTrainedModel):
                 return mixed
         if self._token_table_allowed(input_ids):
             if self.sense_table_mode == 'cached':
-                rows = self.sense_table(verify=self._verify_applies(input_ids))
+                rows = self._sense_table.lookup(self._verify_applies(input_ids))
                 if rows is not None:
                     return self._mix_from_table(contextl_hidden_states, rows, input_ids)
             if self._dedup_applies(input_ids):

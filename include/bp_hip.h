@@ -78,7 +78,8 @@ extern "C" {
                               and one more: bp_sense_anneal_step with bp_sense_anneal_step_ws_floats, the annealed sense
                               weights of a cached step in one fused update;
                               and two more: bp_flash_decode_mx8 / bp_kv_cache_quantize, the trunk's decode step and prefill
-                              fill on an MXFP8 KV cache) */
+                              fill on an MXFP8 KV cache;
+                              and one more: bp_sense_mix_gather_mx8, the gathering sense mix on the MXFP8 sense table) */
 
 /* element type of q/k/v/out/content tensors */
 #define BP_DTYPE_F16 0
@@ -790,6 +791,30 @@ int bp_sense_decode_mx8(const void *q, const void *k_new, void *k_cache, const v
                         int64_t q8_row_stride, int64_t q8_sense_stride, int64_t s8_row_stride, int64_t s8_sense_stride,
                         int64_t idx_batch_stride, int64_t o_batch_stride, int64_t kw_batch_stride, int64_t kw_sense_stride,
                         float softmax_scale, int dtype, bp_stream_t stream);
+
+/*
+ * bp_sense_mix_gather_mx8 -- bp_sense_mix_gather with the table read from its MXFP8 twin (added within ABI 11: additive), so
+ * that prefill and the eval forward need no 16-bit table next to the pair the decode step reads:
+ *   out[b,t,:] = sum_l sum_{s<=t} alpha[b,l,t,s] e4m3(q8[row_index[b,s], l, :]) 2^(scale8[row_index[b,s], l, :/32] - 127)
+ *   q8, scale8   as in "MXFP8 sense table", byte strides q8_row / q8_sense (multiples of 16, q8 16-byte aligned, each at
+ *                least d_out) and s8_row / s8_sense (each at least d_out / 32)
+ *   row_index    as bp_sense_mix_gather's: NOT validated, clamped as an unsigned value to table_rows - 1
+ *   qk, out, lse_ws / lse_ready, softmax_scale   as bp_sense_mix_gather's; there is no queue_ws (not a persistent launch), so
+ *                the call is legal on a capturing stream as it stands
+ * Every element is widened to `dtype` exactly as bp_sense_table_dequantize does it (the same bits) and enters the 16-bit
+ * MFMA; fp32 accumulation, no atomics, bit-identical across calls.  Masked keys contribute exactly 0.
+ * Restrictions: dtype fp16 / bf16 (BP_ERR_DTYPE); d_k % 8 == 0, 8 <= d_k <= 128 (BP_ERR_HEAD_DIM); d_out % 32 == 0 and >= 32
+ * (BP_ERR_DOUT); the 16-byte vector path for qk and out, q8 and its strides as above, 1 <= table_rows <= 2^31 - 1
+ * (BP_ERR_SHAPE).  Row offsets are 64-bit: the table's size and row count are not limited otherwise.  seqlen: any length
+ * whose launch fits a grid, ceil(batch * ceil(d_out / 256) / 8) * 8 * ceil(seqlen / 256) <= 2^31 - 1 (BP_ERR_SHAPE).
+ */
+int bp_sense_mix_gather_mx8(const void *qk, const void *q8, const void *scale8, const int32_t *row_index, void *out,
+                            float *lse_ws, int lse_ready,
+                            int batch, int seqlen, int nsenses, int d_k, int d_out, int64_t table_rows,
+                            int64_t qk_batch_stride, int64_t qk_row_stride, int64_t qk_two_stride, int64_t qk_sense_stride,
+                            int64_t q8_row_stride, int64_t q8_sense_stride, int64_t s8_row_stride, int64_t s8_sense_stride,
+                            int64_t idx_batch_stride, int64_t o_batch_stride, int64_t o_row_stride,
+                            float softmax_scale, int dtype, bp_stream_t stream);
 
 /*
  * MXFP8 KV cache -- the trunk's K/V cache of one layer as ONE byte tensor (max_batch, max_seqlen, row_bytes), byte strides

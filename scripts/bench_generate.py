@@ -84,7 +84,8 @@ def main():
     ap.add_argument('--repeats', type=int, default=1)
     ap.add_argument('--beams', default=None, help='W[,W...]: time beam search against greedy at the same number of rows')
     ap.add_argument('--prompt-lengths', default=None, help='LO:HI[:SEED]: add the picks ragged and ragged_equal (kv legs only)')
-    ap.add_argument('--sense-table-dtype', default=None, choices=['mxfp8'], help='add the pick `mxfp8`: a second model with this config')
+    ap.add_argument('--sense-table-dtype', default=None, choices=['mxfp8', 'mxfp8_only'],
+                    help='add the pick of that name: a second model with this config')
     ap.add_argument('--kv-cache-dtype', default=None, choices=['mxfp8'], help='add the pick `kv_mxfp8`: a second model with this config')
     ap.add_argument('--fused-anneal-step', nargs='?', const='alternate', default=None, choices=['alternate', 'only'],
                     help='with --intervention weighted-anneal: add the pick `fused_anneal`, the same wrapper with '
